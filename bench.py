@@ -12,8 +12,9 @@ Order of a run (single process, --gpus 1):
      flight, pinned staging: queries up, records down every step), then 20 batches one at a time;
   3. W untimed warm-up steps, then EXACTLY K timed steps rotating through the batches, bracketed by synchronisations; kernel
      durations by HIP events on the launch stream (roofline.kernel_ms);
-  4. outside the timed region: 64 queries of batch 0 checked bit-exact against the oracle (config.verified_sample; --verify:
-     every query of every batch), the CPU baseline (oracle's Block-WAND, T = 1 and T = usable cores), and -- C3 only, under
+  4. outside the timed region: --dump-outputs DIR writes the hits of the last timed step as .npy files (the same arguments give the
+     same corpus and queries, so two builds can be compared output for output); 64 queries of batch 0 checked bit-exact against
+     the oracle (config.verified_sample; --verify: every query of every batch), the CPU baseline (oracle's Block-WAND, T = 1 and T = usable cores), and -- C3 only, under
      --extra-budget-s -- C2 and C5 in the same process (`extra`, C5 with its own CPU baseline).
 The rotation is there so that a step's reads come from HBM and not from the previous step's leftovers; profiles/r5_warmup.txt
 shows the kernel's duration does not depend on it (1, 4 or 16 batches: the same), and why step 2 comes first.
@@ -198,6 +199,32 @@ def extra_workload(vb, name, budget_s, sha16, with_cpu=True):
     return out
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, hits, n_hits=None):
+    """--dump-outputs: the records the timed path handed its caller in its last step, one DIR/<field>.npy each (score and doc_id
+    float64, payload float32: every value exact), and the per-query hit counts where the path returns them.  Above 64 MB in all,
+    a fixed seeded sample of the queries is written, with their indices in query_index.npy."""
+    nq, k = hits.shape
+    row_bytes = k * (8 + 8 + 3 * 4) + (8 if n_hits is not None else 0)
+    rows = None
+    if nq * row_bytes > DUMP_MAX_BYTES:
+        budget = DUMP_MAX_BYTES - 5 * 4096  # (room for the five .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(nq, budget // (row_bytes + 8), replace=False))
+        hits = hits[rows]
+        n_hits = None if n_hits is None else n_hits[rows]
+    arrays = {"score": hits["score"].astype(np.float64), "doc_id": hits["doc_id"].astype(np.float64),
+              "payload": hits["payload"].astype(np.float32)}
+    if n_hits is not None:
+        arrays["n_hits"] = n_hits.astype(np.float64)
+    if rows is not None:
+        arrays["query_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def make_queries(seg, vocab, nq, nterms, seed, zipf_s):
     rng = np.random.default_rng(seed)
     if zipf_s > 0:
@@ -287,7 +314,11 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
     ap.add_argument("--extra-budget-s", type=float, default=240.0,
                     help="wall-clock budget for the C2 / C5 lines appended as `extra` (N = 1 only; 0 switches them off)")
     ap.add_argument("--tune", default="", help="development aid: library test switches, name=value[,name=value...] (vbm25_tuning_set)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the hits of the last step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -531,6 +562,11 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
         elapsed = float(t.item())
 
     # ---- outside the timed region ----
+    if args.dump_outputs and not use_dist:
+        dump_outputs(args.dump_outputs, *batches[(args.steps - 1) % nb].fetch())
+    elif args.dump_outputs and rank == 0:  # what rank 0 hands its caller: every rank's records, gathered in query order
+        words = last_gathered[0].cpu().numpy()[:n_total * k * 3]
+        dump_outputs(args.dump_outputs, np.frombuffer(words.tobytes(), dtype=vb.HIT_DTYPE).reshape(n_total, k))
     route = None
     if on_gpu:
         route = {0: "general (plan_kernel)", 1: "one launch", 2: "plan-free scan_range_kernel", 3: "scan_win_kernel", 4: "exhaustive"}.get(
@@ -757,6 +793,8 @@ def run_single_process(args, vb):
     elapsed = time.perf_counter() - t0
     for hits, n_hits in results:
         assert (n_hits == k).all(), "missing hits"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *results[(args.steps - 1) % nb])
     verified = None
     if args.verify:
         oix = oracle_index(seg)

@@ -447,6 +447,34 @@ def test_bench_distributed_code_path_single_rank():
     assert cfg["gather_ms"] > 0 and 0 <= cfg["gather_exposed_ms"] <= line["ms_per_step"]
 
 
+def test_bench_dump_outputs_are_the_last_steps_hits(tmp_path):
+    """bench.py --dump-outputs DIR: the hits of the last timed step (batch (steps - 1) % batches, made from the bench's own seeds)
+    as float64 / float32 .npy files, equal to the oracle's brute force on the same corpus and queries."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from bench import WORKLOADS, make_queries as bench_queries
+    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "C1", "--steps", "3",
+                                   "--warmup", "1", "--no-cpu-baseline", "--extra-budget-s", "0", "--dump-outputs", str(tmp_path)],
+                                  text=True, timeout=600)
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("score", "doc_id", "payload", "n_hits")}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(f"{n}.npy" for n in got)
+    assert [got[n].dtype for n in ("score", "doc_id", "payload", "n_hits")] == [np.float64, np.float64, np.float32, np.float64]
+    n_docs, vocab, mean_len, len_mode, zipf_s, nq, nterms, k = WORKLOADS["C1"]
+    dseg = vb.DeviceSegment.synth(n_docs, vocab, mean_len=mean_len, len_mode=len_mode, zipf_s=zipf_s, seed=20260925, device=0)
+    terms, off = bench_queries(dseg, vocab, nq, nterms, seed=1 + 2, zipf_s=zipf_s)  # step 2 of 3 runs batch 2 of 4
+    seg = dseg.download()
+    ref, n_ref, _ = orc.OracleIndex.from_arrays(seg.meta(), seg.arrays()).search_batch(terms, off, k, mode="brute", threads=4)
+    assert np.array_equal(got["n_hits"], n_ref) and n_ref.sum() > 0
+    for q, n in enumerate(n_ref):
+        assert np.array_equal(got["score"][q, :n].view(np.uint64), ref["score"][q, :n].view(np.uint64)), f"q{q}: score bits differ"
+        assert np.array_equal(got["doc_id"][q, :n], ref["doc_id"][q, :n]), f"q{q}: doc ids differ"
+        assert np.array_equal(got["payload"][q, :n], ref["payload"][q, :n]), f"q{q}: payloads differ"
+
+
 def test_c3_full_size_full_batch_parity():
     """BASELINE config C3 at full size (10M docs / 30k vocab, 5-term queries, top-10): ALL 1024 of the
     bench's own queries bit-exact against the oracle's brute force, a sample against the faithful

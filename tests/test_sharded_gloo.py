@@ -109,12 +109,28 @@ def test_bench_step_two_ranks_gloo():
         script = os.path.join(d, "bench_worker.py")
         open(script, "w").write(BENCH_WORKER)
         port = 29500 + (os.getpid() + 77) % 1000
+        dump = os.path.join(d, "dump")
         out = subprocess.run(
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
              "--master-addr", "127.0.0.1", "--master-port", str(port), script, ROOT,
-             "--gpus", "2", "--workload", "C1", "--steps", "3", "--warmup", "1", "--batches", "2", "--verify"],
+             "--gpus", "2", "--workload", "C1", "--steps", "3", "--warmup", "1", "--batches", "2", "--verify",
+             "--dump-outputs", dump],
             timeout=600, capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = {n: np.load(os.path.join(dump, f"{n}.npy")) for n in ("score", "doc_id", "payload")}
+        assert sorted(os.listdir(dump)) == ["doc_id.npy", "payload.npy", "score.npy"]
+    # --dump-outputs: rank 0's gathered records of the last step (step 2 of 3 runs batch 0 of 2), made from the bench's own seeds
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bench
+    import orc
+    import vectorchord_bm25_amd as vb
+    n_docs, vocab, mean_len, len_mode, zipf_s, nq, nterms, k = bench.WORKLOADS["C1"]
+    seg = vb.Segment.synth(n_docs, vocab, mean_len=mean_len, len_mode=len_mode, zipf_s=zipf_s, seed=20260925, threads=2)
+    terms, off = bench.make_queries(seg, vocab, 2 * nq, nterms, seed=1, zipf_s=zipf_s)
+    ref, _, _ = orc.OracleIndex.from_arrays(seg.meta(), seg.arrays()).search_batch(terms, off, k, mode="brute", threads=1)
+    assert [got[n].dtype for n in ("score", "doc_id", "payload")] == [np.float64, np.float64, np.float32]
+    assert np.array_equal(got["score"].view(np.uint64), ref["score"].view(np.uint64))
+    assert np.array_equal(got["doc_id"], ref["doc_id"]) and np.array_equal(got["payload"], ref["payload"])
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0
