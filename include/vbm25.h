@@ -285,6 +285,36 @@ int vbm25_batch_device_results(vbm25_batch *, void **hits, void **n_hits);
 int vbm25_batch_set_timing(vbm25_batch *, int enabled);
 int vbm25_batch_kernel_ms(vbm25_batch *, double *avg_ms, uint32_t *n_launches);
 
+/* Filtered search: bm25::search's `filter` (search.rs:217-236) for filters that are document sets known before the
+ * query runs (deleted documents, a visibility map, one tenant's rows, an evaluated WHERE clause).
+ * A filter holds F bitmaps over the index's document ids in HBM on the index's device: bitmap i is ceil(n_docs / 64)
+ * uint64_t words, bit d % 64 (counted from the least significant bit) of word d / 64 = 1 means document d may be
+ * returned.  Each query names one bitmap by its selector, or UINT32_MAX for none.  The records of a filtered query
+ * are byte-identical to the first min(k, n) entries of the unfiltered full ranking with the rejected documents
+ * removed (n = matching accepted documents), in the same order; there is no depth limit.  A query with selector
+ * UINT32_MAX gets the records vbm25_search_batch gives it.
+ *   vbm25_filter_create        words: F x ceil(n_docs / 64), or NULL for all bits zero.  Bits set at or beyond n_docs
+ *                              -> VBM25_ERR_INVALID (as in vbm25_filter_update).
+ *   vbm25_filter_update        replaces bitmap i from host memory; synchronous (waits for the device first).
+ *   vbm25_filter_device_words  device address of bitmap i, for callers that build the bits on the GPU (their work
+ *                              must be complete before the next run; bits at or beyond n_docs are never read).
+ *   vbm25_filter_destroy       the filter must not be destroyed while a batch refers to it (set its filter to NULL).
+ *   vbm25_search_batch_filtered  vbm25_search_batch with q_filter[q] (nq selectors) for query q.
+ *   vbm25_batch_set_filter     q_filter: max_queries selectors (query q of every later query set takes entry q);
+ *                              the batch keeps filter and selectors until they are set again; NULL filter: none.
+ *                              Changed bits (update, device_words) take effect at the next run.
+ * A filter of another index, or a selector >= F other than UINT32_MAX -> VBM25_ERR_INVALID.
+ * vbm25_stream_* and vbm25_multi_* take no filter. */
+typedef struct vbm25_filter vbm25_filter;
+int vbm25_filter_create(vbm25_index *, uint32_t n_bitmaps, const uint64_t *words, vbm25_filter **out);
+int vbm25_filter_update(vbm25_filter *, uint32_t i, const uint64_t *words);
+int vbm25_filter_device_words(vbm25_filter *, uint32_t i, void **dev);
+void vbm25_filter_destroy(vbm25_filter *);
+int vbm25_search_batch_filtered(vbm25_index *, const vbm25_filter *, const uint32_t *q_filter,
+                                const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, uint32_t k,
+                                vbm25_hit *hits, uint32_t *n_hits);
+int vbm25_batch_set_filter(vbm25_batch *, const vbm25_filter *, const uint32_t *q_filter);
+
 /* The same boundary PIPELINED (the caller hands over host buffers and gets host buffers back, as bm25::search
  * returns a Vec, search.rs:28-36): up to `depth` batches are in flight at once, each on its own stream with its
  * own pinned staging -- the upload of batch n + 1 and the records of batch n - 1 (written straight into pinned memory

@@ -113,6 +113,39 @@ class Index {
     vbm25_index *h_ = nullptr;
 };
 
+// F document bitmaps of one index in HBM (vbm25_filter): bit d % 64 of word d / 64 of bitmap i set = document d may be returned.
+class DocFilter {
+  public:
+    static size_t words_per_bitmap(uint32_t n_docs) { return (size_t(n_docs) + 63) / 64; }
+    // words: n_bitmaps x words_per_bitmap(n_docs), or empty for all bits zero
+    DocFilter(Index &index, uint32_t n_bitmaps, const std::vector<uint64_t> &words = {}) {
+        check(vbm25_filter_create(index.handle(), n_bitmaps, words.empty() ? nullptr : words.data(), &h_));
+    }
+    ~DocFilter() { vbm25_filter_destroy(h_); }
+    DocFilter(const DocFilter &) = delete;
+    DocFilter &operator=(const DocFilter &) = delete;
+    void update(uint32_t i, const std::vector<uint64_t> &words) { check(vbm25_filter_update(h_, i, words.data())); }
+    void *device_words(uint32_t i) {
+        void *p = nullptr;
+        check(vbm25_filter_device_words(h_, i, &p));
+        return p;
+    }
+    // the exact filtered top-k: query q returns documents of bitmap q_filter[q] only (UINT32_MAX: every document)
+    void search_batch(const Index &index, const std::vector<uint32_t> &q_filter, const std::vector<uint32_t> &term_ids,
+                      const std::vector<uint32_t> &q_off, size_t k, std::vector<Hit> &hits, std::vector<uint32_t> &n_hits) const {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        if (q_filter.size() != nq) throw Error(VBM25_ERR_INVALID, "one selector per query");
+        hits.resize(size_t(nq) * k);
+        n_hits.resize(nq);
+        check(vbm25_search_batch_filtered(index.handle(), h_, q_filter.data(), term_ids.data(), q_off.data(), nq, uint32_t(k),
+                                          hits.data(), n_hits.data()));
+    }
+    vbm25_filter *handle() const { return h_; }
+
+  private:
+    vbm25_filter *h_ = nullptr;
+};
+
 // Host copy of a flattened sealed segment (RAII over vbm25_segment).
 class Segment {
   public:

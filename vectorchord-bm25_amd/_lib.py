@@ -77,6 +77,12 @@ ABI = {
     "vbm25_batch_device_results": (i32, [vp, vp, vp]),
     "vbm25_batch_set_timing": (i32, [vp, i32]),
     "vbm25_batch_kernel_ms": (i32, [vp, vp, vp]),
+    "vbm25_filter_create": (i32, [vp, u32, vp, vp]),
+    "vbm25_filter_update": (i32, [vp, u32, vp]),
+    "vbm25_filter_device_words": (i32, [vp, u32, vp]),
+    "vbm25_filter_destroy": (None, [vp]),
+    "vbm25_search_batch_filtered": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
+    "vbm25_batch_set_filter": (i32, [vp, vp, vp]),
     "vbm25_evaluate_batch": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
     "vbm25_device_segment_build": (i32, [i32, C.c_double, C.c_double, u32, vp, vp, u32, vp, vp, vp, vp, vp]),
     "vbm25_device_segment_synth": (i32, [vp, i32, vp]),

@@ -286,7 +286,8 @@ class Batch:
     """Device-resident query batch (vbm25_batch)."""
 
     def __init__(self, index, max_queries, max_total_terms, k):
-        self.index, self.k, self.nq = index, k, 0
+        self.index, self.k, self.nq, self.max_queries = index, k, 0, max_queries
+        self.doc_filter = None
         self.h = C.c_void_p()
         check(lib().vbm25_batch_create(index.h, max_queries, max(1, max_total_terms), k,
                                        C.byref(self.h)))
@@ -317,6 +318,22 @@ class Batch:
 
     def set_timing(self, enabled=True):
         check(lib().vbm25_batch_set_timing(self.h, int(enabled)))
+
+    def set_filter(self, doc_filter, q_filter=None):
+        """vbm25_batch_set_filter: query q of this and every later query set takes bitmap q_filter[q] of `doc_filter`
+        (NO_FILTER, or entries beyond the array: none).  doc_filter=None: no filter."""
+        if doc_filter is None:
+            check(lib().vbm25_batch_set_filter(self.h, None, None))
+            self.doc_filter = None
+            return
+        sel = np.full(self.max_queries, NO_FILTER, dtype=np.uint32)
+        if q_filter is not None:
+            q_filter = np.asarray(q_filter, dtype=np.uint32).reshape(-1)
+            if len(q_filter) > self.max_queries:
+                raise ValueError(f"{len(q_filter)} selectors for a batch of {self.max_queries} queries")
+            sel[:len(q_filter)] = q_filter
+        check(lib().vbm25_batch_set_filter(self.h, doc_filter.h, _p(sel)))
+        self.doc_filter = doc_filter  # (the batch refers to it: kept alive with the batch)
 
     def kernel_ms(self):
         ms, n = C.c_double(), C.c_uint32()
@@ -427,6 +444,75 @@ class Stream:
     @property
     def in_flight(self):
         return int(lib().vbm25_stream_in_flight(self.h))
+
+
+NO_FILTER = 0xFFFFFFFF  # the selector of a query that takes no bitmap
+
+
+class DocFilter:
+    """vbm25_filter: F bitmaps over the index's documents in HBM -- bit d of bitmap i set: document d may be returned.
+    `keep` is a bool array [F, n_docs] (or [n_docs] for one bitmap), or a list of F arrays of document ids."""
+
+    def __init__(self, index, keep):
+        self.index = index
+        words = self.pack(keep, index.n_docs)
+        self.n_bitmaps, self.words = words.shape
+        self.h = C.c_void_p()
+        check(lib().vbm25_filter_create(index.h, self.n_bitmaps, _p(words), C.byref(self.h)))
+
+    @staticmethod
+    def pack(keep, n_docs):
+        """-> uint64 words [F, ceil(n_docs / 64)]: bit d % 64 of word d / 64 (least significant first) = keep[d]."""
+        if isinstance(keep, np.ndarray) and keep.dtype == np.bool_:
+            bits = keep.reshape(1, -1) if keep.ndim == 1 else keep
+            if bits.ndim != 2 or bits.shape[1] != n_docs:
+                raise ValueError(f"keep has shape {keep.shape}; expected [F, {n_docs}]")
+        else:
+            bits = np.zeros((len(keep), n_docs), dtype=bool)
+            for i, ids in enumerate(keep):
+                ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+                if ids.size and (ids.min() < 0 or ids.max() >= n_docs):
+                    raise ValueError(f"bitmap {i}: document ids outside 0 .. {n_docs - 1}")
+                bits[i, ids] = True
+        n_words = (n_docs + 63) // 64
+        padded = np.zeros((bits.shape[0], 64 * n_words), dtype=bool)
+        padded[:, :n_docs] = bits
+        return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little").view("<u8"))
+
+    def update(self, i, keep_i):
+        """vbm25_filter_update: replace bitmap i (bool array [n_docs] or document ids); takes effect at the next run."""
+        words = self.pack(keep_i if isinstance(keep_i, np.ndarray) and keep_i.dtype == np.bool_ else [keep_i], self.index.n_docs)
+        check(lib().vbm25_filter_update(self.h, i, _p(words)))
+
+    def device_words(self, i):
+        """vbm25_filter_device_words: the device address of bitmap i (ceil(n_docs / 64) uint64 words)."""
+        dev = C.c_void_p()
+        check(lib().vbm25_filter_device_words(self.h, i, C.byref(dev)))
+        return dev.value
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().vbm25_filter_destroy(self.h)
+        except Exception:
+            pass
+
+
+def search_batch_masked(index, term_ids, q_off, k, doc_filter, q_filter):
+    """vbm25_search_batch_filtered: search_batch where query q returns only documents of bitmap q_filter[q] of `doc_filter`
+    (NO_FILTER: every document) -- the exact filtered top-k, no depth limit."""
+    term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+    nq = len(q_off) - 1
+    q_filter = np.ascontiguousarray(q_filter, dtype=np.uint32).reshape(-1)
+    if len(q_filter) != nq:
+        raise ValueError(f"{len(q_filter)} selectors for {nq} queries")
+    hits = np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(nq, dtype=np.uint32)
+    check(lib().vbm25_search_batch_filtered(index.h, doc_filter.h if doc_filter is not None else None, _p(q_filter), _p(term_ids),
+                                            q_off.ctypes.data_as(C.c_void_p), nq, k, hits.ctypes.data_as(C.c_void_p),
+                                            n_hits.ctypes.data_as(C.c_void_p)))
+    return hits, n_hits
 
 
 def search_batch_filtered(index, term_ids, q_off, k, keep, overfetch=2, return_truncated=False):

@@ -102,6 +102,12 @@ struct DevBatch {
                                // term's low-16-bit ids in the batch's scratch plane, which decode_id16_kernel fills from the blob ahead of
                                // scan_win_kernel (ix.post_id16 then points at the scratch plane); NULL: the index's own plane, at term_first_block
     uint32_t *dbg;             // -DVBM25_CHECK builds: [0] first violated check (0: none), [1] value, [2] item, [3] thread
+    // filtered search (vbm25_batch_set_filter): filt_sel[q] = the bitmap query q takes (NONE32: none), bitmap s = filt_stride words
+    // at filt_words + s filt_stride, bit d % 64 of word d / 64 = document d may be returned.  Both NULL when the batch has no
+    // filter.  Read through query_filter (cold_args) where a candidate is admitted: nothing of it is live in the scan loops
+    const unsigned long long *filt_words;
+    const uint32_t *filt_sel;
+    unsigned long long filt_stride;
 };
 
 // The arguments of the scan kernels (DevIndex ix, DevBatch bt) as they lie in the kernarg segment.  The pointers that only an
@@ -117,6 +123,18 @@ __device__ __forceinline__ KernArgsP cold_args() {
     asm volatile("" : "+s"(p));  // opaque: the loads stay where they are written
     return p;
 }
+
+// The bitmap of query q (filtered search), NULL when it has none.  A filtered query starts from threshold 0: term_kth_ub (theta0)
+// bounds the k-th score over ALL documents and can exceed the k-th score of the accepted ones.  Every other threshold comes from
+// documents that were admitted, and a document is admitted only through filter_keeps.
+__device__ __forceinline__ const unsigned long long *query_filter(uint32_t q) {
+    const KernArgsP ca = cold_args();
+    const uint32_t *sel = ca->bt.filt_sel;
+    if (!sel) return nullptr;
+    const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)sel[q]);
+    return s == 0xffffffffu ? nullptr : ca->bt.filt_words + (size_t)s * ca->bt.filt_stride;
+}
+__device__ __forceinline__ bool filter_keeps(const unsigned long long *w, uint32_t d) { return (w[d >> 6] >> (d & 63u)) & 1ull; }
 
 // Bounds / consistency assertions of the scan kernels, compiled in by -DVBM25_CHECK only (tools/dense_stress.py): the
 // first violation is recorded in bt.dbg and read back with vbm25_batch_debug_check.

@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             }
             const bool act = lane < m;
             double s0 = 0.0, tub = 0.0, kth = 0.0;
-            const double *kub = ca->ix.term_kth_ub;
+            const double *kub = query_filter(q) ? nullptr : ca->ix.term_kth_ub;  // (a filtered query: no theta0)
             if (act && kub) {  // theta0: the term's 2^i-th largest block maximum, 2^i >= k (k documents of the term score that much)
                 uint32_t kidx = 0;
                 while ((1u << kidx) < k) ++kidx;
@@ -792,12 +792,15 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
                 const double inv = (1.0 / scale) * (1.0 - 1.0 / 131072.0) * S.hscale;  // accumulator -> bucket of the score's lower bound
                 const uint32_t bmv = lane < BPW ? S.bmax[wave * BPW + lane] : 0u;
                 uint32_t hot = (uint32_t)__ballot(bmv >= theta_i && bmv != 0u), left = 0;
+                // (filtered search: a rejected document is neither a candidate -- never re-scored -- nor counted in the histogram)
+                const unsigned long long *fw = hot ? query_filter(q) : nullptr;
                 while (hot) {
                     const uint32_t bk = (uint32_t)__ffs((int)hot) - 1u;
                     hot &= hot - 1u;
                     const uint32_t i = (wave * BPW + bk) * 64u + lane;
                     const uint32_t v = (S.acc[i >> 1] >> (16u * (i & 1u))) & 0xffffu;
-                    const bool cand = v >= theta_i && v != 0u;
+                    bool cand = v >= theta_i && v != 0u;
+                    if (fw && cand) cand = filter_keeps(fw, wlo + i);
                     const unsigned long long cm = __ballot(cand);
                     const uint32_t c = (uint32_t)__popcll(cm);
                     if (cn + c > (uint32_t)D_WCB) {  // the bucket stays whole for the next pass

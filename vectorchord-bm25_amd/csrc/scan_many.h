@@ -165,12 +165,14 @@ __global__ void __launch_bounds__(WG) scan_many_kernel(DevIndex ix, DevBatch bt)
                 const uint32_t n = s_top.count;
                 const double ws = n >= k ? s_top.score[k - 1] : 0.0;
                 const uint32_t wd = n >= k ? s_top.doc[k - 1] : 0u;
+                const unsigned long long *fw = query_filter(q);
                 for (int i = tid; i < SLOTS; i += WG) {
                     const uint32_t key = s_key[i];
                     if (key == EMPTY) continue;
                     const double sc = s_val[i];
                     if ((unsigned long long)__double_as_longlong(sc) < theta) continue;
                     if (n >= k && !better(sc, lo + key, ws, wd)) continue;
+                    if (fw && !filter_keeps(fw, lo + key)) continue;  // (filtered search: a rejected document is not admitted)
                     const uint32_t at = atomicAdd(&s_cand_cnt, 1u);
                     s_cand[at] = (uint16_t)i;
                 }

@@ -436,7 +436,7 @@ __global__ void __launch_bounds__(RWG, KMAX > 64 ? VBM25_RWPS_BIGK : VBM25_RWPS)
             double s0 = 0.0, tub = 0.0, kth = 0.0;
             uint32_t df = 0, b0 = 0, b1 = 0;
             p_cur = p_end = 0;
-            const double *kub = ca->ix.term_kth_ub;
+            const double *kub = query_filter(q) ? nullptr : ca->ix.term_kth_ub;  // (a filtered query: no theta0)
             if (act && kub) {  // (the smallest 2^i >= k: at least k documents of the term score that much)
                 uint32_t kidx = 0;
                 while ((1u << kidx) < k) ++kidx;
@@ -585,6 +585,10 @@ __global__ void __launch_bounds__(RWG, KMAX > 64 ? VBM25_RWPS_BIGK : VBM25_RWPS)
             has = has && (unsigned long long)__double_as_longlong(sc) >= th &&
                   (rtop.cnt < k || better(sc, d, rtop.kth_s, rtop.kth_d));
             if (!__ballot(has)) return;
+            if (const unsigned long long *fw = query_filter(q)) {  // (filtered search: a rejected document is neither admitted nor counted)
+                has = has && filter_keeps(fw, d);
+                if (!__ballot(has)) return;
+            }
             if (has) {
                 const double hb = sc * S.hscale;
                 const uint32_t b = hb >= (double)(CUR_HB - 1) ? (uint32_t)(CUR_HB - 1) : (uint32_t)hb;

@@ -337,7 +337,9 @@ __device__ __forceinline__ void wn_merge_query(const DevIndex &ix, const uint32_
 // MT: the most indexed terms of a query of the batch (2 .. 8).  A query of fewer terms gets NULL terms for the rest -- the window table
 // at the start of win_off, all zeros: runs without postings -- so that the per-term tests of the window loop are decided at compile
 // time and the terms' marks are one straight-line block (with the number of terms a run-time value: 0.215 instead of 0.199 ms on C3)
-template <int MT, int RK>
+// FILT: the batch has a document filter (vbm25_batch_set_filter): a filtered query starts without theta0 and a candidate is admitted only
+// if its bit is set.  An instantiation of its own: the unfiltered ones are compiled exactly as without the feature (same registers)
+template <int MT, int RK, bool FILT>
 __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) / 4) scan_win_kernel(DevIndex ix, DevBatch bt) {
     constexpr int WN_WAVES = wn_waves(MT, RK), WN_WG = WN_WAVES * 64;
     static_assert(sizeof(WinWave<MT>) + WN_BM_WORDS * 4 == wn_wave_lds(MT), "wn_waves() knows the size");
@@ -442,6 +444,8 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
         {
             const KernArgsP ca = cold_args();
             const double *kub = ca->ix.term_kth_ub;
+            if constexpr (FILT)
+                if (query_filter(q)) kub = nullptr;  // (a filtered query: no theta0)
             if (act) {
                 fb = ca->ix.term_first_block[term];
                 if (fbi == NONE32) fbi = fb;
@@ -511,6 +515,12 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
         auto offer = [&](bool has, double sc, uint32_t d) {
             has = has && (unsigned long long)__double_as_longlong(sc) >= th && (rtop.cnt < k || better(sc, d, rtop.kth_s, rtop.kth_d));
             if (!__ballot(has)) return;
+            if constexpr (FILT) {
+                if (const unsigned long long *fw = query_filter(q)) {  // (a rejected document is not admitted)
+                    has = has && filter_keeps(fw, d);
+                    if (!__ballot(has)) return;
+                }
+            }
             rtop.offer(has, sc, d, k, lane);
             if (rtop.cnt >= k) {
                 const unsigned long long kb = (unsigned long long)__double_as_longlong(rtop.kth_s);

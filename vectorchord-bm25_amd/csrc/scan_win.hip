@@ -16,12 +16,18 @@ namespace vbm25 {
 
 // mt: the most indexed terms of a query of the batch; k: the top-k lives in 1, 2 or 4 register rows of 64 entries (beyond five run
 // loads the kernel has registers for one row only: scan_win_max_k)
+template <int MT, bool FILT>
+static void launch_rk(const DevIndex &ix, const DevBatch &bt, uint32_t grid, hipStream_t st) {
+    // (grid: workgroups; a workgroup is wn_waves(MT) independent waves)
+    if (bt.k <= 64u) scan_win_kernel<MT, 1, FILT><<<grid, wn_waves(MT, 1) * 64, 0, st>>>(ix, bt);
+    else if (bt.k <= 128u) scan_win_kernel<MT, 2, FILT><<<grid, wn_waves(MT, 2) * 64, 0, st>>>(ix, bt);
+    else scan_win_kernel<MT, 4, FILT><<<grid, wn_waves(MT, 4) * 64, 0, st>>>(ix, bt);
+}
+// (a batch with a document filter: the FILT instantiations)
 template <int MT>
 static void launch_mt(const DevIndex &ix, const DevBatch &bt, uint32_t grid, hipStream_t st) {
-    // (grid: workgroups; a workgroup is wn_waves(MT) independent waves)
-    if (bt.k <= 64u) scan_win_kernel<MT, 1><<<grid, wn_waves(MT, 1) * 64, 0, st>>>(ix, bt);
-    else if (bt.k <= 128u) scan_win_kernel<MT, 2><<<grid, wn_waves(MT, 2) * 64, 0, st>>>(ix, bt);
-    else scan_win_kernel<MT, 4><<<grid, wn_waves(MT, 4) * 64, 0, st>>>(ix, bt);
+    if (bt.filt_sel) launch_rk<MT, true>(ix, bt, grid, st);
+    else launch_rk<MT, false>(ix, bt, grid, st);
 }
 // mt: the most indexed terms of a query of the batch: the kernel compiled for exactly that many run loads per window (2 .. 8; shorter
 // queries get null terms.  One term: the two-load kernel -- compiled for a single run load the compiler copies the buffer's

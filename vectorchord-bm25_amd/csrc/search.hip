@@ -107,6 +107,11 @@ __global__ void __launch_bounds__(256) bigk_accum_kernel(DevIndex ix, uint32_t t
         }
     }
 }
+// filtered search: the score of every rejected document is wiped before the sort -- a key of 0 is no hit (not emitted, not counted)
+__global__ void __launch_bounds__(256) bigk_mask_kernel(const unsigned long long *words, uint32_t n_docs, double *acc) {
+    for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < n_docs; d += gridDim.x * blockDim.x)
+        if (!((words[d >> 6] >> (d & 63u)) & 1ull)) acc[d] = 0.0;
+}
 __global__ void __launch_bounds__(256) bigk_iota_kernel(uint32_t *v, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) v[i] = i;
 }
@@ -210,6 +215,15 @@ struct vbm25_index {
     uint64_t device_bytes = 0;
 };
 
+// F bitmaps over the documents of one index, in HBM on its device (vbm25_filter_create)
+struct vbm25_filter {
+    const vbm25_index *index = nullptr;
+    int device = 0;
+    uint32_t n_bitmaps = 0;
+    uint32_t words = 0;  // per bitmap: ceil(n_docs / 64)
+    DeviceBuffer bits;   // n_bitmaps x words
+};
+
 // Tuning / test switches (not part of the ABI of include/vbm25.h; set through vbm25_tuning_set by tools and tests, read when a
 // batch object is created).  No entry point of the library reads the environment.
 struct Tuning {
@@ -257,6 +271,12 @@ struct vbm25_batch {
     DeviceBuffer bk_acc, bk_keys, bk_iota, bk_docs, bk_tmp;
     size_t bk_tmp_bytes = 0;
     std::vector<uint32_t> h_terms, h_off;  // host copy of the queries (bigk launches per term)
+    // filtered search (vbm25_batch_set_filter): the filter and per query the bitmap it takes (max_queries selectors, on the device and,
+    // for the k > 1024 path, on the host); filt_on: some selector names a bitmap (else the kernels see no filter at all)
+    const vbm25_filter *filter = nullptr;
+    DeviceBuffer filt_sel;
+    std::vector<uint32_t> h_filt_sel;
+    bool filt_on = false;
     std::vector<uint8_t> h_dense;          // per query: dense (scratch of set_queries, sized once)
     std::vector<unsigned long long> h_postings;
     std::vector<uint32_t> h_order, h_order_q;  // set_queries: the longest-first item order of the route without plan_kernel
@@ -1133,6 +1153,9 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
                 const uint32_t nb = (bt->index->term_df_host[t] + 127) / 128;
                 bigk_accum_kernel<<<std::min<uint32_t>((nb + 3) / 4, 4096u), 256, 0, st>>>(dix, t, bt->bk_acc.as<double>());
             }
+            if (bt->filt_on && bt->h_filt_sel[q] != UINT32_MAX)
+                bigk_mask_kernel<<<std::min<uint32_t>((n + 255) / 256, 4096u), 256, 0, st>>>(
+                    bt->filter->bits.as<unsigned long long>() + size_t(bt->h_filt_sel[q]) * bt->filter->words, n, bt->bk_acc.as<double>());
             size_t tmp = bt->bk_tmp_bytes;
             HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(bt->bk_tmp.p, tmp, bt->bk_acc.as<unsigned long long>(),
                                                                   bt->bk_keys.as<unsigned long long>(), bt->bk_iota.as<uint32_t>(),
@@ -1158,6 +1181,11 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
     db.res_cnt = bt->res_cnt.as<uint32_t>();
     db.hits = bt->hits.as<vbm25_hit>();
     db.n_hits = bt->n_hits.as<uint32_t>();
+    if (bt->filt_on) {
+        db.filt_words = bt->filter->bits.as<unsigned long long>();
+        db.filt_sel = bt->filt_sel.as<uint32_t>();
+        db.filt_stride = bt->filter->words;
+    }
     bt->results_pinned_now = false;
     if (bt->pinned_results && !bt->bigk && !bt->fused_g && bt->lat_stream && bt->pin_out) {
         const size_t nc = (4ull * bt->nq + 7) & ~size_t(7);  // (set_queries sized pin_out for 8 + nc + the records)
@@ -1818,6 +1846,129 @@ static int vbm25_batch_finish_download(vbm25_batch *bt, vbm25_hit *hits, uint32_
 // commands (three per batch) the same ring took 0.25 ms.
 // ---------------------------------------------------------------------------
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Filtered search: bm25::search's `filter` (search.rs:217-236) as per-query document bitmaps.  The kernels check a candidate's bit
+// where it is admitted to a top-k list (query_filter, device_types.h), a filtered query starts from threshold 0 (no theta0), and the
+// k > 1024 path wipes the rejected documents' scores before its sort.  The records are those of the unfiltered full ranking with the
+// rejected documents removed, cut to k.
+// ---------------------------------------------------------------------------
+static int filter_check_words(const vbm25_filter *f, const uint64_t *w) {
+    const uint32_t tail = f->index->n_docs & 63u;  // bits at or beyond n_docs must be zero
+    if (f->words && tail && (w[f->words - 1] >> tail) != 0)
+        return set_error(VBM25_ERR_INVALID, "bitmap has bits set at or beyond n_docs = %u", f->index->n_docs);
+    return VBM25_OK;
+}
+
+static int vbm25_filter_create_impl(vbm25_index *ix, uint32_t n_bitmaps, const uint64_t *words, vbm25_filter **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ix) return set_error(VBM25_ERR_INVALID, "index is NULL");
+    if (n_bitmaps == 0 || n_bitmaps == UINT32_MAX) return set_error(VBM25_ERR_INVALID, "n_bitmaps must be 1 .. 2^32 - 2");
+    if (int rc = use_device(ix->device)) return rc;
+    auto f = std::make_unique<vbm25_filter>();
+    f->index = ix;
+    f->device = ix->device;
+    f->n_bitmaps = n_bitmaps;
+    f->words = (ix->n_docs + 63u) / 64u;
+    const size_t bytes = 8ull * n_bitmaps * f->words;
+    if (words)
+        for (uint32_t i = 0; i < n_bitmaps; ++i)
+            if (int rc = filter_check_words(f.get(), words + size_t(i) * f->words)) return rc;
+    if (int rc = f->bits.alloc(bytes)) return rc;
+    if (words && bytes) HIP_TRY(hipMemcpy(f->bits.p, words, bytes, hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemset(f->bits.p, 0, bytes ? bytes : 16));
+    *out = f.release();
+    return VBM25_OK;
+}
+
+static int vbm25_filter_update_impl(vbm25_filter *f, uint32_t i, const uint64_t *words) {
+    if (!f || !words) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (i >= f->n_bitmaps) return set_error(VBM25_ERR_INVALID, "bitmap %u of a filter of %u", i, f->n_bitmaps);
+    if (int rc = filter_check_words(f, words)) return rc;
+    if (int rc = use_device(f->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old bits to their end)
+    if (f->words) HIP_TRY(hipMemcpy(f->bits.as<uint64_t>() + size_t(i) * f->words, words, 8ull * f->words, hipMemcpyHostToDevice));
+    return VBM25_OK;
+}
+
+// selectors: n_sel of them (query q takes q_filter[q]); the batch's other queries take none
+static int batch_set_filter_impl(vbm25_batch *bt, const vbm25_filter *f, const uint32_t *q_filter, uint32_t n_sel) {
+    if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
+    if (f && f->index != bt->index) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
+    if (f && !q_filter && n_sel) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
+    if (f)
+        for (uint32_t q = 0; q < n_sel; ++q)
+            if (q_filter[q] != UINT32_MAX && q_filter[q] >= f->n_bitmaps)
+                return set_error(VBM25_ERR_INVALID, "query %u: selector %u, the filter has %u bitmaps", q, q_filter[q], f->n_bitmaps);
+    if (int rc = use_device(bt->device)) return rc;
+    bool on = false;
+    for (uint32_t q = 0; f && q < n_sel && !on; ++q) on = q_filter[q] != UINT32_MAX;
+    // a run in flight reads the selectors to its end
+    if (bt->lat_stream) HIP_TRY(hipStreamSynchronize(bt->lat_stream));
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    bt->filter = on ? f : nullptr;
+    bt->filt_on = on;
+    if (!on) return VBM25_OK;
+    bt->h_filt_sel.assign(bt->max_queries, UINT32_MAX);
+    std::copy(q_filter, q_filter + n_sel, bt->h_filt_sel.begin());
+    if (!bt->filt_sel.p)
+        if (int rc = bt->filt_sel.alloc(4ull * bt->max_queries)) return rc;
+    HIP_TRY(hipMemcpy(bt->filt_sel.p, bt->h_filt_sel.data(), 4ull * bt->max_queries, hipMemcpyHostToDevice));
+    return VBM25_OK;
+}
+
+static int vbm25_search_batch_filtered_impl(vbm25_index *ix, const vbm25_filter *f, const uint32_t *q_filter, const uint32_t *term_ids,
+                                            const uint32_t *q_off, uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    if (!ix || !f || (!q_filter && nq) || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (f->index != ix) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
+    for (uint32_t q = 0; q < nq; ++q)
+        if (q_filter[q] != UINT32_MAX && q_filter[q] >= f->n_bitmaps)
+            return set_error(VBM25_ERR_INVALID, "query %u: selector %u, the filter has %u bitmaps", q, q_filter[q], f->n_bitmaps);
+    if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
+    // vbm25_search_batch on the index's batch object with the filter set for this call only
+    vbm25_batch *bt = ix->scratch;
+    const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
+    if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
+        if (bt) vbm25_batch_destroy(bt);
+        ix->scratch = nullptr;
+        if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;
+        bt->pinned_results = true;
+        ix->scratch = bt;
+    }
+    if (int rc = batch_set_filter_impl(bt, f, q_filter, nq)) return rc;
+    const int rc = vbm25_search_batch_impl(ix, term_ids, q_off, nq, k, hits, n_hits);
+    const int rc2 = batch_set_filter_impl(bt, nullptr, nullptr, 0);
+    return rc ? rc : rc2;
+}
+
+extern "C" {
+int vbm25_filter_create(vbm25_index *ix, uint32_t n_bitmaps, const uint64_t *words, vbm25_filter **out) {
+    return guarded([&] { return vbm25_filter_create_impl(ix, n_bitmaps, words, out); });
+}
+int vbm25_filter_update(vbm25_filter *f, uint32_t i, const uint64_t *words) {
+    return guarded([&] { return vbm25_filter_update_impl(f, i, words); });
+}
+int vbm25_filter_device_words(vbm25_filter *f, uint32_t i, void **dev) {
+    if (!f || !dev) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (i >= f->n_bitmaps) return set_error(VBM25_ERR_INVALID, "bitmap %u of a filter of %u", i, f->n_bitmaps);
+    *dev = f->bits.as<uint64_t>() + size_t(i) * f->words;
+    return VBM25_OK;
+}
+void vbm25_filter_destroy(vbm25_filter *f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    delete f;
+}
+int vbm25_batch_set_filter(vbm25_batch *bt, const vbm25_filter *f, const uint32_t *q_filter) {
+    return guarded([&] { return batch_set_filter_impl(bt, f, q_filter, bt && f ? bt->max_queries : 0u); });
+}
+int vbm25_search_batch_filtered(vbm25_index *ix, const vbm25_filter *f, const uint32_t *q_filter, const uint32_t *term_ids,
+                                const uint32_t *q_off, uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    return guarded([&] { return vbm25_search_batch_filtered_impl(ix, f, q_filter, term_ids, q_off, nq, k, hits, n_hits); });
+}
+}  // extern "C"
+
 struct vbm25_stream {
     std::vector<vbm25_batch *> slots;
     uint32_t head = 0, in_flight = 0;  // the oldest batch in flight, their number
