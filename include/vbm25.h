@@ -315,6 +315,36 @@ int vbm25_search_batch_filtered(vbm25_index *, const vbm25_filter *, const uint3
                                 vbm25_hit *hits, uint32_t *n_hits);
 int vbm25_batch_set_filter(vbm25_batch *, const vbm25_filter *, const uint32_t *q_filter);
 
+/* The growing segment on the device: bm25::search's first half (search.rs:83-135), the documents inserted since the last
+ * VACUUM, scored on the GPU and merged into the records of a batch.  A device growing segment is uploaded for one index from
+ * the CSR of vbm25_growing_desc (vbm25_growing_from_pages / vbm25_growing_get_desc, or assembled by the caller).  For query q
+ * the records are byte for byte
+ *     vbm25_merge_hits(the records vbm25_search_batch gives q,
+ *                      vbm25_growing_search(the index's desc, the keys of q's term ids, k, the growing arrays), k):
+ * the sealed segment's statistics score every growing document, elements whose key the sealed segment lacks never score,
+ * a document's score is summed in element (= key = term id) order from 0.0, deleted documents are skipped, a document
+ * enters only with a score > 0; growing hits rank by (score desc, growing index g asc), doc_id = 0xFFFFFFFF - g with the
+ * document's payload; on equal scores sealed hits come first.  Every k of 1 .. 65535 is served.
+ *   vbm25_growing_upload       builds the inverted form in HBM on the index's device (synchronous); the caller's arrays are
+ *                              not kept.  VBM25_ERR_INVALID: a document whose keys are not strictly ascending
+ *                              (vector.rs:56-61), a start array that is not monotone or reaches beyond n_elements,
+ *                              n_docs(sealed) + n_docs(growing) > 2^32 (the doc id ranges would collide).  Appending is a
+ *                              re-upload.
+ *   vbm25_device_growing_free  must not be called while a batch refers to the segment (set it to NULL first).
+ *   vbm25_search_batch_growing   vbm25_search_batch with the growing segment merged in.
+ *   vbm25_batch_set_growing    every later run of the batch merges the segment in (NULL detaches: the batch behaves exactly
+ *                              as without); vbm25_batch_device_results then points at the merged records, and kernel_ms
+ *                              covers the sealed scan through the final merge.
+ * A growing segment of another index -> VBM25_ERR_INVALID.  A batch with both a filter and a growing segment ->
+ * VBM25_ERR_UNSUPPORTED from whichever setter comes second.  vbm25_stream_* and vbm25_multi_* take no growing segment. */
+typedef struct vbm25_device_growing vbm25_device_growing;
+int vbm25_growing_upload(vbm25_index *, const vbm25_growing_desc *, vbm25_device_growing **out);
+void vbm25_device_growing_free(vbm25_device_growing *);
+uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *);
+int vbm25_search_batch_growing(vbm25_index *, const vbm25_device_growing *, const uint32_t *term_ids, const uint32_t *q_off,
+                               uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits);
+int vbm25_batch_set_growing(vbm25_batch *, const vbm25_device_growing *);
+
 /* The same boundary PIPELINED (the caller hands over host buffers and gets host buffers back, as bm25::search
  * returns a Vec, search.rs:28-36): up to `depth` batches are in flight at once, each on its own stream with its
  * own pinned staging -- the upload of batch n + 1 and the records of batch n - 1 (written straight into pinned memory

@@ -224,5 +224,40 @@ inline std::vector<Hit> merge_growing(const std::vector<Hit> &sealed, const std:
     return out;
 }
 
+// The growing segment of one index in HBM (vbm25_device_growing): the device form of search_growing + merge_growing for a whole
+// batch.  Re-upload (a new object) when the relation's unsealed documents change.
+class DeviceGrowing {
+  public:
+    DeviceGrowing(Index &index, const GrowingDocs &g) {
+        vbm25_growing_desc d{};
+        d.n_docs = uint32_t(g.size());
+        d.n_elements = g.tf.size();
+        d.start = g.start.data();
+        d.key = g.key.empty() ? nullptr : g.key[0].data();
+        d.tf = g.tf.data();
+        d.fieldnorm = g.fieldnorm.data();
+        d.payload = g.payload.data();
+        d.deleted = g.deleted.empty() ? nullptr : g.deleted.data();
+        check(vbm25_growing_upload(index.handle(), &d, &h_));
+    }
+    ~DeviceGrowing() { vbm25_device_growing_free(h_); }
+    DeviceGrowing(const DeviceGrowing &) = delete;
+    DeviceGrowing &operator=(const DeviceGrowing &) = delete;
+    uint64_t device_bytes() const { return vbm25_device_growing_bytes(h_); }
+    // per query: the sealed top-k and the growing documents' merged (sealed first on equal scores)
+    void search_batch(const Index &index, const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, size_t k,
+                      std::vector<Hit> &hits, std::vector<uint32_t> &n_hits) const {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        hits.resize(size_t(nq) * k);
+        n_hits.resize(nq);
+        check(vbm25_search_batch_growing(index.handle(), h_, term_ids.data(), q_off.data(), nq, uint32_t(k), hits.data(),
+                                         n_hits.data()));
+    }
+    vbm25_device_growing *handle() const { return h_; }
+
+  private:
+    vbm25_device_growing *h_ = nullptr;
+};
+
 }  // namespace vbm25
 #endif

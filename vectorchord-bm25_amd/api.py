@@ -288,6 +288,7 @@ class Batch:
     def __init__(self, index, max_queries, max_total_terms, k):
         self.index, self.k, self.nq, self.max_queries = index, k, 0, max_queries
         self.doc_filter = None
+        self.growing = None
         self.h = C.c_void_p()
         check(lib().vbm25_batch_create(index.h, max_queries, max(1, max_total_terms), k,
                                        C.byref(self.h)))
@@ -334,6 +335,18 @@ class Batch:
             sel[:len(q_filter)] = q_filter
         check(lib().vbm25_batch_set_filter(self.h, doc_filter.h, _p(sel)))
         self.doc_filter = doc_filter  # (the batch refers to it: kept alive with the batch)
+
+    def set_growing(self, growing):
+        """vbm25_batch_set_growing: every later run merges the growing segment (a GrowingSegment of this batch's index) into the
+        records; None detaches it."""
+        check(lib().vbm25_batch_set_growing(self.h, growing.h if growing is not None else None))
+        self.growing = growing  # (the batch refers to it: kept alive with the batch)
+
+    def device_results(self):
+        """vbm25_batch_device_results: device addresses of the records and counts (every later run leaves them complete there)."""
+        hits, n_hits = C.c_void_p(), C.c_void_p()
+        check(lib().vbm25_batch_device_results(self.h, C.byref(hits), C.byref(n_hits)))
+        return hits.value, n_hits.value
 
     def kernel_ms(self):
         ms, n = C.c_double(), C.c_uint32()
@@ -512,6 +525,58 @@ def search_batch_masked(index, term_ids, q_off, k, doc_filter, q_filter):
     check(lib().vbm25_search_batch_filtered(index.h, doc_filter.h if doc_filter is not None else None, _p(q_filter), _p(term_ids),
                                             q_off.ctypes.data_as(C.c_void_p), nq, k, hits.ctypes.data_as(C.c_void_p),
                                             n_hits.ctypes.data_as(C.c_void_p)))
+    return hits, n_hits
+
+
+class GrowingSegment:
+    """vbm25_device_growing: the growing (unsealed) documents of one index, uploaded to HBM (vbm25_growing_upload).  Built from the
+    CSR arrays growing_search takes (g_start, g_key, g_tf, g_fieldnorm, g_payload, g_deleted) or from growing_from_pages' dict."""
+
+    def __init__(self, index, g_start, g_key, g_tf, g_fieldnorm, g_payload, g_deleted=None):
+        self.index = index
+        g_start = np.ascontiguousarray(g_start, dtype=np.uint64)
+        g_key = np.ascontiguousarray(g_key, dtype=np.uint8).reshape(-1)
+        g_tf = np.ascontiguousarray(g_tf, dtype=np.uint32)
+        g_fieldnorm = np.ascontiguousarray(g_fieldnorm, dtype=np.uint8)
+        g_payload = np.ascontiguousarray(g_payload, dtype=np.uint16).reshape(-1)
+        g_deleted = None if g_deleted is None else np.ascontiguousarray(g_deleted, dtype=np.uint8)
+        self.n_docs = len(g_start) - 1
+        if len(g_key) != 16 * len(g_tf):
+            raise ValueError(f"{len(g_key)} key bytes for {len(g_tf)} elements")
+        d = GrowingDesc()
+        d.n_docs, d.n_elements = self.n_docs, len(g_tf)
+        d.start, d.key, d.tf = _p(g_start), _p(g_key), _p(g_tf)
+        d.fieldnorm, d.payload, d.deleted = _p(g_fieldnorm), _p(g_payload), _p(g_deleted)
+        self.h = C.c_void_p()
+        check(lib().vbm25_growing_upload(index.h, C.byref(d), C.byref(self.h)))
+
+    @classmethod
+    def from_dict(cls, index, grow):
+        """from growing_from_pages(pages)"""
+        return cls(index, grow["g_start"], grow["g_key"], grow["g_tf"], grow["g_fieldnorm"], grow["g_payload"], grow.get("g_deleted"))
+
+    @property
+    def device_bytes(self):
+        return int(lib().vbm25_device_growing_bytes(self.h))
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().vbm25_device_growing_free(self.h)
+        except Exception:
+            pass
+
+
+def search_batch_growing(index, growing, term_ids, q_off, k):
+    """vbm25_search_batch_growing: search_batch with the growing segment's documents merged in (sealed first on equal scores)."""
+    term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+    nq = len(q_off) - 1
+    hits = np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(nq, dtype=np.uint32)
+    check(lib().vbm25_search_batch_growing(index.h, growing.h if growing is not None else None, _p(term_ids),
+                                           q_off.ctypes.data_as(C.c_void_p), nq, k, hits.ctypes.data_as(C.c_void_p),
+                                           n_hits.ctypes.data_as(C.c_void_p)))
     return hits, n_hits
 
 

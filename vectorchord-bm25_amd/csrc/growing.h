@@ -1,0 +1,345 @@
+// growing.h -- the growing (unsealed) segment on the device: upload kernels and the query-time scan and merge.
+// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, after merge.h.
+//
+// search.rs:83-135 scores every unsealed document (a VectorTuple: elements of ascending key) with the SEALED segment's statistics
+// before the WAND loop.  The upload turns the documents into an inverted form: per sealed term id the postings (g, c) of the growing
+// documents that hold the term, g ascending, c = Cache::evaluate(fieldnorm[g], tf) precomputed (bm25.rs:355-358).  A query's score of
+// document g is then the sum of the c of its terms in ascending term-id order -- which is ascending key order, the element order the
+// host sums in -- starting from 0.0.  Deleted documents and keys the sealed segment lacks have no postings.
+//
+// k <= 1024: growing_scan_kernel, one workgroup per (query, run of tiles of GT documents).  A tile's accumulators live in LDS; the
+// query's terms are applied in ascending order with a barrier between terms (the first touch of a document stores, later touches
+// add: 0.0 + c == c), then every wave offers the touched documents of its quarter of the tile to a RegTopK (ties by g ascending).
+// growing_merge_kernel merges a query's lists and then the sealed records with them (sealed first on equal scores).
+// k > 1024: a dense accumulator over the growing documents per query, a stable descending radix sort, growing_final_kernel.
+
+constexpr uint32_t GT = 8192;        // documents per tile: 64 KB of f64 accumulators in LDS
+constexpr uint32_t GWG = 256;        // threads of growing_scan_kernel
+constexpr uint32_t G_MAX_WG = 512;   // workgroups of growing_scan_kernel a batch aims at (two per CU: LDS)
+
+struct DevGrowing {
+    const uint32_t *term_start;  // n_terms + 1: postings of term t are [term_start[t], term_start[t + 1])
+    const uint32_t *post_g;      // per posting: growing document index, ascending inside a term
+    const double *post_c;        // per posting: Cache::evaluate(fieldnorm[g], tf) of the term
+    const uint32_t *tab_idx;     // per term: first entry of its tile table, NONE32 = none (a short list: binary search)
+    const uint32_t *tab;         // a tabled term's n_tiles + 1 entries: entry j = its first posting with g >= j GT
+    const uint16_t *payload;     // n_grow x 3
+    uint32_t n_grow, n_tiles, n_terms;
+};
+
+struct GrowArgs {
+    const uint32_t *term_ids, *q_off;
+    uint32_t nq, k, gq;               // gq: workgroups (runs of tiles) per query
+    const vbm25_hit *sealed;          // the sealed records of the run (a copy: nq x k) and their counts
+    const uint32_t *sealed_cnt;
+    double *ls;                       // per list (query q, workgroup w, wave v: list (q gq + w) 4 + v): k entries
+    uint32_t *lg, *lc;
+    vbm25_hit *hits;                  // the batch's records: the merged result
+    uint32_t *n_hits;
+};
+
+// 16-byte token keys compare as memcmp: two big-endian 64-bit words
+__device__ __forceinline__ int key_cmp(const ulonglong2 a, const ulonglong2 b) {
+    const unsigned long long a0 = __builtin_bswap64(a.x), b0 = __builtin_bswap64(b.x);
+    if (a0 != b0) return a0 < b0 ? -1 : 1;
+    const unsigned long long a1 = __builtin_bswap64(a.y), b1 = __builtin_bswap64(b.y);
+    return a1 < b1 ? -1 : a1 > b1 ? 1 : 0;
+}
+
+// upload 1: per element of a live document the sort key (term id << 32 | g), ~0 for a key the sealed segment lacks or a deleted
+// document; the value is the element's tf.  `n_valid` counts the postings.
+__global__ void __launch_bounds__(256) grow_map_kernel(const ulonglong2 *term_key, uint32_t n_terms, uint32_t n_grow,
+                                                       const uint64_t *start, const ulonglong2 *g_key, const uint32_t *g_tf,
+                                                       const uint8_t *deleted, unsigned long long *keys, uint32_t *vals,
+                                                       uint32_t *n_valid) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_grow) return;
+    const uint64_t e0 = start[g] - start[0], e1 = start[g + 1] - start[0];
+    const bool live = !(deleted && deleted[g]);
+    uint32_t found = 0;
+    for (uint64_t e = e0; e < e1; ++e) {
+        unsigned long long key = ~0ull;
+        if (live) {
+            const ulonglong2 x = g_key[e];
+            uint32_t lo = 0, hi = n_terms;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (key_cmp(term_key[mid], x) < 0) lo = mid + 1; else hi = mid;
+            }
+            if (lo < n_terms && key_cmp(term_key[lo], x) == 0) {
+                key = (unsigned long long)lo << 32 | g;
+                ++found;
+            }
+        }
+        keys[e] = key;
+        vals[e] = g_tf[e];
+    }
+    if (found) atomicAdd(n_valid, found);
+}
+
+// upload 2: the sorted postings -> (g, c) and the term starts.  c exactly as the host's Cache::evaluate (-ffp-contract=off).
+__global__ void __launch_bounds__(256) grow_post_kernel(const unsigned long long *keys, const uint32_t *tf, uint32_t n_post,
+                                                        uint32_t n_terms, const double *s0, const double *s1, const uint8_t *fieldnorm,
+                                                        uint32_t *post_g, double *post_c, uint32_t *term_start) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_post) return;
+    const unsigned long long key = keys[i];
+    const uint32_t t = uint32_t(key >> 32), g = uint32_t(key);
+    const double f = (double)tf[i];
+    post_g[i] = g;
+    post_c[i] = (f * s0[t]) / (f + s1[fieldnorm[g]]);  // Cache::evaluate, bm25.rs:355-358
+    const uint32_t tp = i ? uint32_t(keys[i - 1] >> 32) : 0u;
+    for (uint32_t u = i ? tp + 1 : 0u; u <= t; ++u) term_start[u] = i;  // (the terms without postings before t start here too)
+    if (i + 1 == n_post)
+        for (uint32_t u = t + 1; u <= n_terms; ++u) term_start[u] = n_post;
+}
+
+// upload 3: the tile tables of the terms with at least n_tiles postings
+__global__ void __launch_bounds__(256) grow_tab_kernel(const unsigned long long *keys, uint32_t n_post, DevGrowing G, uint32_t *tab) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_post) return;
+    const uint32_t t = uint32_t(keys[i] >> 32);
+    const uint32_t ti = G.tab_idx[t];
+    if (ti == NONE32) return;
+    const uint32_t p0 = G.term_start[t], p1 = G.term_start[t + 1];
+    const uint32_t j = G.post_g[i] / GT;
+    const uint32_t jp = i == p0 ? 0u : G.post_g[i - 1] / GT + 1u;
+    for (uint32_t u = jp; u <= j; ++u) tab[ti + u] = i;
+    if (i + 1 == p1)
+        for (uint32_t u = j + 1; u <= G.n_tiles; ++u) tab[ti + u] = p1;
+}
+
+// postings of term t with g in tile j
+__device__ __forceinline__ uint2 grow_tile_range(const DevGrowing &G, uint32_t t, uint32_t j) {
+    const uint32_t ti = G.tab_idx[t];
+    if (ti != NONE32) return make_uint2(G.tab[ti + j], G.tab[ti + j + 1]);
+    const uint32_t a = G.term_start[t], b = G.term_start[t + 1];
+    auto lower = [&](uint32_t lo, uint32_t hi, uint64_t g) {
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (uint64_t(G.post_g[mid]) < g) lo = mid + 1; else hi = mid;
+        }
+        return lo;
+    };
+    const uint32_t lo = j == 0 ? a : lower(a, b, uint64_t(j) * GT);
+    const uint32_t hi = j + 1 >= G.n_tiles ? b : lower(lo, b, uint64_t(j + 1) * GT);
+    return make_uint2(lo, hi);
+}
+
+// the records of one query: the sealed list S (ns) and the growing list (gs, gg; ng, best first) merged as vbm25_merge_hits merges
+// them -- a growing hit goes before a sealed one only with a higher score.  Every entry is placed by its rank (binary search in the
+// other list): the threads of the caller write disjoint records, out may not alias S.
+__device__ __forceinline__ void grow_rank_merge(const vbm25_hit *S, uint32_t ns, const double *gs, const uint32_t *gg, uint32_t ng,
+                                                uint32_t k, const uint16_t *payload, vbm25_hit *out, uint32_t *n_out, uint32_t tid,
+                                                uint32_t nthr) {
+    for (uint32_t i = tid; i < ns; i += nthr) {
+        const double s = S[i].score;
+        uint32_t lo = 0, hi = ng;  // growing hits that score higher
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (gs[mid] > s) lo = mid + 1; else hi = mid;
+        }
+        const uint32_t pos = i + lo;
+        if (pos < k) {
+            const unsigned long long *src = reinterpret_cast<const unsigned long long *>(S + i);
+            unsigned long long *dst = reinterpret_cast<unsigned long long *>(out + pos);
+            dst[0] = src[0];
+            dst[1] = src[1];
+            dst[2] = src[2];
+        }
+    }
+    for (uint32_t j = tid; j < ng; j += nthr) {
+        const double s = gs[j];
+        uint32_t lo = 0, hi = ns;  // sealed hits that score at least as high
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (S[mid].score >= s) lo = mid + 1; else hi = mid;
+        }
+        const uint32_t pos = j + lo;
+        if (pos < k) {
+            const uint32_t g = gg[j];
+            const uint16_t *pl = payload + 3ull * g;
+            unsigned long long *dst = reinterpret_cast<unsigned long long *>(out + pos);
+            dst[0] = __double_as_longlong(s);
+            dst[1] = (unsigned long long)(0xffffffffu - g) | (unsigned long long)pl[0] << 32 | (unsigned long long)pl[1] << 48;
+            dst[2] = (unsigned long long)pl[2];
+        }
+    }
+    if (tid == 0) *n_out = min(k, ns + ng);
+}
+
+template <int KM>
+__global__ void __launch_bounds__(GWG) growing_scan_kernel(DevGrowing G, GrowArgs a) {
+    constexpr int RK = KM / 64;
+    __shared__ double acc[GT];
+    __shared__ uint32_t bits[GT / 32];
+    __shared__ uint32_t s_t[MAX_TERMS], s_lo[MAX_TERMS], s_cum[MAX_TERMS + 1];
+    __shared__ uint32_t s_nt;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t q = blockIdx.x / a.gq, w = blockIdx.x % a.gq;
+    const uint32_t k = a.k;
+    const uint32_t j0 = uint32_t(uint64_t(w) * G.n_tiles / a.gq), j1 = uint32_t(uint64_t(w + 1) * G.n_tiles / a.gq);
+    // a growing document must beat the sealed k-th score: on equal scores the sealed hit wins
+    const uint32_t ns = a.sealed_cnt[q];
+    const double thr = ns >= k ? a.sealed[size_t(q) * k + k - 1].score : 0.0;
+    if (tid == 0) s_nt = 0;
+    for (uint32_t i = tid; i < GT / 32; i += GWG) bits[i] = 0;
+    __syncthreads();
+    {   // the query's indexed terms: ids are strictly ascending, so those below n_terms are a prefix
+        const uint32_t q0 = a.q_off[q], q1 = a.q_off[q + 1];
+        for (uint32_t r = tid; r < q1 - q0 && r < (uint32_t)MAX_TERMS; r += GWG) {
+            const uint32_t t = a.term_ids[q0 + r];
+            if (t < G.n_terms) {
+                s_t[r] = t;
+                atomicAdd(&s_nt, 1u);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t nt = s_nt;
+    RegTopK<RK> top;
+    top.init();
+    for (uint32_t j = j0; j < j1 && nt; ++j) {
+        const uint32_t tile_lo = j * GT;
+        __syncthreads();  // (the last tile's reads of s_cum and acc are done)
+        for (uint32_t r = tid; r < nt; r += GWG) {
+            const uint2 rg = grow_tile_range(G, s_t[r], j);
+            s_lo[r] = rg.x;
+            s_cum[r + 1] = rg.y - rg.x;  // (counts: the prefix sum follows)
+        }
+        __syncthreads();
+        if (wave == 0) {
+            uint32_t carry = 0;
+            for (uint32_t base = 0; base < nt; base += 64) {
+                const uint32_t r = base + lane;
+                uint32_t v = r < nt ? s_cum[r + 1] : 0u;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t u = __shfl_up(v, o);
+                    if (lane >= (uint32_t)o) v += u;
+                }
+                if (r < nt) s_cum[r + 1] = carry + v;
+                carry += __shfl(v, 63);
+            }
+            if (lane == 0) s_cum[0] = 0;
+        }
+        __syncthreads();
+        const uint32_t P = s_cum[nt];
+        if (P == 0) continue;
+        auto term_of = [&](uint32_t i) {  // last r with s_cum[r] <= i
+            uint32_t lo = 0, hi = nt;
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (s_cum[mid] <= i) lo = mid; else hi = mid;
+            }
+            return lo;
+        };
+        // postings in chunks of GWG (loads of all the chunk's terms in flight at once), applied term by term
+        for (uint32_t base = 0; base < P; base += GWG) {
+            const uint32_t i = base + tid;
+            const bool mine = i < P;
+            uint32_t r = 0, l = 0;
+            double c = 0.0;
+            if (mine) {
+                r = term_of(i);
+                const uint32_t p = s_lo[r] + (i - s_cum[r]);
+                l = G.post_g[p] - tile_lo;
+                c = G.post_c[p];
+            }
+            const uint32_t r_first = term_of(base), r_last = term_of(min(base + GWG, P) - 1u);
+            for (uint32_t rr = r_first; rr <= r_last; ++rr) {
+                if (mine && r == rr) {
+                    const uint32_t bit = 1u << (l & 31u);
+                    const uint32_t old = atomicOr(&bits[l >> 5], bit);
+                    if (old & bit) acc[l] += c;
+                    else acc[l] = c;
+                }
+                __syncthreads();
+            }
+        }
+        // the touched documents of this wave's quarter of the tile (one bitmap word per lane), cleared for the next tile
+        {
+            const uint32_t wi = wave * 64u + lane;
+            uint32_t word = bits[wi];
+            bits[wi] = 0;
+            while (__ballot(word != 0)) {
+                bool has = word != 0;
+                uint32_t d = 0;
+                double s = 0.0;
+                if (has) {
+                    const uint32_t b = (uint32_t)__builtin_ctz(word);
+                    word &= word - 1u;
+                    const uint32_t ll = wi * 32u + b;
+                    s = acc[ll];
+                    d = tile_lo + ll;
+                    has = s > thr;
+                }
+                top.offer(has, s, d, k, lane);
+            }
+        }
+    }
+    const uint32_t L = (q * a.gq + w) * 4u + wave;
+#pragma unroll
+    for (int rr = 0; rr < RK; ++rr) {
+        const uint32_t e = rr * 64u + lane;
+        if (e < top.cnt) {
+            a.ls[size_t(L) * k + e] = top.score[rr];
+            a.lg[size_t(L) * k + e] = top.doc[rr];
+        }
+    }
+    if (lane == 0) a.lc[L] = top.cnt;
+}
+
+// one wave per query: the query's 4 gq lists -> its growing top-k, then merged with the sealed records into the batch's records
+template <int KM>
+__global__ void __launch_bounds__(64) growing_merge_kernel(DevGrowing G, GrowArgs a) {
+    constexpr int RK = KM / 64;
+    __shared__ double fs[KM];
+    __shared__ uint32_t fg[KM];
+    const uint32_t q = blockIdx.x, lane = threadIdx.x, k = a.k;
+    RegTopK<RK> top;
+    top.init();
+    for (uint32_t L = q * a.gq * 4u; L < (q + 1) * a.gq * 4u; ++L) {
+        const uint32_t cnt = a.lc[L];
+        for (uint32_t base = 0; base < cnt; base += 64) {
+            const uint32_t e = base + lane;
+            const bool has = e < cnt;
+            const double s = has ? a.ls[size_t(L) * k + e] : 0.0;
+            const uint32_t d = has ? a.lg[size_t(L) * k + e] : 0u;
+            top.offer(has, s, d, k, lane);
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RK; ++rr) {
+        const uint32_t e = rr * 64u + lane;
+        if (e < top.cnt) {
+            fs[e] = top.score[rr];
+            fg[e] = top.doc[rr];
+        }
+    }
+    __syncthreads();
+    grow_rank_merge(a.sealed + size_t(q) * k, a.sealed_cnt[q], fs, fg, top.cnt, k, G.payload, a.hits + size_t(q) * k, a.n_hits + q,
+                    lane, 64);
+}
+
+// k > 1024: acc[g] += c for the postings [p0, p0 + n) of one term (a document has one posting per term: the adds never collide)
+__global__ void __launch_bounds__(256) grow_accum_kernel(const uint32_t *post_g, const double *post_c, uint32_t p0, uint32_t n,
+                                                         double *acc) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t g = post_g[p0 + i];
+        acc[g] = acc[g] + post_c[p0 + i];
+    }
+}
+
+// k > 1024: the sorted (score bits, g) of one query (zero keys: no hit) merged with its sealed records
+__global__ void __launch_bounds__(256) growing_final_kernel(const vbm25_hit *sealed, const uint32_t *sealed_cnt,
+                                                            const unsigned long long *keys, const uint32_t *docs, uint32_t n_avail,
+                                                            uint32_t k, const uint16_t *payload, vbm25_hit *hits, uint32_t *n_hits) {
+    uint32_t lo = 0, hi = min(n_avail, k);  // the non-zero keys are a prefix
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] != 0) lo = mid + 1; else hi = mid;
+    }
+    grow_rank_merge(sealed, *sealed_cnt, reinterpret_cast<const double *>(keys), docs, lo, k, payload, hits, n_hits,
+                    blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}

@@ -69,6 +69,7 @@ int set_error(int code, const char *fmt, ...) {
 #include "scan_dense.h"
 #include "scan_many.h"
 #include "merge.h"
+#include "growing.h"
 
 // ---------------------------------------------------------------------------
 // Batched `<&>`: bm25::evaluate (evaluate.rs:22-74) for many documents against one query -- the seq-scan
@@ -207,6 +208,7 @@ struct vbm25_index {
     std::vector<uint8_t> term_key;  // host copy for vbm25_lookup_terms
     std::vector<uint32_t> term_df_host;  // host copy for query routing
     vbm25_batch *scratch = nullptr;      // batch object re-used by vbm25_search_batch
+    vbm25_batch *scratch_grow = nullptr; // ... and by vbm25_search_batch_growing
     DeviceBuffer term_wand_tf, term_wand_fn, term_df, term_first_block, term_s0, blk_min_doc, blk_max_doc, blk_meta, blk_ub, blob,
         post_fn, post_rel16, post_tfn, doc_payload, s1, term_idf, fn_len, term_kth_ub, post_id16, win_off, term_win;
     std::vector<uint32_t> term_win_host;  // host copy of term_win (query routing); empty: the index has no window planes
@@ -222,6 +224,29 @@ struct vbm25_filter {
     uint32_t n_bitmaps = 0;
     uint32_t words = 0;  // per bitmap: ceil(n_docs / 64)
     DeviceBuffer bits;   // n_bitmaps x words
+};
+
+// The growing segment of one index in HBM on its device (vbm25_growing_upload; growing.h has the layout)
+struct vbm25_device_growing {
+    const vbm25_index *index = nullptr;
+    int device = 0;
+    uint32_t n_grow = 0, n_tiles = 0, n_post = 0;
+    DeviceBuffer term_start, post_g, post_c, tab_idx, tab, payload;
+    std::vector<uint32_t> term_start_host;  // (k > 1024: one accumulation launch per term)
+    uint64_t device_bytes = 0;
+    DevGrowing dev() const {
+        DevGrowing g{};
+        g.term_start = term_start.as<uint32_t>();
+        g.post_g = post_g.as<uint32_t>();
+        g.post_c = post_c.as<double>();
+        g.tab_idx = tab_idx.as<uint32_t>();
+        g.tab = tab.as<uint32_t>();
+        g.payload = payload.as<uint16_t>();
+        g.n_grow = n_grow;
+        g.n_tiles = n_tiles;
+        g.n_terms = index->n_terms;
+        return g;
+    }
 };
 
 // Tuning / test switches (not part of the ABI of include/vbm25.h; set through vbm25_tuning_set by tools and tests, read when a
@@ -277,6 +302,11 @@ struct vbm25_batch {
     DeviceBuffer filt_sel;
     std::vector<uint32_t> h_filt_sel;
     bool filt_on = false;
+    // growing segment (vbm25_batch_set_growing): merged into the records by every run (growing.h).  gr_*: the sealed records' copy,
+    // the per-workgroup lists of growing_scan_kernel (k <= 1024) or the dense accumulator and its sort (k > 1024)
+    const vbm25_device_growing *growing = nullptr;
+    DeviceBuffer gr_sealed, gr_sealed_cnt, gr_ls, gr_lg, gr_lc, gr_acc, gr_keys, gr_iota, gr_docs, gr_tmp;
+    size_t gr_tmp_bytes = 0;
     std::vector<uint8_t> h_dense;          // per query: dense (scratch of set_queries, sized once)
     std::vector<unsigned long long> h_postings;
     std::vector<uint32_t> h_order, h_order_q;  // set_queries: the longest-first item order of the route without plan_kernel
@@ -706,6 +736,7 @@ void vbm25_index_destroy(vbm25_index *ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
     if (ix->scratch) vbm25_batch_destroy(ix->scratch);
+    if (ix->scratch_grow) vbm25_batch_destroy(ix->scratch_grow);
     delete ix;
 }
 
@@ -1187,7 +1218,7 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
         db.filt_stride = bt->filter->words;
     }
     bt->results_pinned_now = false;
-    if (bt->pinned_results && !bt->bigk && !bt->fused_g && bt->lat_stream && bt->pin_out) {
+    if (bt->pinned_results && !bt->bigk && !bt->fused_g && bt->lat_stream && bt->pin_out && !bt->growing) {
         const size_t nc = (4ull * bt->nq + 7) & ~size_t(7);  // (set_queries sized pin_out for 8 + nc + the records)
         db.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
         db.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + 8 + nc);
@@ -1338,7 +1369,7 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
         // the per-launch state zero.  A query with an item the kernel gave up comes back with the count NONE32: whoever hands the
         // records to the caller (vbm25_batch_fetch_impl) re-runs the batch with scan_many_kernel and merge_kernel behind the scan.
         // (only when every wave has at most one item: the kernel's merge sits behind its item loop)
-        const bool fuse = bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && uint64_t(bt->nq) * bt->win_g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
+        const bool fuse = bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && !bt->growing && uint64_t(bt->nq) * bt->win_g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
         db.win_fuse = fuse ? 1u : 0u;
         bt->win_fused_run = fuse;
         if (bt->id16_decode) {
@@ -1809,8 +1840,9 @@ int vbm25_batch_set_queries(vbm25_batch *bt, const uint32_t *term_ids, const uin
     return guarded([&] { return vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq); });
 }
 
+static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream);
 int vbm25_batch_run(vbm25_batch *bt, void *hip_stream) {
-    return guarded([&] { return vbm25_batch_run_impl(bt, hip_stream); });
+    return guarded([&] { return bt && bt->growing ? batch_run_growing_impl(bt, hip_stream) : vbm25_batch_run_impl(bt, hip_stream); });
 }
 
 int vbm25_batch_fetch(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits) {
@@ -1896,6 +1928,7 @@ static int vbm25_filter_update_impl(vbm25_filter *f, uint32_t i, const uint64_t 
 static int batch_set_filter_impl(vbm25_batch *bt, const vbm25_filter *f, const uint32_t *q_filter, uint32_t n_sel) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
     if (f && f->index != bt->index) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
+    if (f && bt->growing) return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a growing segment: filters do not apply to growing documents");
     if (f && !q_filter && n_sel) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
     if (f)
         for (uint32_t q = 0; q < n_sel; ++q)
@@ -1966,6 +1999,267 @@ int vbm25_batch_set_filter(vbm25_batch *bt, const vbm25_filter *f, const uint32_
 int vbm25_search_batch_filtered(vbm25_index *ix, const vbm25_filter *f, const uint32_t *q_filter, const uint32_t *term_ids,
                                 const uint32_t *q_off, uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
     return guarded([&] { return vbm25_search_batch_filtered_impl(ix, f, q_filter, term_ids, q_off, nq, k, hits, n_hits); });
+}
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The growing segment (growing.h): uploaded once per change of the relation's unsealed documents, merged into the records of every
+// run of a batch it is attached to.  The sealed route of such a batch is the one vbm25_batch_device_results forces (complete records
+// on the device after the scan: no one-launch scan_win_kernel run that leaves a query to the fetch, no records written straight into
+// pinned host memory); the growing kernels read a copy of those records and write the merged ones in their place, so a re-run merges
+// from the new sealed records again.
+// ---------------------------------------------------------------------------
+static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ix || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const uint32_t n = d->n_docs;
+    if (uint64_t(ix->n_docs) + n > (1ull << 32))
+        return set_error(VBM25_ERR_INVALID, "%u sealed + %u growing documents exceed 2^32: the doc id ranges would collide", ix->n_docs, n);
+    if (n && (!d->start || !d->fieldnorm || !d->payload)) return set_error(VBM25_ERR_INVALID, "growing arrays missing");
+    const uint64_t e_first = n ? d->start[0] : 0, e_end = n ? d->start[n] : 0;
+    for (uint32_t g = 0; g < n; ++g)
+        if (d->start[g + 1] < d->start[g]) return set_error(VBM25_ERR_INVALID, "start not monotone at document %u", g);
+    if (e_end > d->n_elements) return set_error(VBM25_ERR_INVALID, "start reaches element %llu of %llu", (unsigned long long)e_end,
+                                                (unsigned long long)d->n_elements);
+    const uint64_t n_el = e_end - e_first;
+    if (n_el && (!d->key || !d->tf)) return set_error(VBM25_ERR_INVALID, "growing arrays missing");
+    if (n_el >= (1ull << 31)) return set_error(VBM25_ERR_UNSUPPORTED, "%llu growing elements: the device path takes fewer than 2^31",
+                                               (unsigned long long)n_el);
+    for (uint32_t g = 0; g < n; ++g)  // Document::checked_new, vector.rs:56-61
+        for (uint64_t e = d->start[g] + 1; e < d->start[g + 1]; ++e)
+            if (std::memcmp(d->key + 16ull * (e - 1), d->key + 16ull * e, 16) >= 0)
+                return set_error(VBM25_ERR_INVALID, "growing document %u: keys must be strictly ascending", g);
+    if (int rc = use_device(ix->device)) return rc;
+    auto gs = std::make_unique<vbm25_device_growing>();
+    gs->index = ix;
+    gs->device = ix->device;
+    gs->n_grow = n;
+    gs->n_tiles = uint32_t((uint64_t(n) + GT - 1) / GT);
+    const uint32_t nt = ix->n_terms;
+    DeviceBuffer tkey, start, key, tf, fn, del, keys, vals, keys2, vals2, cnt, tmp;
+    int rc = 0;
+    if ((rc = tkey.upload(ix->term_key.data(), 16ull * nt)) || (rc = start.upload(d->start, 8ull * (n + 1ull))) ||
+        (rc = key.upload(d->key ? d->key + 16ull * e_first : nullptr, 16ull * n_el)) ||
+        (rc = tf.upload(d->tf ? d->tf + e_first : nullptr, 4ull * n_el)) || (rc = fn.upload(d->fieldnorm, n)) ||
+        (d->deleted && (rc = del.upload(d->deleted, n))) || (rc = gs->payload.upload(d->payload, 6ull * n)) ||
+        (rc = keys.alloc(8ull * n_el)) || (rc = vals.alloc(4ull * n_el)) || (rc = keys2.alloc(8ull * n_el)) ||
+        (rc = vals2.alloc(4ull * n_el)) || (rc = cnt.alloc(4)) || (rc = gs->term_start.alloc(4ull * (nt + 1ull))))
+        return rc;
+    HIP_TRY(hipMemset(cnt.p, 0, 4));
+    HIP_TRY(hipMemset(gs->term_start.p, 0, 4ull * (nt + 1ull)));
+    uint32_t n_post = 0;
+    if (n_el) {
+        if (n) grow_map_kernel<<<(n + 255) / 256, 256>>>(tkey.as<ulonglong2>(), nt, n, start.as<uint64_t>(), key.as<ulonglong2>(),
+                                                         tf.as<uint32_t>(), d->deleted ? del.as<uint8_t>() : nullptr,
+                                                         keys.as<unsigned long long>(), vals.as<uint32_t>(), cnt.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        // (term id, g) ascending: a stable order of the postings by term with g ascending inside a term (flush.hip's sort of the mappings)
+        size_t tb = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
+                                                   vals.as<uint32_t>(), vals2.as<uint32_t>(), (int)n_el));
+        if ((rc = tmp.alloc(tb))) return rc;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
+                                                   vals.as<uint32_t>(), vals2.as<uint32_t>(), (int)n_el));
+        HIP_TRY(hipMemcpy(&n_post, cnt.p, 4, hipMemcpyDeviceToHost));
+    }
+    gs->n_post = n_post;
+    if ((rc = gs->post_g.alloc(4ull * n_post)) || (rc = gs->post_c.alloc(8ull * n_post))) return rc;
+    if (n_post)
+        grow_post_kernel<<<(n_post + 255) / 256, 256>>>(keys2.as<unsigned long long>(), vals2.as<uint32_t>(), n_post, nt,
+                                                         ix->term_s0.as<double>(), ix->s1.as<double>(), fn.as<uint8_t>(),
+                                                         gs->post_g.as<uint32_t>(), gs->post_c.as<double>(), gs->term_start.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    gs->term_start_host.resize(nt + 1ull);
+    HIP_TRY(hipMemcpy(gs->term_start_host.data(), gs->term_start.p, 4ull * (nt + 1ull), hipMemcpyDeviceToHost));
+    // tile tables for the terms with at least one posting per tile (they take at most about as much as the postings' ids); the
+    // shorter lists are binary-searched
+    std::vector<uint32_t> tab_idx(nt, NONE32);
+    uint64_t n_tab = 0;
+    if (gs->n_tiles > 1)
+        for (uint32_t t = 0; t < nt; ++t)
+            if (gs->term_start_host[t + 1] - gs->term_start_host[t] >= gs->n_tiles && n_tab + gs->n_tiles + 1u < NONE32) {
+                tab_idx[t] = uint32_t(n_tab);
+                n_tab += gs->n_tiles + 1u;
+            }
+    if ((rc = gs->tab_idx.upload(tab_idx.data(), 4ull * nt)) || (rc = gs->tab.alloc(4ull * n_tab))) return rc;
+    if (n_tab) grow_tab_kernel<<<(n_post + 255) / 256, 256>>>(keys2.as<unsigned long long>(), n_post, gs->dev(), gs->tab.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    for (const DeviceBuffer *b : {&gs->term_start, &gs->post_g, &gs->post_c, &gs->tab_idx, &gs->tab, &gs->payload}) gs->device_bytes += b->bytes;
+    *out = gs.release();
+    return VBM25_OK;
+}
+
+// lists of growing_scan_kernel: workgroups per query for nq queries (G_MAX_WG in all, at least one per query, at most one per tile)
+static uint32_t growing_gq(uint32_t nq, uint32_t n_tiles) {
+    return std::max(1u, std::min(std::max(1u, n_tiles), G_MAX_WG / std::max(nq, 1u)));
+}
+
+static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *gs) {
+    if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
+    if (gs && gs->index != bt->index) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    if (gs && bt->filt_on) return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a filter: filters do not apply to growing documents");
+    if (int rc = use_device(bt->device)) return rc;
+    // a run in flight reads the segment and the buffers to its end
+    if (bt->lat_stream) HIP_TRY(hipStreamSynchronize(bt->lat_stream));
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    bt->growing = nullptr;
+    if (!gs) return VBM25_OK;
+    auto grow = [](DeviceBuffer &b, size_t bytes) -> int {
+        if (b.p && b.bytes >= bytes) return VBM25_OK;
+        if (b.p) HIP_TRY(hipFree(b.p));
+        b.p = nullptr;
+        return b.alloc(bytes);
+    };
+    const size_t mq = bt->max_queries, k = bt->k;
+    int rc = 0;
+    if ((rc = grow(bt->gr_sealed, sizeof(vbm25_hit) * mq * k)) || (rc = grow(bt->gr_sealed_cnt, 4 * mq))) return rc;
+    if (bt->bigk) {
+        const size_t n = std::max<size_t>(gs->n_grow, 1);
+        size_t tb = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                             (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n));
+        const bool new_iota = !bt->gr_iota.p || bt->gr_iota.bytes < 4 * n;
+        if ((rc = grow(bt->gr_acc, 8 * n)) || (rc = grow(bt->gr_keys, 8 * n)) || (rc = grow(bt->gr_iota, 4 * n)) ||
+            (rc = grow(bt->gr_docs, 4 * n)) || (rc = grow(bt->gr_tmp, tb)))
+            return rc;
+        bt->gr_tmp_bytes = bt->gr_tmp.bytes;
+        if (new_iota) {
+            bigk_iota_kernel<<<1024, 256>>>(bt->gr_iota.as<uint32_t>(), uint32_t(bt->gr_iota.bytes / 4));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipDeviceSynchronize());
+        }
+    } else {
+        const size_t lists = 4ull * std::max<size_t>(G_MAX_WG, mq);  // (nq gq <= max(G_MAX_WG, nq): growing_gq)
+        if ((rc = grow(bt->gr_ls, 8 * lists * k)) || (rc = grow(bt->gr_lg, 4 * lists * k)) || (rc = grow(bt->gr_lc, 4 * lists))) return rc;
+    }
+    bt->growing = gs;
+    return VBM25_OK;
+}
+
+// the growing segment's part of a run, on the run's stream behind the sealed scan
+static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
+    const vbm25_device_growing *gs = bt->growing;
+    const uint32_t nq = bt->nq, k = bt->k;
+    const DevGrowing G = gs->dev();
+    HIP_TRY(hipMemcpyAsync(bt->gr_sealed.p, bt->hits.p, sizeof(vbm25_hit) * size_t(nq) * k, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(bt->gr_sealed_cnt.p, bt->n_hits.p, 4ull * nq, hipMemcpyDeviceToDevice, st));
+    const vbm25_hit *sealed = bt->gr_sealed.as<vbm25_hit>();
+    const uint32_t *sealed_cnt = bt->gr_sealed_cnt.as<uint32_t>();
+    if (bt->bigk) {
+        const uint32_t n = std::max(gs->n_grow, 1u);
+        for (uint32_t q = 0; q < nq; ++q) {
+            HIP_TRY(hipMemsetAsync(bt->gr_acc.p, 0, 8ull * n, st));
+            for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p) {
+                const uint32_t t = bt->h_terms[p];
+                if (t >= bt->index->n_terms) continue;
+                const uint32_t p0 = gs->term_start_host[t], np = gs->term_start_host[t + 1] - p0;
+                if (np) grow_accum_kernel<<<std::min<uint32_t>((np + 255) / 256, 4096u), 256, 0, st>>>(G.post_g, G.post_c, p0, np, bt->gr_acc.as<double>());
+            }
+            size_t tmp = bt->gr_tmp_bytes;
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(bt->gr_tmp.p, tmp, bt->gr_acc.as<unsigned long long>(),
+                                                                  bt->gr_keys.as<unsigned long long>(), bt->gr_iota.as<uint32_t>(),
+                                                                  bt->gr_docs.as<uint32_t>(), (int)n, 0, 64, st));
+            growing_final_kernel<<<(k + 255) / 256, 256, 0, st>>>(sealed + size_t(q) * k, sealed_cnt + q, bt->gr_keys.as<unsigned long long>(),
+                                                                  bt->gr_docs.as<uint32_t>(), gs->n_grow, k, G.payload,
+                                                                  bt->hits.as<vbm25_hit>() + size_t(q) * k, bt->n_hits.as<uint32_t>() + q);
+        }
+        HIP_TRY(hipGetLastError());
+        return VBM25_OK;
+    }
+    GrowArgs a{};
+    a.term_ids = bt->term_ids.as<uint32_t>();
+    a.q_off = bt->q_off.as<uint32_t>();
+    if (bt->qin_live) {  // the staged descriptors (upload_staged), as vbm25_batch_run_impl reads them
+        a.term_ids = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>());
+        a.q_off = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + bt->pin_nt);
+    }
+    a.nq = nq;
+    a.k = k;
+    a.gq = growing_gq(nq, gs->n_tiles);
+    a.sealed = sealed;
+    a.sealed_cnt = sealed_cnt;
+    a.ls = bt->gr_ls.as<double>();
+    a.lg = bt->gr_lg.as<uint32_t>();
+    a.lc = bt->gr_lc.as<uint32_t>();
+    a.hits = bt->hits.as<vbm25_hit>();
+    a.n_hits = bt->n_hits.as<uint32_t>();
+    (void)dispatch_k(k, [&](auto kmax) {
+        constexpr int KM = decltype(kmax)::value;
+        growing_scan_kernel<KM><<<nq * a.gq, GWG, 0, st>>>(G, a);
+        growing_merge_kernel<KM><<<nq, 64, 0, st>>>(G, a);
+        return int(VBM25_OK);
+    });
+    HIP_TRY(hipGetLastError());
+    return VBM25_OK;
+}
+
+static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
+    if (!bt->nq) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // timed: the sealed scan through the final merge (the sealed route's own events are off for the run)
+    const bool timing = bt->timing;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timing) {
+        if (bt->events_used == bt->events.size()) {
+            HIP_TRY(hipEventCreate(&e0));
+            HIP_TRY(hipEventCreate(&e1));
+            bt->events.emplace_back(e0, e1);
+        }
+        e0 = bt->events[bt->events_used].first;
+        e1 = bt->events[bt->events_used].second;
+        bt->events_used++;
+        HIP_TRY(hipEventRecord(e0, st));
+    }
+    bt->timing = false;
+    int rc = vbm25_batch_run_impl(bt, hip_stream);
+    bt->timing = timing;
+    if (rc) return rc;
+    if ((rc = growing_enqueue(bt, st))) return rc;
+    if (timing) HIP_TRY(hipEventRecord(e1, st));
+    return VBM25_OK;
+}
+
+static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
+                                           uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    if (!ix || !gs || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (gs->index != ix) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
+    // a batch object of the index's for this entry point, re-used while the shape fits; the segment is attached for the call only
+    vbm25_batch *bt = ix->scratch_grow;
+    const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
+    if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
+        if (bt) vbm25_batch_destroy(bt);
+        ix->scratch_grow = nullptr;
+        if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;
+        ix->scratch_grow = bt;
+    }
+    int rc = batch_set_growing_impl(bt, gs);
+    if (!rc) rc = vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq);
+    if (!rc) rc = batch_run_growing_impl(bt, nullptr);
+    if (!rc) rc = vbm25_batch_fetch_impl(bt, hits, n_hits);
+    const int rc2 = batch_set_growing_impl(bt, nullptr);
+    return rc ? rc : rc2;
+}
+
+extern "C" {
+int vbm25_growing_upload(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
+    return guarded([&] { return vbm25_growing_upload_impl(ix, d, out); });
+}
+void vbm25_device_growing_free(vbm25_device_growing *gs) {
+    if (!gs) return;
+    (void)hipSetDevice(gs->device);
+    delete gs;
+}
+uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *gs) { return gs ? gs->device_bytes : 0; }
+int vbm25_search_batch_growing(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
+                               uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    return guarded([&] { return vbm25_search_batch_growing_impl(ix, gs, term_ids, q_off, nq, k, hits, n_hits); });
+}
+int vbm25_batch_set_growing(vbm25_batch *bt, const vbm25_device_growing *gs) {
+    return guarded([&] { return batch_set_growing_impl(bt, gs); });
 }
 }  // extern "C"
 
