@@ -271,6 +271,9 @@ int vbm25_search_batch(vbm25_index *, const uint32_t *term_ids, const uint32_t *
 int vbm25_batch_create(vbm25_index *, uint32_t max_queries, uint32_t max_total_terms, uint32_t k,
                        vbm25_batch **out);
 void vbm25_batch_destroy(vbm25_batch *);
+/* A failed vbm25_batch_set_queries leaves the batch holding no queries: run enqueues nothing, fetch writes
+ * nothing and returns VBM25_OK, and the next successful set_queries works as on a new batch (filter and growing
+ * segment stay attached). */
 int vbm25_batch_set_queries(vbm25_batch *, const uint32_t *term_ids, const uint32_t *q_off,
                             uint32_t nq);
 int vbm25_batch_run(vbm25_batch *, void *hip_stream);
@@ -435,6 +438,7 @@ int vbm25_multi_search_batch(vbm25_multi *, const uint32_t *term_ids, const uint
 int vbm25_multi_batch_create(vbm25_multi *, uint32_t max_queries, uint32_t max_total_terms, uint32_t k,
                              vbm25_multi_batch **out);
 void vbm25_multi_batch_destroy(vbm25_multi_batch *);
+/* A failed vbm25_multi_batch_set_queries leaves every shard holding no queries, as vbm25_batch_set_queries does. */
 int vbm25_multi_batch_set_queries(vbm25_multi_batch *, const uint32_t *term_ids, const uint32_t *q_off,
                                   uint32_t nq);
 int vbm25_multi_batch_run(vbm25_multi_batch *);

@@ -303,8 +303,12 @@ class Batch:
     def set_queries(self, term_ids, q_off):
         term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
         q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
-        check(lib().vbm25_batch_set_queries(self.h, _p(term_ids), q_off.ctypes.data_as(C.c_void_p),
-                                            len(q_off) - 1))
+        try:
+            check(lib().vbm25_batch_set_queries(self.h, _p(term_ids), q_off.ctypes.data_as(C.c_void_p),
+                                                len(q_off) - 1))
+        except Vbm25Error:
+            self.nq = 0  # (a refused query set leaves the batch with none: include/vbm25.h)
+            raise
         self.nq = len(q_off) - 1
 
     def run(self, stream=None):
@@ -670,7 +674,11 @@ class MultiBatch:
     def set_queries(self, term_ids, q_off):
         term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
         q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
-        check(lib().vbm25_multi_batch_set_queries(self.h, _p(term_ids), q_off.ctypes.data_as(C.c_void_p), len(q_off) - 1))
+        try:
+            check(lib().vbm25_multi_batch_set_queries(self.h, _p(term_ids), q_off.ctypes.data_as(C.c_void_p), len(q_off) - 1))
+        except Vbm25Error:
+            self.nq = 0  # (every shard is left with no queries: include/vbm25.h)
+            raise
         self.nq = len(q_off) - 1
 
     def run(self):
@@ -687,8 +695,10 @@ def set_tuning(name, value):
     """test / tuning aid (vbm25_tuning_set, not in include/vbm25.h): process-wide switch read when a Batch / GpuIndex
     scratch batch is created.  Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items,
     range_min_chunk, range_grid, dense_grid, fused_items, arith, win, win_force, win_items, win_grid, win_skew, win_guided,
-    win_planes, rel16_plane and id16_plane (read at index creation).  No switch of the product library changes results (`dbg`, the
-    timing experiments of scan_win_kernel, exists only in the development build libvbm25_dev.so)."""
+    id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
+    takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation).  No switch of
+    the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
+    libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set
     f.restype = C.c_int
     f.argtypes = [C.c_char_p, C.c_longlong]

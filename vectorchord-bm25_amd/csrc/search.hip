@@ -277,6 +277,8 @@ struct Tuning {
     int win_cut1 = 392, win_cut2 = 730;  // ... where a query's three runs are cut, in thousandths of its windows (round 6, tools/skew_sweep.sh: 59 / 52 / 42 of C3's 153)
     int win_order_arith = 1;       // the skewed layout computed in the kernel when the queries keep their order (0: always the host's table)
     int win_skew = 1;              // one item per wave: a query's three runs of windows sized for the three kinds of waves of a SIMD
+    uint32_t id16_max_blocks = 0x00ffffff;  // an index without post_id16: the most 256-byte blocks of a batch's terms its scratch plane takes
+                                   // (a larger batch takes scan_range_kernel; tests lower it to cross the limit on a small corpus)
     uint32_t generation = 0;       // bumped by every vbm25_tuning_set / reset: vbm25_search_batch's batch object is rebuilt when it is stale
 };
 static Tuning g_tune;
@@ -865,8 +867,7 @@ static int upload_staged(vbm25_batch *bt) {
     return VBM25_OK;
 }
 
-static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off,
-                            uint32_t nq, bool fast = false) {
+static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, bool fast) {
     if (!bt || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (!term_ids && nq && q_off[nq] != 0) return set_error(VBM25_ERR_INVALID, "term_ids is NULL but the queries have terms");
     if (nq > bt->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the batch capacity %u", nq, bt->max_queries);
@@ -993,6 +994,25 @@ static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_id
                     }
                 }
             }
+            uint64_t id16_blocks = 0;
+            if (win_g && !ixh->post_id16.p) {
+                // An index without the post_id16 plane: every term position gets its blocks in the batch's scratch plane (a term's
+                // blocks are full but its last: (df + 127) / 128 of them, post_fn_kernel's flag 8 saw to that), which
+                // decode_id16_kernel fills ahead of the scan.  A batch whose terms need more blocks than the plane addresses takes
+                // scan_range_kernel (or the general route), which decodes the blob's blocks itself -- decided before anything is committed.
+                std::vector<uint32_t> &fbv = bt->h_id16_fb;
+                fbv.resize(q_off[nq]);
+                id16_blocks = 2;  // (block 0: what the null terms' run loads read)
+                for (uint32_t p = 0; p < q_off[nq]; ++p) {
+                    const uint32_t t = term_ids[p];
+                    fbv[p] = uint32_t(std::min<uint64_t>(id16_blocks, UINT32_MAX));
+                    if (t < ixh->n_terms) id16_blocks += (uint64_t(ixh->term_df_host[t]) + 127u) / 128u;
+                }
+                if (id16_blocks > std::min<uint64_t>(bt->tune.id16_max_blocks, 0x00ffffffull)) {
+                    win_g = 0;
+                    bt->win_len = 0;
+                }
+            }
             if (bt->tune.fused && nq * g <= bt->tune.fused_items) {
                 bt->fused_g = uint32_t(g);
                 bt->fused_pinned = fast && nq <= 8 && !bt->timing;
@@ -1000,20 +1020,8 @@ static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_id
                 if (win_g) {
                     bt->win_g = win_g;
                     g = win_g;
-                    if (!ixh->post_id16.p) {
-                        // An index without the post_id16 plane: every term position gets its blocks in the batch's scratch plane (a
-                        // term's blocks are full but its last: (df + 127) / 128 of them, post_fn_kernel's flag 8 saw to that), which
-                        // decode_id16_kernel fills ahead of the scan.  The plane grows with the largest batch it has held.
-                        std::vector<uint32_t> &fbv = bt->h_id16_fb;
-                        fbv.resize(q_off[nq]);
-                        uint64_t blocks = 2;  // (block 0: what the null terms' run loads read)
-                        for (uint32_t p = 0; p < q_off[nq]; ++p) {
-                            const uint32_t t = term_ids[p];
-                            fbv[p] = uint32_t(blocks);
-                            if (t < ixh->n_terms) blocks += (uint64_t(ixh->term_df_host[t]) + 127u) / 128u;
-                        }
-                        if (blocks > 0x00ffffffull) return set_error(VBM25_ERR_UNSUPPORTED, "the batch's terms exceed the scratch plane of an index without post_id16");
-                        const size_t need = 256ull * blocks + 1024;
+                    if (!ixh->post_id16.p) {  // (the scratch plane, its blocks counted above: it grows with the largest batch it has held)
+                        const size_t need = 256ull * id16_blocks + 1024;
                         if (need > bt->id16_tmp.bytes) {
                             if (bt->last_stream || bt->lat_stream) HIP_TRY(hipDeviceSynchronize());  // (a run still reading the old plane)
                             if (bt->id16_tmp.p) HIP_TRY(hipFree(bt->id16_tmp.p));
@@ -1023,7 +1031,7 @@ static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_id
                             HIP_TRY(hipMemset(bt->id16_tmp.p, 0, bt->id16_tmp.bytes));
                         }
                         bt->id16_decode = true;
-                        if (!fast && q_off[nq]) HIP_TRY(hipMemcpy(bt->id16_fb.p, fbv.data(), 4ull * q_off[nq], hipMemcpyHostToDevice));
+                        if (!fast && q_off[nq]) HIP_TRY(hipMemcpy(bt->id16_fb.p, bt->h_id16_fb.data(), 4ull * q_off[nq], hipMemcpyHostToDevice));
                     }
                 } else
                 bt->arith_g = uint32_t(g);  // the general route, items made in the kernel: no plan_kernel, merge_kernel cleans
@@ -1159,6 +1167,40 @@ static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_id
     return VBM25_OK;
 }
 
+
+// The batch holds no queries: run enqueues nothing, fetch writes nothing.  What a failed set_queries leaves (include/vbm25.h) -- also
+// when it failed after committing part of the new set (its count and route, an allocation, a copy): the next run must not launch on
+// a mix of the old query set's descriptors and the new one's count.  Filter and growing segment stay attached.
+static void batch_clear_queries(vbm25_batch *bt) {
+    bt->nq = 0;
+    bt->n_term_pos = 0;
+    bt->fused_g = 0;
+    bt->arith_g = 0;
+    bt->win_g = 0;
+    bt->win_len = 0;
+    bt->win_skew = false;
+    bt->id16_decode = false;
+    bt->pin_id16_bytes = 0;
+    bt->need_many = true;
+    bt->has_dense = false;
+    bt->qin_live = false;
+    bt->fused_pinned = false;
+    bt->win_nofuse = false;
+    bt->win_fused_run = false;
+}
+
+static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off,
+                            uint32_t nq, bool fast = false) {
+    int rc;
+    try {
+        rc = batch_set_queries_body(bt, term_ids, q_off, nq, fast);
+    } catch (...) {  // (out of host memory: guarded() makes it the call's error code)
+        if (bt) batch_clear_queries(bt);
+        throw;
+    }
+    if (rc && bt) batch_clear_queries(bt);
+    return rc;
+}
 
 static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
@@ -1632,7 +1674,7 @@ int vbm25_evaluate_batch(vbm25_index *ix, const uint32_t *q_terms, uint32_t n_q,
 
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
-// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, dbg.
+// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg.
 int vbm25_tuning_set(const char *name, long long value) {
     if (!name) return set_error(VBM25_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> guard(g_tune_mutex);
@@ -1665,6 +1707,7 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "win_cut1") g_tune.win_cut1 = int(std::min<long long>(std::max<long long>(value, 1), 998));
     else if (n == "win_cut2") g_tune.win_cut2 = int(std::min<long long>(std::max<long long>(value, 2), 999));
     else if (n == "win_fuse") g_tune.win_fuse = value != 0;
+    else if (n == "id16_max_blocks") g_tune.id16_max_blocks = (uint32_t)std::min<long long>(std::max(2ll, value), 0x00ffffffll);
     else return set_error(VBM25_ERR_INVALID, "unknown tuning switch %s", name);
     ++g_tune.generation;
     return VBM25_OK;
@@ -2522,7 +2565,7 @@ int multi_batch_create_impl(vbm25_multi *m, uint32_t max_queries, uint32_t max_t
     return VBM25_OK;
 }
 
-int multi_batch_set_queries_impl(vbm25_multi_batch *mb, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
+int multi_batch_set_queries_body(vbm25_multi_batch *mb, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
     if (!mb || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (nq > mb->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the batch capacity %u", nq, mb->max_queries);
     if (q_off[0] != 0) return set_error(VBM25_ERR_INVALID, "q_off[0] must be 0");
@@ -2544,6 +2587,25 @@ int multi_batch_set_queries_impl(vbm25_multi_batch *mb, const uint32_t *term_ids
         // staged in the part's pinned memory, copied on its own stream: the devices' uploads overlap
         return vbm25_batch_set_queries_impl(mb->parts[i], term_ids ? term_ids + q_off[a] : nullptr, off.data(), b - a, true);
     });
+}
+
+// A failed call leaves no queries in any part (include/vbm25.h): a shard that rejected the new set must not keep its old one, whose
+// records fetch would write at the new set's shard offset -- past the end of the caller's buffers
+int multi_batch_set_queries_impl(vbm25_multi_batch *mb, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
+    auto clear = [mb] {
+        mb->nq = 0;
+        std::fill(mb->lo.begin(), mb->lo.end(), 0u);
+        for (vbm25_batch *b : mb->parts) batch_clear_queries(b);
+    };
+    int rc;
+    try {
+        rc = multi_batch_set_queries_body(mb, term_ids, q_off, nq);
+    } catch (...) {
+        if (mb) clear();
+        throw;
+    }
+    if (rc && mb) clear();
+    return rc;
 }
 
 int multi_batch_run_impl(vbm25_multi_batch *mb) {
