@@ -338,8 +338,8 @@ int vbm25_batch_set_filter(vbm25_batch *, const vbm25_filter *, const uint32_t *
  *   vbm25_batch_set_growing    every later run of the batch merges the segment in (NULL detaches: the batch behaves exactly
  *                              as without); vbm25_batch_device_results then points at the merged records, and kernel_ms
  *                              covers the sealed scan through the final merge.
- * A growing segment of another index -> VBM25_ERR_INVALID.  A batch with both a filter and a growing segment ->
- * VBM25_ERR_UNSUPPORTED from whichever setter comes second.  vbm25_stream_* and vbm25_multi_* take no growing segment. */
+ * A growing segment of another index -> VBM25_ERR_INVALID.  A batch with both a filter and a growing segment needs the filter's
+ * growing bitmaps of that segment (below).  vbm25_stream_* and vbm25_multi_* take no growing segment. */
 typedef struct vbm25_device_growing vbm25_device_growing;
 int vbm25_growing_upload(vbm25_index *, const vbm25_growing_desc *, vbm25_device_growing **out);
 void vbm25_device_growing_free(vbm25_device_growing *);
@@ -347,6 +347,33 @@ uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *);
 int vbm25_search_batch_growing(vbm25_index *, const vbm25_device_growing *, const uint32_t *term_ids, const uint32_t *q_off,
                                uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits);
 int vbm25_batch_set_growing(vbm25_batch *, const vbm25_device_growing *);
+
+/* Filters on the growing segment: besides its F sealed bitmaps a filter can hold F growing bitmaps for ONE uploaded growing segment.
+ * Growing bitmap i is ceil(n_grow / 64) uint64_t words, bit g % 64 (least significant first) of word g / 64 = 1 means growing
+ * document g (its position in the uploaded CSR) may be returned.  Query q's selector s names sealed bitmap s AND growing bitmap s;
+ * UINT32_MAX filters neither.  For a selector s != UINT32_MAX the records are byte for byte
+ *     vbm25_merge_hits(the records vbm25_search_batch_filtered gives q,
+ *                      vbm25_growing_search(..., deleted = deleted OR NOT growing bit s of g), k)
+ * -- sealed hits first on equal scores, doc_id = 0xFFFFFFFF - g, the sealed segment's statistics, every k of 1 .. 65535.
+ *   vbm25_filter_set_growing   words: F x ceil(n_grow / 64), or NULL for all bits zero; a NULL segment removes the growing
+ *                              bitmaps.  Synchronous.  Bits at or beyond n_grow, a segment of another index -> VBM25_ERR_INVALID.
+ *                              The filter names the segment by its upload (each vbm25_growing_upload is a new one, also at a
+ *                              re-used address) and keeps no pointer to it: freeing the segment stays legal, the bitmaps then
+ *                              match no segment.  A re-upload needs the bitmaps set again.
+ *   vbm25_filter_update_growing        replaces growing bitmap i from host memory (as vbm25_filter_update).
+ *   vbm25_filter_growing_device_words  device address of growing bitmap i (as vbm25_filter_device_words).
+ *   (both: VBM25_ERR_INVALID when the filter has no growing bitmaps)
+ *   vbm25_search_batch_growing_filtered  vbm25_search_batch_growing with q_filter[q] (nq selectors) for query q.
+ * A batch holds a filter and a growing segment together only when the filter's growing bitmaps are that segment's; the second
+ * setter (vbm25_batch_set_filter / vbm25_batch_set_growing, either order) returns VBM25_ERR_UNSUPPORTED when the filter has no
+ * growing bitmaps and VBM25_ERR_INVALID when they belong to another upload.  vbm25_batch_run checks again (the filter's growing
+ * bitmaps may have been set since): on a mismatch it returns VBM25_ERR_INVALID, enqueues nothing and leaves the batch as it was. */
+int vbm25_filter_set_growing(vbm25_filter *, const vbm25_device_growing *, const uint64_t *words);
+int vbm25_filter_update_growing(vbm25_filter *, uint32_t i, const uint64_t *words);
+int vbm25_filter_growing_device_words(vbm25_filter *, uint32_t i, void **dev);
+int vbm25_search_batch_growing_filtered(vbm25_index *, const vbm25_device_growing *, const vbm25_filter *,
+                                        const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off,
+                                        uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits);
 
 /* The same boundary PIPELINED (the caller hands over host buffers and gets host buffers back, as bm25::search
  * returns a Vec, search.rs:28-36): up to `depth` batches are in flight at once, each on its own stream with its

@@ -113,7 +113,10 @@ class Index {
     vbm25_index *h_ = nullptr;
 };
 
+class DeviceGrowing;
+
 // F document bitmaps of one index in HBM (vbm25_filter): bit d % 64 of word d / 64 of bitmap i set = document d may be returned.
+// Optionally F growing bitmaps for one uploaded growing segment (set_growing): bit g = growing document g may be returned.
 class DocFilter {
   public:
     static size_t words_per_bitmap(uint32_t n_docs) { return (size_t(n_docs) + 63) / 64; }
@@ -128,6 +131,14 @@ class DocFilter {
     void *device_words(uint32_t i) {
         void *p = nullptr;
         check(vbm25_filter_device_words(h_, i, &p));
+        return p;
+    }
+    // growing bitmaps: n_bitmaps x words_per_bitmap(n_grow), or empty for all bits zero; a NULL segment removes them
+    inline void set_growing(const DeviceGrowing *growing, const std::vector<uint64_t> &words = {});
+    void update_growing(uint32_t i, const std::vector<uint64_t> &words) { check(vbm25_filter_update_growing(h_, i, words.data())); }
+    void *growing_device_words(uint32_t i) {
+        void *p = nullptr;
+        check(vbm25_filter_growing_device_words(h_, i, &p));
         return p;
     }
     // the exact filtered top-k: query q returns documents of bitmap q_filter[q] only (UINT32_MAX: every document)
@@ -258,6 +269,24 @@ class DeviceGrowing {
   private:
     vbm25_device_growing *h_ = nullptr;
 };
+
+inline void DocFilter::set_growing(const DeviceGrowing *growing, const std::vector<uint64_t> &words) {
+    check(vbm25_filter_set_growing(h_, growing ? growing->handle() : nullptr, words.empty() ? nullptr : words.data()));
+}
+
+// per query: the sealed and the growing records merged, query q taking bitmap q_filter[q] of `filter` on both segments
+// (UINT32_MAX: every document); the filter's growing bitmaps must be those of `growing`
+inline void search_batch_growing_filtered(const Index &index, const DeviceGrowing &growing, const DocFilter &filter,
+                                          const std::vector<uint32_t> &q_filter, const std::vector<uint32_t> &term_ids,
+                                          const std::vector<uint32_t> &q_off, size_t k, std::vector<Hit> &hits,
+                                          std::vector<uint32_t> &n_hits) {
+    const uint32_t nq = uint32_t(q_off.size() - 1);
+    if (q_filter.size() != nq) throw Error(VBM25_ERR_INVALID, "one selector per query");
+    hits.resize(size_t(nq) * k);
+    n_hits.resize(nq);
+    check(vbm25_search_batch_growing_filtered(index.handle(), growing.handle(), filter.handle(), q_filter.data(), term_ids.data(),
+                                              q_off.data(), nq, uint32_t(k), hits.data(), n_hits.data()));
+}
 
 }  // namespace vbm25
 #endif

@@ -88,6 +88,10 @@ ABI = {
     "vbm25_device_growing_bytes": (u64, [vp]),
     "vbm25_search_batch_growing": (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
     "vbm25_batch_set_growing": (i32, [vp, vp]),
+    "vbm25_filter_set_growing": (i32, [vp, vp, vp]),
+    "vbm25_filter_update_growing": (i32, [vp, u32, vp]),
+    "vbm25_filter_growing_device_words": (i32, [vp, u32, vp]),
+    "vbm25_search_batch_growing_filtered": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]),
     "vbm25_evaluate_batch": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
     "vbm25_device_segment_build": (i32, [i32, C.c_double, C.c_double, u32, vp, vp, u32, vp, vp, vp, vp, vp]),
     "vbm25_device_segment_synth": (i32, [vp, i32, vp]),

@@ -472,6 +472,7 @@ class DocFilter:
 
     def __init__(self, index, keep):
         self.index = index
+        self.growing = None  # the GrowingSegment of the growing bitmaps (set_growing)
         words = self.pack(keep, index.n_docs)
         self.n_bitmaps, self.words = words.shape
         self.h = C.c_void_p()
@@ -505,6 +506,36 @@ class DocFilter:
         """vbm25_filter_device_words: the device address of bitmap i (ceil(n_docs / 64) uint64 words)."""
         dev = C.c_void_p()
         check(lib().vbm25_filter_device_words(self.h, i, C.byref(dev)))
+        return dev.value
+
+    def set_growing(self, growing, keep=None):
+        """vbm25_filter_set_growing: F growing bitmaps over the documents of `growing` (a GrowingSegment of this filter's index):
+        bit g of growing bitmap i set = growing document g may be returned; query q's selector names sealed and growing bitmap
+        alike.  `keep` as in the constructor over growing.n_docs documents (None: all bits zero).  growing=None removes them."""
+        if growing is None:
+            check(lib().vbm25_filter_set_growing(self.h, None, None))
+            self.growing = None
+            return
+        words = None
+        if keep is not None:
+            words = self.pack(keep, growing.n_docs)
+            if words.shape[0] != self.n_bitmaps:
+                raise ValueError(f"{words.shape[0]} growing bitmaps for a filter of {self.n_bitmaps}")
+        check(lib().vbm25_filter_set_growing(self.h, growing.h, _p(words)))
+        self.growing = growing
+
+    def update_growing(self, i, keep_i):
+        """vbm25_filter_update_growing: replace growing bitmap i (bool array [n_grow] or growing document ids)."""
+        if self.growing is None:
+            raise ValueError("the filter has no growing bitmaps")
+        n = self.growing.n_docs
+        words = self.pack(keep_i if isinstance(keep_i, np.ndarray) and keep_i.dtype == np.bool_ else [keep_i], n)
+        check(lib().vbm25_filter_update_growing(self.h, i, _p(words)))
+
+    def growing_device_words(self, i):
+        """vbm25_filter_growing_device_words: the device address of growing bitmap i (ceil(n_grow / 64) uint64 words)."""
+        dev = C.c_void_p()
+        check(lib().vbm25_filter_growing_device_words(self.h, i, C.byref(dev)))
         return dev.value
 
     def __del__(self):
@@ -581,6 +612,24 @@ def search_batch_growing(index, growing, term_ids, q_off, k):
     check(lib().vbm25_search_batch_growing(index.h, growing.h if growing is not None else None, _p(term_ids),
                                            q_off.ctypes.data_as(C.c_void_p), nq, k, hits.ctypes.data_as(C.c_void_p),
                                            n_hits.ctypes.data_as(C.c_void_p)))
+    return hits, n_hits
+
+
+def search_batch_growing_masked(index, growing, term_ids, q_off, k, doc_filter, q_filter):
+    """vbm25_search_batch_growing_filtered: search_batch_growing where query q takes bitmap q_filter[q] of `doc_filter` on both
+    segments (its sealed bitmap and its growing bitmap of `growing`, DocFilter.set_growing; NO_FILTER: every document)."""
+    term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
+    q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+    nq = len(q_off) - 1
+    q_filter = np.ascontiguousarray(q_filter, dtype=np.uint32).reshape(-1)
+    if len(q_filter) != nq:
+        raise ValueError(f"{len(q_filter)} selectors for {nq} queries")
+    hits = np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(nq, dtype=np.uint32)
+    check(lib().vbm25_search_batch_growing_filtered(index.h, growing.h if growing is not None else None,
+                                                    doc_filter.h if doc_filter is not None else None, _p(q_filter), _p(term_ids),
+                                                    q_off.ctypes.data_as(C.c_void_p), nq, k, hits.ctypes.data_as(C.c_void_p),
+                                                    n_hits.ctypes.data_as(C.c_void_p)))
     return hits, n_hits
 
 

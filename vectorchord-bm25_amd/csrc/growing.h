@@ -12,6 +12,11 @@
 // add: 0.0 + c == c), then every wave offers the touched documents of its quarter of the tile to a RegTopK (ties by g ascending).
 // growing_merge_kernel merges a query's lists and then the sealed records with them (sealed first on equal scores).
 // k > 1024: a dense accumulator over the growing documents per query, a stable descending radix sort, growing_final_kernel.
+//
+// Filtered batches (vbm25_filter_set_growing): query q with selector s takes growing bitmap s, one bit per growing document g.  In
+// growing_scan_kernel<KM, true> a lane's uint32 word of the bitmap covers exactly the 32 documents of its bits[] word, so a rejected
+// document is dropped where the touched documents are extracted (never read from acc, never offered); a tile whose bitmap words are
+// all zero is skipped by the whole workgroup before any posting is read.  k > 1024: bigk_mask_kernel zeroes the rejected scores.
 
 constexpr uint32_t GT = 8192;        // documents per tile: 64 KB of f64 accumulators in LDS
 constexpr uint32_t GWG = 256;        // threads of growing_scan_kernel
@@ -36,6 +41,11 @@ struct GrowArgs {
     uint32_t *lg, *lc;
     vbm25_hit *hits;                  // the batch's records: the merged result
     uint32_t *n_hits;
+    // filtered batches only (FILT): growing bitmap s = filt_stride uint32 words at filt_words + s filt_stride (bit g % 32 of word
+    // g / 32: document g may be returned), filt_sel[q] = query q's selector (NONE32: none).  Unread by the unfiltered kernels.
+    const uint32_t *filt_words;
+    const uint32_t *filt_sel;
+    uint32_t filt_stride;
 };
 
 // 16-byte token keys compare as memcmp: two big-endian 64-bit words
@@ -168,7 +178,8 @@ __device__ __forceinline__ void grow_rank_merge(const vbm25_hit *S, uint32_t ns,
     if (tid == 0) *n_out = min(k, ns + ng);
 }
 
-template <int KM>
+// FILT: the batch has a document filter with growing bitmaps (see the top of this file)
+template <int KM, bool FILT>
 __global__ void __launch_bounds__(GWG) growing_scan_kernel(DevGrowing G, GrowArgs a) {
     constexpr int RK = KM / 64;
     __shared__ double acc[GT];
@@ -197,10 +208,24 @@ __global__ void __launch_bounds__(GWG) growing_scan_kernel(DevGrowing G, GrowArg
     }
     __syncthreads();
     const uint32_t nt = s_nt;
+    const uint32_t *fw = nullptr;  // the query's growing bitmap (FILT), NULL: none
+    if constexpr (FILT) {
+        const uint32_t s = a.filt_sel[q];
+        if (s != NONE32) fw = a.filt_words + size_t(s) * a.filt_stride;
+    }
     RegTopK<RK> top;
     top.init();
     for (uint32_t j = j0; j < j1 && nt; ++j) {
         const uint32_t tile_lo = j * GT;
+        uint32_t keep = ~0u;  // the bitmap word of this thread's bits[] word (the documents tile_lo + 32 tid ..)
+        if constexpr (FILT) {
+            if (fw) {
+                const uint32_t fi = j * (GT / 32u) + tid;
+                keep = fi < a.filt_stride ? fw[fi] : 0u;
+            }
+            // no document of the tile may be returned: the whole workgroup skips it (a barrier: uniform)
+            if (!__syncthreads_or(keep != 0u)) continue;
+        }
         __syncthreads();  // (the last tile's reads of s_cum and acc are done)
         for (uint32_t r = tid; r < nt; r += GWG) {
             const uint2 rg = grow_tile_range(G, s_t[r], j);
@@ -262,6 +287,7 @@ __global__ void __launch_bounds__(GWG) growing_scan_kernel(DevGrowing G, GrowArg
             const uint32_t wi = wave * 64u + lane;
             uint32_t word = bits[wi];
             bits[wi] = 0;
+            if constexpr (FILT) word &= keep;  // (wi == tid)
             while (__ballot(word != 0)) {
                 bool has = word != 0;
                 uint32_t d = 0;

@@ -21,6 +21,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -217,19 +218,25 @@ struct vbm25_index {
     uint64_t device_bytes = 0;
 };
 
-// F bitmaps over the documents of one index, in HBM on its device (vbm25_filter_create)
+// F bitmaps over the documents of one index, in HBM on its device (vbm25_filter_create), and optionally F bitmaps over the documents
+// of one uploaded growing segment (vbm25_filter_set_growing), named by the upload's serial number -- no pointer into the segment
 struct vbm25_filter {
     const vbm25_index *index = nullptr;
     int device = 0;
     uint32_t n_bitmaps = 0;
     uint32_t words = 0;  // per bitmap: ceil(n_docs / 64)
     DeviceBuffer bits;   // n_bitmaps x words
+    uint64_t grow_serial = 0;  // the growing bitmaps' segment (vbm25_device_growing::serial), 0: none
+    uint32_t grow_n = 0;       // ... its n_grow
+    uint32_t grow_words = 0;   // per growing bitmap: ceil(grow_n / 64)
+    DeviceBuffer grow_bits;    // n_bitmaps x grow_words
 };
 
 // The growing segment of one index in HBM on its device (vbm25_growing_upload; growing.h has the layout)
 struct vbm25_device_growing {
     const vbm25_index *index = nullptr;
     int device = 0;
+    uint64_t serial = 0;  // per upload, from a process-wide counter (never 0): a re-upload at the same address is another segment
     uint32_t n_grow = 0, n_tiles = 0, n_post = 0;
     DeviceBuffer term_start, post_g, post_c, tab_idx, tab, payload;
     std::vector<uint32_t> term_start_host;  // (k > 1024: one accumulation launch per term)
@@ -1971,7 +1978,12 @@ static int vbm25_filter_update_impl(vbm25_filter *f, uint32_t i, const uint64_t 
 static int batch_set_filter_impl(vbm25_batch *bt, const vbm25_filter *f, const uint32_t *q_filter, uint32_t n_sel) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
     if (f && f->index != bt->index) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
-    if (f && bt->growing) return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a growing segment: filters do not apply to growing documents");
+    if (f && bt->growing) {
+        if (!f->grow_serial)
+            return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a growing segment and the filter has no growing bitmaps");
+        if (f->grow_serial != bt->growing->serial)
+            return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps belong to another upload than the batch's growing segment");
+    }
     if (f && !q_filter && n_sel) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
     if (f)
         for (uint32_t q = 0; q < n_sel; ++q)
@@ -2052,6 +2064,8 @@ int vbm25_search_batch_filtered(vbm25_index *ix, const vbm25_filter *f, const ui
 // pinned host memory); the growing kernels read a copy of those records and write the merged ones in their place, so a re-run merges
 // from the new sealed records again.
 // ---------------------------------------------------------------------------
+static std::atomic<uint64_t> g_growing_serial{0};  // uploads so far (vbm25_device_growing::serial)
+
 static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
     if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
     *out = nullptr;
@@ -2077,6 +2091,7 @@ static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *
     auto gs = std::make_unique<vbm25_device_growing>();
     gs->index = ix;
     gs->device = ix->device;
+    gs->serial = g_growing_serial.fetch_add(1) + 1;
     gs->n_grow = n;
     gs->n_tiles = uint32_t((uint64_t(n) + GT - 1) / GT);
     const uint32_t nt = ix->n_terms;
@@ -2142,7 +2157,12 @@ static uint32_t growing_gq(uint32_t nq, uint32_t n_tiles) {
 static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *gs) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
     if (gs && gs->index != bt->index) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
-    if (gs && bt->filt_on) return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a filter: filters do not apply to growing documents");
+    if (gs && bt->filt_on) {
+        if (!bt->filter->grow_serial)
+            return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a filter without growing bitmaps");
+        if (bt->filter->grow_serial != gs->serial)
+            return set_error(VBM25_ERR_INVALID, "the batch's filter has growing bitmaps of another upload than this segment");
+    }
     if (int rc = use_device(bt->device)) return rc;
     // a run in flight reads the segment and the buffers to its end
     if (bt->lat_stream) HIP_TRY(hipStreamSynchronize(bt->lat_stream));
@@ -2200,6 +2220,10 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
                 const uint32_t p0 = gs->term_start_host[t], np = gs->term_start_host[t + 1] - p0;
                 if (np) grow_accum_kernel<<<std::min<uint32_t>((np + 255) / 256, 4096u), 256, 0, st>>>(G.post_g, G.post_c, p0, np, bt->gr_acc.as<double>());
             }
+            if (bt->filt_on && bt->h_filt_sel[q] != UINT32_MAX && gs->n_grow)
+                bigk_mask_kernel<<<std::min<uint32_t>((gs->n_grow + 255) / 256, 4096u), 256, 0, st>>>(
+                    bt->filter->grow_bits.as<unsigned long long>() + size_t(bt->h_filt_sel[q]) * bt->filter->grow_words, gs->n_grow,
+                    bt->gr_acc.as<double>());
             size_t tmp = bt->gr_tmp_bytes;
             HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(bt->gr_tmp.p, tmp, bt->gr_acc.as<unsigned long long>(),
                                                                   bt->gr_keys.as<unsigned long long>(), bt->gr_iota.as<uint32_t>(),
@@ -2228,9 +2252,15 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
     a.lc = bt->gr_lc.as<uint32_t>();
     a.hits = bt->hits.as<vbm25_hit>();
     a.n_hits = bt->n_hits.as<uint32_t>();
+    if (bt->filt_on) {  // (batch_run_growing_impl checked that the growing bitmaps are this segment's)
+        a.filt_words = bt->filter->grow_bits.as<uint32_t>();
+        a.filt_sel = bt->filt_sel.as<uint32_t>();
+        a.filt_stride = 2u * bt->filter->grow_words;
+    }
     (void)dispatch_k(k, [&](auto kmax) {
         constexpr int KM = decltype(kmax)::value;
-        growing_scan_kernel<KM><<<nq * a.gq, GWG, 0, st>>>(G, a);
+        if (bt->filt_on) growing_scan_kernel<KM, true><<<nq * a.gq, GWG, 0, st>>>(G, a);
+        else growing_scan_kernel<KM, false><<<nq * a.gq, GWG, 0, st>>>(G, a);
         growing_merge_kernel<KM><<<nq, 64, 0, st>>>(G, a);
         return int(VBM25_OK);
     });
@@ -2239,6 +2269,9 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
 }
 
 static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
+    // the filter's growing half may have been replaced since the batch took it: nothing is enqueued, the batch stays as it was
+    if (bt->filt_on && bt->filter->grow_serial != bt->growing->serial)
+        return set_error(VBM25_ERR_INVALID, "the batch's filter has no growing bitmaps of its growing segment (set again since)");
     if (!bt->nq) return VBM25_OK;
     if (int rc = use_device(bt->index->device)) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -2265,12 +2298,9 @@ static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
     return VBM25_OK;
 }
 
-static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
-                                           uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
-    if (!ix || !gs || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (gs->index != ix) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
-    if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
-    // a batch object of the index's for this entry point, re-used while the shape fits; the segment is attached for the call only
+// a batch object of the index's for the one-shot growing entry points, re-used while the shape fits (segment and filter are attached
+// for one call only)
+static int scratch_grow_batch(vbm25_index *ix, uint32_t nq, const uint32_t *q_off, uint32_t k, vbm25_batch **out) {
     vbm25_batch *bt = ix->scratch_grow;
     const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
     if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
@@ -2279,6 +2309,17 @@ static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_g
         if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;
         ix->scratch_grow = bt;
     }
+    *out = bt;
+    return VBM25_OK;
+}
+
+static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
+                                           uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    if (!ix || !gs || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (gs->index != ix) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
+    vbm25_batch *bt = nullptr;
+    if (int rc = scratch_grow_batch(ix, nq, q_off, k, &bt)) return rc;
     int rc = batch_set_growing_impl(bt, gs);
     if (!rc) rc = vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq);
     if (!rc) rc = batch_run_growing_impl(bt, nullptr);
@@ -2286,6 +2327,99 @@ static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_g
     const int rc2 = batch_set_growing_impl(bt, nullptr);
     return rc ? rc : rc2;
 }
+
+// ---------------------------------------------------------------------------
+// Filters on the growing segment: a filter's F growing bitmaps (one bit per growing document g of one upload) go with its F sealed
+// bitmaps -- query q's selector s names both.  The records are those of the host composition with the rejected growing documents
+// treated as deleted.  The filter names the upload by its serial number; the batch setters and every run check it.
+// ---------------------------------------------------------------------------
+static int filter_check_growing_words(uint32_t n_grow, uint32_t gw, const uint64_t *w) {
+    const uint32_t tail = n_grow & 63u;  // bits at or beyond n_grow must be zero
+    if (gw && tail && (w[gw - 1] >> tail) != 0)
+        return set_error(VBM25_ERR_INVALID, "growing bitmap has bits set at or beyond n_grow = %u", n_grow);
+    return VBM25_OK;
+}
+
+static int vbm25_filter_set_growing_impl(vbm25_filter *f, const vbm25_device_growing *gs, const uint64_t *words) {
+    if (!f) return set_error(VBM25_ERR_INVALID, "filter is NULL");
+    if (gs && gs->index != f->index) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    const uint32_t gw = gs ? (gs->n_grow + 63u) / 64u : 0u;
+    if (gs && words)
+        for (uint32_t i = 0; i < f->n_bitmaps; ++i)
+            if (int rc = filter_check_growing_words(gs->n_grow, gw, words + size_t(i) * gw)) return rc;
+    if (int rc = use_device(f->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old bits to their end)
+    DeviceBuffer nb;  // the new bitmaps (none: the old ones are freed with it)
+    if (gs) {
+        const size_t bytes = 8ull * f->n_bitmaps * gw;
+        if (int rc = nb.alloc(bytes)) return rc;
+        if (words && bytes) HIP_TRY(hipMemcpy(nb.p, words, bytes, hipMemcpyHostToDevice));
+        else HIP_TRY(hipMemset(nb.p, 0, bytes ? bytes : 16));
+    }
+    std::swap(f->grow_bits.p, nb.p);
+    std::swap(f->grow_bits.bytes, nb.bytes);
+    f->grow_serial = gs ? gs->serial : 0;
+    f->grow_n = gs ? gs->n_grow : 0;
+    f->grow_words = gw;
+    return VBM25_OK;
+}
+
+static int vbm25_filter_update_growing_impl(vbm25_filter *f, uint32_t i, const uint64_t *words) {
+    if (!f || !words) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!f->grow_serial) return set_error(VBM25_ERR_INVALID, "the filter has no growing bitmaps");
+    if (i >= f->n_bitmaps) return set_error(VBM25_ERR_INVALID, "bitmap %u of a filter of %u", i, f->n_bitmaps);
+    if (int rc = filter_check_growing_words(f->grow_n, f->grow_words, words)) return rc;
+    if (int rc = use_device(f->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old bits to their end)
+    if (f->grow_words)
+        HIP_TRY(hipMemcpy(f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_words, words, 8ull * f->grow_words, hipMemcpyHostToDevice));
+    return VBM25_OK;
+}
+
+static int vbm25_search_batch_growing_filtered_impl(vbm25_index *ix, const vbm25_device_growing *gs, const vbm25_filter *f,
+                                                    const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq,
+                                                    uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    if (!ix || !gs || !f || (!q_filter && nq) || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (gs->index != ix) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    if (f->index != ix) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
+    for (uint32_t q = 0; q < nq; ++q)
+        if (q_filter[q] != UINT32_MAX && q_filter[q] >= f->n_bitmaps)
+            return set_error(VBM25_ERR_INVALID, "query %u: selector %u, the filter has %u bitmaps", q, q_filter[q], f->n_bitmaps);
+    if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
+    vbm25_batch *bt = nullptr;
+    if (int rc = scratch_grow_batch(ix, nq, q_off, k, &bt)) return rc;
+    int rc = batch_set_growing_impl(bt, gs);
+    if (!rc) rc = batch_set_filter_impl(bt, f, q_filter, nq);
+    if (!rc) rc = vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq);
+    if (!rc) rc = batch_run_growing_impl(bt, nullptr);
+    if (!rc) rc = vbm25_batch_fetch_impl(bt, hits, n_hits);
+    const int rc2 = batch_set_filter_impl(bt, nullptr, nullptr, 0);
+    const int rc3 = batch_set_growing_impl(bt, nullptr);
+    return rc ? rc : rc2 ? rc2 : rc3;
+}
+
+extern "C" {
+int vbm25_filter_set_growing(vbm25_filter *f, const vbm25_device_growing *gs, const uint64_t *words) {
+    return guarded([&] { return vbm25_filter_set_growing_impl(f, gs, words); });
+}
+int vbm25_filter_update_growing(vbm25_filter *f, uint32_t i, const uint64_t *words) {
+    return guarded([&] { return vbm25_filter_update_growing_impl(f, i, words); });
+}
+int vbm25_filter_growing_device_words(vbm25_filter *f, uint32_t i, void **dev) {
+    if (!f || !dev) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!f->grow_serial) return set_error(VBM25_ERR_INVALID, "the filter has no growing bitmaps");
+    if (i >= f->n_bitmaps) return set_error(VBM25_ERR_INVALID, "bitmap %u of a filter of %u", i, f->n_bitmaps);
+    *dev = f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_words;
+    return VBM25_OK;
+}
+int vbm25_search_batch_growing_filtered(vbm25_index *ix, const vbm25_device_growing *gs, const vbm25_filter *f, const uint32_t *q_filter,
+                                        const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, uint32_t k, vbm25_hit *hits,
+                                        uint32_t *n_hits) {
+    return guarded([&] {
+        return vbm25_search_batch_growing_filtered_impl(ix, gs, f, q_filter, term_ids, q_off, nq, k, hits, n_hits);
+    });
+}
+}  // extern "C"
 
 extern "C" {
 int vbm25_growing_upload(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
