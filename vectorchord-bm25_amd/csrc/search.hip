@@ -295,6 +295,55 @@ static Tuning tuning_snapshot() {
     return g_tune;
 }
 
+// The route a query set takes (the numbers are what vbm25_batch_debug_route returns)
+enum class Route {
+    General = 0,     // plan_kernel, the scan kernels, merge_kernel
+    OneLaunch = 1,   // a handful of sparse queries: scan_range_kernel plans, scans and merges
+    PlanFree = 2,    // every query sparse: scan_range_kernel makes the work items itself, merge_kernel cleans
+    Window = 3,      // every query sparse, <= 8 terms of comparable length: scan_win_kernel
+    Exhaustive = 4,  // k > 1024: one query at a time over a dense accumulator
+};
+
+// The staged descriptors, one block in pinned memory (pin_in) and on the device (qin): term ids at 0, then the byte offsets of the
+// query offsets, the dense flags (padded to 8), the host's item order and the id16 block starts, and the end of the block
+struct StagedLayout {
+    size_t off = 0, dense = 0, order = 0, id16 = 0, end = 0;
+};
+static StagedLayout staged_layout(uint32_t nq, uint32_t n_term_pos, size_t n_order, bool id16) {
+    StagedLayout L;
+    L.off = 4ull * n_term_pos;
+    L.dense = L.off + 4ull * (nq + 1);
+    L.order = L.dense + ((size_t(nq) + 7) & ~size_t(7));
+    L.id16 = L.order + 4 * n_order;
+    L.end = L.id16 + (id16 ? 4ull * n_term_pos : 0);
+    return L;
+}
+
+// The pinned output block (pin_out): the error flag at 0, the counts at 8, the records at the first 8-byte boundary behind them
+static size_t pin_out_records(uint32_t nq) { return 8 + ((4ull * nq + 7) & ~size_t(7)); }
+
+// What set_queries decided for the current query set.  A batch without queries holds QueryPlan{}.
+struct QueryPlan {
+    Route route = Route::General;
+    uint32_t g = 0;               // OneLaunch, PlanFree, Window: work items per query (Window: runs of 2^16-document windows)
+    uint32_t win_len = 0;         // Window: a query's runs are win_len windows each and a shorter rest (0: equal runs)
+    bool win_skew = false;        // ... one item per wave, a query's three runs sized for the three kinds of waves of a SIMD
+    bool order_identity = false;  // ... the queries keep the caller's order in the host's item order (no sort by length)
+    bool order_useful = true;     // ... the queries differ enough in length for the longest-first order to matter
+    uint32_t q_stride = 0;        // != 0: every query has this many terms
+    uint32_t range_mt = 0;        // the most indexed terms of a sparse query of <= 16 (0: none, or k > REG_K)
+    bool has_dense = false;       // some query takes scan_dense_kernel
+    bool need_many = true;        // some query has items for scan_many_kernel (more than 16 terms, 256 < k, dense without the dense kernel)
+    uint32_t dense_c = 0;         // items per dense query (0: chunks by postings, as the other queries)
+    uint32_t range_grid = R_GRID, dense_grid = D_GRID;
+    bool id16_decode = false;     // Window on an index without post_id16: the terms' ids go through the batch's scratch plane
+    uint64_t id16_blocks = 0;     // ... its 256-byte blocks the terms need
+    bool fused_pinned = false;    // OneLaunch with queries and hits in pinned host memory (vbm25_search_batch, <= 8 queries)
+    uint32_t n_term_pos = 0;      // term positions (q_off[nq])
+    StagedLayout staged;
+    uint32_t range_rt() const { return range_mt == 0 ? 0u : range_mt <= 8u ? 8u : 16u; }  // scan_range_kernel's row stride
+};
+
 struct vbm25_batch {
     vbm25_index *index = nullptr;
     int device = 0;  // the index's device ordinal: the batch can be destroyed after its index
@@ -318,42 +367,23 @@ struct vbm25_batch {
     size_t gr_tmp_bytes = 0;
     std::vector<uint8_t> h_dense;          // per query: dense (scratch of set_queries, sized once)
     std::vector<unsigned long long> h_postings;
-    std::vector<uint32_t> h_order, h_order_q;  // set_queries: the longest-first item order of the route without plan_kernel
+    std::vector<uint32_t> h_order, h_order_q;  // set_queries: the longest-first item order of the routes without plan_kernel
     Tuning tune;                  // the switches of the moment the batch was created
     bool timing = false;
     bool use_range = false;       // k <= REG_K: sparse queries of <= 16 terms take scan_range_kernel, dense ones scan_dense_kernel
-    uint32_t range_rt = 0;        // ... with this row stride (8 or 16) for the current queries; 0 = not used
     uint32_t lpi = 1;             // result lists per work item
-    uint32_t range_grid = R_GRID;
     bool use_dense = false;       // dense queries of <= D_T terms take scan_dense_kernel
-    bool has_dense = false;       // ... and the current queries have such a query
-    uint32_t dense_grid = D_GRID;
-    uint32_t dense_c = 0;         // items per dense query of the current queries (0: chunks by postings, as the other queries)
-    // vbm25_search_batch with a handful of sparse queries: ONE launch (scan_range_kernel plans, scans and merges)
-    uint32_t fused_g = 0;         // items per query of the current queries on that route (0: general route)
-    uint32_t arith_g = 0;         // general route without plan_kernel (every query sparse): items per query, made by the scan kernel itself
-    uint32_t win_mt = 8;          // scan_win_kernel: the most indexed terms of a query of the current batch
-    bool win_skew = false;        // scan_win_kernel: one item per wave, a query's three runs sized for the three kinds of waves of a SIMD
-    uint32_t q_stride = 0;        // != 0: every query of the current batch has this many terms
-    bool order_identity = false;  // ... and their order in the host's item order is the caller's (no sort by length)
-    bool order_useful = true;     // the current queries differ enough in length for the longest-first order to matter
-    uint32_t win_g = 0;           // ... and scan_win_kernel's flavour of it (items = runs of 2^16-document windows, one result list each)
-    uint32_t win_len = 0;         // ... a query's runs: win_len windows each and a shorter rest (0: equal runs)
+    QueryPlan plan;               // the current queries' route (set_queries)
     // an index without the post_id16 plane: the batch's scratch plane (the low 16 bits of the ids of the current queries' terms, made by
     // decode_id16_kernel ahead of every scan_win_kernel launch) and, per term position, the term's first 256-byte block in it
     DeviceBuffer id16_tmp, id16_fb;
     std::vector<uint32_t> h_id16_fb;
-    bool id16_decode = false;     // the current queries take scan_win_kernel through the scratch plane
-    uint32_t n_term_pos = 0;      // term positions of the current queries (q_off[nq])
-    size_t pin_id16_bytes = 0;    // ... and their h_id16_fb is staged behind the item order (upload_staged)
-    DeviceBuffer qin;             // the staged descriptors on the device, one block: term ids | offsets | dense flags (padded to 8) | item order
+    DeviceBuffer qin;             // the staged descriptors on the device (StagedLayout)
     bool qin_live = false;        // ... hold the current queries (set by upload_staged; a plain set_queries fills the separate buffers)
     bool device_consumer = false; // vbm25_batch_device_results was called: every run leaves complete records on the device
     bool win_nofuse = false;      // the last run's in-kernel merge marked a query (an item was given up): this query set runs with scan_many_kernel and merge_kernel
-    bool win_fused_run = false;   // the last run was a one-launch run of scan_win_kernel (a count of NONE32 means: re-run, see vbm25_batch_fetch_impl)
-    bool need_many = true;        // the current queries have items for scan_many_kernel (more than 16 terms, 256 < k, dense without the dense kernel)
-    bool fused_pinned = false;    // ... with queries and hits in pinned host memory (vbm25_search_batch, <= 8 queries); else device buffers
-    bool state_clean = false;     // threshold / histogram / counters are zero (the fused route leaves them so; the general one does not)
+    bool win_fused_run = false;   // the last run was a one-launch run of scan_win_kernel (a count of NONE32 means: re-run, see rerun_and_fetch)
+    bool state_clean = false;     // threshold / histogram / counters are zero (the routes without plan_kernel leave them so; the general one does not)
     uint32_t target_items = TARGET_ITEMS;
     uint32_t min_chunk = MIN_CHUNK_POSTINGS;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -367,7 +397,7 @@ struct vbm25_batch {
     // download command on the step: only the 4-byte flag is copied); results_pinned_now: the last run did so
     bool pinned_results = false, results_pinned_now = false;
     uint8_t *pin_in = nullptr, *pin_out = nullptr;
-    size_t pin_in_bytes = 0, pin_out_bytes = 0, pin_nt = 0, pin_order_bytes = 0;
+    size_t pin_in_bytes = 0, pin_out_bytes = 0;
     ~vbm25_batch() {
         if (lat_stream) (void)hipStreamDestroy(lat_stream);
         if (pin_in) (void)hipHostFree(pin_in);
@@ -417,8 +447,6 @@ void fill_dev(vbm25_index *ix) {
 }  // namespace
 
 namespace {
-
-constexpr int VBM25_RETRY_GENERAL = 1000;  // internal: never leaves this file
 
 int use_device(int device) {
     HIP_TRY(hipSetDevice(device));
@@ -861,79 +889,36 @@ void vbm25_batch_destroy(vbm25_batch *bt) {
     delete bt;
 }
 
-// queries staged in the pinned buffer (term ids | offsets | dense flags) -> device, on the batch's own stream
 // The staged descriptors -- term ids, offsets, dense flags, the host's item order -- lie in ONE pinned block and go to ONE device
 // block with one copy command (round 6: they were four commands into four buffers, 15 .. 25 us of a device's 100 us of host time per
 // step on the multi-device route; vbm25_batch_run_impl points the kernels at the block's parts).
-static int upload_staged(vbm25_batch *bt) {
-    const size_t nt = bt->pin_nt, no = 4ull * (bt->nq + 1), nd8 = (size_t(bt->nq) + 7) & ~size_t(7);
-    const size_t total = nt + no + nd8 + bt->pin_order_bytes + bt->pin_id16_bytes;
-    if (total > bt->qin.bytes) return set_error(VBM25_ERR_INVALID, "internal error: staged descriptors exceed the device block");
-    HIP_TRY(hipMemcpyAsync(bt->qin.p, bt->pin_in, total, hipMemcpyHostToDevice, bt->lat_stream));
+static int upload_staged(vbm25_batch *bt, const StagedLayout &L) {
+    if (L.end > bt->qin.bytes) return set_error(VBM25_ERR_INVALID, "internal error: staged descriptors exceed the device block");
+    HIP_TRY(hipMemcpyAsync(bt->qin.p, bt->pin_in, L.end, hipMemcpyHostToDevice, bt->lat_stream));
     bt->qin_live = true;
     return VBM25_OK;
 }
 
-static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, bool fast) {
-    if (!bt || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (!term_ids && nq && q_off[nq] != 0) return set_error(VBM25_ERR_INVALID, "term_ids is NULL but the queries have terms");
-    if (nq > bt->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the batch capacity %u", nq, bt->max_queries);
-    if (q_off[0] != 0) return set_error(VBM25_ERR_INVALID, "q_off[0] must be 0");
-    bool many = false, has_dense = false;
-    uint32_t n_dense = 0, range_mt = 0;
-    // Routing: scan_range_kernel is built for sparse queries; a query with many postings per document (Zipf head terms)
-    // takes the dense-window kernel, one with more than 16 indexed terms scan_many_kernel.  (The scratch vectors were
-    // sized when the batch was created: nothing is allocated here.)
-    const unsigned long long dense_x1000 = (unsigned long long)std::max(0ll, bt->tune.dense_x1000);
-    uint8_t *dense = bt->h_dense.data();
-    unsigned long long *q_postings = bt->h_postings.data();
-    for (uint32_t q = 0; q < nq; ++q) {
-        if (q_off[q + 1] < q_off[q]) return set_error(VBM25_ERR_INVALID, "q_off not monotone at query %u", q);
-        uint32_t valid = 0;
-        unsigned long long postings = 0;
-        for (uint32_t p = q_off[q]; p < q_off[q + 1]; ++p) {
-            if (p > q_off[q] && term_ids[p] <= term_ids[p - 1])  // Query::checked_new, vector.rs:106-110
-                return set_error(VBM25_ERR_INVALID, "query %u: term ids must be strictly ascending", q);
-            valid += term_ids[p] < bt->index->n_terms;
-            if (term_ids[p] < bt->index->n_terms) postings += bt->index->term_df_host[term_ids[p]];
-        }
-        q_postings[q] = postings;
-        dense[q] = 0;
-        if (postings * 1000ull >= dense_x1000 * bt->index->n_docs) {
-            dense[q] = 1;
-            many = true;
-            n_dense += postings != 0;
-        }
-        if (bt->use_range) {  // sparse queries of <= 16 terms: scan_range_kernel; dense ones: scan_dense_kernel; the rest: scan_many_kernel
-            many |= valid > 16u;
-            has_dense |= bt->use_dense && dense[q] && valid <= (uint32_t)D_T;
-            if (!dense[q] && valid <= 16u) range_mt = std::max(range_mt, valid);
-        } else {
-            many = true;
-        }
-        if (valid > MAX_TERMS)
-            return set_error(VBM25_ERR_UNSUPPORTED, "query %u has %u indexed terms; the GPU path handles up to %d", q, valid, MAX_TERMS);
-    }
-    if (q_off[nq] > bt->max_terms) return set_error(VBM25_ERR_INVALID, "%u terms exceed the batch capacity %u", q_off[nq], bt->max_terms);
-    if (int rc = use_device(bt->index->device)) return rc;
-    if (bt->bigk) {
-        bt->h_terms.assign(term_ids, term_ids + q_off[nq]);
-        bt->h_off.assign(q_off, q_off + nq + 1);
-        bt->nq = nq;
-        return VBM25_OK;
-    }
-    bt->nq = nq;
-    bt->fused_g = 0;
-    bt->arith_g = 0;
-    bt->win_g = 0;
-    bt->win_len = 0;
-    bt->win_nofuse = false;
-    bt->id16_decode = false;
-    bt->pin_id16_bytes = 0;
-    bt->n_term_pos = q_off[nq];
-    bt->need_many = many || !bt->use_range;
-    bt->fused_pinned = false;
-    if (bt->use_range && nq && !many && !has_dense && range_mt != 0) {  // every query sparse, <= 16 indexed terms: the one-launch route
+// a pinned host block of at least `need` bytes (twice that when it grows: the next batch may be larger again)
+static int pinned_fit(uint8_t *&p, size_t &bytes, size_t need) {
+    if (need <= bytes) return VBM25_OK;
+    if (p) HIP_TRY(hipHostFree(p));
+    p = nullptr;
+    bytes = 2 * need + 256;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p), bytes, hipHostMallocDefault));
+    return VBM25_OK;
+}
+
+// The route of a validated query set (bt->h_dense and bt->h_postings hold its classes, plan its has_dense and range_mt), its item order
+// in bt->h_order and, for the scratch plane, its id16 block starts in bt->h_id16_fb.  No HIP call, nothing committed.
+static void plan_route(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, bool fast, bool many,
+                       uint32_t n_dense, QueryPlan &plan) {
+    const uint8_t *dense = bt->h_dense.data();
+    const unsigned long long *q_postings = bt->h_postings.data();
+    const vbm25_index *ixh = bt->index;
+    plan.n_term_pos = q_off[nq];
+    plan.need_many = many || !bt->use_range;
+    if (bt->use_range && nq && !many && !plan.has_dense && plan.range_mt != 0) {  // every query sparse, <= 16 indexed terms: the one-launch route
         unsigned long long most = 0;
         bool all = true;
         for (uint32_t q = 0; q < nq; ++q) {
@@ -947,15 +932,14 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
             const unsigned long long chunk = nq <= 8 ? std::max<unsigned long long>(bt->min_chunk / 4, 1) : bt->min_chunk;
             unsigned long long g = (most + chunk / 2) / chunk;
             g = std::min<unsigned long long>(g, std::max<unsigned long long>((bt->target_items + nq / 2) / nq, 1));
-            g = std::min<unsigned long long>(std::max<unsigned long long>(g, 1), std::min<unsigned long long>(64, bt->index->n_docs));
+            g = std::min<unsigned long long>(std::max<unsigned long long>(g, 1), std::min<unsigned long long>(64, ixh->n_docs));
             // only where the launches it saves matter: a batch that fills the GPU runs slower through the FUSED
             // instantiation (more live state in the tile loop) than plan + scan + merge cost
             // scan_win_kernel (the window formulation): every query of <= 8 indexed terms, all with a window table, the lists of
             // comparable length (the MaxScore split of scan_range_kernel has nothing to skip) and neither too thin nor too thick
             // per 2^16-document window (32 .. 232 postings on average: one 8-byte load per lane holds a run)
             uint32_t win_g = 0;
-            const vbm25_index *ixh = bt->index;
-            if (bt->tune.win && bt->k <= scan_win_max_k(range_mt) && !ixh->term_win_host.empty()) {
+            if (bt->tune.win && bt->k <= scan_win_max_k(plan.range_mt) && !ixh->term_win_host.empty()) {
                 const double wins = std::max(1.0, double(ixh->n_docs) / 65536.0);
                 double e_max = 1.0;
                 bool ok = true;
@@ -987,9 +971,9 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
                     // items: one per resident wave (an item's setup is a chain of six round trips to memory: on C3 3072 items of 51
                     // windows take 0.270 ms, 6144 of 25 windows 0.287 ms)
                     // ... of as many windows as give every resident wave the same share of the batch's windows: L = ceil(nq n_win / waves).
-                    // A query is cut into runs of L windows and a shorter rest (win_cut, vbm25_batch_run): with 14 waves per workgroup C3's
+                    // A query is cut into runs of L windows and a shorter rest (win_cut, run_window): with 14 waves per workgroup C3's
                     // 1024 queries x 153 windows are 3072 runs of 44 and 1024 of 21 for 3584 waves -- the short ones go last, two to a wave.
-                    const uint32_t target = bt->tune.win_items ? bt->tune.win_items : scan_win_resident_waves(range_mt, bt->k);
+                    const uint32_t target = bt->tune.win_items ? bt->tune.win_items : scan_win_resident_waves(plan.range_mt, bt->k);
                     const uint32_t g_min = (ixh->n_win + 62u) / 63u;  // (an item holds at most 63 windows)
                     const uint64_t all_win = uint64_t(nq) * ixh->n_win;
                     const uint32_t len = uint32_t(std::min<uint64_t>(63u, std::max<uint64_t>(1u, (all_win + target - 1u) / target)));
@@ -997,51 +981,39 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
                     gw = std::min(std::min(gw, ixh->n_win), bt->max_items / nq);
                     if (gw >= g_min && gw >= 1u) {
                         win_g = gw;
-                        bt->win_len = (ixh->n_win + gw - 1u) / gw > len ? 0u : len;  // (0: equal runs -- the item limit cut the number of runs)
+                        plan.win_len = (ixh->n_win + gw - 1u) / gw > len ? 0u : len;  // (0: equal runs -- the item limit cut the number of runs)
                     }
                 }
             }
-            uint64_t id16_blocks = 0;
             if (win_g && !ixh->post_id16.p) {
                 // An index without the post_id16 plane: every term position gets its blocks in the batch's scratch plane (a term's
                 // blocks are full but its last: (df + 127) / 128 of them, post_fn_kernel's flag 8 saw to that), which
                 // decode_id16_kernel fills ahead of the scan.  A batch whose terms need more blocks than the plane addresses takes
-                // scan_range_kernel (or the general route), which decodes the blob's blocks itself -- decided before anything is committed.
+                // scan_range_kernel (or the general route), which decodes the blob's blocks itself.
                 std::vector<uint32_t> &fbv = bt->h_id16_fb;
                 fbv.resize(q_off[nq]);
-                id16_blocks = 2;  // (block 0: what the null terms' run loads read)
+                uint64_t blocks = 2;  // (block 0: what the null terms' run loads read)
                 for (uint32_t p = 0; p < q_off[nq]; ++p) {
                     const uint32_t t = term_ids[p];
-                    fbv[p] = uint32_t(std::min<uint64_t>(id16_blocks, UINT32_MAX));
-                    if (t < ixh->n_terms) id16_blocks += (uint64_t(ixh->term_df_host[t]) + 127u) / 128u;
+                    fbv[p] = uint32_t(std::min<uint64_t>(blocks, UINT32_MAX));
+                    if (t < ixh->n_terms) blocks += (uint64_t(ixh->term_df_host[t]) + 127u) / 128u;
                 }
-                if (id16_blocks > std::min<uint64_t>(bt->tune.id16_max_blocks, 0x00ffffffull)) {
+                plan.id16_blocks = blocks;
+                if (blocks > std::min<uint64_t>(bt->tune.id16_max_blocks, 0x00ffffffull)) {
                     win_g = 0;
-                    bt->win_len = 0;
+                    plan.win_len = 0;
                 }
             }
             if (bt->tune.fused && nq * g <= bt->tune.fused_items) {
-                bt->fused_g = uint32_t(g);
-                bt->fused_pinned = fast && nq <= 8 && !bt->timing;
+                plan.route = Route::OneLaunch;
+                plan.g = uint32_t(g);
+                plan.fused_pinned = fast && nq <= 8 && !bt->timing;
             } else if (win_g || bt->tune.arith) {
-                if (win_g) {
-                    bt->win_g = win_g;
-                    g = win_g;
-                    if (!ixh->post_id16.p) {  // (the scratch plane, its blocks counted above: it grows with the largest batch it has held)
-                        const size_t need = 256ull * id16_blocks + 1024;
-                        if (need > bt->id16_tmp.bytes) {
-                            if (bt->last_stream || bt->lat_stream) HIP_TRY(hipDeviceSynchronize());  // (a run still reading the old plane)
-                            if (bt->id16_tmp.p) HIP_TRY(hipFree(bt->id16_tmp.p));
-                            bt->id16_tmp.p = nullptr;
-                            bt->id16_tmp.bytes = 0;
-                            if (int rc = bt->id16_tmp.alloc(need + need / 4)) return rc;
-                            HIP_TRY(hipMemset(bt->id16_tmp.p, 0, bt->id16_tmp.bytes));
-                        }
-                        bt->id16_decode = true;
-                        if (!fast && q_off[nq]) HIP_TRY(hipMemcpy(bt->id16_fb.p, bt->h_id16_fb.data(), 4ull * q_off[nq], hipMemcpyHostToDevice));
-                    }
-                } else
-                bt->arith_g = uint32_t(g);  // the general route, items made in the kernel: no plan_kernel, merge_kernel cleans
+                // Window, or the general route with its items made in the kernel (PlanFree: no plan_kernel, merge_kernel cleans)
+                plan.route = win_g ? Route::Window : Route::PlanFree;
+                if (win_g) g = win_g;
+                plan.g = uint32_t(g);
+                plan.id16_decode = win_g && !ixh->post_id16.p;
                 // ... handed out longest first, as plan_kernel would (the host has the posting counts): queries by
                 // descending postings, a query's g parts together
                 std::vector<uint32_t> &ord = bt->h_order;
@@ -1056,21 +1028,21 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
                         lo = std::min(lo, q_postings[q]);
                         hi = std::max(hi, q_postings[q]);
                     }
-                    bt->order_identity = !(hi * 4 > lo * 5);  // (the queries keep their order: the skewed layout is arithmetic -- scan_win.h)
+                    plan.order_identity = !(hi * 4 > lo * 5);  // (the queries keep their order: the skewed layout is arithmetic -- scan_win.h)
                     if (hi * 4 > lo * 5) std::stable_sort(qs.begin(), qs.end(), [&](uint32_t a, uint32_t b) { return q_postings[a] > q_postings[b]; });
                 }
 
-                const uint32_t wpw = win_g ? scan_win_wg(range_mt, bt->k) : 0u;
-                bt->win_skew = win_g == 3u && wpw == 12u && size_t(nq) * 3u <= scan_win_resident_waves(range_mt, bt->k) && bt->tune.win_skew;
+                const uint32_t wpw = win_g ? scan_win_wg(plan.range_mt, bt->k) : 0u;
+                plan.win_skew = win_g == 3u && wpw == 12u && size_t(nq) * 3u <= scan_win_resident_waves(plan.range_mt, bt->k) && bt->tune.win_skew;
                 // (queries of about the same length: the longest-first order buys nothing and costs every work item a dependent load --
                 // unless there are more items than waves: then the queries' short last runs must be the ones drawn late)
-                bt->order_useful = bt->win_skew || (!win_g || !bt->tune.win_guided ? q_postings[qs[0]] * 4 > q_postings[qs[nq - 1]] * 5 : true) ||
-                                   (win_g && size_t(nq) * win_g > scan_win_resident_waves(range_mt, bt->k));
-                if (bt->win_skew) {
+                plan.order_useful = plan.win_skew || (!win_g || !bt->tune.win_guided ? q_postings[qs[0]] * 4 > q_postings[qs[nq - 1]] * 5 : true) ||
+                                 (win_g && size_t(nq) * win_g > scan_win_resident_waves(plan.range_mt, bt->k));
+                if (plan.win_skew) {
                     // One item per wave, three per query: a SIMD's three waves do not run equally fast -- the workgroup's waves 0..3
                     // (the first wave of every SIMD) lived 449 k cycles on C3, 4..7 497 k, 8..11 559 k, whatever priority they set
                     // themselves -- and the launch ends with the slowest.  A workgroup takes four queries; a query's three runs of
-                    // windows, of lengths in the ratio of those speeds (win_cut, vbm25_batch_run), go to one wave of each kind.
+                    // windows, of lengths in the ratio of those speeds (win_cut, run_window), go to one wave of each kind.
                     // (nq mod 4 queries are left over: their items follow in plain order -- written to a partial last workgroup's
                     // slots they would land beyond the end of the array)
                     const uint32_t full = nq / 4u;
@@ -1085,113 +1057,154 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
                 else
                 for (uint32_t i = 0; i < nq; ++i)
                     for (uint32_t part = 0; part < g; ++part) ord[size_t(i) * g + part] = qs[i] * uint32_t(g) + part;
-                // (the fast path stages the order with the queries and copies it on the batch's own stream: upload_staged)
-                if (!fast) HIP_TRY(hipMemcpy(bt->item_order.p, ord.data(), 4ull * ord.size(), hipMemcpyHostToDevice));
             }
         }
     }
-    if (fast && !bt->bigk) {
-        // staged in pinned memory.  One-launch route (fused_g): the kernel reads the queries from there and writes the hits
-        // into the pinned output buffer -- no copy is enqueued at all.  General route: copied on the batch's own stream,
-        // nothing waits here.
-        const size_t nt = 4ull * q_off[nq], no = 4ull * (nq + 1);
-        const bool with_order = bt->arith_g || bt->win_g;
-        const size_t nd8 = (size_t(nq) + 7) & ~size_t(7), nord = with_order ? 4ull * bt->h_order.size() : 0;
-        const size_t nid = bt->id16_decode ? nt : 0;  // (the terms' blocks in the scratch plane of an index without post_id16)
-        if (nt + no + nd8 + nord + nid > bt->pin_in_bytes) {
-            if (bt->pin_in) HIP_TRY(hipHostFree(bt->pin_in));
-            bt->pin_in = nullptr;
-            bt->pin_in_bytes = 2 * (nt + no + nd8 + nord + nid) + 256;
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bt->pin_in), bt->pin_in_bytes, hipHostMallocDefault));
-        }
-        const size_t nh = sizeof(vbm25_hit) * size_t(nq) * bt->k, nc = (4ull * nq + 7) & ~size_t(7);
-        if (8 + nc + nh > bt->pin_out_bytes) {
-            if (bt->pin_out) HIP_TRY(hipHostFree(bt->pin_out));
-            bt->pin_out = nullptr;
-            bt->pin_out_bytes = 2 * (8 + nc + nh) + 256;
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bt->pin_out), bt->pin_out_bytes, hipHostMallocDefault));
-        }
-        if (!bt->lat_stream) HIP_TRY(hipStreamCreateWithFlags(&bt->lat_stream, hipStreamNonBlocking));
-        if (nt) std::memcpy(bt->pin_in, term_ids, nt);
-        std::memcpy(bt->pin_in + nt, q_off, no);
-        if (nq) std::memcpy(bt->pin_in + nt + no, dense, nq);
-        if (nord) std::memcpy(bt->pin_in + nt + no + nd8, bt->h_order.data(), nord);
-        if (nid) std::memcpy(bt->pin_in + nt + no + nd8 + nord, bt->h_id16_fb.data(), nid);
-        bt->pin_nt = nt;
-        bt->pin_order_bytes = nord;
-        bt->pin_id16_bytes = nid;
-        if (!(bt->fused_g && bt->fused_pinned))
-            if (int rc = upload_staged(bt)) return rc;
-    } else {
-        bt->qin_live = false;
-        if (q_off[nq]) HIP_TRY(hipMemcpy(bt->term_ids.p, term_ids, 4ull * q_off[nq], hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(bt->q_off.p, q_off, 4ull * (nq + 1), hipMemcpyHostToDevice));
-        if (nq) HIP_TRY(hipMemcpy(bt->q_dense.p, dense, nq, hipMemcpyHostToDevice));
-    }
-    bt->has_dense = has_dense;
-    bt->range_rt = !bt->use_range || range_mt == 0 ? 0u : (range_mt <= 8u ? 8u : 16u);
-    bt->win_mt = range_mt;
-    bt->q_stride = 0;
+    const bool with_order = plan.route == Route::PlanFree || plan.route == Route::Window;
+    plan.staged = staged_layout(nq, q_off[nq], with_order ? size_t(nq) * plan.g : 0, plan.id16_decode);
     if (nq && q_off[1] != 0) {
-        bt->q_stride = q_off[1];
-        for (uint32_t q = 0; q < nq && bt->q_stride; ++q)
-            if (q_off[q + 1] - q_off[q] != bt->q_stride) bt->q_stride = 0;
+        plan.q_stride = q_off[1];
+        for (uint32_t q = 0; q < nq && plan.q_stride; ++q)
+            if (q_off[q + 1] - q_off[q] != plan.q_stride) plan.q_stride = 0;
     }
-    {   // the number of work items plan_kernel will make (same integer arithmetic): the persistent grids need not be
-        // larger (a single query is a handful of items); with the dense-window kernel every dense query gets the same
-        // number of items (equal document counts)
-        const uint32_t dense_target = std::max(256u, bt->tune.dense_items);
-        bt->dense_c = has_dense ? std::max(1u, (dense_target + n_dense / 2) / std::max(n_dense, 1u)) : 0u;
-        if (has_dense) {
-            // (a few dense queries on a small corpus: no finer than 4096 items in all -- what the rounds before used -- or one item per
-            // 2^16 documents, whichever is more: below that an item is all setup)
-            const uint32_t floor_c = std::max(std::max(1u, 4096u / std::max(n_dense, 1u)), bt->index->n_docs >> 16);
-            if (bt->tune.dense_items == D_TARGET_ITEMS) bt->dense_c = std::min(bt->dense_c, floor_c);
+    // the number of work items plan_kernel will make (same integer arithmetic): the persistent grids need not be larger (a single
+    // query is a handful of items); with the dense-window kernel every dense query gets the same number of items (equal document counts)
+    const uint32_t dense_target = std::max(256u, bt->tune.dense_items);
+    plan.dense_c = plan.has_dense ? std::max(1u, (dense_target + n_dense / 2) / std::max(n_dense, 1u)) : 0u;
+    if (plan.has_dense) {
+        // (a few dense queries on a small corpus: no finer than 4096 items in all -- what the rounds before used -- or one item per
+        // 2^16 documents, whichever is more: below that an item is all setup)
+        const uint32_t floor_c = std::max(std::max(1u, 4096u / std::max(n_dense, 1u)), ixh->n_docs >> 16);
+        if (bt->tune.dense_items == D_TARGET_ITEMS) plan.dense_c = std::min(plan.dense_c, floor_c);
+    }
+    unsigned long long sparse_postings = 0;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (!(plan.dense_c && dense[q])) sparse_postings += q_postings[q];
+    unsigned long long chunk = (sparse_postings + bt->target_items - 1) / bt->target_items;
+    if (chunk < bt->min_chunk) chunk = bt->min_chunk;
+    unsigned long long items = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (!q_postings[q]) continue;
+        if (plan.dense_c && dense[q]) {
+            items += std::min(plan.dense_c, ixh->n_docs);
+            continue;
         }
-        unsigned long long sparse_postings = 0;
-        for (uint32_t q = 0; q < nq; ++q)
-            if (!(bt->dense_c && dense[q])) sparse_postings += q_postings[q];
-        unsigned long long chunk = (sparse_postings + bt->target_items - 1) / bt->target_items;
-        if (chunk < bt->min_chunk) chunk = bt->min_chunk;
-        unsigned long long items = 0;
-        for (uint32_t q = 0; q < nq; ++q) {
-            if (!q_postings[q]) continue;
-            if (bt->dense_c && dense[q]) {
-                items += std::min(bt->dense_c, bt->index->n_docs);
-                continue;
-            }
-            unsigned long long c = (q_postings[q] + chunk / 2) / chunk;
-            if (c == 0) c = 1;
-            if (c > bt->index->n_docs) c = bt->index->n_docs;
-            items += c;
-        }
-        bt->range_grid = uint32_t(std::min<unsigned long long>(std::max<unsigned long long>(items, 1), std::max(1u, bt->tune.range_grid)));
-        bt->dense_grid = uint32_t(std::min<unsigned long long>(std::max<unsigned long long>(items, 1), std::max(1u, bt->tune.dense_grid)));
+        unsigned long long c = (q_postings[q] + chunk / 2) / chunk;
+        if (c == 0) c = 1;
+        if (c > ixh->n_docs) c = ixh->n_docs;
+        items += c;
+    }
+    plan.range_grid = uint32_t(std::min<unsigned long long>(std::max<unsigned long long>(items, 1), std::max(1u, bt->tune.range_grid)));
+    plan.dense_grid = uint32_t(std::min<unsigned long long>(std::max<unsigned long long>(items, 1), std::max(1u, bt->tune.dense_grid)));
 #ifdef VBM25_PROFILE
-        bt->range_grid = std::min<uint32_t>(bt->range_grid, R_GRID);  // (the phase counters are sized for R_GRID workgroups)
+    plan.range_grid = std::min<uint32_t>(plan.range_grid, R_GRID);  // (the phase counters are sized for R_GRID workgroups)
 #endif
+}
+
+// The decided query set to the batch: the scratch plane, then the descriptors -- staged in pinned memory (fast) or copied to the
+// separate device buffers -- and the plan last.  A failure on the way leaves a half-committed set: the caller clears it.
+static int commit_queries(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, bool fast, const QueryPlan &plan) {
+    if (int rc = use_device(bt->index->device)) return rc;
+    if (plan.route == Route::Exhaustive) {
+        bt->h_terms.assign(term_ids, term_ids + q_off[nq]);
+        bt->h_off.assign(q_off, q_off + nq + 1);
+    } else {
+        if (plan.id16_decode) {  // (the scratch plane grows with the largest batch it has held)
+            const size_t need = 256ull * plan.id16_blocks + 1024;
+            if (need > bt->id16_tmp.bytes) {
+                if (bt->last_stream || bt->lat_stream) HIP_TRY(hipDeviceSynchronize());  // (a run still reading the old plane)
+                if (bt->id16_tmp.p) HIP_TRY(hipFree(bt->id16_tmp.p));
+                bt->id16_tmp.p = nullptr;
+                bt->id16_tmp.bytes = 0;
+                if (int rc = bt->id16_tmp.alloc(need + need / 4)) return rc;
+                HIP_TRY(hipMemset(bt->id16_tmp.p, 0, bt->id16_tmp.bytes));
+            }
+            if (!fast && q_off[nq]) HIP_TRY(hipMemcpy(bt->id16_fb.p, bt->h_id16_fb.data(), 4ull * q_off[nq], hipMemcpyHostToDevice));
+        }
+        const StagedLayout &L = plan.staged;
+        // (the fast path stages the item order with the queries and copies it on the batch's own stream: upload_staged)
+        if (!fast && L.id16 > L.order) HIP_TRY(hipMemcpy(bt->item_order.p, bt->h_order.data(), L.id16 - L.order, hipMemcpyHostToDevice));
+        if (fast) {
+            // staged in pinned memory.  One-launch route with fused_pinned: the kernel reads the queries from there and writes the hits
+            // into the pinned output buffer -- no copy is enqueued at all.  The other routes: copied on the batch's own stream,
+            // nothing waits here.
+            if (int rc = pinned_fit(bt->pin_in, bt->pin_in_bytes, L.end)) return rc;
+            if (int rc = pinned_fit(bt->pin_out, bt->pin_out_bytes, pin_out_records(nq) + sizeof(vbm25_hit) * size_t(nq) * bt->k)) return rc;
+            if (!bt->lat_stream) HIP_TRY(hipStreamCreateWithFlags(&bt->lat_stream, hipStreamNonBlocking));
+            if (L.off) std::memcpy(bt->pin_in, term_ids, L.off);
+            std::memcpy(bt->pin_in + L.off, q_off, L.dense - L.off);
+            if (nq) std::memcpy(bt->pin_in + L.dense, bt->h_dense.data(), nq);
+            if (L.id16 > L.order) std::memcpy(bt->pin_in + L.order, bt->h_order.data(), L.id16 - L.order);
+            if (L.end > L.id16) std::memcpy(bt->pin_in + L.id16, bt->h_id16_fb.data(), L.end - L.id16);
+            if (!(plan.route == Route::OneLaunch && plan.fused_pinned))
+                if (int rc = upload_staged(bt, L)) return rc;
+        } else {
+            bt->qin_live = false;
+            if (q_off[nq]) HIP_TRY(hipMemcpy(bt->term_ids.p, term_ids, 4ull * q_off[nq], hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(bt->q_off.p, q_off, 4ull * (nq + 1), hipMemcpyHostToDevice));
+            if (nq) HIP_TRY(hipMemcpy(bt->q_dense.p, bt->h_dense.data(), nq, hipMemcpyHostToDevice));
+        }
+        bt->win_nofuse = false;
     }
+    bt->nq = nq;
+    bt->plan = plan;
     return VBM25_OK;
 }
 
+static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, bool fast) {
+    if (!bt || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!term_ids && nq && q_off[nq] != 0) return set_error(VBM25_ERR_INVALID, "term_ids is NULL but the queries have terms");
+    if (nq > bt->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the batch capacity %u", nq, bt->max_queries);
+    if (q_off[0] != 0) return set_error(VBM25_ERR_INVALID, "q_off[0] must be 0");
+    QueryPlan plan;
+    bool many = false;
+    uint32_t n_dense = 0;
+    // Routing: scan_range_kernel is built for sparse queries; a query with many postings per document (Zipf head terms)
+    // takes the dense-window kernel, one with more than 16 indexed terms scan_many_kernel.  (The scratch vectors were
+    // sized when the batch was created: nothing is allocated here.)
+    const unsigned long long dense_x1000 = (unsigned long long)std::max(0ll, bt->tune.dense_x1000);
+    uint8_t *dense = bt->h_dense.data();
+    unsigned long long *q_postings = bt->h_postings.data();
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (q_off[q + 1] < q_off[q]) return set_error(VBM25_ERR_INVALID, "q_off not monotone at query %u", q);
+        uint32_t valid = 0;
+        unsigned long long postings = 0;
+        for (uint32_t p = q_off[q]; p < q_off[q + 1]; ++p) {
+            if (p > q_off[q] && term_ids[p] <= term_ids[p - 1])  // Query::checked_new, vector.rs:106-110
+                return set_error(VBM25_ERR_INVALID, "query %u: term ids must be strictly ascending", q);
+            valid += term_ids[p] < bt->index->n_terms;
+            if (term_ids[p] < bt->index->n_terms) postings += bt->index->term_df_host[term_ids[p]];
+        }
+        q_postings[q] = postings;
+        dense[q] = 0;
+        if (postings * 1000ull >= dense_x1000 * bt->index->n_docs) {
+            dense[q] = 1;
+            many = true;
+            n_dense += postings != 0;
+        }
+        if (bt->use_range) {  // sparse queries of <= 16 terms: scan_range_kernel; dense ones: scan_dense_kernel; the rest: scan_many_kernel
+            many |= valid > 16u;
+            plan.has_dense |= bt->use_dense && dense[q] && valid <= (uint32_t)D_T;
+            if (!dense[q] && valid <= 16u) plan.range_mt = std::max(plan.range_mt, valid);
+        } else {
+            many = true;
+        }
+        if (valid > MAX_TERMS)
+            return set_error(VBM25_ERR_UNSUPPORTED, "query %u has %u indexed terms; the GPU path handles up to %d", q, valid, MAX_TERMS);
+    }
+    if (q_off[nq] > bt->max_terms) return set_error(VBM25_ERR_INVALID, "%u terms exceed the batch capacity %u", q_off[nq], bt->max_terms);
+    if (bt->bigk) plan.route = Route::Exhaustive;
+    else plan_route(bt, term_ids, q_off, nq, fast, many, n_dense, plan);
+    return commit_queries(bt, term_ids, q_off, nq, fast, plan);
+}
 
 // The batch holds no queries: run enqueues nothing, fetch writes nothing.  What a failed set_queries leaves (include/vbm25.h) -- also
-// when it failed after committing part of the new set (its count and route, an allocation, a copy): the next run must not launch on
-// a mix of the old query set's descriptors and the new one's count.  Filter and growing segment stay attached.
+// when it failed after committing part of the new set (an allocation, a copy): the next run must not launch on a mix of the old query
+// set's descriptors and the new one's count.  Filter and growing segment stay attached.
 static void batch_clear_queries(vbm25_batch *bt) {
     bt->nq = 0;
-    bt->n_term_pos = 0;
-    bt->fused_g = 0;
-    bt->arith_g = 0;
-    bt->win_g = 0;
-    bt->win_len = 0;
-    bt->win_skew = false;
-    bt->id16_decode = false;
-    bt->pin_id16_bytes = 0;
-    bt->need_many = true;
-    bt->has_dense = false;
+    bt->plan = QueryPlan{};
     bt->qin_live = false;
-    bt->fused_pinned = false;
     bt->win_nofuse = false;
     bt->win_fused_run = false;
 }
@@ -1209,47 +1222,57 @@ static int vbm25_batch_set_queries_impl(vbm25_batch *bt, const uint32_t *term_id
     return rc;
 }
 
-static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
-    if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
-    if (!bt->nq) return VBM25_OK;
-    if (int rc = use_device(bt->index->device)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    bt->last_stream = st;
-    bt->win_fused_run = false;
-    bt->download_enqueued = false;
-    bt->results_pinned_now = false;
-    if (bt->index->n_docs == 0) {  // empty sealed segment: no hits (the growing segment is the shim's, search.rs:83-135)
-        HIP_TRY(hipMemsetAsync(bt->n_hits.p, 0, 4ull * bt->nq, st));
-        return VBM25_OK;
+// The per-launch state the routes without plan_kernel need zero -- threshold, histogram, counters and, beyond the one-launch route,
+// the give-up flags and list counts -- unless the last run left it so.  Those routes leave it zero themselves, but only a run that was
+// enqueued completely counts: the flag is cleared before anything is enqueued and set at the very end (an error return in between, or
+// a run on the general route, forces the memsets next time).  Consecutive runs of one batch must use one stream.
+static int reset_launch_state(vbm25_batch *bt, hipStream_t st, bool one_launch) {
+    const bool clean = bt->state_clean;
+    bt->state_clean = false;
+    if (clean) return VBM25_OK;
+    HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->max_queries, st));
+    HIP_TRY(hipMemsetAsync(bt->theta.p, 0, 8ull * bt->max_queries, st));
+    HIP_TRY(hipMemsetAsync(bt->work_ctr.p, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(bt->fused_state.p, 0, 4ull * (bt->max_queries + 1), st));
+    if (one_launch) return VBM25_OK;
+    HIP_TRY(hipMemsetAsync(bt->fail_any.p, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(bt->item_failed.p, 0, 4ull * bt->max_items, st));
+    HIP_TRY(hipMemsetAsync(bt->res_cnt.p, 0, 4ull * bt->max_items * bt->lpi, st));
+    return VBM25_OK;
+}
+
+// timing on: the batch's next event pair, the first one recorded on st now; e1 is the second, for the caller to record where the timed
+// region ends (nullptr with timing off)
+static int take_events(vbm25_batch *bt, hipStream_t st, hipEvent_t &e1) {
+    e1 = nullptr;
+    if (!bt->timing) return VBM25_OK;
+    if (bt->events_used == bt->events.size()) {
+        hipEvent_t a = nullptr, b = nullptr;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        bt->events.emplace_back(a, b);
     }
-    if (bt->bigk) {
-        const DevIndex &dix = bt->index->dev;
-        const uint32_t n = bt->index->n_docs;
-        for (uint32_t q = 0; q < bt->nq; ++q) {
-            HIP_TRY(hipMemsetAsync(bt->bk_acc.p, 0, 8ull * n, st));
-            for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p) {
-                const uint32_t t = bt->h_terms[p];
-                if (t >= bt->index->n_terms) continue;  // search.rs:59-61
-                const uint32_t nb = (bt->index->term_df_host[t] + 127) / 128;
-                bigk_accum_kernel<<<std::min<uint32_t>((nb + 3) / 4, 4096u), 256, 0, st>>>(dix, t, bt->bk_acc.as<double>());
-            }
-            if (bt->filt_on && bt->h_filt_sel[q] != UINT32_MAX)
-                bigk_mask_kernel<<<std::min<uint32_t>((n + 255) / 256, 4096u), 256, 0, st>>>(
-                    bt->filter->bits.as<unsigned long long>() + size_t(bt->h_filt_sel[q]) * bt->filter->words, n, bt->bk_acc.as<double>());
-            size_t tmp = bt->bk_tmp_bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(bt->bk_tmp.p, tmp, bt->bk_acc.as<unsigned long long>(),
-                                                                  bt->bk_keys.as<unsigned long long>(), bt->bk_iota.as<uint32_t>(),
-                                                                  bt->bk_docs.as<uint32_t>(), (int)n, 0, 64, st));
-            bigk_emit_kernel<<<(bt->k + 255) / 256, 256, 0, st>>>(dix, bt->bk_keys.as<unsigned long long>(), bt->bk_docs.as<uint32_t>(), n,
-                                                                  bt->k, bt->hits.as<vbm25_hit>() + size_t(q) * bt->k,
-                                                                  bt->n_hits.as<uint32_t>() + q);
-        }
-        HIP_TRY(hipGetLastError());
-        return VBM25_OK;
-    }
+    e1 = bt->events[bt->events_used].second;
+    HIP_TRY(hipEventRecord(bt->events[bt->events_used++].first, st));
+    return VBM25_OK;
+}
+
+// The kernels' view of the batch as the general route sees it; the other routes change a few fields
+static DevBatch dev_batch(const vbm25_batch *bt) {
     DevBatch db{};
     db.term_ids = bt->term_ids.as<uint32_t>();
     db.q_off = bt->q_off.as<uint32_t>();
+    db.q_dense = bt->q_dense.as<uint8_t>();
+    db.item_order = bt->item_order.as<uint32_t>();
+    if (bt->qin_live) {  // the staged descriptors: one device block (upload_staged)
+        const StagedLayout &L = bt->plan.staged;
+        uint8_t *qp = bt->qin.as<uint8_t>();
+        db.term_ids = reinterpret_cast<const uint32_t *>(qp);
+        db.q_off = reinterpret_cast<const uint32_t *>(qp + L.off);
+        db.q_dense = qp + L.dense;
+        if (L.id16 > L.order)  // (the host's item order of the routes without plan_kernel, which writes its own into item_order)
+            db.item_order = reinterpret_cast<uint32_t *>(qp + L.order);
+    }
     db.nq = bt->nq;
     db.k = bt->k;
     db.items = bt->items.as<Item>();
@@ -1261,31 +1284,17 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
     db.res_cnt = bt->res_cnt.as<uint32_t>();
     db.hits = bt->hits.as<vbm25_hit>();
     db.n_hits = bt->n_hits.as<uint32_t>();
+    if (bt->results_pinned_now) {
+        db.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
+        db.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + pin_out_records(bt->nq));
+    }
     if (bt->filt_on) {
         db.filt_words = bt->filter->bits.as<unsigned long long>();
         db.filt_sel = bt->filt_sel.as<uint32_t>();
         db.filt_stride = bt->filter->words;
     }
-    bt->results_pinned_now = false;
-    if (bt->pinned_results && !bt->bigk && !bt->fused_g && bt->lat_stream && bt->pin_out && !bt->growing) {
-        const size_t nc = (4ull * bt->nq + 7) & ~size_t(7);  // (set_queries sized pin_out for 8 + nc + the records)
-        db.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
-        db.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + 8 + nc);
-        bt->results_pinned_now = true;
-    }
     db.error_flag = bt->error_flag.as<uint32_t>();
-    db.q_dense = bt->q_dense.as<uint8_t>();
-    if (bt->qin_live) {  // the staged descriptors: one device block (upload_staged)
-        uint8_t *qp = bt->qin.as<uint8_t>();
-        const size_t nt = bt->pin_nt, no = 4ull * (bt->nq + 1), nd8 = (size_t(bt->nq) + 7) & ~size_t(7);
-        db.term_ids = reinterpret_cast<const uint32_t *>(qp);
-        db.q_off = reinterpret_cast<const uint32_t *>(qp + nt);
-        db.q_dense = qp + nt + no;
-    }
     db.item_failed = bt->item_failed.as<uint32_t>();
-    db.item_order = bt->item_order.as<uint32_t>();
-    if (bt->qin_live && bt->pin_order_bytes)  // (the host's item order of the routes without plan_kernel, which writes its own into item_order)
-        db.item_order = reinterpret_cast<uint32_t *>(bt->qin.as<uint8_t>() + bt->pin_nt + 4ull * (bt->nq + 1) + ((size_t(bt->nq) + 7) & ~size_t(7)));
     db.prof = bt->prof.as<unsigned long long>();
     db.hist = bt->hist.as<uint32_t>();
     db.work_ctr = bt->work_ctr.as<uint32_t>();
@@ -1300,208 +1309,209 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
     db.fail_any = bt->fail_any.as<uint32_t>();
     db.q_failed = bt->q_failed.as<uint32_t>();
     db.theta_last = bt->theta_last.as<unsigned long long>();
-    db.many_expected = bt->need_many ? 1u : 0u;
+    db.many_expected = bt->plan.need_many ? 1u : 0u;
     db.merge_clean = 0;
     db.order_on = 0;
-    const bool range = bt->use_range;
-    const DevIndex &ix = bt->index->dev;
     db.fused_state = bt->fused_state.as<uint32_t>();
     db.fused_g = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto take_events = [&]() -> int {
-        if (!bt->timing) return VBM25_OK;
-        if (bt->events_used == bt->events.size()) {
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            bt->events.emplace_back(e0, e1);
+    return db;
+}
+
+// k > 1024: per query, one accumulation launch per term, the filter's mask, a radix sort of the scores, the first k of them
+static int run_exhaustive(vbm25_batch *bt, hipStream_t st) {
+    const DevIndex &dix = bt->index->dev;
+    const uint32_t n = bt->index->n_docs;
+    for (uint32_t q = 0; q < bt->nq; ++q) {
+        HIP_TRY(hipMemsetAsync(bt->bk_acc.p, 0, 8ull * n, st));
+        for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p) {
+            const uint32_t t = bt->h_terms[p];
+            if (t >= bt->index->n_terms) continue;  // search.rs:59-61
+            const uint32_t nb = (bt->index->term_df_host[t] + 127) / 128;
+            bigk_accum_kernel<<<std::min<uint32_t>((nb + 3) / 4, 4096u), 256, 0, st>>>(dix, t, bt->bk_acc.as<double>());
         }
-        e0 = bt->events[bt->events_used].first;
-        e1 = bt->events[bt->events_used].second;
-        bt->events_used++;
-        HIP_TRY(hipEventRecord(e0, st));
-        return VBM25_OK;
-    };
-    if (bt->fused_g && bt->range_rt) {
-        // The one-launch route needs threshold, histogram and counters zero; it leaves them so itself -- but only a run
-        // that was enqueued completely counts: the flag is cleared before anything is enqueued and set at the very end
-        // (an error return in between, or a run on the general route, forces the memsets next time).  Consecutive runs
-        // of one batch must use one stream.
-        const bool clean = bt->state_clean;
-        bt->state_clean = false;
-        if (!clean) {
-            HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->max_queries, st));
-            HIP_TRY(hipMemsetAsync(bt->theta.p, 0, 8ull * bt->max_queries, st));
-            HIP_TRY(hipMemsetAsync(bt->work_ctr.p, 0, 8, st));
-            HIP_TRY(hipMemsetAsync(bt->fused_state.p, 0, 4ull * (bt->max_queries + 1), st));
-        }
-        db.fused_g = bt->fused_g;
-        db.dense_on = 0;
-        if (bt->fused_pinned) {  // queries read from, hits written to pinned host memory
-            const size_t nc = (4ull * bt->nq + 7) & ~size_t(7);
-            db.term_ids = reinterpret_cast<const uint32_t *>(bt->pin_in);
-            db.q_off = reinterpret_cast<const uint32_t *>(bt->pin_in + bt->pin_nt);
-            db.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
-            db.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + 8 + nc);
-        }
-        if (int rc = take_events()) return rc;
-        const uint32_t fgrid = std::min<uint32_t>(bt->nq * bt->fused_g, R_GRID);
-        const int rcf = dispatch_k(bt->k, [&](auto kmax) {
-            constexpr int KM = decltype(kmax)::value;
-            if constexpr (KM <= REG_K) {
-                if (bt->range_rt == 8) scan_range_kernel<KM, 8, true><<<fgrid, RWG, 0, st>>>(ix, db);
-                else scan_range_kernel<KM, 16, true><<<fgrid, RWG, 0, st>>>(ix, db);
-                if (!bt->fused_pinned) {
-                    // an item the kernel gave up (rare) is redone by scan_many_kernel and its query merged by merge_kernel;
-                    // both find nothing to do otherwise.  (The pinned flavour leaves that to the host: it re-runs the batch.)
-                    scan_many_kernel<KM><<<std::min<uint32_t>(bt->nq * bt->fused_g, TARGET_ITEMS), WG, 0, st>>>(ix, db);
-                    if (bt->timing) (void)hipEventRecord(e1, st);
-                    DevBatch dm = db;
-                    dm.merge_marked = 1;
-                    merge_kernel<KM><<<bt->nq, 64, 0, st>>>(ix, dm);
-                } else if (bt->timing) {
-                    (void)hipEventRecord(e1, st);
-                }
-            }
-            return int(VBM25_OK);
-        });
-        if (rcf) return rcf;
-        HIP_TRY(hipGetLastError());
-        bt->state_clean = true;
-        return VBM25_OK;
+        if (bt->filt_on && bt->h_filt_sel[q] != UINT32_MAX)
+            bigk_mask_kernel<<<std::min<uint32_t>((n + 255) / 256, 4096u), 256, 0, st>>>(
+                bt->filter->bits.as<unsigned long long>() + size_t(bt->h_filt_sel[q]) * bt->filter->words, n, bt->bk_acc.as<double>());
+        size_t tmp = bt->bk_tmp_bytes;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(bt->bk_tmp.p, tmp, bt->bk_acc.as<unsigned long long>(),
+                                                              bt->bk_keys.as<unsigned long long>(), bt->bk_iota.as<uint32_t>(),
+                                                              bt->bk_docs.as<uint32_t>(), (int)n, 0, 64, st));
+        bigk_emit_kernel<<<(bt->k + 255) / 256, 256, 0, st>>>(dix, bt->bk_keys.as<unsigned long long>(), bt->bk_docs.as<uint32_t>(), n,
+                                                              bt->k, bt->hits.as<vbm25_hit>() + size_t(q) * bt->k,
+                                                              bt->n_hits.as<uint32_t>() + q);
     }
-    if (bt->win_g && bt->k <= scan_win_max_k(bt->win_mt)) {
-        // Every query sparse, <= 8 terms of comparable length: scan_win_kernel (its waves make their work items themselves), then as
-        // on the route below: scan_many_kernel leaves at once unless an item was given up, merge_kernel merges and cleans.
-        const bool clean = bt->state_clean;
-        bt->state_clean = false;
-        if (!clean) {
-            HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->max_queries, st));
-            HIP_TRY(hipMemsetAsync(bt->theta.p, 0, 8ull * bt->max_queries, st));
-            HIP_TRY(hipMemsetAsync(bt->work_ctr.p, 0, 8, st));
-            HIP_TRY(hipMemsetAsync(bt->fused_state.p, 0, 4ull * (bt->max_queries + 1), st));
-            HIP_TRY(hipMemsetAsync(bt->fail_any.p, 0, 4, st));
-            HIP_TRY(hipMemsetAsync(bt->item_failed.p, 0, 4ull * bt->max_items, st));
-            HIP_TRY(hipMemsetAsync(bt->res_cnt.p, 0, 4ull * bt->max_items * bt->lpi, st));
-        }
-        db.fused_g = bt->win_g;  // (merge_kernel: a query's lists are those of its win_g items)
-        db.win_g = bt->win_g;
-        {
-            // a query's items: runs of windows of decreasing length (weights g + 1, g, ..., 2), handed out longest first -- the
-            // last items drawn, which decide when the launch ends, are the short ones.  Equal runs when a run would exceed the
-            // 63 windows an item can hold, or with more than 16 items per query.
-            const uint32_t gq = bt->win_g, nwin = bt->index->n_win;
-            std::memset(db.win_cut, 0, sizeof db.win_cut);
-            if (bt->win_skew) {  // (the three kinds of waves: 59 / 52 / 42 of C3's 153 windows: the third wave of a SIMD takes 1.5 times the first one's time per window)
-                db.win_cut[0] = 0;
-                db.win_cut[1] = uint32_t(uint64_t(nwin) * uint32_t(bt->tune.win_cut1) / 1000u);
-                db.win_cut[2] = uint32_t(uint64_t(nwin) * uint32_t(bt->tune.win_cut2) / 1000u);
-                db.win_cut[3] = nwin;
-                if (db.win_cut[1] > 63u || db.win_cut[2] - db.win_cut[1] > 63u || nwin - db.win_cut[2] > 63u) std::memset(db.win_cut, 0, sizeof db.win_cut);
-            } else if (gq <= 16u && bt->win_len && uint64_t(bt->win_len) * (gq - 1u) < nwin) {
-                // runs of win_len windows and a shorter rest (set_queries: every resident wave the same share of the windows)
-                for (uint32_t p = 0; p < gq; ++p) db.win_cut[p] = bt->win_len * p;
-                db.win_cut[gq] = nwin;
+    HIP_TRY(hipGetLastError());
+    return VBM25_OK;
+}
+
+// A handful of sparse queries (vbm25_search_batch): ONE launch -- scan_range_kernel plans, scans and merges, and leaves threshold,
+// histogram and counters zero
+static int run_one_launch(vbm25_batch *bt, hipStream_t st, DevBatch db) {
+    const QueryPlan &plan = bt->plan;
+    const DevIndex &ix = bt->index->dev;
+    if (int rc = reset_launch_state(bt, st, true)) return rc;
+    db.fused_g = plan.g;
+    db.dense_on = 0;
+    if (plan.fused_pinned) {  // queries read from, hits written to pinned host memory
+        db.term_ids = reinterpret_cast<const uint32_t *>(bt->pin_in);
+        db.q_off = reinterpret_cast<const uint32_t *>(bt->pin_in + plan.staged.off);
+        db.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
+        db.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + pin_out_records(bt->nq));
+    }
+    hipEvent_t e1;
+    if (int rc = take_events(bt, st, e1)) return rc;
+    const uint32_t fgrid = std::min<uint32_t>(bt->nq * plan.g, R_GRID);
+    const int rcf = dispatch_k(bt->k, [&](auto kmax) {
+        constexpr int KM = decltype(kmax)::value;
+        if constexpr (KM <= REG_K) {
+            if (plan.range_rt() == 8) scan_range_kernel<KM, 8, true><<<fgrid, RWG, 0, st>>>(ix, db);
+            else scan_range_kernel<KM, 16, true><<<fgrid, RWG, 0, st>>>(ix, db);
+            if (!plan.fused_pinned) {
+                // an item the kernel gave up (rare) is redone by scan_many_kernel and its query merged by merge_kernel;
+                // both find nothing to do otherwise.  (The pinned flavour leaves that to the host: rerun_and_fetch.)
+                scan_many_kernel<KM><<<std::min<uint32_t>(bt->nq * plan.g, TARGET_ITEMS), WG, 0, st>>>(ix, db);
+                if (bt->timing) (void)hipEventRecord(e1, st);
+                DevBatch dm = db;
+                dm.merge_marked = 1;
+                merge_kernel<KM><<<bt->nq, 64, 0, st>>>(ix, dm);
+            } else if (bt->timing) {
+                (void)hipEventRecord(e1, st);
             }
         }
-        db.lpi = 1;
-        db.hist = nullptr;       // (this kernel keeps no histogram of accepted documents: merge_kernel has none to clean)
-        db.dense_on = 0;
-        db.many_expected = 0;
-        db.merge_clean = 1;
-        // (2: the skewed layout of queries in the caller's order is computed by the kernel itself, nobody loads item_order)
-        db.order_on = bt->order_useful ? (bt->win_skew && bt->order_identity && bt->tune.win_order_arith ? 2u : 1u) : 0u;
-        db.q_stride = bt->q_stride;
-        if (int rc = take_events()) return rc;
-        const uint32_t wmt = bt->range_rt == 8 ? bt->win_mt : 8u, wpw = scan_win_wg(wmt, bt->k);
-        const uint32_t wgrid = std::min<uint32_t>((bt->nq * bt->win_g + wpw - 1u) / wpw, bt->tune.win_grid ? bt->tune.win_grid : scan_win_resident_waves(wmt, bt->k) / wpw);
-        // One launch (round 6): the wave that finishes a query's last item merges the query's lists, writes its records and leaves
-        // the per-launch state zero.  A query with an item the kernel gave up comes back with the count NONE32: whoever hands the
-        // records to the caller (vbm25_batch_fetch_impl) re-runs the batch with scan_many_kernel and merge_kernel behind the scan.
-        // (only when every wave has at most one item: the kernel's merge sits behind its item loop)
-        const bool fuse = bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && !bt->growing && uint64_t(bt->nq) * bt->win_g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
-        db.win_fuse = fuse ? 1u : 0u;
-        bt->win_fused_run = fuse;
-        if (bt->id16_decode) {
-            // An index without the post_id16 plane: the ids of the batch's terms, unpacked from the blob into the batch's scratch
-            // plane (decode_id16.h) -- inside the timed region: kernel_ms is the decode and the scan.
-            db.id16_fb = bt->id16_fb.as<uint32_t>();
-            if (bt->qin_live && bt->pin_id16_bytes)
-                db.id16_fb = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + bt->pin_nt + 4ull * (bt->nq + 1) + ((size_t(bt->nq) + 7) & ~size_t(7)) + bt->pin_order_bytes);
-            const uint32_t n_pos = bt->n_term_pos;
-            if (n_pos) decode_id16_kernel<<<n_pos, DI_WAVES * 64, 0, st>>>(ix, db.term_ids, db.id16_fb, bt->id16_tmp.as<uint32_t>());
-            DevIndex ixw = ix;
-            ixw.post_id16 = bt->id16_tmp.as<uint32_t>();
-            HIP_TRY(scan_win_launch(ixw, db, wmt, wgrid, st));
-        } else
-        HIP_TRY(scan_win_launch(ix, db, wmt, wgrid, st));
-        if (fuse) {
+        return int(VBM25_OK);
+    });
+    if (rcf) return rcf;
+    HIP_TRY(hipGetLastError());
+    bt->state_clean = true;
+    return VBM25_OK;
+}
+
+// Every query sparse, <= 8 terms of comparable length: scan_win_kernel (its waves make their work items themselves), then as on the
+// plan-free route: scan_many_kernel leaves at once unless an item was given up, merge_kernel merges and cleans.
+static int run_window(vbm25_batch *bt, hipStream_t st, DevBatch db) {
+    const QueryPlan &plan = bt->plan;
+    const DevIndex &ix = bt->index->dev;
+    if (int rc = reset_launch_state(bt, st, false)) return rc;
+    db.fused_g = plan.g;  // (merge_kernel: a query's lists are those of its g items)
+    db.win_g = plan.g;
+    {
+        // a query's items: runs of windows of decreasing length (weights g + 1, g, ..., 2), handed out longest first -- the
+        // last items drawn, which decide when the launch ends, are the short ones.  Equal runs when a run would exceed the
+        // 63 windows an item can hold, or with more than 16 items per query.
+        const uint32_t gq = plan.g, nwin = bt->index->n_win;
+        std::memset(db.win_cut, 0, sizeof db.win_cut);
+        if (plan.win_skew) {  // (the three kinds of waves: 59 / 52 / 42 of C3's 153 windows: the third wave of a SIMD takes 1.5 times the first one's time per window)
+            db.win_cut[0] = 0;
+            db.win_cut[1] = uint32_t(uint64_t(nwin) * uint32_t(bt->tune.win_cut1) / 1000u);
+            db.win_cut[2] = uint32_t(uint64_t(nwin) * uint32_t(bt->tune.win_cut2) / 1000u);
+            db.win_cut[3] = nwin;
+            if (db.win_cut[1] > 63u || db.win_cut[2] - db.win_cut[1] > 63u || nwin - db.win_cut[2] > 63u) std::memset(db.win_cut, 0, sizeof db.win_cut);
+        } else if (gq <= 16u && plan.win_len && uint64_t(plan.win_len) * (gq - 1u) < nwin) {
+            // runs of win_len windows and a shorter rest (plan_route: every resident wave the same share of the windows)
+            for (uint32_t p = 0; p < gq; ++p) db.win_cut[p] = plan.win_len * p;
+            db.win_cut[gq] = nwin;
+        }
+    }
+    db.lpi = 1;
+    db.hist = nullptr;       // (this kernel keeps no histogram of accepted documents: merge_kernel has none to clean)
+    db.dense_on = 0;
+    db.many_expected = 0;
+    db.merge_clean = 1;
+    // (2: the skewed layout of queries in the caller's order is computed by the kernel itself, nobody loads item_order)
+    db.order_on = plan.order_useful ? (plan.win_skew && plan.order_identity && bt->tune.win_order_arith ? 2u : 1u) : 0u;
+    db.q_stride = plan.q_stride;
+    hipEvent_t e1;
+    if (int rc = take_events(bt, st, e1)) return rc;
+    const uint32_t wmt = std::min(plan.range_mt, 8u), wpw = scan_win_wg(wmt, bt->k);
+    const uint32_t wgrid = std::min<uint32_t>((bt->nq * plan.g + wpw - 1u) / wpw, bt->tune.win_grid ? bt->tune.win_grid : scan_win_resident_waves(wmt, bt->k) / wpw);
+    // One launch (round 6): the wave that finishes a query's last item merges the query's lists, writes its records and leaves
+    // the per-launch state zero.  A query with an item the kernel gave up comes back with the count NONE32: whoever hands the
+    // records to the caller (vbm25_batch_fetch_impl) re-runs the batch with scan_many_kernel and merge_kernel behind the scan.
+    // (only when every wave has at most one item: the kernel's merge sits behind its item loop)
+    const bool fuse = bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && !bt->growing && uint64_t(bt->nq) * plan.g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
+    db.win_fuse = fuse ? 1u : 0u;
+    bt->win_fused_run = fuse;
+    if (plan.id16_decode) {
+        // An index without the post_id16 plane: the ids of the batch's terms, unpacked from the blob into the batch's scratch
+        // plane (decode_id16.h) -- inside the timed region: kernel_ms is the decode and the scan.
+        const StagedLayout &L = plan.staged;
+        db.id16_fb = bt->id16_fb.as<uint32_t>();
+        if (bt->qin_live && L.end > L.id16) db.id16_fb = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + L.id16);
+        if (plan.n_term_pos) decode_id16_kernel<<<plan.n_term_pos, DI_WAVES * 64, 0, st>>>(ix, db.term_ids, db.id16_fb, bt->id16_tmp.as<uint32_t>());
+        DevIndex ixw = ix;
+        ixw.post_id16 = bt->id16_tmp.as<uint32_t>();
+        HIP_TRY(scan_win_launch(ixw, db, wmt, wgrid, st));
+    } else
+    HIP_TRY(scan_win_launch(ix, db, wmt, wgrid, st));
+    if (fuse) {
+        if (bt->timing) (void)hipEventRecord(e1, st);
+    } else
+    (void)dispatch_k(bt->k, [&](auto kmax) {
+        constexpr int KM = decltype(kmax)::value;
+        if constexpr (KM <= REG_K) {
+            scan_many_kernel<KM><<<64, WG, 0, st>>>(ix, db);
             if (bt->timing) (void)hipEventRecord(e1, st);
-        } else
-        (void)dispatch_k(bt->k, [&](auto kmax) {
-            constexpr int KM = decltype(kmax)::value;
-            if constexpr (KM <= REG_K) {
-                scan_many_kernel<KM><<<64, WG, 0, st>>>(ix, db);
-                if (bt->timing) (void)hipEventRecord(e1, st);
-                merge_kernel<KM><<<bt->nq, 64, 0, st>>>(ix, db);
-            }
-            return int(VBM25_OK);
-        });
-        HIP_TRY(hipGetLastError());
-        bt->state_clean = true;
-        return VBM25_OK;
-    }
-    if (bt->arith_g && bt->range_rt && bt->k <= (uint32_t)REG_K) {
-        // Every query sparse, <= 16 terms: the scan kernel makes the work items itself (no plan_kernel), scan_many_kernel is a
-        // small grid that leaves at once unless an item was given up, merge_kernel merges and leaves the per-launch state zero.
-        const bool clean = bt->state_clean;
-        bt->state_clean = false;
-        if (!clean) {
-            HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->max_queries, st));
-            HIP_TRY(hipMemsetAsync(bt->theta.p, 0, 8ull * bt->max_queries, st));
-            HIP_TRY(hipMemsetAsync(bt->work_ctr.p, 0, 8, st));
-            HIP_TRY(hipMemsetAsync(bt->fused_state.p, 0, 4ull * (bt->max_queries + 1), st));
-            HIP_TRY(hipMemsetAsync(bt->fail_any.p, 0, 4, st));
-            HIP_TRY(hipMemsetAsync(bt->item_failed.p, 0, 4ull * bt->max_items, st));
-            HIP_TRY(hipMemsetAsync(bt->res_cnt.p, 0, 4ull * bt->max_items * bt->lpi, st));
+            merge_kernel<KM><<<bt->nq, 64, 0, st>>>(ix, db);
         }
-        db.fused_g = bt->arith_g;
-        db.dense_on = 0;
-        db.many_expected = 0;
-        db.merge_clean = 1;
-        db.order_on = 1;
-        if (int rc = take_events()) return rc;
-        const uint32_t agrid = std::min<uint32_t>(bt->nq * bt->arith_g, std::max(1u, bt->tune.range_grid));
-        const int rca = dispatch_k(bt->k, [&](auto kmax) {
-            constexpr int KM = decltype(kmax)::value;
-            if constexpr (KM <= REG_K) {
-                if (bt->range_rt == 8) scan_range_kernel<KM, 8><<<agrid, RWG, 0, st>>>(ix, db);
-                else scan_range_kernel<KM, 16><<<agrid, RWG, 0, st>>>(ix, db);
-                scan_many_kernel<KM><<<64, WG, 0, st>>>(ix, db);
-                if (bt->timing) (void)hipEventRecord(e1, st);
-                merge_kernel<KM><<<bt->nq, 64, 0, st>>>(ix, db);
-            }
-            return int(VBM25_OK);
-        });
-        if (rca) return rca;
-        HIP_TRY(hipGetLastError());
-        bt->state_clean = true;
-        return VBM25_OK;
-    }
+        return int(VBM25_OK);
+    });
+    HIP_TRY(hipGetLastError());
+    bt->state_clean = true;
+    return VBM25_OK;
+}
+
+// Every query sparse, <= 16 terms: the scan kernel makes the work items itself (no plan_kernel), scan_many_kernel is a small grid that
+// leaves at once unless an item was given up, merge_kernel merges and leaves the per-launch state zero.
+static int run_plan_free(vbm25_batch *bt, hipStream_t st, DevBatch db) {
+    const QueryPlan &plan = bt->plan;
+    const DevIndex &ix = bt->index->dev;
+    if (int rc = reset_launch_state(bt, st, false)) return rc;
+    db.fused_g = plan.g;
+    db.dense_on = 0;
+    db.many_expected = 0;
+    db.merge_clean = 1;
+    db.order_on = 1;
+    hipEvent_t e1;
+    if (int rc = take_events(bt, st, e1)) return rc;
+    const uint32_t agrid = std::min<uint32_t>(bt->nq * plan.g, std::max(1u, bt->tune.range_grid));
+    const int rca = dispatch_k(bt->k, [&](auto kmax) {
+        constexpr int KM = decltype(kmax)::value;
+        if constexpr (KM <= REG_K) {
+            if (plan.range_rt() == 8) scan_range_kernel<KM, 8><<<agrid, RWG, 0, st>>>(ix, db);
+            else scan_range_kernel<KM, 16><<<agrid, RWG, 0, st>>>(ix, db);
+            scan_many_kernel<KM><<<64, WG, 0, st>>>(ix, db);
+            if (bt->timing) (void)hipEventRecord(e1, st);
+            merge_kernel<KM><<<bt->nq, 64, 0, st>>>(ix, db);
+        }
+        return int(VBM25_OK);
+    });
+    if (rca) return rca;
+    HIP_TRY(hipGetLastError());
+    bt->state_clean = true;
+    return VBM25_OK;
+}
+
+// plan_kernel makes the work items; the sparse, dense and many-term kernels scan them; merge_kernel merges every query's lists
+static int run_general(vbm25_batch *bt, hipStream_t st, const DevBatch &db) {
+    const QueryPlan &plan = bt->plan;
+    const DevIndex &ix = bt->index->dev;
+    const bool range = bt->use_range;
     bt->state_clean = false;
     if (range) HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->nq, st));
-    plan_kernel<<<1, PLAN_WG, 0, st>>>(ix, db, bt->max_items, bt->target_items, bt->min_chunk, bt->dense_c);
-    if (int rc = take_events()) return rc;
+    plan_kernel<<<1, PLAN_WG, 0, st>>>(ix, db, bt->max_items, bt->target_items, bt->min_chunk, plan.dense_c);
+    hipEvent_t e1;
+    if (int rc = take_events(bt, st, e1)) return rc;
     const uint32_t grid = std::min<uint32_t>(bt->max_items, TARGET_ITEMS);
     const int rc = dispatch_k(bt->k, [&](auto kmax) {
         constexpr int KM = decltype(kmax)::value;
         if constexpr (KM <= REG_K) {
             if (range) {  // persistent 8-wave workgroups
-                if (bt->range_rt == 8) scan_range_kernel<KM, 8><<<bt->range_grid, RWG, 0, st>>>(ix, db);
-                else if (bt->range_rt == 16) scan_range_kernel<KM, 16><<<bt->range_grid, RWG, 0, st>>>(ix, db);
+                if (plan.range_rt() == 8) scan_range_kernel<KM, 8><<<plan.range_grid, RWG, 0, st>>>(ix, db);
+                else if (plan.range_rt() == 16) scan_range_kernel<KM, 16><<<plan.range_grid, RWG, 0, st>>>(ix, db);
             }
         }
         if constexpr (KM <= D_KMAX) {
-            if (bt->has_dense) scan_dense_kernel<KM><<<bt->dense_grid, DWG, 0, st>>>(ix, db);
+            if (plan.has_dense) scan_dense_kernel<KM><<<plan.dense_grid, DWG, 0, st>>>(ix, db);
         }
         // many-term queries, every query of 256 < k <= 1024, and items the first-choice kernel gave up on (empty launch: 5 us)
         scan_many_kernel<decltype(kmax)::value><<<grid, WG, 0, st>>>(ix, db);
@@ -1514,20 +1524,65 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
     return VBM25_OK;
 }
 
-static int vbm25_batch_enqueue_download(vbm25_batch *bt);
+static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
+    if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
+    if (!bt->nq) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    bt->last_stream = st;
+    bt->win_fused_run = false;
+    bt->download_enqueued = false;
+    bt->results_pinned_now = false;
+    if (bt->index->n_docs == 0) {  // empty sealed segment: no hits (the growing segment is the shim's, search.rs:83-135)
+        HIP_TRY(hipMemsetAsync(bt->n_hits.p, 0, 4ull * bt->nq, st));
+        return VBM25_OK;
+    }
+    const Route route = bt->plan.route;
+    if (route == Route::Exhaustive) return run_exhaustive(bt, st);
+    bt->results_pinned_now = bt->pinned_results && route != Route::OneLaunch && bt->lat_stream && bt->pin_out && !bt->growing;
+    const DevBatch db = dev_batch(bt);
+    switch (route) {
+    case Route::OneLaunch: return run_one_launch(bt, st, db);
+    case Route::Window: return run_window(bt, st, db);
+    case Route::PlanFree: return run_plan_free(bt, st, db);
+    default: return run_general(bt, st, db);
+    }
+}
+
+// the last run's flag, counts and records to the batch's pinned buffer, behind the run on its private stream (vbm25_search_batch's
+// and vbm25_multi_batch_run's general routes; the one-launch route has written them there itself)
+static int vbm25_batch_enqueue_download(vbm25_batch *bt) {
+    if (bt->bigk || !bt->lat_stream || (bt->plan.route == Route::OneLaunch && bt->plan.fused_pinned)) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    const size_t nh = sizeof(vbm25_hit) * size_t(bt->nq) * bt->k, rec = pin_out_records(bt->nq);
+    if (int rc = pinned_fit(bt->pin_out, bt->pin_out_bytes, rec + nh)) return rc;
+    HIP_TRY(hipMemcpyAsync(bt->pin_out, bt->error_flag.p, 4, hipMemcpyDeviceToHost, bt->lat_stream));
+    if (bt->nq && !bt->results_pinned_now) {
+        HIP_TRY(hipMemcpyAsync(bt->pin_out + 8, bt->n_hits.p, 4ull * bt->nq, hipMemcpyDeviceToHost, bt->lat_stream));
+        HIP_TRY(hipMemcpyAsync(bt->pin_out + rec, bt->hits.p, nh, hipMemcpyDeviceToHost, bt->lat_stream));
+    }
+    bt->download_enqueued = true;
+    return VBM25_OK;
+}
+
 static int vbm25_batch_fetch_impl(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits, bool fast = false);
-// After a one-launch run of scan_win_kernel (win_fuse): a count of NONE32 marks a query with an item the kernel gave up (more second
-// arrivals in a window than its list holds, a term frequency above 255).  The batch is run again with scan_many_kernel and
-// merge_kernel behind the scan -- on the same stream, before any record reaches the caller -- and this query set stays on that route.
-static bool win_marked(const vbm25_batch *bt, const uint32_t *cnt) {
-    if (!bt->win_fused_run) return false;
-    for (uint32_t q = 0; q < bt->nq; ++q)
+static bool any_marked(const uint32_t *cnt, uint32_t nq) {
+    for (uint32_t q = 0; q < nq; ++q)
         if (cnt[q] == UINT32_MAX) return true;
     return false;
 }
-static int win_rerun_and_fetch(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits, bool fast) {
-    bt->win_nofuse = true;
-    bt->state_clean = false;  // (the one-launch run left fail_any set)
+// Records incomplete: a count of NONE32 marks a query with an item a one-launch kernel gave up (scan_win_kernel: more second arrivals in
+// a window than its list holds, a term frequency above 255).  The batch is re-routed and run again on the same stream, before any
+// record reaches the caller.  The pinned one-launch route moves to the general route, whose kernels read the staged block; the
+// one-launch form of scan_win_kernel gets scan_many_kernel and merge_kernel behind it for the rest of this query set.
+static int rerun_and_fetch(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits, bool fast) {
+    if (bt->plan.route == Route::OneLaunch) {
+        bt->plan.route = Route::General;
+        if (int rc = upload_staged(bt, bt->plan.staged)) return rc;
+    } else {
+        bt->win_nofuse = true;
+        bt->state_clean = false;  // (the one-launch run left fail_any set)
+    }
     bt->download_enqueued = false;
     if (int rc = vbm25_batch_run_impl(bt, bt->last_stream)) return rc;
     return vbm25_batch_fetch_impl(bt, hits, n_hits, fast);
@@ -1535,19 +1590,17 @@ static int win_rerun_and_fetch(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hit
 static int vbm25_batch_fetch_impl(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits, bool fast) {
     if (!bt || (!hits && bt->nq) || (!n_hits && bt->nq)) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (int rc = use_device(bt->index->device)) return rc;
-    if (fast && bt->lat_stream && bt->fused_g && bt->fused_pinned) {  // the kernel wrote counts and hits into the pinned buffer: one synchronisation
-        const size_t nh = sizeof(vbm25_hit) * size_t(bt->nq) * bt->k, nc = (4ull * bt->nq + 7) & ~size_t(7);
+    const size_t nh = sizeof(vbm25_hit) * size_t(bt->nq) * bt->k;
+    if (fast && bt->lat_stream && bt->plan.route == Route::OneLaunch && bt->plan.fused_pinned) {
+        // the kernel wrote counts and hits into the pinned buffer: one synchronisation
         HIP_TRY(hipStreamSynchronize(bt->lat_stream));
-        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(bt->pin_out + 8);
-        for (uint32_t q = 0; q < bt->nq; ++q)
-            if (cnt[q] == UINT32_MAX) return VBM25_RETRY_GENERAL;  // an item needs scan_many_kernel
-        std::memcpy(n_hits, cnt, 4ull * bt->nq);
-        std::memcpy(hits, bt->pin_out + 8 + nc, nh);
+        const uint32_t *pin_cnt = reinterpret_cast<const uint32_t *>(bt->pin_out + 8);
+        if (any_marked(pin_cnt, bt->nq)) return rerun_and_fetch(bt, hits, n_hits, fast);  // an item needs scan_many_kernel
+        std::memcpy(n_hits, pin_cnt, 4ull * bt->nq);
+        std::memcpy(hits, bt->pin_out + pin_out_records(bt->nq), nh);
         return VBM25_OK;
     }
     if (fast && bt->lat_stream) {  // flag, counts and hits come down asynchronously; one synchronisation
-        const size_t nh = sizeof(vbm25_hit) * size_t(bt->nq) * bt->k;
-        const size_t nc = bt->results_pinned_now ? (4ull * bt->nq + 7) & ~size_t(7) : 4ull * bt->nq;  // (the kernel's records are 8-byte aligned)
         if (!bt->download_enqueued)
             if (int rc = vbm25_batch_enqueue_download(bt)) return rc;
         bt->download_enqueued = false;
@@ -1559,11 +1612,10 @@ static int vbm25_batch_fetch_impl(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_
             return set_error(VBM25_ERR_DEVICE, "device-side planner overflow (flag %u)", flag);
         }
         if (bt->nq) {
-            if (win_marked(bt, reinterpret_cast<const uint32_t *>(bt->pin_out + 8))) return win_rerun_and_fetch(bt, hits, n_hits, fast);
-            // (nc is the 8-byte aligned OFFSET of the records; the caller's n_hits holds exactly nq counts: copying nc bytes wrote four
-            // bytes past it for an odd nq -- into the next shard's first count on the multi-device route)
-            std::memcpy(n_hits, bt->pin_out + 8, 4ull * bt->nq);
-            std::memcpy(hits, bt->pin_out + 8 + nc, nh);
+            const uint32_t *pin_cnt = reinterpret_cast<const uint32_t *>(bt->pin_out + 8);
+            if (bt->win_fused_run && any_marked(pin_cnt, bt->nq)) return rerun_and_fetch(bt, hits, n_hits, fast);
+            std::memcpy(n_hits, pin_cnt, 4ull * bt->nq);
+            std::memcpy(hits, bt->pin_out + pin_out_records(bt->nq), nh);
         }
         return VBM25_OK;
     }
@@ -1572,7 +1624,7 @@ static int vbm25_batch_fetch_impl(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_
     uint32_t flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, bt->error_flag.p, 4, hipMemcpyDeviceToHost, st));
     if (bt->nq) {
-        HIP_TRY(hipMemcpyAsync(hits, bt->hits.p, sizeof(vbm25_hit) * size_t(bt->nq) * bt->k, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hits, bt->hits.p, nh, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(n_hits, bt->n_hits.p, 4ull * bt->nq, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -1581,28 +1633,7 @@ static int vbm25_batch_fetch_impl(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_
         HIP_TRY(hipStreamSynchronize(st));
         return set_error(VBM25_ERR_DEVICE, "device-side planner overflow (flag %u)", flag);
     }
-    if (bt->nq && win_marked(bt, n_hits)) return win_rerun_and_fetch(bt, hits, n_hits, fast);
-    return VBM25_OK;
-}
-
-// the last run's flag, counts and records to the batch's pinned buffer, behind the run on its private stream (vbm25_search_batch's
-// and vbm25_multi_batch_run's general routes; the one-launch route has written them there itself)
-static int vbm25_batch_enqueue_download(vbm25_batch *bt) {
-    if (bt->bigk || !bt->lat_stream || (bt->fused_g && bt->fused_pinned)) return VBM25_OK;
-    if (int rc = use_device(bt->index->device)) return rc;
-    const size_t nh = sizeof(vbm25_hit) * size_t(bt->nq) * bt->k, nc = 4ull * bt->nq;
-    if (8 + nc + nh > bt->pin_out_bytes) {
-        if (bt->pin_out) HIP_TRY(hipHostFree(bt->pin_out));
-        bt->pin_out = nullptr;
-        bt->pin_out_bytes = 2 * (8 + nc + nh) + 256;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bt->pin_out), bt->pin_out_bytes, hipHostMallocDefault));
-    }
-    HIP_TRY(hipMemcpyAsync(bt->pin_out, bt->error_flag.p, 4, hipMemcpyDeviceToHost, bt->lat_stream));
-    if (bt->nq && !bt->results_pinned_now) {
-        HIP_TRY(hipMemcpyAsync(bt->pin_out + 8, bt->n_hits.p, nc, hipMemcpyDeviceToHost, bt->lat_stream));
-        HIP_TRY(hipMemcpyAsync(bt->pin_out + 8 + nc, bt->hits.p, nh, hipMemcpyDeviceToHost, bt->lat_stream));
-    }
-    bt->download_enqueued = true;
+    if (bt->nq && bt->win_fused_run && any_marked(n_hits, bt->nq)) return rerun_and_fetch(bt, hits, n_hits, fast);
     return VBM25_OK;
 }
 
@@ -1726,14 +1757,17 @@ void vbm25_tuning_reset(void) {
     g_tune.generation = gen;
 }
 
+// the current queries' kernels make their work items themselves and merge_kernel cleans up behind them
+static bool plan_free_kernels(const vbm25_batch *bt) { return bt->plan.route == Route::PlanFree || bt->plan.route == Route::Window; }
+
 // tuning / test aid (not declared in include/vbm25.h): work items of the last run and how many of them the
 // first-choice kernel handed to scan_many_kernel
 int vbm25_batch_debug_counts(vbm25_batch *bt, uint32_t *n_items, uint32_t *n_failed) {
     if (!bt || !n_items || !n_failed) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (int rc = use_device(bt->index->device)) return rc;
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
-    if ((bt->arith_g || bt->win_g) && bt->state_clean) {  // merge_kernel has cleaned the flags and kept the counts per query
-        *n_items = bt->nq * (bt->win_g ? bt->win_g : bt->arith_g);
+    if (plan_free_kernels(bt) && bt->state_clean) {  // merge_kernel has cleaned the flags and kept the counts per query
+        *n_items = bt->nq * bt->plan.g;
         std::vector<uint32_t> qf(bt->nq);
         if (bt->nq) HIP_TRY(hipMemcpy(qf.data(), bt->q_failed.p, 4ull * bt->nq, hipMemcpyDeviceToHost));
         *n_failed = 0;
@@ -1752,7 +1786,7 @@ int vbm25_batch_debug_counts(vbm25_batch *bt, uint32_t *n_items, uint32_t *n_fai
 // 2 plan-free scan_range_kernel, 3 scan_win_kernel, 4 exhaustive k > 1024
 int vbm25_batch_debug_route(vbm25_batch *bt) {
     if (!bt) return -1;
-    return bt->bigk ? 4 : bt->fused_g ? 1 : bt->win_g ? 3 : bt->arith_g ? 2 : 0;
+    return int(bt->bigk ? Route::Exhaustive : bt->plan.route);  // (a k > 1024 batch without queries too)
 }
 
 // test / bench aid (not declared in include/vbm25.h): which kernel the current queries' work goes to.  out[0..2] = queries the host
@@ -1766,7 +1800,7 @@ int vbm25_batch_debug_routes(vbm25_batch *bt, uint32_t *out6) {
     if (int rc = use_device(bt->index->device)) return rc;
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     for (uint32_t q = 0; q < bt->nq; ++q) out6[bt->h_dense[q] ? 1 : 0]++;
-    if (!bt->fused_g && !bt->win_g && !bt->arith_g) {
+    if (bt->plan.route == Route::General) {
         uint32_t n = 0;
         HIP_TRY(hipMemcpy(&n, bt->n_items.p, 4, hipMemcpyDeviceToHost));
         n = std::min(n, bt->max_items);
@@ -1783,7 +1817,7 @@ int vbm25_batch_debug_routes(vbm25_batch *bt, uint32_t *out6) {
 // test aid (not declared in include/vbm25.h): launches of the last run's scan -- 1: scan_win_kernel merged the queries' lists itself
 // (win_fuse), 3: scan_win_kernel, scan_many_kernel, merge_kernel (also after a one-launch run that marked a query), 0: another route
 int vbm25_batch_debug_win_launches(vbm25_batch *bt) {
-    if (!bt || !bt->win_g) return 0;
+    if (!bt || bt->plan.route != Route::Window) return 0;
     return bt->win_fused_run ? 1 : 3;
 }
 
@@ -1809,7 +1843,7 @@ int vbm25_batch_debug_theta(vbm25_batch *bt, unsigned long long *out) {
     if (int rc = use_device(bt->index->device)) return rc;
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     if (bt->nq && bt->theta.p)
-        HIP_TRY(hipMemcpy(out, (bt->arith_g || bt->win_g) && bt->state_clean ? bt->theta_last.p : bt->theta.p, 8ull * bt->nq, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, plan_free_kernels(bt) && bt->state_clean ? bt->theta_last.p : bt->theta.p, 8ull * bt->nq, hipMemcpyDeviceToHost));
     return VBM25_OK;
 }
 
@@ -1845,31 +1879,32 @@ int vbm25_batch_profile(vbm25_batch *bt, unsigned long long *out, uint32_t n_wor
 }
 #endif
 
+// The index's batch object for the one-shot entry points (slot: vbm25_search_batch's or the growing ones'), re-used while the shape
+// and the tuning switches fit: device buffers of a batch are far more expensive to create than a search.  pinned_results: host
+// buffers in, host buffers out -- nobody reads the batch's records on the device.
+static int scratch_batch(vbm25_index *ix, vbm25_batch *vbm25_index::*slot, bool pinned_results, uint32_t nq, const uint32_t *q_off,
+                         uint32_t k, vbm25_batch **out) {
+    vbm25_batch *&bt = ix->*slot;
+    const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
+    if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
+        if (bt) vbm25_batch_destroy(bt);
+        if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;  // (the slot is empty then)
+        bt->pinned_results = pinned_results;
+    }
+    *out = bt;
+    return VBM25_OK;
+}
+
 static int vbm25_search_batch_impl(vbm25_index *ix, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq,
                        uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
     if (!ix || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
-    // the index keeps one batch object for this convenience entry point and re-uses it while
-    // the shape fits (device buffers of a batch are far more expensive to create than a search)
-    vbm25_batch *bt = ix->scratch;
-    const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
-    if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
-        if (bt) vbm25_batch_destroy(bt);
-        ix->scratch = nullptr;
-        if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;
-        bt->pinned_results = true;  // (host buffers in, host buffers out: nobody reads this batch's records on the device)
-        ix->scratch = bt;
-    }
+    vbm25_batch *bt = nullptr;
+    if (int rc = scratch_batch(ix, &vbm25_index::scratch, true, nq, q_off, k, &bt)) return rc;
     const bool fast = !bt->bigk;
     int rc = vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq, fast);
     if (!rc) rc = vbm25_batch_run_impl(bt, fast ? bt->lat_stream : nullptr);
     if (!rc) rc = vbm25_batch_fetch_impl(bt, hits, n_hits, fast);
-    if (rc == VBM25_RETRY_GENERAL) {  // the one-launch route met an item it cannot finish: general route
-        bt->fused_g = 0;
-        rc = upload_staged(bt);
-        if (!rc) rc = vbm25_batch_run_impl(bt, bt->lat_stream);
-        if (!rc) rc = vbm25_batch_fetch_impl(bt, hits, n_hits, fast);
-    }
     return rc;
 }
 
@@ -1904,18 +1939,10 @@ int vbm25_search_batch(vbm25_index *ix, const uint32_t *term_ids, const uint32_t
     return guarded([&] { return vbm25_search_batch_impl(ix, term_ids, q_off, nq, k, hits, n_hits); });
 }
 
-// the shard's part of vbm25_multi_batch_fetch: wait for the part's stream, copy out; an item the one-launch route gave up is
-// redone on the general route, as in vbm25_search_batch
+// the shard's part of vbm25_multi_batch_fetch: wait for the part's stream, copy out (an item a one-launch route gave up is redone
+// first: rerun_and_fetch)
 static int vbm25_batch_finish_download(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits) {
-    const bool fast = !bt->bigk && bt->lat_stream;
-    int rc = vbm25_batch_fetch_impl(bt, hits, n_hits, fast);
-    if (rc == VBM25_RETRY_GENERAL) {
-        bt->fused_g = 0;
-        rc = upload_staged(bt);
-        if (!rc) rc = vbm25_batch_run_impl(bt, bt->lat_stream);
-        if (!rc) rc = vbm25_batch_fetch_impl(bt, hits, n_hits, fast);
-    }
-    return rc;
+    return vbm25_batch_fetch_impl(bt, hits, n_hits, !bt->bigk && bt->lat_stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2015,15 +2042,8 @@ static int vbm25_search_batch_filtered_impl(vbm25_index *ix, const vbm25_filter 
             return set_error(VBM25_ERR_INVALID, "query %u: selector %u, the filter has %u bitmaps", q, q_filter[q], f->n_bitmaps);
     if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
     // vbm25_search_batch on the index's batch object with the filter set for this call only
-    vbm25_batch *bt = ix->scratch;
-    const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
-    if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
-        if (bt) vbm25_batch_destroy(bt);
-        ix->scratch = nullptr;
-        if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;
-        bt->pinned_results = true;
-        ix->scratch = bt;
-    }
+    vbm25_batch *bt = nullptr;
+    if (int rc = scratch_batch(ix, &vbm25_index::scratch, true, nq, q_off, k, &bt)) return rc;
     if (int rc = batch_set_filter_impl(bt, f, q_filter, nq)) return rc;
     const int rc = vbm25_search_batch_impl(ix, term_ids, q_off, nq, k, hits, n_hits);
     const int rc2 = batch_set_filter_impl(bt, nullptr, nullptr, 0);
@@ -2240,7 +2260,7 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
     a.q_off = bt->q_off.as<uint32_t>();
     if (bt->qin_live) {  // the staged descriptors (upload_staged), as vbm25_batch_run_impl reads them
         a.term_ids = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>());
-        a.q_off = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + bt->pin_nt);
+        a.q_off = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + bt->plan.staged.off);
     }
     a.nq = nq;
     a.k = k;
@@ -2277,18 +2297,8 @@ static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // timed: the sealed scan through the final merge (the sealed route's own events are off for the run)
     const bool timing = bt->timing;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) {
-        if (bt->events_used == bt->events.size()) {
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            bt->events.emplace_back(e0, e1);
-        }
-        e0 = bt->events[bt->events_used].first;
-        e1 = bt->events[bt->events_used].second;
-        bt->events_used++;
-        HIP_TRY(hipEventRecord(e0, st));
-    }
+    hipEvent_t e1;
+    if (int rc = take_events(bt, st, e1)) return rc;
     bt->timing = false;
     int rc = vbm25_batch_run_impl(bt, hip_stream);
     bt->timing = timing;
@@ -2298,28 +2308,13 @@ static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
     return VBM25_OK;
 }
 
-// a batch object of the index's for the one-shot growing entry points, re-used while the shape fits (segment and filter are attached
-// for one call only)
-static int scratch_grow_batch(vbm25_index *ix, uint32_t nq, const uint32_t *q_off, uint32_t k, vbm25_batch **out) {
-    vbm25_batch *bt = ix->scratch_grow;
-    const uint32_t n_terms = q_off[nq] ? q_off[nq] : 1;
-    if (!bt || bt->k != k || bt->max_queries < nq || bt->max_terms < n_terms || bt->tune.generation != tuning_snapshot().generation) {
-        if (bt) vbm25_batch_destroy(bt);
-        ix->scratch_grow = nullptr;
-        if (int rc = vbm25_batch_create(ix, std::max(nq, 16u), std::max(n_terms, 256u), k, &bt)) return rc;
-        ix->scratch_grow = bt;
-    }
-    *out = bt;
-    return VBM25_OK;
-}
-
 static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
                                            uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
     if (!ix || !gs || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (gs->index != ix) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
     if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
     vbm25_batch *bt = nullptr;
-    if (int rc = scratch_grow_batch(ix, nq, q_off, k, &bt)) return rc;
+    if (int rc = scratch_batch(ix, &vbm25_index::scratch_grow, false, nq, q_off, k, &bt)) return rc;  // (segment and filter: this call only)
     int rc = batch_set_growing_impl(bt, gs);
     if (!rc) rc = vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq);
     if (!rc) rc = batch_run_growing_impl(bt, nullptr);
@@ -2387,7 +2382,7 @@ static int vbm25_search_batch_growing_filtered_impl(vbm25_index *ix, const vbm25
             return set_error(VBM25_ERR_INVALID, "query %u: selector %u, the filter has %u bitmaps", q, q_filter[q], f->n_bitmaps);
     if (nq == 0) return k ? VBM25_OK : set_error(VBM25_ERR_INVALID, "number of needed rows is set to 0");
     vbm25_batch *bt = nullptr;
-    if (int rc = scratch_grow_batch(ix, nq, q_off, k, &bt)) return rc;
+    if (int rc = scratch_batch(ix, &vbm25_index::scratch_grow, false, nq, q_off, k, &bt)) return rc;  // (segment and filter: this call only)
     int rc = batch_set_growing_impl(bt, gs);
     if (!rc) rc = batch_set_filter_impl(bt, f, q_filter, nq);
     if (!rc) rc = vbm25_batch_set_queries_impl(bt, term_ids, q_off, nq);
