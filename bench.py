@@ -8,16 +8,21 @@ queries, top-10, one MI355X.  --workload C5 is configs[4] (50M docs / 100k vocab
 
 Order of a run (single process, --gpus 1):
   1. corpus generated, flushed and indexed on the device; --batches (default 4) query batches made and handed over;
-  2. the HOST-BUFFER figures, before the timed region (config.host_buffer_*): 400 batches through vbm25_stream_* (three in
-     flight, pinned staging: queries up, records down every step), then 20 batches one at a time;
+  2. the HOST-BUFFER figures, before the timed region (config.host_buffer_*): 20 batches one at a time, then 400 batches through
+     vbm25_stream_* (three in flight, pinned staging: queries up, records down every step);
   3. W untimed warm-up steps, then EXACTLY K timed steps rotating through the batches, bracketed by synchronisations; kernel
      durations by HIP events on the launch stream (roofline.kernel_ms);
   4. outside the timed region: --dump-outputs DIR writes the hits of the last timed step as .npy files (the same arguments give the
-     same corpus and queries, so two builds can be compared output for output); 64 queries of batch 0 checked bit-exact against
-     the oracle (config.verified_sample; --verify: every query of every batch), the CPU baseline (oracle's Block-WAND, T = 1 and T = usable cores), and -- C3 only, under
-     --extra-budget-s -- C2 and C5 in the same process (`extra`, C5 with its own CPU baseline).
-The rotation is there so that a step's reads come from HBM and not from the previous step's leftovers; profiles/r5_warmup.txt
-shows the kernel's duration does not depend on it (1, 4 or 16 batches: the same), and why step 2 comes first.
+     same corpus and queries, so two builds can be compared output for output); --verify checks every query of every batch
+     bit-exact against the oracle;
+  5. with --full only: the resident batches with one stream each (config.resident_one_stream_per_batch_qps_per_gpu), the checks
+     of every batch's hits, 64 queries of batch 0 bit-exact against the oracle (config.verified_sample), the CPU baseline (oracle's
+     Block-WAND, T = 1 and T = usable cores), C2's host-inclusive latencies, and -- C3 only, under --extra-budget-s -- C2 and C5
+     in the same process (`extra`, C5 with its own CPU baseline).
+A plain run is steps 1-4 and prints the headline figure.  Step 2 stays in it: its launches (config.pre_timed_batches) bring the
+chip's clocks to their sustained rate before the W warm-up steps, so the K timed steps see that rate whatever W is.  The rotation is there so that a step's reads
+come from HBM and not from the previous step's leftovers; profiles/r5_warmup.txt shows the kernel's duration does not depend on
+it (1, 4 or 16 batches: the same), and why step 2 comes first.
 
 --gpus N WITHOUT torch.distributed's environment drives N devices from this one process through vbm25_multi_* (one host thread
 per device).  Launched by torch.distributed.run (one rank per GPU) the run is BASELINE.json configs[3] ("C4"): rank 0 makes the
@@ -301,9 +306,12 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--queries", type=int, default=0, help="override queries per GPU")
     ap.add_argument("--k", type=int, default=0, help="development aid: override the workload's k (the line then names that k; not a BASELINE.json configuration)")
-    ap.add_argument("--no-verify-sample", action="store_true", help="skip the 64-query parity sample against the oracle (it downloads the segment)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check what it does not need: the one-stream-per-batch figure, "
+                         "the checks of the hits, the 64-query parity sample, the CPU baseline, C2's latencies and C3's `extra`")
+    ap.add_argument("--no-verify-sample", action="store_true", help="skip the 64-query parity sample against the oracle (it downloads the segment; --full)")
     ap.add_argument("--batches", type=int, default=4, help="distinct query batches the timed loop rotates through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (--full)")
     ap.add_argument("--verify", action="store_true",
                     help="check every query of every batch bit-exact against the oracle (outside the timed region)")
     ap.add_argument("--build-threads", type=int, default=0)
@@ -312,7 +320,7 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
                     help="skip the host-buffer (vbm25_stream_*) figures: profiler runs, whose per-kernel averages the overlapped "
                          "launches of three batches in flight would distort")
     ap.add_argument("--extra-budget-s", type=float, default=240.0,
-                    help="wall-clock budget for the C2 / C5 lines appended as `extra` (N = 1 only; 0 switches them off)")
+                    help="wall-clock budget for the C2 / C5 lines appended as `extra` (--full, N = 1 only; 0 switches them off)")
     ap.add_argument("--tune", default="", help="development aid: library test switches, name=value[,name=value...] (vbm25_tuning_set)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write the hits of the last step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
@@ -572,7 +580,7 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
         route = {0: "general (plan_kernel)", 1: "one launch", 2: "plan-free scan_range_kernel", 3: "scan_win_kernel", 4: "exhaustive"}.get(
             batches[0].debug_route(), "?")
     multi_stream_qps = None
-    if on_gpu and world == 1 and not use_dist and not args.no_host_buffer and args.workload in ("C3", "C1"):
+    if args.full and on_gpu and world == 1 and not use_dist and not args.no_host_buffer and args.workload in ("C3", "C1"):
         # the same resident batches with ONE STREAM PER BATCH OBJECT instead of one stream for all (outside the timed region; the
         # timed loop above stays on one stream so that a kernel's duration means something): the next batch's scan starts in the
         # tail of this one's -- what the pipelined host-buffer figure above has and the one-stream loop does not
@@ -589,12 +597,12 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
         for i in range(nb):  # (a batch's consecutive runs stay on one stream: back to the launch stream through a synchronisation)
             batches[i].run(stream_ptr)
         sync()
-    results = [b.fetch() for b in batches]
-    for hits, n_hits in (results if "dbg" not in args.tune else []):  # (timing experiments switch parts of the kernel off)
+    results = [b.fetch() for b in batches] if args.full or args.verify else None
+    for hits, n_hits in (results if args.full and "dbg" not in args.tune else []):  # (timing experiments switch parts of the kernel off)
         assert (n_hits == k).all() or args.workload in ("C1",), "missing hits"
         s = hits["score"]
         assert (s[:, :-1] >= s[:, 1:]).all()
-    if use_dist and rank == 0 and last_gathered[0] is not None:  # rank 0's shard sits first in the gathered records
+    if args.full and use_dist and rank == 0 and last_gathered[0] is not None:  # rank 0's shard sits first in the gathered records
         hits_last = results[(args.steps - 1) % nb][0]
         got = last_gathered[0].cpu().numpy()[:nq_local * k * 3]
         assert got.tobytes() == np.frombuffer(hits_last.tobytes(), dtype=np.int64).tobytes(), "gathered records differ"
@@ -602,7 +610,7 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
     oix = None
     verified = None
     verified_sample = None
-    if on_gpu and world == 1 and not args.verify and not args.no_verify_sample and "dbg" not in args.tune:
+    if args.full and on_gpu and world == 1 and not args.verify and not args.no_verify_sample and "dbg" not in args.tune:
         # ties the number to parity: a sample of 64 queries of the first batch, bit-exact against the oracle's brute force
         # (outside the timed region; --verify checks every query of every batch)
         t0 = time.perf_counter()
@@ -634,7 +642,7 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
         verified = {"queries": int(nq_local * nb), "batches": nb, "seconds": round(time.perf_counter() - t0, 2)}
 
     latency = None
-    if args.workload == "C2" and on_gpu and world == 1:
+    if args.full and args.workload == "C2" and on_gpu and world == 1:
         # host-inclusive latency of vbm25_search_batch(nq = 1): 1000 different 3-term queries
         lt, lo = make_queries(seg, vocab, 1000, nterms, seed=7, zipf_s=zipf_s)
         one = np.array([0, nterms], dtype=np.uint32)
@@ -728,12 +736,12 @@ def run(argv=None, scorer_factory=None, backend="nccl"):
                                "traffic": committed_traffic(sha16, args.workload if world == 1 else "C3"),
                                "algorithmic_bytes_per_launch": int(algo),
                                "kernel_ms": round(kernel_ms, 4), "launches_timed": n_launch}
-        if world == 1 and not args.no_cpu_baseline and on_gpu:
+        if args.full and world == 1 and not args.no_cpu_baseline and on_gpu:
             oix = oix or oracle_index(seg)
             out["cpu_baseline"] = cpu_baseline(oix, shards[0][0], shards[0][1], k)
         if on_gpu:
             out["config"]["libvbm25_sha256_16"] = sha16
-        if world == 1 and on_gpu and not use_dist and args.workload == "C3" and args.extra_budget_s > 0:
+        if args.full and world == 1 and on_gpu and not use_dist and args.workload == "C3" and args.extra_budget_s > 0:
             # the other single-GPU configurations, driver-timed in the same run (the C3 index is released first)
             del batches, results, gix, oix, seg
             t_extra = time.perf_counter()
@@ -791,7 +799,7 @@ def run_single_process(args, vb):
         batches[i % nb].run()
     results = [b.fetch() for b in batches]  # waits for every device
     elapsed = time.perf_counter() - t0
-    for hits, n_hits in results:
+    for hits, n_hits in (results if args.full else []):
         assert (n_hits == k).all(), "missing hits"
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, *results[(args.steps - 1) % nb])

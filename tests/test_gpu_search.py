@@ -439,7 +439,7 @@ def test_bench_distributed_code_path_single_rank():
     env = dict(os.environ, VBM25_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "C2",
-                                   "--queries", "64", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                                   "--queries", "64", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                                   env=env, text=True, timeout=600)
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["roofline"]["frac"] > 0
@@ -473,6 +473,27 @@ def test_bench_dump_outputs_are_the_last_steps_hits(tmp_path):
         assert np.array_equal(got["score"][q, :n].view(np.uint64), ref["score"][q, :n].view(np.uint64)), f"q{q}: score bits differ"
         assert np.array_equal(got["doc_id"][q, :n], ref["doc_id"][q, :n]), f"q{q}: doc ids differ"
         assert np.array_equal(got["payload"][q, :n], ref["payload"][q, :n]), f"q{q}: payloads differ"
+
+
+def test_bench_full_adds_what_the_headline_does_not_need():
+    """A plain bench.py run prints the headline figure alone; --full adds the one-stream-per-batch figure, the 64-query parity
+    sample and the CPU baseline to the same line."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode in ([], ["--full"]):
+        out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "C1", "--steps", "3",
+                                       "--warmup", "1", *mode], text=True, timeout=600)
+        lines[bool(mode)] = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    for line in lines.values():
+        assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["roofline"]["kernel_ms"] > 0
+        assert line["config"]["host_buffer_inclusive_qps_per_gpu"] > 0  # (the pre-timed launches: in every run)
+    plain, full = lines[False], lines[True]
+    assert "cpu_baseline" not in plain and "verified_sample" not in plain["config"]
+    assert plain["config"]["resident_one_stream_per_batch_qps_per_gpu"] is None
+    assert full["cpu_baseline"]["value"] > 0 and full["config"]["verified_sample"]["bit_exact_vs_oracle_brute_force"]
+    assert full["config"]["resident_one_stream_per_batch_qps_per_gpu"] > 0
 
 
 def test_c3_full_size_full_batch_parity():

@@ -113,7 +113,7 @@ def test_bench_step_two_ranks_gloo():
         out = subprocess.run(
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
              "--master-addr", "127.0.0.1", "--master-port", str(port), script, ROOT,
-             "--gpus", "2", "--workload", "C1", "--steps", "3", "--warmup", "1", "--batches", "2", "--verify",
+             "--gpus", "2", "--workload", "C1", "--steps", "3", "--warmup", "1", "--batches", "2", "--verify", "--full",
              "--dump-outputs", dump],
             timeout=600, capture_output=True, text=True)
         assert out.returncode == 0, out.stderr[-2000:]

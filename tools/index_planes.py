@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for label, tune in (("all planes (default)", "win=1"), ("no window planes", "win_planes=0"), ("no window planes, no post_rel16", "win_planes=0,rel16_plane=0"),
                     ("window tables, no post_id16, no post_rel16", "id16_plane=0,rel16_plane=0")):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "100", "--extra-budget-s", "0", "--tune", tune],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "100", "--extra-budget-s", "0", "--tune", tune],
                          capture_output=True, text=True, timeout=600).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     c, r = d["config"], d["roofline"]

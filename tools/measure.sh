@@ -17,11 +17,11 @@ for step in "$@"; do case $step in
   alltests) timeout 2400 python -m pytest tests -x -q -m gpu > $O/pytest_all.log 2>&1; tail -5 $O/pytest_all.log;;
   c3) seg C3; timeout 600 python bench.py --no-cpu-baseline --verify --steps 100 --extra-budget-s 0 $TUNE_ARG > $O/bench_c3.json 2> $O/bench_c3.err; show $O/bench_c3.json;;
   c3quick) seg C3; timeout 600 python bench.py --no-cpu-baseline --no-verify-sample --steps 100 --extra-budget-s 0 $TUNE_ARG > $O/bench_c3q.json 2> $O/bench_c3q.err; show $O/bench_c3q.json;;
-  c3full) seg C3; timeout 900 python bench.py $TUNE_ARG > $O/bench_c3_full.json 2> $O/bench_c3_full.err; show $O/bench_c3_full.json;;
+  c3full) seg C3; timeout 900 python bench.py --full $TUNE_ARG > $O/bench_c3_full.json 2> $O/bench_c3_full.err; show $O/bench_c3_full.json;;
   c5) seg C5; timeout 900 python bench.py --workload C5 --no-cpu-baseline --steps 10 --warmup 2 $TUNE_ARG > $O/bench_c5.json 2> $O/bench_c5.err; show $O/bench_c5.json;;
   c3z) timeout 900 python bench.py --workload C3z --steps 20 --warmup 3 --extra-budget-s 0 --no-host-buffer $TUNE_ARG > $O/bench_c3z.json 2> $O/bench_c3z.err; show $O/bench_c3z.json
      (cd /tmp; export TMPDIR=/tmp; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats3z -- python $R/bench.py --workload C3z --steps 10 --warmup 2 --no-cpu-baseline --no-verify-sample --no-host-buffer --extra-budget-s 0 $TUNE_ARG > $O/stats3z.log 2>&1); f=$(find $O/stats3z -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/c3z_kernel_stats.csv && head -8 $O/c3z_kernel_stats.csv; find $O/stats3z -name "*.csv" -size +5M -delete;;
-  c2) seg C2; timeout 600 python bench.py --workload C2 --no-cpu-baseline --steps 200 $TUNE_ARG > $O/bench_c2.json 2> $O/bench_c2.err; show $O/bench_c2.json;;
+  c2) seg C2; timeout 600 python bench.py --full --workload C2 --no-cpu-baseline --steps 200 $TUNE_ARG > $O/bench_c2.json 2> $O/bench_c2.err; show $O/bench_c2.json;;
   c3stats) seg C3; (cd /tmp; export TMPDIR=/tmp; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-verify-sample --no-host-buffer --extra-budget-s 0 $TUNE_ARG > $O/stats.log 2>&1); f=$(find $O/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/c3_kernel_stats.csv && head -8 $O/c3_kernel_stats.csv; find $O/stats -name "*.csv" -size +5M -delete;;
   c3pmc) seg C3; B="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-verify-sample --no-host-buffer --extra-budget-s 0 $TUNE_ARG"
      (cd /tmp; export TMPDIR=/tmp
@@ -48,7 +48,7 @@ for step in "$@"; do case $step in
   sweep_items) for t in range_items=2048 range_items=1536 range_items=2048,range_min_chunk=8192; do TUNE=$t bash $0 ${SUB}_$(echo $t | tr '=,' '__') c3quick; done;;
   sweep_grid) for t in range_grid=256 range_grid=384 range_grid=512; do TUNE=$t bash $0 ${SUB}_$(echo $t | tr '=,' '__') c3quick; done;;  # resident workgroups per CU: 1, 1.5, 2
   sweep_c2) for t in range_min_chunk=16384 range_min_chunk=8192 range_min_chunk=4096 range_min_chunk=2048; do
-      timeout 300 python bench.py --workload C2 --no-cpu-baseline --steps 200 --tune $t 2>/dev/null |
+      timeout 300 python bench.py --full --workload C2 --no-cpu-baseline --steps 200 --tune $t 2>/dev/null |
         python -c "import json,sys; d=json.loads(sys.stdin.read()); l=d['config']['latency']; print('$t', 'kernel_ms', d['roofline']['kernel_ms'], 'p50', l['c_abi_nq1_us_p50'], 'p99', l['c_abi_nq1_us_p99'])"; done;;
   sweep_bigk)  # scan_range_kernel<128> / <256> (sparse queries, 64 < k <= 256): LIBS="libvbm25.so libvbm25_bigk.so" compares builds (-DVBM25_RWPS_BIGK=2)
     for lib in ${LIBS:-libvbm25.so}; do for k in 100 200; do
