@@ -11,9 +11,10 @@ def _key_order(keys):
     return np.lexsort((lo, hi))
 
 
-def make_growing(term_key, n_grow, seed, mean_elems=12, n_unknown=50, deleted=0.1, pool=None, pool_p=0.3):
+def make_growing(term_key, n_grow, seed, mean_elems=12, n_unknown=50, deleted=0.1, pool=None, pool_p=0.3,
+                 fieldnorm_hi=200):
     """n_grow documents over the sealed keys plus `n_unknown` keys the sealed segment lacks: elements in ascending key order, tf 1..5,
-    random fieldnorms and payloads; `pool` (term ids) are drawn with probability pool_p per element slot, so queries over them match."""
+    random fieldnorms (0 .. fieldnorm_hi - 1) and payloads; `pool` (term ids) are drawn with probability pool_p per element slot, so queries over them match."""
     rng = np.random.default_rng(seed)
     term_key = np.asarray(term_key, dtype=np.uint8).reshape(-1, 16)
     n_terms = len(term_key)
@@ -37,7 +38,7 @@ def make_growing(term_key, n_grow, seed, mean_elems=12, n_unknown=50, deleted=0.
     np.add.at(start, d + 1, 1)
     start = np.cumsum(start).astype(np.uint64)
     return dict(g_start=start, g_key=universe[u].reshape(-1), g_tf=rng.integers(1, 6, len(u)).astype(np.uint32),
-                g_fieldnorm=rng.integers(0, 200, n_grow).astype(np.uint8),
+                g_fieldnorm=rng.integers(0, fieldnorm_hi, n_grow).astype(np.uint8),
                 g_payload=rng.integers(0, 65535, (n_grow, 3)).astype(np.uint16),
                 g_deleted=(rng.random(n_grow) < deleted).astype(np.uint8) if deleted is not None else None), \
         np.where(u < n_terms, u, 0xFFFFFFFF).astype(np.uint32)

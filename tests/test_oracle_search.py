@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import orc
-from corpus import make_corpus, make_queries
+from corpus import make_corpus, make_long_corpus, make_queries, make_short_corpus, make_tie_corpus
 from parity import assert_same_ranking, edit_distance
 
 
@@ -43,6 +43,27 @@ def test_wand_equals_brute_outside_ties(length, zipf, nterms, k):
         t = terms[off[q]:off[q + 1]]
         assert_same_ranking(ix.search_brute(t, k), ix.search_wand(t, k),
                             ref_ext=ix.search_brute(t, k + 500), what=f"q{q}")
+
+
+@pytest.mark.parametrize("b", [0.0, 1.0])
+@pytest.mark.parametrize("corpus,nterms,k", [
+    ("lognormal", 5, 10), ("mixed", 2, 1), ("zipf", 4, 7), ("long", 4, 10), ("long_wide_tf", 3, 100), ("short", 3, 10),
+    ("tie", 3, 10)])
+def test_wand_equals_brute_outside_ties_at_the_b_edges(corpus, nterms, k, b):
+    """k1 = 2: b = 0 (one S1 for every document: masses of equal scores), b = 1 (S1[0] = 0, S1 tiny for short documents under a
+    large mean length), on corpora of every fieldnorm code too"""
+    c = {"lognormal": lambda: make_corpus(20000, 2000, seed=7, length="lognormal", mean_len=60),
+         "mixed": lambda: make_corpus(20000, 2000, seed=7, length="mixed", mean_len=60),
+         "zipf": lambda: make_corpus(20000, 2000, seed=7, length="lognormal", mean_len=60, zipf=1.0),
+         "long": lambda: make_long_corpus(20000, 1000, seed=1),
+         "long_wide_tf": lambda: make_long_corpus(20000, 1000, seed=2, wide_tf=True),
+         "short": lambda: make_short_corpus(20000, 300, seed=3),
+         "tie": lambda: make_tie_corpus(20000, 100, seed=4)}[corpus]()
+    ix = build(c, k1=2.0, b=b)
+    terms, off = make_queries(c, 30, nterms, seed=9, zipf=1.0 if corpus == "zipf" else None)
+    for q in range(len(off) - 1):
+        t = terms[off[q]:off[q + 1]]
+        assert_same_ranking(ix.search_brute(t, k), ix.search_wand(t, k), ref_ext=ix.search_brute(t, k + 500), what=f"q{q}")
 
 
 def test_edge_cases():

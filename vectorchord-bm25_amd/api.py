@@ -359,7 +359,7 @@ class Batch:
 
     def debug_counts(self):
         """tuning / test aid (not in include/vbm25.h): (work items of the last run, items the first-choice
-        kernel handed to scan_many_kernel)"""
+        kernel handed to scan_many_kernel; (0, 0) on the exhaustive route, which makes no work items)"""
         f = lib().vbm25_batch_debug_counts
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

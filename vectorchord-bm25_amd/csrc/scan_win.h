@@ -666,12 +666,14 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
             uint32_t doc;
         };
         auto c2_calc = [&](const WnPend &d) -> C2R {
-            // (every lane computes -- no branch around the divide, so that it can be scheduled into the search's waits; a lane that found
-            // nothing divides by S1[..] + 0 > 0 and drops the result)
+            // (every lane computes -- no branch around the divide, so that it can be scheduled into the search's waits.  A lane with
+            // tf = 0 -- it found nothing, or its word holds zeros for a tf above 255 -- divides 0 by S1[1] > 0: + 0.0.  Not by the
+            // fieldnorm of its word: a zero word (word 0 of post_tfn for the lanes that found nothing) gives S1[0] = k1 (1 - b), 0 at
+            // b = 1, and 0 / 0 = NaN would enter the row's sum and, through a given-up item's offers, the query's threshold)
             double c;
             {
                 const uint32_t ww = d.gw >> ((d.p & 1u) * 8u);
-                const uint32_t tfv = d.found ? ww & 0xffu : 0u, fn = (ww >> 16) & 0xffu;
+                const uint32_t tfv = d.found ? ww & 0xffu : 0u, fn = tfv ? (ww >> 16) & 0xffu : 1u;
                 notf = notf || (d.found && tfv == 0u);  // (a term frequency above 255: the word holds zeros -- not this kernel's item)
                 const double tf = (double)tfv;
                 c = (tf * s0l) / (tf + S1[fn]);  // Cache::evaluate, bm25.rs:355-358 (tf = 0: + 0.0)
@@ -710,10 +712,10 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
         };
         auto c2_div_begin = [&](const WnPend &d, C2Div &D) {
             const uint32_t ww = d.gw >> ((d.p & 1u) * 8u);
-            const uint32_t tfv = d.found ? ww & 0xffu : 0u, fn = (ww >> 16) & 0xffu;
+            const uint32_t tfv = d.found ? ww & 0xffu : 0u, fn = tfv ? (ww >> 16) & 0xffu : 1u;
             notf = notf || (d.found && tfv == 0u);
             const double tf = (double)tfv;
-            D.num = tf * s0l;       // (a lane that found nothing: 0 / S1[..] = + 0.0)
+            D.num = tf * s0l;       // (tf = 0: 0 / S1[1] = + 0.0, as in c2_calc)
             D.den = tf + S1[fn];
         };
         auto c2_div_step = [&](C2Div &D, auto itc) {

@@ -1764,6 +1764,8 @@ static bool plan_free_kernels(const vbm25_batch *bt) { return bt->plan.route == 
 // first-choice kernel handed to scan_many_kernel
 int vbm25_batch_debug_counts(vbm25_batch *bt, uint32_t *n_items, uint32_t *n_failed) {
     if (!bt || !n_items || !n_failed) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    *n_items = *n_failed = 0;
+    if (bt->bigk) return VBM25_OK;  // (the exhaustive route makes no work items: no n_items / item_failed buffers)
     if (int rc = use_device(bt->index->device)) return rc;
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     if (plan_free_kernels(bt) && bt->state_clean) {  // merge_kernel has cleaned the flags and kept the counts per query
