@@ -433,6 +433,35 @@ void vbm25_device_segment_free(vbm25_device_segment *);
 /* The index of a device segment, on the segment's device; the segment is left as it was. */
 int vbm25_index_create_from_device(const vbm25_device_segment *, vbm25_index **out);
 
+/* VACUUM's compaction (maintain.rs:27-298) on the device: an index, the deletes of its sealed documents and its growing segment
+ * become ONE new sealed segment in HBM on the index's device, byte for byte what vbm25_segment_build(k1 and b of the index, ...)
+ * makes of the records and mappings maintain.rs writes:
+ *   1. sealed documents in id order: a kept document d gets new id = the number of kept sealed documents before d, record
+ *      (length 0, its payload); a deleted one gets no id and no record;
+ *   2. every posting of a kept sealed document becomes the mapping (token key, new id, tf) and adds 1 to that document's length
+ *      (maintain.rs:344-362).  A kept sealed document's new length is therefore the NUMBER OF DISTINCT TOKENS it holds, not the sum
+ *      of its tfs: the sealed segment keeps only fieldnorm codes, the real length is gone.  Its fieldnorm code is recomputed from that
+ *      count and changes wherever a tf > 1.  This is the reference's behaviour, kept on purpose;
+ *   3. the growing documents in desc order: the non-deleted ones get ids n_kept_sealed + 0, 1, ..., record (Document::length() = the
+ *      saturating sum of their tfs, payload) (vector.rs:77-83), and every element becomes a mapping, keys the sealed vocabulary lacks
+ *      included (they become new tokens).  The desc's fieldnorm array is not read;
+ *   4. the mappings sorted by (key, document) and flushed with the index's k1 and b: a token with no mapping left is absent, n_docs
+ *      and sum_len are recomputed;
+ *   5. nothing left: the empty segment (n_docs 0, no tokens, no blocks), which vbm25_index_create_from_device takes and every search
+ *      of returns no hit.  More than 2^32 - 1 documents (io.rs:53-56) -> VBM25_ERR_INVALID.
+ * index: any index (host arrays, pages or a device segment, with or without the derived planes); its blob, block metadata,
+ *   term_first_block, payloads and keys are read, nothing of it changes and it stays usable.
+ * sealed_deleted: NULL (nothing deleted) or ceil(n_docs / 64) words, bit d % 64 of word d / 64 set = sealed document d is DELETED
+ *   (DocumentTuple.deleted) -- the opposite polarity of a filter's keep bits.  Bits at or beyond n_docs -> VBM25_ERR_INVALID.
+ * growing: NULL or n_docs 0 = no growing documents.  Validated as vbm25_growing_upload does (keys strictly ascending inside a
+ *   document, start monotone), and tf 0 is rejected; deleted NULL = none deleted.
+ * relabel: NULL, or n_docs(sealed) + n_docs(growing) entries: every old sealed document, then every growing index, -> its new id or
+ *   UINT32_MAX (to carry filters and payload maps across).
+ * Failure leaves *out NULL and nothing allocated.  The serving loop: compact, vbm25_index_create_from_device, swap the index in,
+ * upload an empty growing segment, remap the filters with relabel. */
+int vbm25_index_maintain(const vbm25_index *index, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing,
+                         uint32_t *relabel, vbm25_device_segment **out);
+
 /* ------------------------------------------------------------------------
  * Several GPUs of one node: independent queries shard
  * across the devices, the index is replicated.  vbm25_multi_create uploads the

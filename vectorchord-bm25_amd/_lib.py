@@ -101,6 +101,7 @@ ABI = {
     "vbm25_device_segment_info": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_device_segment_free": (None, [vp]),
     "vbm25_index_create_from_device": (i32, [vp, vp]),
+    "vbm25_index_maintain": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_multi_create": (i32, [vp, vp, i32, vp]),
     "vbm25_multi_destroy": (None, [vp]),
     "vbm25_multi_device_count": (i32, [vp]),

@@ -212,6 +212,49 @@ class DeviceSegment:
                                                _p(term_key), _p(term_start), _p(post_doc), _p(post_tf), C.byref(out)))
         return cls(out)
 
+    @classmethod
+    def maintain(cls, index, sealed_deleted=None, growing=None, return_relabel=False):
+        """vbm25_index_maintain: VACUUM's compaction of `index` (a GpuIndex) on its device.  sealed_deleted: None, a bool array of
+        n_docs (True = deleted) or the packed uint64 words; growing: None or a dict of growing_data.make_growing's form (g_start,
+        g_key, g_tf, g_payload, g_deleted; g_fieldnorm is not read).  Returns the new DeviceSegment, and with return_relabel the
+        uint32 array old sealed ids + growing indexes -> new id (0xFFFFFFFF: dropped)."""
+        n_docs = index.n_docs
+        words = None
+        if sealed_deleted is not None:
+            a = np.asarray(sealed_deleted)
+            if a.dtype == np.bool_:
+                if len(a) != n_docs:
+                    raise ValueError(f"{len(a)} deleted flags for {n_docs} documents")
+                words = np.zeros((n_docs + 63) // 64, dtype=np.uint64)
+                idx = np.flatnonzero(a)
+                np.bitwise_or.at(words, idx >> 6, np.left_shift(np.uint64(1), (idx & 63).astype(np.uint64)))
+            else:
+                words = np.ascontiguousarray(a, dtype=np.uint64)
+                if len(words) != (n_docs + 63) // 64:
+                    raise ValueError(f"{len(words)} words for {n_docs} documents")
+        d, keep, n_grow = None, [], 0
+        if growing is not None:
+            g_start = np.ascontiguousarray(growing["g_start"], dtype=np.uint64)
+            g_key = np.ascontiguousarray(growing["g_key"], dtype=np.uint8).reshape(-1)
+            g_tf = np.ascontiguousarray(growing["g_tf"], dtype=np.uint32)
+            g_payload = np.ascontiguousarray(growing["g_payload"], dtype=np.uint16).reshape(-1)
+            g_del = growing.get("g_deleted")
+            g_del = None if g_del is None else np.ascontiguousarray(g_del, dtype=np.uint8)
+            if len(g_key) != 16 * len(g_tf):
+                raise ValueError(f"{len(g_key)} key bytes for {len(g_tf)} elements")
+            keep = [g_start, g_key, g_tf, g_payload, g_del]
+            n_grow = len(g_start) - 1
+            d = GrowingDesc()
+            d.n_docs, d.n_elements = n_grow, len(g_tf)
+            d.start, d.key, d.tf = _p(g_start), _p(g_key), _p(g_tf)
+            d.fieldnorm, d.payload, d.deleted = None, _p(g_payload), _p(g_del)
+        relabel = np.zeros(n_docs + n_grow, dtype=np.uint32) if return_relabel else None
+        out = C.c_void_p()
+        check(lib().vbm25_index_maintain(index.h, _p(words), C.byref(d) if d is not None else None,
+                                         relabel.ctypes.data_as(C.c_void_p) if relabel is not None else None, C.byref(out)))
+        seg = cls(out)
+        return (seg, relabel) if return_relabel else seg
+
     def download(self):
         out = C.c_void_p()
         check(lib().vbm25_device_segment_download(self.h, C.byref(out)))

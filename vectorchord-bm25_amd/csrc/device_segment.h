@@ -7,7 +7,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <vector>
+
+#include "../../include/vbm25.h"
 
 namespace vbm25 {
 
@@ -47,5 +50,32 @@ struct vbm25_device_segment {
     vbm25::HbmArray d_term_df, d_term_wand_fn, d_term_wand_tf, d_term_first_block, d_blk_min, d_blk_max, d_blk_n, d_blk_wand_fn,
         d_blk_wand_tf, d_blk_meta_doc, d_blk_meta_tf, d_blk_off8, d_blob, d_doc_fieldnorm, d_doc_payload;
 };
+
+namespace vbm25 {
+
+// The encode of flush.hip, everything left in HBM.  Lengths on the host (doc_len) or the device (dev_len); payloads on the host
+// (doc_payload), the device (dev_payload) or neither (synthetic ctids); the mappings, sorted by (token, document), on the host
+// (post_doc / post_tf) or the device (dev_doc / dev_tf); term_key and term_start on the host.
+int build_device_core(int device, double k1, double b, uint32_t n_docs, const uint32_t *doc_len, const uint32_t *dev_len,
+                      const uint16_t *doc_payload, const uint16_t *dev_payload, uint32_t n_terms, const uint8_t *term_key,
+                      const uint64_t *term_start, const uint32_t *post_doc, const uint32_t *post_tf, const uint32_t *dev_doc,
+                      const uint32_t *dev_tf, std::unique_ptr<vbm25_device_segment> &out);
+
+// What vbm25_index_maintain reads of an index (search.hip fills it in, csrc/maintain.hip compacts): the block metadata, the blob,
+// term_first_block and the payloads in HBM, the keys on the host
+struct MaintainSource {
+    int device;
+    double k1, b;
+    uint32_t n_docs, n_terms, n_blocks;
+    const uint8_t *term_key;           // host, n_terms x 16
+    const uint32_t *term_first_block;  // device, n_terms + 1
+    const uint4 *blk_meta;             // device, per block (min_doc, max_doc, off8, n | meta_doc << 8 | meta_tf << 16 | wand_fn << 24)
+    const uint8_t *blob;               // device
+    const uint16_t *doc_payload;       // device, n_docs x 3
+};
+int maintain_device(const MaintainSource &src, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing, uint32_t *relabel,
+                    vbm25_device_segment **out);
+
+}  // namespace vbm25
 
 #endif

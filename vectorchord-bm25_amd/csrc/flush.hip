@@ -307,12 +307,15 @@ __global__ void __launch_bounds__(256) synth_payload_kernel(uint32_t n_docs, uin
     }
 }
 
+}  // namespace
+
 // The encode, everything left in HBM (vbm25_device_segment).  Inputs on the host, or already on the device: dev_len (document
-// lengths), dev_doc / dev_tf (the mappings, sorted by (token, document)); doc_payload == nullptr: synthetic ctids.
-int build_device_core(int device, double k1, double b, uint32_t n_docs, const uint32_t *doc_len, const uint32_t *dev_len,
-                      const uint16_t *doc_payload, uint32_t n_terms, const uint8_t *term_key, const uint64_t *term_start,
-                      const uint32_t *post_doc, const uint32_t *post_tf, const uint32_t *dev_doc, const uint32_t *dev_tf,
-                      std::unique_ptr<vbm25_device_segment> &out) {
+// lengths), dev_payload, dev_doc / dev_tf (the mappings, sorted by (token, document)); no payload at all: synthetic ctids.
+// (Also the last step of vbm25_index_maintain, csrc/maintain.hip.)
+int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, const uint32_t *doc_len, const uint32_t *dev_len,
+                             const uint16_t *doc_payload, const uint16_t *dev_payload, uint32_t n_terms, const uint8_t *term_key,
+                             const uint64_t *term_start, const uint32_t *post_doc, const uint32_t *post_tf, const uint32_t *dev_doc,
+                             const uint32_t *dev_tf, std::unique_ptr<vbm25_device_segment> &out) {
     if ((!doc_len && !dev_len) || !term_start || (n_terms && (!term_key || ((!post_doc || !post_tf) && (!dev_doc || !dev_tf)))))
         return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (!n_docs) return set_error(VBM25_ERR_INVALID, "segment without documents");
@@ -360,7 +363,8 @@ int build_device_core(int device, double k1, double b, uint32_t n_docs, const ui
         FL_TRY(hipMemcpy(d_len.p, doc_len, 4ull * n_docs, hipMemcpyHostToDevice));
         dev_len = d_len.as<uint32_t>();
     }
-    if (doc_payload) FL_TRY(hipMemcpy(ds->d_doc_payload.p, doc_payload, 6ull * n_docs, hipMemcpyHostToDevice));
+    if (dev_payload) FL_TRY(hipMemcpy(ds->d_doc_payload.p, dev_payload, 6ull * n_docs, hipMemcpyDeviceToDevice));
+    else if (doc_payload) FL_TRY(hipMemcpy(ds->d_doc_payload.p, doc_payload, 6ull * n_docs, hipMemcpyHostToDevice));
     else synth_payload_kernel<<<1024, 256>>>(n_docs, ds->d_doc_payload.as<uint16_t>());
     FL_TRY(hipMemcpy(d_fnlen.p, fieldnorm_lengths(), 4 * 256, hipMemcpyHostToDevice));
     FL_TRY(hipMemset(d_sum.p, 0, 8));
@@ -469,6 +473,8 @@ int build_device_core(int device, double k1, double b, uint32_t n_docs, const ui
     return VBM25_OK;
 }
 
+namespace {
+
 // the host copy of a device segment: the same vbm25_segment the host builder makes, byte for byte
 int download_device_segment(const vbm25_device_segment &ds, vbm25_segment **out) {
     FL_TRY(hipSetDevice(ds.device));
@@ -513,8 +519,8 @@ int build_device_impl(int device, double k1, double b, uint32_t n_docs, const ui
     *out = nullptr;
     if (!doc_len || !doc_payload) return set_error(VBM25_ERR_INVALID, "NULL argument");
     std::unique_ptr<vbm25_device_segment> ds;
-    if (int rc = build_device_core(device, k1, b, n_docs, doc_len, nullptr, doc_payload, n_terms, term_key, term_start, post_doc, post_tf,
-                                   dev_doc, dev_tf, ds))
+    if (int rc = build_device_core(device, k1, b, n_docs, doc_len, nullptr, doc_payload, nullptr, n_terms, term_key, term_start, post_doc,
+                                   post_tf, dev_doc, dev_tf, ds))
         return rc;
     return download_device_segment(*ds, out);
 }
@@ -796,7 +802,7 @@ int synth_device_impl(const vbm25_synth_params *pr, int device, vbm25_device_seg
     (void)hipFree(d_slot.p); d_slot.p = nullptr;
     (void)hipFree(d_draws.p); d_draws.p = nullptr;
     std::unique_ptr<vbm25_device_segment> ds;
-    if (int rc = build_device_core(device, pr->k1, pr->b, n_docs, nullptr, d_len.as<uint32_t>(), nullptr, n_terms, term_key.data(), term_start.data(),
+    if (int rc = build_device_core(device, pr->k1, pr->b, n_docs, nullptr, d_len.as<uint32_t>(), nullptr, nullptr, n_terms, term_key.data(), term_start.data(),
                                    nullptr, nullptr, d_pd.as<uint32_t>(), d_pt.as<uint32_t>(), ds))
         return rc;
     ds->token_term = std::move(token_term);
@@ -923,8 +929,8 @@ extern "C" int vbm25_device_segment_build(int device, double k1, double b, uint3
         *out = nullptr;
         if (!doc_len || !doc_payload) return set_error(VBM25_ERR_INVALID, "NULL argument");
         std::unique_ptr<vbm25_device_segment> ds;
-        if (int rc = build_device_core(device, k1, b, n_docs, doc_len, nullptr, doc_payload, n_terms, term_key, term_start, post_doc, post_tf,
-                                       nullptr, nullptr, ds))
+        if (int rc = build_device_core(device, k1, b, n_docs, doc_len, nullptr, doc_payload, nullptr, n_terms, term_key, term_start, post_doc,
+                                       post_tf, nullptr, nullptr, ds))
             return rc;
         *out = ds.release();
         return VBM25_OK;

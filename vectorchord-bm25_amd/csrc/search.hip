@@ -214,7 +214,7 @@ struct vbm25_index {
         post_fn, post_rel16, post_tfn, doc_payload, s1, term_idf, fn_len, term_kth_ub, post_id16, win_off, term_win;
     std::vector<uint32_t> term_win_host;  // host copy of term_win (query routing); empty: the index has no window planes
     uint32_t n_win = 0;
-    double k1 = 1.2;
+    double k1 = 1.2, b = 0.75;
     uint64_t device_bytes = 0;
 };
 
@@ -501,6 +501,7 @@ static int index_create_common(const RawSegment &r, int device, vbm25_index **ou
     ix->n_terms = r.n_terms;
     ix->n_blocks = r.n_blocks;
     ix->k1 = r.k1;
+    ix->b = r.b;
     ix->term_key.assign(r.term_key, r.term_key + 16ull * r.n_terms);
     ix->term_df_host.assign(r.term_df_host, r.term_df_host + r.n_terms);
     const hipMemcpyKind kind = r.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -767,6 +768,27 @@ static int vbm25_index_create_from_device_impl(const vbm25_device_segment *ds, v
     r.doc_fieldnorm = ds->d_doc_fieldnorm.as<uint8_t>();
     r.doc_payload = ds->d_doc_payload.as<uint16_t>();
     return index_create_common(r, ds->device, out);
+}
+
+// VACUUM's compaction (csrc/maintain.hip): the index's blocks, keys and payloads are read, nothing of it is changed
+static int vbm25_index_maintain_impl(const vbm25_index *ix, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing,
+                                     uint32_t *relabel, vbm25_device_segment **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ix) return set_error(VBM25_ERR_INVALID, "index is NULL");
+    MaintainSource s{};
+    s.device = ix->device;
+    s.k1 = ix->k1;
+    s.b = ix->b;
+    s.n_docs = ix->n_docs;
+    s.n_terms = ix->n_terms;
+    s.n_blocks = ix->n_blocks;
+    s.term_key = ix->term_key.data();
+    s.term_first_block = ix->term_first_block.as<uint32_t>();
+    s.blk_meta = ix->blk_meta.as<uint4>();
+    s.blob = ix->blob.as<uint8_t>();
+    s.doc_payload = ix->doc_payload.as<uint16_t>();
+    return maintain_device(s, sealed_deleted, growing, relabel, out);
 }
 
 void vbm25_index_destroy(vbm25_index *ix) {
@@ -1916,6 +1938,10 @@ int vbm25_index_create(const vbm25_index_desc *d, int device, vbm25_index **out)
 int vbm25_index_create_from_device(const vbm25_device_segment *ds, vbm25_index **out) {
     return guarded([&] { return vbm25_index_create_from_device_impl(ds, out); });
 }
+int vbm25_index_maintain(const vbm25_index *ix, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing, uint32_t *relabel,
+                         vbm25_device_segment **out) {
+    return guarded([&] { return vbm25_index_maintain_impl(ix, sealed_deleted, growing, relabel, out); });
+}
 
 int vbm25_batch_create(vbm25_index *ix, uint32_t max_queries, uint32_t max_total_terms, uint32_t k,
                        vbm25_batch **out) {
@@ -2639,6 +2665,7 @@ int clone_index(const vbm25_index *src, int device, vbm25_index **out) {
     ix->term_win_host = src->term_win_host;
     ix->n_win = src->n_win;
     ix->k1 = src->k1;
+    ix->b = src->b;
     ix->device_bytes = src->device_bytes;
     for (auto member : INDEX_BUFFERS) {
         const DeviceBuffer &from = src->*member;
