@@ -331,9 +331,27 @@ int vbm25_batch_set_filter(vbm25_batch *, const vbm25_filter *, const uint32_t *
  *   vbm25_growing_upload       builds the inverted form in HBM on the index's device (synchronous); the caller's arrays are
  *                              not kept.  VBM25_ERR_INVALID: a document whose keys are not strictly ascending
  *                              (vector.rs:56-61), a start array that is not monotone or reaches beyond n_elements,
- *                              n_docs(sealed) + n_docs(growing) > 2^32 (the doc id ranges would collide).  Appending is a
- *                              re-upload.
+ *                              n_docs(sealed) + n_docs(growing) > 2^32 (the doc id ranges would collide).
  *   vbm25_device_growing_free  must not be called while a batch refers to the segment (set it to NULL first).
+ *   vbm25_device_growing_append  `delta` is a CSR of the NEW documents only, in the form vbm25_growing_upload takes (start may
+ *                              begin anywhere): document i of the delta becomes growing document g = n_grow + i.  Afterwards the
+ *                              segment searches exactly as an upload of the old documents followed by the delta's would.  Only
+ *                              the delta crosses the host link (plus O(n_terms) words back, and once per segment, at its first
+ *                              append, the index's term keys); the merge into the term-major postings runs on the device.
+ *                              Validation is upload's, applied to the delta (VBM25_ERR_INVALID; the postings the segment holds
+ *                              reaching 2^31 -> VBM25_ERR_UNSUPPORTED), and it and every allocation come before anything a search
+ *                              reads is changed: a failed append leaves the segment exactly as it was.  An empty delta changes
+ *                              nothing.  Synchronous: it waits for the device first, so a run in flight ends on the old arrays.
+ *                              The handle and its upload stay the same: a batch that holds the segment sees the new documents at
+ *                              its next run with no setter call.  A filter's growing bitmaps are stale after an append (below).
+ *   vbm25_device_growing_delete  g[0 .. n): growing indices to drop (any order, repeats and already deleted ones allowed); any
+ *                              g[i] >= n_grow -> VBM25_ERR_INVALID and nothing changed.  Afterwards the segment searches as an
+ *                              upload with deleted[g] = 1 would; later appends keep the documents deleted.  Their postings stay
+ *                              in HBM (scoring nothing) until the next compaction.  Synchronous.  Growing bitmaps stay valid.
+ *                              Neither call may run while another host thread runs a batch that holds the segment.
+ *   vbm25_device_growing_docs  n_grow now (0 for NULL).
+ *   vbm25_device_growing_bytes what the segment has allocated: after an append that includes the second copy of the postings the
+ *                              merge writes into and the room to spare of the buffers (they grow geometrically).
  *   vbm25_search_batch_growing   vbm25_search_batch with the growing segment merged in.
  *   vbm25_batch_set_growing    every later run of the batch merges the segment in (NULL detaches: the batch behaves exactly
  *                              as without); vbm25_batch_device_results then points at the merged records, and kernel_ms
@@ -344,6 +362,9 @@ typedef struct vbm25_device_growing vbm25_device_growing;
 int vbm25_growing_upload(vbm25_index *, const vbm25_growing_desc *, vbm25_device_growing **out);
 void vbm25_device_growing_free(vbm25_device_growing *);
 uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *);
+int vbm25_device_growing_append(vbm25_device_growing *, const vbm25_growing_desc *delta);
+int vbm25_device_growing_delete(vbm25_device_growing *, const uint32_t *g, uint32_t n);
+uint32_t vbm25_device_growing_docs(const vbm25_device_growing *);
 int vbm25_search_batch_growing(vbm25_index *, const vbm25_device_growing *, const uint32_t *term_ids, const uint32_t *q_off,
                                uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits);
 int vbm25_batch_set_growing(vbm25_batch *, const vbm25_device_growing *);
@@ -359,15 +380,17 @@ int vbm25_batch_set_growing(vbm25_batch *, const vbm25_device_growing *);
  *                              bitmaps.  Synchronous.  Bits at or beyond n_grow, a segment of another index -> VBM25_ERR_INVALID.
  *                              The filter names the segment by its upload (each vbm25_growing_upload is a new one, also at a
  *                              re-used address) and keeps no pointer to it: freeing the segment stays legal, the bitmaps then
- *                              match no segment.  A re-upload needs the bitmaps set again.
+ *                              match no segment.  A re-upload needs the bitmaps set again, and so does an append: the bitmaps
+ *                              are sized for the n_grow they were set at (deletes leave them valid).
  *   vbm25_filter_update_growing        replaces growing bitmap i from host memory (as vbm25_filter_update).
  *   vbm25_filter_growing_device_words  device address of growing bitmap i (as vbm25_filter_device_words).
  *   (both: VBM25_ERR_INVALID when the filter has no growing bitmaps)
  *   vbm25_search_batch_growing_filtered  vbm25_search_batch_growing with q_filter[q] (nq selectors) for query q.
  * A batch holds a filter and a growing segment together only when the filter's growing bitmaps are that segment's; the second
  * setter (vbm25_batch_set_filter / vbm25_batch_set_growing, either order) returns VBM25_ERR_UNSUPPORTED when the filter has no
- * growing bitmaps and VBM25_ERR_INVALID when they belong to another upload.  vbm25_batch_run checks again (the filter's growing
- * bitmaps may have been set since): on a mismatch it returns VBM25_ERR_INVALID, enqueues nothing and leaves the batch as it was. */
+ * growing bitmaps and VBM25_ERR_INVALID when they belong to another upload or to another document count (the segment was appended
+ * to since).  vbm25_batch_run checks again (the filter's growing bitmaps may have been set, or the segment appended to, since): on
+ * a mismatch it returns VBM25_ERR_INVALID, enqueues nothing and leaves the batch as it was. */
 int vbm25_filter_set_growing(vbm25_filter *, const vbm25_device_growing *, const uint64_t *words);
 int vbm25_filter_update_growing(vbm25_filter *, uint32_t i, const uint64_t *words);
 int vbm25_filter_growing_device_words(vbm25_filter *, uint32_t i, void **dev);

@@ -236,21 +236,21 @@ inline std::vector<Hit> merge_growing(const std::vector<Hit> &sealed, const std:
 }
 
 // The growing segment of one index in HBM (vbm25_device_growing): the device form of search_growing + merge_growing for a whole
-// batch.  Re-upload (a new object) when the relation's unsealed documents change.
+// batch.  append() the documents the relation gained and erase() those it marked deleted; both change the segment in place.
 class DeviceGrowing {
   public:
     DeviceGrowing(Index &index, const GrowingDocs &g) {
-        vbm25_growing_desc d{};
-        d.n_docs = uint32_t(g.size());
-        d.n_elements = g.tf.size();
-        d.start = g.start.data();
-        d.key = g.key.empty() ? nullptr : g.key[0].data();
-        d.tf = g.tf.data();
-        d.fieldnorm = g.fieldnorm.data();
-        d.payload = g.payload.data();
-        d.deleted = g.deleted.empty() ? nullptr : g.deleted.data();
+        const vbm25_growing_desc d = desc_of(g);
         check(vbm25_growing_upload(index.handle(), &d, &h_));
     }
+    // the new documents only: document i of `delta` becomes growing document docs() + i (vbm25_device_growing_append)
+    void append(const GrowingDocs &delta) {
+        const vbm25_growing_desc d = desc_of(delta);
+        check(vbm25_device_growing_append(h_, &d));
+    }
+    // growing indices below docs(), any order (vbm25_device_growing_delete)
+    void erase(const std::vector<uint32_t> &g) { check(vbm25_device_growing_delete(h_, g.data(), uint32_t(g.size()))); }
+    uint32_t docs() const { return vbm25_device_growing_docs(h_); }
     ~DeviceGrowing() { vbm25_device_growing_free(h_); }
     DeviceGrowing(const DeviceGrowing &) = delete;
     DeviceGrowing &operator=(const DeviceGrowing &) = delete;
@@ -267,6 +267,18 @@ class DeviceGrowing {
     vbm25_device_growing *handle() const { return h_; }
 
   private:
+    static vbm25_growing_desc desc_of(const GrowingDocs &g) {
+        vbm25_growing_desc d{};
+        d.n_docs = uint32_t(g.size());
+        d.n_elements = g.tf.size();
+        d.start = g.start.data();
+        d.key = g.key.empty() ? nullptr : g.key[0].data();
+        d.tf = g.tf.data();
+        d.fieldnorm = g.fieldnorm.data();
+        d.payload = g.payload.data();
+        d.deleted = g.deleted.empty() ? nullptr : g.deleted.data();
+        return d;
+    }
     vbm25_device_growing *h_ = nullptr;
 };
 

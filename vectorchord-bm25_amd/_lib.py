@@ -86,6 +86,9 @@ ABI = {
     "vbm25_growing_upload": (i32, [vp, vp, vp]),
     "vbm25_device_growing_free": (None, [vp]),
     "vbm25_device_growing_bytes": (u64, [vp]),
+    "vbm25_device_growing_append": (i32, [vp, vp]),
+    "vbm25_device_growing_delete": (i32, [vp, vp, u32]),
+    "vbm25_device_growing_docs": (u32, [vp]),
     "vbm25_search_batch_growing": (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
     "vbm25_batch_set_growing": (i32, [vp, vp]),
     "vbm25_filter_set_growing": (i32, [vp, vp, vp]),

@@ -633,6 +633,31 @@ class GrowingSegment:
         """from growing_from_pages(pages)"""
         return cls(index, grow["g_start"], grow["g_key"], grow["g_tf"], grow["g_fieldnorm"], grow["g_payload"], grow.get("g_deleted"))
 
+    def append(self, g_start, g_key, g_tf, g_fieldnorm, g_payload, g_deleted=None):
+        """vbm25_device_growing_append: the CSR of the new documents only (the constructor's form); document i becomes growing
+        document n_docs + i.  Only these arrays cross the host link; a batch that holds the segment sees them at its next run."""
+        g_start = np.ascontiguousarray(g_start, dtype=np.uint64)
+        g_key = np.ascontiguousarray(g_key, dtype=np.uint8).reshape(-1)
+        g_tf = np.ascontiguousarray(g_tf, dtype=np.uint32)
+        g_fieldnorm = np.ascontiguousarray(g_fieldnorm, dtype=np.uint8)
+        g_payload = np.ascontiguousarray(g_payload, dtype=np.uint16).reshape(-1)
+        g_deleted = None if g_deleted is None else np.ascontiguousarray(g_deleted, dtype=np.uint8)
+        if len(g_key) != 16 * len(g_tf):
+            raise ValueError(f"{len(g_key)} key bytes for {len(g_tf)} elements")
+        d = GrowingDesc()
+        d.n_docs, d.n_elements = max(len(g_start) - 1, 0), len(g_tf)
+        d.start, d.key, d.tf = _p(g_start), _p(g_key), _p(g_tf)
+        d.fieldnorm, d.payload, d.deleted = _p(g_fieldnorm), _p(g_payload), _p(g_deleted)
+        try:
+            check(lib().vbm25_device_growing_append(self.h, C.byref(d)))
+        finally:
+            self.n_docs = int(lib().vbm25_device_growing_docs(self.h))
+
+    def delete(self, indices):
+        """vbm25_device_growing_delete: growing documents (indices below n_docs, any order) score nothing from now on."""
+        g = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        check(lib().vbm25_device_growing_delete(self.h, _p(g), len(g)))
+
     @property
     def device_bytes(self):
         return int(lib().vbm25_device_growing_bytes(self.h))

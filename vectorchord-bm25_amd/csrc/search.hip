@@ -71,6 +71,7 @@ int set_error(int code, const char *fmt, ...) {
 #include "scan_many.h"
 #include "merge.h"
 #include "growing.h"
+#include "growing_append.h"
 
 // ---------------------------------------------------------------------------
 // Batched `<&>`: bm25::evaluate (evaluate.rs:22-74) for many documents against one query -- the seq-scan
@@ -241,6 +242,17 @@ struct vbm25_device_growing {
     DeviceBuffer term_start, post_g, post_c, tab_idx, tab, payload;
     std::vector<uint32_t> term_start_host;  // (k > 1024: one accumulation launch per term)
     uint64_t device_bytes = 0;
+    // vbm25_device_growing_append / _delete (growing_append.h).  An append writes the spare arrays and swaps them in at its end; the
+    // postings, the payloads and the tables are buffers with room to spare (their `bytes` is the capacity, grown geometrically).
+    DeviceBuffer term_start2, post_g2, post_c2, tab_idx2, tab2;
+    DeviceBuffer term_key;  // the index's keys (from the first append on)
+    DeviceBuffer stage;     // the delta and the scratch of one call
+    void count_bytes() {    // everything allocated, the room to spare included
+        device_bytes = 0;
+        for (const DeviceBuffer *b : {&term_start, &post_g, &post_c, &tab_idx, &tab, &payload, &term_start2, &post_g2, &post_c2, &tab_idx2,
+                                      &tab2, &term_key, &stage})
+            if (b->p) device_bytes += b->bytes;
+    }
     DevGrowing dev() const {
         DevGrowing g{};
         g.term_start = term_start.as<uint32_t>();
@@ -365,6 +377,7 @@ struct vbm25_batch {
     const vbm25_device_growing *growing = nullptr;
     DeviceBuffer gr_sealed, gr_sealed_cnt, gr_ls, gr_lg, gr_lc, gr_acc, gr_keys, gr_iota, gr_docs, gr_tmp;
     size_t gr_tmp_bytes = 0;
+    uint32_t gr_n = 0;  // growing documents the k > 1024 scratch holds
     std::vector<uint8_t> h_dense;          // per query: dense (scratch of set_queries, sized once)
     std::vector<unsigned long long> h_postings;
     std::vector<uint32_t> h_order, h_order_q;  // set_queries: the longest-first item order of the routes without plan_kernel
@@ -2029,6 +2042,14 @@ static int vbm25_filter_update_impl(vbm25_filter *f, uint32_t i, const uint64_t 
     return VBM25_OK;
 }
 
+// a filter's growing bitmaps are sized for the n_grow they were set at: after vbm25_device_growing_append they are stale until
+// vbm25_filter_set_growing is called again (rejecting the new documents silently would hide inserts from filtered queries)
+static int filter_growing_count_check(const vbm25_filter *f, const vbm25_device_growing *gs) {
+    if (f->grow_n == gs->n_grow) return VBM25_OK;
+    return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps cover %u documents and the growing segment holds %u (appended to since): "
+                                        "set the growing bitmaps again", f->grow_n, gs->n_grow);
+}
+
 // selectors: n_sel of them (query q takes q_filter[q]); the batch's other queries take none
 static int batch_set_filter_impl(vbm25_batch *bt, const vbm25_filter *f, const uint32_t *q_filter, uint32_t n_sel) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
@@ -2038,6 +2059,7 @@ static int batch_set_filter_impl(vbm25_batch *bt, const vbm25_filter *f, const u
             return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a growing segment and the filter has no growing bitmaps");
         if (f->grow_serial != bt->growing->serial)
             return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps belong to another upload than the batch's growing segment");
+        if (int rc = filter_growing_count_check(f, bt->growing)) return rc;
     }
     if (f && !q_filter && n_sel) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
     if (f)
@@ -2114,13 +2136,13 @@ int vbm25_search_batch_filtered(vbm25_index *ix, const vbm25_filter *f, const ui
 // ---------------------------------------------------------------------------
 static std::atomic<uint64_t> g_growing_serial{0};  // uploads so far (vbm25_device_growing::serial)
 
-static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
-    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!ix || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+// the CSR of an upload or of an append's delta: `held_docs` / `held_el` are the growing documents and postings the segment holds already
+static int growing_desc_check(const vbm25_index *ix, const vbm25_growing_desc *d, uint64_t held_docs, uint64_t held_el, uint64_t *e_first_out,
+                              uint64_t *n_el_out) {
     const uint32_t n = d->n_docs;
-    if (uint64_t(ix->n_docs) + n > (1ull << 32))
-        return set_error(VBM25_ERR_INVALID, "%u sealed + %u growing documents exceed 2^32: the doc id ranges would collide", ix->n_docs, n);
+    if (uint64_t(ix->n_docs) + held_docs + n > (1ull << 32))
+        return set_error(VBM25_ERR_INVALID, "%u sealed + %llu growing documents exceed 2^32: the doc id ranges would collide", ix->n_docs,
+                         (unsigned long long)(held_docs + n));
     if (n && (!d->start || !d->fieldnorm || !d->payload)) return set_error(VBM25_ERR_INVALID, "growing arrays missing");
     const uint64_t e_first = n ? d->start[0] : 0, e_end = n ? d->start[n] : 0;
     for (uint32_t g = 0; g < n; ++g)
@@ -2129,12 +2151,24 @@ static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *
                                                 (unsigned long long)d->n_elements);
     const uint64_t n_el = e_end - e_first;
     if (n_el && (!d->key || !d->tf)) return set_error(VBM25_ERR_INVALID, "growing arrays missing");
-    if (n_el >= (1ull << 31)) return set_error(VBM25_ERR_UNSUPPORTED, "%llu growing elements: the device path takes fewer than 2^31",
-                                               (unsigned long long)n_el);
+    if (held_el + n_el >= (1ull << 31)) return set_error(VBM25_ERR_UNSUPPORTED, "%llu growing elements: the device path takes fewer than 2^31",
+                                                         (unsigned long long)(held_el + n_el));
     for (uint32_t g = 0; g < n; ++g)  // Document::checked_new, vector.rs:56-61
         for (uint64_t e = d->start[g] + 1; e < d->start[g + 1]; ++e)
             if (std::memcmp(d->key + 16ull * (e - 1), d->key + 16ull * e, 16) >= 0)
                 return set_error(VBM25_ERR_INVALID, "growing document %u: keys must be strictly ascending", g);
+    *e_first_out = e_first;
+    *n_el_out = n_el;
+    return VBM25_OK;
+}
+
+static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ix || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const uint32_t n = d->n_docs;
+    uint64_t e_first = 0, n_el = 0;
+    if (int rc = growing_desc_check(ix, d, 0, 0, &e_first, &n_el)) return rc;
     if (int rc = use_device(ix->device)) return rc;
     auto gs = std::make_unique<vbm25_device_growing>();
     gs->index = ix;
@@ -2192,14 +2226,207 @@ static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *
     if (n_tab) grow_tab_kernel<<<(n_post + 255) / 256, 256>>>(keys2.as<unsigned long long>(), n_post, gs->dev(), gs->tab.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    for (const DeviceBuffer *b : {&gs->term_start, &gs->post_g, &gs->post_c, &gs->tab_idx, &gs->tab, &gs->payload}) gs->device_bytes += b->bytes;
+    gs->count_bytes();
     *out = gs.release();
+    return VBM25_OK;
+}
+
+// ---------------------------------------------------------------------------
+// vbm25_device_growing_append / vbm25_device_growing_delete (growing_append.h).  Both wait for the device first (a run in flight ends
+// on the old arrays) and return when the segment is the new one.  An append validates, allocates and computes into the spare arrays
+// and the stage, none of which a search reads, and only then swaps them in: a failure at any point leaves the segment as it was.
+// ---------------------------------------------------------------------------
+static void swap_buffers(DeviceBuffer &a, DeviceBuffer &b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+}
+
+// room for `need` bytes in a buffer nobody reads (a spare, the stage); the contents are not kept.  A buffer that is too small is
+// replaced by one half as large again as needed: sizes grow geometrically, a run of small appends allocates (and hipFree
+// synchronises) only now and then.
+static int reserve_spare(DeviceBuffer &b, size_t need) {
+    if (b.p && b.bytes >= need) return VBM25_OK;
+    DeviceBuffer nb;
+    if (int rc = nb.alloc(need + need / 2)) return rc;
+    swap_buffers(b, nb);
+    return VBM25_OK;
+}
+
+constexpr size_t GROW_STAGE_KEEP = 16u << 20;  // a larger stage (a bulk append) is released at the end of the call
+
+static int device_growing_append_impl(vbm25_device_growing *gs, const vbm25_growing_desc *d) {
+    if (!gs || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const vbm25_index *ix = gs->index;
+    uint64_t e_first = 0, n_el = 0;
+    if (int rc = growing_desc_check(ix, d, gs->n_grow, gs->n_post, &e_first, &n_el)) return rc;
+    const uint32_t n = d->n_docs, g0 = gs->n_grow, nt = ix->n_terms;
+    if (!n) return VBM25_OK;
+    if (uint64_t(g0) + n > 0xffffffffull) return set_error(VBM25_ERR_INVALID, "%llu growing documents: at most 2^32 - 1", (unsigned long long)g0 + n);
+    if (int rc = use_device(gs->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old arrays to their end)
+    // on every way out: a stage that a bulk append made larger than GROW_STAGE_KEEP is given back (small appends keep theirs, so a
+    // run of them allocates nothing; a bulk append pays one hipFree, little next to its sort), and device_bytes is counted again
+    struct ReleaseStageAndCount {
+        vbm25_device_growing *gs;
+        ~ReleaseStageAndCount() {
+            if (gs->stage.bytes > GROW_STAGE_KEEP) {
+                DeviceBuffer none;
+                swap_buffers(gs->stage, none);
+            }
+            gs->count_bytes();
+        }
+    } on_exit{gs};
+    const uint32_t n_new = g0 + n, n_tiles = uint32_t((uint64_t(n_new) + GT - 1) / GT);
+    int rc = 0;
+    if (!gs->term_key.p && (rc = gs->term_key.upload(ix->term_key.data(), 16ull * nt))) {  // (once per segment: 16 B per term)
+        DeviceBuffer none;  // a buffer whose copy failed holds no keys
+        swap_buffers(gs->term_key, none);
+        return rc;
+    }
+    // the stage: the delta's arrays, the sort's and the scan's
+    size_t sort_tb = 0, scan_tb = 0, stage_bytes = 0;
+    if (n_el)
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                   (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_el));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(nt + 1u)));
+    auto take = [&](size_t bytes) {
+        const size_t at = stage_bytes;
+        stage_bytes += (bytes + 255u) & ~size_t(255);
+        return at;
+    };
+    const size_t o_start = take(8ull * (n + 1ull)), o_key = take(16ull * n_el), o_tf = take(4ull * n_el), o_fn = take(n), o_del = take(n),
+                 o_keys = take(8ull * n_el), o_vals = take(4ull * n_el), o_keys2 = take(8ull * n_el), o_vals2 = take(4ull * n_el),
+                 o_cnt = take(8), o_ins = take(4ull * n_el), o_flags = take(4ull * (nt + 1ull)), o_offs = take(4ull * (nt + 1ull)),
+                 o_tterm = take(4ull * nt), o_sort = take(sort_tb), o_scan = take(scan_tb);
+    if ((rc = reserve_spare(gs->stage, stage_bytes))) return rc;
+    uint8_t *sp = gs->stage.as<uint8_t>();
+    auto at = [&](size_t o) { return static_cast<void *>(sp + o); };
+    uint64_t *start = static_cast<uint64_t *>(at(o_start));
+    unsigned long long *keys = static_cast<unsigned long long *>(at(o_keys)), *keys2 = static_cast<unsigned long long *>(at(o_keys2));
+    uint32_t *tf = static_cast<uint32_t *>(at(o_tf)), *vals = static_cast<uint32_t *>(at(o_vals)), *vals2 = static_cast<uint32_t *>(at(o_vals2));
+    uint32_t *cnt = static_cast<uint32_t *>(at(o_cnt)), *ins = static_cast<uint32_t *>(at(o_ins)), *flags = static_cast<uint32_t *>(at(o_flags)),
+             *offs = static_cast<uint32_t *>(at(o_offs)), *tterm = static_cast<uint32_t *>(at(o_tterm));
+    uint8_t *fn = static_cast<uint8_t *>(at(o_fn)), *del = static_cast<uint8_t *>(at(o_del));
+    HIP_TRY(hipMemcpy(start, d->start, 8ull * (n + 1ull), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(fn, d->fieldnorm, n, hipMemcpyHostToDevice));
+    if (d->deleted) HIP_TRY(hipMemcpy(del, d->deleted, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(cnt, 0, 8));
+    // 1. the delta's postings as sorted (term, g) keys
+    uint32_t n_dpost = 0;
+    if (n_el) {
+        HIP_TRY(hipMemcpy(at(o_key), d->key + 16ull * e_first, 16ull * n_el, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tf, d->tf + e_first, 4ull * n_el, hipMemcpyHostToDevice));
+        grow_append_map_kernel<<<uint32_t((n_el + 255) / 256), 256>>>(gs->term_key.as<ulonglong2>(), nt, n, g0, start, uint32_t(n_el),
+                                                                      static_cast<const ulonglong2 *>(at(o_key)), tf,
+                                                                      d->deleted ? del : nullptr, keys, vals, cnt);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(at(o_sort), sort_tb, keys, keys2, vals, vals2, (int)n_el));
+        HIP_TRY(hipMemcpy(&n_dpost, cnt, 4, hipMemcpyDeviceToHost));
+    }
+    const uint32_t n_post = gs->n_post + n_dpost;
+    // every array the new segment needs, before anything is written
+    DeviceBuffer new_payload;  // (only when the payloads outgrow their buffer)
+    if ((rc = reserve_spare(gs->post_g2, 4ull * n_post)) || (rc = reserve_spare(gs->post_c2, 8ull * n_post)) ||
+        (rc = reserve_spare(gs->term_start2, 4ull * (nt + 1ull))) || (rc = reserve_spare(gs->tab_idx2, 4ull * nt)))
+        return rc;
+    if (gs->payload.bytes < 6ull * n_new) {
+        if ((rc = new_payload.alloc(6ull * n_new + 3ull * n_new))) return rc;  // (half as much again, as reserve_spare)
+        if (g0) HIP_TRY(hipMemcpyAsync(new_payload.p, gs->payload.p, 6ull * g0, hipMemcpyDeviceToDevice));
+    }
+    uint16_t *payload = new_payload.p ? new_payload.as<uint16_t>() : gs->payload.as<uint16_t>();
+    HIP_TRY(hipMemcpy(payload + 3ull * g0, d->payload, 6ull * n, hipMemcpyHostToDevice));  // (behind the documents the searches read)
+    // 2 - 4. the merged postings and their term starts
+    uint32_t *new_start = gs->term_start2.as<uint32_t>(), *new_g = gs->post_g2.as<uint32_t>();
+    double *new_c = gs->post_c2.as<double>();
+    grow_append_starts_kernel<<<nt / 256 + 1, 256>>>(keys2, n_dpost, nt, gs->term_start.as<uint32_t>(), new_start);
+    if (n_dpost)
+        grow_append_post_kernel<<<(n_dpost + 255) / 256, 256>>>(keys2, vals2, n_dpost, g0, ix->term_s0.as<double>(), ix->s1.as<double>(), fn,
+                                                                gs->term_start.as<uint32_t>(), ins, new_g, new_c);
+    if (gs->n_post)
+        grow_append_move_kernel<<<(gs->n_post + 256 * GA_ITEMS - 1) / (256 * GA_ITEMS), 256>>>(gs->post_g.as<uint32_t>(), gs->post_c.as<double>(),
+                                                                                             gs->n_post, ins, n_dpost, new_g, new_c);
+    HIP_TRY(hipGetLastError());
+    // 5. the tile tables of the new n_tiles
+    uint32_t n_tab = 0;
+    grow_append_flag_kernel<<<nt / 256 + 1, 256>>>(new_start, nt, n_tiles, flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(at(o_scan), scan_tb, flags, offs, (int)(nt + 1u)));
+    HIP_TRY(hipMemcpy(&n_tab, offs + nt, 4, hipMemcpyDeviceToHost));
+    if ((rc = reserve_spare(gs->tab2, 4ull * n_tab))) return rc;
+    if (nt) grow_append_tabidx_kernel<<<(nt + 255) / 256, 256>>>(flags, offs, nt, n_tiles, gs->tab_idx2.as<uint32_t>(), tterm);
+    if (n_tab) grow_append_tab_kernel<<<(n_tab + 255) / 256, 256>>>(tterm, n_tab, n_tiles, new_start, new_g, gs->tab2.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> start_host(nt + 1ull);
+    HIP_TRY(hipMemcpy(start_host.data(), new_start, 4ull * (nt + 1ull), hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
+    // the new segment
+    swap_buffers(gs->term_start, gs->term_start2);
+    swap_buffers(gs->post_g, gs->post_g2);
+    swap_buffers(gs->post_c, gs->post_c2);
+    swap_buffers(gs->tab_idx, gs->tab_idx2);
+    swap_buffers(gs->tab, gs->tab2);
+    if (new_payload.p) swap_buffers(gs->payload, new_payload);
+    gs->term_start_host.swap(start_host);
+    gs->n_grow = n_new;
+    gs->n_tiles = n_tiles;
+    gs->n_post = n_post;
+    return VBM25_OK;
+}
+
+static int device_growing_delete_impl(vbm25_device_growing *gs, const uint32_t *g, uint32_t n) {
+    if (!gs || (!g && n)) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    for (uint32_t i = 0; i < n; ++i)
+        if (g[i] >= gs->n_grow) return set_error(VBM25_ERR_INVALID, "index %u: growing document %u of %u", i, g[i], gs->n_grow);
+    if (!n || !gs->n_post) return VBM25_OK;
+    if (int rc = use_device(gs->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old scores to their end)
+    const size_t o_bits = (4ull * n + 255u) & ~size_t(255), bit_bytes = 4ull * ((gs->n_grow + 31u) / 32u);
+    const int rc = reserve_spare(gs->stage, o_bits + bit_bytes);
+    gs->count_bytes();
+    if (rc) return rc;
+    uint32_t *idx = gs->stage.as<uint32_t>(), *bits = reinterpret_cast<uint32_t *>(gs->stage.as<uint8_t>() + o_bits);
+    HIP_TRY(hipMemcpy(idx, g, 4ull * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(bits, 0, bit_bytes));
+    grow_delete_bits_kernel<<<uint32_t((uint64_t(n) + 255) / 256), 256>>>(idx, n, bits);
+    grow_delete_kernel<<<(gs->n_post + 255) / 256, 256>>>(gs->post_g.as<uint32_t>(), gs->n_post, bits, gs->post_c.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return VBM25_OK;
 }
 
 // lists of growing_scan_kernel: workgroups per query for nq queries (G_MAX_WG in all, at least one per query, at most one per tile)
 static uint32_t growing_gq(uint32_t nq, uint32_t n_tiles) {
     return std::max(1u, std::min(std::max(1u, n_tiles), G_MAX_WG / std::max(nq, 1u)));
+}
+
+// (no run of the batch may be in flight)
+static int batch_grow_buffer(DeviceBuffer &b, size_t bytes) {
+    if (b.p && b.bytes >= bytes) return VBM25_OK;
+    if (b.p) HIP_TRY(hipFree(b.p));
+    b.p = nullptr;
+    return b.alloc(bytes);
+}
+
+// k > 1024: the accumulator, the sort's arrays and the iota for n_grow documents.  Sized when the segment is attached and again by
+// the first run after an append has outgrown them (bt->gr_n).
+static int batch_growing_bigk_scratch(vbm25_batch *bt, uint32_t n_grow) {
+    const size_t n = std::max<size_t>(n_grow, 1);
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                         (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n));
+    const bool new_iota = !bt->gr_iota.p || bt->gr_iota.bytes < 4 * n;
+    int rc = 0;
+    if ((rc = batch_grow_buffer(bt->gr_acc, 8 * n)) || (rc = batch_grow_buffer(bt->gr_keys, 8 * n)) || (rc = batch_grow_buffer(bt->gr_iota, 4 * n)) ||
+        (rc = batch_grow_buffer(bt->gr_docs, 4 * n)) || (rc = batch_grow_buffer(bt->gr_tmp, tb)))
+        return rc;
+    bt->gr_tmp_bytes = bt->gr_tmp.bytes;
+    if (new_iota) {
+        bigk_iota_kernel<<<1024, 256>>>(bt->gr_iota.as<uint32_t>(), uint32_t(bt->gr_iota.bytes / 4));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    bt->gr_n = std::max(bt->gr_n, uint32_t(n));
+    return VBM25_OK;
 }
 
 static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *gs) {
@@ -2210,6 +2437,7 @@ static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *g
             return set_error(VBM25_ERR_UNSUPPORTED, "the batch has a filter without growing bitmaps");
         if (bt->filter->grow_serial != gs->serial)
             return set_error(VBM25_ERR_INVALID, "the batch's filter has growing bitmaps of another upload than this segment");
+        if (int rc = filter_growing_count_check(bt->filter, gs)) return rc;
     }
     if (int rc = use_device(bt->device)) return rc;
     // a run in flight reads the segment and the buffers to its end
@@ -2217,33 +2445,16 @@ static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *g
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     bt->growing = nullptr;
     if (!gs) return VBM25_OK;
-    auto grow = [](DeviceBuffer &b, size_t bytes) -> int {
-        if (b.p && b.bytes >= bytes) return VBM25_OK;
-        if (b.p) HIP_TRY(hipFree(b.p));
-        b.p = nullptr;
-        return b.alloc(bytes);
-    };
     const size_t mq = bt->max_queries, k = bt->k;
     int rc = 0;
-    if ((rc = grow(bt->gr_sealed, sizeof(vbm25_hit) * mq * k)) || (rc = grow(bt->gr_sealed_cnt, 4 * mq))) return rc;
+    if ((rc = batch_grow_buffer(bt->gr_sealed, sizeof(vbm25_hit) * mq * k)) || (rc = batch_grow_buffer(bt->gr_sealed_cnt, 4 * mq))) return rc;
     if (bt->bigk) {
-        const size_t n = std::max<size_t>(gs->n_grow, 1);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                             (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n));
-        const bool new_iota = !bt->gr_iota.p || bt->gr_iota.bytes < 4 * n;
-        if ((rc = grow(bt->gr_acc, 8 * n)) || (rc = grow(bt->gr_keys, 8 * n)) || (rc = grow(bt->gr_iota, 4 * n)) ||
-            (rc = grow(bt->gr_docs, 4 * n)) || (rc = grow(bt->gr_tmp, tb)))
-            return rc;
-        bt->gr_tmp_bytes = bt->gr_tmp.bytes;
-        if (new_iota) {
-            bigk_iota_kernel<<<1024, 256>>>(bt->gr_iota.as<uint32_t>(), uint32_t(bt->gr_iota.bytes / 4));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipDeviceSynchronize());
-        }
+        if ((rc = batch_growing_bigk_scratch(bt, gs->n_grow))) return rc;
     } else {
         const size_t lists = 4ull * std::max<size_t>(G_MAX_WG, mq);  // (nq gq <= max(G_MAX_WG, nq): growing_gq)
-        if ((rc = grow(bt->gr_ls, 8 * lists * k)) || (rc = grow(bt->gr_lg, 4 * lists * k)) || (rc = grow(bt->gr_lc, 4 * lists))) return rc;
+        if ((rc = batch_grow_buffer(bt->gr_ls, 8 * lists * k)) || (rc = batch_grow_buffer(bt->gr_lg, 4 * lists * k)) ||
+            (rc = batch_grow_buffer(bt->gr_lc, 4 * lists)))
+            return rc;
     }
     bt->growing = gs;
     return VBM25_OK;
@@ -2320,8 +2531,15 @@ static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
     // the filter's growing half may have been replaced since the batch took it: nothing is enqueued, the batch stays as it was
     if (bt->filt_on && bt->filter->grow_serial != bt->growing->serial)
         return set_error(VBM25_ERR_INVALID, "the batch's filter has no growing bitmaps of its growing segment (set again since)");
+    if (bt->filt_on)
+        if (int rc = filter_growing_count_check(bt->filter, bt->growing)) return rc;
     if (!bt->nq) return VBM25_OK;
     if (int rc = use_device(bt->index->device)) return rc;
+    if (bt->bigk && std::max(bt->growing->n_grow, 1u) > bt->gr_n) {  // the segment was appended to since the batch took it
+        if (bt->lat_stream) HIP_TRY(hipStreamSynchronize(bt->lat_stream));
+        HIP_TRY(hipStreamSynchronize(bt->last_stream));
+        if (int rc = batch_growing_bigk_scratch(bt, bt->growing->n_grow)) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // timed: the sealed scan through the final merge (the sealed route's own events are off for the run)
     const bool timing = bt->timing;
@@ -2454,6 +2672,13 @@ void vbm25_device_growing_free(vbm25_device_growing *gs) {
     delete gs;
 }
 uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *gs) { return gs ? gs->device_bytes : 0; }
+uint32_t vbm25_device_growing_docs(const vbm25_device_growing *gs) { return gs ? gs->n_grow : 0; }
+int vbm25_device_growing_append(vbm25_device_growing *gs, const vbm25_growing_desc *delta) {
+    return guarded([&] { return device_growing_append_impl(gs, delta); });
+}
+int vbm25_device_growing_delete(vbm25_device_growing *gs, const uint32_t *g, uint32_t n) {
+    return guarded([&] { return device_growing_delete_impl(gs, g, n); });
+}
 int vbm25_search_batch_growing(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
                                uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
     return guarded([&] { return vbm25_search_batch_growing_impl(ix, gs, term_ids, q_off, nq, k, hits, n_hits); });
