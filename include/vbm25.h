@@ -307,7 +307,8 @@ int vbm25_batch_kernel_ms(vbm25_batch *, double *avg_ms, uint32_t *n_launches);
  *                              the batch keeps filter and selectors until they are set again; NULL filter: none.
  *                              Changed bits (update, device_words) take effect at the next run.
  * A filter of another index, or a selector >= F other than UINT32_MAX -> VBM25_ERR_INVALID.
- * vbm25_stream_* and vbm25_multi_* take no filter. */
+ * The pipelined ring takes a filter through vbm25_stream_set_filter / vbm25_stream_submit_filtered and the multi-GPU batch through
+ * vbm25_multi_batch_set_filter (both below). */
 typedef struct vbm25_filter vbm25_filter;
 int vbm25_filter_create(vbm25_index *, uint32_t n_bitmaps, const uint64_t *words, vbm25_filter **out);
 int vbm25_filter_update(vbm25_filter *, uint32_t i, const uint64_t *words);
@@ -357,7 +358,8 @@ int vbm25_batch_set_filter(vbm25_batch *, const vbm25_filter *, const uint32_t *
  *                              as without); vbm25_batch_device_results then points at the merged records, and kernel_ms
  *                              covers the sealed scan through the final merge.
  * A growing segment of another index -> VBM25_ERR_INVALID.  A batch with both a filter and a growing segment needs the filter's
- * growing bitmaps of that segment (below).  vbm25_stream_* and vbm25_multi_* take no growing segment. */
+ * growing bitmaps of that segment (below).  vbm25_stream_set_growing and vbm25_multi_batch_set_growing (below) attach a segment to
+ * the pipelined ring and to the multi-GPU batch. */
 typedef struct vbm25_device_growing vbm25_device_growing;
 int vbm25_growing_upload(vbm25_index *, const vbm25_growing_desc *, vbm25_device_growing **out);
 void vbm25_device_growing_free(vbm25_device_growing *);
@@ -380,8 +382,20 @@ int vbm25_batch_set_growing(vbm25_batch *, const vbm25_device_growing *);
  *                              bitmaps.  Synchronous.  Bits at or beyond n_grow, a segment of another index -> VBM25_ERR_INVALID.
  *                              The filter names the segment by its upload (each vbm25_growing_upload is a new one, also at a
  *                              re-used address) and keeps no pointer to it: freeing the segment stays legal, the bitmaps then
- *                              match no segment.  A re-upload needs the bitmaps set again, and so does an append: the bitmaps
- *                              are sized for the n_grow they were set at (deletes leave them valid).
+ *                              match no segment.  A re-upload needs the bitmaps set again; after an append the bitmaps are stale
+ *                              (they cover the n_grow they were set at) until they are set again or extended (deletes leave them valid).
+ *   vbm25_filter_extend_growing        after vbm25_device_growing_append: extends the F growing bitmaps to the segment's new document
+ *                              count, in place on the device.  The filter must hold growing bitmaps of this upload and n_grow(segment)
+ *                              >= the count they cover (else VBM25_ERR_INVALID).  With d = the difference, words = F x ceil(d / 64)
+ *                              words: bit j of delta bitmap i belongs to growing document (old count + j); NULL = all zero; bits set at
+ *                              or beyond d -> VBM25_ERR_INVALID.  Only the delta crosses the host link: the device ORs it, shifted by
+ *                              (old count % 64), into each bitmap's boundary word and writes the words behind it.  The bitmaps have
+ *                              room to spare that grows geometrically, so most calls touch the tail words only and a growth step
+ *                              re-strides all F bitmaps on the device.  d = 0: VBM25_OK, nothing changes.  Every failure leaves the
+ *                              filter exactly as it was.  Synchronous: waits for the device first, so a run in flight ends on the old
+ *                              bits.  Afterwards the filter is, for every search, what vbm25_filter_set_growing of the concatenated
+ *                              bitmaps would be.  The addresses vbm25_filter_growing_device_words returns may change across the call:
+ *                              ask again.
  *   vbm25_filter_update_growing        replaces growing bitmap i from host memory (as vbm25_filter_update).
  *   vbm25_filter_growing_device_words  device address of growing bitmap i (as vbm25_filter_device_words).
  *   (both: VBM25_ERR_INVALID when the filter has no growing bitmaps)
@@ -393,6 +407,7 @@ int vbm25_batch_set_growing(vbm25_batch *, const vbm25_device_growing *);
  * a mismatch it returns VBM25_ERR_INVALID, enqueues nothing and leaves the batch as it was. */
 int vbm25_filter_set_growing(vbm25_filter *, const vbm25_device_growing *, const uint64_t *words);
 int vbm25_filter_update_growing(vbm25_filter *, uint32_t i, const uint64_t *words);
+int vbm25_filter_extend_growing(vbm25_filter *, const vbm25_device_growing *, const uint64_t *words);
 int vbm25_filter_growing_device_words(vbm25_filter *, uint32_t i, void **dev);
 int vbm25_search_batch_growing_filtered(vbm25_index *, const vbm25_device_growing *, const vbm25_filter *,
                                         const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off,
@@ -408,13 +423,41 @@ int vbm25_search_batch_growing_filtered(vbm25_index *, const vbm25_device_growin
  *   vbm25_stream_collect  waits for the OLDEST batch in flight and writes its records (nq x k hits, nq counts, in
  *                         submission order -- first in, first out); *nq_out = its number of queries.
  *                         VBM25_ERR_INVALID when nothing is in flight.
- * Records are byte-identical to vbm25_search_batch's. */
+ * Records are byte-identical to vbm25_search_batch's.
+ *
+ * A live table on the ring: a growing segment and a filter can be attached to the ring itself.
+ *   vbm25_stream_set_growing    batches submitted afterwards merge the segment in (NULL detaches).
+ *   vbm25_stream_set_filter     batches submitted afterwards with vbm25_stream_submit_filtered take their bitmaps from this filter
+ *                               (NULL detaches).
+ *                               Neither setter waits for anything: a slot of the ring picks up the ring's current segment and filter at
+ *                               its next submit, when it is idle; batches in flight finish with what they were submitted with.  A
+ *                               segment or filter of another index -> VBM25_ERR_INVALID, and the ring keeps what it had.  A segment or
+ *                               filter must not be freed while a batch submitted with it is in flight.
+ *   vbm25_stream_submit_filtered  vbm25_stream_submit with q_filter[q] (nq selectors) for query q.  The selectors go up in the slot's
+ *                               one staged block beside the queries: a filtered step has the same single upload command.  Without a
+ *                               filter set -> VBM25_ERR_INVALID; a selector >= F other than UINT32_MAX -> VBM25_ERR_INVALID.
+ *   vbm25_stream_submit         on a ring that holds a filter filters nothing (every selector UINT32_MAX); it still merges an
+ *                               attached segment.
+ * Pairing, checked at submit with the rules and codes of vbm25_batch_set_filter / vbm25_batch_set_growing: a submit whose selectors
+ * name a bitmap while a segment is attached needs the filter's growing bitmaps of that upload and that document count
+ * (VBM25_ERR_UNSUPPORTED without growing bitmaps, VBM25_ERR_INVALID for another upload or a stale count after an append).  A refused
+ * submit enqueues nothing, leaves vbm25_stream_in_flight as it was and the ring usable.
+ * Records: byte for byte what vbm25_search_batch_growing_filtered (with only one of the two attached: _growing, _filtered) returns
+ * for the query set against the state at submit time, for every k of 1 .. 65535.  With a segment attached a k <= 1024 step still has
+ * no download command: the growing merge writes counts and records into the slot's pinned output.
+ * The snapshot rule: vbm25_device_growing_append, _delete, vbm25_filter_update*, vbm25_filter_set_growing and
+ * vbm25_filter_extend_growing wait for the device before they change anything.  A batch submitted before such a call is searched
+ * against the old state, a batch submitted after it against the new one, whenever they are collected. */
 typedef struct vbm25_stream vbm25_stream;
 int vbm25_stream_create(vbm25_index *, uint32_t depth, uint32_t max_queries, uint32_t max_total_terms, uint32_t k,
                         vbm25_stream **out);
 void vbm25_stream_destroy(vbm25_stream *);
 int vbm25_stream_submit(vbm25_stream *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq);
 int vbm25_stream_collect(vbm25_stream *, vbm25_hit *hits, uint32_t *n_hits, uint32_t *nq_out);
+int vbm25_stream_set_growing(vbm25_stream *, const vbm25_device_growing *);
+int vbm25_stream_set_filter(vbm25_stream *, const vbm25_filter *);
+int vbm25_stream_submit_filtered(vbm25_stream *, const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off,
+                                 uint32_t nq);
 int vbm25_stream_in_flight(const vbm25_stream *);
 
 /* bm25::evaluate (evaluate.rs:22-74) for n_docs documents against ONE query on the device: the seq-scan
@@ -520,6 +563,20 @@ void vbm25_multi_batch_destroy(vbm25_multi_batch *);
 /* A failed vbm25_multi_batch_set_queries leaves every shard holding no queries, as vbm25_batch_set_queries does. */
 int vbm25_multi_batch_set_queries(vbm25_multi_batch *, const uint32_t *term_ids, const uint32_t *q_off,
                                   uint32_t nq);
+/* A live table on several GPUs: the caller builds one growing segment and one filter PER REPLICA, on vbm25_multi_index(m, i), and
+ * hands over the arrays of handles (one entry per replica; a NULL array detaches).  Entry i must belong to replica i's index: otherwise
+ * VBM25_ERR_INVALID and nothing changes on any replica.  The pairing rules and codes are vbm25_batch_set_growing's and
+ * vbm25_batch_set_filter's, applied per replica, before anything changes.
+ *   vbm25_multi_batch_set_growing  every later run merges replica i's segment into shard i's records.
+ *   vbm25_multi_batch_set_filter   q_filter: max_queries selectors (query q of every later query set takes entry q; a selector must
+ *                                  be below every filter's bitmap count or UINT32_MAX).  The selectors are cut by the same shard bounds
+ *                                  as the queries when vbm25_multi_batch_set_queries fixes nq, and travel with the shard's queries: a
+ *                                  filter takes effect at the next vbm25_multi_batch_set_queries.  A NULL array removes the filter at
+ *                                  once.
+ * vbm25_multi_batch_set_queries and vbm25_multi_batch_run check the growing bitmaps again (VBM25_ERR_INVALID after an append without
+ * an extend).  Records are byte-identical to vbm25_search_batch_growing_filtered on one device. */
+int vbm25_multi_batch_set_growing(vbm25_multi_batch *, const vbm25_device_growing *const *per_device);
+int vbm25_multi_batch_set_filter(vbm25_multi_batch *, const vbm25_filter *const *per_device, const uint32_t *q_filter);
 int vbm25_multi_batch_run(vbm25_multi_batch *);
 int vbm25_multi_batch_fetch(vbm25_multi_batch *, vbm25_hit *hits, uint32_t *n_hits);
 

@@ -136,6 +136,10 @@ class DocFilter {
     // growing bitmaps: n_bitmaps x words_per_bitmap(n_grow), or empty for all bits zero; a NULL segment removes them
     inline void set_growing(const DeviceGrowing *growing, const std::vector<uint64_t> &words = {});
     void update_growing(uint32_t i, const std::vector<uint64_t> &words) { check(vbm25_filter_update_growing(h_, i, words.data())); }
+    // after DeviceGrowing::append: the growing bitmaps extended in place to the segment's document count.  words: n_bitmaps x
+    // words_per_bitmap(d) for the d new documents (bit j: growing document old count + j), or empty for all bits zero.  The
+    // addresses growing_device_words returns may change.
+    inline void extend_growing(const DeviceGrowing &growing, const std::vector<uint64_t> &words = {});
     void *growing_device_words(uint32_t i) {
         void *p = nullptr;
         check(vbm25_filter_growing_device_words(h_, i, &p));
@@ -284,6 +288,10 @@ class DeviceGrowing {
 
 inline void DocFilter::set_growing(const DeviceGrowing *growing, const std::vector<uint64_t> &words) {
     check(vbm25_filter_set_growing(h_, growing ? growing->handle() : nullptr, words.empty() ? nullptr : words.data()));
+}
+
+inline void DocFilter::extend_growing(const DeviceGrowing &growing, const std::vector<uint64_t> &words) {
+    check(vbm25_filter_extend_growing(h_, growing.handle(), words.empty() ? nullptr : words.data()));
 }
 
 // per query: the sealed and the growing records merged, query q taking bitmap q_filter[q] of `filter` on both segments

@@ -93,6 +93,7 @@ ABI = {
     "vbm25_batch_set_growing": (i32, [vp, vp]),
     "vbm25_filter_set_growing": (i32, [vp, vp, vp]),
     "vbm25_filter_update_growing": (i32, [vp, u32, vp]),
+    "vbm25_filter_extend_growing": (i32, [vp, vp, vp]),
     "vbm25_filter_growing_device_words": (i32, [vp, u32, vp]),
     "vbm25_search_batch_growing_filtered": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]),
     "vbm25_evaluate_batch": (i32, [vp, vp, u32, u32, vp, vp, vp, vp]),
@@ -113,6 +114,8 @@ ABI = {
     "vbm25_multi_batch_create": (i32, [vp, u32, u32, u32, vp]),
     "vbm25_multi_batch_destroy": (None, [vp]),
     "vbm25_multi_batch_set_queries": (i32, [vp, vp, vp, u32]),
+    "vbm25_multi_batch_set_growing": (i32, [vp, vp]),
+    "vbm25_multi_batch_set_filter": (i32, [vp, vp, vp]),
     "vbm25_multi_batch_run": (i32, [vp]),
     "vbm25_multi_batch_fetch": (i32, [vp, vp, vp]),
     "vbm25_stream_create": (i32, [vp, u32, u32, u32, u32, vp]),
@@ -120,6 +123,9 @@ ABI = {
     "vbm25_stream_submit": (i32, [vp, vp, vp, u32]),
     "vbm25_stream_collect": (i32, [vp, vp, vp, vp]),
     "vbm25_stream_in_flight": (i32, [vp]),
+    "vbm25_stream_set_growing": (i32, [vp, vp]),
+    "vbm25_stream_set_filter": (i32, [vp, vp]),
+    "vbm25_stream_submit_filtered": (i32, [vp, vp, vp, vp, u32]),
 }
 
 

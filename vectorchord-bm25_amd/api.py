@@ -468,6 +468,9 @@ class Stream:
         L = lib()
         check(L.vbm25_stream_create(index.h, depth, max_queries, max(1, max_total_terms), k, C.byref(self.h)))
         self._nq = []
+        self.growing = None     # what the next submit takes (set_growing / set_filter)
+        self.doc_filter = None
+        self._held = []         # per batch in flight: the (segment, filter) it was submitted with, kept alive until its collect
 
     def __del__(self):
         try:
@@ -476,11 +479,32 @@ class Stream:
         except Exception:
             pass
 
-    def submit(self, term_ids, q_off):
+    def set_growing(self, growing):
+        """vbm25_stream_set_growing: batches submitted from now on merge the growing segment in (None detaches); batches in flight
+        keep what they were submitted with.  Waits for nothing."""
+        check(lib().vbm25_stream_set_growing(self.h, growing.h if growing is not None else None))
+        self.growing = growing
+
+    def set_filter(self, doc_filter):
+        """vbm25_stream_set_filter: the filter of later submit(..., q_filter=...) calls (None detaches)."""
+        check(lib().vbm25_stream_set_filter(self.h, doc_filter.h if doc_filter is not None else None))
+        self.doc_filter = doc_filter
+
+    def submit(self, term_ids, q_off, q_filter=None):
+        """vbm25_stream_submit, or with q_filter (one selector per query, NO_FILTER: none) vbm25_stream_submit_filtered."""
         term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
         q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
-        check(lib().vbm25_stream_submit(self.h, term_ids.ctypes.data if len(term_ids) else None, q_off.ctypes.data, len(q_off) - 1))
-        self._nq.append(len(q_off) - 1)  # (only a batch the library accepted is in the ring)
+        nq = len(q_off) - 1
+        if q_filter is None:
+            check(lib().vbm25_stream_submit(self.h, term_ids.ctypes.data if len(term_ids) else None, q_off.ctypes.data, nq))
+        else:
+            q_filter = np.ascontiguousarray(q_filter, dtype=np.uint32).reshape(-1)
+            if len(q_filter) != nq:
+                raise ValueError(f"{len(q_filter)} selectors for {nq} queries")
+            check(lib().vbm25_stream_submit_filtered(self.h, q_filter.ctypes.data if nq else None,
+                                                     term_ids.ctypes.data if len(term_ids) else None, q_off.ctypes.data, nq))
+        self._nq.append(nq)  # (only a batch the library accepted is in the ring)
+        self._held.append((self.growing, self.doc_filter))
 
     def collect_raw(self):
         """collect without this object's bookkeeping (tests: the library's own error on an empty ring)"""
@@ -498,6 +522,8 @@ class Stream:
         got = C.c_uint32()
         check(lib().vbm25_stream_collect(self.h, hits.ctypes.data, n_hits.ctypes.data, C.byref(got)))
         self._nq.pop(0)  # (popped only after the library handed the batch over: an error leaves the bookkeeping in step with the ring)
+        if self._held:
+            self._held.pop(0)
         assert got.value == nq
         return hits, n_hits
 
@@ -516,6 +542,7 @@ class DocFilter:
     def __init__(self, index, keep):
         self.index = index
         self.growing = None  # the GrowingSegment of the growing bitmaps (set_growing)
+        self.grow_n = 0      # ... and the number of its documents they cover (set_growing, extend_growing)
         words = self.pack(keep, index.n_docs)
         self.n_bitmaps, self.words = words.shape
         self.h = C.c_void_p()
@@ -558,6 +585,7 @@ class DocFilter:
         if growing is None:
             check(lib().vbm25_filter_set_growing(self.h, None, None))
             self.growing = None
+            self.grow_n = 0
             return
         words = None
         if keep is not None:
@@ -566,6 +594,21 @@ class DocFilter:
                 raise ValueError(f"{words.shape[0]} growing bitmaps for a filter of {self.n_bitmaps}")
         check(lib().vbm25_filter_set_growing(self.h, growing.h, _p(words)))
         self.growing = growing
+        self.grow_n = growing.n_docs
+
+    def extend_growing(self, growing, keep_new=None):
+        """vbm25_filter_extend_growing: after growing.append(...), extend the F growing bitmaps to the segment's document count in
+        place on the device.  `keep_new` as in the constructor over the d = growing.n_docs - (documents covered so far) NEW
+        documents (bit j: growing document old count + j); None: all bits zero.  Only the delta crosses the host link."""
+        d = growing.n_docs - self.grow_n
+        words = None
+        if keep_new is not None and d > 0:
+            words = self.pack(keep_new, d)
+            if words.shape[0] != self.n_bitmaps:
+                raise ValueError(f"{words.shape[0]} delta bitmaps for a filter of {self.n_bitmaps}")
+        check(lib().vbm25_filter_extend_growing(self.h, growing.h, _p(words)))
+        self.growing = growing
+        self.grow_n = growing.n_docs
 
     def update_growing(self, i, keep_i):
         """vbm25_filter_update_growing: replace growing bitmap i (bool array [n_grow] or growing document ids)."""
@@ -760,6 +803,16 @@ class MultiIndex:
         except Exception:
             pass
 
+    def index(self, i):
+        """vbm25_multi_index: replica i as a GpuIndex that does not own its handle (for lookup_terms, and to build that replica's
+        DocFilter and GrowingSegment on); it keeps this MultiIndex alive."""
+        ix = _ReplicaIndex.__new__(_ReplicaIndex)
+        ix.h = C.c_void_p()
+        check(lib().vbm25_multi_index(self.h, int(i), C.byref(ix.h)))
+        ix.n_terms, ix.n_docs = self.segment.n_terms, self.segment.n_docs
+        ix.multi = self
+        return ix
+
     def search_batch(self, term_ids, q_off, k):
         """vbm25_multi_search_batch: as search_batch(), the batch cut into contiguous shards over the replicas."""
         term_ids = np.ascontiguousarray(term_ids, dtype=np.uint32)
@@ -772,12 +825,21 @@ class MultiIndex:
         return hits, n_hits
 
 
+class _ReplicaIndex(GpuIndex):
+    """A replica of a MultiIndex (MultiIndex.index): a GpuIndex whose handle belongs to the vbm25_multi."""
+
+    def __del__(self):  # (the handle is borrowed: nothing to destroy)
+        pass
+
+
 class MultiBatch:
     """vbm25_multi_batch_*: the shards resident on their devices; run() is asynchronous on every device's stream
     (scan + download of the records), fetch() waits for all of them."""
 
     def __init__(self, multi, max_queries, max_total_terms, k):
-        self.multi, self.k, self.nq = multi, k, 0
+        self.multi, self.k, self.nq, self.max_queries = multi, k, 0, max_queries
+        self.growing = None      # per replica (set_growing / set_filter): kept alive with the batch
+        self.doc_filters = None
         self.h = C.c_void_p()
         check(lib().vbm25_multi_batch_create(multi.h, max_queries, max(1, max_total_terms), k, C.byref(self.h)))
 
@@ -797,6 +859,39 @@ class MultiBatch:
             self.nq = 0  # (every shard is left with no queries: include/vbm25.h)
             raise
         self.nq = len(q_off) - 1
+
+    def set_growing(self, growing):
+        """vbm25_multi_batch_set_growing: one GrowingSegment per replica (built on multi.index(i)), or None to detach."""
+        if growing is None:
+            check(lib().vbm25_multi_batch_set_growing(self.h, None))
+            self.growing = None
+            return
+        growing = list(growing)
+        if len(growing) != self.multi.n_devices:
+            raise ValueError(f"{len(growing)} growing segments for {self.multi.n_devices} replicas")
+        arr = (C.c_void_p * len(growing))(*[g.h.value if g is not None else None for g in growing])
+        check(lib().vbm25_multi_batch_set_growing(self.h, arr))
+        self.growing = growing
+
+    def set_filter(self, doc_filters, q_filter=None):
+        """vbm25_multi_batch_set_filter: one DocFilter per replica (built on multi.index(i)) and the batch's selectors (query q of
+        every later query set takes q_filter[q]; entries beyond the array: NO_FILTER).  None removes the filter."""
+        if doc_filters is None:
+            check(lib().vbm25_multi_batch_set_filter(self.h, None, None))
+            self.doc_filters = None
+            return
+        doc_filters = list(doc_filters)
+        if len(doc_filters) != self.multi.n_devices:
+            raise ValueError(f"{len(doc_filters)} filters for {self.multi.n_devices} replicas")
+        sel = np.full(self.max_queries, NO_FILTER, dtype=np.uint32)
+        if q_filter is not None:
+            q_filter = np.asarray(q_filter, dtype=np.uint32).reshape(-1)
+            if len(q_filter) > self.max_queries:
+                raise ValueError(f"{len(q_filter)} selectors for a batch of {self.max_queries} queries")
+            sel[:len(q_filter)] = q_filter
+        arr = (C.c_void_p * len(doc_filters))(*[f.h.value for f in doc_filters])
+        check(lib().vbm25_multi_batch_set_filter(self.h, arr, _p(sel)))
+        self.doc_filters = doc_filters
 
     def run(self):
         check(lib().vbm25_multi_batch_run(self.h))

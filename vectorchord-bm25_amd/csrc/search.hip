@@ -230,7 +230,11 @@ struct vbm25_filter {
     uint64_t grow_serial = 0;  // the growing bitmaps' segment (vbm25_device_growing::serial), 0: none
     uint32_t grow_n = 0;       // ... its n_grow
     uint32_t grow_words = 0;   // per growing bitmap: ceil(grow_n / 64)
-    DeviceBuffer grow_bits;    // n_bitmaps x grow_words
+    // ... its capacity in words, >= grow_words: bitmap i starts at word i grow_stride (vbm25_filter_set_growing sizes it exactly,
+    // vbm25_filter_extend_growing grows it geometrically).  Every bit at or beyond grow_n is zero, up to the capacity.
+    uint32_t grow_stride = 0;
+    DeviceBuffer grow_bits;    // n_bitmaps x grow_stride
+    DeviceBuffer grow_stage;   // vbm25_filter_extend_growing: the delta words of one call
 };
 
 // The growing segment of one index in HBM on its device (vbm25_growing_upload; growing.h has the layout)
@@ -317,9 +321,11 @@ enum class Route {
 };
 
 // The staged descriptors, one block in pinned memory (pin_in) and on the device (qin): term ids at 0, then the byte offsets of the
-// query offsets, the dense flags (padded to 8), the host's item order and the id16 block starts, and the end of the block
+// query offsets, the dense flags (padded to 8), the host's item order, the id16 block starts and the filter selectors (stage_sel), and
+// the end of the block
 struct StagedLayout {
     size_t off = 0, dense = 0, order = 0, id16 = 0, end = 0;
+    size_t sel = 0;  // the filter selectors of a staged filtered query set (nq words in front of `end`), 0: none staged
 };
 static StagedLayout staged_layout(uint32_t nq, uint32_t n_term_pos, size_t n_order, bool id16) {
     StagedLayout L;
@@ -372,6 +378,9 @@ struct vbm25_batch {
     DeviceBuffer filt_sel;
     std::vector<uint32_t> h_filt_sel;
     bool filt_on = false;
+    // vbm25_stream_* / vbm25_multi_*: the selectors of the query set being set (nq of them, host memory, for the duration of
+    // set_queries): they go up in the staged block (StagedLayout::sel), not through filt_sel
+    const uint32_t *stage_sel = nullptr;
     // growing segment (vbm25_batch_set_growing): merged into the records by every run (growing.h).  gr_*: the sealed records' copy,
     // the per-workgroup lists of growing_scan_kernel (k <= 1024) or the dense accumulator and its sort (k > 1024)
     const vbm25_device_growing *growing = nullptr;
@@ -407,7 +416,8 @@ struct vbm25_batch {
     hipStream_t last_stream = nullptr;  // the stream of the last run: what fetch waits for (not the whole device)
     bool download_enqueued = false;     // the last run's records are already on their way to pin_out (vbm25_multi_batch_run)
     // vbm25_stream_*: merge_kernel writes counts and records straight into the pinned output buffer (posted writes over PCIe, no
-    // download command on the step: only the 4-byte flag is copied); results_pinned_now: the last run did so
+    // download command on the step: only the 4-byte flag is copied); results_pinned_now: the last run did so.  With a growing segment
+    // attached the sealed route writes device records and growing_merge_kernel the pinned ones (growing_enqueue).
     bool pinned_results = false, results_pinned_now = false;
     uint8_t *pin_in = nullptr, *pin_out = nullptr;
     size_t pin_in_bytes = 0, pin_out_bytes = 0;
@@ -888,7 +898,7 @@ static int vbm25_batch_create_impl(vbm25_index *ix, uint32_t max_queries, uint32
         (rc = bt->hits.alloc(sizeof(vbm25_hit) * size_t(max_queries) * k)) ||
         (rc = bt->n_hits.alloc(4ull * max_queries)) || (rc = bt->error_flag.alloc(4)) ||
         (rc = bt->q_dense.alloc(max_queries)) ||
-        (rc = bt->qin.alloc(8ull * max_total_terms + 4ull * (max_queries + 1) + max_queries + 8 + 4ull * bt->max_items + 64)) ||
+        (rc = bt->qin.alloc(8ull * max_total_terms + 4ull * (max_queries + 1) + max_queries + 8 + 4ull * bt->max_items + 4ull * max_queries + 64)) ||
         (rc = bt->id16_fb.alloc(4ull * max_total_terms)) ||
         (rc = bt->item_failed.alloc(4ull * bt->max_items)) || (rc = bt->item_order.alloc(4ull * bt->max_items)) || (rc = bt->work_ctr.alloc(8)) ||
         (rc = bt->hist.alloc(4ull * CUR_HB * max_queries)) || (rc = bt->fused_state.alloc(4ull * (max_queries + 1))) ||
@@ -1170,7 +1180,10 @@ static int commit_queries(vbm25_batch *bt, const uint32_t *term_ids, const uint3
             std::memcpy(bt->pin_in + L.off, q_off, L.dense - L.off);
             if (nq) std::memcpy(bt->pin_in + L.dense, bt->h_dense.data(), nq);
             if (L.id16 > L.order) std::memcpy(bt->pin_in + L.order, bt->h_order.data(), L.id16 - L.order);
-            if (L.end > L.id16) std::memcpy(bt->pin_in + L.id16, bt->h_id16_fb.data(), L.end - L.id16);
+            if (L.sel) {
+                if (L.sel > L.id16) std::memcpy(bt->pin_in + L.id16, bt->h_id16_fb.data(), L.sel - L.id16);
+                std::memcpy(bt->pin_in + L.sel, bt->stage_sel, L.end - L.sel);
+            } else if (L.end > L.id16) std::memcpy(bt->pin_in + L.id16, bt->h_id16_fb.data(), L.end - L.id16);
             if (!(plan.route == Route::OneLaunch && plan.fused_pinned))
                 if (int rc = upload_staged(bt, L)) return rc;
         } else {
@@ -1230,6 +1243,10 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
     if (q_off[nq] > bt->max_terms) return set_error(VBM25_ERR_INVALID, "%u terms exceed the batch capacity %u", q_off[nq], bt->max_terms);
     if (bt->bigk) plan.route = Route::Exhaustive;
     else plan_route(bt, term_ids, q_off, nq, fast, many, n_dense, plan);
+    if (fast && bt->stage_sel && nq && plan.route != Route::Exhaustive) {  // the selectors ride in the staged block: one upload command
+        plan.staged.sel = plan.staged.end;
+        plan.staged.end += 4ull * nq;
+    }
     return commit_queries(bt, term_ids, q_off, nq, fast, plan);
 }
 
@@ -1326,6 +1343,8 @@ static DevBatch dev_batch(const vbm25_batch *bt) {
     if (bt->filt_on) {
         db.filt_words = bt->filter->bits.as<unsigned long long>();
         db.filt_sel = bt->filt_sel.as<uint32_t>();
+        if (bt->plan.staged.sel)  // staged with the queries (a run that reads them from pinned memory: run_one_launch)
+            db.filt_sel = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + bt->plan.staged.sel);
         db.filt_stride = bt->filter->words;
     }
     db.error_flag = bt->error_flag.as<uint32_t>();
@@ -1390,6 +1409,7 @@ static int run_one_launch(vbm25_batch *bt, hipStream_t st, DevBatch db) {
     if (plan.fused_pinned) {  // queries read from, hits written to pinned host memory
         db.term_ids = reinterpret_cast<const uint32_t *>(bt->pin_in);
         db.q_off = reinterpret_cast<const uint32_t *>(bt->pin_in + plan.staged.off);
+        if (bt->filt_on && plan.staged.sel) db.filt_sel = reinterpret_cast<const uint32_t *>(bt->pin_in + plan.staged.sel);
         db.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
         db.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + pin_out_records(bt->nq));
     }
@@ -1471,7 +1491,7 @@ static int run_window(vbm25_batch *bt, hipStream_t st, DevBatch db) {
         // plane (decode_id16.h) -- inside the timed region: kernel_ms is the decode and the scan.
         const StagedLayout &L = plan.staged;
         db.id16_fb = bt->id16_fb.as<uint32_t>();
-        if (bt->qin_live && L.end > L.id16) db.id16_fb = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + L.id16);
+        if (bt->qin_live && (L.sel ? L.sel : L.end) > L.id16) db.id16_fb = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + L.id16);
         if (plan.n_term_pos) decode_id16_kernel<<<plan.n_term_pos, DI_WAVES * 64, 0, st>>>(ix, db.term_ids, db.id16_fb, bt->id16_tmp.as<uint32_t>());
         DevIndex ixw = ix;
         ixw.post_id16 = bt->id16_tmp.as<uint32_t>();
@@ -2132,7 +2152,8 @@ int vbm25_search_batch_filtered(vbm25_index *ix, const vbm25_filter *f, const ui
 // run of a batch it is attached to.  The sealed route of such a batch is the one vbm25_batch_device_results forces (complete records
 // on the device after the scan: no one-launch scan_win_kernel run that leaves a query to the fetch, no records written straight into
 // pinned host memory); the growing kernels read a copy of those records and write the merged ones in their place, so a re-run merges
-// from the new sealed records again.
+// from the new sealed records again.  On vbm25_stream_* and vbm25_multi_* (k <= 1024) the merged records go straight into the batch's
+// pinned output instead and the sealed records are read where they lie, without the copy (growing_enqueue).
 // ---------------------------------------------------------------------------
 static std::atomic<uint64_t> g_growing_serial{0};  // uploads so far (vbm25_device_growing::serial)
 
@@ -2429,6 +2450,20 @@ static int batch_growing_bigk_scratch(vbm25_batch *bt, uint32_t n_grow) {
     return VBM25_OK;
 }
 
+// the buffers a batch needs to merge `gs` in (sized by the batch's shape, the k > 1024 scratch by n_grow): no run of the batch may be
+// in flight.  Nothing is allocated once they fit.
+static int batch_growing_buffers(vbm25_batch *bt, const vbm25_device_growing *gs) {
+    const size_t mq = bt->max_queries, k = bt->k;
+    int rc = 0;
+    if ((rc = batch_grow_buffer(bt->gr_sealed, sizeof(vbm25_hit) * mq * k)) || (rc = batch_grow_buffer(bt->gr_sealed_cnt, 4 * mq))) return rc;
+    if (bt->bigk) return std::max(gs->n_grow, 1u) > bt->gr_n ? batch_growing_bigk_scratch(bt, gs->n_grow) : int(VBM25_OK);
+    const size_t lists = 4ull * std::max<size_t>(G_MAX_WG, mq);  // (nq gq <= max(G_MAX_WG, nq): growing_gq)
+    if ((rc = batch_grow_buffer(bt->gr_ls, 8 * lists * k)) || (rc = batch_grow_buffer(bt->gr_lg, 4 * lists * k)) ||
+        (rc = batch_grow_buffer(bt->gr_lc, 4 * lists)))
+        return rc;
+    return VBM25_OK;
+}
+
 static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *gs) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
     if (gs && gs->index != bt->index) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
@@ -2445,17 +2480,7 @@ static int batch_set_growing_impl(vbm25_batch *bt, const vbm25_device_growing *g
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     bt->growing = nullptr;
     if (!gs) return VBM25_OK;
-    const size_t mq = bt->max_queries, k = bt->k;
-    int rc = 0;
-    if ((rc = batch_grow_buffer(bt->gr_sealed, sizeof(vbm25_hit) * mq * k)) || (rc = batch_grow_buffer(bt->gr_sealed_cnt, 4 * mq))) return rc;
-    if (bt->bigk) {
-        if ((rc = batch_growing_bigk_scratch(bt, gs->n_grow))) return rc;
-    } else {
-        const size_t lists = 4ull * std::max<size_t>(G_MAX_WG, mq);  // (nq gq <= max(G_MAX_WG, nq): growing_gq)
-        if ((rc = batch_grow_buffer(bt->gr_ls, 8 * lists * k)) || (rc = batch_grow_buffer(bt->gr_lg, 4 * lists * k)) ||
-            (rc = batch_grow_buffer(bt->gr_lc, 4 * lists)))
-            return rc;
-    }
+    if (int rc = batch_growing_buffers(bt, gs)) return rc;
     bt->growing = gs;
     return VBM25_OK;
 }
@@ -2465,10 +2490,20 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
     const vbm25_device_growing *gs = bt->growing;
     const uint32_t nq = bt->nq, k = bt->k;
     const DevGrowing G = gs->dev();
-    HIP_TRY(hipMemcpyAsync(bt->gr_sealed.p, bt->hits.p, sizeof(vbm25_hit) * size_t(nq) * k, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(bt->gr_sealed_cnt.p, bt->n_hits.p, 4ull * nq, hipMemcpyDeviceToDevice, st));
-    const vbm25_hit *sealed = bt->gr_sealed.as<vbm25_hit>();
-    const uint32_t *sealed_cnt = bt->gr_sealed_cnt.as<uint32_t>();
+    // vbm25_stream_* and vbm25_multi_* (k <= 1024): growing_merge_kernel writes the final counts and records straight into the slot's
+    // pinned output, as merge_kernel does without a segment -- no download command on the step.  The merged records then do not
+    // replace the sealed ones, so the two device-to-device copies in front of the scan go too: the growing kernels read the sealed
+    // route's records where its last kernel left them.
+    const bool pinned = bt->pinned_results && !bt->bigk && bt->lat_stream && st == bt->lat_stream && bt->pin_out &&
+                        bt->pin_out_bytes >= pin_out_records(nq) + sizeof(vbm25_hit) * size_t(nq) * k;
+    const vbm25_hit *sealed = bt->hits.as<vbm25_hit>();
+    const uint32_t *sealed_cnt = bt->n_hits.as<uint32_t>();
+    if (!pinned) {
+        HIP_TRY(hipMemcpyAsync(bt->gr_sealed.p, bt->hits.p, sizeof(vbm25_hit) * size_t(nq) * k, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(bt->gr_sealed_cnt.p, bt->n_hits.p, 4ull * nq, hipMemcpyDeviceToDevice, st));
+        sealed = bt->gr_sealed.as<vbm25_hit>();
+        sealed_cnt = bt->gr_sealed_cnt.as<uint32_t>();
+    }
     if (bt->bigk) {
         const uint32_t n = std::max(gs->n_grow, 1u);
         for (uint32_t q = 0; q < nq; ++q) {
@@ -2481,7 +2516,7 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
             }
             if (bt->filt_on && bt->h_filt_sel[q] != UINT32_MAX && gs->n_grow)
                 bigk_mask_kernel<<<std::min<uint32_t>((gs->n_grow + 255) / 256, 4096u), 256, 0, st>>>(
-                    bt->filter->grow_bits.as<unsigned long long>() + size_t(bt->h_filt_sel[q]) * bt->filter->grow_words, gs->n_grow,
+                    bt->filter->grow_bits.as<unsigned long long>() + size_t(bt->h_filt_sel[q]) * bt->filter->grow_stride, gs->n_grow,
                     bt->gr_acc.as<double>());
             size_t tmp = bt->gr_tmp_bytes;
             HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(bt->gr_tmp.p, tmp, bt->gr_acc.as<unsigned long long>(),
@@ -2511,10 +2546,15 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
     a.lc = bt->gr_lc.as<uint32_t>();
     a.hits = bt->hits.as<vbm25_hit>();
     a.n_hits = bt->n_hits.as<uint32_t>();
+    if (pinned) {
+        a.n_hits = reinterpret_cast<uint32_t *>(bt->pin_out + 8);
+        a.hits = reinterpret_cast<vbm25_hit *>(bt->pin_out + pin_out_records(nq));
+    }
     if (bt->filt_on) {  // (batch_run_growing_impl checked that the growing bitmaps are this segment's)
         a.filt_words = bt->filter->grow_bits.as<uint32_t>();
         a.filt_sel = bt->filt_sel.as<uint32_t>();
-        a.filt_stride = 2u * bt->filter->grow_words;
+        if (bt->plan.staged.sel) a.filt_sel = reinterpret_cast<const uint32_t *>(bt->qin.as<uint8_t>() + bt->plan.staged.sel);
+        a.filt_stride = 2u * bt->filter->grow_stride;
     }
     (void)dispatch_k(k, [&](auto kmax) {
         constexpr int KM = decltype(kmax)::value;
@@ -2524,6 +2564,7 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
         return int(VBM25_OK);
     });
     HIP_TRY(hipGetLastError());
+    bt->results_pinned_now = pinned;  // (vbm25_batch_enqueue_download: only the flag is copied)
     return VBM25_OK;
 }
 
@@ -2541,6 +2582,12 @@ static int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
         if (int rc = batch_growing_bigk_scratch(bt, bt->growing->n_grow)) return rc;
     }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (bt->plan.route == Route::OneLaunch && bt->plan.fused_pinned) {
+        // the one-launch route's own pinned write would publish unmerged sealed records: with a segment attached it reads the queries
+        // from the device block and leaves its records on the device, where the growing kernels find them
+        if (int rc = upload_staged(bt, bt->plan.staged)) return rc;
+        bt->plan.fused_pinned = false;
+    }
     // timed: the sealed scan through the final merge (the sealed route's own events are off for the run)
     const bool timing = bt->timing;
     hipEvent_t e1;
@@ -2602,6 +2649,7 @@ static int vbm25_filter_set_growing_impl(vbm25_filter *f, const vbm25_device_gro
     f->grow_serial = gs ? gs->serial : 0;
     f->grow_n = gs ? gs->n_grow : 0;
     f->grow_words = gw;
+    f->grow_stride = gw;
     return VBM25_OK;
 }
 
@@ -2613,7 +2661,62 @@ static int vbm25_filter_update_growing_impl(vbm25_filter *f, uint32_t i, const u
     if (int rc = use_device(f->device)) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old bits to their end)
     if (f->grow_words)
-        HIP_TRY(hipMemcpy(f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_words, words, 8ull * f->grow_words, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_stride, words, 8ull * f->grow_words, hipMemcpyHostToDevice));
+    return VBM25_OK;
+}
+
+// Growing bitmaps extended in place after vbm25_device_growing_append: only the delta's F x ceil(d / 64) words cross the host link,
+// filter_extend_growing_kernel (growing.h) merges them in.  The bitmaps have a capacity in words (grow_stride) that grows
+// geometrically: most calls keep the stride and touch the tail words only, a growth step re-strides all F bitmaps into a new buffer
+// on the device.  Everything that can fail short of the device itself comes before the filter changes.
+static int vbm25_filter_extend_growing_impl(vbm25_filter *f, const vbm25_device_growing *gs, const uint64_t *words) {
+    if (!f || !gs) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!f->grow_serial) return set_error(VBM25_ERR_INVALID, "the filter has no growing bitmaps");
+    if (f->grow_serial != gs->serial) return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps belong to another upload than this segment");
+    if (gs->n_grow < f->grow_n)
+        return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps cover %u documents, the segment holds %u", f->grow_n, gs->n_grow);
+    const uint32_t d = gs->n_grow - f->grow_n;
+    if (d == 0) return VBM25_OK;
+    const uint32_t dw = (d + 63u) / 64u, F = f->n_bitmaps, n_old = f->grow_n, new_words = (gs->n_grow + 63u) / 64u;
+    if (words && (d & 63u))
+        for (uint32_t i = 0; i < F; ++i)
+            if ((words[size_t(i) * dw + dw - 1] >> (d & 63u)) != 0)
+                return set_error(VBM25_ERR_INVALID, "delta bitmap %u has bits set at or beyond the %u new documents", i, d);
+    if (int rc = use_device(f->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (runs in flight read the old bits to their end)
+    const unsigned long long *delta = nullptr;
+    if (words) {
+        const size_t bytes = 8ull * F * dw;
+        if (!f->grow_stage.p || f->grow_stage.bytes < bytes)
+            if (int rc = batch_grow_buffer(f->grow_stage, std::max(bytes, 2 * f->grow_stage.bytes))) return rc;
+        HIP_TRY(hipMemcpy(f->grow_stage.p, words, bytes, hipMemcpyHostToDevice));
+        delta = f->grow_stage.as<unsigned long long>();
+    }
+    auto launch = [&](const unsigned long long *src, uint32_t src_stride, unsigned long long *dst, uint32_t dst_stride, uint32_t w0) {
+        const unsigned long long total = (unsigned long long)F * (new_words - w0);
+        const uint32_t grid = uint32_t(std::min<unsigned long long>((total + 255) / 256, 4096));
+        filter_extend_growing_kernel<<<grid, 256>>>(src, src_stride, f->grow_words, dst, dst_stride, F, n_old, delta, dw, w0, new_words);
+    };
+    if (new_words <= f->grow_stride) {
+        if (delta) {  // (an all-zero delta: the words beyond the old count are zero already)
+            launch(f->grow_bits.as<unsigned long long>(), f->grow_stride, f->grow_bits.as<unsigned long long>(), f->grow_stride, n_old >> 6);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipDeviceSynchronize());
+        }
+    } else {
+        const uint32_t stride = uint32_t(std::min<uint64_t>(std::max<uint64_t>(new_words, 2ull * f->grow_stride), 1ull << 26));
+        DeviceBuffer nb;
+        if (int rc = nb.alloc(8ull * F * stride)) return rc;
+        HIP_TRY(hipMemset(nb.p, 0, nb.bytes));
+        launch(f->grow_bits.as<unsigned long long>(), f->grow_stride, nb.as<unsigned long long>(), stride, 0u);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        std::swap(f->grow_bits.p, nb.p);
+        std::swap(f->grow_bits.bytes, nb.bytes);
+        f->grow_stride = stride;
+    }
+    f->grow_n = gs->n_grow;
+    f->grow_words = new_words;
     return VBM25_OK;
 }
 
@@ -2646,11 +2749,14 @@ int vbm25_filter_set_growing(vbm25_filter *f, const vbm25_device_growing *gs, co
 int vbm25_filter_update_growing(vbm25_filter *f, uint32_t i, const uint64_t *words) {
     return guarded([&] { return vbm25_filter_update_growing_impl(f, i, words); });
 }
+int vbm25_filter_extend_growing(vbm25_filter *f, const vbm25_device_growing *gs, const uint64_t *words) {
+    return guarded([&] { return vbm25_filter_extend_growing_impl(f, gs, words); });
+}
 int vbm25_filter_growing_device_words(vbm25_filter *f, uint32_t i, void **dev) {
     if (!f || !dev) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (!f->grow_serial) return set_error(VBM25_ERR_INVALID, "the filter has no growing bitmaps");
     if (i >= f->n_bitmaps) return set_error(VBM25_ERR_INVALID, "bitmap %u of a filter of %u", i, f->n_bitmaps);
-    *dev = f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_words;
+    *dev = f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_stride;
     return VBM25_OK;
 }
 int vbm25_search_batch_growing_filtered(vbm25_index *ix, const vbm25_device_growing *gs, const vbm25_filter *f, const uint32_t *q_filter,
@@ -2691,6 +2797,11 @@ int vbm25_batch_set_growing(vbm25_batch *bt, const vbm25_device_growing *gs) {
 struct vbm25_stream {
     std::vector<vbm25_batch *> slots;
     uint32_t head = 0, in_flight = 0;  // the oldest batch in flight, their number
+    vbm25_index *index = nullptr;
+    // what the next submit takes (vbm25_stream_set_growing / _set_filter): a slot picks them up when it is idle, at its next submit --
+    // the batches in flight keep what they were submitted with, and the setters wait for nobody
+    const vbm25_device_growing *growing = nullptr;
+    const vbm25_filter *filter = nullptr;
     ~vbm25_stream() {
         for (vbm25_batch *b : slots) vbm25_batch_destroy(b);
     }
@@ -2707,17 +2818,86 @@ static int stream_create_impl(vbm25_index *ix, uint32_t depth, uint32_t max_quer
         b->pinned_results = true;
         s->slots.push_back(b);
     }
+    s->index = ix;
     *out = s.release();
     return VBM25_OK;
 }
-static int stream_submit_impl(vbm25_stream *s, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
+static int stream_set_growing_impl(vbm25_stream *s, const vbm25_device_growing *gs) {
+    if (!s) return set_error(VBM25_ERR_INVALID, "stream is NULL");
+    if (gs && gs->index != s->index) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    s->growing = gs;
+    return VBM25_OK;
+}
+static int stream_set_filter_impl(vbm25_stream *s, const vbm25_filter *f) {
+    if (!s) return set_error(VBM25_ERR_INVALID, "stream is NULL");
+    if (f && f->index != s->index) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
+    s->filter = f;
+    return VBM25_OK;
+}
+// An idle batch (a ring slot, a shard) takes the segment, the filter and the selectors of its next query set: sel = nq selectors that
+// go up with the queries in the staged block (k > 1024: read on the host), NULL or all UINT32_MAX = no filter.  The pairing rules of
+// vbm25_batch_set_filter / _set_growing, checked before anything changes; no copy, no synchronisation.
+static int batch_attach_check(const vbm25_batch *b, const vbm25_device_growing *gs, const vbm25_filter *f, const uint32_t *sel, uint32_t nq,
+                              bool *on_out) {
+    if (gs && gs->index != b->index) return set_error(VBM25_ERR_INVALID, "the growing segment belongs to another index");
+    if (f && f->index != b->index) return set_error(VBM25_ERR_INVALID, "the filter belongs to another index");
+    bool on = false;
+    if (f && sel)
+        for (uint32_t q = 0; q < nq; ++q) {
+            if (sel[q] == UINT32_MAX) continue;
+            if (sel[q] >= f->n_bitmaps)
+                return set_error(VBM25_ERR_INVALID, "query %u: selector %u, the filter has %u bitmaps", q, sel[q], f->n_bitmaps);
+            on = true;
+        }
+    if (on && gs) {
+        if (!f->grow_serial) return set_error(VBM25_ERR_UNSUPPORTED, "a growing segment is attached and the filter has no growing bitmaps");
+        if (f->grow_serial != gs->serial)
+            return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps belong to another upload than the attached growing segment");
+        if (int rc = filter_growing_count_check(f, gs)) return rc;
+    }
+    *on_out = on;
+    return VBM25_OK;
+}
+static int batch_attach(vbm25_batch *b, const vbm25_device_growing *gs, const vbm25_filter *f, const uint32_t *sel, uint32_t nq, bool on) {
+    if (gs) {
+        if (int rc = use_device(b->device)) return rc;
+        if (int rc = batch_growing_buffers(b, gs)) {
+            b->growing = nullptr;
+            return rc;
+        }
+    }
+    b->growing = gs;
+    b->filter = on ? f : nullptr;
+    b->filt_on = on;
+    b->stage_sel = on ? sel : nullptr;
+    if (on && b->bigk) {
+        b->h_filt_sel.assign(b->max_queries, UINT32_MAX);
+        std::copy(sel, sel + nq, b->h_filt_sel.begin());
+    }
+    return VBM25_OK;
+}
+// set_queries (staged) + run + the flag's download, on the batch's own stream
+static int batch_submit(vbm25_batch *b, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
+    const bool fast = !b->bigk;
+    const int rcq = vbm25_batch_set_queries_impl(b, term_ids, q_off, nq, fast);
+    b->stage_sel = nullptr;
+    if (rcq) return rcq;
+    void *st = fast ? b->lat_stream : nullptr;
+    if (int rc = b->growing ? batch_run_growing_impl(b, st) : vbm25_batch_run_impl(b, st)) return rc;
+    return vbm25_batch_enqueue_download(b);
+}
+static int stream_submit_impl(vbm25_stream *s, bool filtered, const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off,
+                              uint32_t nq) {
     if (!s || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (s->in_flight == s->slots.size()) return set_error(VBM25_ERR_INVALID, "%u batches in flight: collect one first", s->in_flight);
+    if (filtered && !s->filter) return set_error(VBM25_ERR_INVALID, "the stream has no filter set");
+    if (filtered && !q_filter && nq) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
     vbm25_batch *b = s->slots[(s->head + s->in_flight) % s->slots.size()];
-    const bool fast = !b->bigk;
-    if (int rc = vbm25_batch_set_queries_impl(b, term_ids, q_off, nq, fast)) return rc;
-    if (int rc = vbm25_batch_run_impl(b, fast ? b->lat_stream : nullptr)) return rc;
-    if (int rc = vbm25_batch_enqueue_download(b)) return rc;
+    if (nq > b->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the batch capacity %u", nq, b->max_queries);
+    bool on = false;
+    if (int rc = batch_attach_check(b, s->growing, filtered ? s->filter : nullptr, q_filter, nq, &on)) return rc;
+    if (int rc = batch_attach(b, s->growing, s->filter, q_filter, nq, on)) return rc;
+    if (int rc = batch_submit(b, term_ids, q_off, nq)) return rc;
     ++s->in_flight;
     return VBM25_OK;
 }
@@ -2738,7 +2918,16 @@ int vbm25_stream_create(vbm25_index *ix, uint32_t depth, uint32_t max_queries, u
 }
 void vbm25_stream_destroy(vbm25_stream *s) { delete s; }
 int vbm25_stream_submit(vbm25_stream *s, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
-    return guarded([&] { return stream_submit_impl(s, term_ids, q_off, nq); });
+    return guarded([&] { return stream_submit_impl(s, false, nullptr, term_ids, q_off, nq); });
+}
+int vbm25_stream_submit_filtered(vbm25_stream *s, const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
+    return guarded([&] { return stream_submit_impl(s, true, q_filter, term_ids, q_off, nq); });
+}
+int vbm25_stream_set_growing(vbm25_stream *s, const vbm25_device_growing *gs) {
+    return guarded([&] { return stream_set_growing_impl(s, gs); });
+}
+int vbm25_stream_set_filter(vbm25_stream *s, const vbm25_filter *f) {
+    return guarded([&] { return stream_set_filter_impl(s, f); });
 }
 int vbm25_stream_collect(vbm25_stream *s, vbm25_hit *hits, uint32_t *n_hits, uint32_t *nq_out) {
     return guarded([&] { return stream_collect_impl(s, hits, n_hits, nq_out); });
@@ -2856,6 +3045,12 @@ struct vbm25_multi_batch {
     std::vector<uint32_t> lo;              // shard bounds: replica i has the queries [lo[i], lo[i + 1])
     std::vector<std::vector<uint32_t>> off_parts;  // per part: its queries' offsets rebased to 0
     uint32_t tune_generation = 0;          // of the tuning switches its parts copied (vbm25_multi_search_batch rebuilds a stale one)
+    // vbm25_multi_batch_set_growing / _set_filter: per replica its own handles; the selectors of the whole batch (max_queries), cut by
+    // the shard bounds when set_queries fixes them and staged with each shard's queries
+    std::vector<const vbm25_device_growing *> growing;
+    std::vector<const vbm25_filter *> filters;
+    std::vector<uint32_t> sel;
+    bool sel_on = false;                   // some selector names a bitmap
     ~vbm25_multi_batch() {
         for (vbm25_batch *b : parts) vbm25_batch_destroy(b);
     }
@@ -2943,6 +3138,8 @@ int multi_batch_create_impl(vbm25_multi *m, uint32_t max_queries, uint32_t max_t
         mb->parts.push_back(b);
     }
     mb->lo.assign(n + 1, 0);
+    mb->growing.assign(n, nullptr);
+    mb->filters.assign(n, nullptr);
     mb->tune_generation = tuning_snapshot().generation;
     *out = mb.release();
     return VBM25_OK;
@@ -2967,8 +3164,16 @@ int multi_batch_set_queries_body(vbm25_multi_batch *mb, const uint32_t *term_ids
         std::vector<uint32_t> &off = mb->off_parts[i];
         off.resize(size_t(b - a) + 1);
         for (uint32_t q = a; q <= b; ++q) off[q - a] = q_off[q] - q_off[a];
+        // the shard's filter and its cut of the selectors (they ride in the shard's staged block)
+        vbm25_batch *part = mb->parts[i];
+        const uint32_t *sel = mb->filters[i] && mb->sel_on ? mb->sel.data() + a : nullptr;
+        bool on = false;
+        if (int rc = batch_attach_check(part, mb->growing[i], mb->filters[i], sel, b - a, &on)) return rc;
+        if (int rc = batch_attach(part, mb->growing[i], mb->filters[i], sel, b - a, on)) return rc;
         // staged in the part's pinned memory, copied on its own stream: the devices' uploads overlap
-        return vbm25_batch_set_queries_impl(mb->parts[i], term_ids ? term_ids + q_off[a] : nullptr, off.data(), b - a, true);
+        const int rc = vbm25_batch_set_queries_impl(part, term_ids ? term_ids + q_off[a] : nullptr, off.data(), b - a, true);
+        part->stage_sel = nullptr;
+        return rc;
     });
 }
 
@@ -2997,9 +3202,78 @@ int multi_batch_run_impl(vbm25_multi_batch *mb) {
     return mb->multi->each_part(mb->parts.size(), [&](size_t i) -> int {
         vbm25_batch *b = mb->parts[i];
         if (!b->nq) return VBM25_OK;
-        if (int rc = vbm25_batch_run_impl(b, b->bigk ? nullptr : b->lat_stream)) return rc;
+        void *st = b->bigk ? nullptr : b->lat_stream;
+        if (int rc = b->growing ? batch_run_growing_impl(b, st) : vbm25_batch_run_impl(b, st)) return rc;
         return vbm25_batch_enqueue_download(b);  // the shard's records to pinned host memory, behind its scan
     });
+}
+
+// a filter with selectors that name a bitmap and a growing segment on one replica: the pairing rules of the batch setters
+int multi_pair_check(const vbm25_filter *f, const vbm25_device_growing *gs, size_t i) {
+    if (!f || !gs) return VBM25_OK;
+    if (!f->grow_serial) return set_error(VBM25_ERR_UNSUPPORTED, "replica %zu: a growing segment and a filter without growing bitmaps", i);
+    if (f->grow_serial != gs->serial)
+        return set_error(VBM25_ERR_INVALID, "replica %zu: the filter's growing bitmaps belong to another upload than the growing segment", i);
+    return filter_growing_count_check(f, gs);
+}
+
+// per_device NULL: every replica's segment detached.  Everything is checked before any replica changes.
+int multi_batch_set_growing_impl(vbm25_multi_batch *mb, const vbm25_device_growing *const *per_device) {
+    if (!mb) return set_error(VBM25_ERR_INVALID, "batch is NULL");
+    const size_t n = mb->parts.size();
+    for (size_t i = 0; per_device && i < n; ++i) {
+        if (per_device[i] && per_device[i]->index != mb->multi->replicas[i])
+            return set_error(VBM25_ERR_INVALID, "growing segment %zu does not belong to replica %zu's index", i, i);
+        if (mb->sel_on)
+            if (int rc = multi_pair_check(mb->filters[i], per_device[i], i)) return rc;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const vbm25_device_growing *gs = per_device ? per_device[i] : nullptr;
+        vbm25_batch *b = mb->parts[i];
+        if (int rc = use_device(b->device)) return rc;
+        if (b->lat_stream) HIP_TRY(hipStreamSynchronize(b->lat_stream));  // (a run in flight reads the old segment to its end)
+        HIP_TRY(hipStreamSynchronize(b->last_stream));
+        if (gs)
+            if (int rc = batch_growing_buffers(b, gs)) return rc;
+        b->growing = gs;
+        mb->growing[i] = gs;
+    }
+    return VBM25_OK;
+}
+
+// per_device NULL: no filter.  q_filter: max_queries selectors; a selector must be UINT32_MAX or below every filter's bitmap count.
+int multi_batch_set_filter_impl(vbm25_multi_batch *mb, const vbm25_filter *const *per_device, const uint32_t *q_filter) {
+    if (!mb) return set_error(VBM25_ERR_INVALID, "batch is NULL");
+    const size_t n = mb->parts.size();
+    if (!per_device) {
+        std::fill(mb->filters.begin(), mb->filters.end(), nullptr);
+        mb->sel_on = false;
+        for (vbm25_batch *b : mb->parts) {  // (the current query set's next run filters nothing either)
+            b->filter = nullptr;
+            b->filt_on = false;
+        }
+        return VBM25_OK;
+    }
+    if (!q_filter) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
+    uint32_t f_min = UINT32_MAX;
+    for (size_t i = 0; i < n; ++i) {
+        if (!per_device[i]) return set_error(VBM25_ERR_INVALID, "filter %zu is NULL", i);
+        if (per_device[i]->index != mb->multi->replicas[i])
+            return set_error(VBM25_ERR_INVALID, "filter %zu does not belong to replica %zu's index", i, i);
+        f_min = std::min(f_min, per_device[i]->n_bitmaps);
+    }
+    bool on = false;
+    for (uint32_t q = 0; q < mb->max_queries; ++q) {
+        if (q_filter[q] == UINT32_MAX) continue;
+        if (q_filter[q] >= f_min) return set_error(VBM25_ERR_INVALID, "query %u: selector %u, a filter has %u bitmaps", q, q_filter[q], f_min);
+        on = true;
+    }
+    for (size_t i = 0; on && i < n; ++i)
+        if (int rc = multi_pair_check(per_device[i], mb->growing[i], i)) return rc;
+    mb->filters.assign(per_device, per_device + n);
+    mb->sel.assign(q_filter, q_filter + mb->max_queries);
+    mb->sel_on = on;
+    return VBM25_OK;
 }
 
 int multi_batch_fetch_impl(vbm25_multi_batch *mb, vbm25_hit *hits, uint32_t *n_hits) {
@@ -3039,6 +3313,12 @@ int vbm25_multi_batch_create(vbm25_multi *m, uint32_t max_queries, uint32_t max_
 void vbm25_multi_batch_destroy(vbm25_multi_batch *mb) { delete mb; }
 int vbm25_multi_batch_set_queries(vbm25_multi_batch *mb, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq) {
     return guarded([&] { return multi_batch_set_queries_impl(mb, term_ids, q_off, nq); });
+}
+int vbm25_multi_batch_set_growing(vbm25_multi_batch *mb, const vbm25_device_growing *const *per_device) {
+    return guarded([&] { return multi_batch_set_growing_impl(mb, per_device); });
+}
+int vbm25_multi_batch_set_filter(vbm25_multi_batch *mb, const vbm25_filter *const *per_device, const uint32_t *q_filter) {
+    return guarded([&] { return multi_batch_set_filter_impl(mb, per_device, q_filter); });
 }
 int vbm25_multi_batch_run(vbm25_multi_batch *mb) {
     return guarded([&] { return multi_batch_run_impl(mb); });
