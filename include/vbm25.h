@@ -524,9 +524,35 @@ int vbm25_index_create_from_device(const vbm25_device_segment *, vbm25_index **o
  * relabel: NULL, or n_docs(sealed) + n_docs(growing) entries: every old sealed document, then every growing index, -> its new id or
  *   UINT32_MAX (to carry filters and payload maps across).
  * Failure leaves *out NULL and nothing allocated.  The serving loop: compact, vbm25_index_create_from_device, swap the index in,
- * upload an empty growing segment, remap the filters with relabel. */
+ * upload an empty growing segment, carry the filters across with vbm25_filter_remap (below; relabel is for what the caller keeps
+ * by document id on the host). */
 int vbm25_index_maintain(const vbm25_index *index, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing,
                          uint32_t *relabel, vbm25_device_segment **out);
+
+/* Filters across a compaction.  vbm25_filter_remap makes, on the device, the filter of the compacted index out of the filter of
+ * the old one: no relabel table and no bitmap crosses the host link, only the two deletion inputs go up.
+ *   old: a filter of the index that was compacted, with the growing bitmaps of the growing segment that was compacted in (if
+ *     any).  It is only read and stays valid: batches still running on the old index keep using it.
+ *   sealed_deleted, growing_deleted: the SAME deletion inputs vbm25_index_maintain got -- NULL or ceil(n_docs / 64) words, DELETED
+ *     polarity; NULL or n_grow bytes (vbm25_growing_desc.deleted), nonzero = deleted.  The relabel is the monotone compaction the
+ *     two define.  n_grow: the growing documents the compaction took (0: none, the filter's growing bitmaps are then ignored).
+ *   new_index: the index made of the compacted segment (vbm25_index_create_from_device, or a replica of
+ *     vbm25_multi_create_from_device), on the old filter's device.
+ * *out: a new filter on new_index with the same number of bitmaps.  Its bitmap i is two bit runs back to back: old sealed bitmap
+ * i's bits of the kept sealed documents in id order, then old growing bitmap i's bits of the live growing documents in growing
+ * order -- in the filter's own packing (bit d % 64 of word d / 64, least significant first), bits at or beyond the new n_docs
+ * zero.  It has no growing bitmaps: the caller sets them for the fresh growing segment as usual.
+ * Synchronous: waits for the device before it reads.  On any failure *out is NULL and nothing is allocated:
+ *   NULL old, new_index or out; new_index on another device; sealed_deleted bits at or beyond the old n_docs -> VBM25_ERR_INVALID
+ *   n_grow > 0 and old has no growing bitmaps -> VBM25_ERR_UNSUPPORTED; they cover another document count -> VBM25_ERR_INVALID
+ *   kept sealed + live growing documents != new_index's n_docs (another compaction's index) -> VBM25_ERR_INVALID
+ * A new index of 0 documents is valid: a filter of zero words.
+ * vbm25_filter_read copies a bitmap back to the host (checkpoints of bitmaps only ever extended on the device): growing == 0:
+ * sealed bitmap i, ceil(n_docs / 64) words; growing != 0: growing bitmap i, ceil(covered documents / 64) words
+ * (VBM25_ERR_INVALID when the filter has none).  Synchronous. */
+int vbm25_filter_remap(const vbm25_filter *old, const uint64_t *sealed_deleted, uint32_t n_grow, const uint8_t *growing_deleted,
+                       vbm25_index *new_index, vbm25_filter **out);
+int vbm25_filter_read(const vbm25_filter *, uint32_t i, int growing, uint64_t *words);
 
 /* ------------------------------------------------------------------------
  * Several GPUs of one node: independent queries shard
@@ -547,6 +573,12 @@ typedef struct vbm25_multi vbm25_multi;
 typedef struct vbm25_multi_batch vbm25_multi_batch;
 int vbm25_multi_create(const vbm25_index_desc *desc, const int *devices, int n_devices,
                        vbm25_multi **out);
+/* The replicas of a device segment (a compacted one: vbm25_index_maintain): the first is vbm25_index_create_from_device on the
+ * segment's device -- devices[0] must be that device, else VBM25_ERR_INVALID --, the others are copied from it GPU to GPU; the segment
+ * is left as it was and nothing goes through the host.  The handle is a vbm25_multi like any other.  After a compaction: compact
+ * replica 0, make the new vbm25_multi of the device segment, vbm25_filter_remap per replica against vbm25_multi_index(new, i),
+ * upload empty growing segments, destroy the old handle. */
+int vbm25_multi_create_from_device(const vbm25_device_segment *, const int *devices, int n_devices, vbm25_multi **out);
 void vbm25_multi_destroy(vbm25_multi *);
 int vbm25_multi_device_count(const vbm25_multi *);
 /* The replica on devices[i] (borrowed: e.g. for vbm25_lookup_terms, which is the same on every replica). */

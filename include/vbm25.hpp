@@ -81,6 +81,8 @@ class Query {
 class Index {
   public:
     Index(const vbm25_index_desc &desc, int device = 0) { check(vbm25_index_create(&desc, device, &h_)); }
+    // of a segment in HBM (a compacted one: vbm25_index_maintain), on the segment's device; the segment is left as it was
+    explicit Index(const vbm25_device_segment *segment) { check(vbm25_index_create_from_device(segment, &h_)); }
     ~Index() { vbm25_index_destroy(h_); }
     Index(const Index &) = delete;
     Index &operator=(const Index &) = delete;
@@ -127,6 +129,30 @@ class DocFilter {
     ~DocFilter() { vbm25_filter_destroy(h_); }
     DocFilter(const DocFilter &) = delete;
     DocFilter &operator=(const DocFilter &) = delete;
+    DocFilter(DocFilter &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    // This filter carried across vbm25_index_maintain on the device (vbm25_filter_remap): sealed_deleted (empty: none; else
+    // words_per_bitmap(old n_docs) words, DELETED polarity) and the n_grow growing documents' deleted flags (empty: none deleted) are
+    // what the compaction got; new_index is the index of the compacted segment (an Index, or a replica of a MultiIndex).  The new
+    // filter has no growing bitmaps; this one is only read and stays valid.
+    DocFilter remap(vbm25_index *new_index, const std::vector<uint64_t> &sealed_deleted = {}, uint32_t n_grow = 0,
+                    const std::vector<uint8_t> &growing_deleted = {}) const {
+        if (!growing_deleted.empty() && growing_deleted.size() != n_grow) throw Error(VBM25_ERR_INVALID, "one deleted flag per growing document");
+        vbm25_filter *h = nullptr;
+        check(vbm25_filter_remap(h_, sealed_deleted.empty() ? nullptr : sealed_deleted.data(), n_grow,
+                                 growing_deleted.empty() ? nullptr : growing_deleted.data(), new_index, &h));
+        return DocFilter(h);
+    }
+    DocFilter remap(const Index &new_index, const std::vector<uint64_t> &sealed_deleted = {}, uint32_t n_grow = 0,
+                    const std::vector<uint8_t> &growing_deleted = {}) const {
+        return remap(new_index.handle(), sealed_deleted, n_grow, growing_deleted);
+    }
+    // bitmap i back on the host (vbm25_filter_read): n_words = words_per_bitmap(n_docs), or of the growing documents covered
+    std::vector<uint64_t> read(uint32_t i, size_t n_words, bool growing = false) const {
+        std::vector<uint64_t> w(n_words ? n_words : 1);
+        check(vbm25_filter_read(h_, i, growing ? 1 : 0, w.data()));
+        w.resize(n_words);
+        return w;
+    }
     void update(uint32_t i, const std::vector<uint64_t> &words) { check(vbm25_filter_update(h_, i, words.data())); }
     void *device_words(uint32_t i) {
         void *p = nullptr;
@@ -158,7 +184,41 @@ class DocFilter {
     vbm25_filter *handle() const { return h_; }
 
   private:
+    explicit DocFilter(vbm25_filter *h) : h_(h) {}
     vbm25_filter *h_ = nullptr;
+};
+
+// The sealed segment replicated on several GPUs of one node (vbm25_multi): uploaded from the host once, or made of a device segment
+// (a compacted one) on the segment's device, which devices[0] must name; the other replicas are copied GPU to GPU.
+class MultiIndex {
+  public:
+    MultiIndex(const vbm25_index_desc &desc, const std::vector<int> &devices) {
+        check(vbm25_multi_create(&desc, devices.data(), int(devices.size()), &h_));
+    }
+    MultiIndex(const vbm25_device_segment *segment, const std::vector<int> &devices) {
+        check(vbm25_multi_create_from_device(segment, devices.data(), int(devices.size()), &h_));
+    }
+    ~MultiIndex() { vbm25_multi_destroy(h_); }
+    MultiIndex(const MultiIndex &) = delete;
+    MultiIndex &operator=(const MultiIndex &) = delete;
+    int device_count() const { return vbm25_multi_device_count(h_); }
+    // replica i (borrowed): what that replica's DocFilter::remap, filters and growing segments are made on
+    vbm25_index *replica(int i) const {
+        vbm25_index *ix = nullptr;
+        check(vbm25_multi_index(h_, i, &ix));
+        return ix;
+    }
+    void search_batch(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, size_t k, std::vector<Hit> &hits,
+                      std::vector<uint32_t> &n_hits) const {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        hits.resize(size_t(nq) * k);
+        n_hits.resize(nq);
+        check(vbm25_multi_search_batch(h_, term_ids.data(), q_off.data(), nq, uint32_t(k), hits.data(), n_hits.data()));
+    }
+    vbm25_multi *handle() const { return h_; }
+
+  private:
+    vbm25_multi *h_ = nullptr;
 };
 
 // Host copy of a flattened sealed segment (RAII over vbm25_segment).

@@ -106,7 +106,10 @@ ABI = {
     "vbm25_device_segment_free": (None, [vp]),
     "vbm25_index_create_from_device": (i32, [vp, vp]),
     "vbm25_index_maintain": (i32, [vp, vp, vp, vp, vp]),
+    "vbm25_filter_remap": (i32, [vp, vp, u32, vp, vp, vp]),
+    "vbm25_filter_read": (i32, [vp, u32, i32, vp]),
     "vbm25_multi_create": (i32, [vp, vp, i32, vp]),
+    "vbm25_multi_create_from_device": (i32, [vp, vp, i32, vp]),
     "vbm25_multi_destroy": (None, [vp]),
     "vbm25_multi_device_count": (i32, [vp]),
     "vbm25_multi_index": (i32, [vp, i32, vp]),

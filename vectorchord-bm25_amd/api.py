@@ -182,6 +182,25 @@ class Segment:
         return int(lib().vbm25_query_bytes(C.byref(self.desc), _p(term_ids), len(term_ids), k))
 
 
+def _deleted_words(sealed_deleted, n_docs):
+    """vbm25_index_maintain's / vbm25_filter_remap's sealed_deleted: None, a bool array of n_docs (True = deleted) or the packed
+    uint64 words -> None or the words"""
+    if sealed_deleted is None:
+        return None
+    a = np.asarray(sealed_deleted)
+    if a.dtype == np.bool_:
+        if len(a) != n_docs:
+            raise ValueError(f"{len(a)} deleted flags for {n_docs} documents")
+        words = np.zeros((n_docs + 63) // 64, dtype=np.uint64)
+        idx = np.flatnonzero(a)
+        np.bitwise_or.at(words, idx >> 6, np.left_shift(np.uint64(1), (idx & 63).astype(np.uint64)))
+        return words
+    words = np.ascontiguousarray(a, dtype=np.uint64)
+    if len(words) != (n_docs + 63) // 64:
+        raise ValueError(f"{len(words)} words for {n_docs} documents")
+    return words
+
+
 class DeviceSegment:
     """A sealed segment that lives in HBM (vbm25_device_segment): built or generated on the device, never downloaded unless
     asked (download() -> Segment).  GpuIndex(device_segment) makes the index of it without a round trip through the host."""
@@ -219,19 +238,7 @@ class DeviceSegment:
         g_key, g_tf, g_payload, g_deleted; g_fieldnorm is not read).  Returns the new DeviceSegment, and with return_relabel the
         uint32 array old sealed ids + growing indexes -> new id (0xFFFFFFFF: dropped)."""
         n_docs = index.n_docs
-        words = None
-        if sealed_deleted is not None:
-            a = np.asarray(sealed_deleted)
-            if a.dtype == np.bool_:
-                if len(a) != n_docs:
-                    raise ValueError(f"{len(a)} deleted flags for {n_docs} documents")
-                words = np.zeros((n_docs + 63) // 64, dtype=np.uint64)
-                idx = np.flatnonzero(a)
-                np.bitwise_or.at(words, idx >> 6, np.left_shift(np.uint64(1), (idx & 63).astype(np.uint64)))
-            else:
-                words = np.ascontiguousarray(a, dtype=np.uint64)
-                if len(words) != (n_docs + 63) // 64:
-                    raise ValueError(f"{len(words)} words for {n_docs} documents")
+        words = _deleted_words(sealed_deleted, n_docs)
         d, keep, n_grow = None, [], 0
         if growing is not None:
             g_start = np.ascontiguousarray(growing["g_start"], dtype=np.uint64)
@@ -624,6 +631,33 @@ class DocFilter:
         check(lib().vbm25_filter_growing_device_words(self.h, i, C.byref(dev)))
         return dev.value
 
+    def read(self, i, growing=False):
+        """vbm25_filter_read: bitmap i back on the host as uint64 words -- the sealed one (ceil(n_docs / 64) words) or, with
+        growing=True, the growing one (ceil(grow_n / 64) words; Vbm25Error when the filter has none)."""
+        n = self.grow_n if growing else self.index.n_docs
+        words = np.zeros(max(1, (n + 63) // 64), dtype=np.uint64)  # (never a NULL pointer, also for zero words)
+        check(lib().vbm25_filter_read(self.h, i, 1 if growing else 0, words.ctypes.data_as(C.c_void_p)))
+        return words[:(n + 63) // 64]
+
+    def remap(self, new_index, sealed_deleted=None, growing_deleted=None):
+        """vbm25_filter_remap: this filter carried across DeviceSegment.maintain(index, sealed_deleted, growing) on the device.
+        `new_index`: the GpuIndex of the compacted segment (or a replica of MultiIndex.from_device); sealed_deleted: what maintain
+        got (None, a bool array or the packed words); growing_deleted: the growing segment's g_deleted flags (None: none deleted) --
+        without them the growing documents are those this filter's growing bitmaps cover (none: no growing segment was compacted
+        in).  Returns the new DocFilter (no growing bitmaps yet); this one is only read and stays valid."""
+        words = _deleted_words(sealed_deleted, self.index.n_docs)
+        n_grow = self.grow_n
+        g_del = None
+        if growing_deleted is not None:  # (one flag per growing document of the compaction: the library compares the counts)
+            g_del = np.ascontiguousarray(growing_deleted, dtype=np.uint8).reshape(-1)
+            n_grow = len(g_del)
+        h = C.c_void_p()
+        check(lib().vbm25_filter_remap(self.h, _p(words), n_grow, _p(g_del), new_index.h, C.byref(h)))
+        f = DocFilter.__new__(DocFilter)
+        f.index, f.growing, f.grow_n = new_index, None, 0
+        f.n_bitmaps, f.words, f.h = self.n_bitmaps, (new_index.n_docs + 63) // 64, h
+        return f
+
     def __del__(self):
         try:
             if self.h:
@@ -795,6 +829,18 @@ class MultiIndex:
         self.h = C.c_void_p()
         check(lib().vbm25_multi_create(C.byref(segment.desc), devs, len(devices), C.byref(self.h)))
         self.n_devices = lib().vbm25_multi_device_count(self.h)
+
+    @classmethod
+    def from_device(cls, device_segment, devices):
+        """vbm25_multi_create_from_device: the replicas of a DeviceSegment (a compacted one) -- the first made on the segment's
+        device, which devices[0] must name, the others copied GPU to GPU; the segment is left as it was."""
+        m = cls.__new__(cls)
+        m.segment = device_segment  # (n_terms / n_docs for index(); not needed alive by the library)
+        m.h = C.c_void_p()
+        devs = (C.c_int * len(devices))(*[int(d) for d in devices])
+        check(lib().vbm25_multi_create_from_device(device_segment.h, devs, len(devices), C.byref(m.h)))
+        m.n_devices = lib().vbm25_multi_device_count(m.h)
+        return m
 
     def __del__(self):
         try:

@@ -76,6 +76,13 @@ struct MaintainSource {
 int maintain_device(const MaintainSource &src, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing, uint32_t *relabel,
                     vbm25_device_segment **out);
 
+// vbm25_filter_remap's device half (csrc/maintain.hip: the relabel is the compaction's).  bits: the old filter's n_bitmaps x
+// ceil(n_docs / 64) sealed words; grow_bits: its growing words, bitmap i at word i grow_stride (not read when n_grow is 0); both on
+// `device`, as is out: n_bitmaps x ceil(new_n_docs / 64) words, written only when the kept sealed and the live growing documents
+// number new_n_docs (else VBM25_ERR_INVALID).  sealed_deleted / growing_deleted: host, as vbm25_index_maintain takes them.
+int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const uint64_t *sealed_deleted, const void *bits, uint32_t n_grow,
+                        const uint8_t *growing_deleted, const void *grow_bits, uint32_t grow_stride, uint32_t new_n_docs, void *out);
+
 }  // namespace vbm25
 
 #endif

@@ -712,6 +712,100 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     return VBM25_OK;
 }
 
+// ---------------------------------------------------------------------------
+// vbm25_filter_remap: a filter's bitmaps carried across the compaction (search.hip owns the filters and checks the arguments)
+// ---------------------------------------------------------------------------
+// The old documents are one run of input words: the sealed bitmaps' W words, then the growing bitmaps' GW words.  keep / base are the
+// relabel's pair over that run (mt_keep_kernel per side, ONE exclusive scan over both), so base[w] is input word w's first OUTPUT BIT:
+// the growing side starts at bit n_kept, whatever n_kept % 64 is.  One thread per input word with a kept bit: the kept bits of the
+// word compressed to its low end (the parallel-suffix compress of Hacker's Delight 7-4, its six move masks a function of keep[w] alone
+// and so computed once for all F bitmaps) and ORed into the one or two output words at bit base[w].  Output words are shared between
+// neighbouring input words (and between the last sealed and the first growing one): the output is zeroed first and written with
+// atomicOr, which commutes -- the result does not depend on the order.  A run of fully deleted words costs its threads one load each.
+namespace {
+__global__ void __launch_bounds__(256) filter_remap_kernel(uint32_t n_in, uint32_t n_sealed_words, const ull *keep, const uint32_t *base,
+                                                           const ull *bits, const ull *grow_bits, uint32_t grow_stride, uint32_t n_bitmaps,
+                                                           ull *out, uint32_t out_words) {
+    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < n_in; w += gridDim.x * blockDim.x) {
+        const ull k = keep[w];  // (the tail word's bits at or beyond the document count are cleared)
+        if (!k) continue;
+        ull m = k, mk = ~k << 1, mv[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            ull mp = mk ^ (mk << 1);
+            mp ^= mp << 2;
+            mp ^= mp << 4;
+            mp ^= mp << 8;
+            mp ^= mp << 16;
+            mp ^= mp << 32;
+            mv[i] = mp & m;
+            m = (m ^ mv[i]) | (mv[i] >> (1 << i));
+            mk &= ~mp;
+        }
+        const uint32_t at = base[w], ow = at >> 6, sh = at & 63u;
+        const bool sealed = w < n_sealed_words;
+        const ull *src = sealed ? bits + w : grow_bits + (w - n_sealed_words);
+        const size_t stride = sealed ? n_sealed_words : grow_stride;
+        for (uint32_t f = 0; f < n_bitmaps; ++f) {
+            ull x = src[f * stride] & k;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const ull t = x & mv[i];
+                x = (x ^ t) | (t >> (1 << i));
+            }
+            if (!x) continue;
+            ull *o = out + size_t(f) * out_words + ow;
+            atomicOr(o, x << sh);
+            // (sh == 0: the word takes all 64 bits, and a shift by 64 is undefined)
+            if (sh && (x >> (64u - sh)) && ow + 1u < out_words) atomicOr(o + 1, x >> (64u - sh));
+        }
+    }
+}
+}  // namespace
+
+int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const uint64_t *sealed_deleted, const void *bits, uint32_t n_grow,
+                        const uint8_t *growing_deleted, const void *grow_bits, uint32_t grow_stride, uint32_t new_n_docs, void *out) {
+    const uint32_t W = (n_docs + 63u) / 64u, GW = (n_grow + 63u) / 64u, OW = (new_n_docs + 63u) / 64u;
+    const uint64_t TW = uint64_t(W) + GW;
+    // growing_deleted packed to the polarity and the form of sealed_deleted: both sides go through mt_keep_kernel
+    std::vector<ull> del(sealed_deleted || growing_deleted ? TW : 0, 0ull);
+    if (sealed_deleted) std::copy(sealed_deleted, sealed_deleted + W, del.begin());
+    if (growing_deleted)
+        for (uint32_t g = 0; g < n_grow; ++g)
+            if (growing_deleted[g]) del[W + (g >> 6)] |= 1ull << (g & 63u);
+    MT_TRY(hipSetDevice(device));
+    DBuf d_del, d_keep, d_cnt, d_base, tmp;
+    uint32_t got[2] = {0, 0};  // kept sealed documents, kept sealed + live growing
+    if (TW) {
+        MT_TRY(d_keep.alloc(8ull * TW));
+        MT_TRY(d_cnt.alloc(4ull * (TW + 1ull)));
+        MT_TRY(d_base.alloc(4ull * (TW + 1ull)));
+        if (!del.empty()) {
+            MT_TRY(d_del.alloc(8ull * TW));
+            MT_TRY(hipMemcpy(d_del.p, del.data(), 8ull * TW, hipMemcpyHostToDevice));
+        }
+        MT_TRY(hipMemset(d_cnt.as<uint32_t>() + TW, 0, 4));
+        if (W) mt_keep_kernel<<<grid_of(W), 256>>>(W, n_docs, sealed_deleted ? d_del.as<ull>() : nullptr, d_keep.as<ull>(), d_cnt.as<uint32_t>());
+        if (GW)
+            mt_keep_kernel<<<grid_of(GW), 256>>>(GW, n_grow, growing_deleted ? d_del.as<ull>() + W : nullptr, d_keep.as<ull>() + W,
+                                                  d_cnt.as<uint32_t>() + W);
+        MT_TRY(hipGetLastError());
+        MT_TRY(exclusive_sum(d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), uint32_t(TW + 1ull), tmp));
+        MT_TRY(hipMemcpy(&got[0], d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
+        MT_TRY(hipMemcpy(&got[1], d_base.as<uint32_t>() + TW, 4, hipMemcpyDeviceToHost));
+    }
+    if (got[1] != new_n_docs)
+        return set_error(VBM25_ERR_INVALID, "%u kept sealed + %u live growing documents = %u, the new index holds %u: the filter is being "
+                                            "remapped against another compaction", got[0], got[1] - got[0], got[1], new_n_docs);
+    if (!OW) return VBM25_OK;
+    MT_TRY(hipMemset(out, 0, 8ull * n_bitmaps * OW));
+    filter_remap_kernel<<<grid_of(TW), 256>>>(uint32_t(TW), W, d_keep.as<ull>(), d_base.as<uint32_t>(), static_cast<const ull *>(bits),
+                                              static_cast<const ull *>(grow_bits), grow_stride, n_bitmaps, static_cast<ull *>(out), OW);
+    MT_TRY(hipGetLastError());
+    MT_TRY(hipDeviceSynchronize());
+    return VBM25_OK;
+}
+
 }  // namespace vbm25
 
 // tools/maintain_cost.py: the phases of the calling thread's last vbm25_index_maintain (not part of include/vbm25.h)

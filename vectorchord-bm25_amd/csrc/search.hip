@@ -2768,6 +2768,62 @@ int vbm25_search_batch_growing_filtered(vbm25_index *ix, const vbm25_device_grow
 }
 }  // extern "C"
 
+// A filter carried across vbm25_index_maintain: the relabel is the monotone compaction the two deletion inputs define, so the new
+// filter's bitmap i is the old sealed bitmap i's bits of the kept documents followed by the old growing bitmap i's bits of the live
+// ones (filter_remap_device, maintain.hip).  The old filter is only read.  Everything is checked, and the new words are written,
+// before *out is set: a failure leaves nothing behind.
+static int vbm25_filter_remap_impl(const vbm25_filter *old, const uint64_t *sealed_deleted, uint32_t n_grow, const uint8_t *growing_deleted,
+                                   vbm25_index *nix, vbm25_filter **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!old || !nix) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (nix->device != old->device)
+        return set_error(VBM25_ERR_INVALID, "the new index is on device %d, the filter on device %d", nix->device, old->device);
+    const uint32_t N = old->index->n_docs;
+    if (sealed_deleted && (N & 63u) && (sealed_deleted[old->words - 1] >> (N & 63u)))
+        return set_error(VBM25_ERR_INVALID, "sealed_deleted has bits at or beyond n_docs = %u", N);
+    if (n_grow) {
+        if (!old->grow_serial) return set_error(VBM25_ERR_UNSUPPORTED, "%u growing documents and the filter has no growing bitmaps", n_grow);
+        if (old->grow_n != n_grow)
+            return set_error(VBM25_ERR_INVALID, "the filter's growing bitmaps cover %u documents, the compaction took %u", old->grow_n, n_grow);
+    }
+    if (int rc = use_device(old->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (device-side writers of the old bits and extends in flight end first)
+    auto f = std::make_unique<vbm25_filter>();
+    f->index = nix;
+    f->device = nix->device;
+    f->n_bitmaps = old->n_bitmaps;
+    f->words = (nix->n_docs + 63u) / 64u;
+    if (int rc = f->bits.alloc(8ull * f->n_bitmaps * f->words)) return rc;
+    if (int rc = filter_remap_device(old->device, old->n_bitmaps, N, sealed_deleted, old->bits.p, n_grow, n_grow ? growing_deleted : nullptr,
+                                     n_grow ? old->grow_bits.p : nullptr, old->grow_stride, nix->n_docs, f->bits.p))
+        return rc;
+    *out = f.release();
+    return VBM25_OK;
+}
+
+static int vbm25_filter_read_impl(const vbm25_filter *f, uint32_t i, int growing, uint64_t *words) {
+    if (!f || !words) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (growing && !f->grow_serial) return set_error(VBM25_ERR_INVALID, "the filter has no growing bitmaps");
+    if (i >= f->n_bitmaps) return set_error(VBM25_ERR_INVALID, "bitmap %u of a filter of %u", i, f->n_bitmaps);
+    if (int rc = use_device(f->device)) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (device-side writers of the bits end first)
+    const uint32_t n = growing ? f->grow_words : f->words;
+    const uint64_t *src = growing ? f->grow_bits.as<uint64_t>() + size_t(i) * f->grow_stride : f->bits.as<uint64_t>() + size_t(i) * f->words;
+    if (n) HIP_TRY(hipMemcpy(words, src, 8ull * n, hipMemcpyDeviceToHost));
+    return VBM25_OK;
+}
+
+extern "C" {
+int vbm25_filter_remap(const vbm25_filter *old, const uint64_t *sealed_deleted, uint32_t n_grow, const uint8_t *growing_deleted,
+                       vbm25_index *new_index, vbm25_filter **out) {
+    return guarded([&] { return vbm25_filter_remap_impl(old, sealed_deleted, n_grow, growing_deleted, new_index, out); });
+}
+int vbm25_filter_read(const vbm25_filter *f, uint32_t i, int growing, uint64_t *words) {
+    return guarded([&] { return vbm25_filter_read_impl(f, i, growing, words); });
+}
+}  // extern "C"
+
 extern "C" {
 int vbm25_growing_upload(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
     return guarded([&] { return vbm25_growing_upload_impl(ix, d, out); });
@@ -3102,13 +3158,21 @@ int clone_index(const vbm25_index *src, int device, vbm25_index **out) {
     return VBM25_OK;
 }
 
-int multi_create_impl(const vbm25_index_desc *desc, const int *devices, int n_devices, vbm25_multi **out) {
+// the first replica: uploaded from the host (desc), or made of the device segment on the segment's device (from_device)
+int multi_create_impl(const vbm25_index_desc *desc, const vbm25_device_segment *dseg, bool from_device, const int *devices, int n_devices,
+                      vbm25_multi **out) {
     if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!devices || n_devices <= 0) return set_error(VBM25_ERR_INVALID, "no devices given");
+    if (from_device) {
+        if (!dseg) return set_error(VBM25_ERR_INVALID, "device segment is NULL");
+        if (devices[0] != dseg->device)
+            return set_error(VBM25_ERR_INVALID, "devices[0] is %d, the segment lives on device %d: the first replica is made where the segment is",
+                             devices[0], dseg->device);
+    }
     auto m = std::make_unique<vbm25_multi>();
     vbm25_index *first = nullptr;
-    if (int rc = vbm25_index_create(desc, devices[0], &first)) return rc;
+    if (int rc = from_device ? vbm25_index_create_from_device(dseg, &first) : vbm25_index_create(desc, devices[0], &first)) return rc;
     m->replicas.push_back(first);
     for (int i = 1; i < n_devices; ++i) {
         vbm25_index *r = nullptr;
@@ -3294,7 +3358,10 @@ int multi_batch_fetch_impl(vbm25_multi_batch *mb, vbm25_hit *hits, uint32_t *n_h
 extern "C" {
 
 int vbm25_multi_create(const vbm25_index_desc *desc, const int *devices, int n_devices, vbm25_multi **out) {
-    return guarded([&] { return multi_create_impl(desc, devices, n_devices, out); });
+    return guarded([&] { return multi_create_impl(desc, nullptr, false, devices, n_devices, out); });
+}
+int vbm25_multi_create_from_device(const vbm25_device_segment *seg, const int *devices, int n_devices, vbm25_multi **out) {
+    return guarded([&] { return multi_create_impl(nullptr, seg, true, devices, n_devices, out); });
 }
 void vbm25_multi_destroy(vbm25_multi *m) {
     if (!m) return;
