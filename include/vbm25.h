@@ -496,6 +496,19 @@ uint64_t vbm25_device_segment_query_bytes(const vbm25_device_segment *, const ui
 int vbm25_device_segment_info(const vbm25_device_segment *, uint32_t *n_docs, uint32_t *n_terms, uint32_t *n_blocks,
                               uint64_t *n_postings);
 void vbm25_device_segment_free(vbm25_device_segment *);
+/* The device reader: vbm25_segment_from_pages whose result is a device segment on `device` -- the relation's sealed segment read into
+ * HBM without a host copy of the index.  Same accept / refuse contract as vbm25_segment_from_pages (Meta -> Jump -> the documents,
+ * tokens, summaries and blocks tapes; not the vectors tape, not the address trees, not DocumentTuple.deleted), and
+ * vbm25_device_segment_download of the result is byte for byte what vbm25_segment_from_pages returns.  The host follows the page
+ * chains (one header check and one copy into pinned staging per page, uploaded in chunks while the walk goes on); every tuple is
+ * parsed, validated and flattened by kernels (csrc/pages_device.hip).  read_page is called once per page, from the calling thread;
+ * a page image is not read again after the callback for the next page was made.
+ *   What vbm25_segment_from_pages refuses as VBM25_ERR_CORRUPT is refused with that code here, message "data corruption: ...
+ *   (page N)", and so is everything vbm25_index_create's structural check refuses on the flattened arrays; k1 / b out of range
+ *   -> VBM25_ERR_INVALID; no HIP device -> VBM25_ERR_DEVICE (no host fallback); NULL argument -> VBM25_ERR_INVALID.  On every
+ *   refusal *out is NULL, the HBM and pinned memory of the call is released and the device is as usable as before.
+ *   An empty sealed segment (n_docs == 0) is valid: its index returns nothing.  Synchronous; one host thread. */
+int vbm25_device_segment_from_pages(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_device_segment **out);
 /* The index of a device segment, on the segment's device; the segment is left as it was. */
 int vbm25_index_create_from_device(const vbm25_device_segment *, vbm25_index **out);
 

@@ -246,6 +246,33 @@ class Segment {
     vbm25_segment *h_;
 };
 
+// A sealed segment in HBM (RAII over vbm25_device_segment): Index(seg.handle()) and MultiIndex(seg.handle(), devices) make
+// indexes of it, download() the host copy.
+class DeviceSegment {
+  public:
+    // The device reader: the relation's sealed segment read into the HBM of `device` without a host copy of the index (the host
+    // follows the page chains, kernels parse, validate and flatten).  Accepts and refuses what Segment::from_pages does.
+    static DeviceSegment from_pages(vbm25_read_page_fn read_page, void *ctx, int device = 0) {
+        vbm25_device_segment *h = nullptr;
+        check(vbm25_device_segment_from_pages(read_page, ctx, device, &h));
+        return DeviceSegment(h);
+    }
+    explicit DeviceSegment(vbm25_device_segment *h) : h_(h) {}
+    DeviceSegment(DeviceSegment &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DeviceSegment(const DeviceSegment &) = delete;
+    DeviceSegment &operator=(const DeviceSegment &) = delete;
+    ~DeviceSegment() { vbm25_device_segment_free(h_); }
+    Segment download() const {
+        vbm25_segment *s = nullptr;
+        check(vbm25_device_segment_download(h_, &s));
+        return Segment(s);
+    }
+    const vbm25_device_segment *handle() const { return h_; }
+
+  private:
+    vbm25_device_segment *h_;
+};
+
 // The growing (unsealed) segment, search.rs:83-135: documents as CSR over their VectorTuple elements.
 struct GrowingDocs {
     std::vector<uint64_t> start{0};      // n + 1 offsets into key / tf

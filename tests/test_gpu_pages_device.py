@@ -1,0 +1,204 @@
+"""The device reader (vbm25_device_segment_from_pages, csrc/pages_device.hip): a relation in the reference's on-disk format read into
+HBM.  The yardstick is the host reader (vbm25_segment_from_pages): the downloaded segment is byte for byte the host reader's, what
+the host reader refuses is refused with the same code, and the device segment serves every route a built one does.  -m gpu only.
+
+Out-of-bounds reads are not hunted here: tests/test_pages_device_host.py runs the same per-tuple functions under AddressSanitizer on
+the CPU, on the damaged relations of this file first."""
+import os
+
+import numpy as np
+import pytest
+
+import vectorchord_bm25_amd as vb
+import pages_device_data as D
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_C = {}
+
+
+def cached(name, make):
+    if name not in _C:
+        _C[name] = make()
+    return _C[name]
+
+
+def assert_same_segment(got, want):
+    assert got.meta() == want.meta()
+    x, y = got.arrays(), want.arrays()
+    assert set(x) == set(y)
+    for name in y:
+        assert x[name].shape == y[name].shape and np.array_equal(x[name], y[name]), name
+
+
+def assert_device_equals_host(pl):
+    want = vb.segment_from_pages(pl)
+    ds = vb.DeviceSegment.from_pages(pl)
+    assert (ds.n_docs, ds.n_terms, ds.n_blocks) == (want.n_docs, want.n_terms, want.n_blocks)
+    assert ds.n_postings == int(want.arrays()["term_df"].sum())
+    assert_same_segment(ds.download(), want)
+    return ds, want
+
+
+def rel3000():
+    def make():
+        c, seg, oix, pages = D.relation()
+        return seg, pages, [p.copy() for p in D.page_list(pages)]
+    return cached("3000", make)
+
+
+def queries(n_terms, nq, nt, seed):
+    rng = np.random.default_rng(seed)
+    terms = np.sort(np.stack([rng.choice(n_terms, nt, replace=False) for _ in range(nq)]), axis=1).reshape(-1).astype(np.uint32)
+    return terms, (np.arange(nq + 1) * nt).astype(np.uint32)
+
+
+# ---- 1. byte identity
+
+def test_interleaved_tapes_of_several_pages():
+    seg, pages, pl = rel3000()
+    (docs, toks, sums, blks), _ = D.tapes(pl)
+    # 5 document pages, 3 token pages, several summary pages, page ids interleaved between the tapes; only the last page of a tape
+    # is partial (counted with the host reader's layout when this test was written: 5 / 3 / 4 / 23 pages)
+    assert (len(docs), len(toks)) == (5, 3) and len(sums) > 1 and len(blks) > len(sums)
+    assert min(blks) < max(toks) and min(toks) < max(sums)
+    for tape, full in ((docs, 680), (toks, 226), (sums, 291)):
+        assert [len(D.slots(pl[p])) for p in tape[:-1]] == [full] * (len(tape) - 1)
+    ds, want = assert_device_equals_host(pl)
+    assert_same_segment(want, seg)
+    # the host members a built device segment has: query_bytes as the host segment's, no token map
+    terms = np.array([0, 7, ds.n_terms - 1], np.uint32)
+    assert ds.query_bytes(terms, 10) == want.query_bytes(terms, 10)
+    with pytest.raises(vb.Vbm25Error):
+        ds.token_terms(np.zeros(1, np.uint32))
+
+
+def test_many_pages_and_byte_packed_tails():
+    c, seg, oix, pages = D.relation(n_docs=20000, vocab=300, seed=9)
+    # 164 pages; 299 of the 300 terms end in a byte-packed tail, one (df = 2432 = 19 x 128) in a full block
+    df = seg.arrays()["term_df"]
+    assert len(pages) > 100 and len(df) == 300 and int((df % 128 != 0).sum()) == 299
+    assert_device_equals_host(D.page_list(pages))
+
+
+def test_terms_of_interest():
+    seg = D.terms_of_interest_segment()
+    assert set([128, 129, 1, 256]) <= set(seg.arrays()["term_df"].tolist())
+    oix, pages = D.relation_of(seg)
+    ds, want = assert_device_equals_host(D.page_list(pages))
+    assert_same_segment(want, seg)
+
+
+def test_one_document_one_term():
+    seg = vb.Segment.build(1.2, 0.75, np.array([3], np.uint32), np.array([[0, 0, 1]], np.uint16), np.frombuffer(b"solo".ljust(16, b"\0"), np.uint8),
+                           np.array([0, 1], np.uint64), np.array([0], np.uint32), np.array([3], np.uint32))
+    oix, pages = D.relation_of(seg)
+    ds, want = assert_device_equals_host(D.page_list(pages))
+    assert (ds.n_docs, ds.n_terms, ds.n_blocks) == (1, 1, 1)
+
+
+def test_golden_page_fixture():
+    raw = open(os.path.join(GOLD, "page_fixture.bin"), "rb").read()
+    assert_device_equals_host([raw[i:i + 8192] for i in range(0, len(raw), 8192)])
+
+
+def test_inserts_leave_the_sealed_part_alone_and_the_callable_form():
+    c, seg, oix, pages = D.relation()
+    a = seg.arrays()
+    rng = np.random.default_rng(4)
+    for i in range(30):
+        ranks = np.sort(rng.choice(seg.n_terms, int(rng.choice([1, 3, 40, 200])), replace=False))
+        pages.insert(rng.integers(0, 65535, 3).astype(np.uint16), [a["term_key"][r].tobytes() for r in ranks], rng.integers(1, 9, len(ranks)).astype(np.uint32))
+    ds, want = assert_device_equals_host(D.page_list(pages))
+    assert_same_segment(want, seg)
+    # the address-returning callable: no copies of the pages
+    assert_same_segment(vb.DeviceSegment.from_pages(lambda i: pages.address(i)).download(), seg)
+
+
+# ---- 2. the empty sealed segment
+
+def test_empty_sealed_segment():
+    pl = D.empty_relation()
+    want = vb.segment_from_pages(pl)
+    assert (want.n_docs, want.n_terms, want.n_blocks) == (0, 0, 0)
+    ds = vb.DeviceSegment.from_pages(pl)
+    assert (ds.n_docs, ds.n_terms, ds.n_blocks, ds.n_postings) == (0, 0, 0, 0)
+    assert_same_segment(ds.download(), want)
+    terms, off = np.array([0, 1], np.uint32), np.array([0, 1, 2], np.uint32)
+    h0, n0 = vb.search_batch(vb.GpuIndex(want), terms, off, 5)
+    h1, n1 = vb.search_batch(vb.GpuIndex(ds), terms, off, 5)
+    assert n1.tolist() == [0, 0] and np.array_equal(n0, n1) and h0.tobytes() == h1.tobytes()
+
+
+# ---- 3. search through it
+
+def test_search_through_the_device_segment():
+    c, seg, oix, pages = D.relation(n_docs=12000, vocab=600, seed=2)
+    pl = D.page_list(pages)
+    host, dev = vb.GpuIndex(vb.segment_from_pages(pl)), vb.GpuIndex(vb.DeviceSegment.from_pages(pl))
+    keys = [seg.arrays()["term_key"][r].tobytes() for r in (3, 77, 400)] + [b"no such token".ljust(16, b"\0")]
+    assert dev.lookup_terms(keys).tolist() == [3, 77, 400, 0xFFFFFFFF] == host.lookup_terms(keys).tolist()
+    for nq, k in ((16, 10), (16, 300)):
+        terms, off = queries(seg.n_terms, nq, 4, seed=k)
+        h0, n0 = vb.search_batch(host, terms, off, k)
+        h1, n1 = vb.search_batch(dev, terms, off, k)
+        assert int(n0.sum()) > 0 and np.array_equal(n0, n1) and h0.tobytes() == h1.tobytes(), k
+
+
+# ---- 4. lifecycle
+
+def test_compaction_and_replicas_of_the_device_segment():
+    seg, pages, pl = rel3000()
+    ds = vb.DeviceSegment.from_pages(pl)
+    host_ix, dev_ix = vb.GpuIndex(vb.segment_from_pages(pl)), vb.GpuIndex(ds)
+    deleted = np.arange(seg.n_docs) % 7 == 0
+    assert_same_segment(vb.DeviceSegment.maintain(dev_ix, sealed_deleted=deleted).download(),
+                        vb.DeviceSegment.maintain(host_ix, sealed_deleted=deleted).download())
+    terms, off = queries(seg.n_terms, 9, 3, seed=1)
+    h0, n0 = vb.search_batch(host_ix, terms, off, 10)
+    h1, n1 = vb.MultiIndex.from_device(ds, [0, 0]).search_batch(terms, off, 10)
+    assert int(n0.sum()) > 0 and np.array_equal(n0, n1) and h0.tobytes() == h1.tobytes()
+
+
+# ---- 5. named damage
+
+def test_named_damage_is_refused_and_the_device_stays_usable():
+    def make():
+        c, seg, oix, pages = D.relation(n_docs=800, vocab=100)
+        return [p.copy() for p in D.page_list(pages)]
+    pl = cached("800", make)
+    cases = D.named_damage(pl)
+    assert len(cases) == 19
+    for name, edit in cases:
+        cp = [p.copy() for p in pl]
+        edit(cp)
+        with pytest.raises(vb.Vbm25Error) as e:   # (a) the host reader refuses it (a case it accepts does not belong in the list)
+            vb.segment_from_pages(cp)
+        assert e.value.code == -2, name
+        with pytest.raises(vb.Vbm25Error) as e:   # (b) and so does the device reader
+            vb.DeviceSegment.from_pages(cp)
+        assert e.value.code == -2 and "data corruption" in str(e.value) and "(page " in str(e.value), (name, str(e.value))
+    assert_device_equals_host(pl)
+
+
+# ---- 6. seeded random damage
+
+def test_random_damage_is_classed_as_the_host_reader_classes_it():
+    """The first 40 cases of test_random_damage_never_crashes_the_reader's generator (seed 0; the CPU harness of
+    tests/test_pages_device_host.py runs the same 40 under AddressSanitizer first): accepted or refused case by case as the host
+    reader does, the accepted ones byte-identical.  Seed 0 gives both classes (19 accepted, 21 refused by the host reader)."""
+    base = cached("damage", D.damage_relation)
+    outcomes = []
+    for edits in D.random_damage(len(base), 40, seed=0):
+        cp = D.apply_edits(base, edits)
+        ok, want = D.host_outcome(cp)
+        try:
+            got = vb.DeviceSegment.from_pages(cp)
+            assert ok, edits
+            assert_same_segment(got.download(), want)
+        except vb.Vbm25Error as e:
+            assert not ok and e.code == want, (edits, str(e))
+        outcomes.append(ok)
+    assert any(outcomes) and not all(outcomes)
+    assert_device_equals_host(base)

@@ -104,6 +104,7 @@ ABI = {
     "vbm25_device_segment_query_bytes": (u64, [vp, vp, u32, u32]),
     "vbm25_device_segment_info": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_device_segment_free": (None, [vp]),
+    "vbm25_device_segment_from_pages": (i32, [vp, vp, i32, vp]),
     "vbm25_index_create_from_device": (i32, [vp, vp]),
     "vbm25_index_maintain": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_filter_remap": (i32, [vp, vp, u32, vp, vp, vp]),

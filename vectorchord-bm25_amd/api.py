@@ -232,6 +232,17 @@ class DeviceSegment:
         return cls(out)
 
     @classmethod
+    def from_pages(cls, pages, device=0):
+        """vbm25_device_segment_from_pages: the sealed segment of a bm25 index relation in the reference's on-disk format, read into
+        the HBM of `device` (the host follows the page chains, kernels parse, validate and flatten the tuples).  `pages` as
+        segment_from_pages takes it: a sequence of 8192-byte page images or a callable page_id -> address.  download() of the
+        result is byte for byte segment_from_pages(pages)."""
+        cb, keep = _page_reader(pages)
+        out = C.c_void_p()
+        check(lib().vbm25_device_segment_from_pages(C.cast(cb, C.c_void_p), None, device, C.byref(out)))
+        return cls(out)
+
+    @classmethod
     def maintain(cls, index, sealed_deleted=None, growing=None, return_relabel=False):
         """vbm25_index_maintain: VACUUM's compaction of `index` (a GpuIndex) on its device.  sealed_deleted: None, a bool array of
         n_docs (True = deleted) or the packed uint64 words; growing: None or a dict of growing_data.make_growing's form (g_start,

@@ -1,0 +1,391 @@
+// pages_device.hip -- the device reader: a bm25 index relation in the reference's on-disk format -> a sealed segment in HBM
+// (vbm25_device_segment_from_pages).  Same accept / refuse contract as the host reader (csrc/pages.cpp) followed by check_desc
+// (csrc/segment.cpp); the result is byte for byte what vbm25_segment_from_pages flattens, without a host copy of the index.
+//
+//   host pass      Meta, Jump, then the four tapes by Opaque.next (pages_parse.h: walk_relation): one header check and one memcpy of the
+//                  8 KiB image into pinned staging per page; a chunk of 1024 pages goes up asynchronously while the next one fills
+//                  (two staging buffers).  Kept per page: its id and the running tuple count.  No tuple is touched on the host.
+//   tape_kernel    documents / tokens / summaries: one wave per page, lane i takes slot i + 1 (+ 64 ...): line pointer validated,
+//                  fields written at prefix[page] + i into the segment's planes
+//   (scan)         ceil(df / 128) -> term_first_block, in 64 bits (hipcub)
+//   term_kernel    one thread per token: its summaries lie inside the tape and begin where its pointer says; check_desc's per-term rules
+//   tape_kernel    blocks: summary j points at the tape's j-th tuple, header against codec metadata, padded body length; check_desc's
+//                  per-block rules (the first / last block of a token from the head flags term_kernel set)
+//   (scan)         body lengths -> blk_off8; the total in 64 bits
+//   copy_kernel    one wave per block page, 16 lanes per block: 8-byte units, doc bytes, zero padding, tf bytes, zero padding
+// Every kernel is a loop over the functions of pages_parse.h and finishes normally on any input; errors meet in one 64-bit word
+// (atomicMin of (class, tape, position, reason)): the reported one is the first in walk order.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "vbm25_internal.h"
+#include "device_segment.h"
+#include "pages_parse.h"
+
+namespace {
+
+using namespace vbm25;
+using namespace vbm25::pgs;
+
+#define PG_TRY(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+struct DBuf {
+    void *p = nullptr;
+    ~DBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+    template <class T>
+    T *as() const {
+        return static_cast<T *>(p);
+    }
+};
+struct Pinned {
+    void *p = nullptr;
+    ~Pinned() {
+        if (p) (void)hipHostFree(p);
+    }
+};
+struct Stream {
+    hipStream_t s = nullptr;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+};
+
+struct WidenU32 {
+    __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
+};
+
+// the last call's cost on this thread (vbm25_debug_pages_device_stats): kernels and scans between HIP events, bytes over the host
+// link in both directions, host memory the call allocated (pinned staging included)
+thread_local double g_stats[4];
+
+constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
+uint32_t grid_for(uint64_t units, uint32_t per_block) { return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block)); }
+
+// one wave per page of tape TAPE, lane i takes slot i + 1 (+ 64 ...)
+template <uint32_t TAPE>
+__global__ void __launch_bounds__(WG_THREADS) tape_kernel(Planes c, unsigned long long *err) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    const uint32_t n_pages = c.tape[TAPE].n_pages;
+    for (uint32_t p = wave; p < n_pages; p += n_waves) {
+        const uint32_t base = c.tape[TAPE].pre[p], n = c.tape[TAPE].pre[p + 1] - base;
+        for (uint32_t i = lane; i < n; i += 64) {
+            const uint32_t r = TAPE == T_DOCS ? doc_lane(c, p, i) : TAPE == T_TOKENS ? token_lane(c, p, i) : TAPE == T_SUMMARIES ? summary_lane(c, p, i) : block_lane(c, p, i);
+            if (r) atomicMin(err, (unsigned long long)error_key(TAPE, (uint64_t)base + i, r));
+        }
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) term_kernel(Planes c, unsigned long long *err) {
+    const uint32_t n = c.tape[T_TOKENS].n_tuples;
+    for (uint32_t t = blockIdx.x * WG_THREADS + threadIdx.x; t < n; t += gridDim.x * WG_THREADS) {
+        const uint32_t r = term_lane(c, t);
+        if (r) atomicMin(err, (unsigned long long)error_key(T_TOKENS, t, r));
+    }
+}
+
+// one wave per block page, COPY_LANES lanes per block: a body of 16 (b_d + b_t) bytes is one or two coalesced requests
+__global__ void __launch_bounds__(WG_THREADS) copy_kernel(Planes c) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    const uint32_t n_pages = c.tape[T_BLOCKS].n_pages;
+    for (uint32_t p = wave; p < n_pages; p += n_waves) {
+        const uint32_t n = c.tape[T_BLOCKS].pre[p + 1] - c.tape[T_BLOCKS].pre[p];
+        for (uint32_t i = lane / COPY_LANES; i < n; i += 64 / COPY_LANES) copy_lane(c, p, i, lane % COPY_LANES);
+    }
+}
+
+// out[t] = src[idx[t]]: the body offsets at the tokens' first blocks (the algorithmic bytes per token)
+__global__ void __launch_bounds__(WG_THREADS) gather_kernel(uint32_t n, const uint32_t *idx, const uint32_t *src, uint32_t *out) {
+    for (uint32_t t = blockIdx.x * WG_THREADS + threadIdx.x; t < n; t += gridDim.x * WG_THREADS) out[t] = src[idx[t]];
+}
+
+// Pinned staging of the host pass: pages fill one buffer while the other one's chunk is on its way up
+struct Stager {
+    hipStream_t s = nullptr;
+    Pinned pin[2];
+    Event ev[2];
+    bool in_flight[2] = {false, false};
+    int cur = 0;
+    uint32_t fill = 0, tape = 0;
+    uint64_t bytes_up = 0;
+    std::vector<std::unique_ptr<DBuf>> chunks[N_TAPES];
+
+    int init(hipStream_t stream) {
+        s = stream;
+        for (int i = 0; i < 2; ++i) {
+            PG_TRY(hipHostMalloc(&pin[i].p, (size_t)CHUNK_PAGES * BLCKSZ, hipHostMallocDefault));
+            PG_TRY(hipEventCreateWithFlags(&ev[i].e, hipEventDisableTiming));
+        }
+        return VBM25_OK;
+    }
+    int flush() {
+        if (!fill) return VBM25_OK;
+        auto d = std::make_unique<DBuf>();
+        PG_TRY(d->alloc((size_t)fill * BLCKSZ));
+        PG_TRY(hipMemcpyAsync(d->p, pin[cur].p, (size_t)fill * BLCKSZ, hipMemcpyHostToDevice, s));
+        PG_TRY(hipEventRecord(ev[cur].e, s));
+        in_flight[cur] = true;
+        bytes_up += (uint64_t)fill * BLCKSZ;
+        chunks[tape].push_back(std::move(d));
+        fill = 0;
+        cur ^= 1;
+        if (in_flight[cur]) {  // the buffer to fill next: its chunk had a whole chunk's walk to arrive
+            PG_TRY(hipEventSynchronize(ev[cur].e));
+            in_flight[cur] = false;
+        }
+        return VBM25_OK;
+    }
+    int add(uint32_t t, const uint8_t *image) {
+        if (t != tape || fill == CHUNK_PAGES) {
+            if (int rc = flush()) return rc;
+            tape = t;
+        }
+        std::memcpy(static_cast<uint8_t *>(pin[cur].p) + (size_t)fill * BLCKSZ, image, BLCKSZ);
+        ++fill;
+        return VBM25_OK;
+    }
+};
+
+int corrupt(const char *what, uint32_t page) { return set_error(VBM25_ERR_CORRUPT, "data corruption: %s (page %u)", what, page); }
+
+int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_device_segment **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!read_page) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the device reader has no CPU fallback (vbm25_segment_from_pages is the host reader)");
+    if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
+    PG_TRY(hipSetDevice(device));
+    for (double &x : g_stats) x = 0.0;
+
+    Stream stream;
+    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t s = stream.s;
+    Stager st;
+    if (int rc = st.init(s)) return rc;
+
+    // ---- the host pass
+    Walk w;
+    int sink_rc = 0;
+    const bool walked = walk_relation(read_page, ctx, w, [&](uint32_t tape, uint32_t, const uint8_t *image) { return st.add(tape, image); }, sink_rc);
+    if (!walked) {
+        (void)hipStreamSynchronize(s);  // nothing is freed under a copy in flight
+        return sink_rc ? sink_rc : corrupt(w.what, w.bad_page);
+    }
+    if (int rc = st.flush()) return rc;
+    const uint32_t n_docs = w.n_docs, n_tok = w.pre[T_TOKENS].back(), n_sum = w.pre[T_SUMMARIES].back();
+    if (n_sum >= (uint32_t)INT_MAX || n_tok >= (uint32_t)INT_MAX) return set_error(VBM25_ERR_UNSUPPORTED, "more than 2^31 tokens or blocks");
+    uint64_t host_bytes = 2ull * CHUNK_PAGES * BLCKSZ, bytes_down = 0;
+
+    // ---- the tapes' tables
+    DBuf d_chunk[N_TAPES], d_pid[N_TAPES], d_pre[N_TAPES];
+    std::vector<const uint8_t *> chunk_ptr[N_TAPES];
+    Planes c{};
+    c.n_docs = n_docs;
+    for (uint32_t t = 0; t < N_TAPES; ++t) {
+        const size_t np = w.pid[t].size();
+        for (const auto &d : st.chunks[t]) chunk_ptr[t].push_back(d->as<uint8_t>());
+        PG_TRY(d_chunk[t].alloc(sizeof(void *) * chunk_ptr[t].size()));
+        PG_TRY(d_pid[t].alloc(4 * np));
+        PG_TRY(d_pre[t].alloc(4 * (np + 1)));
+        if (np) {
+            PG_TRY(hipMemcpyAsync(d_chunk[t].p, chunk_ptr[t].data(), sizeof(void *) * chunk_ptr[t].size(), hipMemcpyHostToDevice, s));
+            PG_TRY(hipMemcpyAsync(d_pid[t].p, w.pid[t].data(), 4 * np, hipMemcpyHostToDevice, s));
+        }
+        PG_TRY(hipMemcpyAsync(d_pre[t].p, w.pre[t].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
+        st.bytes_up += 8 * chunk_ptr[t].size() + 8 * np + 4;
+        host_bytes += 8 * np + 4 + 8 * chunk_ptr[t].size();
+        c.tape[t] = TapeView{d_chunk[t].as<const uint8_t *>(), d_pid[t].as<uint32_t>(), d_pre[t].as<uint32_t>(), (uint32_t)np, w.pre[t].back()};
+    }
+
+    // ---- the segment's planes and the call's scratch
+    auto ds = std::make_unique<vbm25_device_segment>();
+    ds->device = device;
+    ds->k1 = w.k1;
+    ds->b = w.b;
+    ds->n_docs = n_docs;
+    ds->n_terms = n_tok;
+    ds->n_blocks = n_sum;
+    ds->sum_len = w.sum_len;
+    DBuf d_key, d_tok_page, d_tok_slot, d_tok_nb, d_tok_fb, d_sum_page, d_sum_slot, d_head, d_len8, d_err, d_total, d_tmp, d_bnd;
+    PG_TRY(ds->d_doc_fieldnorm.alloc(n_docs));
+    PG_TRY(ds->d_doc_payload.alloc(6ull * n_docs));
+    PG_TRY(ds->d_term_df.alloc(4ull * n_tok));
+    PG_TRY(ds->d_term_wand_fn.alloc(n_tok));
+    PG_TRY(ds->d_term_wand_tf.alloc(4ull * n_tok));
+    PG_TRY(ds->d_term_first_block.alloc(4ull * (n_tok + 1)));
+    PG_TRY(ds->d_blk_min.alloc(4ull * n_sum));
+    PG_TRY(ds->d_blk_max.alloc(4ull * n_sum));
+    PG_TRY(ds->d_blk_wand_tf.alloc(4ull * n_sum));
+    PG_TRY(ds->d_blk_n.alloc(n_sum));
+    PG_TRY(ds->d_blk_wand_fn.alloc(n_sum));
+    PG_TRY(ds->d_blk_meta_doc.alloc(n_sum));
+    PG_TRY(ds->d_blk_meta_tf.alloc(n_sum));
+    PG_TRY(ds->d_blk_off8.alloc(4ull * (n_sum + 1)));
+    PG_TRY(d_key.alloc(16ull * n_tok));
+    PG_TRY(d_tok_page.alloc(4ull * n_tok));
+    PG_TRY(d_tok_slot.alloc(2ull * n_tok));
+    PG_TRY(d_tok_nb.alloc(4ull * n_tok));
+    PG_TRY(d_tok_fb.alloc(8ull * n_tok));
+    PG_TRY(d_sum_page.alloc(4ull * n_sum));
+    PG_TRY(d_sum_slot.alloc(2ull * n_sum));
+    PG_TRY(d_head.alloc(n_sum + 1ull));
+    PG_TRY(d_len8.alloc(4ull * (n_sum + 1)));
+    PG_TRY(d_err.alloc(8));
+    PG_TRY(d_total.alloc(8));
+    c.doc_fieldnorm = ds->d_doc_fieldnorm.as<uint8_t>();
+    c.doc_payload = ds->d_doc_payload.as<uint16_t>();
+    c.term_key = d_key.as<uint8_t>();
+    c.term_wand_fn = ds->d_term_wand_fn.as<uint8_t>();
+    c.term_wand_tf = ds->d_term_wand_tf.as<uint32_t>();
+    c.term_df = ds->d_term_df.as<uint32_t>();
+    c.term_first_block = ds->d_term_first_block.as<uint32_t>();
+    c.tok_page = d_tok_page.as<uint32_t>();
+    c.tok_slot = d_tok_slot.as<uint16_t>();
+    c.tok_nb = d_tok_nb.as<uint32_t>();
+    c.tok_fb = d_tok_fb.as<unsigned long long>();
+    c.blk_min = ds->d_blk_min.as<uint32_t>();
+    c.blk_max = ds->d_blk_max.as<uint32_t>();
+    c.blk_wand_tf = ds->d_blk_wand_tf.as<uint32_t>();
+    c.blk_n = ds->d_blk_n.as<uint8_t>();
+    c.blk_wand_fn = ds->d_blk_wand_fn.as<uint8_t>();
+    c.blk_meta_doc = ds->d_blk_meta_doc.as<uint8_t>();
+    c.blk_meta_tf = ds->d_blk_meta_tf.as<uint8_t>();
+    c.sum_blk_page = d_sum_page.as<uint32_t>();
+    c.sum_blk_slot = d_sum_slot.as<uint16_t>();
+    c.blk_head = d_head.as<uint8_t>();
+    c.len8 = d_len8.as<uint32_t>();
+    c.off8 = ds->d_blk_off8.as<uint32_t>();
+    unsigned long long *err = d_err.as<unsigned long long>();
+
+    Event ev[4];
+    for (Event &e : ev) PG_TRY(hipEventCreate(&e.e));
+    PG_TRY(hipEventRecord(ev[0].e, s));
+    PG_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
+    PG_TRY(hipMemsetAsync(d_total.p, 0, 8, s));
+    PG_TRY(hipMemsetAsync(d_head.p, 0, n_sum + 1ull, s));
+    PG_TRY(hipMemsetAsync(d_len8.p, 0, 4ull * (n_sum + 1), s));
+    PG_TRY(hipMemsetAsync(ds->d_term_first_block.p, 0, 4, s));
+    if (n_docs) tape_kernel<T_DOCS><<<grid_for(c.tape[T_DOCS].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
+    if (n_tok) {
+        tape_kernel<T_TOKENS><<<grid_for(c.tape[T_TOKENS].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
+        hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(c.tok_nb, WidenU32());
+        size_t tb = 0;
+        PG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, wide, d_tok_fb.as<unsigned long long>(), (int)n_tok, s));
+        PG_TRY(d_tmp.alloc(tb));
+        PG_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, wide, d_tok_fb.as<unsigned long long>(), (int)n_tok, s));
+    }
+    if (n_sum) tape_kernel<T_SUMMARIES><<<grid_for(c.tape[T_SUMMARIES].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
+    if (n_tok) term_kernel<<<grid_for(n_tok, WG_THREADS), WG_THREADS, 0, s>>>(c, err);
+    DBuf d_tmp2, d_tmp3;
+    if (n_sum) {
+        tape_kernel<T_BLOCKS><<<grid_for(c.tape[T_BLOCKS].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
+        size_t tb = 0;
+        PG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.len8, ds->d_blk_off8.as<uint32_t>(), (int)(n_sum + 1), s));
+        PG_TRY(d_tmp2.alloc(tb));
+        PG_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp2.p, tb, c.len8, ds->d_blk_off8.as<uint32_t>(), (int)(n_sum + 1), s));
+        // a 32-bit scan wraps silently beyond 2^32 units of 8 bytes: the total in 64 bits as well
+        hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(c.len8, WidenU32());
+        PG_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, wide, d_total.as<unsigned long long>(), (int)n_sum, s));
+        PG_TRY(d_tmp3.alloc(tb));
+        PG_TRY(hipcub::DeviceReduce::Sum(d_tmp3.p, tb, wide, d_total.as<unsigned long long>(), (int)n_sum, s));
+    } else {
+        PG_TRY(hipMemsetAsync(ds->d_blk_off8.p, 0, 4, s));
+    }
+    PG_TRY(hipGetLastError());
+    PG_TRY(hipEventRecord(ev[1].e, s));
+    unsigned long long key = 0, total8 = 0;
+    PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    PG_TRY(hipMemcpyAsync(&total8, d_total.p, 8, hipMemcpyDeviceToHost, s));
+    PG_TRY(hipStreamSynchronize(s));
+    bytes_down += 16;
+
+    // ---- the verdict, in the host reader's order
+    bool ascending = true;
+    uint32_t unordered_at = 0;
+    if (key == NO_ERROR || key_reason(key) >= R_DESC) {
+        ds->term_key.resize(16ull * n_tok);
+        if (n_tok) PG_TRY(hipMemcpy(ds->term_key.data(), d_key.p, 16ull * n_tok, hipMemcpyDeviceToHost));
+        bytes_down += 16ull * n_tok;
+        for (uint32_t t = 1; t < n_tok && ascending; ++t)
+            if (std::memcmp(ds->term_key.data() + 16ull * (t - 1), ds->term_key.data() + 16ull * t, 16) >= 0) ascending = false, unordered_at = t;
+    }
+    const char *what = nullptr;
+    if (int rc = verdict(w, key, ascending, what)) {
+        if (rc != VBM25_ERR_CORRUPT) return set_error(rc, "%s", what);
+        const uint64_t at = key != NO_ERROR ? key : !ascending ? error_key(T_TOKENS, unordered_at, 0) : error_key(T_TOKENS, 0, 0);
+        return corrupt(what, error_page(w, at));
+    }
+    if (total8 > 0xffffffffull) return set_error(VBM25_ERR_UNSUPPORTED, "block bodies exceed 32 GiB");
+
+    // ---- the bodies, and what the host keeps of the tokens
+    ds->blob_bytes = 8ull * total8;
+    PG_TRY(ds->d_blob.alloc(ds->blob_bytes));
+    c.blob = ds->d_blob.as<uint8_t>();
+    ds->term_df.resize(n_tok);
+    ds->term_first_block.assign(size_t(n_tok) + 1, 0);
+    ds->term_bytes.assign(n_tok, 0);
+    PG_TRY(hipEventRecord(ev[2].e, s));
+    if (n_sum) copy_kernel<<<grid_for(c.tape[T_BLOCKS].n_pages, 4), WG_THREADS, 0, s>>>(c);
+    if (n_tok) {
+        PG_TRY(d_bnd.alloc(4ull * (n_tok + 1)));
+        gather_kernel<<<grid_for(n_tok + 1ull, WG_THREADS), WG_THREADS, 0, s>>>(n_tok + 1, c.term_first_block, c.off8, d_bnd.as<uint32_t>());
+    }
+    PG_TRY(hipGetLastError());
+    PG_TRY(hipEventRecord(ev[3].e, s));
+    std::vector<uint32_t> bnd(size_t(n_tok) + 1, 0);
+    if (n_tok) {
+        PG_TRY(hipMemcpyAsync(ds->term_df.data(), ds->d_term_df.p, 4ull * n_tok, hipMemcpyDeviceToHost, s));
+        PG_TRY(hipMemcpyAsync(ds->term_first_block.data(), ds->d_term_first_block.p, 4ull * (n_tok + 1), hipMemcpyDeviceToHost, s));
+        PG_TRY(hipMemcpyAsync(bnd.data(), d_bnd.p, 4ull * (n_tok + 1), hipMemcpyDeviceToHost, s));
+        bytes_down += 12ull * n_tok + 8;
+    }
+    PG_TRY(hipStreamSynchronize(s));
+    for (uint32_t t = 0; t < n_tok; ++t)
+        ds->term_bytes[t] = 8ull * (bnd[t + 1] - bnd[t]) + 40ull * (ds->term_first_block[t + 1] - ds->term_first_block[t]) + ds->term_df[t];
+    float ms_a = 0, ms_b = 0;
+    PG_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
+    PG_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
+    host_bytes += 16ull * n_tok + 4ull * n_tok + 4ull * (n_tok + 1) + 8ull * n_tok + 4ull * (n_tok + 1);  // keys, df, first blocks, bytes, bnd
+    g_stats[0] = (double)ms_a + (double)ms_b;
+    g_stats[1] = (double)st.bytes_up;
+    g_stats[2] = (double)bytes_down;
+    g_stats[3] = (double)host_bytes;
+    *out = ds.release();
+    return VBM25_OK;
+}
+
+}  // namespace
+
+extern "C" int vbm25_device_segment_from_pages(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_device_segment **out) {
+    return vbm25::guarded([&] { return from_pages_impl(read_page, ctx, device, out); });
+}
+
+// The last successful vbm25_device_segment_from_pages of this thread (tools/pages_device_cost.py; not part of the ABI): [0] ms of the
+// kernels and scans between HIP events, [1] bytes host -> device, [2] bytes device -> host, [3] bytes of host memory the call
+// allocated (pinned staging, the per-page tables, the segment's host members)
+extern "C" int vbm25_debug_pages_device_stats(double *out4) {
+    if (!out4) return vbm25::set_error(VBM25_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < 4; ++i) out4[i] = g_stats[i];
+    return VBM25_OK;
+}
