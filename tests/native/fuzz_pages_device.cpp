@@ -6,6 +6,8 @@
 //
 // argv[1] (optional): a case file written by the test -- u32 n_pages, the page images, u32 n_cases, per case u32 n_edits and n_edits x
 // (u32 page, u32 position, u32 byte) -- run before the 4000 damaged relations of tests/native/fuzz_pages.cpp's generator.
+// argv[2] (optional): "only" -- the case file and nothing else (a relation of several chunks of CHUNK_PAGES pages takes seconds per
+// case under AddressSanitizer).
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -235,6 +237,7 @@ static bool run_case_file(const char *path) {
 
 int main(int argc, char **argv) {
     if (argc > 1 && !run_case_file(argv[1])) return 1;
+    if (argc > 2) return std::strcmp(argv[2], "only") == 0 ? 0 : (std::printf("unknown argument %s\n", argv[2]), 1);
     // the corpus and the damage of tests/native/fuzz_pages.cpp: 40 terms over 3000 documents, 30 inserted documents
     std::mt19937_64 rng(7);
     const uint32_t n_docs = 3000, n_terms = 40;

@@ -163,6 +163,11 @@ def test_compaction_and_replicas_of_the_device_segment():
 
 # ---- 5. named damage
 
+# the named cases that end the host pass (walk_relation): Meta, Jump, page headers, the page chains, the tapes' counts
+WALK_LEVEL = ("bad magic", "version 2", "next of a documents page -> 10^6", "pd_lower = 9000", "a page's next pointing at itself",
+              "special != 8184", "the last documents page's pd_lower - 4", "Jump n_docs + 1")
+
+
 def test_named_damage_is_refused_and_the_device_stays_usable():
     def make():
         c, seg, oix, pages = D.relation(n_docs=800, vocab=100)
@@ -170,15 +175,21 @@ def test_named_damage_is_refused_and_the_device_stays_usable():
     pl = cached("800", make)
     cases = D.named_damage(pl)
     assert len(cases) == 19
+    seen = []
     for name, edit in cases:
         cp = [p.copy() for p in pl]
         edit(cp)
         with pytest.raises(vb.Vbm25Error) as e:   # (a) the host reader refuses it (a case it accepts does not belong in the list)
             vb.segment_from_pages(cp)
         assert e.value.code == -2, name
+        host_text = str(e.value)
         with pytest.raises(vb.Vbm25Error) as e:   # (b) and so does the device reader
             vb.DeviceSegment.from_pages(cp)
         assert e.value.code == -2 and "data corruption" in str(e.value) and "(page " in str(e.value), (name, str(e.value))
+        if name in WALK_LEVEL:   # (c) what the walk of the page chains finds: the host reader's text and page id
+            assert str(e.value) == host_text, name
+            seen.append(name)
+    assert sorted(seen) == sorted(WALK_LEVEL)
     assert_device_equals_host(pl)
 
 

@@ -15,37 +15,91 @@ import pages_device_data as D
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_parse_functions_under_asan(tmp_path):
-    """tests/native/fuzz_pages_device.cpp: the host pass and the kernels' (page, slot) grid as plain loops over csrc/pages_parse.h,
-    output arrays sized exactly as the device allocates them, built with AddressSanitizer + UBSan (the build line of
-    test_page_reader_under_asan).  First the 40 damaged relations tests/test_gpu_pages_device.py reads on the GPU, then 4000 more: every
-    one accepted or refused as vbm25_segment_from_pages does, equal arrays when accepted, no out-of-bounds access."""
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    """tests/native/fuzz_pages_device.cpp built with AddressSanitizer + UBSan (the build line of test_page_reader_under_asan): a
+    stand-alone program, nothing of it is loaded into this process"""
     if not shutil.which("g++"):
         pytest.skip("no g++")
-    base = D.damage_relation()
-    cases = D.random_damage(len(base), 40, seed=0)
-    outcomes = [D.host_outcome(D.apply_edits(base, e))[0] for e in cases]
-    assert any(outcomes) and not all(outcomes)   # seed 0 gives both classes
-    case_file = str(tmp_path / "cases.bin")
-    with open(case_file, "wb") as f:
-        f.write(struct.pack("<I", len(base)))
-        for p in base:
-            f.write(p.tobytes())
-        f.write(struct.pack("<I", len(cases)))
-        for edits in cases:
-            f.write(struct.pack("<I", len(edits)))
-            for e in edits:
-                f.write(struct.pack("<III", *e))
-    exe = str(tmp_path / "fuzz_pages_device")
+    exe = str(tmp_path_factory.mktemp("harness") / "fuzz_pages_device")
     src = [os.path.join(ROOT, p) for p in ("tests/native/fuzz_pages_device.cpp", "vectorchord-bm25_amd/csrc/pages.cpp",
                                            "vectorchord-bm25_amd/csrc/segment.cpp", "vectorchord-bm25_amd/csrc/blake3.cpp", "oracle/oracle.cpp",
                                            "oracle/pages.cpp")]
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
                            "-pthread", *src, "-o", exe])
-    out = subprocess.run([exe, case_file], capture_output=True, text=True, timeout=600)
+    return exe
+
+
+_C = {}
+
+
+def big540():
+    if "540" not in _C:
+        _C["540"] = D.single_posting_relation(540_000)
+    return _C["540"]
+
+
+def test_parse_functions_under_asan(tmp_path, harness):
+    """tests/native/fuzz_pages_device.cpp: the host pass and the kernels' (page, slot) grid as plain loops over csrc/pages_parse.h,
+    output arrays sized exactly as the device allocates them, built with AddressSanitizer + UBSan.  First the 40 damaged relations
+    tests/test_gpu_pages_device.py reads on the GPU, then 4000 more: every one accepted or refused as vbm25_segment_from_pages does,
+    equal arrays when accepted, no out-of-bounds access."""
+    base = D.damage_relation()
+    cases = D.random_damage(len(base), 40, seed=0)
+    outcomes = [D.host_outcome(D.apply_edits(base, e))[0] for e in cases]
+    assert any(outcomes) and not all(outcomes)   # seed 0 gives both classes
+    case_file = str(tmp_path / "cases.bin")
+    D.write_case_file(case_file, base, cases)
+    out = subprocess.run([harness, case_file], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert f"case file done: {sum(outcomes)} flattened, {len(outcomes) - sum(outcomes)} rejected" in out.stdout
     assert "fuzz done" in out.stdout
+
+
+def test_relations_reach_past_a_chunk_and_a_grid_pass():
+    """What tests/test_gpu_pages_device_scale.py relies on, counted on the pages the writer makes: a change of its layout cannot
+    quietly shrink the relations below the device reader's thresholds (CHUNK_PAGES pages per chunk; 2048 workgroups of 4 waves: 8192
+    pages per pass of the per-page kernels; 2048 x 256 tokens per pass of the per-token kernels)."""
+    seg, pl = big540()
+    (docs, toks, sums, blks), _ = D.tapes(pl)
+    assert min(len(toks), len(sums), len(blks)) > D.CHUNK_PAGES and len(toks) > 2 * D.CHUNK_PAGES and len(blks) > 2 * D.CHUNK_PAGES
+    assert seg.n_terms == 540_000 > D.TOKENS_PER_PASS and D.tuples_before(pl, toks, len(toks)) == seg.n_terms
+    tape_of = {"tokens": toks, "summaries": sums, "blocks": blks}
+    for name, kind, pages, edit, (tape, index, g) in D.chunk_damage(pl):
+        # every damaged tuple lies beyond chunk 0 of its tape, on the page the case names
+        assert index >= D.CHUNK_PAGES and pages == [tape_of[tape][index]], name
+        assert D.tuples_before(pl, tape_of[tape], index) <= g < D.tuples_before(pl, tape_of[tape], index + 1), name
+        if "chunk 2" in name or "last blocks page" in name:
+            assert index >= 2 * D.CHUNK_PAGES, name
+        if "first pass" in name:
+            assert g > D.TOKENS_PER_PASS, name
+    seg, pl = D.single_posting_relation(1_860_000)
+    (docs, toks, sums, blks), _ = D.tapes(pl)
+    assert len(toks) > 8192 and len(blks) > 8192 and len(sums) > D.CHUNK_PAGES
+    del pl
+    seg, pl, expect = D.wide_relation()
+    (docs, toks, sums, blks), _ = D.tapes(pl)
+    assert len(docs) > D.CHUNK_PAGES
+    D.check_wide_widths(vb.segment_from_pages(pl), expect)
+
+
+def test_chunked_relation_under_asan(tmp_path, harness):
+    """The harness on single_posting_relation(540 000), whose tokens, summaries and blocks tapes take two and three chunks: undamaged,
+    and with every case of chunk_damage (what tests/test_gpu_pages_device_scale.py then reads on the GPU).  Its loops reach
+    p / CHUNK_PAGES >= 1, with the chunks allocated exactly as the device allocates them.  The case file only: no generated relations."""
+    seg, pl = big540()
+    cases = [[]]
+    for name, kind, pages, edit, where in D.chunk_damage(pl):
+        cp = D.damaged(pl, pages, edit)
+        assert D.host_error(cp)[0] == -2, name
+        cases.append(D.byte_edits(pl, cp, pages))
+        assert cases[-1], name
+    case_file = str(tmp_path / "cases.bin")
+    D.write_case_file(case_file, pl, cases)
+    out = subprocess.run([harness, case_file, "only"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert f"case file done: 1 flattened, {len(cases) - 1} rejected" in out.stdout
+    assert "fuzz done" not in out.stdout
 
 
 def test_named_damage_belongs_in_the_list():
@@ -59,6 +113,36 @@ def test_named_damage_belongs_in_the_list():
         assert not ok and code == -2, name
     ok, seg0 = D.host_outcome(D.empty_relation())
     assert ok and seg0.n_docs == 0
+
+
+@pytest.mark.parametrize("params", [dict(k1=3.0), dict(b=1.5)], ids=["k1", "b"])
+def test_illegal_parameters_come_before_the_arrays_and_after_the_structure(params):
+    """The host reader's order, which the device reader has to reproduce (tests/test_gpu_pages_device_scale.py compares the two case by
+    case): with an illegal k1 or b the undamaged relation and the four named cases that leave the relation's structure whole are
+    VBM25_ERR_INVALID, the other fifteen stay VBM25_ERR_CORRUPT, and an empty index is accepted whatever its parameters."""
+    c, seg, oix, pages = D.relation(n_docs=800, vocab=100)
+    pl = [p.copy() for p in D.page_list(pages)]
+    assert D.host_outcome(D.damaged(pl, [0], D.set_params(**params))) == (False, -1)
+    codes = {}
+    for name, edit in D.named_damage(pl):
+        cp = [p.copy() for p in pl]
+        edit(cp)
+        D.set_params(**params)(cp)
+        codes[name] = D.host_error(cp)[0]
+    assert len(codes) == 19 and sorted(n for n, code in codes.items() if code == -1) == sorted(D.ARRAY_LEVEL_DAMAGE)
+    assert all(code == -2 for n, code in codes.items() if n not in D.ARRAY_LEVEL_DAMAGE)
+    empty = D.empty_relation()
+    D.set_params(**params)(empty)
+    ok, seg0 = D.host_outcome(empty)
+    assert ok and (seg0.n_docs, seg0.n_terms) == (0, 0) and seg0.meta()[next(iter(params))] == next(iter(params.values()))
+
+
+def test_paired_damage_names_the_first_error():
+    """the pairs of tests/test_gpu_pages_device_scale.py on the host reader: refused with the text and the page the construction says"""
+    c, seg, oix, pages = D.relation()
+    pl = [p.copy() for p in D.page_list(pages)]
+    for name, pgs, edits, text, page in D.paired_damage(pl):
+        assert D.host_error(D.damaged(pl, pgs, *edits)) == (-2, f"vbm25 error -2: data corruption: {text} (page {page})"), name
 
 
 def test_symbol_is_exported_and_declared():
