@@ -16,6 +16,7 @@ import pytest
 
 import orc
 import vectorchord_bm25_amd as vb
+from codec_data import TAIL_DOCS, WIDTH_DOCS, assert_tail_blocks, assert_width_blocks, build_args, tail_lists, width_lists
 from parity import assert_bit_exact
 
 pytestmark = pytest.mark.gpu
@@ -23,17 +24,7 @@ pytestmark = pytest.mark.gpu
 
 def _index(n_docs, lists, seed=0):
     """lists: [(docs ascending, tfs)] one per term -> (segment, arrays, GpuIndex, oracle index)."""
-    rng = np.random.default_rng(seed)
-    keys = np.zeros((len(lists), 16), dtype=np.uint8)
-    for i in range(len(lists)):
-        s = b"t%03d" % i
-        keys[i, :len(s)] = np.frombuffer(s, dtype=np.uint8)
-    term_start = np.cumsum([0] + [len(d) for d, _ in lists]).astype(np.uint64)
-    post_doc = np.concatenate([np.asarray(d, dtype=np.uint32) for d, _ in lists])
-    post_tf = np.concatenate([np.asarray(t, dtype=np.uint32) for _, t in lists])
-    # (2^31 documents: drawn as 32-bit values, the 64-bit ones would be another 17 GB)
-    doc_len = rng.integers(1, 3000, n_docs, dtype=np.uint32) if n_docs > (1 << 29) else rng.integers(1, 3000, n_docs).astype(np.uint32)
-    seg = vb.Segment.build(1.2, 0.75, doc_len, np.zeros((n_docs, 3), dtype=np.uint16), keys, term_start, post_doc, post_tf)
+    seg = vb.Segment.build(1.2, 0.75, *build_args(n_docs, lists, seed))
     a = seg.arrays()
     gix = vb.GpuIndex(seg)
     vb.set_tuning("id16_plane", 0)  # (read at index creation)
@@ -72,26 +63,8 @@ def _check_routes(tuning, gix, oix, terms, off, ks=(10, 128)):
 
 
 def test_byte_packed_tails_of_width_3_and_4(tuning):
-    n_docs = (1 << 25) + 5000
-    rng = np.random.default_rng(4)
-    a_docs = 7 + np.cumsum(rng.integers(1 << 16, 1 << 17, 40))               # tail of 40: gaps >= 2^16 -> 3-byte deltas
-    a_tf = rng.integers(1, 60000, 40)
-    a_tf[3] = 65535                                                         # 2-byte term frequencies
-    b_docs = np.array([5, 5 + (1 << 24) + 3, 5 + (1 << 25) + 9])             # a gap >= 2^24 -> width 4: raw absolute ids
-    b_tf = np.array([3, 1 << 17, 70000])                                     # 3-byte term frequencies
-    c_docs = np.r_[np.arange(128) * 3 + 1, (1 << 24) + 77]                   # a full block and a tail of ONE posting
-    c_tf = np.r_[rng.integers(1, 4, 128), 2]
-    d_docs = np.arange(0, n_docs - 1, 100_003)[:336]                         # two full wide blocks (no plane word) + a 3-byte tail of 80
-    d_tf = rng.integers(1, 300, len(d_docs))
-    e_docs = np.unique(np.r_[a_docs[::2], b_docs, c_docs[::7], d_docs[::5], rng.integers(0, n_docs, 300)])  # meets all of them
-    e_tf = rng.integers(1, 5, len(e_docs))
-    seg, a, gix, oix = _index(n_docs, [(a_docs, a_tf), (b_docs, b_tf), (c_docs, c_tf), (d_docs, d_tf), (e_docs, e_tf)])
-    first = a["term_first_block"]
-    md, mt, nblk = a["blk_meta_doc"], a["blk_meta_tf"], a["blk_n"]
-    assert md[first[0]] == 0x83 and mt[first[0]] == 0x82 and nblk[first[0]] == 40
-    assert md[first[1]] == 0x84 and mt[first[1]] == 0x83 and nblk[first[1]] == 3
-    assert nblk[first[2] + 1] == 1 and md[first[2]] < 32
-    assert md[first[3] + 2] == 0x83 and nblk[first[3] + 2] == 80 and a["blk_max_doc"][first[3]] - a["blk_min_doc"][first[3]] > 65535
+    seg, a, gix, oix = _index(TAIL_DOCS, tail_lists())
+    assert_tail_blocks(a)
     terms = np.array([0, 1, 2, 3, 4, 0, 4, 1, 4, 2, 4, 3, 4, 0, 1, 2, 3, 4, 0, 3, 1, 2], dtype=np.uint32)
     off = np.array([0, 1, 2, 3, 4, 5, 7, 9, 11, 13, 18, 20, 22], dtype=np.uint32)
     _check_routes(tuning, gix, oix, terms, off)
@@ -99,26 +72,9 @@ def test_byte_packed_tails_of_width_3_and_4(tuning):
 
 @pytest.mark.parametrize("seed", [1, 2])
 def test_every_bit_width_of_full_blocks(tuning, seed):
-    n_docs = (1 << 25) + 200_000
-    rng = np.random.default_rng(seed)
-    lists = []
-    for w in range(1, 26):  # 128 postings: gaps below 2^w, ONE of them with bit w - 1 set
-        gaps = rng.integers(1, min(1 << w, 400) + 1, 128) if w > 1 else np.ones(128, dtype=np.int64)
-        gaps = np.minimum(gaps, (1 << w) - 1)
-        gaps[0] = 0
-        gaps[rng.integers(1, 128)] = rng.integers(1 << (w - 1), 1 << w)
-        docs = rng.integers(0, 1000) + np.cumsum(gaps)
-        wt = 1 + (w - 1) % 17  # tf field width
-        tf = rng.integers(1, 1 << min(wt, 3), 128)
-        tf[rng.integers(0, 128)] = rng.integers(1 << (wt - 1), 1 << wt)
-        lists.append((docs, tf))
-    # a term that meets every list a few times, and a dense one
-    mix = np.unique(np.concatenate([d[::9] for d, _ in lists] + [rng.integers(0, n_docs, 500)]))
-    lists.append((mix, rng.integers(1, 4, len(mix))))
-    seg, a, gix, oix = _index(n_docs, lists, seed)
-    first = a["term_first_block"]
-    for w in range(1, 26):
-        assert a["blk_meta_doc"][first[w - 1]] == w and a["blk_meta_tf"][first[w - 1]] == 1 + (w - 1) % 17, w
+    lists = width_lists(seed)
+    seg, a, gix, oix = _index(WIDTH_DOCS, lists, seed)
+    assert_width_blocks(a)
     nterm = len(lists)
     terms, off = [], [0]
     for t in range(nterm - 1):  # every width alone and with the mixed term

@@ -8,8 +8,10 @@ import pytest
 
 import orc
 import vectorchord_bm25_amd as vb
+from codec_data import TAIL_DOCS, assert_tail_blocks, build_args, codec_growing, low_lists, tail_lists, wide_tf_tail
 from corpus import make_corpus, make_long_corpus
 from growing_data import make_growing
+from maintain_edge_data import FORMS, U32, growing_form, hand_tf_growing, sparse_corpus, sparse_deletes
 from maintain_model import NONE, decode_all_np, key_halves, maintain, make_growing_new_keys
 from test_segment_builder import assert_same_index, decode_all
 
@@ -67,25 +69,77 @@ def test_packed_words_and_flags_agree():
     assert np.array_equal(r1, r2) and all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a1, a2))
 
 
-@pytest.mark.parametrize("seed,frac,grow", [(1, 0.0, False), (2, 0.01, True), (3, 0.5, True), (4, 0.99, False), (5, 0.3, "new")])
+EDGE_PARAMS = [(1.2, 0.0), (2.0, 1.0), (1.6, 0.5)]
+
+
+@pytest.mark.parametrize("seed,frac,grow", [(1, 0.0, False), (2, 0.01, True), (3, 0.5, True), (4, 0.99, False), (5, 0.3, "new")]
+                         + [(6 + i, None, g) for i, g in enumerate(["hand_tf"] + FORMS)])
 def test_model_through_the_host_builder_equals_the_oracle_flush(seed, frac, grow):
-    c = make_corpus(3000, 150, seed=seed, length="lognormal", mean_len=30, zipf=1.0 if seed % 2 else None)
-    seg = vb.Segment.build(1.5, 0.6, c["doc_len"], c["doc_payload"], c["term_key"], c["term_start"], c["post_doc"], c["post_tf"])
-    deleted = np.random.default_rng(seed).random(3000) < frac
-    G = None
-    if grow is True:
-        G, _ = make_growing(seg.arrays()["term_key"], 400, seed=seed)
-    elif grow == "new":
-        G = make_growing_new_keys(seg.arrays()["term_key"], 400, seed=seed)
+    """frac None: the inputs of tests/test_gpu_maintain_edges.py at 3000 documents -- sealed documents without a posting (some kept,
+    some deleted), growing lengths at and beyond 2^32 - 1 (a tf of 2^32 - 1: a 4-byte tf tail), a growing CSR sliced out of a
+    larger one, growing segments all empty, all deleted, without flags, without and with nothing but unknown keys -- at three (k1, b)"""
+    if frac is None:
+        k1, b = EDGE_PARAMS[seed % 3]
+        args, bare = sparse_corpus()
+        seg = vb.Segment.build(k1, b, *args)
+        deleted = sparse_deletes(bare)
+        if grow == "hand_tf":
+            G, picked = hand_tf_growing(seg.arrays()["term_key"])
+        else:
+            G = growing_form(grow, seg.arrays()["term_key"])
+    else:
+        k1, b = 1.5, 0.6
+        c = make_corpus(3000, 150, seed=seed, length="lognormal", mean_len=30, zipf=1.0 if seed % 2 else None)
+        seg = vb.Segment.build(k1, b, c["doc_len"], c["doc_payload"], c["term_key"], c["term_start"], c["post_doc"], c["post_tf"])
+        deleted = np.random.default_rng(seed).random(3000) < frac
+        G = None
+        if grow is True:
+            G, _ = make_growing(seg.arrays()["term_key"], 400, seed=seed)
+        elif grow == "new":
+            G = make_growing_new_keys(seg.arrays()["term_key"], 400, seed=seed)
     args, relabel = maintain(seg.arrays(), seg.meta(), deleted, G)
-    assert args[0] == 1.5 and args[1] == 0.6
+    assert args[0] == k1 and args[1] == b
     oix = orc.OracleIndex.build(*args)
-    assert_same_index(vb.Segment.build(*args), oix)
+    out = vb.Segment.build(*args)
+    assert_same_index(out, oix)
     hi, lo = key_halves(args[4])
     assert np.all((hi[1:] > hi[:-1]) | ((hi[1:] == hi[:-1]) & (lo[1:] > lo[:-1])))
-    n_live_g = 0 if G is None else int((G["g_deleted"] == 0).sum())
+    n_grow = 0 if G is None else len(G["g_start"]) - 1
+    n_live_g = n_grow if G is None or G["g_deleted"] is None else int((G["g_deleted"] == 0).sum())
     assert len(args[2]) == int((~deleted).sum()) + n_live_g
     assert np.array_equal(np.sort(relabel[relabel != NONE]), np.arange(len(args[2])))
+    if frac is None:  # the kept documents without a posting: length 0, fieldnorm code 0
+        kept_bare = bare[~deleted[bare]]
+        fn = out.arrays()["doc_fieldnorm"]
+        assert 0 < len(kept_bare) < len(bare) and np.all(args[2][relabel[kept_bare]] == 0) and np.all(fn[relabel[kept_bare]] == 0)
+    if grow == "hand_tf":
+        for case, (g, length) in picked.items():
+            assert args[2][relabel[3000 + g]] == length, case
+        assert sorted(length for _, length in picked.values()) == [U32 - 1, U32, U32, U32]
+        assert fn[relabel[3000 + picked["over"][0]]] == 255 and 0x84 in out.arrays()["blk_meta_tf"]
+    if grow == "sliced":
+        assert G["g_start"][0] != 0 and len(G["g_tf"]) > G["g_start"][-1]
+    if grow == "all_empty":
+        assert len(G["g_tf"]) == 0 and np.all(fn[-n_grow:] == 0)
+
+
+def test_model_at_the_widest_tails_equals_the_oracle_flush():
+    """The byte-packed tails of tests/test_gpu_codec.py (3-byte deltas, raw absolute 4-byte ids, 2- and 3-byte tfs), a 4-byte tf tail and
+    the growing documents of tests/test_gpu_maintain_edges.py behind two lists that end at a low id, on 2^25 + 5000 documents, half
+    of the posting-bearing ones deleted: the model decodes them, and what it makes of them is the oracle's flush"""
+    lists = tail_lists() + [wide_tf_tail()] + low_lists()
+    seg = vb.Segment.build(1.2, 0.75, *build_args(TAIL_DOCS, lists, 1, payload=True))
+    a = seg.arrays()
+    assert_tail_blocks(a)
+    assert a["blk_meta_doc"][a["term_first_block"][5]] == 0x83 and a["blk_meta_tf"][a["term_first_block"][5]] == 0x84
+    bearing = np.unique(np.concatenate([np.asarray(d) for d, _ in lists]))
+    deleted = np.zeros(TAIL_DOCS, bool)
+    deleted[np.random.default_rng(9).choice(bearing, len(bearing) // 2, replace=False)] = True
+    args, relabel = maintain(a, seg.meta(), deleted, codec_growing(lists, deleted))
+    out = vb.Segment.build(*args)
+    assert_same_index(out, orc.OracleIndex.build(*args))
+    md, mt = out.arrays()["blk_meta_doc"], out.arrays()["blk_meta_tf"]
+    assert 0x83 in md and 0x84 in md and 0x84 in mt and np.any((md < 0x80) & (md >= 20))
 
 
 @pytest.mark.parametrize("kind", ["lognormal", "widetf", "mixed"])

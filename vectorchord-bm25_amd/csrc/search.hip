@@ -1590,6 +1590,8 @@ static int vbm25_batch_run_impl(vbm25_batch *bt, void *hip_stream) {
     bt->results_pinned_now = false;
     if (bt->index->n_docs == 0) {  // empty sealed segment: no hits (the growing segment is the shim's, search.rs:83-135)
         HIP_TRY(hipMemsetAsync(bt->n_hits.p, 0, 4ull * bt->nq, st));
+        // no kernel runs, and the fetch copies all nq x k records out: zeros, not what the allocator left in the buffer
+        if (bt->k) HIP_TRY(hipMemsetAsync(bt->hits.p, 0, sizeof(vbm25_hit) * size_t(bt->nq) * bt->k, st));
         return VBM25_OK;
     }
     const Route route = bt->plan.route;
