@@ -222,6 +222,15 @@ typedef struct vbm25_growing_desc {
     const uint8_t *deleted;    /* n_docs */
 } vbm25_growing_desc;
 int vbm25_growing_from_pages(vbm25_read_page_fn read_page, void *ctx, vbm25_growing **out);
+/* The sealed documents' `deleted` flags (DocumentTuple.deleted, byte 0 of the tuple; the reference's Bool: != 0), which neither
+ * reader of the sealed segment keeps: Meta -> Jump -> the documents tape with vbm25_segment_from_pages' checks and its
+ * VBM25_ERR_CORRUPT cases.  Bit d % 64 of words[d / 64] is set for every deleted document d and the other bits of the first
+ * ceil(n_docs / 64) words are cleared: DELETED polarity, the form vbm25_index_maintain and vbm25_filter_remap take.
+ * *n_docs receives the relation's document count, *n_deleted (may be NULL) the number of flags set.  words == NULL only counts
+ * (n_words is not looked at), so the caller can size the buffer; n_words < ceil(n_docs / 64) -> VBM25_ERR_INVALID and nothing
+ * written.  NULL read_page or n_docs -> VBM25_ERR_INVALID.  Host only: both consumers take host words. */
+int vbm25_sealed_deleted_from_pages(vbm25_read_page_fn read_page, void *ctx, uint64_t *words, uint32_t n_words, uint32_t *n_docs,
+                                    uint32_t *n_deleted);
 /* Cache key of the HBM copy of a relation's sealed segment: 32 bytes hashed (BLAKE3) over the Meta and Jump
  * tuples.  VACUUM replaces the sealed segment by rewriting the Jump tuple (maintain.rs:268-298: new tape
  * pointers, document count, sum of lengths), REINDEX rewrites Meta (new seed): either changes the fingerprint,
@@ -362,6 +371,26 @@ int vbm25_batch_set_filter(vbm25_batch *, const vbm25_filter *, const uint32_t *
  * the pipelined ring and to the multi-GPU batch. */
 typedef struct vbm25_device_growing vbm25_device_growing;
 int vbm25_growing_upload(vbm25_index *, const vbm25_growing_desc *, vbm25_device_growing **out);
+/* The device reader of the vectors tape: *out is what vbm25_growing_from_pages + vbm25_growing_get_desc + vbm25_growing_upload(index,
+ * ...) give, an ordinary device growing segment on the index's device (searched, appended to, deleted from and attached like any
+ * other; every search returns the same records byte for byte), without the host touching a tuple.  The host follows Meta -> Jump ->
+ * Jump.ptr_vectors -> Opaque.next (one header check and one copy into pinned staging per page, uploaded in chunks while the walk
+ * goes on; read_page is called once per page, from the calling thread); kernels classify the tuples, run the state machine of
+ * search.rs:83-135 as scans (an insert that did not reach its _0 is validated and dropped), copy the elements into the CSR's planes
+ * and check it (csrc/pages_device.hip, csrc/vectors_parse.h); vbm25_growing_upload's device half builds the segment from there.
+ *   csr: NULL, or *csr receives the CSR copied back from the device, byte for byte vbm25_growing_from_pages' six arrays (what
+ *   vbm25_index_maintain later takes; vbm25_growing_get_desc, vbm25_growing_free).  With csr == NULL no element array comes back.
+ *   Whatever vbm25_growing_from_pages refuses is VBM25_ERR_CORRUPT here, message "data corruption: ... (page N)": with several
+ *   damages the first in tape order, inside a tuple in the host reader's order (line pointer, too short, tag, no start, element
+ *   range); a refusal of the page walk (unreadable page, page header, special area, page linked twice) may come before a tuple's
+ *   on an earlier page.  What the reader accepts and vbm25_growing_upload refuses has upload's code: keys not strictly ascending
+ *   -> VBM25_ERR_INVALID naming the first such document, 2^31 elements or more (or 2^31 - 1 tuples) -> VBM25_ERR_UNSUPPORTED,
+ *   colliding document ranges -> VBM25_ERR_INVALID.  No HIP device -> VBM25_ERR_DEVICE (no host fallback); NULL index, read_page
+ *   or out -> VBM25_ERR_INVALID.  On every refusal *out and *csr are NULL, the HBM and pinned memory of the call is released and
+ *   the index and the device are as usable as before.  A tape of pages without tuples is a valid segment of 0 documents.
+ *   Synchronous; it uses a stream of its own until the segment's build, which is vbm25_growing_upload's. */
+int vbm25_device_growing_from_pages(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_growing **out,
+                                    vbm25_growing **csr);
 void vbm25_device_growing_free(vbm25_device_growing *);
 uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *);
 int vbm25_device_growing_append(vbm25_device_growing *, const vbm25_growing_desc *delta);

@@ -9,6 +9,7 @@
 //   vbm25::Index::search crates/bm25/src/search.rs:28-36   (bm25::search, filter == true)
 //   vbm25::search_growing, vbm25::merge_growing   crates/bm25/src/search.rs:83-135  (unsealed documents, host side)
 //   vbm25::Segment::from_pages, vbm25::growing_from_pages   the relation's pages -> flat arrays (tape.rs, tuples.rs)
+//   vbm25::DeviceGrowing::from_pages, vbm25::sealed_deleted_from_pages   the vectors tape read on the device; the sealed deleted flags
 // Reference panics ("data corruption", "invalid data") and pgrx::error! become vbm25::Error.
 #ifndef VBM25_HPP
 #define VBM25_HPP
@@ -284,9 +285,13 @@ struct GrowingDocs {
     size_t size() const { return start.size() - 1; }
 };
 // The unsealed documents of a relation (vectors tape from Jump.ptr_vectors; VectorTuple _2 / _1 / _0).
+inline GrowingDocs growing_docs_of(vbm25_growing *g);  // (takes the handle over)
 inline GrowingDocs growing_from_pages(vbm25_read_page_fn read_page, void *ctx) {
     vbm25_growing *g = nullptr;
     check(vbm25_growing_from_pages(read_page, ctx, &g));
+    return growing_docs_of(g);
+}
+inline GrowingDocs growing_docs_of(vbm25_growing *g) {
     vbm25_growing_desc d;
     const int rc = vbm25_growing_get_desc(g, &d);
     GrowingDocs out;
@@ -302,6 +307,16 @@ inline GrowingDocs growing_from_pages(vbm25_read_page_fn read_page, void *ctx) {
     vbm25_growing_free(g);
     check(rc);
     return out;
+}
+// DocumentTuple.deleted of every sealed document of a relation as the DELETED words vbm25_index_maintain and vbm25_filter_remap
+// take (bit d % 64 of word d / 64); n_docs, when given, receives the document count (vbm25_sealed_deleted_from_pages)
+inline std::vector<uint64_t> sealed_deleted_from_pages(vbm25_read_page_fn read_page, void *ctx, uint32_t *n_docs = nullptr) {
+    uint32_t n = 0;
+    check(vbm25_sealed_deleted_from_pages(read_page, ctx, nullptr, 0, &n, nullptr));
+    std::vector<uint64_t> words((size_t(n) + 63) / 64);
+    check(vbm25_sealed_deleted_from_pages(read_page, ctx, words.data(), uint32_t(words.size()), &n, nullptr));
+    if (n_docs) *n_docs = n;
+    return words;
 }
 // Scores the unsealed documents with the sealed segment's statistics (host code, as in the reference).
 inline std::vector<Hit> search_growing(const vbm25_index_desc &desc, const Query &query, size_t k,
@@ -334,6 +349,17 @@ class DeviceGrowing {
         const vbm25_growing_desc d = desc_of(g);
         check(vbm25_growing_upload(index.handle(), &d, &h_));
     }
+    // The growing segment of a relation read on the index's device (vbm25_device_growing_from_pages: the host follows the vectors
+    // tape's page chain, kernels parse, validate and flatten): the segment DeviceGrowing(index, growing_from_pages(...)) makes.
+    // `csr`, when given, receives the CSR copied back from the device (growing_from_pages' arrays).
+    static DeviceGrowing from_pages(Index &index, vbm25_read_page_fn read_page, void *ctx, GrowingDocs *csr = nullptr) {
+        DeviceGrowing out;
+        vbm25_growing *g = nullptr;
+        check(vbm25_device_growing_from_pages(index.handle(), read_page, ctx, &out.h_, csr ? &g : nullptr));
+        if (csr) *csr = growing_docs_of(g);
+        return out;
+    }
+    DeviceGrowing(DeviceGrowing &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     // the new documents only: document i of `delta` becomes growing document docs() + i (vbm25_device_growing_append)
     void append(const GrowingDocs &delta) {
         const vbm25_growing_desc d = desc_of(delta);
@@ -358,6 +384,7 @@ class DeviceGrowing {
     vbm25_device_growing *handle() const { return h_; }
 
   private:
+    DeviceGrowing() = default;
     static vbm25_growing_desc desc_of(const GrowingDocs &g) {
         vbm25_growing_desc d{};
         d.n_docs = uint32_t(g.size());

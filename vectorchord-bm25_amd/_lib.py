@@ -59,6 +59,7 @@ ABI = {
     "vbm25_evaluate": (i32, [vp, vp, vp, u32, vp, u32, vp]),
     "vbm25_segment_from_pages": (i32, [vp, vp, vp]),
     "vbm25_growing_from_pages": (i32, [vp, vp, vp]),
+    "vbm25_sealed_deleted_from_pages": (i32, [vp, vp, vp, u32, vp, vp]),
     "vbm25_growing_get_desc": (i32, [vp, vp]),
     "vbm25_growing_free": (None, [vp]),
     "vbm25_pages_fingerprint": (i32, [vp, vp, vp]),
@@ -84,6 +85,7 @@ ABI = {
     "vbm25_search_batch_filtered": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
     "vbm25_batch_set_filter": (i32, [vp, vp, vp]),
     "vbm25_growing_upload": (i32, [vp, vp, vp]),
+    "vbm25_device_growing_from_pages": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_device_growing_free": (None, [vp]),
     "vbm25_device_growing_bytes": (u64, [vp]),
     "vbm25_device_growing_append": (i32, [vp, vp]),

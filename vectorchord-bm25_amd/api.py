@@ -721,6 +721,28 @@ class GrowingSegment:
         """from growing_from_pages(pages)"""
         return cls(index, grow["g_start"], grow["g_key"], grow["g_tf"], grow["g_fieldnorm"], grow["g_payload"], grow.get("g_deleted"))
 
+    @classmethod
+    def from_pages(cls, index, pages, return_csr=False):
+        """vbm25_device_growing_from_pages: the growing segment of a bm25 index relation in the reference's on-disk format, read on
+        the device of `index` (the host follows the vectors tape's page chain, kernels parse, validate and flatten the tuples) --
+        the segment from_dict(index, growing_from_pages(pages)) makes, without the host touching a tuple.  `pages` as
+        DeviceSegment.from_pages takes it.  With return_csr the CSR comes back from the device as well: (segment, the dict of
+        growing_from_pages)."""
+        cb, keep = _page_reader(pages)
+        self = cls.__new__(cls)
+        self.index = index
+        self.h = C.c_void_p()
+        csr = C.c_void_p()
+        check(lib().vbm25_device_growing_from_pages(index.h, C.cast(cb, C.c_void_p), None, C.byref(self.h),
+                                                    C.byref(csr) if return_csr else None))
+        self.n_docs = int(lib().vbm25_device_growing_docs(self.h))
+        if not return_csr:
+            return self
+        try:
+            return self, _growing_dict(csr)
+        finally:
+            lib().vbm25_growing_free(csr)
+
     def append(self, g_start, g_key, g_tf, g_fieldnorm, g_payload, g_deleted=None):
         """vbm25_device_growing_append: the CSR of the new documents only (the constructor's form); document i becomes growing
         document n_docs + i.  Only these arrays cross the host link; a batch that holds the segment sees them at its next run."""
@@ -1086,20 +1108,37 @@ def growing_from_pages(pages):
     h = C.c_void_p()
     check(lib().vbm25_growing_from_pages(C.cast(cb, C.c_void_p), None, C.byref(h)))
     try:
-        d = GrowingDesc()
-        check(lib().vbm25_growing_get_desc(h, C.byref(d)))
-
-        def arr(ptr, n, dt):
-            if not n or not ptr:
-                return np.zeros(0, dtype=dt)
-            buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(ptr)
-            return np.frombuffer(buf, dtype=dt).copy()
-        return dict(g_start=arr(d.start, d.n_docs + 1, np.uint64), g_key=arr(d.key, 16 * d.n_elements, np.uint8),
-                    g_tf=arr(d.tf, d.n_elements, np.uint32), g_fieldnorm=arr(d.fieldnorm, d.n_docs, np.uint8),
-                    g_payload=arr(d.payload, 3 * d.n_docs, np.uint16).reshape(-1, 3),
-                    g_deleted=arr(d.deleted, d.n_docs, np.uint8))
+        return _growing_dict(h)
     finally:
         lib().vbm25_growing_free(h)
+
+
+def _growing_dict(h):
+    """copies of the six arrays of a vbm25_growing"""
+    d = GrowingDesc()
+    check(lib().vbm25_growing_get_desc(h, C.byref(d)))
+
+    def arr(ptr, n, dt):
+        if not n or not ptr:
+            return np.zeros(0, dtype=dt)
+        buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(ptr)
+        return np.frombuffer(buf, dtype=dt).copy()
+    return dict(g_start=arr(d.start, d.n_docs + 1, np.uint64), g_key=arr(d.key, 16 * d.n_elements, np.uint8),
+                g_tf=arr(d.tf, d.n_elements, np.uint32), g_fieldnorm=arr(d.fieldnorm, d.n_docs, np.uint8),
+                g_payload=arr(d.payload, 3 * d.n_docs, np.uint16).reshape(-1, 3),
+                g_deleted=arr(d.deleted, d.n_docs, np.uint8))
+
+
+def sealed_deleted_from_pages(pages):
+    """vbm25_sealed_deleted_from_pages: DocumentTuple.deleted of every sealed document of the relation, a bool array of n_docs
+    (True = deleted): what DeviceSegment.maintain and DocFilter.remap take as sealed_deleted."""
+    cb, keep = _page_reader(pages)
+    fn = C.cast(cb, C.c_void_p)
+    n_docs = C.c_uint32()
+    check(lib().vbm25_sealed_deleted_from_pages(fn, None, None, 0, C.byref(n_docs), None))
+    words = np.zeros((n_docs.value + 63) // 64, dtype=np.uint64)
+    check(lib().vbm25_sealed_deleted_from_pages(fn, None, _p(words), len(words), C.byref(n_docs), None))
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:n_docs.value].astype(bool)
 
 
 def evaluate(segment_or_desc, doc_keys, doc_tfs, query):

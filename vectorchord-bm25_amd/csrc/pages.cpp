@@ -1,5 +1,5 @@
 // pages.cpp -- host side: a bm25 index relation in the reference's on-disk format -> flattened
-// arrays (vbm25_segment) and the growing segment's CSR.  See include/vbm25.h for the contract; the
+// arrays (vbm25_segment), the growing segment's CSR and the sealed documents' deleted flags.  See include/vbm25.h for the contract; the
 // reference files restated here are cited there and below.  No device code.
 #include "vbm25_internal.h"
 
@@ -109,15 +109,6 @@ Jump read_meta_jump(const Relation &rel, double &k1, double &b) {
 }
 
 }  // namespace
-
-struct vbm25_growing {
-    std::vector<uint64_t> start{0};
-    std::vector<uint8_t> key;
-    std::vector<uint32_t> tf;
-    std::vector<uint8_t> fieldnorm;
-    std::vector<uint16_t> payload;
-    std::vector<uint8_t> deleted;
-};
 
 extern "C" {
 
@@ -281,6 +272,45 @@ int vbm25_growing_from_pages(vbm25_read_page_fn read_page, void *ctx, vbm25_grow
         return set_error(VBM25_ERR_CORRUPT, "data corruption: %s (page %u)", c.what, c.page);
     } catch (const std::bad_alloc &) {
         return set_error(VBM25_ERR_NOMEM, "out of host memory while reading the growing segment");
+    } catch (const std::exception &e) {
+        return set_error(VBM25_ERR_INVALID, "internal error: %s", e.what());
+    }
+}
+
+int vbm25_sealed_deleted_from_pages(vbm25_read_page_fn read_page, void *ctx, uint64_t *words, uint32_t n_words, uint32_t *n_docs,
+                                    uint32_t *n_deleted) {
+    if (!read_page || !n_docs) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    *n_docs = 0;
+    if (n_deleted) *n_deleted = 0;
+    try {
+        const Relation rel{read_page, ctx, {}};
+        double k1, b;
+        const Jump jump = read_meta_jump(rel, k1, b);
+        const uint64_t need = (uint64_t(jump.n_docs) + 63) / 64;
+        if (words && n_words < need)
+            return set_error(VBM25_ERR_INVALID, "%u words for the deleted flags of %u documents: %llu needed", n_words, jump.n_docs,
+                             (unsigned long long)need);
+        // the flags go into the caller's words only when the whole tape was read
+        std::vector<uint64_t> bits(words ? need : 0, 0);
+        uint64_t d = 0;
+        uint32_t deleted = 0;
+        walk_tape(rel, jump.ptr_documents, [&](uint32_t page, uint16_t, const uint8_t *t, uint32_t size) {
+            if (size < 8) throw Corrupt{"document tuple too short", page};
+            if (t[0] != 0) {  // DocumentTuple.deleted (tuples.rs:756-781)
+                ++deleted;
+                if (words && d < jump.n_docs) bits[d / 64] |= 1ull << (d % 64);
+            }
+            ++d;
+        });
+        if (d != jump.n_docs) throw Corrupt{"document count differs from the Jump tuple", jump.ptr_documents};
+        if (words) std::memcpy(words, bits.data(), 8 * bits.size());
+        *n_docs = jump.n_docs;
+        if (n_deleted) *n_deleted = deleted;
+        return VBM25_OK;
+    } catch (const Corrupt &c) {
+        return set_error(VBM25_ERR_CORRUPT, "data corruption: %s (page %u)", c.what, c.page);
+    } catch (const std::bad_alloc &) {
+        return set_error(VBM25_ERR_NOMEM, "out of host memory while reading the deleted flags");
     } catch (const std::exception &e) {
         return set_error(VBM25_ERR_INVALID, "internal error: %s", e.what());
     }

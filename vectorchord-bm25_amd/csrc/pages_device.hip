@@ -1,5 +1,6 @@
-// pages_device.hip -- the device reader: a bm25 index relation in the reference's on-disk format -> a sealed segment in HBM
-// (vbm25_device_segment_from_pages).  Same accept / refuse contract as the host reader (csrc/pages.cpp) followed by check_desc
+// pages_device.hip -- the device readers: a bm25 index relation in the reference's on-disk format -> a sealed segment in HBM
+// (vbm25_device_segment_from_pages, below) and its vectors tape -> a device growing segment (vbm25_device_growing_from_pages,
+// further down).  The sealed segment: same accept / refuse contract as the host reader (csrc/pages.cpp) followed by check_desc
 // (csrc/segment.cpp); the result is byte for byte what vbm25_segment_from_pages flattens, without a host copy of the index.
 //
 //   host pass      Meta, Jump, then the four tapes by Opaque.next (pages_parse.h: walk_relation): one header check and one memcpy of the
@@ -27,6 +28,7 @@
 #include "vbm25_internal.h"
 #include "device_segment.h"
 #include "pages_parse.h"
+#include "vectors_parse.h"
 
 namespace {
 
@@ -375,6 +377,259 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     return VBM25_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The vectors tape -> a device growing segment (vbm25_device_growing_from_pages; vectors_parse.h has the tuple layout and the lanes).
+//   host pass            Meta, Jump, the vectors tape by Opaque.next (walk_vectors), staged and uploaded as above
+//   vec_classify_kernel  one wave per page, lane i takes slot i + 1 (+ 64 ...): line pointer, length, tag, element range
+//   (scans)              t_sum: attempt number and documents ended; t_last: is the tuple open (hipcub, 64 bits)
+//   vec_resolve_kernel   one thread per tuple: continuation / end without a start; an open _0 finishes its attempt
+//   vec_kept_kernel      one thread per tuple: the elements it gives (none in an attempt that did not finish)
+//   (scan)               t_eoff: element offsets, the total in 64 bits
+//   vec_finish_kernel    one wave per page, lane per slot: fieldnorm from the _2; deleted, payload and start[g + 1] from the _0
+//   vec_copy_kernel      one wave per page, lanes over the page's ELEMENTS: 20 bytes -> the key plane (16) and the tf plane (4)
+//   vec_check_kernel     the same lanes: keys strictly ascending inside a document (vbm25_growing_upload's rule)
+// then the device half of vbm25_growing_upload (search.hip) on those arrays.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct TupleIncrement {
+    __host__ __device__ unsigned long long operator()(uint32_t meta) const { return tuple_increment(meta); }
+};
+struct MaxU64 {
+    __host__ __device__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a > b ? a : b; }
+};
+
+thread_local double g_vec_stats[4];
+
+__global__ void __launch_bounds__(WG_THREADS) vec_classify_kernel(VecPlanes c, unsigned long long *err) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    for (uint32_t p = wave; p < c.tape.n_pages; p += n_waves) {
+        const uint32_t base = c.tape.pre[p], n = c.tape.pre[p + 1] - base;
+        for (uint32_t i = lane; i < n; i += 64)
+            if (const uint32_t r = classify_lane(c, p, i)) atomicMin(err, (unsigned long long)error_key(0, (uint64_t)base + i, r));
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) vec_resolve_kernel(VecPlanes c, unsigned long long *err) {
+    for (uint64_t g = (uint64_t)blockIdx.x * WG_THREADS + threadIdx.x; g < c.tape.n_tuples; g += (uint64_t)gridDim.x * WG_THREADS)
+        if (const uint32_t r = resolve_lane(c, g)) atomicMin(err, (unsigned long long)error_key(0, g, r));
+}
+
+__global__ void __launch_bounds__(WG_THREADS) vec_kept_kernel(VecPlanes c) {
+    for (uint64_t g = (uint64_t)blockIdx.x * WG_THREADS + threadIdx.x; g < c.tape.n_tuples; g += (uint64_t)gridDim.x * WG_THREADS) kept_lane(c, g);
+}
+
+__global__ void __launch_bounds__(WG_THREADS) vec_finish_kernel(VecPlanes c) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    for (uint32_t p = wave; p < c.tape.n_pages; p += n_waves) {
+        const uint32_t n = c.tape.pre[p + 1] - c.tape.pre[p];
+        for (uint32_t i = lane; i < n; i += 64) finish_lane(c, p, i);
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) vec_copy_kernel(VecPlanes c) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    for (uint32_t p = wave; p < c.tape.n_pages; p += n_waves) {
+        const uint32_t m = page_elements(c, p);
+        for (uint32_t j = lane; j < m; j += 64) copy_element_lane(c, p, j);
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) vec_check_kernel(VecPlanes c, unsigned long long *err) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    for (uint32_t p = wave; p < c.tape.n_pages; p += n_waves) {
+        const uint32_t m = page_elements(c, p);
+        for (uint32_t j = lane; j < m; j += 64) {
+            uint32_t doc = 0;
+            if (const uint32_t r = check_element_lane(c, p, j, doc)) atomicMin(err, (unsigned long long)error_key(0, doc, r));
+        }
+    }
+}
+
+int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_growing **out, vbm25_growing **csr) {
+    if (csr) *csr = nullptr;
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!index || !read_page) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the device reader has no CPU fallback (vbm25_growing_from_pages is the host reader)");
+    int device = 0;
+    uint32_t sealed_docs = 0;
+    if (int rc = index_device_and_docs(index, &device, &sealed_docs)) return rc;
+    PG_TRY(hipSetDevice(device));
+    for (double &x : g_vec_stats) x = 0.0;
+
+    Stream stream;
+    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t s = stream.s;
+    Stager st;
+    if (int rc = st.init(s)) return rc;
+
+    // ---- the host pass
+    Walk w;
+    int sink_rc = 0;
+    const bool walked = walk_vectors(read_page, ctx, w, [&](uint32_t tape, uint32_t, const uint8_t *image) { return st.add(tape, image); }, sink_rc);
+    if (!walked) {
+        (void)hipStreamSynchronize(s);  // nothing is freed under a copy in flight
+        return sink_rc ? sink_rc : corrupt(w.what, w.bad_page);
+    }
+    if (int rc = st.flush()) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    const size_t np = w.pid[0].size();
+    const uint64_t n = w.pre[0].back();
+    if (n + 1 >= (uint64_t)INT_MAX) {
+        (void)hipStreamSynchronize(s);
+        return set_error(VBM25_ERR_UNSUPPORTED, "more than 2^31 tuples on the vectors tape");
+    }
+    uint64_t bytes_down = 0;
+
+    // ---- the tape's tables and the call's scratch.  From here on a failure returns through the buffers' destructors: hipFree waits
+    // for the device, nothing is freed under a kernel or a copy in flight
+    DBuf d_chunk, d_pre, d_meta, d_cnt, d_mark, d_sum, d_last, d_fin, d_kept, d_eoff, d_err, d_tmp[3];
+    std::vector<const uint8_t *> chunk_ptr;
+    for (const auto &d : st.chunks[0]) chunk_ptr.push_back(d->as<uint8_t>());
+    PG_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
+    PG_TRY(d_pre.alloc(4 * (np + 1)));
+    if (np) PG_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
+    PG_TRY(hipMemcpyAsync(d_pre.p, w.pre[0].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
+    st.bytes_up += 8 * chunk_ptr.size() + 4 * (np + 1);
+    PG_TRY(d_meta.alloc(4 * n));
+    PG_TRY(d_cnt.alloc(4 * n));
+    PG_TRY(d_mark.alloc(8 * n));
+    PG_TRY(d_sum.alloc(8 * n));
+    PG_TRY(d_last.alloc(8 * n));
+    PG_TRY(d_fin.alloc(n + 1));
+    PG_TRY(d_kept.alloc(4 * (n + 1)));
+    PG_TRY(d_eoff.alloc(8 * (n + 1)));
+    PG_TRY(d_err.alloc(8));
+    VecPlanes c{};
+    c.tape = TapeView{d_chunk.as<const uint8_t *>(), nullptr, d_pre.as<uint32_t>(), (uint32_t)np, (uint32_t)n};
+    c.t_meta = d_meta.as<uint32_t>();
+    c.t_cnt = d_cnt.as<uint32_t>();
+    c.t_mark = d_mark.as<unsigned long long>();
+    c.t_sum = d_sum.as<unsigned long long>();
+    c.t_last = d_last.as<unsigned long long>();
+    c.finished = d_fin.as<uint8_t>();
+    c.t_kept = d_kept.as<uint32_t>();
+    c.t_eoff = d_eoff.as<unsigned long long>();
+    unsigned long long *err = d_err.as<unsigned long long>();
+    const uint32_t page_grid = grid_for(np, 4), tuple_grid = grid_for(n, WG_THREADS);
+
+    Event ev[4];
+    for (Event &e : ev) PG_TRY(hipEventCreate(&e.e));
+    PG_TRY(hipEventRecord(ev[0].e, s));
+    PG_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
+    PG_TRY(hipMemsetAsync(d_fin.p, 0, n + 1, s));
+    PG_TRY(hipMemsetAsync(d_kept.p, 0, 4 * (n + 1), s));
+    if (n) {
+        vec_classify_kernel<<<page_grid, WG_THREADS, 0, s>>>(c, err);
+        hipcub::TransformInputIterator<unsigned long long, TupleIncrement, const uint32_t *> inc(c.t_meta, TupleIncrement());
+        size_t tb = 0;
+        PG_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, inc, d_sum.as<unsigned long long>(), (int)n, s));
+        PG_TRY(d_tmp[0].alloc(tb));
+        PG_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp[0].p, tb, inc, d_sum.as<unsigned long long>(), (int)n, s));
+        PG_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, c.t_mark, d_last.as<unsigned long long>(), MaxU64(), 0ull, (int)n, s));
+        PG_TRY(d_tmp[1].alloc(tb));
+        PG_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp[1].p, tb, c.t_mark, d_last.as<unsigned long long>(), MaxU64(), 0ull, (int)n, s));
+        vec_resolve_kernel<<<tuple_grid, WG_THREADS, 0, s>>>(c, err);
+        vec_kept_kernel<<<tuple_grid, WG_THREADS, 0, s>>>(c);
+    }
+    {   // n + 1 entries: the last one is the total
+        hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(c.t_kept, WidenU32());
+        size_t tb = 0;
+        PG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, wide, d_eoff.as<unsigned long long>(), (int)(n + 1), s));
+        PG_TRY(d_tmp[2].alloc(tb));
+        PG_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp[2].p, tb, wide, d_eoff.as<unsigned long long>(), (int)(n + 1), s));
+    }
+    PG_TRY(hipGetLastError());
+    PG_TRY(hipEventRecord(ev[1].e, s));
+    unsigned long long key = 0, counts = 0, n_el = 0;
+    PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    if (n) PG_TRY(hipMemcpyAsync(&counts, d_sum.as<unsigned long long>() + (n - 1), 8, hipMemcpyDeviceToHost, s));
+    PG_TRY(hipMemcpyAsync(&n_el, d_eoff.as<unsigned long long>() + n, 8, hipMemcpyDeviceToHost, s));
+    PG_TRY(hipStreamSynchronize(s));
+    bytes_down += 24;
+
+    // ---- the verdict so far: the host reader's refusals, then vbm25_growing_upload's in its order
+    if (key != NO_ERROR) return corrupt(vreason_text(key_reason(key)), error_page(w, key));
+    const uint32_t n_docs = (uint32_t)counts;  // every _0 of a tape without a refusal ended a document
+    if ((uint64_t)sealed_docs + n_docs > (1ull << 32))
+        return set_error(VBM25_ERR_INVALID, "%u sealed + %llu growing documents exceed 2^32: the doc id ranges would collide", sealed_docs,
+                         (unsigned long long)n_docs);
+    if (n_el >= (1ull << 31))
+        return set_error(VBM25_ERR_UNSUPPORTED, "%llu growing elements: the device path takes fewer than 2^31", n_el);
+
+    // ---- the CSR
+    DBuf d_start, d_key, d_tf, d_fn, d_del, d_payload;
+    PG_TRY(d_start.alloc(8ull * (n_docs + 1ull)));
+    PG_TRY(d_key.alloc(16ull * n_el));
+    PG_TRY(d_tf.alloc(4ull * n_el));
+    PG_TRY(d_fn.alloc(n_docs));
+    PG_TRY(d_del.alloc(n_docs));
+    PG_TRY(d_payload.alloc(6ull * n_docs));
+    c.n_docs = n_docs;
+    c.n_el = n_el;
+    c.start = d_start.as<unsigned long long>();
+    c.key = d_key.as<uint8_t>();
+    c.tf = d_tf.as<uint32_t>();
+    c.fieldnorm = d_fn.as<uint8_t>();
+    c.deleted = d_del.as<uint8_t>();
+    c.payload = d_payload.as<uint16_t>();
+    PG_TRY(hipEventRecord(ev[2].e, s));
+    PG_TRY(hipMemsetAsync(d_start.p, 0, 8, s));
+    if (n_docs) vec_finish_kernel<<<page_grid, WG_THREADS, 0, s>>>(c);
+    if (n_el) {
+        vec_copy_kernel<<<page_grid, WG_THREADS, 0, s>>>(c);
+        vec_check_kernel<<<page_grid, WG_THREADS, 0, s>>>(c, err);
+    }
+    PG_TRY(hipGetLastError());
+    PG_TRY(hipEventRecord(ev[3].e, s));
+    PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    PG_TRY(hipStreamSynchronize(s));
+    bytes_down += 8;
+    if (key != NO_ERROR)
+        return set_error(VBM25_ERR_INVALID, "growing document %u: keys must be strictly ascending", (uint32_t)key_pos(key));
+
+    // ---- the CSR's host copy, when asked for, before the scratch goes
+    std::unique_ptr<vbm25_growing> host;
+    if (csr) {
+        host = std::make_unique<vbm25_growing>();
+        host->start.resize(n_docs + 1ull);
+        host->key.resize(16ull * n_el);
+        host->tf.resize(n_el);
+        host->fieldnorm.resize(n_docs);
+        host->payload.resize(3ull * n_docs);
+        host->deleted.resize(n_docs);
+        PG_TRY(hipMemcpyAsync(host->start.data(), d_start.p, 8ull * (n_docs + 1ull), hipMemcpyDeviceToHost, s));
+        if (n_el) {
+            PG_TRY(hipMemcpyAsync(host->key.data(), d_key.p, 16ull * n_el, hipMemcpyDeviceToHost, s));
+            PG_TRY(hipMemcpyAsync(host->tf.data(), d_tf.p, 4ull * n_el, hipMemcpyDeviceToHost, s));
+        }
+        if (n_docs) {
+            PG_TRY(hipMemcpyAsync(host->fieldnorm.data(), d_fn.p, n_docs, hipMemcpyDeviceToHost, s));
+            PG_TRY(hipMemcpyAsync(host->payload.data(), d_payload.p, 6ull * n_docs, hipMemcpyDeviceToHost, s));
+            PG_TRY(hipMemcpyAsync(host->deleted.data(), d_del.p, n_docs, hipMemcpyDeviceToHost, s));
+        }
+        PG_TRY(hipStreamSynchronize(s));
+        bytes_down += 8ull * (n_docs + 1ull) + 20ull * n_el + 8ull * n_docs;
+    }
+
+    // ---- the segment: the device half of vbm25_growing_upload
+    const GrowingDeviceArrays a{n_docs, n_el, d_start.as<uint64_t>(), d_key.as<uint8_t>(), d_tf.as<uint32_t>(), d_fn.as<uint8_t>(),
+                                d_del.as<uint8_t>(), d_payload.as<uint16_t>()};
+    if (int rc = growing_from_device_arrays(index, a, out)) return rc;
+    float ms_a = 0, ms_b = 0;
+    PG_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
+    PG_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
+    g_vec_stats[0] = (double)ms_a + (double)ms_b;
+    g_vec_stats[1] = (double)st.bytes_up;
+    g_vec_stats[2] = (double)bytes_down;
+    g_vec_stats[3] = (double)n_el;
+    if (csr) *csr = host.release();
+    return VBM25_OK;
+}
+
 }  // namespace
 
 extern "C" int vbm25_device_segment_from_pages(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_device_segment **out) {
@@ -387,5 +642,19 @@ extern "C" int vbm25_device_segment_from_pages(vbm25_read_page_fn read_page, voi
 extern "C" int vbm25_debug_pages_device_stats(double *out4) {
     if (!out4) return vbm25::set_error(VBM25_ERR_INVALID, "NULL argument");
     for (int i = 0; i < 4; ++i) out4[i] = g_stats[i];
+    return VBM25_OK;
+}
+
+extern "C" int vbm25_device_growing_from_pages(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_growing **out,
+                                               vbm25_growing **csr) {
+    return vbm25::guarded([&] { return growing_from_pages_impl(index, read_page, ctx, out, csr); });
+}
+
+// The last successful vbm25_device_growing_from_pages of this thread (tools/growing_pages_cost.py; not part of the ABI): [0] ms of the
+// reader's kernels and scans between HIP events (the segment's build behind them is vbm25_growing_upload's), [1] bytes host ->
+// device, [2] bytes device -> host, [3] elements read
+extern "C" int vbm25_debug_growing_pages_stats(double *out4) {
+    if (!out4) return vbm25::set_error(VBM25_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < 4; ++i) out4[i] = g_vec_stats[i];
     return VBM25_OK;
 }

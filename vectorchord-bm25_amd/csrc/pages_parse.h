@@ -324,49 +324,65 @@ inline const uint8_t *first_tuple(Walk &w, const uint8_t *page, uint32_t id, uin
     return page + off;
 }
 
-// false: refused (w.what / w.bad_page), or the sink's status in `sink_rc`
-template <class Sink>
-bool walk_relation(vbm25_read_page_fn fn, void *ctx, Walk &w, Sink &&sink, int &sink_rc) {
-    sink_rc = 0;
+// Meta (page 0, slot 1) and Jump (slot 1 of the page Meta names), as the host reader's read_meta_jump: k1, b, n_docs and sum_len go
+// into `w`; returns the Jump tuple (at least 64 bytes), nullptr: refused (w.what / w.bad_page)
+inline const uint8_t *read_meta_jump(vbm25_read_page_fn fn, void *ctx, Walk &w) {
     uint32_t len = 0;
     const uint8_t *mp = fn(ctx, 0);
-    if (!mp) return w.fail("page cannot be read", 0);
+    if (!mp) return w.fail("page cannot be read", 0), nullptr;
     const uint8_t *m = first_tuple(w, mp, 0, len);
-    if (!m) return false;
-    if (len < 72 || std::memcmp(m, "vchordbm", 8) != 0) return w.fail("bad magic number", 0);
+    if (!m) return nullptr;
+    if (len < 72 || std::memcmp(m, "vchordbm", 8) != 0) return w.fail("bad magic number", 0), nullptr;
     uint64_t version;
     std::memcpy(&version, m + 8, 8);
-    if (version != 1) return w.fail("bad version number: REINDEX needed", 0);
+    if (version != 1) return w.fail("bad version number: REINDEX needed", 0), nullptr;
     std::memcpy(&w.k1, m + 16, 8);
     std::memcpy(&w.b, m + 24, 8);
     const uint32_t ptr_jump = host_rd32(m + 36);
     const uint8_t *jp = fn(ctx, ptr_jump);
-    if (!jp) return w.fail("page cannot be read", ptr_jump);
+    if (!jp) return w.fail("page cannot be read", ptr_jump), nullptr;
     const uint8_t *j = first_tuple(w, jp, ptr_jump, len);
-    if (!j) return false;
-    if (len < 64) return w.fail("jump tuple too short", ptr_jump);
+    if (!j) return nullptr;
+    if (len < 64) return w.fail("jump tuple too short", ptr_jump), nullptr;
     w.n_docs = host_rd32(j + 4);
     std::memcpy(&w.sum_len, j + 8, 8);
+    return j;
+}
+
+// One tape from page `first` by Opaque.next into w.pid[t] / w.pre[t]; `walked` holds the pages seen so far.  false: refused
+// (w.what / w.bad_page), or the sink's status in `sink_rc`
+template <class Sink>
+bool walk_tape_pages(vbm25_read_page_fn fn, void *ctx, Walk &w, uint32_t t, uint32_t first, std::unordered_set<uint32_t> &walked, Sink &&sink,
+                     int &sink_rc) {
+    uint64_t tuples = 0;
+    w.pre[t].push_back(0);
+    for (uint32_t cur = first; cur != NONE;) {
+        if (!walked.insert(cur).second) return w.fail("page linked twice", cur);
+        const uint8_t *page = fn(ctx, cur);
+        if (!page) return w.fail("page cannot be read", cur);
+        const int n = page_tuples(page);
+        if (n < 0) return w.fail("page header out of range", cur);
+        if (host_rd16(page + 16) != BLCKSZ - 8) return w.fail("special area is not Opaque", cur);
+        tuples += (uint32_t)n;
+        if (tuples > 0xfffffff0ull || w.pid[t].size() >= 0xfffffff0ull) return w.fail("more than 2^32 tuples on a tape", cur);
+        if ((sink_rc = sink(t, (uint32_t)w.pid[t].size(), page)) != 0) return false;
+        w.pid[t].push_back(cur);
+        w.pre[t].push_back((uint32_t)tuples);
+        cur = host_rd32(page + BLCKSZ - 8);
+    }
+    return true;
+}
+
+// false: refused (w.what / w.bad_page), or the sink's status in `sink_rc`
+template <class Sink>
+bool walk_relation(vbm25_read_page_fn fn, void *ctx, Walk &w, Sink &&sink, int &sink_rc) {
+    sink_rc = 0;
+    const uint8_t *j = read_meta_jump(fn, ctx, w);
+    if (!j) return false;
     const uint32_t first[N_TAPES] = {host_rd32(j + 44), host_rd32(j + 48), host_rd32(j + 52), host_rd32(j + 56)};
     std::unordered_set<uint32_t> walked;
-    for (uint32_t t = 0; t < N_TAPES; ++t) {
-        uint64_t tuples = 0;
-        w.pre[t].push_back(0);
-        for (uint32_t cur = first[t]; cur != NONE;) {
-            if (!walked.insert(cur).second) return w.fail("page linked twice", cur);
-            const uint8_t *page = fn(ctx, cur);
-            if (!page) return w.fail("page cannot be read", cur);
-            const int n = page_tuples(page);
-            if (n < 0) return w.fail("page header out of range", cur);
-            if (host_rd16(page + 16) != BLCKSZ - 8) return w.fail("special area is not Opaque", cur);
-            tuples += (uint32_t)n;
-            if (tuples > 0xfffffff0ull || w.pid[t].size() >= 0xfffffff0ull) return w.fail("more than 2^32 tuples on a tape", cur);
-            if ((sink_rc = sink(t, (uint32_t)w.pid[t].size(), page)) != 0) return false;
-            w.pid[t].push_back(cur);
-            w.pre[t].push_back((uint32_t)tuples);
-            cur = host_rd32(page + BLCKSZ - 8);
-        }
-    }
+    for (uint32_t t = 0; t < N_TAPES; ++t)
+        if (!walk_tape_pages(fn, ctx, w, t, first[t], walked, sink, sink_rc)) return false;
     // the counts the host reader compares while it flattens
     if (w.pre[T_DOCS].back() != w.n_docs) return w.fail("document count differs from the Jump tuple", first[T_DOCS]);
     if (w.pre[T_TOKENS].back() == 0 && w.pre[T_SUMMARIES].back() != 0)

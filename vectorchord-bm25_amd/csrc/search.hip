@@ -2185,14 +2185,16 @@ static int growing_desc_check(const vbm25_index *ix, const vbm25_growing_desc *d
     return VBM25_OK;
 }
 
-static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
-    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!ix || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    const uint32_t n = d->n_docs;
-    uint64_t e_first = 0, n_el = 0;
-    if (int rc = growing_desc_check(ix, d, 0, 0, &e_first, &n_el)) return rc;
-    if (int rc = use_device(ix->device)) return rc;
+static void swap_buffers(DeviceBuffer &a, DeviceBuffer &b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+}
+
+// vbm25_growing_upload, device half: the CSR in HBM on the index's device -> the segment.  `start` may begin anywhere (the kernels
+// take it relative to start[0]); `payload`: the buffer of a.payload when the segment may keep it, NULL: the segment takes a copy.
+static int growing_build(vbm25_index *ix, const GrowingDeviceArrays &a, DeviceBuffer *payload, vbm25_device_growing **out) {
+    const uint32_t n = a.n_docs;
+    const uint64_t n_el = a.n_elements;
     auto gs = std::make_unique<vbm25_device_growing>();
     gs->index = ix;
     gs->device = ix->device;
@@ -2200,22 +2202,25 @@ static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *
     gs->n_grow = n;
     gs->n_tiles = uint32_t((uint64_t(n) + GT - 1) / GT);
     const uint32_t nt = ix->n_terms;
-    DeviceBuffer tkey, start, key, tf, fn, del, keys, vals, keys2, vals2, cnt, tmp;
+    DeviceBuffer tkey, keys, vals, keys2, vals2, cnt, tmp;
     int rc = 0;
-    if ((rc = tkey.upload(ix->term_key.data(), 16ull * nt)) || (rc = start.upload(d->start, 8ull * (n + 1ull))) ||
-        (rc = key.upload(d->key ? d->key + 16ull * e_first : nullptr, 16ull * n_el)) ||
-        (rc = tf.upload(d->tf ? d->tf + e_first : nullptr, 4ull * n_el)) || (rc = fn.upload(d->fieldnorm, n)) ||
-        (d->deleted && (rc = del.upload(d->deleted, n))) || (rc = gs->payload.upload(d->payload, 6ull * n)) ||
-        (rc = keys.alloc(8ull * n_el)) || (rc = vals.alloc(4ull * n_el)) || (rc = keys2.alloc(8ull * n_el)) ||
-        (rc = vals2.alloc(4ull * n_el)) || (rc = cnt.alloc(4)) || (rc = gs->term_start.alloc(4ull * (nt + 1ull))))
+    if (payload) {
+        swap_buffers(gs->payload, *payload);
+    } else {
+        if ((rc = gs->payload.alloc(6ull * n))) return rc;
+        if (n) HIP_TRY(hipMemcpy(gs->payload.p, a.payload, 6ull * n, hipMemcpyDeviceToDevice));
+    }
+    if ((rc = tkey.upload(ix->term_key.data(), 16ull * nt)) || (rc = keys.alloc(8ull * n_el)) || (rc = vals.alloc(4ull * n_el)) ||
+        (rc = keys2.alloc(8ull * n_el)) || (rc = vals2.alloc(4ull * n_el)) || (rc = cnt.alloc(4)) ||
+        (rc = gs->term_start.alloc(4ull * (nt + 1ull))))
         return rc;
     HIP_TRY(hipMemset(cnt.p, 0, 4));
     HIP_TRY(hipMemset(gs->term_start.p, 0, 4ull * (nt + 1ull)));
     uint32_t n_post = 0;
     if (n_el) {
-        if (n) grow_map_kernel<<<(n + 255) / 256, 256>>>(tkey.as<ulonglong2>(), nt, n, start.as<uint64_t>(), key.as<ulonglong2>(),
-                                                         tf.as<uint32_t>(), d->deleted ? del.as<uint8_t>() : nullptr,
-                                                         keys.as<unsigned long long>(), vals.as<uint32_t>(), cnt.as<uint32_t>());
+        if (n) grow_map_kernel<<<(n + 255) / 256, 256>>>(tkey.as<ulonglong2>(), nt, n, a.start, reinterpret_cast<const ulonglong2 *>(a.key),
+                                                         a.tf, a.deleted, keys.as<unsigned long long>(), vals.as<uint32_t>(),
+                                                         cnt.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         // (term id, g) ascending: a stable order of the postings by term with g ascending inside a term (flush.hip's sort of the mappings)
         size_t tb = 0;
@@ -2230,7 +2235,7 @@ static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *
     if ((rc = gs->post_g.alloc(4ull * n_post)) || (rc = gs->post_c.alloc(8ull * n_post))) return rc;
     if (n_post)
         grow_post_kernel<<<(n_post + 255) / 256, 256>>>(keys2.as<unsigned long long>(), vals2.as<uint32_t>(), n_post, nt,
-                                                         ix->term_s0.as<double>(), ix->s1.as<double>(), fn.as<uint8_t>(),
+                                                         ix->term_s0.as<double>(), ix->s1.as<double>(), a.fieldnorm,
                                                          gs->post_g.as<uint32_t>(), gs->post_c.as<double>(), gs->term_start.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     gs->term_start_host.resize(nt + 1ull);
@@ -2254,15 +2259,44 @@ static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *
     return VBM25_OK;
 }
 
+// vbm25_growing_upload, host half: the checked CSR of the caller goes up
+static int vbm25_growing_upload_impl(vbm25_index *ix, const vbm25_growing_desc *d, vbm25_device_growing **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ix || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const uint32_t n = d->n_docs;
+    uint64_t e_first = 0, n_el = 0;
+    if (int rc = growing_desc_check(ix, d, 0, 0, &e_first, &n_el)) return rc;
+    if (int rc = use_device(ix->device)) return rc;
+    DeviceBuffer start, key, tf, fn, del, payload;
+    int rc = 0;
+    if ((rc = start.upload(d->start, 8ull * (n + 1ull))) || (rc = key.upload(d->key ? d->key + 16ull * e_first : nullptr, 16ull * n_el)) ||
+        (rc = tf.upload(d->tf ? d->tf + e_first : nullptr, 4ull * n_el)) || (rc = fn.upload(d->fieldnorm, n)) ||
+        (d->deleted && (rc = del.upload(d->deleted, n))) || (rc = payload.upload(d->payload, 6ull * n)))
+        return rc;
+    const GrowingDeviceArrays a{n, n_el, start.as<uint64_t>(), key.as<uint8_t>(), tf.as<uint32_t>(), fn.as<uint8_t>(),
+                                d->deleted ? del.as<uint8_t>() : nullptr, payload.as<uint16_t>()};
+    return growing_build(ix, a, &payload, out);
+}
+
+// vbm25_device_growing_from_pages (pages_device.hip) reads the vectors tape into a CSR on the index's device and builds from there
+namespace vbm25 {
+int index_device_and_docs(const vbm25_index *ix, int *device, uint32_t *n_docs) {
+    *device = ix->device;
+    *n_docs = ix->n_docs;
+    return VBM25_OK;
+}
+int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vbm25_device_growing **out) {
+    if (int rc = use_device(ix->device)) return rc;
+    return growing_build(ix, a, nullptr, out);
+}
+}  // namespace vbm25
+
 // ---------------------------------------------------------------------------
 // vbm25_device_growing_append / vbm25_device_growing_delete (growing_append.h).  Both wait for the device first (a run in flight ends
 // on the old arrays) and return when the segment is the new one.  An append validates, allocates and computes into the spare arrays
 // and the stage, none of which a search reads, and only then swaps them in: a failure at any point leaves the segment as it was.
 // ---------------------------------------------------------------------------
-static void swap_buffers(DeviceBuffer &a, DeviceBuffer &b) {
-    std::swap(a.p, b.p);
-    std::swap(a.bytes, b.bytes);
-}
 
 // room for `need` bytes in a buffer nobody reads (a spare, the stage); the contents are not kept.  A buffer that is too small is
 // replaced by one half as large again as needed: sizes grow geometrically, a run of small appends allocates (and hipFree

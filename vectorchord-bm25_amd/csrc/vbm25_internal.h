@@ -63,8 +63,33 @@ struct Segment {
     void desc(vbm25_index_desc *d) const;
 };
 
+// The growing segment's CSR in HBM on the index's device (vbm25_growing_desc's arrays, start[0] == 0): what the device reader of the
+// vectors tape (pages_device.hip) hands to the builder of the device growing segment (search.hip)
+struct GrowingDeviceArrays {
+    uint32_t n_docs;
+    uint64_t n_elements;
+    const uint64_t *start;
+    const uint8_t *key;
+    const uint32_t *tf;
+    const uint8_t *fieldnorm, *deleted;
+    const uint16_t *payload;
+};
+int index_device_and_docs(const vbm25_index *ix, int *device, uint32_t *n_docs);
+// the device half of vbm25_growing_upload; synchronous, the arrays may be freed when it returns
+int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vbm25_device_growing **out);
+
 }  // namespace vbm25
 
 struct vbm25_segment : vbm25::Segment {};
+
+// Host copy of the growing segment's CSR (vbm25_growing_from_pages; vbm25_device_growing_from_pages' `csr`)
+struct vbm25_growing {
+    std::vector<uint64_t> start{0};
+    std::vector<uint8_t> key;
+    std::vector<uint32_t> tf;
+    std::vector<uint8_t> fieldnorm;
+    std::vector<uint16_t> payload;
+    std::vector<uint8_t> deleted;
+};
 
 #endif
