@@ -538,6 +538,44 @@ void vbm25_device_segment_free(vbm25_device_segment *);
  *   refusal *out is NULL, the HBM and pinned memory of the call is released and the device is as usable as before.
  *   An empty sealed segment (n_docs == 0) is valid: its index returns nothing.  Synchronous; one host thread. */
 int vbm25_device_segment_from_pages(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_device_segment **out);
+
+/* The device writer, the inverse of the device reader: a device segment goes out as the 8192-byte page images flush.rs:40-158
+ * writes (tuple layouts: tuples.rs; page layout: PageInit with the 8-byte special area {next, flags = 0}, 4-byte line pointers,
+ * tuples MAXALIGNed downwards, every other byte zero).  Kernels compute where every tuple goes and fill the images
+ * (csrc/pages_write.hip, csrc/pages_emit.h); the host moves finished images through pinned staging to write_page, 1024 at a time,
+ * and assembles the two small address trees.  write_page is called once per page from the calling thread; `image` is valid only
+ * during the call; a non-zero return stops the write.
+ *   vbm25_device_segment_page_count  the pages flush() allocates for the segment: the documents, tokens, summaries and blocks tapes
+ *                                    and both address tapes
+ *   vbm25_device_segment_write_pages flush() with its i-th page allocation getting page_ids[i] (page_ids == NULL: first_page + i).
+ *                                    Allocation order: the documents tape's first page and its overflow pages; the first pages of
+ *                                    the tokens, summaries and blocks tapes; the overflow pages of those three in the order the
+ *                                    pushes meet them (per term and block: the block, then its summary; after the term's last
+ *                                    block: its token); address_documents (one page at create, one after every tuple: its head ends
+ *                                    empty and is free_documents); address_tokens likewise.  *out: what maintain.rs:282-296 /
+ *                                    build.rs:49-66 put into the Jump tuple
+ *   vbm25_device_segment_write_relation  build.rs:22-71: a whole fresh relation -- the Meta page 0 (k1 and b of the segment, seed32 or
+ *                                    zeros), the flush into pages 1 .., the empty vectors tape, the Jump page, the lock page;
+ *                                    *n_pages (may be NULL): pages written
+ *   VBM25_ERR_INVALID: a NULL segment, callback or output; n_page_ids different from the page count (page_ids != NULL); an id equal
+ *   to 0xFFFFFFFF or repeated; first_page + count beyond 2^32 - 1; a callback that returned non-zero (the message names the page).
+ *   VBM25_ERR_DEVICE without a gfx950 device: no host fallback.  After any refusal the segment and the device are as usable as
+ *   before.  On success every page id was handed to the callback exactly once.  Synchronous; calls on different threads are
+ *   independent. */
+typedef int (*vbm25_write_page_fn)(void *ctx, uint32_t page_id, const uint8_t *image);
+typedef struct vbm25_flushed {
+    uint32_t number_of_documents, _pad;
+    uint64_t sum_of_document_lengths;
+    uint16_t width_1_documents, width_0_documents;
+    uint32_t depth_documents, start_documents, free_documents;
+    uint32_t depth_tokens, start_tokens, free_tokens;
+    uint32_t ptr_documents, ptr_tokens, ptr_summaries, ptr_blocks;
+} vbm25_flushed;
+int vbm25_device_segment_page_count(const vbm25_device_segment *, uint32_t *n_pages);
+int vbm25_device_segment_write_pages(const vbm25_device_segment *, const uint32_t *page_ids, uint32_t n_page_ids, uint32_t first_page,
+                                     vbm25_write_page_fn write_page, void *ctx, vbm25_flushed *out);
+int vbm25_device_segment_write_relation(const vbm25_device_segment *, const uint8_t *seed32, vbm25_write_page_fn write_page, void *ctx,
+                                        uint32_t *n_pages);
 /* The index of a device segment, on the segment's device; the segment is left as it was. */
 int vbm25_index_create_from_device(const vbm25_device_segment *, vbm25_index **out);
 

@@ -268,6 +268,24 @@ class DeviceSegment {
         check(vbm25_device_segment_download(h_, &s));
         return Segment(s);
     }
+    // The device writer (the inverse of from_pages): the pages a flush of the segment allocates; the flush with the i-th allocation
+    // getting page_ids[i] (empty: first_page + i), one write_page call per finished image; a whole fresh relation (build.rs:22-71).
+    uint32_t page_count() const {
+        uint32_t n = 0;
+        check(vbm25_device_segment_page_count(h_, &n));
+        return n;
+    }
+    vbm25_flushed write_pages(vbm25_write_page_fn write_page, void *ctx, const std::vector<uint32_t> &page_ids = {}, uint32_t first_page = 0) const {
+        vbm25_flushed f;
+        check(vbm25_device_segment_write_pages(h_, page_ids.empty() ? nullptr : page_ids.data(), (uint32_t)page_ids.size(), first_page, write_page,
+                                               ctx, &f));
+        return f;
+    }
+    uint32_t write_relation(vbm25_write_page_fn write_page, void *ctx, const uint8_t *seed32 = nullptr) const {
+        uint32_t n = 0;
+        check(vbm25_device_segment_write_relation(h_, seed32, write_page, ctx, &n));
+        return n;
+    }
     const vbm25_device_segment *handle() const { return h_; }
 
   private:

@@ -37,6 +37,17 @@ class SynthParams(C.Structure):
     ]
 
 
+class Flushed(C.Structure):
+    """vbm25_flushed: what a flush leaves for the Jump tuple"""
+    _fields_ = [
+        ("number_of_documents", C.c_uint32), ("_pad", C.c_uint32), ("sum_of_document_lengths", C.c_uint64),
+        ("width_1_documents", C.c_uint16), ("width_0_documents", C.c_uint16),
+        ("depth_documents", C.c_uint32), ("start_documents", C.c_uint32), ("free_documents", C.c_uint32),
+        ("depth_tokens", C.c_uint32), ("start_tokens", C.c_uint32), ("free_tokens", C.c_uint32),
+        ("ptr_documents", C.c_uint32), ("ptr_tokens", C.c_uint32), ("ptr_summaries", C.c_uint32), ("ptr_blocks", C.c_uint32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/vbm25.h declares
 vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 ABI = {
@@ -107,6 +118,9 @@ ABI = {
     "vbm25_device_segment_info": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_device_segment_free": (None, [vp]),
     "vbm25_device_segment_from_pages": (i32, [vp, vp, i32, vp]),
+    "vbm25_device_segment_page_count": (i32, [vp, vp]),
+    "vbm25_device_segment_write_pages": (i32, [vp, vp, u32, u32, vp, vp, vp]),
+    "vbm25_device_segment_write_relation": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_index_create_from_device": (i32, [vp, vp]),
     "vbm25_index_maintain": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_filter_remap": (i32, [vp, vp, u32, vp, vp, vp]),

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import IndexDesc, SynthParams, Vbm25Error, check, lib
+from ._lib import Flushed, IndexDesc, SynthParams, Vbm25Error, check, lib
 
 HIT_DTYPE = np.dtype({"names": ["score", "doc_id", "payload"],
                       "formats": ["<f8", "<u4", ("<u2", (3,))],
@@ -277,6 +277,53 @@ class DeviceSegment:
         out = C.c_void_p()
         check(lib().vbm25_device_segment_download(self.h, C.byref(out)))
         return Segment(out)
+
+    def page_count(self):
+        """vbm25_device_segment_page_count: the pages a flush of this segment allocates (four tapes and both address tapes)."""
+        n = C.c_uint32()
+        check(lib().vbm25_device_segment_page_count(self.h, C.byref(n)))
+        return n.value
+
+    def write_pages(self, page_ids=None, first_page=0, write_page=None):
+        """vbm25_device_segment_write_pages: the segment as the reference's page images, laid out and filled on the device.  The
+        i-th page allocation of flush.rs gets page_ids[i] (None: first_page + i).  Returns (dict page id -> np.uint8[8192], dict of
+        vbm25_flushed's fields: what goes into the Jump tuple).  write_page(page_id, address): called instead of collecting the
+        pages (the image is valid during the call only; a non-zero return stops the write); the dict then stays empty."""
+        pages = {}
+        if write_page is None:
+            def cb(ctx, page_id, image):
+                pages[page_id] = np.frombuffer(C.string_at(image, 8192), dtype=np.uint8).copy()
+                return 0
+        else:
+            def cb(ctx, page_id, image):
+                return int(write_page(page_id, image) or 0)
+        fn = WRITE_PAGE_FN(cb)
+        ids, n_ids = None, 0
+        if page_ids is not None:
+            ids = np.ascontiguousarray(page_ids, dtype=np.uint32)
+            n_ids = len(ids)
+        f = Flushed()
+        check(lib().vbm25_device_segment_write_pages(self.h, _p(ids), n_ids, first_page, C.cast(fn, C.c_void_p), None, C.byref(f)))
+        return pages, {name: getattr(f, name) for name, _ in Flushed._fields_ if name != "_pad"}
+
+    def to_relation(self, seed=None):
+        """vbm25_device_segment_write_relation: a whole fresh relation of this segment as build.rs:22-71 writes it (Meta page 0 with
+        the segment's k1 and b and `seed` -- 32 bytes, None: zeros --, the flush, the empty vectors tape, Jump, lock): the list of
+        its page images, indexable by page id, as segment_from_pages and DeviceSegment.from_pages take it."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("the seed is 32 bytes")
+        pages = {}
+
+        def cb(ctx, page_id, image):
+            pages[page_id] = np.frombuffer(C.string_at(image, 8192), dtype=np.uint8).copy()
+            return 0
+        fn = WRITE_PAGE_FN(cb)
+        seed_buf = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+        n = C.c_uint32()
+        check(lib().vbm25_device_segment_write_relation(self.h, seed_buf, C.cast(fn, C.c_void_p), None, C.byref(n)))
+        if sorted(pages) != list(range(n.value)):
+            raise Vbm25Error(-1, f"{len(pages)} distinct pages delivered for a relation of {n.value}")
+        return [pages[i] for i in range(n.value)]
 
     def token_terms(self, tokens):
         tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
@@ -1055,6 +1102,7 @@ def merge_hits(sealed, grow, k):
 
 
 READ_PAGE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint32)
+WRITE_PAGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p)
 
 
 class GrowingDesc(C.Structure):
