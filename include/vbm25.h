@@ -228,7 +228,8 @@ int vbm25_growing_from_pages(vbm25_read_page_fn read_page, void *ctx, vbm25_grow
  * ceil(n_docs / 64) words are cleared: DELETED polarity, the form vbm25_index_maintain and vbm25_filter_remap take.
  * *n_docs receives the relation's document count, *n_deleted (may be NULL) the number of flags set.  words == NULL only counts
  * (n_words is not looked at), so the caller can size the buffer; n_words < ceil(n_docs / 64) -> VBM25_ERR_INVALID and nothing
- * written.  NULL read_page or n_docs -> VBM25_ERR_INVALID.  Host only: both consumers take host words. */
+ * written.  NULL read_page or n_docs -> VBM25_ERR_INVALID.  Host only; vbm25_device_vacuum_from_pages (below) reads the same
+ * words on the device, for the consumers that take them there. */
 int vbm25_sealed_deleted_from_pages(vbm25_read_page_fn read_page, void *ctx, uint64_t *words, uint32_t n_words, uint32_t *n_docs,
                                     uint32_t *n_deleted);
 /* Cache key of the HBM copy of a relation's sealed segment: 32 bytes hashed (BLAKE3) over the Meta and Jump
@@ -633,6 +634,46 @@ int vbm25_index_maintain(const vbm25_index *index, const uint64_t *sealed_delete
 int vbm25_filter_remap(const vbm25_filter *old, const uint64_t *sealed_deleted, uint32_t n_grow, const uint8_t *growing_deleted,
                        vbm25_index *new_index, vbm25_filter **out);
 int vbm25_filter_read(const vbm25_filter *, uint32_t i, int growing, uint64_t *words);
+
+/* VACUUM's inputs read on the device.  A vbm25_device_vacuum holds a relation's compaction inputs in HBM on the index's device: the
+ * sealed documents' deleted flags as ceil(n_docs / 64) words in DELETED polarity (what vbm25_sealed_deleted_from_pages gives, bits at
+ * or beyond n_docs zero) and the growing segment's CSR (what vbm25_growing_from_pages gives: the six arrays of vbm25_growing_desc,
+ * keys the sealed vocabulary lacks included).  It is only ever read: one handle serves any number of compactions and remaps.
+ *   vbm25_device_vacuum_from_pages   index: the resident index of the relation's sealed segment (its device, its document count).
+ *     The host reads Meta and Jump once and follows the documents tape, then the vectors tape, by Opaque.next: one header check and
+ *     one copy into pinned staging per page, uploaded in chunks while the walk goes on; read_page is called once per page, from the
+ *     calling thread, and no tuple is touched on the host.  Kernels read byte 0 of every DocumentTuple (!= 0: deleted) into the words
+ *     and build the CSR as vbm25_device_growing_from_pages does (no vbm25_device_growing is made).  Refusals, in this order:
+ *       1. what vbm25_sealed_deleted_from_pages refuses on this relation, with its code and its message ("data corruption: ... (page
+ *          N)"): with several damages the first in tape order, a refusal of the page walk after the tuples in front of it;
+ *       2. what vbm25_device_growing_from_pages refuses, in its documented order and with its codes;
+ *       3. a Jump document count different from the index's -> VBM25_ERR_INVALID (the index of another relation).
+ *     NULL index, read_page or out -> VBM25_ERR_INVALID; no HIP device -> VBM25_ERR_DEVICE (no host fallback).  On any failure *out
+ *     is NULL, nothing stays allocated, and the index and the device are as usable as before.  Synchronous, on a stream of its own.
+ *   vbm25_device_vacuum_info   the counts (any pointer may be NULL): sealed documents and how many are deleted, growing documents
+ *     and how many are deleted, the CSR's elements.  No device work.
+ *   vbm25_device_vacuum_read   the two deletion inputs copied back (checkpoints, tests): ceil(n_sealed / 64) words and n_grow bytes;
+ *     either pointer may be NULL.  The CSR itself comes back through vbm25_device_growing_from_pages(..., csr).
+ *   vbm25_device_vacuum_free   NULL is a no-op.
+ *   vbm25_index_maintain_device   vbm25_index_maintain(index, words, desc, relabel, out) with words and desc taken from the handle:
+ *     the same segment and relabel, byte for byte, and the same refusals (tf 0 -> VBM25_ERR_INVALID "growing document %u: tf 0"
+ *     naming the first such document: the reader accepts tf 0, the compaction does not; more than 2^32 - 1 documents; more than 2^32
+ *     tokens); the empty result is the empty segment.  The kernels read the handle's planes in place: nothing proportional to the
+ *     documents or the elements crosses the host link (the index's term keys go up; the new vocabulary's keys, starts and block
+ *     boundaries, O(terms), come down and go up as in vbm25_index_maintain; relabel when asked for).  A handle of another document
+ *     count or on another device -> VBM25_ERR_INVALID.
+ *   vbm25_filter_remap_device   vbm25_filter_remap(old, words, n_grow, growing_deleted, new_index, out) with the three deletion
+ *     arguments taken from the handle: same words, codes and failure behaviour; no array crosses the host link (two counts come down).
+ * The VACUUM loop is then: vbm25_device_vacuum_from_pages, vbm25_index_maintain_device, vbm25_device_segment_write_pages,
+ * vbm25_index_create_from_device, vbm25_filter_remap_device. */
+typedef struct vbm25_device_vacuum vbm25_device_vacuum;
+int vbm25_device_vacuum_from_pages(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_vacuum **out);
+int vbm25_device_vacuum_info(const vbm25_device_vacuum *, uint32_t *n_sealed, uint32_t *n_sealed_deleted, uint32_t *n_grow,
+                             uint32_t *n_grow_deleted, uint64_t *n_elements);
+int vbm25_device_vacuum_read(const vbm25_device_vacuum *, uint64_t *sealed_deleted_words, uint8_t *growing_deleted);
+void vbm25_device_vacuum_free(vbm25_device_vacuum *);
+int vbm25_index_maintain_device(const vbm25_index *index, const vbm25_device_vacuum *in, uint32_t *relabel, vbm25_device_segment **out);
+int vbm25_filter_remap_device(const vbm25_filter *old, const vbm25_device_vacuum *in, vbm25_index *new_index, vbm25_filter **out);
 
 /* ------------------------------------------------------------------------
  * Several GPUs of one node: independent queries shard

@@ -10,6 +10,7 @@
 //   vbm25::search_growing, vbm25::merge_growing   crates/bm25/src/search.rs:83-135  (unsealed documents, host side)
 //   vbm25::Segment::from_pages, vbm25::growing_from_pages   the relation's pages -> flat arrays (tape.rs, tuples.rs)
 //   vbm25::DeviceGrowing::from_pages, vbm25::sealed_deleted_from_pages   the vectors tape read on the device; the sealed deleted flags
+//   vbm25::DeviceVacuum::from_pages, ::maintain, DocFilter::remap(index, vacuum)   VACUUM's inputs read and consumed on the device
 // Reference panics ("data corruption", "invalid data") and pgrx::error! become vbm25::Error.
 #ifndef VBM25_HPP
 #define VBM25_HPP
@@ -117,6 +118,7 @@ class Index {
 };
 
 class DeviceGrowing;
+class DeviceVacuum;
 
 // F document bitmaps of one index in HBM (vbm25_filter): bit d % 64 of word d / 64 of bitmap i set = document d may be returned.
 // Optionally F growing bitmaps for one uploaded growing segment (set_growing): bit g = growing document g may be returned.
@@ -147,6 +149,9 @@ class DocFilter {
                     const std::vector<uint8_t> &growing_deleted = {}) const {
         return remap(new_index.handle(), sealed_deleted, n_grow, growing_deleted);
     }
+    // ... with the three deletion arguments taken from the handle the compaction read (vbm25_filter_remap_device)
+    inline DocFilter remap(vbm25_index *new_index, const DeviceVacuum &in) const;
+    inline DocFilter remap(const Index &new_index, const DeviceVacuum &in) const;
     // bitmap i back on the host (vbm25_filter_read): n_words = words_per_bitmap(n_docs), or of the growing documents covered
     std::vector<uint64_t> read(uint32_t i, size_t n_words, bool growing = false) const {
         std::vector<uint64_t> w(n_words ? n_words : 1);
@@ -417,6 +422,54 @@ class DeviceGrowing {
     }
     vbm25_device_growing *h_ = nullptr;
 };
+
+// A relation's compaction inputs in HBM on the index's device (RAII over vbm25_device_vacuum): the sealed documents' deleted words and
+// the growing segment's CSR, read from the pages by kernels.  maintain() is vbm25_index_maintain_device: VACUUM's compaction with
+// these inputs read in place; DocFilter::remap(new_index, vacuum) carries the filters across.  The handle is only read.
+class DeviceVacuum {
+  public:
+    static DeviceVacuum from_pages(Index &index, vbm25_read_page_fn read_page, void *ctx) {
+        DeviceVacuum out;
+        check(vbm25_device_vacuum_from_pages(index.handle(), read_page, ctx, &out.h_));
+        check(vbm25_device_vacuum_info(out.h_, &out.n_sealed, &out.n_sealed_deleted, &out.n_grow, &out.n_grow_deleted, &out.n_elements));
+        return out;
+    }
+    DeviceVacuum(DeviceVacuum &&o) noexcept
+        : n_sealed(o.n_sealed), n_sealed_deleted(o.n_sealed_deleted), n_grow(o.n_grow), n_grow_deleted(o.n_grow_deleted),
+          n_elements(o.n_elements), h_(o.h_) {
+        o.h_ = nullptr;
+    }
+    DeviceVacuum(const DeviceVacuum &) = delete;
+    DeviceVacuum &operator=(const DeviceVacuum &) = delete;
+    ~DeviceVacuum() { vbm25_device_vacuum_free(h_); }
+    // the compacted segment; relabel, when given, receives n_sealed + n_grow entries: old id -> new id or UINT32_MAX
+    DeviceSegment maintain(const Index &index, std::vector<uint32_t> *relabel = nullptr) const {
+        if (relabel) relabel->assign(size_t(n_sealed) + n_grow, 0);
+        vbm25_device_segment *seg = nullptr;
+        check(vbm25_index_maintain_device(index.handle(), h_, relabel ? relabel->data() : nullptr, &seg));
+        return DeviceSegment(seg);
+    }
+    // the two deletion inputs back on the host (vbm25_device_vacuum_read)
+    void read(std::vector<uint64_t> &sealed_deleted_words, std::vector<uint8_t> &growing_deleted) const {
+        sealed_deleted_words.assign((size_t(n_sealed) + 63) / 64, 0);
+        growing_deleted.assign(n_grow, 0);
+        check(vbm25_device_vacuum_read(h_, sealed_deleted_words.data(), growing_deleted.data()));
+    }
+    const vbm25_device_vacuum *handle() const { return h_; }
+    uint32_t n_sealed = 0, n_sealed_deleted = 0, n_grow = 0, n_grow_deleted = 0;
+    uint64_t n_elements = 0;
+
+  private:
+    DeviceVacuum() = default;
+    vbm25_device_vacuum *h_ = nullptr;
+};
+
+inline DocFilter DocFilter::remap(vbm25_index *new_index, const DeviceVacuum &in) const {
+    vbm25_filter *h = nullptr;
+    check(vbm25_filter_remap_device(h_, in.handle(), new_index, &h));
+    return DocFilter(h);
+}
+inline DocFilter DocFilter::remap(const Index &new_index, const DeviceVacuum &in) const { return remap(new_index.handle(), in); }
 
 inline void DocFilter::set_growing(const DeviceGrowing *growing, const std::vector<uint64_t> &words) {
     check(vbm25_filter_set_growing(h_, growing ? growing->handle() : nullptr, words.empty() ? nullptr : words.data()));

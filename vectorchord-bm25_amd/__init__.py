@@ -7,6 +7,6 @@ used by the tests and bench.py; it never touches oracle/.
 """
 from ._lib import build, lib, library_path, Vbm25Error  # noqa: F401
 from .api import (  # noqa: F401
-    HIT_DTYPE, Segment, DeviceSegment, GpuIndex, Batch, Query, intern, search, search_batch, search_batch_filtered, search_batch_masked, DocFilter, NO_FILTER, GrowingSegment, search_batch_growing, search_batch_growing_masked, growing_search, merge_hits,
+    HIT_DTYPE, Segment, DeviceSegment, GpuIndex, Batch, Query, intern, search, search_batch, search_batch_filtered, search_batch_masked, DocFilter, NO_FILTER, GrowingSegment, DeviceVacuum, search_batch_growing, search_batch_growing_masked, growing_search, merge_hits,
     segment_from_pages, growing_from_pages, sealed_deleted_from_pages, evaluate, evaluate_batch, set_tuning, reset_tuning, MultiIndex, MultiBatch, Stream)
 from . import api, sharded  # noqa: F401,E402

@@ -125,6 +125,12 @@ ABI = {
     "vbm25_index_maintain": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_filter_remap": (i32, [vp, vp, u32, vp, vp, vp]),
     "vbm25_filter_read": (i32, [vp, u32, i32, vp]),
+    "vbm25_device_vacuum_from_pages": (i32, [vp, vp, vp, vp]),
+    "vbm25_device_vacuum_info": (i32, [vp, vp, vp, vp, vp, vp]),
+    "vbm25_device_vacuum_read": (i32, [vp, vp, vp]),
+    "vbm25_device_vacuum_free": (None, [vp]),
+    "vbm25_index_maintain_device": (i32, [vp, vp, vp, vp]),
+    "vbm25_filter_remap_device": (i32, [vp, vp, vp, vp]),
     "vbm25_multi_create": (i32, [vp, vp, i32, vp]),
     "vbm25_multi_create_from_device": (i32, [vp, vp, i32, vp]),
     "vbm25_multi_destroy": (None, [vp]),

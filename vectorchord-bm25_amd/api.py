@@ -273,6 +273,18 @@ class DeviceSegment:
         seg = cls(out)
         return (seg, relabel) if return_relabel else seg
 
+    @classmethod
+    def maintain_device(cls, index, vacuum, return_relabel=False):
+        """vbm25_index_maintain_device: maintain(index, words, csr) with the deletion words and the growing CSR taken from a
+        DeviceVacuum's planes in HBM -- the same segment and relabel byte for byte, nothing of the inputs but the index's term keys
+        crossing the host link.  The handle is only read: it serves remap_device and further compactions afterwards."""
+        relabel = np.zeros(index.n_docs + vacuum.n_grow, dtype=np.uint32) if return_relabel else None
+        out = C.c_void_p()
+        check(lib().vbm25_index_maintain_device(index.h, vacuum.h, relabel.ctypes.data_as(C.c_void_p) if relabel is not None else None,
+                                                C.byref(out)))
+        seg = cls(out)
+        return (seg, relabel) if return_relabel else seg
+
     def download(self):
         out = C.c_void_p()
         check(lib().vbm25_device_segment_download(self.h, C.byref(out)))
@@ -716,6 +728,16 @@ class DocFilter:
         f.n_bitmaps, f.words, f.h = self.n_bitmaps, (new_index.n_docs + 63) // 64, h
         return f
 
+    def remap_device(self, new_index, vacuum):
+        """vbm25_filter_remap_device: remap(new_index, words, growing_deleted) with the deletion inputs taken from the DeviceVacuum
+        that DeviceSegment.maintain_device compacted: the same words, no array crossing the host link."""
+        h = C.c_void_p()
+        check(lib().vbm25_filter_remap_device(self.h, vacuum.h, new_index.h, C.byref(h)))
+        f = DocFilter.__new__(DocFilter)
+        f.index, f.growing, f.grow_n = new_index, None, 0
+        f.n_bitmaps, f.words, f.h = self.n_bitmaps, (new_index.n_docs + 63) // 64, h
+        return f
+
     def __del__(self):
         try:
             if self.h:
@@ -823,6 +845,43 @@ class GrowingSegment:
         try:
             if self.h:
                 lib().vbm25_device_growing_free(self.h)
+        except Exception:
+            pass
+
+
+class DeviceVacuum:
+    """vbm25_device_vacuum: a relation's compaction inputs in HBM on the index's device -- the sealed documents' deleted flags as
+    words and the growing segment's CSR, read from the page images by kernels (from_pages).  DeviceSegment.maintain_device and
+    DocFilter.remap_device consume it in place.  n_sealed / n_sealed_deleted / n_grow / n_grow_deleted / n_elements: the counts."""
+
+    def __init__(self, index, handle):
+        self.index, self.h = index, handle
+        ns, nsd, ng, ngd, ne = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        check(lib().vbm25_device_vacuum_info(self.h, C.byref(ns), C.byref(nsd), C.byref(ng), C.byref(ngd), C.byref(ne)))
+        self.n_sealed, self.n_sealed_deleted, self.n_grow, self.n_grow_deleted = ns.value, nsd.value, ng.value, ngd.value
+        self.n_elements = ne.value
+
+    @classmethod
+    def from_pages(cls, index, pages):
+        """vbm25_device_vacuum_from_pages: `index` is the GpuIndex of the relation's sealed segment, `pages` as
+        DeviceSegment.from_pages takes it.  The host follows the documents tape and the vectors tape; no tuple is touched on it."""
+        cb, keep = _page_reader(pages)
+        h = C.c_void_p()
+        check(lib().vbm25_device_vacuum_from_pages(index.h, C.cast(cb, C.c_void_p), None, C.byref(h)))
+        return cls(index, h)
+
+    def read(self):
+        """vbm25_device_vacuum_read: (the sealed deleted words, uint64 x ceil(n_sealed / 64); the growing deleted flags, uint8 x n_grow)"""
+        n_words = (self.n_sealed + 63) // 64
+        words = np.zeros(max(1, n_words), dtype=np.uint64)   # (never a NULL pointer, also for zero words)
+        g_del = np.zeros(max(1, self.n_grow), dtype=np.uint8)
+        check(lib().vbm25_device_vacuum_read(self.h, words.ctypes.data_as(C.c_void_p), g_del.ctypes.data_as(C.c_void_p)))
+        return words[:n_words], g_del[:self.n_grow]
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().vbm25_device_vacuum_free(self.h)
         except Exception:
             pass
 

@@ -51,11 +51,24 @@ struct vbm25_device_segment {
         d_blk_wand_tf, d_blk_meta_doc, d_blk_meta_tf, d_blk_off8, d_blob, d_doc_fieldnorm, d_doc_payload;
 };
 
+// A relation's compaction inputs in HBM (vbm25_device_vacuum_from_pages, csrc/pages_device.hip): the sealed documents' deleted flags
+// as ceil(n_sealed / 64) words in DELETED polarity and the growing segment's CSR (vbm25_growing_desc's arrays, start[0] == 0, keys
+// strictly ascending inside a document).  Only ever read after it is made: vbm25_index_maintain_device and
+// vbm25_filter_remap_device take the planes in place.
+struct vbm25_device_vacuum {
+    int device = 0;
+    uint32_t n_sealed = 0, n_sealed_deleted = 0, n_grow = 0, n_grow_deleted = 0;
+    uint64_t n_elements = 0;
+    vbm25::HbmArray d_sealed_deleted, d_start, d_key, d_tf, d_fieldnorm, d_deleted, d_payload;
+};
+
 namespace vbm25 {
 
 // The encode of flush.hip, everything left in HBM.  Lengths on the host (doc_len) or the device (dev_len); payloads on the host
 // (doc_payload), the device (dev_payload) or neither (synthetic ctids); the mappings, sorted by (token, document), on the host
 // (post_doc / post_tf) or the device (dev_doc / dev_tf); term_key and term_start on the host.
+// The bytes the calling thread's last build_device_core copied over the host link: [0] host -> device, [1] device -> host
+void encode_link_bytes(double out2[2]);
 int build_device_core(int device, double k1, double b, uint32_t n_docs, const uint32_t *doc_len, const uint32_t *dev_len,
                       const uint16_t *doc_payload, const uint16_t *dev_payload, uint32_t n_terms, const uint8_t *term_key,
                       const uint64_t *term_start, const uint32_t *post_doc, const uint32_t *post_tf, const uint32_t *dev_doc,
@@ -73,15 +86,29 @@ struct MaintainSource {
     const uint8_t *blob;               // device
     const uint16_t *doc_payload;       // device, n_docs x 3
 };
-int maintain_device(const MaintainSource &src, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing, uint32_t *relabel,
-                    vbm25_device_segment **out);
+// The compaction's inputs: the host arrays vbm25_index_maintain takes (sealed_deleted, growing), or -- dev != NULL, the host ones are
+// then not looked at -- a handle whose planes the kernels read in place (vbm25_index_maintain_device)
+struct MaintainInput {
+    const uint64_t *sealed_deleted;
+    const vbm25_growing_desc *growing;
+    const vbm25_device_vacuum *dev;
+};
+int maintain_device(const MaintainSource &src, const MaintainInput &in, uint32_t *relabel, vbm25_device_segment **out);
 
 // vbm25_filter_remap's device half (csrc/maintain.hip: the relabel is the compaction's).  bits: the old filter's n_bitmaps x
 // ceil(n_docs / 64) sealed words; grow_bits: its growing words, bitmap i at word i grow_stride (not read when n_grow is 0); both on
 // `device`, as is out: n_bitmaps x ceil(new_n_docs / 64) words, written only when the kept sealed and the live growing documents
-// number new_n_docs (else VBM25_ERR_INVALID).  sealed_deleted / growing_deleted: host, as vbm25_index_maintain takes them.
-int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const uint64_t *sealed_deleted, const void *bits, uint32_t n_grow,
-                        const uint8_t *growing_deleted, const void *grow_bits, uint32_t grow_stride, uint32_t new_n_docs, void *out);
+// number new_n_docs (else VBM25_ERR_INVALID).  del: the remap's deletion inputs, see RemapDeletions.
+// The deletion inputs of the remap: the host arrays vbm25_filter_remap takes (sealed_deleted: NULL or ceil(n_docs / 64) words;
+// growing_deleted: NULL or n_grow bytes), or -- dev != NULL, the host ones are then not looked at -- a handle on the filter's device
+// whose words and bytes are read in place (vbm25_filter_remap_device; its n_sealed and n_grow are the caller's n_docs and n_grow)
+struct RemapDeletions {
+    const uint64_t *sealed_deleted;
+    const uint8_t *growing_deleted;
+    const vbm25_device_vacuum *dev;
+};
+int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const void *bits, uint32_t n_grow, const RemapDeletions &del,
+                        const void *grow_bits, uint32_t grow_stride, uint32_t new_n_docs, void *out);
 
 }  // namespace vbm25
 

@@ -307,7 +307,15 @@ __global__ void __launch_bounds__(256) synth_payload_kernel(uint32_t n_docs, uin
     }
 }
 
+// the bytes the calling thread's last build_device_core copied over the host link: host -> device, device -> host
+thread_local double g_encode_link[2];
+
 }  // namespace
+
+void vbm25::encode_link_bytes(double out2[2]) {
+    out2[0] = g_encode_link[0];
+    out2[1] = g_encode_link[1];
+}
 
 // The encode, everything left in HBM (vbm25_device_segment).  Inputs on the host, or already on the device: dev_len (document
 // lengths), dev_payload, dev_doc / dev_tf (the mappings, sorted by (token, document)); no payload at all: synthetic ctids.
@@ -329,6 +337,7 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the device builder has no CPU fallback (vbm25_segment_build is the host builder)");
     if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
     FL_TRY(hipSetDevice(device));
+    g_encode_link[0] = g_encode_link[1] = 0.0;
 
     auto ds = std::make_unique<vbm25_device_segment>();
     ds->device = device;
@@ -361,10 +370,14 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
     if (!dev_len) {
         FL_TRY(d_len.alloc(4ull * n_docs));
         FL_TRY(hipMemcpy(d_len.p, doc_len, 4ull * n_docs, hipMemcpyHostToDevice));
+        g_encode_link[0] += 4.0 * n_docs;
         dev_len = d_len.as<uint32_t>();
     }
     if (dev_payload) FL_TRY(hipMemcpy(ds->d_doc_payload.p, dev_payload, 6ull * n_docs, hipMemcpyDeviceToDevice));
-    else if (doc_payload) FL_TRY(hipMemcpy(ds->d_doc_payload.p, doc_payload, 6ull * n_docs, hipMemcpyHostToDevice));
+    else if (doc_payload) {
+        FL_TRY(hipMemcpy(ds->d_doc_payload.p, doc_payload, 6ull * n_docs, hipMemcpyHostToDevice));
+        g_encode_link[0] += 6.0 * n_docs;
+    }
     else synth_payload_kernel<<<1024, 256>>>(n_docs, ds->d_doc_payload.as<uint16_t>());
     FL_TRY(hipMemcpy(d_fnlen.p, fieldnorm_lengths(), 4 * 256, hipMemcpyHostToDevice));
     FL_TRY(hipMemset(d_sum.p, 0, 8));
@@ -373,6 +386,8 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
     FL_TRY(hipGetLastError());
     unsigned long long sum_len = 0;
     FL_TRY(hipMemcpy(&sum_len, d_sum.p, 8, hipMemcpyDeviceToHost));
+    g_encode_link[0] += 4 * 256;  // (the fieldnorm table above)
+    g_encode_link[1] += 8;
     ds->sum_len = sum_len;
     double denom[256];
     bm25_tables(n_docs, sum_len, k1, b, denom);
@@ -389,8 +404,10 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
     if (n_post && !dev_doc) {
         FL_TRY(hipMemcpy(d_pd.p, post_doc, 4ull * n_post, hipMemcpyHostToDevice));
         FL_TRY(hipMemcpy(d_pt.p, post_tf, 4ull * n_post, hipMemcpyHostToDevice));
+        g_encode_link[0] += 8.0 * n_post;
     }
     FL_TRY(hipMemcpy(d_denom.p, denom, 8 * 256, hipMemcpyHostToDevice));
+    g_encode_link[0] += 12.0 * (n_terms + 1.0) + 8 * 256;  // term_start, first blocks, the table
     FL_TRY(ds->d_blk_min.alloc(4ull * n_blocks));
     FL_TRY(ds->d_blk_max.alloc(4ull * n_blocks));
     FL_TRY(ds->d_blk_wand_tf.alloc(4ull * n_blocks));
@@ -448,6 +465,7 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
             FL_TRY(d_rt.alloc(rb));
             FL_TRY(hipcub::DeviceReduce::Sum(d_rt.p, rb, wide, d_sum.as<unsigned long long>(), (int)n_blocks));
             FL_TRY(hipMemcpy(&total8, d_sum.p, 8, hipMemcpyDeviceToHost));
+            g_encode_link[1] += 4 + 8;  // (the error flag above)
         }
         if (total8 > 0xffffffffull) return set_error(VBM25_ERR_UNSUPPORTED, "block bodies exceed 32 GiB");
         ds->blob_bytes = 8ull * total8;
@@ -463,6 +481,7 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
         FL_TRY(hipGetLastError());
         std::vector<uint32_t> bnd(size_t(n_terms) + 1);
         FL_TRY(hipMemcpy(bnd.data(), d_bnd.p, 4ull * (n_terms + 1), hipMemcpyDeviceToHost));
+        g_encode_link[1] += 4.0 * (n_terms + 1.0);
         for (uint32_t t = 0; t < n_terms; ++t)
             ds->term_bytes[t] = 8ull * (bnd[t + 1] - bnd[t]) + 40ull * (ds->term_first_block[t + 1] - ds->term_first_block[t]) + ds->term_df[t];
     } else {

@@ -62,6 +62,10 @@ struct WidenU32 {
 
 // phase times of the last call on this thread (tools/maintain_cost.py): relabel, count, vocabulary, scatter, encode
 thread_local double g_phase_ms[5];
+// every byte the call copied over the host link, the encode's copies included (tools/vacuum_device_cost.py): [0] host -> device
+// (deletion words, the growing arrays, the term keys; the new vocabulary's starts and first blocks), [1] device -> host (scalars,
+// the new vocabulary's keys, starts and block boundaries, the relabel table when asked for)
+thread_local double g_link_bytes[2];
 
 // ---------------------------------------------------------------------------
 // relabel
@@ -192,6 +196,19 @@ __device__ __forceinline__ uint32_t mt_lower_bound(const ull *hi, const ull *lo,
         if (mt_key_less(hi[m], lo[m], qh, ql)) a = m + 1; else b = m;
     }
     return a;
+}
+
+// tf 0 among the elements of a device CSR (Document::checked_new, vector.rs:56-64): the smallest document that holds one
+// One thread per element, no grid cap and no stride (fewer than 2^31 elements: at most 2^23 workgroups).
+__global__ void __launch_bounds__(256) mt_tf_zero_kernel(uint64_t n_el, uint32_t n_grow, const uint64_t *start, const uint32_t *tf, uint32_t *first) {
+    const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (e >= n_el || tf[e] != 0) return;
+    uint32_t lo = 0, hi = n_grow;  // start[lo] <= e < start[hi]: the last such lo is e's document (empty documents lie below it)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (start[mid] <= e) lo = mid; else hi = mid;
+    }
+    atomicMin(first, lo);
 }
 
 struct GrowArgs {
@@ -387,17 +404,24 @@ int empty_segment(const MaintainSource &s, std::unique_ptr<vbm25_device_segment>
 
 namespace vbm25 {
 
-int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing, uint32_t *relabel,
-                    vbm25_device_segment **out) {
+int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *relabel, vbm25_device_segment **out) {
     using clock = std::chrono::steady_clock;
     for (double &x : g_phase_ms) x = 0.0;
+    for (double &x : g_link_bytes) x = 0.0;
     const uint32_t N = s.n_docs, T = s.n_terms, B = s.n_blocks, W = (N + 63u) / 64u;
+    const vbm25_device_vacuum *dev = in.dev;
+    const uint64_t *sealed_deleted = dev ? nullptr : in.sealed_deleted;
+    const vbm25_growing_desc *growing = dev ? nullptr : in.growing;
     // arguments (all on the host, before the device is touched)
+    if (dev && dev->device != s.device)
+        return set_error(VBM25_ERR_INVALID, "the compaction inputs are on device %d, the index on device %d", dev->device, s.device);
+    if (dev && dev->n_sealed != N)
+        return set_error(VBM25_ERR_INVALID, "the compaction inputs are of %u sealed documents, the index holds %u", dev->n_sealed, N);
     if (sealed_deleted && (N & 63u) && (sealed_deleted[W - 1] >> (N & 63u)))
         return set_error(VBM25_ERR_INVALID, "sealed_deleted has bits at or beyond n_docs = %u", N);
-    const uint32_t G = growing ? growing->n_docs : 0u;
-    uint64_t e_first = 0, n_el = 0;
-    if (G) {
+    const uint32_t G = dev ? dev->n_grow : growing ? growing->n_docs : 0u;
+    uint64_t e_first = 0, n_el = dev ? dev->n_elements : 0;
+    if (G && !dev) {
         const vbm25_growing_desc *d = growing;
         if (!d->start || !d->payload) return set_error(VBM25_ERR_INVALID, "growing arrays missing");
         for (uint32_t g = 0; g < G; ++g)
@@ -420,6 +444,17 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return set_error(VBM25_ERR_DEVICE, "no HIP device: maintain has no CPU entry point");
     MT_TRY(hipSetDevice(s.device));
+    if (dev && n_el) {  // the host loop's tf check on the handle's planes (its keys were checked when the handle was made)
+        DBuf d_first;
+        uint32_t first = 0xffffffffu;
+        MT_TRY(d_first.alloc(4));
+        MT_TRY(hipMemset(d_first.p, 0xff, 4));
+        mt_tf_zero_kernel<<<(uint32_t)((n_el + 255) / 256), 256>>>(n_el, G, dev->d_start.as<uint64_t>(), dev->d_tf.as<uint32_t>(), d_first.as<uint32_t>());
+        MT_TRY(hipGetLastError());
+        MT_TRY(hipMemcpy(&first, d_first.p, 4, hipMemcpyDeviceToHost));
+        g_link_bytes[1] += 4;
+        if (first != 0xffffffffu) return set_error(VBM25_ERR_INVALID, "growing document %u: tf 0", first);
+    }
     auto t0 = clock::now();
     auto lap = [&](int phase) -> hipError_t {
         const hipError_t e = hipDeviceSynchronize();
@@ -436,15 +471,19 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     MT_TRY(d_base.alloc(4ull * (W + 1ull)));
     uint32_t K = 0;
     if (W) {
+        const ull *del_words = dev ? dev->d_sealed_deleted.as<ull>() : nullptr;  // (the handle's words: read in place)
         if (sealed_deleted) {
             MT_TRY(d_del.alloc(8ull * W));
             MT_TRY(hipMemcpy(d_del.p, sealed_deleted, 8ull * W, hipMemcpyHostToDevice));
+            g_link_bytes[0] += 8.0 * W;
+            del_words = d_del.as<ull>();
         }
         MT_TRY(hipMemset(d_cnt.as<uint32_t>() + W, 0, 4));
-        mt_keep_kernel<<<grid_of(W), 256>>>(W, N, sealed_deleted ? d_del.as<ull>() : nullptr, d_keep.as<ull>(), d_cnt.as<uint32_t>());
+        mt_keep_kernel<<<grid_of(W), 256>>>(W, N, del_words, d_keep.as<ull>(), d_cnt.as<uint32_t>());
         MT_TRY(hipGetLastError());
         MT_TRY(exclusive_sum(d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), W + 1, tmp));
         MT_TRY(hipMemcpy(&K, d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
+        g_link_bytes[1] += 4;
         d_del.release();
     }
     MT_TRY(lap(0));
@@ -486,6 +525,7 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     MT_TRY(d_slo.alloc(8ull * T));
     if (T) {
         MT_TRY(hipMemcpy(d_skey.p, s.term_key, 16ull * T, hipMemcpyHostToDevice));
+        g_link_bytes[0] += 16.0 * T;
         mt_key_split_kernel<<<grid_of(T), 256>>>(T, d_skey.as<ulonglong2>(), d_shi.as<ull>(), d_slo.as<ull>());
         MT_TRY(hipGetLastError());
     }
@@ -499,47 +539,70 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     MT_TRY(hipMemset(d_nunk.p, 0, 4));
     GrowArgs ga{};
     if (G) {
-        std::vector<uint64_t> start(size_t(G) + 1);
-        for (uint32_t g = 0; g <= G; ++g) start[g] = growing->start[g] - e_first;
-        MT_TRY(d_start.alloc(8ull * (G + 1ull)));
-        MT_TRY(hipMemcpy(d_start.p, start.data(), 8ull * (G + 1ull), hipMemcpyHostToDevice));
-        MT_TRY(d_gkey.alloc(16ull * n_el));
+        // the growing arrays: the handle's planes where they are (only read: nothing of the handle is freed or written), or the host
+        // arrays' copies in buffers of the call
+        const uint64_t *g_start = nullptr;
+        const ulonglong2 *g_key = nullptr;
+        const uint32_t *g_tf = nullptr;
+        const uint8_t *g_del = nullptr;
+        const uint16_t *g_pay = nullptr;
         MT_TRY(d_ghi.alloc(8ull * n_el));
         MT_TRY(d_glo.alloc(8ull * n_el));
-        MT_TRY(d_gtf.alloc(4ull * n_el));
-        MT_TRY(d_gpay.alloc(6ull * G));
         MT_TRY(d_live.alloc(4ull * (G + 1ull)));
         MT_TRY(d_live_el.alloc(4ull * (G + 1ull)));
+        if (dev) {
+            g_start = dev->d_start.as<uint64_t>();
+            g_key = dev->d_key.as<ulonglong2>();
+            g_tf = dev->d_tf.as<uint32_t>();
+            g_del = dev->d_deleted.as<uint8_t>();
+            g_pay = dev->d_payload.as<uint16_t>();
+        } else {
+            std::vector<uint64_t> start(size_t(G) + 1);
+            for (uint32_t g = 0; g <= G; ++g) start[g] = growing->start[g] - e_first;
+            MT_TRY(d_start.alloc(8ull * (G + 1ull)));
+            MT_TRY(hipMemcpy(d_start.p, start.data(), 8ull * (G + 1ull), hipMemcpyHostToDevice));
+            MT_TRY(d_gkey.alloc(16ull * n_el));
+            MT_TRY(d_gtf.alloc(4ull * n_el));
+            MT_TRY(d_gpay.alloc(6ull * G));
+            if (n_el) {
+                MT_TRY(hipMemcpy(d_gkey.p, growing->key + 16ull * e_first, 16ull * n_el, hipMemcpyHostToDevice));
+                MT_TRY(hipMemcpy(d_gtf.p, growing->tf + e_first, 4ull * n_el, hipMemcpyHostToDevice));
+            }
+            if (growing->deleted) {
+                MT_TRY(d_gdel.alloc(G));
+                MT_TRY(hipMemcpy(d_gdel.p, growing->deleted, G, hipMemcpyHostToDevice));
+                g_del = d_gdel.as<uint8_t>();
+            }
+            MT_TRY(hipMemcpy(d_gpay.p, growing->payload, 6ull * G, hipMemcpyHostToDevice));
+            g_link_bytes[0] += 8.0 * (G + 1.0) + 20.0 * n_el + 6.0 * G + (growing->deleted ? G : 0);
+            g_start = d_start.as<uint64_t>();
+            g_key = d_gkey.as<ulonglong2>();
+            g_tf = d_gtf.as<uint32_t>();
+            g_pay = d_gpay.as<uint16_t>();
+        }
         if (n_el) {
-            MT_TRY(hipMemcpy(d_gkey.p, growing->key + 16ull * e_first, 16ull * n_el, hipMemcpyHostToDevice));
-            MT_TRY(hipMemcpy(d_gtf.p, growing->tf + e_first, 4ull * n_el, hipMemcpyHostToDevice));
-            mt_key_split_kernel<<<grid_of(n_el), 256>>>(n_el, d_gkey.as<ulonglong2>(), d_ghi.as<ull>(), d_glo.as<ull>());
+            mt_key_split_kernel<<<grid_of(n_el), 256>>>(n_el, g_key, d_ghi.as<ull>(), d_glo.as<ull>());
             MT_TRY(hipGetLastError());
         }
-        d_gkey.release();
-        if (growing->deleted) {
-            MT_TRY(d_gdel.alloc(G));
-            MT_TRY(hipMemcpy(d_gdel.p, growing->deleted, G, hipMemcpyHostToDevice));
-        }
-        MT_TRY(hipMemcpy(d_gpay.p, growing->payload, 6ull * G, hipMemcpyHostToDevice));
+        d_gkey.release();  // (after the split on the null stream: hipFree waits for it)
         MT_TRY(hipMemset(d_live.as<uint32_t>() + G, 0, 4));
         MT_TRY(hipMemset(d_live_el.as<uint32_t>() + G, 0, 4));
-        mt_grow_live_kernel<<<grid_of(G), 256>>>(G, d_start.as<uint64_t>(), growing->deleted ? d_gdel.as<uint8_t>() : nullptr,
-                                                  d_live.as<uint32_t>(), d_live_el.as<uint32_t>());
+        mt_grow_live_kernel<<<grid_of(G), 256>>>(G, g_start, g_del, d_live.as<uint32_t>(), d_live_el.as<uint32_t>());
         MT_TRY(hipGetLastError());
         MT_TRY(exclusive_sum(d_live.as<uint32_t>(), d_gnew.as<uint32_t>(), G + 1, tmp));
         MT_TRY(exclusive_sum(d_live_el.as<uint32_t>(), d_gel.as<uint32_t>(), G + 1, tmp));
         MT_TRY(hipMemcpy(&Gk, d_gnew.as<uint32_t>() + G, 4, hipMemcpyDeviceToHost));
         MT_TRY(hipMemcpy(&n_gel, d_gel.as<uint32_t>() + G, 4, hipMemcpyDeviceToHost));
+        g_link_bytes[1] += 8;
         ga.n_grow = G;
         ga.n_terms = T;
         ga.n_sealed_kept = K;
-        ga.start = d_start.as<uint64_t>();
+        ga.start = g_start;
         ga.key_hi = d_ghi.as<ull>();
         ga.key_lo = d_glo.as<ull>();
-        ga.tf = d_gtf.as<uint32_t>();
-        ga.deleted = growing->deleted ? d_gdel.as<uint8_t>() : nullptr;
-        ga.payload = d_gpay.as<uint16_t>();
+        ga.tf = g_tf;
+        ga.deleted = g_del;
+        ga.payload = g_pay;
         ga.gnew = d_gnew.as<uint32_t>();
         ga.gel = d_gel.as<uint32_t>();
         ga.skey_hi = d_shi.as<ull>();
@@ -564,6 +627,7 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     }
     uint32_t n_unk = 0;
     MT_TRY(hipMemcpy(&n_unk, d_nunk.p, 4, hipMemcpyDeviceToHost));
+    g_link_bytes[1] += 4;
     DBuf d_nhi, d_nlo;
     if (n_unk) {  // sort the unknown elements by key: low halves, then (stable) high halves
         DBuf k1, k2, v2, fl, incl;
@@ -590,6 +654,7 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
         MT_TRY(tmp.alloc(tb));
         MT_TRY(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, fl.as<uint32_t>(), incl.as<uint32_t>(), (int)n_unk));
         MT_TRY(hipMemcpy(&U, incl.as<uint32_t>() + (n_unk - 1), 4, hipMemcpyDeviceToHost));
+        g_link_bytes[1] += 4;
         MT_TRY(d_nhi.alloc(8ull * U));
         MT_TRY(d_nlo.alloc(8ull * U));
         mt_unique_write_kernel<<<grid_of(n_unk), 256>>>(n_unk, T, d_unk.as<uint32_t>(), fl.as<uint32_t>(), incl.as<uint32_t>(), d_ghi.as<ull>(),
@@ -645,6 +710,7 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     uint64_t P = 0;
     MT_TRY(hipMemcpy(&F, d_fid.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost));
     MT_TRY(hipMemcpy(&P, d_ts_m.as<ull>() + M, 8, hipMemcpyDeviceToHost));
+    g_link_bytes[1] += 12;
     MT_TRY(d_key_f.alloc(16ull * F));
     MT_TRY(d_ts_f.alloc(8ull * (F + 1ull)));
     MT_TRY(d_sbase.alloc(8ull * T));
@@ -658,6 +724,7 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     std::vector<uint64_t> ts_f(size_t(F) + 1);
     if (F) MT_TRY(hipMemcpy(key_f.data(), d_key_f.p, 16ull * F, hipMemcpyDeviceToHost));
     MT_TRY(hipMemcpy(ts_f.data(), d_ts_f.p, 8ull * (F + 1ull), hipMemcpyDeviceToHost));
+    g_link_bytes[1] += 16.0 * F + 8.0 * (F + 1.0);
     for (DBuf *b : {&d_rank, &d_mkey, &d_skept, &d_total, &d_nz, &d_fid, &d_gscan, &d_key_f, &d_ts_f, &d_ghi, &d_glo, &d_shi, &d_slo, &d_ext,
                     &d_unk, &d_gtf})
         b->release();
@@ -696,7 +763,10 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
                                                         d_tf.as<uint32_t>());
         MT_TRY(hipGetLastError());
     }
-    if (relabel) MT_TRY(hipMemcpy(relabel, d_relabel.p, 4ull * (uint64_t(N) + G), hipMemcpyDeviceToHost));
+    if (relabel) {
+        MT_TRY(hipMemcpy(relabel, d_relabel.p, 4ull * (uint64_t(N) + G), hipMemcpyDeviceToHost));
+        g_link_bytes[1] += 4.0 * (double(N) + G);
+    }
     for (DBuf *b : {&d_keep, &d_cnt, &d_base, &d_kept_blk, &d_blk_base, &d_sbase, &d_gbase, &d_mkey_tf, &d_mtf, &d_relabel, &d_start, &d_gdel,
                     &d_gpay, &d_live, &d_live_el, &d_gnew, &d_gel, &tmp, &d_src, &d_gcnt, &d_ts_m})
         b->release();
@@ -707,6 +777,10 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
     if (int rc = build_device_core(s.device, s.k1, s.b, N2, nullptr, d_len.as<uint32_t>(), nullptr, d_pay.as<uint16_t>(), F, key_f.data(),
                                    ts_f.data(), nullptr, nullptr, d_doc.as<uint32_t>(), d_tf.as<uint32_t>(), ds))
         return rc;
+    double encode[2];
+    encode_link_bytes(encode);
+    g_link_bytes[0] += encode[0];
+    g_link_bytes[1] += encode[1];
     MT_TRY(lap(4));
     *out = ds.release();
     return VBM25_OK;
@@ -723,6 +797,15 @@ int maintain_device(const MaintainSource &s, const uint64_t *sealed_deleted, con
 // neighbouring input words (and between the last sealed and the first growing one): the output is zeroed first and written with
 // atomicOr, which commutes -- the result does not depend on the order.  A run of fully deleted words costs its threads one load each.
 namespace {
+// n bytes (nonzero = deleted) -> ceil(n / 64) words, bit g % 64 of word g / 64: one wave per word, a ballot of its 64 bytes
+__global__ void __launch_bounds__(256) mt_pack_deleted_kernel(uint32_t n, const uint8_t *deleted, ull *words) {
+    const uint32_t lane = threadIdx.x & 63u, w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (w >= (n + 63u) / 64u) return;  // (whole waves)
+    const uint64_t g = 64ull * w + lane;
+    const ull m = __ballot(g < n && deleted[g] != 0);
+    if (lane == 0) words[w] = m;
+}
+
 __global__ void __launch_bounds__(256) filter_remap_kernel(uint32_t n_in, uint32_t n_sealed_words, const ull *keep, const uint32_t *base,
                                                            const ull *bits, const ull *grow_bits, uint32_t grow_stride, uint32_t n_bitmaps,
                                                            ull *out, uint32_t out_words) {
@@ -763,14 +846,18 @@ __global__ void __launch_bounds__(256) filter_remap_kernel(uint32_t n_in, uint32
 }
 }  // namespace
 
-int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const uint64_t *sealed_deleted, const void *bits, uint32_t n_grow,
-                        const uint8_t *growing_deleted, const void *grow_bits, uint32_t grow_stride, uint32_t new_n_docs, void *out) {
+int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const void *bits, uint32_t n_grow, const RemapDeletions &in,
+                        const void *grow_bits, uint32_t grow_stride, uint32_t new_n_docs, void *out) {
+    const bool deletions_on_device = in.dev != nullptr;
+    const uint64_t *sealed_deleted = in.dev ? nullptr : in.sealed_deleted;
+    const uint8_t *growing_deleted = in.dev || !n_grow ? nullptr : in.growing_deleted;
     const uint32_t W = (n_docs + 63u) / 64u, GW = (n_grow + 63u) / 64u, OW = (new_n_docs + 63u) / 64u;
     const uint64_t TW = uint64_t(W) + GW;
-    // growing_deleted packed to the polarity and the form of sealed_deleted: both sides go through mt_keep_kernel
-    std::vector<ull> del(sealed_deleted || growing_deleted ? TW : 0, 0ull);
-    if (sealed_deleted) std::copy(sealed_deleted, sealed_deleted + W, del.begin());
-    if (growing_deleted)
+    // growing_deleted packed to the polarity and the form of sealed_deleted: both sides go through mt_keep_kernel.  Host inputs are
+    // packed here and go up as one run of words; device inputs stay where they are, the bytes packed by mt_pack_deleted_kernel
+    std::vector<ull> del(!deletions_on_device && (sealed_deleted || growing_deleted) ? TW : 0, 0ull);
+    if (!del.empty() && sealed_deleted) std::copy(sealed_deleted, sealed_deleted + W, del.begin());
+    if (!del.empty() && growing_deleted)
         for (uint32_t g = 0; g < n_grow; ++g)
             if (growing_deleted[g]) del[W + (g >> 6)] |= 1ull << (g & 63u);
     MT_TRY(hipSetDevice(device));
@@ -780,15 +867,24 @@ int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const u
         MT_TRY(d_keep.alloc(8ull * TW));
         MT_TRY(d_cnt.alloc(4ull * (TW + 1ull)));
         MT_TRY(d_base.alloc(4ull * (TW + 1ull)));
+        const ull *sealed_words = nullptr, *grow_words = nullptr;
         if (!del.empty()) {
             MT_TRY(d_del.alloc(8ull * TW));
             MT_TRY(hipMemcpy(d_del.p, del.data(), 8ull * TW, hipMemcpyHostToDevice));
+            if (sealed_deleted) sealed_words = d_del.as<ull>();
+            if (growing_deleted) grow_words = d_del.as<ull>() + W;
+        } else if (deletions_on_device) {
+            sealed_words = in.dev->d_sealed_deleted.as<ull>();
+            if (GW) {
+                MT_TRY(d_del.alloc(8ull * GW));
+                mt_pack_deleted_kernel<<<(GW + 3) / 4, 256>>>(n_grow, in.dev->d_deleted.as<uint8_t>(), d_del.as<ull>());
+                MT_TRY(hipGetLastError());
+                grow_words = d_del.as<ull>();
+            }
         }
         MT_TRY(hipMemset(d_cnt.as<uint32_t>() + TW, 0, 4));
-        if (W) mt_keep_kernel<<<grid_of(W), 256>>>(W, n_docs, sealed_deleted ? d_del.as<ull>() : nullptr, d_keep.as<ull>(), d_cnt.as<uint32_t>());
-        if (GW)
-            mt_keep_kernel<<<grid_of(GW), 256>>>(GW, n_grow, growing_deleted ? d_del.as<ull>() + W : nullptr, d_keep.as<ull>() + W,
-                                                  d_cnt.as<uint32_t>() + W);
+        if (W) mt_keep_kernel<<<grid_of(W), 256>>>(W, n_docs, sealed_words, d_keep.as<ull>(), d_cnt.as<uint32_t>());
+        if (GW) mt_keep_kernel<<<grid_of(GW), 256>>>(GW, n_grow, grow_words, d_keep.as<ull>() + W, d_cnt.as<uint32_t>() + W);
         MT_TRY(hipGetLastError());
         MT_TRY(exclusive_sum(d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), uint32_t(TW + 1ull), tmp));
         MT_TRY(hipMemcpy(&got[0], d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
@@ -809,6 +905,12 @@ int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const u
 }  // namespace vbm25
 
 // tools/maintain_cost.py: the phases of the calling thread's last vbm25_index_maintain (not part of include/vbm25.h)
+// ... and every byte it copied over the host link, the encode included: [0] host -> device, [1] device -> host
+extern "C" int vbm25_debug_maintain_link_bytes(double *out2) {
+    if (!out2) return VBM25_ERR_INVALID;
+    for (int i = 0; i < 2; ++i) out2[i] = g_link_bytes[i];
+    return VBM25_OK;
+}
 extern "C" int vbm25_debug_maintain_phases(double *ms5) {
     if (!ms5) return VBM25_ERR_INVALID;
     for (int i = 0; i < 5; ++i) ms5[i] = g_phase_ms[i];

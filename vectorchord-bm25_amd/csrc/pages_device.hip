@@ -23,6 +23,7 @@
 #include <climits>
 #include <cstring>
 #include <memory>
+#include <unordered_set>
 #include <vector>
 
 #include "vbm25_internal.h"
@@ -444,30 +445,26 @@ __global__ void __launch_bounds__(WG_THREADS) vec_check_kernel(VecPlanes c, unsi
     }
 }
 
-int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_growing **out, vbm25_growing **csr) {
-    if (csr) *csr = nullptr;
-    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!index || !read_page) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
-        return set_error(VBM25_ERR_DEVICE, "no HIP device: the device reader has no CPU fallback (vbm25_growing_from_pages is the host reader)");
-    int device = 0;
-    uint32_t sealed_docs = 0;
-    if (int rc = index_device_and_docs(index, &device, &sealed_docs)) return rc;
-    PG_TRY(hipSetDevice(device));
-    for (double &x : g_vec_stats) x = 0.0;
+// The vectors tape's CSR in HBM: where the reader's first half leaves it and what its callers keep (the vacuum handle) or build a
+// device growing segment of
+struct VecCsr {
+    uint32_t n_docs = 0;
+    uint64_t n_el = 0;
+    HbmArray *start, *key, *tf, *fieldnorm, *deleted, *payload;
+    double kernel_ms = 0.0;
+    uint64_t bytes_down = 0;
+};
 
-    Stream stream;
-    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
-    hipStream_t s = stream.s;
-    Stager st;
-    if (int rc = st.init(s)) return rc;
-
+// The reader's first half: the host pass and the kernels above, up to a validated CSR in HBM (synchronised).  The pages are staged
+// through `st` into its chunk list `slot`; ptr_vectors: Jump.ptr_vectors of a Jump tuple the caller has read (NULL: Meta and Jump
+// are read here).  Refusals in vbm25_device_growing_from_pages' documented order.
+int vectors_csr(hipStream_t s, Stager &st, uint32_t slot, vbm25_read_page_fn read_page, void *ctx, const uint32_t *ptr_vectors,
+                uint32_t sealed_docs, VecCsr &o) {
     // ---- the host pass
     Walk w;
     int sink_rc = 0;
-    const bool walked = walk_vectors(read_page, ctx, w, [&](uint32_t tape, uint32_t, const uint8_t *image) { return st.add(tape, image); }, sink_rc);
+    auto sink = [&](uint32_t, uint32_t, const uint8_t *image) { return st.add(slot, image); };
+    const bool walked = ptr_vectors ? walk_vectors_from(read_page, ctx, w, *ptr_vectors, sink, sink_rc) : walk_vectors(read_page, ctx, w, sink, sink_rc);
     if (!walked) {
         (void)hipStreamSynchronize(s);  // nothing is freed under a copy in flight
         return sink_rc ? sink_rc : corrupt(w.what, w.bad_page);
@@ -488,7 +485,7 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
     // for the device, nothing is freed under a kernel or a copy in flight
     DBuf d_chunk, d_pre, d_meta, d_cnt, d_mark, d_sum, d_last, d_fin, d_kept, d_eoff, d_err, d_tmp[3];
     std::vector<const uint8_t *> chunk_ptr;
-    for (const auto &d : st.chunks[0]) chunk_ptr.push_back(d->as<uint8_t>());
+    for (const auto &d : st.chunks[slot]) chunk_ptr.push_back(d->as<uint8_t>());
     PG_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
     PG_TRY(d_pre.alloc(4 * (np + 1)));
     if (np) PG_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
@@ -561,7 +558,7 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
         return set_error(VBM25_ERR_UNSUPPORTED, "%llu growing elements: the device path takes fewer than 2^31", n_el);
 
     // ---- the CSR
-    DBuf d_start, d_key, d_tf, d_fn, d_del, d_payload;
+    HbmArray &d_start = *o.start, &d_key = *o.key, &d_tf = *o.tf, &d_fn = *o.fieldnorm, &d_del = *o.deleted, &d_payload = *o.payload;
     PG_TRY(d_start.alloc(8ull * (n_docs + 1ull)));
     PG_TRY(d_key.alloc(16ull * n_el));
     PG_TRY(d_tf.alloc(4ull * n_el));
@@ -590,8 +587,45 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
     bytes_down += 8;
     if (key != NO_ERROR)
         return set_error(VBM25_ERR_INVALID, "growing document %u: keys must be strictly ascending", (uint32_t)key_pos(key));
+    float ms_a = 0, ms_b = 0;
+    PG_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
+    PG_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
+    o.n_docs = n_docs;
+    o.n_el = n_el;
+    o.kernel_ms = (double)ms_a + (double)ms_b;
+    o.bytes_down = bytes_down;
+    return VBM25_OK;
+}
 
-    // ---- the CSR's host copy, when asked for, before the scratch goes
+int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_growing **out, vbm25_growing **csr) {
+    if (csr) *csr = nullptr;
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!index || !read_page) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the device reader has no CPU fallback (vbm25_growing_from_pages is the host reader)");
+    int device = 0;
+    uint32_t sealed_docs = 0;
+    if (int rc = index_device_and_docs(index, &device, &sealed_docs)) return rc;
+    PG_TRY(hipSetDevice(device));
+    for (double &x : g_vec_stats) x = 0.0;
+
+    Stream stream;
+    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t s = stream.s;
+    // (the planes before the stager: they go last, after the stream's work has been waited for)
+    HbmArray d_start, d_key, d_tf, d_fn, d_del, d_payload;
+    Stager st;
+    if (int rc = st.init(s)) return rc;
+    VecCsr v;
+    v.start = &d_start, v.key = &d_key, v.tf = &d_tf, v.fieldnorm = &d_fn, v.deleted = &d_del, v.payload = &d_payload;
+    if (int rc = vectors_csr(s, st, 0, read_page, ctx, nullptr, sealed_docs, v)) return rc;
+    const uint32_t n_docs = v.n_docs;
+    const uint64_t n_el = v.n_el;
+    uint64_t bytes_down = v.bytes_down;
+
+    // ---- the CSR's host copy, when asked for
     std::unique_ptr<vbm25_growing> host;
     if (csr) {
         host = std::make_unique<vbm25_growing>();
@@ -619,14 +653,188 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
     const GrowingDeviceArrays a{n_docs, n_el, d_start.as<uint64_t>(), d_key.as<uint8_t>(), d_tf.as<uint32_t>(), d_fn.as<uint8_t>(),
                                 d_del.as<uint8_t>(), d_payload.as<uint16_t>()};
     if (int rc = growing_from_device_arrays(index, a, out)) return rc;
-    float ms_a = 0, ms_b = 0;
-    PG_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
-    PG_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
-    g_vec_stats[0] = (double)ms_a + (double)ms_b;
+    g_vec_stats[0] = v.kernel_ms;
     g_vec_stats[1] = (double)st.bytes_up;
     g_vec_stats[2] = (double)bytes_down;
     g_vec_stats[3] = (double)n_el;
     if (csr) *csr = host.release();
+    return VBM25_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// A relation's compaction inputs -> HBM (vbm25_device_vacuum_from_pages): the sealed documents' deleted flags as words, then the
+// vectors tape's CSR by vectors_csr above, both kept in the handle.
+//   host pass            Meta and Jump once; the documents tape by Opaque.next, staged and uploaded as above; then the vectors tape
+//   doc_deleted_kernel   one wave per documents-tape page, lane i takes slot i + 1 (+ 64 ...): doc_deleted_lane, a ballot per round of
+//                        64 slots, the round's 64 flags ORed into the one or two words they fall into
+//   (reductions)         popcounts of the words, nonzero bytes of the growing `deleted` plane (hipcub)
+// A page holds up to 680 document tuples = 10 x 64 + 40, so the rounds of a page are not word aligned and the words at a page boundary
+// belong to two waves.  The words are zeroed first and written with atomicOr only: OR commutes, the result does not depend on the
+// order the waves run in, and a round costs two atomics where a byte-per-document plane packed by a second kernel would cost a
+// store per document, a second pass over n_docs bytes and the plane itself.  No grid cap and no stride: one wave per page.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct PopCount64 {
+    __host__ __device__ uint32_t operator()(unsigned long long w) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return (uint32_t)__popcll(w);
+#else
+        return (uint32_t)__builtin_popcountll(w);
+#endif
+    }
+};
+struct NonZeroByte {
+    __host__ __device__ uint32_t operator()(uint8_t v) const { return v != 0; }
+};
+
+thread_local double g_vac_stats[4];
+
+__global__ void __launch_bounds__(WG_THREADS) doc_deleted_kernel(TapeView docs, uint32_t n_docs, unsigned long long *words, unsigned long long *err) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t p64 = ((uint64_t)blockIdx.x * WG_THREADS + threadIdx.x) >> 6;
+    if (p64 >= docs.n_pages) return;  // (whole waves)
+    const uint32_t p = (uint32_t)p64, base = docs.pre[p], n = docs.pre[p + 1] - base;
+    for (uint32_t r = 0; r < n; r += 64) {  // every lane of the wave takes every round: the ballot reads them all
+        const uint32_t i = r + lane;
+        bool deleted = false;
+        if (i < n) {
+            if (const uint32_t reason = doc_deleted_lane(docs, p, i, deleted)) atomicMin(err, (unsigned long long)error_key(T_DOCS, (uint64_t)base + i, reason));
+            // a tape longer than Jump's count is refused by the caller: its surplus tuples have no bit
+            if ((uint64_t)base + i >= n_docs) deleted = false;
+        }
+        const unsigned long long m = __ballot(deleted);
+        if (!m) continue;
+        const uint64_t first = (uint64_t)base + r;  // the document of lane 0; every set bit of m is a document < n_docs
+        uint64_t lo, hi;
+        flag_round_words(first, m, lo, hi);
+        if (lane == 0 && lo) atomicOr(words + (first >> 6), (unsigned long long)lo);
+        if (lane == 1 && hi) atomicOr(words + (first >> 6) + 1, (unsigned long long)hi);
+    }
+}
+
+const char *doc_reason_text(uint32_t r) { return r == R_TUPLE_SHORT ? "document tuple too short" : reason_text(r); }
+
+int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_vacuum **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!index || !read_page) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the device reader has no CPU fallback (vbm25_sealed_deleted_from_pages and "
+                                           "vbm25_growing_from_pages are the host readers)");
+    int device = 0;
+    uint32_t sealed_docs = 0;
+    if (int rc = index_device_and_docs(index, &device, &sealed_docs)) return rc;
+    PG_TRY(hipSetDevice(device));
+    for (double &x : g_vac_stats) x = 0.0;
+
+    Stream stream;
+    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    hipStream_t s = stream.s;
+    auto dv = std::make_unique<vbm25_device_vacuum>();  // (before the stager: its planes go last)
+    dv->device = device;
+    Stager st;
+    if (int rc = st.init(s)) return rc;
+
+    // ---- the host pass over the documents tape.  A refusal of the walk is held back until the lanes have looked at the pages in
+    // front of it: the host reader meets their tuples first
+    Walk w;
+    const uint8_t *j = read_meta_jump(read_page, ctx, w);
+    if (!j) return corrupt(w.what, w.bad_page);
+    const uint32_t ptr_vectors = host_rd32(j), ptr_documents = host_rd32(j + 44), n_docs = w.n_docs;
+    int sink_rc = 0;
+    std::unordered_set<uint32_t> seen;
+    const bool walked = walk_tape_pages(read_page, ctx, w, T_DOCS, ptr_documents, seen,
+                                        [&](uint32_t tape, uint32_t, const uint8_t *image) { return st.add(tape, image); }, sink_rc, true);
+    int rc = !walked && sink_rc ? sink_rc : st.flush();
+    if (rc) {
+        (void)hipStreamSynchronize(s);  // nothing is freed under a copy in flight
+        return rc;
+    }
+    const size_t np = w.pid[T_DOCS].size();
+    const uint32_t W = (uint32_t)(((uint64_t)n_docs + 63u) / 64u);
+    uint64_t bytes_down = 0;
+
+    // ---- the flags.  From here on a failure returns through the buffers' destructors (hipFree waits for the device)
+    float ms_flags = 0;
+    {
+        DBuf d_chunk, d_pre, d_err, d_cnt, d_tmp;
+        std::vector<const uint8_t *> chunk_ptr;
+        for (const auto &d : st.chunks[T_DOCS]) chunk_ptr.push_back(d->as<uint8_t>());
+        PG_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
+        PG_TRY(d_pre.alloc(4 * (np + 1)));
+        PG_TRY(d_err.alloc(8));
+        PG_TRY(d_cnt.alloc(4));
+        PG_TRY(dv->d_sealed_deleted.alloc(8ull * W));
+        if (np) PG_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
+        PG_TRY(hipMemcpyAsync(d_pre.p, w.pre[T_DOCS].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
+        st.bytes_up += 8 * chunk_ptr.size() + 4 * (np + 1);
+        Event ev[2];
+        for (Event &e : ev) PG_TRY(hipEventCreate(&e.e));
+        PG_TRY(hipEventRecord(ev[0].e, s));
+        PG_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
+        PG_TRY(hipMemsetAsync(d_cnt.p, 0, 4, s));
+        PG_TRY(hipMemsetAsync(dv->d_sealed_deleted.p, 0, W ? 8ull * W : 16, s));
+        const TapeView docs{d_chunk.as<const uint8_t *>(), nullptr, d_pre.as<uint32_t>(), (uint32_t)np, w.pre[T_DOCS].back()};
+        if (np && docs.n_tuples)
+            doc_deleted_kernel<<<(uint32_t)((np + 3) / 4), WG_THREADS, 0, s>>>(docs, n_docs, dv->d_sealed_deleted.as<unsigned long long>(),
+                                                                               d_err.as<unsigned long long>());
+        if (W) {
+            hipcub::TransformInputIterator<uint32_t, PopCount64, const unsigned long long *> pop(dv->d_sealed_deleted.as<unsigned long long>(), PopCount64());
+            size_t tb = 0;
+            PG_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, pop, d_cnt.as<uint32_t>(), (int)W, s));
+            PG_TRY(d_tmp.alloc(tb));
+            PG_TRY(hipcub::DeviceReduce::Sum(d_tmp.p, tb, pop, d_cnt.as<uint32_t>(), (int)W, s));
+        }
+        PG_TRY(hipGetLastError());
+        PG_TRY(hipEventRecord(ev[1].e, s));
+        unsigned long long key = 0;
+        PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+        PG_TRY(hipMemcpyAsync(&dv->n_sealed_deleted, d_cnt.p, 4, hipMemcpyDeviceToHost, s));
+        PG_TRY(hipStreamSynchronize(s));
+        bytes_down += 12;
+        // ---- the verdict on the documents tape, in vbm25_sealed_deleted_from_pages' order
+        if (key != NO_ERROR) return corrupt(doc_reason_text(key_reason(key)), error_page(w, key));
+        if (!walked) return corrupt(w.what, w.bad_page);
+        if (w.pre[T_DOCS].back() != n_docs) return corrupt("document count differs from the Jump tuple", ptr_documents);
+        PG_TRY(hipEventElapsedTime(&ms_flags, ev[0].e, ev[1].e));
+    }
+    st.chunks[T_DOCS].clear();  // (synchronised above: the documents tape's images are done with)
+    dv->n_sealed = n_docs;
+
+    // ---- the vectors tape, into the handle's planes
+    VecCsr v;
+    v.start = &dv->d_start, v.key = &dv->d_key, v.tf = &dv->d_tf, v.fieldnorm = &dv->d_fieldnorm, v.deleted = &dv->d_deleted, v.payload = &dv->d_payload;
+    if (int rc2 = vectors_csr(s, st, 1, read_page, ctx, &ptr_vectors, sealed_docs, v)) return rc2;
+    dv->n_grow = v.n_docs;
+    dv->n_elements = v.n_el;
+    if (v.n_docs) {
+        DBuf d_cnt, d_tmp;
+        PG_TRY(d_cnt.alloc(4));
+        hipcub::TransformInputIterator<uint32_t, NonZeroByte, const uint8_t *> nz(dv->d_deleted.as<uint8_t>(), NonZeroByte());
+        size_t tb = 0;
+        PG_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, nz, d_cnt.as<uint32_t>(), (int)v.n_docs, s));
+        PG_TRY(d_tmp.alloc(tb));
+        PG_TRY(hipcub::DeviceReduce::Sum(d_tmp.p, tb, nz, d_cnt.as<uint32_t>(), (int)v.n_docs, s));
+        PG_TRY(hipMemcpyAsync(&dv->n_grow_deleted, d_cnt.p, 4, hipMemcpyDeviceToHost, s));
+        PG_TRY(hipStreamSynchronize(s));
+        bytes_down += 4;
+    }
+    if (n_docs != sealed_docs)
+        return set_error(VBM25_ERR_INVALID, "the relation holds %u sealed documents, the index %u: the index of another relation", n_docs, sealed_docs);
+    g_vac_stats[0] = (double)ms_flags + v.kernel_ms;
+    g_vac_stats[1] = (double)st.bytes_up;
+    g_vac_stats[2] = (double)(bytes_down + v.bytes_down);
+    g_vac_stats[3] = (double)v.n_el;
+    *out = dv.release();
+    return VBM25_OK;
+}
+
+int vacuum_read_impl(const vbm25_device_vacuum *v, uint64_t *sealed_deleted_words, uint8_t *growing_deleted) {
+    if (!v) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    PG_TRY(hipSetDevice(v->device));
+    const uint64_t W = ((uint64_t)v->n_sealed + 63u) / 64u;
+    if (sealed_deleted_words && W) PG_TRY(hipMemcpy(sealed_deleted_words, v->d_sealed_deleted.p, 8ull * W, hipMemcpyDeviceToHost));
+    if (growing_deleted && v->n_grow) PG_TRY(hipMemcpy(growing_deleted, v->d_deleted.p, v->n_grow, hipMemcpyDeviceToHost));
     return VBM25_OK;
 }
 
@@ -656,5 +864,35 @@ extern "C" int vbm25_device_growing_from_pages(vbm25_index *index, vbm25_read_pa
 extern "C" int vbm25_debug_growing_pages_stats(double *out4) {
     if (!out4) return vbm25::set_error(VBM25_ERR_INVALID, "NULL argument");
     for (int i = 0; i < 4; ++i) out4[i] = g_vec_stats[i];
+    return VBM25_OK;
+}
+
+extern "C" int vbm25_device_vacuum_from_pages(vbm25_index *index, vbm25_read_page_fn read_page, void *ctx, vbm25_device_vacuum **out) {
+    return vbm25::guarded([&] { return vacuum_from_pages_impl(index, read_page, ctx, out); });
+}
+extern "C" int vbm25_device_vacuum_info(const vbm25_device_vacuum *v, uint32_t *n_sealed, uint32_t *n_sealed_deleted, uint32_t *n_grow,
+                                        uint32_t *n_grow_deleted, uint64_t *n_elements) {
+    if (!v) return vbm25::set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (n_sealed) *n_sealed = v->n_sealed;
+    if (n_sealed_deleted) *n_sealed_deleted = v->n_sealed_deleted;
+    if (n_grow) *n_grow = v->n_grow;
+    if (n_grow_deleted) *n_grow_deleted = v->n_grow_deleted;
+    if (n_elements) *n_elements = v->n_elements;
+    return VBM25_OK;
+}
+extern "C" int vbm25_device_vacuum_read(const vbm25_device_vacuum *v, uint64_t *sealed_deleted_words, uint8_t *growing_deleted) {
+    return vbm25::guarded([&] { return vacuum_read_impl(v, sealed_deleted_words, growing_deleted); });
+}
+extern "C" void vbm25_device_vacuum_free(vbm25_device_vacuum *v) {
+    if (!v) return;
+    (void)hipSetDevice(v->device);
+    delete v;
+}
+
+// The last successful vbm25_device_vacuum_from_pages of this thread (tools/vacuum_device_cost.py; not part of the ABI): [0] ms of the
+// reader's kernels, scans and reductions between HIP events, [1] bytes host -> device, [2] bytes device -> host, [3] elements read
+extern "C" int vbm25_debug_vacuum_pages_stats(double *out4) {
+    if (!out4) return vbm25::set_error(VBM25_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < 4; ++i) out4[i] = g_vac_stats[i];
     return VBM25_OK;
 }

@@ -172,6 +172,25 @@ PGS_HD inline uint32_t doc_lane(const Planes &c, uint32_t p, uint32_t i) {
     return R_OK;
 }
 
+// DocumentTuple.deleted (byte 0; the reference's Bool: != 0) of slot i of documents-tape page p, with doc_lane's line pointer check:
+// what vbm25_sealed_deleted_from_pages reads, per lane (csrc/pages_device.hip: doc_deleted_kernel)
+PGS_HD inline uint32_t doc_deleted_lane(const TapeView &docs, uint32_t p, uint32_t i, bool &deleted) {
+    const uint8_t *page = tape_page(docs, p);
+    uint32_t off, len;
+    deleted = false;
+    if (uint32_t r = line_pointer(page, i, 8, off, len)) return r;
+    deleted = page[off] != 0;
+    return R_OK;
+}
+
+// The 64 flags of one round of a wave (bit l of m: the document first + l) as the one or two words of the bitmap they fall into:
+// lo for word first / 64, hi for the next one (0 when the round is word aligned; a shift by 64 is undefined)
+PGS_HD inline void flag_round_words(uint64_t first, uint64_t m, uint64_t &lo, uint64_t &hi) {
+    const uint32_t sh = (uint32_t)(first & 63u);
+    lo = m << sh;
+    hi = sh ? m >> (64u - sh) : 0;
+}
+
 // TokenTuple (>= 32 bytes): key at 0, wand fieldnorm at 17, first summary (page at 18, slot at 22), df at 24, wand tf at 28
 PGS_HD inline uint32_t token_lane(const Planes &c, uint32_t p, uint32_t i) {
     const uint8_t *page = tape_page(c.tape[T_TOKENS], p);
@@ -350,10 +369,11 @@ inline const uint8_t *read_meta_jump(vbm25_read_page_fn fn, void *ctx, Walk &w) 
 }
 
 // One tape from page `first` by Opaque.next into w.pid[t] / w.pre[t]; `walked` holds the pages seen so far.  false: refused
-// (w.what / w.bad_page), or the sink's status in `sink_rc`
+// (w.what / w.bad_page), or the sink's status in `sink_rc`.  special_last: the page whose special area is refused is handed to the
+// sink and counted first, as the host readers meet its tuples before they follow its link (the vacuum reader's documents tape)
 template <class Sink>
 bool walk_tape_pages(vbm25_read_page_fn fn, void *ctx, Walk &w, uint32_t t, uint32_t first, std::unordered_set<uint32_t> &walked, Sink &&sink,
-                     int &sink_rc) {
+                     int &sink_rc, bool special_last = false) {
     uint64_t tuples = 0;
     w.pre[t].push_back(0);
     for (uint32_t cur = first; cur != NONE;) {
@@ -362,12 +382,14 @@ bool walk_tape_pages(vbm25_read_page_fn fn, void *ctx, Walk &w, uint32_t t, uint
         if (!page) return w.fail("page cannot be read", cur);
         const int n = page_tuples(page);
         if (n < 0) return w.fail("page header out of range", cur);
-        if (host_rd16(page + 16) != BLCKSZ - 8) return w.fail("special area is not Opaque", cur);
+        const bool opaque = host_rd16(page + 16) == BLCKSZ - 8;
+        if (!opaque && !special_last) return w.fail("special area is not Opaque", cur);
         tuples += (uint32_t)n;
         if (tuples > 0xfffffff0ull || w.pid[t].size() >= 0xfffffff0ull) return w.fail("more than 2^32 tuples on a tape", cur);
         if ((sink_rc = sink(t, (uint32_t)w.pid[t].size(), page)) != 0) return false;
         w.pid[t].push_back(cur);
         w.pre[t].push_back((uint32_t)tuples);
+        if (!opaque) return w.fail("special area is not Opaque", cur);
         cur = host_rd32(page + BLCKSZ - 8);
     }
     return true;

@@ -794,11 +794,16 @@ static int vbm25_index_create_from_device_impl(const vbm25_device_segment *ds, v
 }
 
 // VACUUM's compaction (csrc/maintain.hip): the index's blocks, keys and payloads are read, nothing of it is changed
-static int vbm25_index_maintain_impl(const vbm25_index *ix, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing,
-                                     uint32_t *relabel, vbm25_device_segment **out) {
+// (in.dev: vbm25_index_maintain_device, the inputs in a vbm25_device_vacuum's planes)
+static int vbm25_index_maintain_impl(const vbm25_index *ix, const MaintainInput &in, uint32_t *relabel, vbm25_device_segment **out) {
     if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!ix) return set_error(VBM25_ERR_INVALID, "index is NULL");
+    if (in.dev) {
+        int n_dev = 0;  // before the handles are looked into: without a device there is neither
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+            return set_error(VBM25_ERR_DEVICE, "no HIP device: maintain has no CPU entry point");
+    }
     MaintainSource s{};
     s.device = ix->device;
     s.k1 = ix->k1;
@@ -811,7 +816,7 @@ static int vbm25_index_maintain_impl(const vbm25_index *ix, const uint64_t *seal
     s.blk_meta = ix->blk_meta.as<uint4>();
     s.blob = ix->blob.as<uint8_t>();
     s.doc_payload = ix->doc_payload.as<uint16_t>();
-    return maintain_device(s, sealed_deleted, growing, relabel, out);
+    return maintain_device(s, in, relabel, out);
 }
 
 void vbm25_index_destroy(vbm25_index *ix) {
@@ -1975,7 +1980,12 @@ int vbm25_index_create_from_device(const vbm25_device_segment *ds, vbm25_index *
 }
 int vbm25_index_maintain(const vbm25_index *ix, const uint64_t *sealed_deleted, const vbm25_growing_desc *growing, uint32_t *relabel,
                          vbm25_device_segment **out) {
-    return guarded([&] { return vbm25_index_maintain_impl(ix, sealed_deleted, growing, relabel, out); });
+    return guarded([&] { return vbm25_index_maintain_impl(ix, MaintainInput{sealed_deleted, growing, nullptr}, relabel, out); });
+}
+int vbm25_index_maintain_device(const vbm25_index *ix, const vbm25_device_vacuum *in, uint32_t *relabel, vbm25_device_segment **out) {
+    if (out) *out = nullptr;
+    if (out && !in) return set_error(VBM25_ERR_INVALID, "NULL argument");  // (a NULL handle is not "no inputs")
+    return guarded([&] { return vbm25_index_maintain_impl(ix, MaintainInput{nullptr, nullptr, in}, relabel, out); });
 }
 
 int vbm25_batch_create(vbm25_index *ix, uint32_t max_queries, uint32_t max_total_terms, uint32_t k,
@@ -2808,14 +2818,28 @@ int vbm25_search_batch_growing_filtered(vbm25_index *ix, const vbm25_device_grow
 // filter's bitmap i is the old sealed bitmap i's bits of the kept documents followed by the old growing bitmap i's bits of the live
 // ones (filter_remap_device, maintain.hip).  The old filter is only read.  Everything is checked, and the new words are written,
 // before *out is set: a failure leaves nothing behind.
-static int vbm25_filter_remap_impl(const vbm25_filter *old, const uint64_t *sealed_deleted, uint32_t n_grow, const uint8_t *growing_deleted,
-                                   vbm25_index *nix, vbm25_filter **out) {
+// del.dev: vbm25_filter_remap_device, the three deletion arguments taken from the handle (n_grow is then the handle's)
+static int vbm25_filter_remap_impl(const vbm25_filter *old, const RemapDeletions &del, uint32_t n_grow, vbm25_index *nix, vbm25_filter **out) {
     if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!old || !nix) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const vbm25_device_vacuum *dv = del.dev;
+    const uint64_t *sealed_deleted = dv ? nullptr : del.sealed_deleted;  // (the handle's words have no bits at or beyond n_docs)
+    if (dv) {
+        int n_dev = 0;  // before the handles are looked into: without a device there is none of them
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+            return set_error(VBM25_ERR_DEVICE, "no HIP device: a filter lives on the device");
+    }
     if (nix->device != old->device)
         return set_error(VBM25_ERR_INVALID, "the new index is on device %d, the filter on device %d", nix->device, old->device);
     const uint32_t N = old->index->n_docs;
+    if (dv) {
+        if (dv->device != old->device)
+            return set_error(VBM25_ERR_INVALID, "the compaction inputs are on device %d, the filter on device %d", dv->device, old->device);
+        if (dv->n_sealed != N)
+            return set_error(VBM25_ERR_INVALID, "the compaction inputs are of %u sealed documents, the filter's index holds %u", dv->n_sealed, N);
+        n_grow = dv->n_grow;
+    }
     if (sealed_deleted && (N & 63u) && (sealed_deleted[old->words - 1] >> (N & 63u)))
         return set_error(VBM25_ERR_INVALID, "sealed_deleted has bits at or beyond n_docs = %u", N);
     if (n_grow) {
@@ -2831,8 +2855,8 @@ static int vbm25_filter_remap_impl(const vbm25_filter *old, const uint64_t *seal
     f->n_bitmaps = old->n_bitmaps;
     f->words = (nix->n_docs + 63u) / 64u;
     if (int rc = f->bits.alloc(8ull * f->n_bitmaps * f->words)) return rc;
-    if (int rc = filter_remap_device(old->device, old->n_bitmaps, N, sealed_deleted, old->bits.p, n_grow, n_grow ? growing_deleted : nullptr,
-                                     n_grow ? old->grow_bits.p : nullptr, old->grow_stride, nix->n_docs, f->bits.p))
+    if (int rc = filter_remap_device(old->device, old->n_bitmaps, N, old->bits.p, n_grow, del, n_grow ? old->grow_bits.p : nullptr,
+                                     old->grow_stride, nix->n_docs, f->bits.p))
         return rc;
     *out = f.release();
     return VBM25_OK;
@@ -2853,7 +2877,12 @@ static int vbm25_filter_read_impl(const vbm25_filter *f, uint32_t i, int growing
 extern "C" {
 int vbm25_filter_remap(const vbm25_filter *old, const uint64_t *sealed_deleted, uint32_t n_grow, const uint8_t *growing_deleted,
                        vbm25_index *new_index, vbm25_filter **out) {
-    return guarded([&] { return vbm25_filter_remap_impl(old, sealed_deleted, n_grow, growing_deleted, new_index, out); });
+    return guarded([&] { return vbm25_filter_remap_impl(old, RemapDeletions{sealed_deleted, growing_deleted, nullptr}, n_grow, new_index, out); });
+}
+int vbm25_filter_remap_device(const vbm25_filter *old, const vbm25_device_vacuum *in, vbm25_index *new_index, vbm25_filter **out) {
+    if (out) *out = nullptr;
+    if (out && !in) return set_error(VBM25_ERR_INVALID, "NULL argument");  // (a NULL handle is not "nothing deleted")
+    return guarded([&] { return vbm25_filter_remap_impl(old, RemapDeletions{nullptr, nullptr, in}, 0, new_index, out); });
 }
 int vbm25_filter_read(const vbm25_filter *f, uint32_t i, int growing, uint64_t *words) {
     return guarded([&] { return vbm25_filter_read_impl(f, i, growing, words); });

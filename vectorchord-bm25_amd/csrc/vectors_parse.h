@@ -202,15 +202,20 @@ PGS_HD inline uint32_t check_element_lane(const VecPlanes &c, uint32_t p, uint32
 
 // The host pass: Meta -> Jump -> the vectors tape by Opaque.next into w.pid[0] / w.pre[0], with walk_relation's per-page checks;
 // "page linked twice" within this tape, as the host reader has it.  No tuple is touched.
+// `first`: Jump.ptr_vectors of a Jump tuple the caller has read
+template <class Sink>
+bool walk_vectors_from(vbm25_read_page_fn fn, void *ctx, Walk &w, uint32_t first, Sink &&sink, int &sink_rc) {
+    sink_rc = 0;
+    if (first == NONE) return w.fail("no vectors tape", 0);  // search.rs:85
+    std::unordered_set<uint32_t> walked;
+    return walk_tape_pages(fn, ctx, w, 0, first, walked, sink, sink_rc);
+}
 template <class Sink>
 bool walk_vectors(vbm25_read_page_fn fn, void *ctx, Walk &w, Sink &&sink, int &sink_rc) {
     sink_rc = 0;
     const uint8_t *j = read_meta_jump(fn, ctx, w);
     if (!j) return false;
-    const uint32_t first = host_rd32(j);  // Jump.ptr_vectors
-    if (first == NONE) return w.fail("no vectors tape", 0);  // search.rs:85
-    std::unordered_set<uint32_t> walked;
-    return walk_tape_pages(fn, ctx, w, 0, first, walked, sink, sink_rc);
+    return walk_vectors_from(fn, ctx, w, host_rd32(j) /* Jump.ptr_vectors */, sink, sink_rc);
 }
 
 }  // namespace pgs
