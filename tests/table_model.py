@@ -1,0 +1,303 @@
+"""A model of one table's rows through INSERT, SELECT, DELETE and VACUUM (the reference's tests/fuzz transposed), for
+tests/test_table_model.py and tests/test_gpu_table_fuzz.py.  It knows which rows the table holds and the reference's rules, and
+nothing of the library: its only dependencies are numpy and the oracle (tests/orc.py), which flushes the rows (flush.rs), lays the
+relation out (build.rs, insert.rs), ranks the sealed rows by brute force and evaluates one BM25 term.  No GPU use.
+
+The rules:
+  * a growing row's length is min(sum tf, 2^32 - 1) (vector.rs:77-83);
+  * deleted sealed rows stay in the index and in its statistics until the next VACUUM (search.rs:226-229 only skips them);
+  * a growing row is scored with the sealed segment's statistics over the query keys both it and the sealed vocabulary hold,
+    summed in ascending key order from 0.0, and enters with a score > 0 as doc_id 0xFFFFFFFF - g (search.rs:83-135);
+  * order: score descending; on equal scores sealed before growing, sealed by id, growing by g;
+  * VACUUM keeps the live sealed rows in order, then the live growing rows in order; a kept sealed row's new length is its number
+    of postings (maintain.rs:344-362), a growing row keeps its length; everything is flushed again from scratch."""
+import struct
+
+import numpy as np
+
+import orc
+
+NONE = 0xFFFFFFFF
+MAX_K = 65535
+KS = (1, 10, 100, 300, 1025)
+NO_ROW_KEY = b"~no row".ljust(16, b"\0")
+INSERT_KEYS = (1, 3, 30, 250)
+INSERT_ROWS = (1, 4, 16)
+
+
+def new_key(i):
+    """a key no initial row holds (corpus.token_keys are decimal digits)"""
+    return (b"n%06d" % i).ljust(16, b"\0")
+
+
+def random_rows(n_docs, vocab, seed, mean_len=40):
+    """n_docs rows of lognormal length (mean about mean_len) over `vocab` Zipf(1) tokens (tests/fuzz:168-205 of the reference: a row
+    is its length in token draws, tf the multiplicity); token t's key is its decimal digits, zero padded (vector.rs:21-24).
+    Returns (rows, the keys of all `vocab` tokens)."""
+    rng = np.random.default_rng(seed)
+    keys = [str(t).encode().ljust(16, b"\0") for t in range(vocab)]
+    lens = np.clip(np.rint(rng.lognormal(np.log(mean_len * 0.8), 0.6, n_docs)), 8, 2000).astype(np.int64)
+    p = 1.0 / np.arange(1, vocab + 1)
+    rows = []
+    for d in range(n_docs):
+        tok, cnt = np.unique(rng.choice(vocab, int(lens[d]), p=p / p.sum()), return_counts=True)
+        rows.append((((d // 64) >> 16, (d // 64) & 0xffff, d % 64 + 1), {keys[t]: int(c) for t, c in zip(tok, cnt)}, int(lens[d])))
+    return rows, keys
+
+
+def length_of(kt):
+    return min(sum(kt.values()), 2 ** 32 - 1)
+
+
+def _slots(page):
+    lower = struct.unpack_from("<H", page, 12)[0]
+    return [struct.unpack_from("<I", page, 24 + 4 * i)[0] & 0x7fff for i in range((lower - 24) // 4)]
+
+
+class Table:
+    def __init__(self, rows, k1, b, seed32):
+        self.k1, self.b, self.seed = float(k1), float(b), bytes(seed32)
+        self.vacuums = []   # per VACUUM: (sealed rows deleted, growing rows deleted, keys the sealed vocabulary lacked)
+        self.stats = dict(selects=0, both=0, nothing=0, deleted_shown=0, mixed_ties=0)
+        self._seal([(tuple(p), dict(kt), int(ln)) for p, kt, ln in rows])
+
+    # ---- state
+
+    def _seal(self, rows):
+        """flush `rows` from scratch: the oracle's index and its relation; no growing rows, nothing deleted"""
+        self.sealed = rows
+        self.sealed_deleted = np.zeros(len(rows), bool)
+        self.growing, self.growing_deleted = [], []
+        self.ginv = {}     # key -> [(g, tf)] of the growing rows, g ascending
+        vocab = sorted({key for _, kt, _ in rows for key in kt})
+        self.vocab, self.rank = vocab, {key: t for t, key in enumerate(vocab)}
+        t_of, d_of, tf_of = [], [], []
+        for d, (_, kt, _) in enumerate(rows):
+            for key, tf in kt.items():
+                t_of.append(self.rank[key])
+                d_of.append(d)
+                tf_of.append(tf)
+        t_of, d_of, tf_of = np.array(t_of, np.int64), np.array(d_of, np.int64), np.array(tf_of, np.uint32)
+        order = np.lexsort((d_of, t_of))
+        term_start = np.r_[0, np.cumsum(np.bincount(t_of, minlength=len(vocab)))].astype(np.uint64)
+        term_key = np.frombuffer(b"".join(vocab), np.uint8).reshape(-1, 16) if vocab else np.zeros((0, 16), np.uint8)
+        self.oix = orc.OracleIndex.build(self.k1, self.b, np.array([ln for _, _, ln in rows], np.uint32),
+                                         np.array([p for p, _, _ in rows], np.uint16).reshape(-1, 3), term_key, term_start,
+                                         d_of[order].astype(np.uint32), tf_of[order])
+        assert self.oix.n_docs == len(rows) and self.oix.n_terms == len(vocab)
+        self.pages = orc.Pages(self.oix, seed=self.seed)
+        self._doc_slots = None
+        self._eval = {}
+
+    def doc_slots(self):
+        """(page id, offset of the DocumentTuple) of every sealed row in id order: Meta -> Jump -> ptr_documents -> the chain"""
+        if self._doc_slots is None:
+            p0 = self.pages.page(0)
+            ptr_jump = struct.unpack_from("<I", p0, _slots(p0)[0] + 36)[0]
+            pj = self.pages.page(ptr_jump)
+            p = struct.unpack_from("<I", pj, _slots(pj)[0] + 44)[0]
+            where = []
+            while p != NONE:
+                pg = self.pages.page(p)
+                where += [(p, off) for off in _slots(pg)]
+                p = struct.unpack_from("<I", pg, 8184)[0]
+            assert len(where) == len(self.sealed)
+            self._doc_slots = where
+        return self._doc_slots
+
+    def page_list(self):
+        return [self.pages.page(i) for i in range(len(self.pages))]
+
+    # ---- mutations
+
+    def insert(self, payload, kt):
+        keys = sorted(kt)
+        self.pages.insert(np.array(payload, np.uint16), keys, [kt[key] for key in keys])
+        g = len(self.growing)
+        self.growing.append((tuple(int(x) for x in payload), dict(kt), length_of(kt)))
+        self.growing_deleted.append(False)
+        for key in keys:
+            self.ginv.setdefault(key, []).append((g, kt[key]))
+        return g
+
+    def delete_sealed(self, d):
+        p, off = self.doc_slots()[d]
+        self.pages.page(p, writable=True)[off] = 1   # DocumentTuple.deleted
+        self.sealed_deleted[d] = True
+
+    def delete_growing(self, g):
+        self.pages.mark_deleted_growing(g)
+        self.growing_deleted[g] = True
+
+    # ---- what a filter built from the rows holds
+
+    def alive(self):
+        """keep predicate 0: (sealed, growing) bool arrays, not deleted"""
+        return ~self.sealed_deleted, ~np.array(self.growing_deleted, bool)
+
+    @staticmethod
+    def tenant_bits(rows):
+        return np.array([p[2] % 3 == 0 for p, _, _ in rows], bool)
+
+    def tenant(self):
+        """keep predicate 1: payload[2] % 3 == 0 and alive"""
+        s, g = self.alive()
+        return s & self.tenant_bits(self.sealed), g & self.tenant_bits(self.growing)
+
+    def keep_of(self, selector):
+        return None if selector == NONE else (self.alive(), self.tenant())[selector]
+
+    def growing_csr(self, lo=0, hi=None):
+        """the growing rows lo .. hi - 1 (default: all) as the arrays vbm25_growing_from_pages gives"""
+        L = orc.lib()
+        rows, deleted = self.growing[lo:hi], self.growing_deleted[lo:hi]
+        counts = [len(kt) for _, kt, _ in rows]
+        keys = b"".join(key for _, kt, _ in rows for key in sorted(kt))
+        return dict(g_start=np.r_[0, np.cumsum(counts)].astype(np.uint64), g_key=np.frombuffer(keys, np.uint8).copy(),
+                    g_tf=np.array([kt[key] for _, kt, _ in rows for key in sorted(kt)], np.uint32),
+                    g_fieldnorm=np.array([L.orc_length_to_fieldnorm(ln) for _, _, ln in rows], np.uint8),
+                    g_payload=np.array([p for p, _, _ in rows], np.uint16).reshape(-1, 3),
+                    g_deleted=np.array(deleted, np.uint8))
+
+    def counts(self):
+        """(sealed rows, deleted ones, growing rows, deleted ones, growing elements): vbm25_device_vacuum_info's five"""
+        return (len(self.sealed), int(self.sealed_deleted.sum()), len(self.growing), int(sum(self.growing_deleted)),
+                sum(len(kt) for _, kt, _ in self.growing))
+
+    # ---- SELECT
+
+    def _evaluate(self, t, fieldnorm, tf):
+        at = (t, fieldnorm, tf)
+        if at not in self._eval:
+            o = self.oix
+            self._eval[at] = orc.lib().orc_cache_evaluate(o.n_docs, int(o.arrays["term_df"][t]), o.k1, o.b, o.sum_len / o.n_docs,
+                                                          fieldnorm, tf)
+        return self._eval[at]
+
+    def select(self, query_keys, k, keep=None, count=True):
+        """the first k records (orc.HIT_DTYPE) of the table's ranking for the query; keep: None (every sealed row, deleted ones
+        included; every live growing row) or (sealed, growing) bool arrays"""
+        out = np.zeros(0, orc.HIT_DTYPE)
+        if self.oix.n_docs == 0:   # no statistics: nothing scores
+            return self._counted(out, False, False, count)
+        L = orc.lib()
+        qkeys = [key for key in sorted(set(query_keys)) if key in self.rank]   # unknown keys are ignored (search.rs:59-61)
+        sealed = self.oix.search_brute([self.rank[key] for key in qkeys], MAX_K)
+        assert len(sealed) < MAX_K, "the brute-force ranking was cut"
+        if keep is not None:
+            sealed = sealed[keep[0][sealed["doc_id"]]]
+        acc = {}
+        for key in qkeys:   # ascending keys: each row's sum runs in key order
+            for g, tf in self.ginv.get(key, ()):
+                if self.growing_deleted[g] or (keep is not None and not keep[1][g]):
+                    continue
+                fn = L.orc_length_to_fieldnorm(self.growing[g][2])
+                acc[g] = acc.get(g, 0.0) + self._evaluate(self.rank[key], fn, tf)
+        grow = sorted((-s, g) for g, s in acc.items() if s > 0)
+        merged, i, j = [], 0, 0
+        while len(merged) < k and (i < len(sealed) or j < len(grow)):
+            if j == len(grow) or (i < len(sealed) and sealed["score"][i] >= -grow[j][0]):   # sealed first on equal scores
+                merged.append((float(sealed["score"][i]), int(sealed["doc_id"][i]), tuple(sealed["payload"][i])))
+                i += 1
+            else:
+                g = grow[j][1]
+                merged.append((-grow[j][0], NONE - g, self.growing[g][0]))
+                j += 1
+        out = np.zeros(len(merged), orc.HIT_DTYPE)
+        for r, (s, d, p) in enumerate(merged):
+            out[r] = (s, d, p)
+        n_sealed = len(self.sealed)
+        is_g = out["doc_id"] >= n_sealed
+        tie = bool(np.any((out["score"][1:] == out["score"][:-1]) & (is_g[1:] != is_g[:-1])))
+        shown = keep is None and bool(self.sealed_deleted[out["doc_id"][~is_g]].any())
+        return self._counted(out, tie, shown, count, both=bool(is_g.any() and (~is_g).any()))
+
+    def _counted(self, out, tie, shown, count, both=False):
+        if count:
+            s = self.stats
+            s["selects"] += 1
+            s["both"] += both
+            s["nothing"] += len(out) == 0
+            s["deleted_shown"] += shown
+            s["mixed_ties"] += tie
+        return out
+
+    # ---- VACUUM
+
+    def vacuum(self):
+        """compacts the table; returns the relabel array: old sealed ids, then old growing indices -> new id or 0xFFFFFFFF"""
+        rows, relabel = [], []
+        for d, (p, kt, _) in enumerate(self.sealed):
+            relabel.append(NONE if self.sealed_deleted[d] else len(rows))
+            if not self.sealed_deleted[d]:
+                rows.append((p, kt, len(kt)))   # maintain.rs:344-362: one per posting
+        for g, row in enumerate(self.growing):
+            relabel.append(NONE if self.growing_deleted[g] else len(rows))
+            if not self.growing_deleted[g]:
+                rows.append(row)
+        new_keys = {key for g, (_, kt, _) in enumerate(self.growing) if not self.growing_deleted[g] for key in kt if key not in self.rank}
+        self.vacuums.append((int(self.sealed_deleted.sum()), int(sum(self.growing_deleted)), len(new_keys)))
+        self._seal(rows)
+        return np.array(relabel, np.uint32)
+
+    # ---- the operation sequence
+
+    def epoch_k(self):
+        """the k of the front ends that are created once per epoch (the time between two VACUUMs): every k of KS in turn"""
+        return KS[len(self.vacuums) % len(KS)]
+
+    def ops(self, seed, n, universe=None):
+        """n operations drawn from the reference's mix (tests/fuzz: 2 INSERT : 4 SELECT : 3 DELETE : 1 VACUUM) against the table's
+        state at the time each is drawn (the consumer applies an operation before it asks for the next), a ("reopen",) in front of
+        every 10th:
+          ("insert", [(payload, {key: tf})])      1, 4 or 16 rows, to be inserted one by one (with one row per INSERT the growing
+                                                  segment of this mix holds two rows on average and few selects see it): each of
+                                                  1, 3, 30 or 250 distinct keys of `universe` (default: the vocabulary now), tf 1..8;
+                                                  with probability 0.2 one of them is a key no row has held
+          ("delete", "sealed" | "growing", ids)   1, 3 or 40 rows of one segment, already deleted ones included
+          ("select", queries, selectors, k, front end)   8 queries of 1 to 6 keys from the sealed vocabulary and the last inserts' keys,
+                                                  a third of them with a key no row holds as well; selectors cycle NO_FILTER, 0, 1;
+                                                  front ends 0, 1, 2 in rotation: 0 takes a k drawn from KS, the others epoch_k()
+          ("vacuum",)"""
+        rng = np.random.default_rng(seed)
+        universe = list(self.vocab if universe is None else universe)
+        recent, serial, n_selects = [], 0, 0
+        for i in range(n):
+            if i and i % 10 == 0:
+                yield ("reopen",)
+            kind = int(rng.choice(4, p=[0.2, 0.4, 0.3, 0.1]))
+            if kind == 0:
+                docs = []
+                for _ in range(int(rng.choice(INSERT_ROWS))):
+                    nk = int(rng.choice(INSERT_KEYS))
+                    keys = [universe[j] for j in rng.choice(len(universe), min(nk, len(universe)), replace=False)]
+                    if rng.random() < 0.2:
+                        keys[0] = new_key(seed * 1000 + serial)
+                        serial += 1
+                    kt = {key: int(tf) for key, tf in zip(keys, rng.integers(1, 9, len(keys)))}
+                    recent = (recent + [list(kt)])[-8:]
+                    docs.append((tuple(int(x) for x in rng.integers(0, 65536, 3)), kt))
+                yield ("insert", docs)
+            elif kind == 1:
+                queries = []
+                for _ in range(8):
+                    pool_r = [key for keys in recent for key in keys]
+                    q = []
+                    for _ in range(int(rng.integers(1, 7))):
+                        pool = pool_r if pool_r and (rng.random() < 0.5 or not self.vocab) else self.vocab
+                        if pool:
+                            q.append(pool[int(rng.integers(len(pool)))])
+                    if not q or rng.random() < 1 / 3:
+                        q.append(NO_ROW_KEY)
+                    queries.append(sorted(set(q)))
+                selectors = [(NONE, 0, 1)[(q + n_selects) % 3] for q in range(8)]
+                k, front = int(rng.choice(KS)), n_selects % 3
+                yield ("select", queries, selectors, k if front == 0 else self.epoch_k(), front)
+                n_selects += 1
+            elif kind == 2:
+                where = "growing" if self.growing and rng.random() < 0.4 else "sealed"
+                n_rows = len(self.growing) if where == "growing" else len(self.sealed)
+                many = int(rng.choice((1, 3, 40)))
+                yield ("delete", where, [int(x) for x in rng.integers(0, n_rows, many)] if n_rows else [])
+            else:
+                yield ("vacuum",)
