@@ -72,6 +72,20 @@ int main(int argc, char **argv) {
     vbm25::Index ix(desc, 0);
     for (const vbm25::Hit &h : ix.search(5, q))
         std::printf("doc %u score %.17g ctid (%u,%u,%u)\n", h.doc_id, h.score, h.payload[0], h.payload[1], h.payload[2]);
+    {   // the same query from its lexemes: interned, sorted, de-duplicated and looked up on the device (vbm25_resolver), then searched
+        vbm25::LexemeBatch b;
+        for (const char *t : toks) b.add(t);
+        b.end_query();
+        vbm25::Resolver res(ix, nullptr, 1, 1, 4, 16);
+        res.submit(b);
+        std::vector<uint32_t> term_ids, q_off;
+        res.collect(term_ids, q_off);
+        std::printf("lexeme query: %u lexemes -> %zu term ids\n", b.lexemes(), term_ids.size());
+        std::vector<vbm25::Hit> hits;
+        std::vector<uint32_t> n_hits;
+        vbm25::search_batch_lexemes(ix, nullptr, b, 5, hits, n_hits);
+        for (uint32_t i = 0; i < n_hits[0]; ++i) std::printf("from lexemes: doc %u score %.17g\n", hits[i].doc_id, hits[i].score);
+    }
     vbm25_segment_free(seg);
     return 0;
 }

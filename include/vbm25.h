@@ -490,6 +490,50 @@ int vbm25_stream_submit_filtered(vbm25_stream *, const uint32_t *q_filter, const
                                  uint32_t nq);
 int vbm25_stream_in_flight(const vbm25_stream *);
 
+/* The Query step on the device (csrc/resolve.hip): cast_tsvector_to_query (src/datatype/tsvector.rs:96-105: intern every lexeme, sort,
+ * dedup) followed by the key lookup of bm25::search (search.rs:59-61: keys the index lacks are dropped), for a batch of queries.
+ * Lexemes or 16-byte keys in; out comes what every search entry point takes: per query the ascending term ids, as a CSR
+ * term_ids / q_off with q_off[0] == 0.  The vocabulary is ascending by key, so the ascending distinct found ids ARE the sorted,
+ * de-duplicated, known keys -- array for array what vbm25_intern + sort + dedup + vbm25_lookup_terms + drop gives on the host.
+ *
+ * A resolver is a ring like vbm25_stream: `depth` (1 .. 16) slots, each with pinned input and output, one HIP stream of its own; no
+ * call synchronises the device or touches the index's batches.  It holds the vocabulary's keys in HBM (16 bytes a term, uploaded once
+ * at create; vbm25_index_device_bytes does not count them, vbm25_resolver_device_bytes does).  It is valid for ITS index: after a
+ * compaction the caller makes a new one.  On several GPUs a resolver on any replica serves all of them, because term ids are the same
+ * on every replica.  One host thread drives a resolver (two threads: two resolvers, also on one index).
+ *   seed32         MetaTuple.seed (vbm25_pages_seed), copied.  NULL: lexemes that need the hash (16 bytes or more, or a NUL inside) are
+ *                  refused at submit, with the words of vbm25_intern's error.
+ *   capacities     a batch has at most max_queries queries, max_lexemes lexemes (or keys) and max_bytes lexeme bytes.
+ *   submit_lexemes query q = lexemes q_lex[q] .. q_lex[q+1]; lexeme i = bytes[lex_off[i] .. lex_off[i+1]), any length, any alignment.
+ *                  Copies the arrays into the slot's pinned block and enqueues; returns at once.
+ *   submit_keys    the same from interned keys (16 bytes each): query q = keys q_key[q] .. q_key[q+1].
+ *   collect        waits for the OLDEST batch in flight: q_off (nq + 1 entries) and term_ids (q_off[nq] ids; the caller provides room
+ *                  for as many as it submitted lexemes); *nq_out = its number of queries.  First in, first out.
+ * Refused with VBM25_ERR_INVALID and a message, before anything is enqueued and with the ring unchanged: NULL arguments, q_lex[0] != 0,
+ * offsets that are not monotone, counts or bytes over capacity, depth outside 1 .. 16, a lexeme that needs the hash without a seed, a
+ * submit on a full ring, a collect on an empty one.  A query may resolve to more ids than a scan takes; the resolver does not judge
+ * that, the search entry point refuses it as it always did.
+ * Every query of a batch at most 64 lexemes long: one wave a query ranks the ids by cross-lane compares; otherwise a radix sort of
+ * (query, id) takes any length.  Both give identical bytes.
+ *   vbm25_intern_batch_device   the intern step alone, synchronous, on `device`: keys16 = n_lex x 16 bytes, byte for byte
+ *                               vbm25_intern's.  For the documents a shim interns for vbm25_device_growing_append.
+ *   vbm25_search_batch_lexemes  resolve, then vbm25_search_batch: bm25::search from the lexemes of tsvectors in one synchronous call.  It
+ *                               makes and frees a resolver per call; a caller with many batches keeps one and pipelines it in front of
+ *                               vbm25_stream_submit. */
+typedef struct vbm25_resolver vbm25_resolver;
+int vbm25_resolver_create(vbm25_index *, const uint8_t *seed32, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes,
+                          uint64_t max_bytes, vbm25_resolver **out);
+void vbm25_resolver_destroy(vbm25_resolver *);
+uint64_t vbm25_resolver_device_bytes(const vbm25_resolver *);
+int vbm25_resolver_submit_lexemes(vbm25_resolver *, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq);
+int vbm25_resolver_submit_keys(vbm25_resolver *, const uint8_t *keys16, const uint32_t *q_key, uint32_t nq);
+int vbm25_resolver_collect(vbm25_resolver *, uint32_t *term_ids, uint32_t *q_off, uint32_t *nq_out);
+int vbm25_resolver_in_flight(const vbm25_resolver *);
+int vbm25_intern_batch_device(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, uint32_t n_lex,
+                              uint8_t *keys16);
+int vbm25_search_batch_lexemes(vbm25_index *, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off,
+                               const uint32_t *q_lex, uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits);
+
 /* bm25::evaluate (evaluate.rs:22-74) for n_docs documents against ONE query on the device: the seq-scan
  * form of `tsvector <&> bm25query` (src/index/operators.rs:22-55), batched.  Everything is in term-id space
  * (vbm25_lookup_terms): q_terms = the query's ids, strictly ascending; ids >= the index's term count (tokens

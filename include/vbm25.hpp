@@ -117,6 +117,77 @@ class Index {
     vbm25_index *h_ = nullptr;
 };
 
+// Lexemes back to back, as the resolver takes them: lexeme i = bytes[lex_off[i] .. lex_off[i + 1]), query q = lexemes
+// q_lex[q] .. q_lex[q + 1].
+struct LexemeBatch {
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> lex_off{0};
+    std::vector<uint32_t> q_lex{0};
+    void add(std::string_view lexeme) {  // to the query that end_query() closes next
+        bytes.insert(bytes.end(), lexeme.begin(), lexeme.end());
+        lex_off.push_back(bytes.size());
+    }
+    void end_query() { q_lex.push_back(uint32_t(lex_off.size() - 1)); }
+    uint32_t queries() const { return uint32_t(q_lex.size() - 1); }
+    uint32_t lexemes() const { return uint32_t(lex_off.size() - 1); }
+};
+
+// The Query step on the device (vbm25_resolver): cast_tsvector_to_query + the key lookup of bm25::search for a batch -- lexemes or
+// keys in, per query the ascending term ids out, the CSR every search entry point takes.  A ring of `depth` slots, first in first
+// out; valid for its index only (on several GPUs a resolver on any replica serves all of them).
+class Resolver {
+  public:
+    Resolver(const Index &index, const Seed *seed, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes) {
+        check(vbm25_resolver_create(index.handle(), seed ? seed->data() : nullptr, depth, max_queries, max_lexemes, max_bytes, &h_));
+    }
+    ~Resolver() { vbm25_resolver_destroy(h_); }
+    Resolver(const Resolver &) = delete;
+    Resolver &operator=(const Resolver &) = delete;
+
+    void submit(const LexemeBatch &b) {
+        check(vbm25_resolver_submit_lexemes(h_, b.bytes.data(), b.lex_off.data(), b.q_lex.data(), b.queries()));
+        shape_.push_back({b.queries(), b.lexemes()});
+    }
+    void submit_keys(const std::vector<Key> &keys, const std::vector<uint32_t> &q_key) {
+        check(vbm25_resolver_submit_keys(h_, keys.empty() ? nullptr : keys[0].data(), q_key.data(), uint32_t(q_key.size() - 1)));
+        shape_.push_back({uint32_t(q_key.size() - 1), uint32_t(keys.size())});
+    }
+    // the oldest batch in flight (nothing in flight: the library's error)
+    void collect(std::vector<uint32_t> &term_ids, std::vector<uint32_t> &q_off) {
+        const std::array<uint32_t, 2> shape = shape_.empty() ? std::array<uint32_t, 2>{0, 0} : shape_.front();
+        q_off.assign(size_t(shape[0]) + 1, 0);
+        term_ids.assign(size_t(shape[1]) + 1, 0);
+        uint32_t nq = 0;
+        check(vbm25_resolver_collect(h_, term_ids.data(), q_off.data(), &nq));
+        shape_.erase(shape_.begin());
+        term_ids.resize(q_off[nq]);
+    }
+    int in_flight() const { return vbm25_resolver_in_flight(h_); }
+    uint64_t device_bytes() const { return vbm25_resolver_device_bytes(h_); }
+    vbm25_resolver *handle() const { return h_; }
+
+  private:
+    vbm25_resolver *h_ = nullptr;
+    std::vector<std::array<uint32_t, 2>> shape_;  // per batch in flight: queries, lexemes
+};
+
+// bm25::search from the lexemes of tsvectors in one call (vbm25_search_batch_lexemes): hits is nq x k, n_hits nq
+inline void search_batch_lexemes(const Index &index, const Seed *seed, const LexemeBatch &b, size_t k, std::vector<Hit> &hits,
+                                 std::vector<uint32_t> &n_hits) {
+    hits.resize(size_t(b.queries()) * k);
+    n_hits.resize(b.queries());
+    check(vbm25_search_batch_lexemes(index.handle(), seed ? seed->data() : nullptr, b.bytes.data(), b.lex_off.data(), b.q_lex.data(), b.queries(),
+                                     uint32_t(k), hits.data(), n_hits.data()));
+}
+
+// intern for n lexemes at once on `device` (vbm25_intern_batch_device): byte for byte intern()'s keys
+inline std::vector<Key> intern_batch(int device, const Seed *seed, const LexemeBatch &b) {
+    std::vector<Key> keys(b.lexemes());
+    check(vbm25_intern_batch_device(device, seed ? seed->data() : nullptr, b.bytes.data(), b.lex_off.data(), b.lexemes(),
+                                    keys.empty() ? nullptr : keys[0].data()));
+    return keys;
+}
+
 class DeviceGrowing;
 class DeviceVacuum;
 

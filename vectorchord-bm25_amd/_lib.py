@@ -152,6 +152,15 @@ ABI = {
     "vbm25_stream_set_growing": (i32, [vp, vp]),
     "vbm25_stream_set_filter": (i32, [vp, vp]),
     "vbm25_stream_submit_filtered": (i32, [vp, vp, vp, vp, u32]),
+    "vbm25_resolver_create": (i32, [vp, vp, u32, u32, u32, u64, vp]),
+    "vbm25_resolver_destroy": (None, [vp]),
+    "vbm25_resolver_device_bytes": (u64, [vp]),
+    "vbm25_resolver_submit_lexemes": (i32, [vp, vp, vp, vp, u32]),
+    "vbm25_resolver_submit_keys": (i32, [vp, vp, vp, u32]),
+    "vbm25_resolver_collect": (i32, [vp, vp, vp, vp]),
+    "vbm25_resolver_in_flight": (i32, [vp]),
+    "vbm25_intern_batch_device": (i32, [i32, vp, vp, vp, u32, vp]),
+    "vbm25_search_batch_lexemes": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
 }
 
 

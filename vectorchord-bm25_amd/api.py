@@ -1122,6 +1122,111 @@ def search_batch(index, term_ids, q_off, k):
     return hits, n_hits
 
 
+def pack_lexemes(queries):
+    """A list of queries, each a list of `bytes` lexemes -> the prepacked form (bytes uint8, lex_off uint64, q_lex uint32) that
+    Resolver.submit and search_batch_lexemes also take: the lexemes back to back, lexeme i = bytes[lex_off[i]:lex_off[i+1]], query q =
+    lexemes q_lex[q] .. q_lex[q+1]."""
+    flat = [bytes(t) for q in queries for t in q]
+    lex_off = np.zeros(len(flat) + 1, dtype=np.uint64)
+    if flat:
+        np.cumsum([len(t) for t in flat], out=lex_off[1:])
+    q_lex = np.zeros(len(queries) + 1, dtype=np.uint32)
+    if len(queries):
+        np.cumsum([len(q) for q in queries], out=q_lex[1:])
+    return np.frombuffer(b"".join(flat), dtype=np.uint8), lex_off, q_lex
+
+
+def _packed(queries):
+    if isinstance(queries, tuple) and len(queries) == 3:
+        data, lex_off, q_lex = queries
+        return (np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(lex_off, dtype=np.uint64),
+                np.ascontiguousarray(q_lex, dtype=np.uint32))
+    return pack_lexemes(queries)
+
+
+def _seed_arg(seed):
+    if seed is not None and len(seed) != 32:
+        raise ValueError("the seed is 32 bytes")
+    return bytes(seed) if seed is not None else None
+
+
+def intern_batch(lexemes, seed=None, device=0):
+    """vbm25_intern_batch_device: intern (vector.rs:19-35) of a list of `bytes` lexemes on the device -> uint8 [n, 16], byte for byte
+    what `intern` gives for each.  `lexemes` may also be the prepacked (bytes, lex_off)."""
+    if isinstance(lexemes, tuple):
+        data, lex_off = np.ascontiguousarray(lexemes[0], dtype=np.uint8), np.ascontiguousarray(lexemes[1], dtype=np.uint64)
+    else:
+        data, lex_off, _ = pack_lexemes([lexemes])
+    n = len(lex_off) - 1
+    keys = np.zeros((n, WIDTH), dtype=np.uint8)
+    check(lib().vbm25_intern_batch_device(device, _seed_arg(seed), _p(data), lex_off.ctypes.data, n, _p(keys)))
+    return keys
+
+
+class Resolver:
+    """The Query step on the device (vbm25_resolver_*): lexemes or keys in, per query the ascending term ids out, as the CSR
+    (term_ids, q_off) every search entry point takes.  A ring of `depth` slots, first in first out; valid for its index only."""
+
+    def __init__(self, index, depth, max_queries, max_lexemes, max_bytes, seed=None):
+        self.index = index
+        self.h = C.c_void_p()
+        check(lib().vbm25_resolver_create(index.h, _seed_arg(seed), depth, max_queries, max_lexemes, max_bytes, C.byref(self.h)))
+        self._n = []  # per batch in flight: (queries, lexemes)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().vbm25_resolver_destroy(self.h)
+        except Exception:
+            pass
+
+    @property
+    def device_bytes(self):
+        return int(lib().vbm25_resolver_device_bytes(self.h))
+
+    def submit(self, queries):
+        """vbm25_resolver_submit_lexemes: `queries` is a list of lists of `bytes`, or the prepacked (bytes, lex_off, q_lex) of
+        pack_lexemes for callers that care about the host's time."""
+        data, lex_off, q_lex = _packed(queries)
+        nq = len(q_lex) - 1
+        check(lib().vbm25_resolver_submit_lexemes(self.h, _p(data), lex_off.ctypes.data, q_lex.ctypes.data, nq))
+        self._n.append((nq, len(lex_off) - 1))  # (only a batch the library accepted is in the ring)
+
+    def submit_keys(self, keys, q_key):
+        """vbm25_resolver_submit_keys: keys = uint8 [n, 16] (or n x 16 bytes), query q = keys q_key[q] .. q_key[q+1]."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1)
+        q_key = np.ascontiguousarray(q_key, dtype=np.uint32)
+        nq = len(q_key) - 1
+        check(lib().vbm25_resolver_submit_keys(self.h, _p(keys), q_key.ctypes.data, nq))
+        self._n.append((nq, len(keys) // WIDTH))
+
+    def collect(self):
+        """The oldest batch in flight: (term_ids, q_off)."""
+        nq, n_lex = self._n[0] if self._n else (0, 0)  # (an empty ring: the library's own error)
+        term_ids, q_off = np.zeros(max(n_lex, 1), dtype=np.uint32), np.zeros(nq + 1, dtype=np.uint32)
+        got = C.c_uint32()
+        check(lib().vbm25_resolver_collect(self.h, term_ids.ctypes.data, q_off.ctypes.data, C.byref(got)))
+        self._n.pop(0)
+        assert got.value == nq
+        return term_ids[:q_off[nq]], q_off
+
+    @property
+    def in_flight(self):
+        return int(lib().vbm25_resolver_in_flight(self.h))
+
+
+def search_batch_lexemes(index, queries, k, seed=None):
+    """vbm25_search_batch_lexemes: bm25::search for nq tsvectors' lexemes (list of lists of `bytes`, or prepacked) in one call ->
+    (hits[nq,k], n_hits[nq])."""
+    data, lex_off, q_lex = _packed(queries)
+    nq = len(q_lex) - 1
+    hits = np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE)
+    n_hits = np.zeros(nq, dtype=np.uint32)
+    check(lib().vbm25_search_batch_lexemes(index.h, _seed_arg(seed), _p(data), lex_off.ctypes.data, q_lex.ctypes.data, nq, k,
+                                           hits.ctypes.data, n_hits.ctypes.data))
+    return hits, n_hits
+
+
 def search(index, k, query):
     """bm25::search(&index, k, &query, |_| true) (search.rs:28-36) for one Query:
     best-first list of (score, payload) with the doc id alongside."""

@@ -1,0 +1,530 @@
+// resolve.hip -- the query resolver: cast_tsvector_to_query (src/datatype/tsvector.rs:96-105: intern every lexeme, sort, dedup) and
+// the key lookup of bm25::search (address_tokens::read, search.rs:59-61: keys the index lacks are dropped) on the device, batched.
+// Lexemes or 16-byte keys in, ascending term ids out, as a CSR term_ids / q_off in pinned host memory -- the form every search entry
+// point takes.  resolve_lane.h holds the per-lexeme and per-key functions; the kernels here are loops over them.
+//
+// Why sorting ids is the reference's sort: the vocabulary is ascending by key (memcmp order) and term id = position in it.  Two keys
+// that the index holds therefore compare as their ids do, equal keys have equal ids, and a key the index lacks has no id.  Sorting the
+// FOUND ids ascending and dropping repeats and misses gives exactly the ids of (sort keys, dedup keys, drop unknown keys), in the same
+// order -- without ever sorting 16-byte keys.
+//
+//   per batch, all on the resolver's own stream (nothing synchronises the device or touches the index's batches):
+//     upload            the slot's pinned block (q_lex | lex_off | bytes, or q_key | keys) in ONE copy into the device staging
+//     intern_kernel     one lane a lexeme: intern_lane -> key -> lookup_lane -> id            (lexeme entry)
+//     lookup_kernel     one lane a key: lookup_lane -> id                                     (keys entry)
+//     step (c), every query of the batch <= 64 lexemes  -- the wave path:
+//       pack_wave_kernel   one wave a query, one lane a lexeme: duplicates (an equal id in a lower lane) and misses leave by ballot, a
+//                          lane's rank is the number of surviving lower ids (cross-lane compares, no LDS, no sort); the survivors go
+//                          to tmp[q_lex[q] + rank] and the query's count to counts[q]
+//       (scan)             exclusive sum of the counts -> q_off (hipcub)
+//       gather_kernel      one wave a query: tmp -> term_ids[q_off[q] ..) and q_off, both in pinned host memory
+//     step (c), otherwise -- the general path, any query length up to the capacity:
+//       sortkey_kernel     one lane a lexeme: (query << 32 | id), the query by bisection of q_lex
+//       (radix sort)       hipcub, the bits of the id and of the query number only; a query keeps its range q_lex[q] .. q_lex[q + 1]
+//       flag_kernel        first of its run and found -> 1
+//       (scan)             exclusive sum of the flags -> position
+//       emit_kernel        term_ids[position] and q_off[q] = position[q_lex[q]], both in pinned host memory
+//   Both paths write identical bytes; the switch is the longest query of the batch, which submit knows from validating q_lex.
+//   The chaining-value stack of lexemes over 1024 bytes lives in LDS, sized per launch from the batch's longest lexeme (0 bytes when
+//   every lexeme fits a chunk): no kernel here has scratch memory.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "vbm25_internal.h"
+#include "resolve_lane.h"
+
+namespace {
+
+using namespace vbm25;
+using namespace vbm25::rsv;
+
+#define RS_TRY(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+struct DBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    ~DBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) {
+        bytes = n ? n : 16;
+        return hipMalloc(&p, bytes);
+    }
+    template <class T>
+    T *as() const {
+        return static_cast<T *>(p);
+    }
+};
+
+constexpr uint32_t INTERN_THREADS = 64;   // one wave a block: the LDS stack is 32 bytes a level a lane
+constexpr uint32_t INTERN_GRID = 1024;    // one wave a SIMD of the 256 CUs; more lexemes than 65536 stride the grid
+constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
+constexpr uint32_t MAX_LEVELS = 32;       // 64 KiB of LDS: lexemes up to 2^32 chunks
+constexpr uint32_t WAVE_QUERY = 64;       // the wave path's longest query
+constexpr const char *NEEDS_SEED = "a lexeme of 16 bytes or more needs the index's seed (Meta tuple)";
+
+uint32_t grid_for(uint64_t units, uint32_t per_block) {
+    return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block));
+}
+size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+struct Seed {
+    uint32_t w[8];
+};
+
+// keys_out and ids may each be NULL.  The pool is 4-byte aligned and ends on a multiple of 4 (WordLoad).
+__global__ void __launch_bounds__(INTERN_THREADS) intern_kernel(Seed seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex,
+                                                                const Key *vocab, uint32_t n_terms, Key *keys_out, uint32_t *ids) {
+    extern __shared__ uint32_t cv_stack[];
+    const WordLoad ld{pool};
+    for (uint32_t i = blockIdx.x * INTERN_THREADS + threadIdx.x; i < n_lex; i += gridDim.x * INTERN_THREADS) {
+        const uint64_t begin = lex_off[i];
+        const Key key = intern_lane(seed.w, ld, begin, lex_off[i + 1] - begin, cv_stack + threadIdx.x, INTERN_THREADS);
+        if (keys_out) keys_out[i] = key;
+        if (ids) ids[i] = lookup_lane(vocab, n_terms, key);
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) lookup_kernel(const Key *keys, uint32_t n, const Key *vocab, uint32_t n_terms, uint32_t *ids) {
+    for (uint32_t i = blockIdx.x * WG_THREADS + threadIdx.x; i < n; i += gridDim.x * WG_THREADS) ids[i] = lookup_lane(vocab, n_terms, keys[i]);
+}
+
+// the wave path; every query has at most 64 lexemes.  counts has nq + 1 entries, the last one 0 (the scan's total lands there).
+__global__ void __launch_bounds__(WG_THREADS) pack_wave_kernel(const uint32_t *ids, const uint32_t *q_lex, uint32_t nq, uint32_t *tmp,
+                                                               uint32_t *counts) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[nq] = 0;
+    for (uint32_t q = wave; q < nq; q += n_waves) {
+        const uint32_t b = q_lex[q], n = q_lex[q + 1] - b;
+        const uint32_t id = lane < n ? ids[b + lane] : NOT_FOUND;
+        bool dup = false;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t v = __shfl(id, j);
+            dup |= v == id && j < lane;
+        }
+        const bool keep = id != NOT_FOUND && !dup;
+        const unsigned long long kept = __ballot(keep);
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t v = __shfl(id, j);
+            rank += ((kept >> j) & 1ull) && v < id;
+        }
+        if (keep) tmp[b + rank] = id;
+        if (lane == 0) counts[q] = __popcll(kept);
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) gather_kernel(const uint32_t *tmp, const uint32_t *q_lex, const uint32_t *q_off, uint32_t nq,
+                                                            uint32_t *out_ids, uint32_t *out_q_off) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG_THREADS + threadIdx.x) >> 6, n_waves = (gridDim.x * WG_THREADS) >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) out_q_off[nq] = q_off[nq];
+    for (uint32_t q = wave; q < nq; q += n_waves) {
+        const uint32_t o = q_off[q], c = q_off[q + 1] - o;
+        if (lane < c) out_ids[o + lane] = tmp[q_lex[q] + lane];
+        if (lane == 0) out_q_off[q] = o;
+    }
+}
+
+// the general path
+__global__ void __launch_bounds__(WG_THREADS) sortkey_kernel(const uint32_t *ids, const uint32_t *q_lex, uint32_t nq, uint32_t n_lex,
+                                                             unsigned long long *keys) {
+    for (uint32_t i = blockIdx.x * WG_THREADS + threadIdx.x; i < n_lex; i += gridDim.x * WG_THREADS) {
+        uint32_t lo = 0, hi = nq;  // the last q with q_lex[q] <= i (empty queries in front of it share its start)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (q_lex[mid] <= i) lo = mid; else hi = mid;
+        }
+        keys[i] = (unsigned long long)lo << 32 | ids[i];
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) flag_kernel(const unsigned long long *sorted, uint32_t n_lex, uint32_t *flags) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) flags[n_lex] = 0;
+    for (uint32_t i = blockIdx.x * WG_THREADS + threadIdx.x; i < n_lex; i += gridDim.x * WG_THREADS) {
+        const unsigned long long k = sorted[i];
+        flags[i] = uint32_t(k) != NOT_FOUND && (i == 0 || sorted[i - 1] != k);
+    }
+}
+
+__global__ void __launch_bounds__(WG_THREADS) emit_kernel(const unsigned long long *sorted, const uint32_t *flags, const uint32_t *pos,
+                                                          const uint32_t *q_lex, uint32_t nq, uint32_t n_lex, uint32_t *out_ids,
+                                                          uint32_t *out_q_off) {
+    const uint32_t units = n_lex > nq + 1 ? n_lex : nq + 1;
+    for (uint32_t i = blockIdx.x * WG_THREADS + threadIdx.x; i < units; i += gridDim.x * WG_THREADS) {
+        if (i < n_lex && flags[i]) out_ids[pos[i]] = uint32_t(sorted[i]);
+        if (i <= nq) out_q_off[i] = pos[q_lex[i]];
+    }
+}
+
+void seed_words(const uint8_t *seed32, Seed *s) {
+    for (int i = 0; i < 8; ++i)
+        s->w[i] = seed32 ? uint32_t(seed32[4 * i]) | uint32_t(seed32[4 * i + 1]) << 8 | uint32_t(seed32[4 * i + 2]) << 16 | uint32_t(seed32[4 * i + 3]) << 24 : 0u;
+}
+
+// what a lexeme batch is, checked before anything is allocated or enqueued
+struct LexShape {
+    uint32_t n_lex = 0, longest_query = 0;
+    uint64_t n_bytes = 0, longest_lexeme = 0;
+};
+int check_offsets32(const uint32_t *q, uint32_t nq, const char *what, LexShape *s) {
+    if (q[0] != 0) return set_error(VBM25_ERR_INVALID, "%s[0] is %u, not 0", what, q[0]);
+    for (uint32_t i = 0; i < nq; ++i) {
+        if (q[i + 1] < q[i]) return set_error(VBM25_ERR_INVALID, "%s is not monotone at query %u", what, i);
+        s->longest_query = std::max(s->longest_query, q[i + 1] - q[i]);
+    }
+    s->n_lex = q[nq];
+    return VBM25_OK;
+}
+int check_lexemes(bool has_seed, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq, LexShape *s) {
+    if (!q_lex || !lex_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (int rc = check_offsets32(q_lex, nq, "q_lex", s)) return rc;
+    bool hashed = false;
+    for (uint32_t i = 0; i < s->n_lex; ++i) {
+        if (lex_off[i + 1] < lex_off[i]) return set_error(VBM25_ERR_INVALID, "lex_off is not monotone at lexeme %u", i);
+        const uint64_t len = lex_off[i + 1] - lex_off[i];
+        s->longest_lexeme = std::max(s->longest_lexeme, len);
+        hashed |= len >= 16;
+    }
+    s->n_bytes = lex_off[s->n_lex];
+    if (s->n_bytes && !bytes) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (stack_levels(s->longest_lexeme) > MAX_LEVELS) return set_error(VBM25_ERR_INVALID, "a lexeme of %llu bytes is over the resolver's limit", (unsigned long long)s->longest_lexeme);
+    if (!has_seed) {  // (every lexeme is short here or refused: a NUL anywhere in the lexemes' bytes is a NUL inside one of them)
+        if (hashed || (s->n_bytes > lex_off[0] && std::memchr(bytes + lex_off[0], 0, s->n_bytes - lex_off[0])))
+            return set_error(VBM25_ERR_INVALID, "%s", NEEDS_SEED);
+    }
+    return VBM25_OK;
+}
+
+int launch_intern(hipStream_t st, const Seed &seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex, uint64_t longest,
+                  const Key *vocab, uint32_t n_terms, Key *keys_out, uint32_t *ids) {
+    if (!n_lex) return VBM25_OK;
+    const size_t lds = size_t(stack_levels(longest)) * 8 * sizeof(uint32_t) * INTERN_THREADS;
+    intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS)), INTERN_THREADS, lds, st>>>(seed, pool, lex_off, n_lex, vocab, n_terms, keys_out, ids);
+    RS_TRY(hipGetLastError());
+    return VBM25_OK;
+}
+
+struct Slot {
+    uint8_t *in = nullptr;    // pinned: the staged block of one batch
+    uint32_t *out = nullptr;  // pinned: q_off (max_queries + 1) then term_ids (max_lexemes)
+    hipEvent_t start = nullptr, done = nullptr;
+    uint32_t nq = 0;
+};
+
+}  // namespace
+
+struct vbm25_resolver {
+    const vbm25_index *index = nullptr;
+    int device = 0;
+    uint32_t depth = 0, max_queries = 0, max_lexemes = 0, n_terms = 0;
+    uint64_t max_bytes = 0, device_bytes = 0;
+    bool has_seed = false;
+    Seed seed{};
+    hipStream_t stream = nullptr;
+    size_t in_capacity = 0, cub_bytes = 0;
+    DBuf vocab, in_dev, ids, tmp, counts, q_off, sort_a, sort_b, cub;
+    Slot slots[16];
+    uint32_t head = 0, count = 0;  // the oldest slot in flight; slots in flight
+    int last_collected = -1;
+};
+
+namespace {
+
+int use_device(int device) {
+    RS_TRY(hipSetDevice(device));
+    return VBM25_OK;
+}
+
+int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes,
+                    vbm25_resolver **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!ix) return set_error(VBM25_ERR_INVALID, "index is NULL");
+    if (depth < 1 || depth > 16) return set_error(VBM25_ERR_INVALID, "depth %u is outside 1 .. 16", depth);
+    if (!max_queries || !max_lexemes) return set_error(VBM25_ERR_INVALID, "max_queries or max_lexemes is 0");
+    if (max_queries >= (1u << 31) || max_lexemes >= (1u << 31)) return set_error(VBM25_ERR_INVALID, "max_queries or max_lexemes is 2^31 or more");
+    int device = 0;
+    uint32_t n_terms = 0;
+    const uint8_t *term_key = nullptr;
+    if (int rc = index_vocabulary(ix, &device, &n_terms, &term_key)) return rc;
+    if (int rc = use_device(device)) return rc;
+    struct Guard {
+        vbm25_resolver *r;
+        ~Guard() {
+            if (r) vbm25_resolver_destroy(r);
+        }
+    } guard{new vbm25_resolver};
+    vbm25_resolver *r = guard.r;
+    r->index = ix;
+    r->device = device;
+    r->depth = depth;
+    r->max_queries = max_queries;
+    r->max_lexemes = max_lexemes;
+    r->max_bytes = max_bytes;
+    r->n_terms = n_terms;
+    r->has_seed = seed32 != nullptr;
+    seed_words(seed32, &r->seed);
+    RS_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    // the staged block: q_lex | lex_off | bytes (rounded up to 4), or q_key | keys
+    const size_t head_bytes = align_up(align_up(4ull * (max_queries + 1), 8) + 8ull * (max_lexemes + 1), 16);
+    r->in_capacity = head_bytes + std::max<size_t>(align_up(max_bytes, 4), 16ull * max_lexemes);
+    const size_t n1 = size_t(max_lexemes) + 1;
+    size_t scan_q = 0, scan_l = 0, sort_l = 0;
+    RS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_q, (uint32_t *)nullptr, (uint32_t *)nullptr, int(max_queries + 1), r->stream));
+    RS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_l, (uint32_t *)nullptr, (uint32_t *)nullptr, int(n1), r->stream));
+    RS_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_l, (unsigned long long *)nullptr, (unsigned long long *)nullptr, int(max_lexemes), 0, 64,
+                                             r->stream));
+    r->cub_bytes = std::max(scan_q, std::max(scan_l, sort_l));
+    RS_TRY(r->vocab.alloc(16ull * n_terms));
+    RS_TRY(r->in_dev.alloc(r->in_capacity));
+    RS_TRY(r->ids.alloc(4 * n1));       // ids; the general path's flags
+    RS_TRY(r->tmp.alloc(4 * n1));       // the wave path's packed ids; the general path's positions
+    RS_TRY(r->counts.alloc(4ull * (max_queries + 1)));
+    RS_TRY(r->q_off.alloc(4ull * (max_queries + 1)));
+    RS_TRY(r->sort_a.alloc(8ull * max_lexemes));
+    RS_TRY(r->sort_b.alloc(8ull * max_lexemes + 4 * n1));  // the sorted keys, then the general path's flags
+    RS_TRY(r->cub.alloc(r->cub_bytes));
+    for (const DBuf *b : {&r->vocab, &r->in_dev, &r->ids, &r->tmp, &r->counts, &r->q_off, &r->sort_a, &r->sort_b, &r->cub}) r->device_bytes += b->bytes;
+    if (n_terms) RS_TRY(hipMemcpyAsync(r->vocab.p, term_key, 16ull * n_terms, hipMemcpyHostToDevice, r->stream));
+    for (uint32_t i = 0; i < depth; ++i) {
+        Slot &s = r->slots[i];
+        RS_TRY(hipHostMalloc((void **)&s.in, r->in_capacity, hipHostMallocDefault));
+        RS_TRY(hipHostMalloc((void **)&s.out, 4ull * (max_queries + 1) + 4ull * max_lexemes, hipHostMallocDefault));
+        RS_TRY(hipEventCreate(&s.start));
+        RS_TRY(hipEventCreate(&s.done));
+    }
+    RS_TRY(hipStreamSynchronize(r->stream));  // (the index's host keys are not read after create)
+    *out = r;
+    guard.r = nullptr;
+    return VBM25_OK;
+}
+
+// step (c) and the slot's completion, after the ids are in r->ids
+int enqueue_pack(vbm25_resolver *r, Slot &s, const uint32_t *q_lex_dev, uint32_t nq, uint32_t n_lex, uint32_t longest_query) {
+    hipStream_t st = r->stream;
+    uint32_t *out_q_off = s.out, *out_ids = s.out + (r->max_queries + 1);
+    if (longest_query <= WAVE_QUERY) {
+        pack_wave_kernel<<<grid_for(nq, WG_THREADS / 64), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, r->tmp.as<uint32_t>(),
+                                                                                r->counts.as<uint32_t>());
+        RS_TRY(hipGetLastError());
+        size_t tb = r->cub_bytes;
+        RS_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, r->counts.as<uint32_t>(), r->q_off.as<uint32_t>(), int(nq + 1), st));
+        gather_kernel<<<grid_for(nq, WG_THREADS / 64), WG_THREADS, 0, st>>>(r->tmp.as<uint32_t>(), q_lex_dev, r->q_off.as<uint32_t>(), nq, out_ids,
+                                                                             out_q_off);
+        RS_TRY(hipGetLastError());
+    } else {
+        unsigned long long *ka = r->sort_a.as<unsigned long long>(), *kb = r->sort_b.as<unsigned long long>();
+        uint32_t *flags = reinterpret_cast<uint32_t *>(kb + r->max_lexemes), *pos = r->tmp.as<uint32_t>();
+        sortkey_kernel<<<grid_for(n_lex, WG_THREADS), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, n_lex, ka);
+        RS_TRY(hipGetLastError());
+        int q_bits = 0;
+        while (q_bits < 32 && (uint64_t(nq) >> q_bits)) ++q_bits;
+        size_t tb = r->cub_bytes;
+        RS_TRY(hipcub::DeviceRadixSort::SortKeys(r->cub.p, tb, ka, kb, int(n_lex), 0, 32 + q_bits, st));
+        flag_kernel<<<grid_for(n_lex, WG_THREADS), WG_THREADS, 0, st>>>(kb, n_lex, flags);
+        RS_TRY(hipGetLastError());
+        tb = r->cub_bytes;
+        RS_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, flags, pos, int(n_lex + 1), st));
+        emit_kernel<<<grid_for(std::max(n_lex, nq + 1), WG_THREADS), WG_THREADS, 0, st>>>(kb, flags, pos, q_lex_dev, nq, n_lex, out_ids, out_q_off);
+        RS_TRY(hipGetLastError());
+    }
+    RS_TRY(hipEventRecord(s.done, st));
+    return VBM25_OK;
+}
+
+int submit_common(vbm25_resolver *r, uint32_t nq) {
+    if (r->count == r->depth) return set_error(VBM25_ERR_INVALID, "the resolver's %u slots are all in flight: collect first", r->depth);
+    if (nq > r->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the resolver's max_queries %u", nq, r->max_queries);
+    return VBM25_OK;
+}
+
+int resolver_submit_lexemes(vbm25_resolver *r, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq) {
+    if (!r) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    LexShape sh;
+    if (int rc = check_lexemes(r->has_seed, bytes, lex_off, q_lex, nq, &sh)) return rc;
+    if (int rc = submit_common(r, nq)) return rc;
+    if (sh.n_lex > r->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u lexemes exceed the resolver's max_lexemes %u", sh.n_lex, r->max_lexemes);
+    if (sh.n_bytes > r->max_bytes) return set_error(VBM25_ERR_INVALID, "%llu bytes exceed the resolver's max_bytes %llu", (unsigned long long)sh.n_bytes, (unsigned long long)r->max_bytes);
+    if (int rc = use_device(r->device)) return rc;
+    Slot &s = r->slots[(r->head + r->count) % r->depth];
+    const size_t o_lex = align_up(4ull * (nq + 1), 8), o_bytes = align_up(o_lex + 8ull * (sh.n_lex + 1), 16), total = o_bytes + align_up(sh.n_bytes, 4);
+    std::memcpy(s.in, q_lex, 4ull * (nq + 1));
+    std::memcpy(s.in + o_lex, lex_off, 8ull * (sh.n_lex + 1));
+    if (sh.n_bytes) std::memcpy(s.in + o_bytes, bytes, sh.n_bytes);
+    uint8_t *d = r->in_dev.as<uint8_t>();
+    RS_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
+    RS_TRY(hipEventRecord(s.start, r->stream));
+    const uint32_t *q_lex_dev = reinterpret_cast<const uint32_t *>(d);
+    if (int rc = launch_intern(r->stream, r->seed, reinterpret_cast<const uint32_t *>(d + o_bytes), reinterpret_cast<const uint64_t *>(d + o_lex),
+                               sh.n_lex, sh.longest_lexeme, r->vocab.as<Key>(), r->n_terms, nullptr, r->ids.as<uint32_t>()))
+        return rc;
+    if (int rc = enqueue_pack(r, s, q_lex_dev, nq, sh.n_lex, sh.longest_query)) return rc;
+    s.nq = nq;
+    ++r->count;
+    return VBM25_OK;
+}
+
+int resolver_submit_keys(vbm25_resolver *r, const uint8_t *keys16, const uint32_t *q_key, uint32_t nq) {
+    if (!r || !q_key) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    LexShape sh;
+    if (int rc = check_offsets32(q_key, nq, "q_key", &sh)) return rc;
+    if (sh.n_lex && !keys16) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (int rc = submit_common(r, nq)) return rc;
+    if (sh.n_lex > r->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u keys exceed the resolver's max_lexemes %u", sh.n_lex, r->max_lexemes);
+    if (int rc = use_device(r->device)) return rc;
+    Slot &s = r->slots[(r->head + r->count) % r->depth];
+    const size_t o_keys = align_up(4ull * (nq + 1), 16), total = o_keys + 16ull * sh.n_lex;
+    std::memcpy(s.in, q_key, 4ull * (nq + 1));
+    if (sh.n_lex) std::memcpy(s.in + o_keys, keys16, 16ull * sh.n_lex);
+    uint8_t *d = r->in_dev.as<uint8_t>();
+    RS_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
+    RS_TRY(hipEventRecord(s.start, r->stream));
+    if (sh.n_lex) {
+        lookup_kernel<<<grid_for(sh.n_lex, WG_THREADS), WG_THREADS, 0, r->stream>>>(reinterpret_cast<const Key *>(d + o_keys), sh.n_lex, r->vocab.as<Key>(),
+                                                                                     r->n_terms, r->ids.as<uint32_t>());
+        RS_TRY(hipGetLastError());
+    }
+    if (int rc = enqueue_pack(r, s, reinterpret_cast<const uint32_t *>(d), nq, sh.n_lex, sh.longest_query)) return rc;
+    s.nq = nq;
+    ++r->count;
+    return VBM25_OK;
+}
+
+int resolver_collect(vbm25_resolver *r, uint32_t *term_ids, uint32_t *q_off, uint32_t *nq_out) {
+    if (!r || !q_off || !nq_out) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!r->count) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the resolver");
+    if (int rc = use_device(r->device)) return rc;
+    Slot &s = r->slots[r->head];
+    RS_TRY(hipEventSynchronize(s.done));
+    const uint32_t n_ids = s.out[s.nq];
+    if (n_ids && !term_ids) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    std::memcpy(q_off, s.out, 4ull * (s.nq + 1));
+    if (n_ids) std::memcpy(term_ids, s.out + (r->max_queries + 1), 4ull * n_ids);
+    *nq_out = s.nq;
+    r->last_collected = int(r->head);
+    r->head = (r->head + 1) % r->depth;
+    --r->count;
+    return VBM25_OK;
+}
+
+int intern_batch_device(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, uint32_t n_lex, uint8_t *keys16) {
+    if (!lex_off || (n_lex && !keys16)) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    LexShape sh;
+    const uint32_t one_query[2] = {0, n_lex};
+    if (int rc = check_lexemes(seed32 != nullptr, bytes, lex_off, one_query, 1, &sh)) return rc;
+    if (int rc = use_device(device)) return rc;
+    if (!n_lex) return VBM25_OK;
+    Seed seed;
+    seed_words(seed32, &seed);
+    const size_t o_bytes = align_up(8ull * (n_lex + 1), 16), total = o_bytes + align_up(sh.n_bytes, 4);
+    std::vector<uint8_t> stage(total, 0);
+    std::memcpy(stage.data(), lex_off, 8ull * (n_lex + 1));
+    if (sh.n_bytes) std::memcpy(stage.data() + o_bytes, bytes, sh.n_bytes);
+    struct OwnStream {  // (a stream of its own: a launch on the null stream would wait for every other stream of the device)
+        hipStream_t s = nullptr;
+        ~OwnStream() {
+            if (s) {
+                (void)hipStreamSynchronize(s);
+                (void)hipStreamDestroy(s);
+            }
+        }
+    };
+    DBuf in, keys;
+    OwnStream st;  // (declared behind the buffers, so destroyed -- and waited for -- before they are freed)
+    RS_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    RS_TRY(in.alloc(total));
+    RS_TRY(keys.alloc(16ull * n_lex));
+    RS_TRY(hipMemcpyAsync(in.p, stage.data(), total, hipMemcpyHostToDevice, st.s));
+    if (int rc = launch_intern(st.s, seed, reinterpret_cast<const uint32_t *>(in.as<uint8_t>() + o_bytes), in.as<uint64_t>(), n_lex, sh.longest_lexeme,
+                               nullptr, 0, keys.as<Key>(), nullptr))
+        return rc;
+    RS_TRY(hipMemcpyAsync(keys16, keys.p, 16ull * n_lex, hipMemcpyDeviceToHost, st.s));
+    RS_TRY(hipStreamSynchronize(st.s));
+    return VBM25_OK;
+}
+
+int search_batch_lexemes(vbm25_index *ix, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq,
+                         uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    if (!ix) return set_error(VBM25_ERR_INVALID, "index is NULL");
+    LexShape sh;
+    if (int rc = check_lexemes(seed32 != nullptr, bytes, lex_off, q_lex, nq, &sh)) return rc;
+    vbm25_resolver *r = nullptr;
+    if (int rc = resolver_create(ix, seed32, 1, std::max(nq, 1u), std::max(sh.n_lex, 1u), sh.n_bytes, &r)) return rc;
+    struct Free {
+        vbm25_resolver *r;
+        ~Free() { vbm25_resolver_destroy(r); }
+    } free_it{r};
+    std::vector<uint32_t> term_ids(std::max(sh.n_lex, 1u)), q_off(size_t(nq) + 1);
+    uint32_t got = 0;
+    if (int rc = resolver_submit_lexemes(r, bytes, lex_off, q_lex, nq)) return rc;
+    if (int rc = resolver_collect(r, term_ids.data(), q_off.data(), &got)) return rc;
+    return vbm25_search_batch(ix, term_ids.data(), q_off.data(), nq, k, hits, n_hits);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vbm25_resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes,
+                          vbm25_resolver **out) {
+    return guarded([&] { return resolver_create(ix, seed32, depth, max_queries, max_lexemes, max_bytes, out); });
+}
+
+void vbm25_resolver_destroy(vbm25_resolver *r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    if (r->stream) (void)hipStreamSynchronize(r->stream);  // nothing is freed under a kernel or a copy in flight
+    for (Slot &s : r->slots) {
+        if (s.in) (void)hipHostFree(s.in);
+        if (s.out) (void)hipHostFree(s.out);
+        if (s.start) (void)hipEventDestroy(s.start);
+        if (s.done) (void)hipEventDestroy(s.done);
+    }
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    delete r;
+}
+
+uint64_t vbm25_resolver_device_bytes(const vbm25_resolver *r) { return r ? r->device_bytes : 0; }
+
+int vbm25_resolver_submit_lexemes(vbm25_resolver *r, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq) {
+    return guarded([&] { return resolver_submit_lexemes(r, bytes, lex_off, q_lex, nq); });
+}
+
+int vbm25_resolver_submit_keys(vbm25_resolver *r, const uint8_t *keys16, const uint32_t *q_key, uint32_t nq) {
+    return guarded([&] { return resolver_submit_keys(r, keys16, q_key, nq); });
+}
+
+int vbm25_resolver_collect(vbm25_resolver *r, uint32_t *term_ids, uint32_t *q_off, uint32_t *nq_out) {
+    return guarded([&] { return resolver_collect(r, term_ids, q_off, nq_out); });
+}
+
+int vbm25_resolver_in_flight(const vbm25_resolver *r) { return r ? int(r->count) : 0; }
+
+int vbm25_intern_batch_device(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, uint32_t n_lex, uint8_t *keys16) {
+    return guarded([&] { return intern_batch_device(device, seed32, bytes, lex_off, n_lex, keys16); });
+}
+
+int vbm25_search_batch_lexemes(vbm25_index *ix, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex,
+                               uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
+    return guarded([&] { return search_batch_lexemes(ix, seed32, bytes, lex_off, q_lex, nq, k, hits, n_hits); });
+}
+
+// tools/resolve_cost.py: the device time of the last collected batch's kernels (upload excluded), by the slot's HIP events.  Not in the header.
+int vbm25_debug_resolver_kernel_ms(vbm25_resolver *r, double *ms) {
+    if (!r || !ms || r->last_collected < 0) return set_error(VBM25_ERR_INVALID, "no collected batch");
+    float f = 0;
+    RS_TRY(hipEventElapsedTime(&f, r->slots[r->last_collected].start, r->slots[r->last_collected].done));
+    *ms = f;
+    return VBM25_OK;
+}
+
+}  // extern "C"

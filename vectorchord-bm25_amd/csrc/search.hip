@@ -2296,6 +2296,12 @@ int index_device_and_docs(const vbm25_index *ix, int *device, uint32_t *n_docs) 
     *n_docs = ix->n_docs;
     return VBM25_OK;
 }
+int index_vocabulary(const vbm25_index *ix, int *device, uint32_t *n_terms, const uint8_t **term_key) {
+    *device = ix->device;
+    *n_terms = ix->n_terms;
+    *term_key = ix->term_key.data();
+    return VBM25_OK;
+}
 int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vbm25_device_growing **out) {
     if (int rc = use_device(ix->device)) return rc;
     return growing_build(ix, a, nullptr, out);

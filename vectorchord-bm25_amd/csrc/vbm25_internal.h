@@ -75,6 +75,8 @@ struct GrowingDeviceArrays {
     const uint16_t *payload;
 };
 int index_device_and_docs(const vbm25_index *ix, int *device, uint32_t *n_docs);
+// the index's device and its host copy of the vocabulary (16 bytes a term, ascending): what a resolver (resolve.hip) uploads at create
+int index_vocabulary(const vbm25_index *ix, int *device, uint32_t *n_terms, const uint8_t **term_key);
 // the device half of vbm25_growing_upload; synchronous, the arrays may be freed when it returns
 int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vbm25_device_growing **out);
 
