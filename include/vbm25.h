@@ -777,6 +777,41 @@ int vbm25_multi_batch_set_filter(vbm25_multi_batch *, const vbm25_filter *const 
 int vbm25_multi_batch_run(vbm25_multi_batch *);
 int vbm25_multi_batch_fetch(vbm25_multi_batch *, vbm25_hit *hits, uint32_t *n_hits);
 
+/* The Document step on the device (csrc/cast.hip): cast_tsvector_to_document (src/datatype/tsvector.rs:84-94: intern every lexeme, sort
+ * the elements by key, sum equal keys saturating) for a batch of tsvectors, the result kept in the HBM of `device` -- what ambuild
+ * (am_build.rs:722) and aminsert (am/mod.rs:284) make of a tuple before anything else happens to it.
+ *   input     document i = lexemes doc_lex[i] .. doc_lex[i+1]; lexeme j = bytes[lex_off[j] .. lex_off[j+1]), any length, any alignment,
+ *             with lex_count[j] positions (vbm25_resolver_submit_lexemes' packing plus the counts).  Repeated lexemes in a document and
+ *             lexemes whose keys collide are allowed.  doc_payload: n_docs x 3, or NULL for documents nobody will index or append.
+ *   result    byte for byte the reference's: key = intern(seed, lexeme); a document's elements strictly ascending in memcmp order of
+ *             the key; equal keys merged, tf = the saturating u32 sum; length = the saturating u32 sum of the tfs (vector.rs:76-83);
+ *             fieldnorm = length_to_fieldnorm(length).  A document without lexemes is kept, with 0 elements and length 0.
+ *   download  the arrays as a vbm25_growing (vbm25_growing_get_desc: start, key, tf, fieldnorm, payload -- NULL when none was given --,
+ *             deleted all 0: a legal vbm25_growing_desc) and, when doc_len is not NULL, the n_docs lengths.
+ * Refused before anything is enqueued, *out == NULL: VBM25_ERR_INVALID for a NULL argument, doc_lex[0] != 0, offsets that are not
+ * monotone, a lexeme with count 0 (the message names the first; the reference panics there) and a lexeme that needs the hash when
+ * seed32 == NULL (vbm25_intern's words); VBM25_ERR_UNSUPPORTED for 2^31 lexemes or 2^31 - 1 documents or more; VBM25_ERR_DEVICE without a HIP
+ * device (there is no host fallback).  n_docs == 0 gives a valid handle of 0 documents.
+ * Synchronous, on a stream of the call's own: it issues no device-wide synchronisation and touches no index; freeing its staging
+ * and scratch at return does wait for the device's other streams, as every hipFree does.  Two threads may cast at once.  Per document one of three sorts, by its number of lexemes: one wave (<= 64), one workgroup in LDS (<= 2048), radix
+ * passes (any length); all three give identical bytes.
+ *   vbm25_device_segment_build_documents   what ambuild + io.rs + flush.rs make of the documents: document i becomes doc id i, the
+ *             vocabulary is the distinct keys ascending, every element a mapping.  The result is the device segment
+ *             vbm25_device_segment_build makes of the same vocabulary and mappings; no posting crosses the host link.
+ *             VBM25_ERR_INVALID for a handle without payloads or of 0 documents; k1, b and the rest as the encode refuses them.
+ *   vbm25_device_growing_append_documents  vbm25_device_growing_append with the delta read from the handle's arrays in HBM: the same
+ *             result, refusals and guarantee (a failed append leaves the segment as it was; a handle of 0 documents changes
+ *             nothing).  VBM25_ERR_INVALID for a handle on another device than the segment's or without payloads. */
+typedef struct vbm25_documents vbm25_documents;
+int vbm25_documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count,
+                         const uint32_t *doc_lex, uint32_t n_docs, const uint16_t *doc_payload, vbm25_documents **out);
+int vbm25_documents_info(const vbm25_documents *, uint32_t *n_docs, uint64_t *n_elements, int *device);
+int vbm25_documents_download(const vbm25_documents *, vbm25_growing **csr, uint32_t *doc_len);
+uint64_t vbm25_documents_device_bytes(const vbm25_documents *);
+void vbm25_documents_free(vbm25_documents *);
+int vbm25_device_segment_build_documents(const vbm25_documents *, double k1, double b, vbm25_device_segment **out);
+int vbm25_device_growing_append_documents(vbm25_device_growing *, const vbm25_documents *);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,56 @@ inline std::vector<Key> intern_batch(int device, const Seed *seed, const LexemeB
     return keys;
 }
 
+// tsvectors as the document cast takes them: LexemeBatch's packing plus the lexemes' position counts; a "query" of the batch is a
+// document (add a lexeme with its count, end_document() closes the document).
+struct DocumentBatch {
+    LexemeBatch lexemes;
+    std::vector<uint32_t> lex_count;
+    std::vector<uint16_t> payload;  // 3 per document, or empty: documents nobody will index or append
+    void add(std::string_view lexeme, uint32_t count) {
+        lexemes.add(lexeme);
+        lex_count.push_back(count);
+    }
+    void end_document() { lexemes.end_query(); }
+    void end_document(const uint16_t (&ctid)[3]) {
+        lexemes.end_query();
+        payload.insert(payload.end(), ctid, ctid + 3);
+    }
+    uint32_t documents() const { return lexemes.queries(); }
+};
+
+struct GrowingDocs;
+// The Document step on the device (RAII over vbm25_documents): cast_tsvector_to_document for a batch of tsvectors, the result kept in
+// HBM.  DeviceSegment::from_documents makes the index of it, DeviceGrowing::append appends it, download() brings the CSR back.
+class Documents {
+  public:
+    Documents(int device, const Seed *seed, const DocumentBatch &b) {
+        check(vbm25_documents_cast(device, seed ? seed->data() : nullptr, b.lexemes.bytes.data(), b.lexemes.lex_off.data(), b.lex_count.data(),
+                                   b.lexemes.q_lex.data(), b.documents(), b.payload.empty() ? nullptr : b.payload.data(), &h_));
+    }
+    Documents(Documents &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Documents(const Documents &) = delete;
+    Documents &operator=(const Documents &) = delete;
+    ~Documents() { vbm25_documents_free(h_); }
+    uint32_t docs() const {
+        uint32_t n = 0;
+        check(vbm25_documents_info(h_, &n, nullptr, nullptr));
+        return n;
+    }
+    uint64_t elements() const {
+        uint64_t n = 0;
+        check(vbm25_documents_info(h_, nullptr, &n, nullptr));
+        return n;
+    }
+    uint64_t device_bytes() const { return vbm25_documents_device_bytes(h_); }
+    // the CSR (payload empty when the cast had none) and, when asked for, the documents' lengths
+    inline GrowingDocs download(std::vector<uint32_t> *doc_len = nullptr) const;
+    const vbm25_documents *handle() const { return h_; }
+
+  private:
+    vbm25_documents *h_ = nullptr;
+};
+
 class DeviceGrowing;
 class DeviceVacuum;
 
@@ -334,6 +384,13 @@ class DeviceSegment {
         check(vbm25_device_segment_from_pages(read_page, ctx, device, &h));
         return DeviceSegment(h);
     }
+    // The index ambuild makes of cast documents (vbm25_device_segment_build_documents): document i = doc id i, the vocabulary = their
+    // distinct keys; sorted, ranked and encoded on the documents' device.
+    static DeviceSegment from_documents(const Documents &documents, double k1, double b) {
+        vbm25_device_segment *h = nullptr;
+        check(vbm25_device_segment_build_documents(documents.handle(), k1, b, &h));
+        return DeviceSegment(h);
+    }
     explicit DeviceSegment(vbm25_device_segment *h) : h_(h) {}
     DeviceSegment(DeviceSegment &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     DeviceSegment(const DeviceSegment &) = delete;
@@ -395,12 +452,18 @@ inline GrowingDocs growing_docs_of(vbm25_growing *g) {
         if (d.n_elements) std::memcpy(out.key[0].data(), d.key, 16 * d.n_elements);
         out.tf.assign(d.tf, d.tf + d.n_elements);
         out.fieldnorm.assign(d.fieldnorm, d.fieldnorm + d.n_docs);
-        out.payload.assign(d.payload, d.payload + 3ull * d.n_docs);
+        if (d.payload) out.payload.assign(d.payload, d.payload + 3ull * d.n_docs);  // (NULL: documents cast without payloads)
         out.deleted.assign(d.deleted, d.deleted + d.n_docs);
     }
     vbm25_growing_free(g);
     check(rc);
     return out;
+}
+inline GrowingDocs Documents::download(std::vector<uint32_t> *doc_len) const {
+    vbm25_growing *g = nullptr;
+    if (doc_len) doc_len->assign(docs(), 0);
+    check(vbm25_documents_download(h_, &g, doc_len && !doc_len->empty() ? doc_len->data() : nullptr));
+    return growing_docs_of(g);
 }
 // DocumentTuple.deleted of every sealed document of a relation as the DELETED words vbm25_index_maintain and vbm25_filter_remap
 // take (bit d % 64 of word d / 64); n_docs, when given, receives the document count (vbm25_sealed_deleted_from_pages)
@@ -459,6 +522,8 @@ class DeviceGrowing {
         const vbm25_growing_desc d = desc_of(delta);
         check(vbm25_device_growing_append(h_, &d));
     }
+    // the same from cast documents in HBM on the segment's device (vbm25_device_growing_append_documents)
+    void append(const Documents &delta) { check(vbm25_device_growing_append_documents(h_, delta.handle())); }
     // growing indices below docs(), any order (vbm25_device_growing_delete)
     void erase(const std::vector<uint32_t> &g) { check(vbm25_device_growing_delete(h_, g.data(), uint32_t(g.size()))); }
     uint32_t docs() const { return vbm25_device_growing_docs(h_); }

@@ -161,6 +161,13 @@ ABI = {
     "vbm25_resolver_in_flight": (i32, [vp]),
     "vbm25_intern_batch_device": (i32, [i32, vp, vp, vp, u32, vp]),
     "vbm25_search_batch_lexemes": (i32, [vp, vp, vp, vp, vp, u32, u32, vp, vp]),
+    "vbm25_documents_cast": (i32, [i32, vp, vp, vp, vp, vp, u32, vp, vp]),
+    "vbm25_documents_info": (i32, [vp, vp, vp, vp]),
+    "vbm25_documents_download": (i32, [vp, vp, vp]),
+    "vbm25_documents_device_bytes": (u64, [vp]),
+    "vbm25_documents_free": (None, [vp]),
+    "vbm25_device_segment_build_documents": (i32, [vp, C.c_double, C.c_double, vp]),
+    "vbm25_device_growing_append_documents": (i32, [vp, vp]),
 }
 
 

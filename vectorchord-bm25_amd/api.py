@@ -232,6 +232,15 @@ class DeviceSegment:
         return cls(out)
 
     @classmethod
+    def from_documents(cls, documents, k1, b):
+        """vbm25_device_segment_build_documents: the index ambuild makes of cast Documents (document i = doc id i, the vocabulary =
+        their distinct keys), sorted, ranked and encoded on the documents' device; download() is byte for byte Segment.build of
+        the same vocabulary and mappings."""
+        out = C.c_void_p()
+        check(lib().vbm25_device_segment_build_documents(documents.h, k1, b, C.byref(out)))
+        return cls(out)
+
+    @classmethod
     def from_pages(cls, pages, device=0):
         """vbm25_device_segment_from_pages: the sealed segment of a bm25 index relation in the reference's on-disk format, read into
         the HBM of `device` (the host follows the page chains, kernels parse, validate and flatten the tuples).  `pages` as
@@ -832,6 +841,14 @@ class GrowingSegment:
         finally:
             self.n_docs = int(lib().vbm25_device_growing_docs(self.h))
 
+    def append_documents(self, documents):
+        """vbm25_device_growing_append_documents: append() with the delta taken from cast Documents in HBM on the segment's device;
+        nothing of it crosses the host link."""
+        try:
+            check(lib().vbm25_device_growing_append_documents(self.h, documents.h))
+        finally:
+            self.n_docs = int(lib().vbm25_device_growing_docs(self.h))
+
     def delete(self, indices):
         """vbm25_device_growing_delete: growing documents (indices below n_docs, any order) score nothing from now on."""
         g = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
@@ -1093,7 +1110,8 @@ def set_tuning(name, value):
     scratch batch is created.  Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items,
     range_min_chunk, range_grid, dense_grid, fused_items, arith, win, win_force, win_items, win_grid, win_skew, win_guided,
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
-    takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation).  No switch of
+    takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
+    and cast_group_max (the class bounds of Documents.cast, read at the start of each cast; 0 turns the class off).  No switch of
     the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
     libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set
@@ -1161,6 +1179,73 @@ def intern_batch(lexemes, seed=None, device=0):
     keys = np.zeros((n, WIDTH), dtype=np.uint8)
     check(lib().vbm25_intern_batch_device(device, _seed_arg(seed), _p(data), lex_off.ctypes.data, n, _p(keys)))
     return keys
+
+
+def pack_documents(docs):
+    """A list of documents, each a list of (lexeme `bytes`, count) -> the prepacked form (bytes uint8, lex_off uint64, lex_count uint32,
+    doc_lex uint32) that Documents.cast also takes: pack_lexemes' packing plus the lexemes' position counts."""
+    data, lex_off, doc_lex = pack_lexemes([[t for t, _ in d] for d in docs])
+    lex_count = np.array([c for d in docs for _, c in d], dtype=np.uint32)
+    return data, lex_off, lex_count, doc_lex
+
+
+class Documents:
+    """vbm25_documents: cast_tsvector_to_document for a batch of tsvectors on the device, the result kept in HBM -- per document the
+    distinct keys ascending with their saturating tf sums, the length and its fieldnorm code.  DeviceSegment.from_documents makes an
+    index of it, GrowingSegment.append_documents appends it; download() brings the arrays back."""
+
+    def __init__(self, handle):
+        self.h = handle
+        nd, ne, dev = C.c_uint32(), C.c_uint64(), C.c_int()
+        check(lib().vbm25_documents_info(self.h, C.byref(nd), C.byref(ne), C.byref(dev)))
+        self.n_docs, self.n_elements, self.device = nd.value, ne.value, dev.value
+
+    @classmethod
+    def cast(cls, docs_or_packed, payload=None, seed=None, device=0):
+        """`docs_or_packed`: a list of lists of (lexeme, count), or pack_documents' tuple.  payload: None or uint16 [n_docs, 3]."""
+        if isinstance(docs_or_packed, tuple) and len(docs_or_packed) == 4:
+            data, lex_off, lex_count, doc_lex = docs_or_packed
+            data, lex_off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(lex_off, dtype=np.uint64)
+            lex_count, doc_lex = np.ascontiguousarray(lex_count, dtype=np.uint32), np.ascontiguousarray(doc_lex, dtype=np.uint32)
+        else:
+            data, lex_off, lex_count, doc_lex = pack_documents(docs_or_packed)
+        n_docs = len(doc_lex) - 1
+        if payload is not None:
+            payload = np.ascontiguousarray(payload, dtype=np.uint16).reshape(-1)
+            if len(payload) != 3 * n_docs:
+                raise ValueError(f"{len(payload)} payload words for {n_docs} documents")
+            if not n_docs:
+                payload = np.zeros(3, dtype=np.uint16)  # (a non-NULL pointer: the handle is one with payloads)
+        out = C.c_void_p()
+        check(lib().vbm25_documents_cast(device, _seed_arg(seed), _p(data), lex_off.ctypes.data, lex_count.ctypes.data, doc_lex.ctypes.data,
+                                         n_docs, _p(payload), C.byref(out)))
+        return cls(out)
+
+    def device_bytes(self):
+        return int(lib().vbm25_documents_device_bytes(self.h))
+
+    def download(self, with_length=True):
+        """dict: g_start, g_key, g_tf, g_fieldnorm, g_payload (None when the cast had none), g_deleted (all 0) and length"""
+        csr = C.c_void_p()
+        length = np.zeros(self.n_docs, dtype=np.uint32) if with_length else None
+        check(lib().vbm25_documents_download(self.h, C.byref(csr), _p(length)))
+        try:
+            d = GrowingDesc()
+            check(lib().vbm25_growing_get_desc(csr, C.byref(d)))
+            out = _growing_dict(csr)
+            if not d.payload:
+                out["g_payload"] = None
+        finally:
+            lib().vbm25_growing_free(csr)
+        out["length"] = length
+        return out
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().vbm25_documents_free(self.h)
+        except Exception:
+            pass
 
 
 class Resolver:

@@ -1,0 +1,727 @@
+// cast.hip -- the document cast: cast_tsvector_to_document (src/datatype/tsvector.rs:84-94: intern every lexeme, sort the elements by
+// key, sum equal keys saturating -- dedup at :107-127) on the device, batched, the result kept in HBM (vbm25_documents), and the index
+// ambuild + io.rs + flush.rs make of such documents (vbm25_device_segment_build_documents).  cast_lane.h holds the per-document
+// functions; the kernels here are loops over them.
+//
+//   per cast, all on a stream of the call's own; no call here is a device-wide synchronisation and no index is touched.  The call
+//   does allocate and free its staging and scratch (a pinned block, a dozen device buffers), and the runtime's hipFree / hipHostFree
+//   wait for the device's other streams when the cast returns: a cast beside a serving stream stalls it for that moment.
+//     upload              the pinned block (doc_lex | lex_off | lex_count | class lists | fieldnorm lengths | bytes) in ONE copy, the
+//                         payloads in a second one straight into the handle's array
+//     cast_intern_kernel  one lane a lexeme: intern_lane -> key; the chaining-value stack in LDS, sized from the longest lexeme
+//     sort and dedup, per DOCUMENT one of three classes (doc_class; the host lists the documents of each while it validates doc_lex):
+//       cast_wave_kernel    <= 64 lexemes: one wave a document, one lane a lexeme.  Equal keys in lower lanes and the rank among the
+//                           distinct keys by cross-lane compares of the 128-bit key, the heads by ballot, no LDS
+//       cast_group_kernel   <= CAST_GROUP_MAX lexemes: one workgroup a document.  Keys and counts sorted in LDS (bitonic; padding sorts
+//                           behind every key), then head flags, the runs' saturating sums and the compaction by ballot
+//       general             any length: the class's elements, tagged with their document's slot, through three stable radix passes
+//                           (key bytes 8..15, key bytes 0..7, slot), head flags, an inclusive scan of the flags (the run numbers) and one
+//                           of the counts in 64 bits (a run's sum is a difference of two prefixes, clamped to u32)
+//     every class writes a document's survivors at its input offset (tmp_key / tmp_tf) and their number to counts[doc]
+//     (scan)              exclusive sum of the counts in 64 bits -> start
+//     cast_gather_kernel  one wave a document: tmp -> key / tf at start[doc], the length (saturating) and its fieldnorm code
+//   The classes write identical bytes: the order is memcmp's in all three and the saturating sum does not depend on the order.
+//   No kernel here has scratch memory.
+//
+//   the index from documents (document i = doc id i), on the handle's device:
+//     (radix sort)        all elements by key, stable: two 64-bit passes with the element index as the value.  Elements are in document
+//                         order, so every key's run comes out in ascending document order
+//     build_flag_kernel   first of its key -> 1; (scan) inclusive -> rank + 1, the last one = n_terms
+//     build_emit_kernel   post_doc (bisection of start), post_tf, term_key and term_start at the heads
+//     term_key and term_start go to the host (build_device_core takes them there); the postings never do
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "vbm25_internal.h"
+#include "device_segment.h"
+#include "cast_lane.h"
+#include "lexeme_input.h"
+
+namespace {
+
+using namespace vbm25;
+using namespace vbm25::rsv;
+using namespace vbm25::cst;
+using vbm25::lexin::Seed;
+using vbm25::lexin::seed_words;
+using ull = unsigned long long;
+
+#define CS_TRY(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+struct DBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DBuf() = default;
+    DBuf(const DBuf &) = delete;
+    DBuf &operator=(const DBuf &) = delete;
+    ~DBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) {
+        bytes = n ? n : 16;
+        return hipMalloc(&p, bytes);
+    }
+    template <class T>
+    T *as() const {
+        return static_cast<T *>(p);
+    }
+};
+struct Pinned {
+    uint8_t *p = nullptr;
+    ~Pinned() {
+        if (p) (void)hipHostFree(p);
+    }
+};
+// (a stream of the call's own: a launch on the null stream would wait for every other stream of the device)
+struct OwnStream {
+    hipStream_t s = nullptr;
+    hipEvent_t start = nullptr, mid = nullptr, resume = nullptr, done = nullptr;
+    ~OwnStream() {
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+        if (start) (void)hipEventDestroy(start);
+        if (done) (void)hipEventDestroy(done);
+        if (mid) (void)hipEventDestroy(mid);
+        if (resume) (void)hipEventDestroy(resume);
+    }
+};
+
+constexpr uint32_t INTERN_THREADS = 64;  // one wave a block: the LDS stack is 32 bytes a level a lane
+constexpr uint32_t INTERN_GRID = 1024;   // more lexemes than 65536 stride the grid
+constexpr uint32_t WG = 256, MAX_GRID = 2048;
+
+// cast_wave_max / cast_group_max of vbm25_tuning_set: read at the start of each cast
+std::atomic<uint32_t> g_wave_max{CAST_WAVE_MAX}, g_group_max{CAST_GROUP_MAX};
+// the calling thread's last cast: its kernels by HIP events -- upload excluded, and so is the host's allocation of key / tf between
+// the scan and the gather (two spans: upload's end .. the scan's end, the gather's start .. its end)
+thread_local double g_kernel_ms = -1.0;
+
+uint32_t grid_for(uint64_t units, uint32_t per_block) {
+    return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block));
+}
+size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+struct WidenU32 {
+    __host__ __device__ ull operator()(uint32_t v) const { return v; }
+};
+
+// The pool is 4-byte aligned and ends on a multiple of 4 (WordLoad).
+__global__ void __launch_bounds__(INTERN_THREADS) cast_intern_kernel(Seed seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex,
+                                                                     Key *keys) {
+    extern __shared__ uint32_t cv_stack[];
+    const WordLoad ld{pool};
+    for (uint32_t i = blockIdx.x * INTERN_THREADS + threadIdx.x; i < n_lex; i += gridDim.x * INTERN_THREADS) {
+        const uint64_t begin = lex_off[i];
+        keys[i] = intern_lane(seed.w, ld, begin, lex_off[i + 1] - begin, cv_stack + threadIdx.x, INTERN_THREADS);
+    }
+}
+
+// what a sort kernel reads and writes: document d = lexemes doc_lex[d] .. doc_lex[d + 1]; its survivors go to tmp_*[doc_lex[d] ..)
+struct SortArgs {
+    const Key *keys;
+    const uint32_t *lex_count, *doc_lex;
+    Key *tmp_key;
+    uint32_t *tmp_tf, *counts;
+};
+
+// element j of the wave's document: lane j's registers (every lane of the wave calls with the same j)
+struct LaneAt {
+    Key k;
+    uint32_t c;
+    __device__ void operator()(uint32_t j, Key &kj, uint32_t &cj) const {
+        kj.x = __shfl(ull(k.x), int(j));
+        kj.y = __shfl(ull(k.y), int(j));
+        cj = __shfl(c, int(j));
+    }
+};
+struct MaskHead {
+    ull mask;
+    __device__ bool operator()(uint32_t j) const { return (mask >> j) & 1ull; }
+};
+
+// the wave class: every listed document has at most 64 lexemes
+__global__ void __launch_bounds__(WG) cast_wave_kernel(SortArgs a, const uint32_t *list, uint32_t n_list) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG + threadIdx.x) >> 6, n_waves = (gridDim.x * WG) >> 6;
+    for (uint32_t s = wave; s < n_list; s += n_waves) {
+        const uint32_t d = list[s], b = a.doc_lex[d], n = a.doc_lex[d + 1] - b;
+        const bool mine = lane < n;
+        const LaneAt at{mine ? a.keys[b + lane] : Key{0, 0}, mine ? a.lex_count[b + lane] : 0u};
+        uint32_t sum;
+        const bool head = head_and_sum(at, n, lane, at.k, sum) && mine;
+        const ull heads = __ballot(head);
+        const uint32_t rank = rank_of(at, MaskHead{heads}, n, at.k);
+        if (head) {
+            a.tmp_key[b + rank] = at.k;
+            a.tmp_tf[b + rank] = sum;
+        }
+        if (lane == 0) a.counts[d] = __popcll(heads);
+    }
+}
+
+// order of two LDS elements of the workgroup class: a count of 0 marks padding (a lexeme's count is never 0), which sorts last
+__device__ __forceinline__ bool slot_less(const Key &ka, uint32_t ca, const Key &kb, uint32_t cb) {
+    if ((ca == 0) != (cb == 0)) return cb == 0;
+    return ca != 0 && key_less(ka, kb);
+}
+
+// the workgroup class: every listed document has at most CAST_GROUP_MAX lexemes
+__global__ void __launch_bounds__(WG) cast_group_kernel(SortArgs a, const uint32_t *list, uint32_t n_list) {
+    __shared__ Key s_key[CAST_GROUP_MAX];
+    __shared__ uint32_t s_tf[CAST_GROUP_MAX];
+    __shared__ uint32_t s_wave[WG / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    for (uint32_t s = blockIdx.x; s < n_list; s += gridDim.x) {
+        const uint32_t d = list[s], b = a.doc_lex[d], n = a.doc_lex[d + 1] - b;
+        uint32_t P = 1;
+        while (P < n) P <<= 1;
+        for (uint32_t i = t; i < P; i += WG) {
+            s_key[i] = i < n ? a.keys[b + i] : Key{0, 0};
+            s_tf[i] = i < n ? a.lex_count[b + i] : 0u;
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= P; k <<= 1) {
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t i = t; i < P; i += WG) {
+                    const uint32_t o = i ^ j;
+                    if (o > i) {
+                        const Key ki = s_key[i], ko = s_key[o];
+                        const uint32_t ci = s_tf[i], co = s_tf[o];
+                        const bool up = (i & k) == 0;
+                        if (up ? slot_less(ko, co, ki, ci) : slot_less(ki, ci, ko, co)) {
+                            s_key[i] = ko;
+                            s_key[o] = ki;
+                            s_tf[i] = co;
+                            s_tf[o] = ci;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // heads, their runs' sums and their positions among the heads
+        uint32_t base = 0;
+        for (uint32_t r = 0; r < n; r += WG) {
+            const uint32_t i = r + t;
+            const bool head = i < n && (i == 0 || !key_equal(s_key[i], s_key[i - 1]));
+            const ull heads = __ballot(head);
+            if (lane == 0) s_wave[w] = __popcll(heads);
+            __syncthreads();
+            uint32_t at = base, total = 0;
+#pragma unroll
+            for (uint32_t x = 0; x < WG / 64; ++x) {
+                const uint32_t v = s_wave[x];
+                at += x < w ? v : 0u;
+                total += v;
+            }
+            if (head) {
+                const Key k = s_key[i];
+                uint32_t sum = s_tf[i];
+                for (uint32_t e = i + 1; e < n && key_equal(s_key[e], k); ++e) sum = sat_add(sum, s_tf[e]);
+                at += __popcll(heads & ((1ull << lane) - 1ull));
+                a.tmp_key[b + at] = k;
+                a.tmp_tf[b + at] = sum;
+            }
+            base += total;
+            __syncthreads();
+        }
+        if (t == 0) a.counts[d] = base;
+    }
+}
+
+// ---- the general class.  Slot s of the class is document list[s], its elements are e = off[s] .. off[s + 1] of the class ----
+struct GenArgs {
+    SortArgs a;
+    const uint32_t *list, *off;  // n_gen documents, n_gen + 1 offsets
+    uint32_t n_gen, n_el;
+    uint32_t *src, *slot;        // per element: its lexeme, its slot (slot: the run numbers once the sorts are done)
+    ull *ka, *kb;                // the sort's keys (ka: the counts in 64 bits once the sorts are done; kb: the slot per sorted position)
+    uint32_t *va, *vb;           // the sort's values: element numbers (va: the head flags once the sorts are done)
+    ull *prefix;                 // inclusive sums of the counts in sorted order
+    uint32_t *head_pos;          // n_el + 1: run q starts at sorted position head_pos[q]
+};
+
+__global__ void __launch_bounds__(WG) gen_fill_kernel(GenArgs g) {
+    for (uint32_t e = blockIdx.x * WG + threadIdx.x; e < g.n_el; e += gridDim.x * WG) {
+        uint32_t lo = 0, hi = g.n_gen;  // the last slot with off[slot] <= e (empty documents in front of it share its start)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (g.off[mid] <= e) lo = mid; else hi = mid;
+        }
+        const uint32_t src = g.a.doc_lex[g.list[lo]] + (e - g.off[lo]);
+        g.src[e] = src;
+        g.slot[e] = lo;
+        g.ka[e] = __builtin_bswap64(g.a.keys[src].y);
+        g.va[e] = e;
+    }
+}
+__global__ void __launch_bounds__(WG) gen_key_high_kernel(GenArgs g) {  // after pass 1: (kb, vb)
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < g.n_el; p += gridDim.x * WG) g.ka[p] = __builtin_bswap64(g.a.keys[g.src[g.vb[p]]].x);
+}
+__global__ void __launch_bounds__(WG) gen_key_slot_kernel(GenArgs g) {  // after pass 2: (kb, va)
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < g.n_el; p += gridDim.x * WG) g.ka[p] = g.slot[g.va[p]];
+}
+// after pass 3: (kb = slot, vb = element) by (slot, key).  flags -> va, counts in 64 bits -> ka
+__global__ void __launch_bounds__(WG) gen_flag_kernel(GenArgs g) {
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < g.n_el; p += gridDim.x * WG) {
+        const uint32_t src = g.src[g.vb[p]];
+        const bool head = p == g.off[uint32_t(g.kb[p])] || !key_equal(g.a.keys[src], g.a.keys[g.src[g.vb[p - 1]]]);
+        g.va[p] = head ? 1u : 0u;
+        g.ka[p] = g.a.lex_count[src];
+    }
+}
+// run numbers (inclusive sums of the flags) -> slot
+__global__ void __launch_bounds__(WG) gen_head_pos_kernel(GenArgs g) {
+    const uint32_t *run = g.slot;
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < g.n_el; p += gridDim.x * WG) {
+        if (g.va[p]) g.head_pos[run[p] - 1] = p;
+        if (p == g.n_el - 1) g.head_pos[run[p]] = g.n_el;
+    }
+}
+__global__ void __launch_bounds__(WG) gen_emit_kernel(GenArgs g) {
+    const uint32_t *run = g.slot;
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < g.n_el; p += gridDim.x * WG) {
+        const uint32_t s = uint32_t(g.kb[p]), first = g.off[s], d = g.list[s], in_doc = run[p] - run[first];
+        if (g.va[p]) {
+            const uint32_t end = g.head_pos[run[p]];
+            const ull sum = g.prefix[end - 1] - (p ? g.prefix[p - 1] : 0ull);
+            const uint32_t out = g.a.doc_lex[d] + in_doc;
+            g.a.tmp_key[out] = g.a.keys[g.src[g.vb[p]]];
+            g.a.tmp_tf[out] = clamp_u32(sum);
+        }
+        if (p == g.off[s + 1] - 1) g.a.counts[d] = in_doc + 1;
+    }
+}
+
+// one wave a document: the survivors to their place, the length and the fieldnorm code
+__global__ void __launch_bounds__(WG) cast_gather_kernel(const Key *tmp_key, const uint32_t *tmp_tf, const uint32_t *doc_lex, const ull *start,
+                                                         uint32_t n_docs, const uint32_t *fn_len, Key *key, uint32_t *tf, uint32_t *length,
+                                                         uint8_t *fieldnorm) {
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * WG + threadIdx.x) >> 6, n_waves = (gridDim.x * WG) >> 6;
+    for (uint32_t d = wave; d < n_docs; d += n_waves) {
+        const ull o = start[d];
+        const uint32_t c = uint32_t(start[d + 1] - o), b = doc_lex[d];
+        uint32_t len = 0;
+        for (uint32_t j = lane; j < c; j += 64) {
+            const uint32_t v = tmp_tf[b + j];
+            key[o + j] = tmp_key[b + j];
+            tf[o + j] = v;
+            len = sat_add(len, v);
+        }
+#pragma unroll
+        for (int x = 32; x > 0; x >>= 1) len = sat_add(len, __shfl_xor(len, x));
+        if (lane == 0) {
+            length[d] = len;
+            fieldnorm[d] = fieldnorm_of(fn_len, len);
+        }
+    }
+}
+
+// ---- the index from documents ----
+__global__ void __launch_bounds__(WG) build_key_kernel(const Key *key, const uint32_t *idx, uint32_t n, int high, ull *out, uint32_t *iota) {
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < n; p += gridDim.x * WG) {
+        const Key k = key[idx ? idx[p] : p];
+        out[p] = __builtin_bswap64(high ? k.x : k.y);
+        if (iota) iota[p] = p;
+    }
+}
+__global__ void __launch_bounds__(WG) build_flag_kernel(const Key *key, const uint32_t *order, uint32_t n, uint32_t *flags) {
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < n; p += gridDim.x * WG)
+        flags[p] = (p == 0 || !key_equal(key[order[p]], key[order[p - 1]])) ? 1u : 0u;
+}
+__global__ void __launch_bounds__(WG) build_emit_kernel(const Key *key, const uint32_t *tf, const ull *start, uint32_t n_docs, const uint32_t *order,
+                                                        const uint32_t *flags, const uint32_t *rank1, uint32_t n, uint32_t *post_doc,
+                                                        uint32_t *post_tf, Key *term_key, ull *term_start) {
+    for (uint32_t p = blockIdx.x * WG + threadIdx.x; p < n; p += gridDim.x * WG) {
+        const uint32_t e = order[p];
+        uint32_t lo = 0, hi = n_docs;  // the last document with start[doc] <= e (empty documents in front of it share its start)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (start[mid] <= e) lo = mid; else hi = mid;
+        }
+        post_doc[p] = lo;
+        post_tf[p] = tf[e];
+        if (flags[p]) {
+            term_key[rank1[p] - 1] = key[e];
+            term_start[rank1[p] - 1] = p;
+        }
+        if (p == n - 1) term_start[rank1[p]] = n;
+    }
+}
+
+int use_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the document cast has no host fallback");
+    if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
+    CS_TRY(hipSetDevice(device));
+    return VBM25_OK;
+}
+
+// what a batch of documents is, checked before anything is allocated or enqueued
+struct Shape {
+    uint32_t n_lex = 0;
+    uint64_t n_bytes = 0, longest_lexeme = 0;
+};
+int check_documents(bool has_seed, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count, const uint32_t *doc_lex, uint32_t n_docs,
+                    Shape *s) {
+    if (!doc_lex || !lex_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (n_docs >= (1u << 31) - 1u) return set_error(VBM25_ERR_UNSUPPORTED, "%u documents: one cast takes fewer than 2^31 - 1", n_docs);
+    if (doc_lex[0] != 0) return set_error(VBM25_ERR_INVALID, "doc_lex[0] is %u, not 0", doc_lex[0]);
+    for (uint32_t i = 0; i < n_docs; ++i)
+        if (doc_lex[i + 1] < doc_lex[i]) return set_error(VBM25_ERR_INVALID, "doc_lex is not monotone at document %u", i);
+    s->n_lex = doc_lex[n_docs];
+    if (s->n_lex >= (1u << 31)) return set_error(VBM25_ERR_UNSUPPORTED, "%u lexemes: one cast takes fewer than 2^31", s->n_lex);
+    if (s->n_lex && !lex_count) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    // (the offsets and the pool first, as they were; the seed last, behind the counts)
+    if (int rc = lexin::check_pool(true, bytes, lex_off, s->n_lex, "cast", &s->n_bytes, &s->longest_lexeme)) return rc;
+    for (uint32_t d = 0; d < n_docs; ++d)  // (the reference panics on a lexeme without positions)
+        for (uint32_t i = doc_lex[d]; i < doc_lex[d + 1]; ++i)
+            if (lex_count[i] == 0) return set_error(VBM25_ERR_INVALID, "lexeme %u (document %u) has count 0", i, d);
+    return has_seed ? VBM25_OK : lexin::check_pool(false, bytes, lex_off, s->n_lex, "cast", &s->n_bytes, &s->longest_lexeme);
+}
+
+uint64_t handle_bytes(const vbm25_documents *h) {
+    uint64_t n = 0;
+    for (const HbmArray *a : {&h->d_start, &h->d_key, &h->d_tf, &h->d_length, &h->d_fieldnorm, &h->d_payload}) n += a->bytes;
+    return n;
+}
+
+int documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count,
+                   const uint32_t *doc_lex, uint32_t n_docs, const uint16_t *doc_payload, vbm25_documents **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    const uint32_t wave_max = g_wave_max.load(), group_max = g_group_max.load();
+    Shape sh;
+    if (int rc = check_documents(seed32 != nullptr, bytes, lex_off, lex_count, doc_lex, n_docs, &sh)) return rc;
+    // the documents of each class, and the general class's element offsets
+    std::vector<uint32_t> lists[3], gen_off{0};
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        const uint32_t n = doc_lex[d + 1] - doc_lex[d];
+        const DocClass c = doc_class(n, wave_max, group_max);
+        lists[c].push_back(d);
+        if (c == CLASS_GENERAL) gen_off.push_back(gen_off.back() + n);
+    }
+    const uint32_t n_lex = sh.n_lex, n_wave = uint32_t(lists[0].size()), n_group = uint32_t(lists[1].size()), n_gen = uint32_t(lists[2].size()),
+                   n_gen_el = gen_off.back();
+    if (int rc = use_device(device)) return rc;
+    g_kernel_ms = -1.0;
+
+    auto h = std::make_unique<vbm25_documents>();
+    h->device = device;
+    h->n_docs = n_docs;
+    h->has_payload = doc_payload != nullptr;
+    Seed seed;
+    seed_words(seed32, &seed);
+    // the staged block
+    size_t total = 0;
+    auto take = [&](size_t n) {
+        const size_t at = total;
+        total = align_up(total + n, 16);
+        return at;
+    };
+    const size_t o_doc = take(4ull * (n_docs + 1ull)), o_off = take(8ull * (n_lex + 1ull)), o_cnt = take(4ull * n_lex), o_list = take(4ull * n_docs),
+                 o_goff = take(4ull * (n_gen + 1ull)), o_fn = take(4 * 256), o_pay = take(doc_payload ? 6ull * n_docs : 0), o_bytes = take(sh.n_bytes);
+    Pinned stage;
+    DBuf in, keys, tmp_key, tmp_tf, counts, cub, g_src, g_slot, g_ka, g_kb, g_va, g_vb, g_prefix, g_head_pos;
+    OwnStream st;  // (declared behind the buffers, so destroyed -- and waited for -- before they are freed)
+    CS_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    CS_TRY(hipEventCreate(&st.start));
+    CS_TRY(hipEventCreate(&st.done));
+    CS_TRY(hipEventCreate(&st.mid));
+    CS_TRY(hipEventCreate(&st.resume));
+    CS_TRY(hipHostMalloc((void **)&stage.p, total, hipHostMallocDefault));
+    std::memcpy(stage.p + o_doc, doc_lex, 4ull * (n_docs + 1ull));
+    std::memcpy(stage.p + o_off, lex_off, 8ull * (n_lex + 1ull));
+    if (n_lex) std::memcpy(stage.p + o_cnt, lex_count, 4ull * n_lex);
+    {
+        size_t at = o_list;
+        for (const auto &l : lists) {
+            if (!l.empty()) std::memcpy(stage.p + at, l.data(), 4ull * l.size());
+            at += 4ull * l.size();
+        }
+    }
+    std::memcpy(stage.p + o_goff, gen_off.data(), 4ull * gen_off.size());
+    std::memcpy(stage.p + o_fn, fieldnorm_lengths(), 4 * 256);
+    if (doc_payload && n_docs) std::memcpy(stage.p + o_pay, doc_payload, 6ull * n_docs);
+    if (sh.n_bytes) std::memcpy(stage.p + o_bytes, bytes, sh.n_bytes);
+    if (total > o_bytes + sh.n_bytes) std::memset(stage.p + o_bytes + sh.n_bytes, 0, total - o_bytes - sh.n_bytes);
+
+    size_t cub_bytes = 0, tb = 0;
+    CS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
+                                            (ull *)nullptr, int(n_docs + 1), st.s));
+    cub_bytes = std::max(cub_bytes, tb);
+    if (n_gen_el) {
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                  int(n_gen_el), 0, 64, st.s));
+        cub_bytes = std::max(cub_bytes, tb);
+        CS_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n_gen_el), st.s));
+        cub_bytes = std::max(cub_bytes, tb);
+        CS_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, int(n_gen_el), st.s));
+        cub_bytes = std::max(cub_bytes, tb);
+    }
+    CS_TRY(in.alloc(total));
+    CS_TRY(keys.alloc(16ull * n_lex));
+    CS_TRY(tmp_key.alloc(16ull * n_lex));
+    CS_TRY(tmp_tf.alloc(4ull * n_lex));
+    CS_TRY(counts.alloc(4ull * (n_docs + 1ull)));
+    CS_TRY(cub.alloc(cub_bytes));
+    CS_TRY(h->d_start.alloc(8ull * (n_docs + 1ull)));
+    CS_TRY(h->d_length.alloc(4ull * n_docs));
+    CS_TRY(h->d_fieldnorm.alloc(n_docs));
+    if (doc_payload) CS_TRY(h->d_payload.alloc(6ull * n_docs));
+    if (n_gen_el) {
+        CS_TRY(g_src.alloc(4ull * n_gen_el));
+        CS_TRY(g_slot.alloc(4ull * n_gen_el));
+        CS_TRY(g_ka.alloc(8ull * n_gen_el));
+        CS_TRY(g_kb.alloc(8ull * n_gen_el));
+        CS_TRY(g_va.alloc(4ull * n_gen_el));
+        CS_TRY(g_vb.alloc(4ull * n_gen_el));
+        CS_TRY(g_prefix.alloc(8ull * n_gen_el));
+        CS_TRY(g_head_pos.alloc(4ull * (n_gen_el + 1ull)));
+    }
+    uint8_t *d = in.as<uint8_t>();
+    CS_TRY(hipMemcpyAsync(d, stage.p, total, hipMemcpyHostToDevice, st.s));
+    if (doc_payload && n_docs) CS_TRY(hipMemcpyAsync(h->d_payload.p, stage.p + o_pay, 6ull * n_docs, hipMemcpyHostToDevice, st.s));
+    CS_TRY(hipEventRecord(st.start, st.s));
+    CS_TRY(hipMemsetAsync(counts.p, 0, 4ull * (n_docs + 1ull), st.s));
+    const uint32_t *d_doc = reinterpret_cast<const uint32_t *>(d + o_doc), *d_cnt = reinterpret_cast<const uint32_t *>(d + o_cnt),
+                   *d_list = reinterpret_cast<const uint32_t *>(d + o_list), *d_goff = reinterpret_cast<const uint32_t *>(d + o_goff),
+                   *d_fn = reinterpret_cast<const uint32_t *>(d + o_fn);
+    const SortArgs sa{keys.as<Key>(), d_cnt, d_doc, tmp_key.as<Key>(), tmp_tf.as<uint32_t>(), counts.as<uint32_t>()};
+    if (n_lex) {
+        const size_t lds = size_t(stack_levels(sh.longest_lexeme)) * 8 * sizeof(uint32_t) * INTERN_THREADS;
+        cast_intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS)), INTERN_THREADS, lds, st.s>>>(
+            seed, reinterpret_cast<const uint32_t *>(d + o_bytes), reinterpret_cast<const uint64_t *>(d + o_off), n_lex, keys.as<Key>());
+        CS_TRY(hipGetLastError());
+    }
+    if (n_wave && n_lex) {
+        cast_wave_kernel<<<grid_for(n_wave, WG / 64), WG, 0, st.s>>>(sa, d_list, n_wave);
+        CS_TRY(hipGetLastError());
+    }
+    if (n_group && n_lex) {
+        cast_group_kernel<<<grid_for(n_group, 1), WG, 0, st.s>>>(sa, d_list + n_wave, n_group);
+        CS_TRY(hipGetLastError());
+    }
+    if (n_gen_el) {
+        const GenArgs g{sa, d_list + n_wave + n_group, d_goff, n_gen, n_gen_el, g_src.as<uint32_t>(), g_slot.as<uint32_t>(), g_ka.as<ull>(), g_kb.as<ull>(),
+                        g_va.as<uint32_t>(), g_vb.as<uint32_t>(), g_prefix.as<ull>(), g_head_pos.as<uint32_t>()};
+        const uint32_t grid = grid_for(n_gen_el, WG);
+        int slot_bits = 1;
+        while (slot_bits < 32 && (uint64_t(n_gen - 1) >> slot_bits)) ++slot_bits;
+        gen_fill_kernel<<<grid, WG, 0, st.s>>>(g);
+        CS_TRY(hipGetLastError());
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, 64, st.s));
+        gen_key_high_kernel<<<grid, WG, 0, st.s>>>(g);
+        CS_TRY(hipGetLastError());
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.vb, g.va, int(n_gen_el), 0, 64, st.s));
+        gen_key_slot_kernel<<<grid, WG, 0, st.s>>>(g);
+        CS_TRY(hipGetLastError());
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, slot_bits, st.s));
+        gen_flag_kernel<<<grid, WG, 0, st.s>>>(g);
+        CS_TRY(hipGetLastError());
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.va, g.slot, int(n_gen_el), st.s));
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.ka, g.prefix, int(n_gen_el), st.s));
+        gen_head_pos_kernel<<<grid, WG, 0, st.s>>>(g);
+        CS_TRY(hipGetLastError());
+        gen_emit_kernel<<<grid, WG, 0, st.s>>>(g);
+        CS_TRY(hipGetLastError());
+    }
+    tb = cub_bytes;
+    CS_TRY(hipcub::DeviceScan::ExclusiveSum(cub.p, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(counts.as<uint32_t>(), WidenU32()),
+                                            h->d_start.as<ull>(), int(n_docs + 1), st.s));
+    CS_TRY(hipEventRecord(st.mid, st.s));
+    ull n_elements = 0;
+    CS_TRY(hipMemcpyAsync(&n_elements, h->d_start.as<ull>() + n_docs, 8, hipMemcpyDeviceToHost, st.s));
+    CS_TRY(hipStreamSynchronize(st.s));
+    h->n_elements = n_elements;
+    CS_TRY(h->d_key.alloc(16ull * n_elements));
+    CS_TRY(h->d_tf.alloc(4ull * n_elements));
+    CS_TRY(hipEventRecord(st.resume, st.s));
+    if (n_docs) {
+        cast_gather_kernel<<<grid_for(n_docs, WG / 64), WG, 0, st.s>>>(tmp_key.as<Key>(), tmp_tf.as<uint32_t>(), d_doc, h->d_start.as<ull>(), n_docs, d_fn,
+                                                                       h->d_key.as<Key>(), h->d_tf.as<uint32_t>(), h->d_length.as<uint32_t>(),
+                                                                       h->d_fieldnorm.as<uint8_t>());
+        CS_TRY(hipGetLastError());
+    }
+    CS_TRY(hipEventRecord(st.done, st.s));
+    CS_TRY(hipStreamSynchronize(st.s));
+    float ms = 0, ms2 = 0;
+    CS_TRY(hipEventElapsedTime(&ms, st.start, st.mid));
+    CS_TRY(hipEventElapsedTime(&ms2, st.resume, st.done));
+    g_kernel_ms = double(ms) + ms2;
+    *out = h.release();
+    return VBM25_OK;
+}
+
+int documents_download(const vbm25_documents *h, vbm25_growing **csr, uint32_t *doc_len) {
+    if (!csr) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    *csr = nullptr;
+    if (!h) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (int rc = use_device(h->device)) return rc;
+    auto g = std::make_unique<vbm25_growing>();
+    const size_t n = h->n_docs, e = h->n_elements;
+    g->start.assign(n + 1, 0);
+    g->key.resize(16 * e);
+    g->tf.resize(e);
+    g->fieldnorm.resize(n);
+    g->deleted.assign(n, 0);
+    CS_TRY(hipMemcpy(g->start.data(), h->d_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+    if (e) {
+        CS_TRY(hipMemcpy(g->key.data(), h->d_key.p, 16 * e, hipMemcpyDeviceToHost));
+        CS_TRY(hipMemcpy(g->tf.data(), h->d_tf.p, 4 * e, hipMemcpyDeviceToHost));
+    }
+    if (n) {
+        CS_TRY(hipMemcpy(g->fieldnorm.data(), h->d_fieldnorm.p, n, hipMemcpyDeviceToHost));
+        if (h->has_payload) {
+            g->payload.resize(3 * n);
+            CS_TRY(hipMemcpy(g->payload.data(), h->d_payload.p, 6 * n, hipMemcpyDeviceToHost));
+        }
+        if (doc_len) CS_TRY(hipMemcpy(doc_len, h->d_length.p, 4 * n, hipMemcpyDeviceToHost));
+    }
+    *csr = g.release();
+    return VBM25_OK;
+}
+
+int build_documents(const vbm25_documents *h, double k1, double b, vbm25_device_segment **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the device builder has no CPU fallback (vbm25_segment_build is the host builder)");
+    if (!h) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!h->has_payload) return set_error(VBM25_ERR_INVALID, "the documents were cast without payloads: an index needs them");
+    if (!h->n_docs) return set_error(VBM25_ERR_INVALID, "segment without documents");
+    if (int rc = use_device(h->device)) return rc;
+    const uint32_t n = uint32_t(h->n_elements);  // (fewer than 2^31: a cast takes fewer lexemes than that)
+    uint32_t n_terms = 0;
+    std::vector<uint8_t> term_key;
+    std::vector<uint64_t> term_start{0};
+    DBuf ka, kb, va, vb, flags, rank1, cub, post_doc, post_tf, d_tkey, d_tstart;
+    OwnStream st;
+    if (n) {
+        CS_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        size_t sort_b = 0, scan_b = 0;
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n),
+                                                  0, 64, st.s));
+        CS_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n), st.s));
+        const size_t cub_bytes = std::max(sort_b, scan_b);
+        CS_TRY(ka.alloc(8ull * n));
+        CS_TRY(kb.alloc(8ull * n));
+        CS_TRY(va.alloc(4ull * n));
+        CS_TRY(vb.alloc(4ull * n));
+        CS_TRY(flags.alloc(4ull * n));
+        CS_TRY(rank1.alloc(4ull * n));
+        CS_TRY(cub.alloc(cub_bytes));
+        CS_TRY(post_doc.alloc(4ull * n));
+        CS_TRY(post_tf.alloc(4ull * n));
+        const Key *key = h->d_key.as<Key>();
+        const uint32_t grid = grid_for(n, WG);
+        build_key_kernel<<<grid, WG, 0, st.s>>>(key, nullptr, n, 0, ka.as<ull>(), va.as<uint32_t>());
+        CS_TRY(hipGetLastError());
+        size_t tb = cub_bytes;
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, ka.as<ull>(), kb.as<ull>(), va.as<uint32_t>(), vb.as<uint32_t>(), int(n), 0, 64, st.s));
+        build_key_kernel<<<grid, WG, 0, st.s>>>(key, vb.as<uint32_t>(), n, 1, ka.as<ull>(), nullptr);
+        CS_TRY(hipGetLastError());
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, ka.as<ull>(), kb.as<ull>(), vb.as<uint32_t>(), va.as<uint32_t>(), int(n), 0, 64, st.s));
+        build_flag_kernel<<<grid, WG, 0, st.s>>>(key, va.as<uint32_t>(), n, flags.as<uint32_t>());
+        CS_TRY(hipGetLastError());
+        tb = cub_bytes;
+        CS_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, flags.as<uint32_t>(), rank1.as<uint32_t>(), int(n), st.s));
+        CS_TRY(hipMemcpyAsync(&n_terms, rank1.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st.s));
+        CS_TRY(hipStreamSynchronize(st.s));
+        CS_TRY(d_tkey.alloc(16ull * n_terms));
+        CS_TRY(d_tstart.alloc(8ull * (n_terms + 1ull)));
+        build_emit_kernel<<<grid, WG, 0, st.s>>>(key, h->d_tf.as<uint32_t>(), h->d_start.as<ull>(), h->n_docs, va.as<uint32_t>(), flags.as<uint32_t>(),
+                                                 rank1.as<uint32_t>(), n, post_doc.as<uint32_t>(), post_tf.as<uint32_t>(), d_tkey.as<Key>(),
+                                                 d_tstart.as<ull>());
+        CS_TRY(hipGetLastError());
+        term_key.resize(16ull * n_terms);
+        term_start.resize(n_terms + 1ull);
+        CS_TRY(hipMemcpyAsync(term_key.data(), d_tkey.p, 16ull * n_terms, hipMemcpyDeviceToHost, st.s));
+        CS_TRY(hipMemcpyAsync(term_start.data(), d_tstart.p, 8ull * (n_terms + 1ull), hipMemcpyDeviceToHost, st.s));
+        CS_TRY(hipStreamSynchronize(st.s));
+    }
+    std::unique_ptr<vbm25_device_segment> ds;
+    if (int rc = build_device_core(h->device, k1, b, h->n_docs, nullptr, h->d_length.as<uint32_t>(), nullptr, h->d_payload.as<uint16_t>(), n_terms,
+                                   term_key.data(), term_start.data(), nullptr, nullptr, post_doc.as<uint32_t>(), post_tf.as<uint32_t>(), ds))
+        return rc;
+    *out = ds.release();
+    return VBM25_OK;
+}
+
+}  // namespace
+
+namespace vbm25 {
+int cast_tuning_set(const char *name, long long value) {
+    const std::string n(name);
+    std::atomic<uint32_t> &slot = n == "cast_wave_max" ? g_wave_max : g_group_max;
+    const uint32_t bound = n == "cast_wave_max" ? CAST_WAVE_MAX : CAST_GROUP_MAX;
+    if (value < 0 || value > (long long)bound) return set_error(VBM25_ERR_INVALID, "%s %lld is outside 0 .. %u", name, value, bound);
+    slot.store(uint32_t(value));
+    return VBM25_OK;
+}
+void cast_tuning_reset() {
+    g_wave_max.store(CAST_WAVE_MAX);
+    g_group_max.store(CAST_GROUP_MAX);
+}
+}  // namespace vbm25
+
+extern "C" {
+
+int vbm25_documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count,
+                         const uint32_t *doc_lex, uint32_t n_docs, const uint16_t *doc_payload, vbm25_documents **out) {
+    return guarded([&] { return documents_cast(device, seed32, bytes, lex_off, lex_count, doc_lex, n_docs, doc_payload, out); });
+}
+
+int vbm25_documents_info(const vbm25_documents *h, uint32_t *n_docs, uint64_t *n_elements, int *device) {
+    if (!h) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (n_docs) *n_docs = h->n_docs;
+    if (n_elements) *n_elements = h->n_elements;
+    if (device) *device = h->device;
+    return VBM25_OK;
+}
+
+int vbm25_documents_download(const vbm25_documents *h, vbm25_growing **csr, uint32_t *doc_len) {
+    return guarded([&] { return documents_download(h, csr, doc_len); });
+}
+
+uint64_t vbm25_documents_device_bytes(const vbm25_documents *h) { return h ? handle_bytes(h) : 0; }
+
+void vbm25_documents_free(vbm25_documents *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+int vbm25_device_segment_build_documents(const vbm25_documents *h, double k1, double b, vbm25_device_segment **out) {
+    return guarded([&] { return build_documents(h, k1, b, out); });
+}
+
+// tools/cast_cost.py: the device time of the calling thread's last cast's kernels (upload and the host's allocation in front of the
+// gather excluded), by HIP events.  Not in the header.
+int vbm25_debug_cast_kernel_ms(double *ms) {
+    if (!ms || g_kernel_ms < 0) return set_error(VBM25_ERR_INVALID, "no cast on this thread");
+    *ms = g_kernel_ms;
+    return VBM25_OK;
+}
+
+}  // extern "C"

@@ -62,6 +62,17 @@ struct vbm25_device_vacuum {
     vbm25::HbmArray d_sealed_deleted, d_start, d_key, d_tf, d_fieldnorm, d_deleted, d_payload;
 };
 
+// Cast documents in HBM (vbm25_documents_cast, csrc/cast.hip): the CSR cast_tsvector_to_document makes of a batch of tsvectors -- start
+// (n_docs + 1, start[0] == 0), per element the key and the tf (keys strictly ascending inside a document), per document the length, its
+// fieldnorm code and, when the caller gave them, the payload.  Only ever read after it is made.
+struct vbm25_documents {
+    int device = 0;
+    uint32_t n_docs = 0;
+    uint64_t n_elements = 0;
+    bool has_payload = false;
+    vbm25::HbmArray d_start, d_key, d_tf, d_length, d_fieldnorm, d_payload;
+};
+
 namespace vbm25 {
 
 // The encode of flush.hip, everything left in HBM.  Lengths on the host (doc_len) or the device (dev_len); payloads on the host

@@ -36,11 +36,16 @@
 
 #include "vbm25_internal.h"
 #include "resolve_lane.h"
+#include "lexeme_input.h"
 
 namespace {
 
 using namespace vbm25;
 using namespace vbm25::rsv;
+using vbm25::lexin::MAX_LEVELS;
+using vbm25::lexin::NEEDS_SEED;
+using vbm25::lexin::Seed;
+using vbm25::lexin::seed_words;
 
 #define RS_TRY(expr)                                                                                              \
     do {                                                                                                          \
@@ -68,18 +73,12 @@ struct DBuf {
 constexpr uint32_t INTERN_THREADS = 64;   // one wave a block: the LDS stack is 32 bytes a level a lane
 constexpr uint32_t INTERN_GRID = 1024;    // one wave a SIMD of the 256 CUs; more lexemes than 65536 stride the grid
 constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
-constexpr uint32_t MAX_LEVELS = 32;       // 64 KiB of LDS: lexemes up to 2^32 chunks
 constexpr uint32_t WAVE_QUERY = 64;       // the wave path's longest query
-constexpr const char *NEEDS_SEED = "a lexeme of 16 bytes or more needs the index's seed (Meta tuple)";
 
 uint32_t grid_for(uint64_t units, uint32_t per_block) {
     return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block));
 }
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Seed {
-    uint32_t w[8];
-};
 
 // keys_out and ids may each be NULL.  The pool is 4-byte aligned and ends on a multiple of 4 (WordLoad).
 __global__ void __launch_bounds__(INTERN_THREADS) intern_kernel(Seed seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex,
@@ -165,11 +164,6 @@ __global__ void __launch_bounds__(WG_THREADS) emit_kernel(const unsigned long lo
     }
 }
 
-void seed_words(const uint8_t *seed32, Seed *s) {
-    for (int i = 0; i < 8; ++i)
-        s->w[i] = seed32 ? uint32_t(seed32[4 * i]) | uint32_t(seed32[4 * i + 1]) << 8 | uint32_t(seed32[4 * i + 2]) << 16 | uint32_t(seed32[4 * i + 3]) << 24 : 0u;
-}
-
 // what a lexeme batch is, checked before anything is allocated or enqueued
 struct LexShape {
     uint32_t n_lex = 0, longest_query = 0;
@@ -187,21 +181,7 @@ int check_offsets32(const uint32_t *q, uint32_t nq, const char *what, LexShape *
 int check_lexemes(bool has_seed, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq, LexShape *s) {
     if (!q_lex || !lex_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (int rc = check_offsets32(q_lex, nq, "q_lex", s)) return rc;
-    bool hashed = false;
-    for (uint32_t i = 0; i < s->n_lex; ++i) {
-        if (lex_off[i + 1] < lex_off[i]) return set_error(VBM25_ERR_INVALID, "lex_off is not monotone at lexeme %u", i);
-        const uint64_t len = lex_off[i + 1] - lex_off[i];
-        s->longest_lexeme = std::max(s->longest_lexeme, len);
-        hashed |= len >= 16;
-    }
-    s->n_bytes = lex_off[s->n_lex];
-    if (s->n_bytes && !bytes) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (stack_levels(s->longest_lexeme) > MAX_LEVELS) return set_error(VBM25_ERR_INVALID, "a lexeme of %llu bytes is over the resolver's limit", (unsigned long long)s->longest_lexeme);
-    if (!has_seed) {  // (every lexeme is short here or refused: a NUL anywhere in the lexemes' bytes is a NUL inside one of them)
-        if (hashed || (s->n_bytes > lex_off[0] && std::memchr(bytes + lex_off[0], 0, s->n_bytes - lex_off[0])))
-            return set_error(VBM25_ERR_INVALID, "%s", NEEDS_SEED);
-    }
-    return VBM25_OK;
+    return lexin::check_pool(has_seed, bytes, lex_off, s->n_lex, "resolver", &s->n_bytes, &s->longest_lexeme);
 }
 
 int launch_intern(hipStream_t st, const Seed &seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex, uint64_t longest,

@@ -1774,7 +1774,8 @@ int vbm25_evaluate_batch(vbm25_index *ix, const uint32_t *q_terms, uint32_t n_q,
 
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
-// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg.
+// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg; cast_wave_max and cast_group_max (read
+// at the start of each vbm25_documents_cast).
 int vbm25_tuning_set(const char *name, long long value) {
     if (!name) return set_error(VBM25_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> guard(g_tune_mutex);
@@ -1808,6 +1809,9 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "win_cut2") g_tune.win_cut2 = int(std::min<long long>(std::max<long long>(value, 2), 999));
     else if (n == "win_fuse") g_tune.win_fuse = value != 0;
     else if (n == "id16_max_blocks") g_tune.id16_max_blocks = (uint32_t)std::min<long long>(std::max(2ll, value), 0x00ffffffll);
+    else if (n == "cast_wave_max" || n == "cast_group_max") {  // (vbm25_documents_cast's class bounds: cast.hip keeps and reads them)
+        if (int rc = vbm25::cast_tuning_set(name, value)) return rc;
+    }
     else return set_error(VBM25_ERR_INVALID, "unknown tuning switch %s", name);
     ++g_tune.generation;
     return VBM25_OK;
@@ -1817,6 +1821,7 @@ void vbm25_tuning_reset(void) {
     const uint32_t gen = g_tune.generation + 1u;
     g_tune = Tuning();
     g_tune.generation = gen;
+    vbm25::cast_tuning_reset();
 }
 
 // the current queries' kernels make their work items themselves and merge_kernel cleans up behind them
@@ -2327,11 +2332,12 @@ static int reserve_spare(DeviceBuffer &b, size_t need) {
 
 constexpr size_t GROW_STAGE_KEEP = 16u << 20;  // a larger stage (a bulk append) is released at the end of the call
 
-static int device_growing_append_impl(vbm25_device_growing *gs, const vbm25_growing_desc *d) {
-    if (!gs || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+// The append behind its checks.  The delta's arrays (d's, its elements e_first .. e_first + n_el) are on the host (`kind`
+// hipMemcpyHostToDevice: vbm25_device_growing_append) or in HBM on the segment's device (hipMemcpyDeviceToDevice:
+// vbm25_device_growing_append_documents); they go into the stage either way, and everything behind the copies reads the stage.
+// With hipMemcpyDeviceToDevice no pointer of `d` may be dereferenced on the host: this body only hands them to hipMemcpy.
+static int device_growing_append_core(vbm25_device_growing *gs, const vbm25_growing_desc *d, uint64_t e_first, uint64_t n_el, hipMemcpyKind kind) {
     const vbm25_index *ix = gs->index;
-    uint64_t e_first = 0, n_el = 0;
-    if (int rc = growing_desc_check(ix, d, gs->n_grow, gs->n_post, &e_first, &n_el)) return rc;
     const uint32_t n = d->n_docs, g0 = gs->n_grow, nt = ix->n_terms;
     if (!n) return VBM25_OK;
     if (uint64_t(g0) + n > 0xffffffffull) return set_error(VBM25_ERR_INVALID, "%llu growing documents: at most 2^32 - 1", (unsigned long long)g0 + n);
@@ -2380,15 +2386,15 @@ static int device_growing_append_impl(vbm25_device_growing *gs, const vbm25_grow
     uint32_t *cnt = static_cast<uint32_t *>(at(o_cnt)), *ins = static_cast<uint32_t *>(at(o_ins)), *flags = static_cast<uint32_t *>(at(o_flags)),
              *offs = static_cast<uint32_t *>(at(o_offs)), *tterm = static_cast<uint32_t *>(at(o_tterm));
     uint8_t *fn = static_cast<uint8_t *>(at(o_fn)), *del = static_cast<uint8_t *>(at(o_del));
-    HIP_TRY(hipMemcpy(start, d->start, 8ull * (n + 1ull), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(fn, d->fieldnorm, n, hipMemcpyHostToDevice));
-    if (d->deleted) HIP_TRY(hipMemcpy(del, d->deleted, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(start, d->start, 8ull * (n + 1ull), kind));
+    HIP_TRY(hipMemcpy(fn, d->fieldnorm, n, kind));
+    if (d->deleted) HIP_TRY(hipMemcpy(del, d->deleted, n, kind));
     HIP_TRY(hipMemsetAsync(cnt, 0, 8));
     // 1. the delta's postings as sorted (term, g) keys
     uint32_t n_dpost = 0;
     if (n_el) {
-        HIP_TRY(hipMemcpy(at(o_key), d->key + 16ull * e_first, 16ull * n_el, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(tf, d->tf + e_first, 4ull * n_el, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(at(o_key), d->key + 16ull * e_first, 16ull * n_el, kind));
+        HIP_TRY(hipMemcpy(tf, d->tf + e_first, 4ull * n_el, kind));
         grow_append_map_kernel<<<uint32_t((n_el + 255) / 256), 256>>>(gs->term_key.as<ulonglong2>(), nt, n, g0, start, uint32_t(n_el),
                                                                       static_cast<const ulonglong2 *>(at(o_key)), tf,
                                                                       d->deleted ? del : nullptr, keys, vals, cnt);
@@ -2407,7 +2413,7 @@ static int device_growing_append_impl(vbm25_device_growing *gs, const vbm25_grow
         if (g0) HIP_TRY(hipMemcpyAsync(new_payload.p, gs->payload.p, 6ull * g0, hipMemcpyDeviceToDevice));
     }
     uint16_t *payload = new_payload.p ? new_payload.as<uint16_t>() : gs->payload.as<uint16_t>();
-    HIP_TRY(hipMemcpy(payload + 3ull * g0, d->payload, 6ull * n, hipMemcpyHostToDevice));  // (behind the documents the searches read)
+    HIP_TRY(hipMemcpy(payload + 3ull * g0, d->payload, 6ull * n, kind));  // (behind the documents the searches read)
     // 2 - 4. the merged postings and their term starts
     uint32_t *new_start = gs->term_start2.as<uint32_t>(), *new_g = gs->post_g2.as<uint32_t>();
     double *new_c = gs->post_c2.as<double>();
@@ -2444,6 +2450,41 @@ static int device_growing_append_impl(vbm25_device_growing *gs, const vbm25_grow
     gs->n_tiles = n_tiles;
     gs->n_post = n_post;
     return VBM25_OK;
+}
+
+static int device_growing_append_impl(vbm25_device_growing *gs, const vbm25_growing_desc *d) {
+    if (!gs || !d) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    uint64_t e_first = 0, n_el = 0;
+    if (int rc = growing_desc_check(gs->index, d, gs->n_grow, gs->n_post, &e_first, &n_el)) return rc;
+    return device_growing_append_core(gs, d, e_first, n_el, hipMemcpyHostToDevice);
+}
+
+// vbm25_device_growing_append_documents: the delta is a cast's arrays in HBM.  Its keys are strictly ascending inside a document and
+// its start is monotone by construction; the checks of growing_desc_check that read no element data apply.
+static int device_growing_append_documents_impl(vbm25_device_growing *gs, const vbm25_documents *h) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return set_error(VBM25_ERR_DEVICE, "no HIP device: the growing segment has no host fallback");
+    if (!gs || !h) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (h->device != gs->device) return set_error(VBM25_ERR_INVALID, "the documents are on device %d, the segment on device %d", h->device, gs->device);
+    if (!h->has_payload) return set_error(VBM25_ERR_INVALID, "the documents were cast without payloads: a growing segment needs them");
+    const vbm25_index *ix = gs->index;
+    if (uint64_t(ix->n_docs) + gs->n_grow + h->n_docs > (1ull << 32))
+        return set_error(VBM25_ERR_INVALID, "%u sealed + %llu growing documents exceed 2^32: the doc id ranges would collide", ix->n_docs,
+                         (unsigned long long)gs->n_grow + h->n_docs);
+    if (gs->n_post + h->n_elements >= (1ull << 31))
+        return set_error(VBM25_ERR_UNSUPPORTED, "%llu growing elements: the device path takes fewer than 2^31", (unsigned long long)(gs->n_post + h->n_elements));
+    // CAUTION: this desc's pointers are in HBM.  It exists only to be handed to device_growing_append_core with
+    // hipMemcpyDeviceToDevice, which passes them to hipMemcpy and reads none on the host; nothing else may take it.
+    vbm25_growing_desc d{};
+    d.n_docs = h->n_docs;
+    d.n_elements = h->n_elements;
+    d.start = h->d_start.as<uint64_t>();
+    d.key = h->d_key.as<uint8_t>();
+    d.tf = h->d_tf.as<uint32_t>();
+    d.fieldnorm = h->d_fieldnorm.as<uint8_t>();
+    d.payload = h->d_payload.as<uint16_t>();
+    d.deleted = nullptr;
+    return device_growing_append_core(gs, &d, 0, h->n_elements, hipMemcpyDeviceToDevice);
 }
 
 static int device_growing_delete_impl(vbm25_device_growing *gs, const uint32_t *g, uint32_t n) {
@@ -2908,6 +2949,9 @@ uint64_t vbm25_device_growing_bytes(const vbm25_device_growing *gs) { return gs 
 uint32_t vbm25_device_growing_docs(const vbm25_device_growing *gs) { return gs ? gs->n_grow : 0; }
 int vbm25_device_growing_append(vbm25_device_growing *gs, const vbm25_growing_desc *delta) {
     return guarded([&] { return device_growing_append_impl(gs, delta); });
+}
+int vbm25_device_growing_append_documents(vbm25_device_growing *gs, const vbm25_documents *documents) {
+    return guarded([&] { return device_growing_append_documents_impl(gs, documents); });
 }
 int vbm25_device_growing_delete(vbm25_device_growing *gs, const uint32_t *g, uint32_t n) {
     return guarded([&] { return device_growing_delete_impl(gs, g, n); });

@@ -79,6 +79,10 @@ int index_device_and_docs(const vbm25_index *ix, int *device, uint32_t *n_docs);
 int index_vocabulary(const vbm25_index *ix, int *device, uint32_t *n_terms, const uint8_t **term_key);
 // the device half of vbm25_growing_upload; synchronous, the arrays may be freed when it returns
 int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vbm25_device_growing **out);
+// vbm25_tuning_set's cast_wave_max / cast_group_max (cast.hip keeps them: the class bounds of vbm25_documents_cast, 0 = class off,
+// values over the built-in bounds refused) and their reset
+int cast_tuning_set(const char *name, long long value);
+void cast_tuning_reset();
 
 }  // namespace vbm25
 
