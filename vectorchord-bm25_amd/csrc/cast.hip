@@ -52,53 +52,6 @@ using vbm25::lexin::Seed;
 using vbm25::lexin::seed_words;
 using ull = unsigned long long;
 
-#define CS_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DBuf() = default;
-    DBuf(const DBuf &) = delete;
-    DBuf &operator=(const DBuf &) = delete;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        bytes = n ? n : 16;
-        return hipMalloc(&p, bytes);
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-struct Pinned {
-    uint8_t *p = nullptr;
-    ~Pinned() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-// (a stream of the call's own: a launch on the null stream would wait for every other stream of the device)
-struct OwnStream {
-    hipStream_t s = nullptr;
-    hipEvent_t start = nullptr, mid = nullptr, resume = nullptr, done = nullptr;
-    ~OwnStream() {
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-        if (start) (void)hipEventDestroy(start);
-        if (done) (void)hipEventDestroy(done);
-        if (mid) (void)hipEventDestroy(mid);
-        if (resume) (void)hipEventDestroy(resume);
-    }
-};
-
 constexpr uint32_t INTERN_THREADS = 64;  // one wave a block: the LDS stack is 32 bytes a level a lane
 constexpr uint32_t INTERN_GRID = 1024;   // more lexemes than 65536 stride the grid
 constexpr uint32_t WG = 256, MAX_GRID = 2048;
@@ -108,15 +61,6 @@ std::atomic<uint32_t> g_wave_max{CAST_WAVE_MAX}, g_group_max{CAST_GROUP_MAX};
 // the calling thread's last cast: its kernels by HIP events -- upload excluded, and so is the host's allocation of key / tf between
 // the scan and the gather (two spans: upload's end .. the scan's end, the gather's start .. its end)
 thread_local double g_kernel_ms = -1.0;
-
-uint32_t grid_for(uint64_t units, uint32_t per_block) {
-    return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block));
-}
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct WidenU32 {
-    __host__ __device__ ull operator()(uint32_t v) const { return v; }
-};
 
 // The pool is 4-byte aligned and ends on a multiple of 4 (WordLoad).
 __global__ void __launch_bounds__(INTERN_THREADS) cast_intern_kernel(Seed seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex,
@@ -361,13 +305,13 @@ __global__ void __launch_bounds__(WG) build_emit_kernel(const Key *key, const ui
     }
 }
 
-int use_device(int device) {
+// the device of a cast: checked to be there, then made the calling thread's
+int use_cast_device(int device) {
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the document cast has no host fallback");
     if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
-    CS_TRY(hipSetDevice(device));
-    return VBM25_OK;
+    return use_device(device);
 }
 
 // what a batch of documents is, checked before anything is allocated or enqueued
@@ -416,7 +360,7 @@ int documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, cons
     }
     const uint32_t n_lex = sh.n_lex, n_wave = uint32_t(lists[0].size()), n_group = uint32_t(lists[1].size()), n_gen = uint32_t(lists[2].size()),
                    n_gen_el = gen_off.back();
-    if (int rc = use_device(device)) return rc;
+    if (int rc = use_cast_device(device)) return rc;
     g_kernel_ms = -1.0;
 
     auto h = std::make_unique<vbm25_documents>();
@@ -434,138 +378,143 @@ int documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, cons
     };
     const size_t o_doc = take(4ull * (n_docs + 1ull)), o_off = take(8ull * (n_lex + 1ull)), o_cnt = take(4ull * n_lex), o_list = take(4ull * n_docs),
                  o_goff = take(4ull * (n_gen + 1ull)), o_fn = take(4 * 256), o_pay = take(doc_payload ? 6ull * n_docs : 0), o_bytes = take(sh.n_bytes);
-    Pinned stage;
-    DBuf in, keys, tmp_key, tmp_tf, counts, cub, g_src, g_slot, g_ka, g_kb, g_va, g_vb, g_prefix, g_head_pos;
-    OwnStream st;  // (declared behind the buffers, so destroyed -- and waited for -- before they are freed)
-    CS_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    CS_TRY(hipEventCreate(&st.start));
-    CS_TRY(hipEventCreate(&st.done));
-    CS_TRY(hipEventCreate(&st.mid));
-    CS_TRY(hipEventCreate(&st.resume));
-    CS_TRY(hipHostMalloc((void **)&stage.p, total, hipHostMallocDefault));
-    std::memcpy(stage.p + o_doc, doc_lex, 4ull * (n_docs + 1ull));
-    std::memcpy(stage.p + o_off, lex_off, 8ull * (n_lex + 1ull));
-    if (n_lex) std::memcpy(stage.p + o_cnt, lex_count, 4ull * n_lex);
+    PinnedHost stage;
+    HbmArray in, keys, tmp_key, tmp_tf, counts, cub, g_src, g_slot, g_ka, g_kb, g_va, g_vb, g_prefix, g_head_pos;
+    // a stream of the call's own (a launch on the null stream would wait for every other stream of the device), declared behind the
+    // buffers and waited for by `quiesce` behind it: the stream is idle before it is destroyed, and both before anything is freed
+    Event ev_start, ev_mid, ev_resume, ev_done;
+    Stream st;
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    Quiesce quiesce(st.s);
+    HIP_TRY(hipEventCreate(&ev_start.e));
+    HIP_TRY(hipEventCreate(&ev_done.e));
+    HIP_TRY(hipEventCreate(&ev_mid.e));
+    HIP_TRY(hipEventCreate(&ev_resume.e));
+    HIP_TRY(hipHostMalloc((void **)&stage.p, total, hipHostMallocDefault));
+    uint8_t *const staged = stage.as<uint8_t>();
+    std::memcpy(staged + o_doc, doc_lex, 4ull * (n_docs + 1ull));
+    std::memcpy(staged + o_off, lex_off, 8ull * (n_lex + 1ull));
+    if (n_lex) std::memcpy(staged + o_cnt, lex_count, 4ull * n_lex);
     {
         size_t at = o_list;
         for (const auto &l : lists) {
-            if (!l.empty()) std::memcpy(stage.p + at, l.data(), 4ull * l.size());
+            if (!l.empty()) std::memcpy(staged + at, l.data(), 4ull * l.size());
             at += 4ull * l.size();
         }
     }
-    std::memcpy(stage.p + o_goff, gen_off.data(), 4ull * gen_off.size());
-    std::memcpy(stage.p + o_fn, fieldnorm_lengths(), 4 * 256);
-    if (doc_payload && n_docs) std::memcpy(stage.p + o_pay, doc_payload, 6ull * n_docs);
-    if (sh.n_bytes) std::memcpy(stage.p + o_bytes, bytes, sh.n_bytes);
-    if (total > o_bytes + sh.n_bytes) std::memset(stage.p + o_bytes + sh.n_bytes, 0, total - o_bytes - sh.n_bytes);
+    std::memcpy(staged + o_goff, gen_off.data(), 4ull * gen_off.size());
+    std::memcpy(staged + o_fn, fieldnorm_lengths(), 4 * 256);
+    if (doc_payload && n_docs) std::memcpy(staged + o_pay, doc_payload, 6ull * n_docs);
+    if (sh.n_bytes) std::memcpy(staged + o_bytes, bytes, sh.n_bytes);
+    if (total > o_bytes + sh.n_bytes) std::memset(staged + o_bytes + sh.n_bytes, 0, total - o_bytes - sh.n_bytes);
 
     size_t cub_bytes = 0, tb = 0;
-    CS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
                                             (ull *)nullptr, int(n_docs + 1), st.s));
     cub_bytes = std::max(cub_bytes, tb);
     if (n_gen_el) {
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                                   int(n_gen_el), 0, 64, st.s));
         cub_bytes = std::max(cub_bytes, tb);
-        CS_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n_gen_el), st.s));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n_gen_el), st.s));
         cub_bytes = std::max(cub_bytes, tb);
-        CS_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, int(n_gen_el), st.s));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, int(n_gen_el), st.s));
         cub_bytes = std::max(cub_bytes, tb);
     }
-    CS_TRY(in.alloc(total));
-    CS_TRY(keys.alloc(16ull * n_lex));
-    CS_TRY(tmp_key.alloc(16ull * n_lex));
-    CS_TRY(tmp_tf.alloc(4ull * n_lex));
-    CS_TRY(counts.alloc(4ull * (n_docs + 1ull)));
-    CS_TRY(cub.alloc(cub_bytes));
-    CS_TRY(h->d_start.alloc(8ull * (n_docs + 1ull)));
-    CS_TRY(h->d_length.alloc(4ull * n_docs));
-    CS_TRY(h->d_fieldnorm.alloc(n_docs));
-    if (doc_payload) CS_TRY(h->d_payload.alloc(6ull * n_docs));
+    HIP_TRY(in.alloc(total));
+    HIP_TRY(keys.alloc(16ull * n_lex));
+    HIP_TRY(tmp_key.alloc(16ull * n_lex));
+    HIP_TRY(tmp_tf.alloc(4ull * n_lex));
+    HIP_TRY(counts.alloc(4ull * (n_docs + 1ull)));
+    HIP_TRY(cub.alloc(cub_bytes));
+    HIP_TRY(h->d_start.alloc(8ull * (n_docs + 1ull)));
+    HIP_TRY(h->d_length.alloc(4ull * n_docs));
+    HIP_TRY(h->d_fieldnorm.alloc(n_docs));
+    if (doc_payload) HIP_TRY(h->d_payload.alloc(6ull * n_docs));
     if (n_gen_el) {
-        CS_TRY(g_src.alloc(4ull * n_gen_el));
-        CS_TRY(g_slot.alloc(4ull * n_gen_el));
-        CS_TRY(g_ka.alloc(8ull * n_gen_el));
-        CS_TRY(g_kb.alloc(8ull * n_gen_el));
-        CS_TRY(g_va.alloc(4ull * n_gen_el));
-        CS_TRY(g_vb.alloc(4ull * n_gen_el));
-        CS_TRY(g_prefix.alloc(8ull * n_gen_el));
-        CS_TRY(g_head_pos.alloc(4ull * (n_gen_el + 1ull)));
+        HIP_TRY(g_src.alloc(4ull * n_gen_el));
+        HIP_TRY(g_slot.alloc(4ull * n_gen_el));
+        HIP_TRY(g_ka.alloc(8ull * n_gen_el));
+        HIP_TRY(g_kb.alloc(8ull * n_gen_el));
+        HIP_TRY(g_va.alloc(4ull * n_gen_el));
+        HIP_TRY(g_vb.alloc(4ull * n_gen_el));
+        HIP_TRY(g_prefix.alloc(8ull * n_gen_el));
+        HIP_TRY(g_head_pos.alloc(4ull * (n_gen_el + 1ull)));
     }
     uint8_t *d = in.as<uint8_t>();
-    CS_TRY(hipMemcpyAsync(d, stage.p, total, hipMemcpyHostToDevice, st.s));
-    if (doc_payload && n_docs) CS_TRY(hipMemcpyAsync(h->d_payload.p, stage.p + o_pay, 6ull * n_docs, hipMemcpyHostToDevice, st.s));
-    CS_TRY(hipEventRecord(st.start, st.s));
-    CS_TRY(hipMemsetAsync(counts.p, 0, 4ull * (n_docs + 1ull), st.s));
+    HIP_TRY(hipMemcpyAsync(d, stage.p, total, hipMemcpyHostToDevice, st.s));
+    if (doc_payload && n_docs) HIP_TRY(hipMemcpyAsync(h->d_payload.p, staged + o_pay, 6ull * n_docs, hipMemcpyHostToDevice, st.s));
+    HIP_TRY(hipEventRecord(ev_start.e, st.s));
+    HIP_TRY(hipMemsetAsync(counts.p, 0, 4ull * (n_docs + 1ull), st.s));
     const uint32_t *d_doc = reinterpret_cast<const uint32_t *>(d + o_doc), *d_cnt = reinterpret_cast<const uint32_t *>(d + o_cnt),
                    *d_list = reinterpret_cast<const uint32_t *>(d + o_list), *d_goff = reinterpret_cast<const uint32_t *>(d + o_goff),
                    *d_fn = reinterpret_cast<const uint32_t *>(d + o_fn);
     const SortArgs sa{keys.as<Key>(), d_cnt, d_doc, tmp_key.as<Key>(), tmp_tf.as<uint32_t>(), counts.as<uint32_t>()};
     if (n_lex) {
         const size_t lds = size_t(stack_levels(sh.longest_lexeme)) * 8 * sizeof(uint32_t) * INTERN_THREADS;
-        cast_intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS)), INTERN_THREADS, lds, st.s>>>(
+        cast_intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS, MAX_GRID)), INTERN_THREADS, lds, st.s>>>(
             seed, reinterpret_cast<const uint32_t *>(d + o_bytes), reinterpret_cast<const uint64_t *>(d + o_off), n_lex, keys.as<Key>());
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (n_wave && n_lex) {
-        cast_wave_kernel<<<grid_for(n_wave, WG / 64), WG, 0, st.s>>>(sa, d_list, n_wave);
-        CS_TRY(hipGetLastError());
+        cast_wave_kernel<<<grid_for(n_wave, WG / 64, MAX_GRID), WG, 0, st.s>>>(sa, d_list, n_wave);
+        HIP_TRY(hipGetLastError());
     }
     if (n_group && n_lex) {
-        cast_group_kernel<<<grid_for(n_group, 1), WG, 0, st.s>>>(sa, d_list + n_wave, n_group);
-        CS_TRY(hipGetLastError());
+        cast_group_kernel<<<grid_for(n_group, 1, MAX_GRID), WG, 0, st.s>>>(sa, d_list + n_wave, n_group);
+        HIP_TRY(hipGetLastError());
     }
     if (n_gen_el) {
         const GenArgs g{sa, d_list + n_wave + n_group, d_goff, n_gen, n_gen_el, g_src.as<uint32_t>(), g_slot.as<uint32_t>(), g_ka.as<ull>(), g_kb.as<ull>(),
                         g_va.as<uint32_t>(), g_vb.as<uint32_t>(), g_prefix.as<ull>(), g_head_pos.as<uint32_t>()};
-        const uint32_t grid = grid_for(n_gen_el, WG);
+        const uint32_t grid = grid_for(n_gen_el, WG, MAX_GRID);
         int slot_bits = 1;
         while (slot_bits < 32 && (uint64_t(n_gen - 1) >> slot_bits)) ++slot_bits;
         gen_fill_kernel<<<grid, WG, 0, st.s>>>(g);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, 64, st.s));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, 64, st.s));
         gen_key_high_kernel<<<grid, WG, 0, st.s>>>(g);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.vb, g.va, int(n_gen_el), 0, 64, st.s));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.vb, g.va, int(n_gen_el), 0, 64, st.s));
         gen_key_slot_kernel<<<grid, WG, 0, st.s>>>(g);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, slot_bits, st.s));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, slot_bits, st.s));
         gen_flag_kernel<<<grid, WG, 0, st.s>>>(g);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.va, g.slot, int(n_gen_el), st.s));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.va, g.slot, int(n_gen_el), st.s));
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.ka, g.prefix, int(n_gen_el), st.s));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.ka, g.prefix, int(n_gen_el), st.s));
         gen_head_pos_kernel<<<grid, WG, 0, st.s>>>(g);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         gen_emit_kernel<<<grid, WG, 0, st.s>>>(g);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     tb = cub_bytes;
-    CS_TRY(hipcub::DeviceScan::ExclusiveSum(cub.p, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(counts.as<uint32_t>(), WidenU32()),
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub.p, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(counts.as<uint32_t>(), WidenU32()),
                                             h->d_start.as<ull>(), int(n_docs + 1), st.s));
-    CS_TRY(hipEventRecord(st.mid, st.s));
+    HIP_TRY(hipEventRecord(ev_mid.e, st.s));
     ull n_elements = 0;
-    CS_TRY(hipMemcpyAsync(&n_elements, h->d_start.as<ull>() + n_docs, 8, hipMemcpyDeviceToHost, st.s));
-    CS_TRY(hipStreamSynchronize(st.s));
+    HIP_TRY(hipMemcpyAsync(&n_elements, h->d_start.as<ull>() + n_docs, 8, hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
     h->n_elements = n_elements;
-    CS_TRY(h->d_key.alloc(16ull * n_elements));
-    CS_TRY(h->d_tf.alloc(4ull * n_elements));
-    CS_TRY(hipEventRecord(st.resume, st.s));
+    HIP_TRY(h->d_key.alloc(16ull * n_elements));
+    HIP_TRY(h->d_tf.alloc(4ull * n_elements));
+    HIP_TRY(hipEventRecord(ev_resume.e, st.s));
     if (n_docs) {
-        cast_gather_kernel<<<grid_for(n_docs, WG / 64), WG, 0, st.s>>>(tmp_key.as<Key>(), tmp_tf.as<uint32_t>(), d_doc, h->d_start.as<ull>(), n_docs, d_fn,
+        cast_gather_kernel<<<grid_for(n_docs, WG / 64, MAX_GRID), WG, 0, st.s>>>(tmp_key.as<Key>(), tmp_tf.as<uint32_t>(), d_doc, h->d_start.as<ull>(), n_docs, d_fn,
                                                                        h->d_key.as<Key>(), h->d_tf.as<uint32_t>(), h->d_length.as<uint32_t>(),
                                                                        h->d_fieldnorm.as<uint8_t>());
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    CS_TRY(hipEventRecord(st.done, st.s));
-    CS_TRY(hipStreamSynchronize(st.s));
+    HIP_TRY(hipEventRecord(ev_done.e, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
     float ms = 0, ms2 = 0;
-    CS_TRY(hipEventElapsedTime(&ms, st.start, st.mid));
-    CS_TRY(hipEventElapsedTime(&ms2, st.resume, st.done));
+    HIP_TRY(hipEventElapsedTime(&ms, ev_start.e, ev_mid.e));
+    HIP_TRY(hipEventElapsedTime(&ms2, ev_resume.e, ev_done.e));
     g_kernel_ms = double(ms) + ms2;
     *out = h.release();
     return VBM25_OK;
@@ -575,7 +524,7 @@ int documents_download(const vbm25_documents *h, vbm25_growing **csr, uint32_t *
     if (!csr) return set_error(VBM25_ERR_INVALID, "NULL argument");
     *csr = nullptr;
     if (!h) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (int rc = use_device(h->device)) return rc;
+    if (int rc = use_cast_device(h->device)) return rc;
     auto g = std::make_unique<vbm25_growing>();
     const size_t n = h->n_docs, e = h->n_elements;
     g->start.assign(n + 1, 0);
@@ -583,18 +532,18 @@ int documents_download(const vbm25_documents *h, vbm25_growing **csr, uint32_t *
     g->tf.resize(e);
     g->fieldnorm.resize(n);
     g->deleted.assign(n, 0);
-    CS_TRY(hipMemcpy(g->start.data(), h->d_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(g->start.data(), h->d_start.p, 8 * (n + 1), hipMemcpyDeviceToHost));
     if (e) {
-        CS_TRY(hipMemcpy(g->key.data(), h->d_key.p, 16 * e, hipMemcpyDeviceToHost));
-        CS_TRY(hipMemcpy(g->tf.data(), h->d_tf.p, 4 * e, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(g->key.data(), h->d_key.p, 16 * e, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(g->tf.data(), h->d_tf.p, 4 * e, hipMemcpyDeviceToHost));
     }
     if (n) {
-        CS_TRY(hipMemcpy(g->fieldnorm.data(), h->d_fieldnorm.p, n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(g->fieldnorm.data(), h->d_fieldnorm.p, n, hipMemcpyDeviceToHost));
         if (h->has_payload) {
             g->payload.resize(3 * n);
-            CS_TRY(hipMemcpy(g->payload.data(), h->d_payload.p, 6 * n, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(g->payload.data(), h->d_payload.p, 6 * n, hipMemcpyDeviceToHost));
         }
-        if (doc_len) CS_TRY(hipMemcpy(doc_len, h->d_length.p, 4 * n, hipMemcpyDeviceToHost));
+        if (doc_len) HIP_TRY(hipMemcpy(doc_len, h->d_length.p, 4 * n, hipMemcpyDeviceToHost));
     }
     *csr = g.release();
     return VBM25_OK;
@@ -609,56 +558,58 @@ int build_documents(const vbm25_documents *h, double k1, double b, vbm25_device_
     if (!h) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (!h->has_payload) return set_error(VBM25_ERR_INVALID, "the documents were cast without payloads: an index needs them");
     if (!h->n_docs) return set_error(VBM25_ERR_INVALID, "segment without documents");
-    if (int rc = use_device(h->device)) return rc;
+    if (int rc = use_cast_device(h->device)) return rc;
     const uint32_t n = uint32_t(h->n_elements);  // (fewer than 2^31: a cast takes fewer lexemes than that)
     uint32_t n_terms = 0;
     std::vector<uint8_t> term_key;
     std::vector<uint64_t> term_start{0};
-    DBuf ka, kb, va, vb, flags, rank1, cub, post_doc, post_tf, d_tkey, d_tstart;
-    OwnStream st;
+    HbmArray ka, kb, va, vb, flags, rank1, cub, post_doc, post_tf, d_tkey, d_tstart;
+    Stream st;  // (of the call's own, as the cast's)
+    Quiesce quiesce;
     if (n) {
-        CS_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        quiesce.s = st.s;
         size_t sort_b = 0, scan_b = 0;
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n),
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n),
                                                   0, 64, st.s));
-        CS_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n), st.s));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n), st.s));
         const size_t cub_bytes = std::max(sort_b, scan_b);
-        CS_TRY(ka.alloc(8ull * n));
-        CS_TRY(kb.alloc(8ull * n));
-        CS_TRY(va.alloc(4ull * n));
-        CS_TRY(vb.alloc(4ull * n));
-        CS_TRY(flags.alloc(4ull * n));
-        CS_TRY(rank1.alloc(4ull * n));
-        CS_TRY(cub.alloc(cub_bytes));
-        CS_TRY(post_doc.alloc(4ull * n));
-        CS_TRY(post_tf.alloc(4ull * n));
+        HIP_TRY(ka.alloc(8ull * n));
+        HIP_TRY(kb.alloc(8ull * n));
+        HIP_TRY(va.alloc(4ull * n));
+        HIP_TRY(vb.alloc(4ull * n));
+        HIP_TRY(flags.alloc(4ull * n));
+        HIP_TRY(rank1.alloc(4ull * n));
+        HIP_TRY(cub.alloc(cub_bytes));
+        HIP_TRY(post_doc.alloc(4ull * n));
+        HIP_TRY(post_tf.alloc(4ull * n));
         const Key *key = h->d_key.as<Key>();
-        const uint32_t grid = grid_for(n, WG);
+        const uint32_t grid = grid_for(n, WG, MAX_GRID);
         build_key_kernel<<<grid, WG, 0, st.s>>>(key, nullptr, n, 0, ka.as<ull>(), va.as<uint32_t>());
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         size_t tb = cub_bytes;
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, ka.as<ull>(), kb.as<ull>(), va.as<uint32_t>(), vb.as<uint32_t>(), int(n), 0, 64, st.s));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, ka.as<ull>(), kb.as<ull>(), va.as<uint32_t>(), vb.as<uint32_t>(), int(n), 0, 64, st.s));
         build_key_kernel<<<grid, WG, 0, st.s>>>(key, vb.as<uint32_t>(), n, 1, ka.as<ull>(), nullptr);
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, ka.as<ull>(), kb.as<ull>(), vb.as<uint32_t>(), va.as<uint32_t>(), int(n), 0, 64, st.s));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, ka.as<ull>(), kb.as<ull>(), vb.as<uint32_t>(), va.as<uint32_t>(), int(n), 0, 64, st.s));
         build_flag_kernel<<<grid, WG, 0, st.s>>>(key, va.as<uint32_t>(), n, flags.as<uint32_t>());
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         tb = cub_bytes;
-        CS_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, flags.as<uint32_t>(), rank1.as<uint32_t>(), int(n), st.s));
-        CS_TRY(hipMemcpyAsync(&n_terms, rank1.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st.s));
-        CS_TRY(hipStreamSynchronize(st.s));
-        CS_TRY(d_tkey.alloc(16ull * n_terms));
-        CS_TRY(d_tstart.alloc(8ull * (n_terms + 1ull)));
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, flags.as<uint32_t>(), rank1.as<uint32_t>(), int(n), st.s));
+        HIP_TRY(hipMemcpyAsync(&n_terms, rank1.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipStreamSynchronize(st.s));
+        HIP_TRY(d_tkey.alloc(16ull * n_terms));
+        HIP_TRY(d_tstart.alloc(8ull * (n_terms + 1ull)));
         build_emit_kernel<<<grid, WG, 0, st.s>>>(key, h->d_tf.as<uint32_t>(), h->d_start.as<ull>(), h->n_docs, va.as<uint32_t>(), flags.as<uint32_t>(),
                                                  rank1.as<uint32_t>(), n, post_doc.as<uint32_t>(), post_tf.as<uint32_t>(), d_tkey.as<Key>(),
                                                  d_tstart.as<ull>());
-        CS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         term_key.resize(16ull * n_terms);
         term_start.resize(n_terms + 1ull);
-        CS_TRY(hipMemcpyAsync(term_key.data(), d_tkey.p, 16ull * n_terms, hipMemcpyDeviceToHost, st.s));
-        CS_TRY(hipMemcpyAsync(term_start.data(), d_tstart.p, 8ull * (n_terms + 1ull), hipMemcpyDeviceToHost, st.s));
-        CS_TRY(hipStreamSynchronize(st.s));
+        HIP_TRY(hipMemcpyAsync(term_key.data(), d_tkey.p, 16ull * n_terms, hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipMemcpyAsync(term_start.data(), d_tstart.p, 8ull * (n_terms + 1ull), hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipStreamSynchronize(st.s));
     }
     std::unique_ptr<vbm25_device_segment> ds;
     if (int rc = build_device_core(h->device, k1, b, h->n_docs, nullptr, h->d_length.as<uint32_t>(), nullptr, h->d_payload.as<uint16_t>(), n_terms,

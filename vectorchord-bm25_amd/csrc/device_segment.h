@@ -4,36 +4,12 @@
 #ifndef VBM25_DEVICE_SEGMENT_H
 #define VBM25_DEVICE_SEGMENT_H
 
-#include <hip/hip_runtime.h>
-
 #include <cstdint>
 #include <memory>
 #include <vector>
 
 #include "../../include/vbm25.h"
-
-namespace vbm25 {
-
-struct HbmArray {
-    void *p = nullptr;
-    size_t bytes = 0;
-    HbmArray() = default;
-    HbmArray(const HbmArray &) = delete;
-    HbmArray &operator=(const HbmArray &) = delete;
-    ~HbmArray() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        bytes = n;
-        return hipMalloc(&p, n ? n : 16);
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
-}  // namespace vbm25
+#include "hip_host.h"
 
 // The values flush.rs:40-158 writes to the Token / Summary / Block / Document tapes (the arrays of vbm25_index_desc), in the
 // HBM of `device`; the few things the host needs again (keys for the token lookup, block counts) as host copies.

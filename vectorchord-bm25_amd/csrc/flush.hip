@@ -31,29 +31,6 @@ namespace {
 
 using namespace vbm25;
 
-#define FL_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
-struct WidenU32 {
-    __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
-};
-
 struct FlushArgs {
     uint32_t n_docs, n_terms, n_blocks;
     const uint64_t *term_start;         // n_terms + 1
@@ -336,7 +313,7 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the device builder has no CPU fallback (vbm25_segment_build is the host builder)");
     if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
-    FL_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     g_encode_link[0] = g_encode_link[1] = 0.0;
 
     auto ds = std::make_unique<vbm25_device_segment>();
@@ -361,66 +338,66 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
     const uint32_t n_blocks = ds->n_blocks = uint32_t(nb);
     const uint64_t n_post = n_terms ? term_start[n_terms] : 0;
 
-    DBuf d_len, d_fnlen, d_sum, d_ts, d_pd, d_pt, d_denom, d_err, b_len8, b_wval, d_tmp, d_bnd;
-    FL_TRY(d_fnlen.alloc(4 * 256));
-    FL_TRY(ds->d_doc_fieldnorm.alloc(n_docs));
-    FL_TRY(ds->d_doc_payload.alloc(6ull * n_docs));
-    FL_TRY(d_sum.alloc(8));
-    FL_TRY(d_err.alloc(4));
+    HbmArray d_len, d_fnlen, d_sum, d_ts, d_pd, d_pt, d_denom, d_err, b_len8, b_wval, d_tmp, d_bnd;
+    HIP_TRY(d_fnlen.alloc(4 * 256));
+    HIP_TRY(ds->d_doc_fieldnorm.alloc(n_docs));
+    HIP_TRY(ds->d_doc_payload.alloc(6ull * n_docs));
+    HIP_TRY(d_sum.alloc(8));
+    HIP_TRY(d_err.alloc(4));
     if (!dev_len) {
-        FL_TRY(d_len.alloc(4ull * n_docs));
-        FL_TRY(hipMemcpy(d_len.p, doc_len, 4ull * n_docs, hipMemcpyHostToDevice));
+        HIP_TRY(d_len.alloc(4ull * n_docs));
+        HIP_TRY(hipMemcpy(d_len.p, doc_len, 4ull * n_docs, hipMemcpyHostToDevice));
         g_encode_link[0] += 4.0 * n_docs;
         dev_len = d_len.as<uint32_t>();
     }
-    if (dev_payload) FL_TRY(hipMemcpy(ds->d_doc_payload.p, dev_payload, 6ull * n_docs, hipMemcpyDeviceToDevice));
+    if (dev_payload) HIP_TRY(hipMemcpy(ds->d_doc_payload.p, dev_payload, 6ull * n_docs, hipMemcpyDeviceToDevice));
     else if (doc_payload) {
-        FL_TRY(hipMemcpy(ds->d_doc_payload.p, doc_payload, 6ull * n_docs, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ds->d_doc_payload.p, doc_payload, 6ull * n_docs, hipMemcpyHostToDevice));
         g_encode_link[0] += 6.0 * n_docs;
     }
     else synth_payload_kernel<<<1024, 256>>>(n_docs, ds->d_doc_payload.as<uint16_t>());
-    FL_TRY(hipMemcpy(d_fnlen.p, fieldnorm_lengths(), 4 * 256, hipMemcpyHostToDevice));
-    FL_TRY(hipMemset(d_sum.p, 0, 8));
-    FL_TRY(hipMemset(d_err.p, 0, 4));
+    HIP_TRY(hipMemcpy(d_fnlen.p, fieldnorm_lengths(), 4 * 256, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_sum.p, 0, 8));
+    HIP_TRY(hipMemset(d_err.p, 0, 4));
     doc_kernel<<<1024, 256>>>(n_docs, dev_len, d_fnlen.as<uint32_t>(), ds->d_doc_fieldnorm.as<uint8_t>(), d_sum.as<unsigned long long>());
-    FL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned long long sum_len = 0;
-    FL_TRY(hipMemcpy(&sum_len, d_sum.p, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&sum_len, d_sum.p, 8, hipMemcpyDeviceToHost));
     g_encode_link[0] += 4 * 256;  // (the fieldnorm table above)
     g_encode_link[1] += 8;
     ds->sum_len = sum_len;
     double denom[256];
     bm25_tables(n_docs, sum_len, k1, b, denom);
 
-    FL_TRY(d_ts.alloc(8ull * (n_terms + 1)));
-    FL_TRY(ds->d_term_first_block.alloc(4ull * (n_terms + 1)));
+    HIP_TRY(d_ts.alloc(8ull * (n_terms + 1)));
+    HIP_TRY(ds->d_term_first_block.alloc(4ull * (n_terms + 1)));
     if (!dev_doc) {
-        FL_TRY(d_pd.alloc(4ull * n_post));
-        FL_TRY(d_pt.alloc(4ull * n_post));
+        HIP_TRY(d_pd.alloc(4ull * n_post));
+        HIP_TRY(d_pt.alloc(4ull * n_post));
     }
-    FL_TRY(d_denom.alloc(8 * 256));
-    FL_TRY(hipMemcpy(d_ts.p, term_start, 8ull * (n_terms + 1), hipMemcpyHostToDevice));
-    FL_TRY(hipMemcpy(ds->d_term_first_block.p, ds->term_first_block.data(), 4ull * (n_terms + 1), hipMemcpyHostToDevice));
+    HIP_TRY(d_denom.alloc(8 * 256));
+    HIP_TRY(hipMemcpy(d_ts.p, term_start, 8ull * (n_terms + 1), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ds->d_term_first_block.p, ds->term_first_block.data(), 4ull * (n_terms + 1), hipMemcpyHostToDevice));
     if (n_post && !dev_doc) {
-        FL_TRY(hipMemcpy(d_pd.p, post_doc, 4ull * n_post, hipMemcpyHostToDevice));
-        FL_TRY(hipMemcpy(d_pt.p, post_tf, 4ull * n_post, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_pd.p, post_doc, 4ull * n_post, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_pt.p, post_tf, 4ull * n_post, hipMemcpyHostToDevice));
         g_encode_link[0] += 8.0 * n_post;
     }
-    FL_TRY(hipMemcpy(d_denom.p, denom, 8 * 256, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_denom.p, denom, 8 * 256, hipMemcpyHostToDevice));
     g_encode_link[0] += 12.0 * (n_terms + 1.0) + 8 * 256;  // term_start, first blocks, the table
-    FL_TRY(ds->d_blk_min.alloc(4ull * n_blocks));
-    FL_TRY(ds->d_blk_max.alloc(4ull * n_blocks));
-    FL_TRY(ds->d_blk_wand_tf.alloc(4ull * n_blocks));
-    FL_TRY(b_len8.alloc(4ull * (n_blocks + 1)));
-    FL_TRY(ds->d_blk_off8.alloc(4ull * (n_blocks + 1)));
-    FL_TRY(ds->d_blk_n.alloc(n_blocks));
-    FL_TRY(ds->d_blk_wand_fn.alloc(n_blocks));
-    FL_TRY(ds->d_blk_meta_doc.alloc(n_blocks));
-    FL_TRY(ds->d_blk_meta_tf.alloc(n_blocks));
-    FL_TRY(b_wval.alloc(8ull * n_blocks));
-    FL_TRY(ds->d_term_wand_fn.alloc(n_terms));
-    FL_TRY(ds->d_term_wand_tf.alloc(4ull * n_terms));
-    FL_TRY(ds->d_term_df.alloc(4ull * n_terms));
+    HIP_TRY(ds->d_blk_min.alloc(4ull * n_blocks));
+    HIP_TRY(ds->d_blk_max.alloc(4ull * n_blocks));
+    HIP_TRY(ds->d_blk_wand_tf.alloc(4ull * n_blocks));
+    HIP_TRY(b_len8.alloc(4ull * (n_blocks + 1)));
+    HIP_TRY(ds->d_blk_off8.alloc(4ull * (n_blocks + 1)));
+    HIP_TRY(ds->d_blk_n.alloc(n_blocks));
+    HIP_TRY(ds->d_blk_wand_fn.alloc(n_blocks));
+    HIP_TRY(ds->d_blk_meta_doc.alloc(n_blocks));
+    HIP_TRY(ds->d_blk_meta_tf.alloc(n_blocks));
+    HIP_TRY(b_wval.alloc(8ull * n_blocks));
+    HIP_TRY(ds->d_term_wand_fn.alloc(n_terms));
+    HIP_TRY(ds->d_term_wand_tf.alloc(4ull * n_terms));
+    HIP_TRY(ds->d_term_df.alloc(4ull * n_terms));
     FlushArgs a{};
     a.n_docs = n_docs;
     a.n_terms = n_terms;
@@ -445,49 +422,43 @@ int vbm25::build_device_core(int device, double k1, double b, uint32_t n_docs, c
     a.error_flag = d_err.as<uint32_t>();
     ds->term_bytes.assign(n_terms, 0);
     if (n_blocks) {
-        FL_TRY(hipMemset(b_len8.p, 0, 4ull * (n_blocks + 1)));
+        HIP_TRY(hipMemset(b_len8.p, 0, 4ull * (n_blocks + 1)));
         block_stats_kernel<<<(n_blocks + 3) / 4, 256>>>(a);
-        FL_TRY(hipGetLastError());
-        size_t tmp_bytes = 0;
-        FL_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, a.len8, a.off8, (int)(n_blocks + 1)));
-        FL_TRY(d_tmp.alloc(tmp_bytes));
-        FL_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, a.len8, a.off8, (int)(n_blocks + 1)));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, a.len8, a.off8, (int)(n_blocks + 1)); }));
         uint32_t flag = 0;
-        FL_TRY(hipMemcpy(&flag, d_err.p, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&flag, d_err.p, 4, hipMemcpyDeviceToHost));
         if (flag) return set_error(VBM25_ERR_INVALID, "mappings must be sorted by (token, document), ids < n_docs, tf > 0");
         // total body length: a 32-bit scan would wrap silently beyond 2^32 units of 8 bytes -- summed in 64 bits as well
         unsigned long long total8 = 0;
         {
-            size_t rb = 0;
             hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(a.len8, WidenU32());
-            FL_TRY(hipcub::DeviceReduce::Sum(nullptr, rb, wide, d_sum.as<unsigned long long>(), (int)n_blocks));
-            DBuf d_rt;
-            FL_TRY(d_rt.alloc(rb));
-            FL_TRY(hipcub::DeviceReduce::Sum(d_rt.p, rb, wide, d_sum.as<unsigned long long>(), (int)n_blocks));
-            FL_TRY(hipMemcpy(&total8, d_sum.p, 8, hipMemcpyDeviceToHost));
+            HbmArray d_rt;
+            HIP_TRY(with_cub_temp(d_rt, [&](void *t, size_t &tb) { return hipcub::DeviceReduce::Sum(t, tb, wide, d_sum.as<unsigned long long>(), (int)n_blocks); }));
+            HIP_TRY(hipMemcpy(&total8, d_sum.p, 8, hipMemcpyDeviceToHost));
             g_encode_link[1] += 4 + 8;  // (the error flag above)
         }
         if (total8 > 0xffffffffull) return set_error(VBM25_ERR_UNSUPPORTED, "block bodies exceed 32 GiB");
         ds->blob_bytes = 8ull * total8;
-        FL_TRY(ds->d_blob.alloc(ds->blob_bytes));
+        HIP_TRY(ds->d_blob.alloc(ds->blob_bytes));
         a.blob = ds->d_blob.as<uint8_t>();
         block_pack_kernel<<<(n_blocks + 3) / 4, 256>>>(a);
-        FL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         term_wand_kernel<<<n_terms, 64>>>(a, ds->d_term_wand_fn.as<uint8_t>(), ds->d_term_wand_tf.as<uint32_t>(), ds->d_term_df.as<uint32_t>());
-        FL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // the body offsets at the tokens' first blocks: the algorithmic bytes per token (vbm25_query_bytes)
-        FL_TRY(d_bnd.alloc(4ull * (n_terms + 1)));
+        HIP_TRY(d_bnd.alloc(4ull * (n_terms + 1)));
         gather_u32_kernel<<<(n_terms + 1 + 255) / 256, 256>>>(n_terms + 1, ds->d_term_first_block.as<uint32_t>(), a.off8, d_bnd.as<uint32_t>());
-        FL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         std::vector<uint32_t> bnd(size_t(n_terms) + 1);
-        FL_TRY(hipMemcpy(bnd.data(), d_bnd.p, 4ull * (n_terms + 1), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bnd.data(), d_bnd.p, 4ull * (n_terms + 1), hipMemcpyDeviceToHost));
         g_encode_link[1] += 4.0 * (n_terms + 1.0);
         for (uint32_t t = 0; t < n_terms; ++t)
             ds->term_bytes[t] = 8ull * (bnd[t + 1] - bnd[t]) + 40ull * (ds->term_first_block[t + 1] - ds->term_first_block[t]) + ds->term_df[t];
     } else {
-        FL_TRY(hipMemset(ds->d_blk_off8.p, 0, 4));
+        HIP_TRY(hipMemset(ds->d_blk_off8.p, 0, 4));
     }
-    FL_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     out = std::move(ds);
     return VBM25_OK;
 }
@@ -496,7 +467,7 @@ namespace {
 
 // the host copy of a device segment: the same vbm25_segment the host builder makes, byte for byte
 int download_device_segment(const vbm25_device_segment &ds, vbm25_segment **out) {
-    FL_TRY(hipSetDevice(ds.device));
+    HIP_TRY(hipSetDevice(ds.device));
     auto seg = std::make_unique<vbm25_segment>();
     seg->k1 = ds.k1;
     seg->b = ds.b;
@@ -511,20 +482,20 @@ int download_device_segment(const vbm25_device_segment &ds, vbm25_segment **out)
         vec.resize(n);
         return n ? hipMemcpy(vec.data(), src.p, n * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
     };
-    FL_TRY(fetch(seg->doc_fieldnorm, ds.d_doc_fieldnorm, ds.n_docs));
-    FL_TRY(fetch(seg->doc_payload, ds.d_doc_payload, 3ull * ds.n_docs));
-    FL_TRY(fetch(seg->blk_off8, ds.d_blk_off8, size_t(ds.n_blocks) + 1));
-    FL_TRY(fetch(seg->blob, ds.d_blob, ds.blob_bytes));
-    FL_TRY(fetch(seg->blk_min_doc, ds.d_blk_min, ds.n_blocks));
-    FL_TRY(fetch(seg->blk_max_doc, ds.d_blk_max, ds.n_blocks));
-    FL_TRY(fetch(seg->blk_wand_tf, ds.d_blk_wand_tf, ds.n_blocks));
-    FL_TRY(fetch(seg->blk_n, ds.d_blk_n, ds.n_blocks));
-    FL_TRY(fetch(seg->blk_wand_fn, ds.d_blk_wand_fn, ds.n_blocks));
-    FL_TRY(fetch(seg->blk_meta_doc, ds.d_blk_meta_doc, ds.n_blocks));
-    FL_TRY(fetch(seg->blk_meta_tf, ds.d_blk_meta_tf, ds.n_blocks));
-    FL_TRY(fetch(seg->term_wand_fn, ds.d_term_wand_fn, ds.n_terms));
-    FL_TRY(fetch(seg->term_wand_tf, ds.d_term_wand_tf, ds.n_terms));
-    FL_TRY(fetch(seg->term_df, ds.d_term_df, ds.n_terms));
+    HIP_TRY(fetch(seg->doc_fieldnorm, ds.d_doc_fieldnorm, ds.n_docs));
+    HIP_TRY(fetch(seg->doc_payload, ds.d_doc_payload, 3ull * ds.n_docs));
+    HIP_TRY(fetch(seg->blk_off8, ds.d_blk_off8, size_t(ds.n_blocks) + 1));
+    HIP_TRY(fetch(seg->blob, ds.d_blob, ds.blob_bytes));
+    HIP_TRY(fetch(seg->blk_min_doc, ds.d_blk_min, ds.n_blocks));
+    HIP_TRY(fetch(seg->blk_max_doc, ds.d_blk_max, ds.n_blocks));
+    HIP_TRY(fetch(seg->blk_wand_tf, ds.d_blk_wand_tf, ds.n_blocks));
+    HIP_TRY(fetch(seg->blk_n, ds.d_blk_n, ds.n_blocks));
+    HIP_TRY(fetch(seg->blk_wand_fn, ds.d_blk_wand_fn, ds.n_blocks));
+    HIP_TRY(fetch(seg->blk_meta_doc, ds.d_blk_meta_doc, ds.n_blocks));
+    HIP_TRY(fetch(seg->blk_meta_tf, ds.d_blk_meta_tf, ds.n_blocks));
+    HIP_TRY(fetch(seg->term_wand_fn, ds.d_term_wand_fn, ds.n_terms));
+    HIP_TRY(fetch(seg->term_wand_tf, ds.d_term_wand_tf, ds.n_terms));
+    HIP_TRY(fetch(seg->term_df, ds.d_term_df, ds.n_terms));
     *out = seg.release();
     return VBM25_OK;
 }
@@ -697,7 +668,7 @@ int synth_device_impl(const vbm25_synth_params *pr, int device, vbm25_device_seg
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the device generator has no CPU fallback (vbm25_segment_synth is the host generator)");
     if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
-    FL_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const uint32_t n_docs = pr->n_docs, vocab = pr->vocab, n_chunks = (n_docs + SYNTH_CHUNK - 1) / SYNTH_CHUNK;
     // token probabilities and the tokens in key order (bytewise order of their decimal strings): vocabulary-sized, on the host
     std::vector<double> log1mp(vocab);
@@ -736,31 +707,28 @@ int synth_device_impl(const vbm25_synth_params *pr, int device, vbm25_device_seg
     task_base[vocab] = n_tasks;
     if (n_tasks > 0x7fffffffull) return set_error(VBM25_ERR_UNSUPPORTED, "more than 2^31 generation tasks");
 
-    DBuf d_draws, d_slot, d_l1p, d_order, d_count, d_off, d_len, d_pd, d_pt, d_tmp, d_bnd, d_tbase, d_sub;
-    FL_TRY(d_draws.alloc(4ull * n_docs));
-    FL_TRY(d_slot.alloc(8ull * (n_docs + 1ull)));
-    FL_TRY(d_l1p.alloc(8ull * vocab));
-    FL_TRY(d_order.alloc(4ull * vocab));
-    FL_TRY(d_count.alloc(4ull * n_tasks));
-    FL_TRY(d_off.alloc(8ull * n_tasks));
-    FL_TRY(d_len.alloc(4ull * n_docs));
-    FL_TRY(d_bnd.alloc(8ull * (vocab + 1ull)));
-    FL_TRY(hipMemcpy(d_l1p.p, log1mp.data(), 8ull * vocab, hipMemcpyHostToDevice));
-    FL_TRY(hipMemcpy(d_order.p, order.data(), 4ull * vocab, hipMemcpyHostToDevice));
-    FL_TRY(d_tbase.alloc(8ull * (vocab + 1ull)));
-    FL_TRY(d_sub.alloc(vocab));
-    FL_TRY(hipMemcpy(d_tbase.p, task_base.data(), 8ull * (vocab + 1ull), hipMemcpyHostToDevice));
-    FL_TRY(hipMemcpy(d_sub.p, sub_log2.data(), vocab, hipMemcpyHostToDevice));
-    FL_TRY(hipMemset(d_len.p, 0, 4ull * n_docs));
-    FL_TRY(hipMemset(d_slot.p, 0, 8));
+    HbmArray d_draws, d_slot, d_l1p, d_order, d_count, d_off, d_len, d_pd, d_pt, d_tmp, d_bnd, d_tbase, d_sub;
+    HIP_TRY(d_draws.alloc(4ull * n_docs));
+    HIP_TRY(d_slot.alloc(8ull * (n_docs + 1ull)));
+    HIP_TRY(d_l1p.alloc(8ull * vocab));
+    HIP_TRY(d_order.alloc(4ull * vocab));
+    HIP_TRY(d_count.alloc(4ull * n_tasks));
+    HIP_TRY(d_off.alloc(8ull * n_tasks));
+    HIP_TRY(d_len.alloc(4ull * n_docs));
+    HIP_TRY(d_bnd.alloc(8ull * (vocab + 1ull)));
+    HIP_TRY(hipMemcpy(d_l1p.p, log1mp.data(), 8ull * vocab, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_order.p, order.data(), 4ull * vocab, hipMemcpyHostToDevice));
+    HIP_TRY(d_tbase.alloc(8ull * (vocab + 1ull)));
+    HIP_TRY(d_sub.alloc(vocab));
+    HIP_TRY(hipMemcpy(d_tbase.p, task_base.data(), 8ull * (vocab + 1ull), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_sub.p, sub_log2.data(), vocab, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_len.p, 0, 4ull * n_docs));
+    HIP_TRY(hipMemset(d_slot.p, 0, 8));
     synth_draws_kernel<<<2048, 256>>>(n_docs, pr->mean_len, pr->len_mode, synth_mix(pr->seed, 0xD0C5, 0), d_draws.as<uint32_t>());
-    FL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     {   // slot[d + 1] = draws[0] + ... + draws[d]
-        size_t tb = 0;
         hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(d_draws.as<uint32_t>(), WidenU32());
-        FL_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, wide, d_slot.as<unsigned long long>() + 1, (int)n_docs));
-        FL_TRY(d_tmp.alloc(tb));
-        FL_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp.p, tb, wide, d_slot.as<unsigned long long>() + 1, (int)n_docs));
+        HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, wide, d_slot.as<unsigned long long>() + 1, (int)n_docs); }));
     }
     SynthArgs a{};
     a.n_docs = n_docs;
@@ -778,26 +746,23 @@ int synth_device_impl(const vbm25_synth_params *pr, int device, vbm25_device_seg
     a.doc_len = d_len.as<uint32_t>();
     const uint32_t grid = (uint32_t)((n_tasks + 255) / 256);
     synth_gen_kernel<false><<<grid, 256>>>(a);  // pass 1: postings per task, document lengths
-    FL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned long long n_post = 0;
     {
-        size_t tb = 0;
         hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(d_count.as<uint32_t>(), WidenU32());
-        DBuf d_t2;
-        FL_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, wide, d_off.as<unsigned long long>(), (int)n_tasks));
-        FL_TRY(d_t2.alloc(tb));
-        FL_TRY(hipcub::DeviceScan::ExclusiveSum(d_t2.p, tb, wide, d_off.as<unsigned long long>(), (int)n_tasks));
+        HbmArray d_t2;
+        HIP_TRY(with_cub_temp(d_t2, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, wide, d_off.as<unsigned long long>(), (int)n_tasks); }));
         unsigned long long last_off = 0;
         uint32_t last_cnt = 0;
-        FL_TRY(hipMemcpy(&last_off, d_off.as<unsigned long long>() + (n_tasks - 1), 8, hipMemcpyDeviceToHost));
-        FL_TRY(hipMemcpy(&last_cnt, d_count.as<uint32_t>() + (n_tasks - 1), 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&last_off, d_off.as<unsigned long long>() + (n_tasks - 1), 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&last_cnt, d_count.as<uint32_t>() + (n_tasks - 1), 4, hipMemcpyDeviceToHost));
         n_post = last_off + last_cnt;
     }
     // the first mapping of every token (key order); tokens that never occur are left out of the segment
     gather_u64_at_kernel<<<(vocab + 1 + 255) / 256, 256>>>(vocab, d_tbase.as<unsigned long long>(), d_off.as<unsigned long long>(), n_post, d_bnd.as<unsigned long long>());
-    FL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<uint64_t> bnd(size_t(vocab) + 1);
-    FL_TRY(hipMemcpy(bnd.data(), d_bnd.p, 8ull * (vocab + 1ull), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(bnd.data(), d_bnd.p, 8ull * (vocab + 1ull), hipMemcpyDeviceToHost));
     std::vector<uint64_t> term_start;
     std::vector<uint8_t> term_key;
     std::vector<uint32_t> token_term(vocab, UINT32_MAX);
@@ -809,17 +774,14 @@ int synth_device_impl(const vbm25_synth_params *pr, int device, vbm25_device_seg
     }
     const uint32_t n_terms = uint32_t(term_start.size());
     term_start.push_back(n_post);
-    FL_TRY(d_pd.alloc(4ull * n_post));
-    FL_TRY(d_pt.alloc(4ull * n_post));
+    HIP_TRY(d_pd.alloc(4ull * n_post));
+    HIP_TRY(d_pt.alloc(4ull * n_post));
     a.post_doc = d_pd.as<uint32_t>();
     a.post_tf = d_pt.as<uint32_t>();
     synth_gen_kernel<true><<<grid, 256>>>(a);  // pass 2: the mappings, in (token, document) order
-    FL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // the generation buffers go before the encode's are made
-    (void)hipFree(d_count.p); d_count.p = nullptr;
-    (void)hipFree(d_off.p); d_off.p = nullptr;
-    (void)hipFree(d_slot.p); d_slot.p = nullptr;
-    (void)hipFree(d_draws.p); d_draws.p = nullptr;
+    for (HbmArray *b : {&d_count, &d_off, &d_slot, &d_draws}) b->release();
     std::unique_ptr<vbm25_device_segment> ds;
     if (int rc = build_device_core(device, pr->k1, pr->b, n_docs, nullptr, d_len.as<uint32_t>(), nullptr, nullptr, n_terms, term_key.data(), term_start.data(),
                                    nullptr, nullptr, d_pd.as<uint32_t>(), d_pt.as<uint32_t>(), ds))
@@ -867,45 +829,42 @@ int build_device_unsorted_impl(int device, double k1, double b, uint32_t n_docs,
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the device builder has no CPU fallback (vbm25_segment_build is the host builder)");
     if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
-    FL_TRY(hipSetDevice(device));
-    DBuf d_term, d_doc, d_tf, d_tf2, d_key, d_key2, d_tmp, d_ts, d_err;
-    FL_TRY(d_term.alloc(4ull * n_map));
-    FL_TRY(d_doc.alloc(4ull * n_map));
-    FL_TRY(d_tf.alloc(4ull * n_map));
-    FL_TRY(d_tf2.alloc(4ull * n_map));
-    FL_TRY(d_key.alloc(8ull * n_map));
-    FL_TRY(d_key2.alloc(8ull * n_map));
-    FL_TRY(d_ts.alloc(8ull * (n_terms + 1ull)));
-    FL_TRY(d_err.alloc(4));
-    FL_TRY(hipMemset(d_err.p, 0, 4));
-    FL_TRY(hipMemset(d_ts.p, 0xff, 8ull * (n_terms + 1ull)));
+    HIP_TRY(hipSetDevice(device));
+    HbmArray d_term, d_doc, d_tf, d_tf2, d_key, d_key2, d_tmp, d_ts, d_err;
+    HIP_TRY(d_term.alloc(4ull * n_map));
+    HIP_TRY(d_doc.alloc(4ull * n_map));
+    HIP_TRY(d_tf.alloc(4ull * n_map));
+    HIP_TRY(d_tf2.alloc(4ull * n_map));
+    HIP_TRY(d_key.alloc(8ull * n_map));
+    HIP_TRY(d_key2.alloc(8ull * n_map));
+    HIP_TRY(d_ts.alloc(8ull * (n_terms + 1ull)));
+    HIP_TRY(d_err.alloc(4));
+    HIP_TRY(hipMemset(d_err.p, 0, 4));
+    HIP_TRY(hipMemset(d_ts.p, 0xff, 8ull * (n_terms + 1ull)));
     std::vector<uint64_t> term_start(size_t(n_terms) + 1, n_map);
     if (n_map) {
-        FL_TRY(hipMemcpy(d_term.p, map_term, 4ull * n_map, hipMemcpyHostToDevice));
-        FL_TRY(hipMemcpy(d_doc.p, map_doc, 4ull * n_map, hipMemcpyHostToDevice));
-        FL_TRY(hipMemcpy(d_tf.p, map_tf, 4ull * n_map, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_term.p, map_term, 4ull * n_map, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_doc.p, map_doc, 4ull * n_map, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_tf.p, map_tf, 4ull * n_map, hipMemcpyHostToDevice));
         mapping_keys_kernel<<<2048, 256>>>(n_map, n_terms, d_term.as<uint32_t>(), d_doc.as<uint32_t>(), d_key.as<unsigned long long>(),
                                            d_err.as<uint32_t>());
-        FL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         {   // a token rank >= n_terms: rejected BEFORE the sort and the split (term_start has n_terms + 1 entries)
             uint32_t bad = 0;
-            FL_TRY(hipMemcpy(&bad, d_err.p, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&bad, d_err.p, 4, hipMemcpyDeviceToHost));
             if (bad) return set_error(VBM25_ERR_INVALID, "a mapping names a token >= n_terms");
         }
         int end_bit = 32;  // the bits of the key that can differ: the document and as much of the token as n_terms needs
         while (end_bit < 64 && (uint64_t(n_terms) >> (end_bit - 32)) != 0) ++end_bit;
         hipcub::DoubleBuffer<unsigned long long> keys(d_key.as<unsigned long long>(), d_key2.as<unsigned long long>());
         hipcub::DoubleBuffer<uint32_t> vals(d_tf.as<uint32_t>(), d_tf2.as<uint32_t>());
-        size_t tmp_bytes = 0;
-        FL_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, vals, (int)n_map, 0, end_bit));
-        FL_TRY(d_tmp.alloc(tmp_bytes));
-        FL_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, keys, vals, (int)n_map, 0, end_bit));
+        HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceRadixSort::SortPairs(t, tb, keys, vals, (int)n_map, 0, end_bit); }));
         mapping_split_kernel<<<2048, 256>>>(n_map, n_terms, keys.Current(), d_doc.as<uint32_t>(), d_ts.as<unsigned long long>());
-        FL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         uint32_t flag = 0;
-        FL_TRY(hipMemcpy(&flag, d_err.p, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&flag, d_err.p, 4, hipMemcpyDeviceToHost));
         if (flag) return set_error(VBM25_ERR_INVALID, "a mapping names a token >= n_terms");
-        FL_TRY(hipMemcpy(term_start.data(), d_ts.p, 8ull * n_terms, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(term_start.data(), d_ts.p, 8ull * n_terms, hipMemcpyDeviceToHost));
         term_start[n_terms] = n_map;
         for (uint32_t t = 0; t < n_terms; ++t)
             if (term_start[t] == ~0ull) return set_error(VBM25_ERR_INVALID, "term %u has no postings", t);

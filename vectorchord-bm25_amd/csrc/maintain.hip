@@ -33,33 +33,6 @@ namespace {
 using namespace vbm25;
 using ull = unsigned long long;
 
-#define MT_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
-struct WidenU32 {
-    __host__ __device__ ull operator()(uint32_t v) const { return v; }
-};
-
 // phase times of the last call on this thread (tools/maintain_cost.py): relabel, count, vocabulary, scatter, encode
 thread_local double g_phase_ms[5];
 // every byte the call copied over the host link, the encode's copies included (tools/vacuum_device_cost.py): [0] host -> device
@@ -368,17 +341,7 @@ __global__ void __launch_bounds__(256) mt_grow_scatter_kernel(uint32_t n, const 
     }
 }
 
-template <class In, class Out>
-hipError_t exclusive_sum(In in, Out out, uint32_t n, DBuf &tmp) {
-    size_t tb = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n);
-    if (e != hipSuccess) return e;
-    tmp.release();
-    if ((e = tmp.alloc(tb)) != hipSuccess) return e;
-    return hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, (int)n);
-}
-
-uint32_t grid_of(uint64_t n) { return (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (n + 255) / 256)); }
+uint32_t grid_of(uint64_t n) { return grid_for(n, 256, 4096); }
 
 // The result of compacting everything away: no documents, no tokens, no blocks (as an index over an empty table)
 int empty_segment(const MaintainSource &s, std::unique_ptr<vbm25_device_segment> &out) {
@@ -390,12 +353,12 @@ int empty_segment(const MaintainSource &s, std::unique_ptr<vbm25_device_segment>
     for (HbmArray *h : {&ds->d_term_df, &ds->d_term_wand_fn, &ds->d_term_wand_tf, &ds->d_blk_min, &ds->d_blk_max, &ds->d_blk_n,
                         &ds->d_blk_wand_fn, &ds->d_blk_wand_tf, &ds->d_blk_meta_doc, &ds->d_blk_meta_tf, &ds->d_blob, &ds->d_doc_fieldnorm,
                         &ds->d_doc_payload})
-        MT_TRY(h->alloc(0));
-    MT_TRY(ds->d_term_first_block.alloc(4));
-    MT_TRY(ds->d_blk_off8.alloc(4));
-    MT_TRY(hipMemset(ds->d_term_first_block.p, 0, 4));
-    MT_TRY(hipMemset(ds->d_blk_off8.p, 0, 4));
-    MT_TRY(hipDeviceSynchronize());
+        HIP_TRY(h->alloc(0));
+    HIP_TRY(ds->d_term_first_block.alloc(4));
+    HIP_TRY(ds->d_blk_off8.alloc(4));
+    HIP_TRY(hipMemset(ds->d_term_first_block.p, 0, 4));
+    HIP_TRY(hipMemset(ds->d_blk_off8.p, 0, 4));
+    HIP_TRY(hipDeviceSynchronize());
     out = std::move(ds);
     return VBM25_OK;
 }
@@ -443,15 +406,15 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
     }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return set_error(VBM25_ERR_DEVICE, "no HIP device: maintain has no CPU entry point");
-    MT_TRY(hipSetDevice(s.device));
+    HIP_TRY(hipSetDevice(s.device));
     if (dev && n_el) {  // the host loop's tf check on the handle's planes (its keys were checked when the handle was made)
-        DBuf d_first;
+        HbmArray d_first;
         uint32_t first = 0xffffffffu;
-        MT_TRY(d_first.alloc(4));
-        MT_TRY(hipMemset(d_first.p, 0xff, 4));
+        HIP_TRY(d_first.alloc(4));
+        HIP_TRY(hipMemset(d_first.p, 0xff, 4));
         mt_tf_zero_kernel<<<(uint32_t)((n_el + 255) / 256), 256>>>(n_el, G, dev->d_start.as<uint64_t>(), dev->d_tf.as<uint32_t>(), d_first.as<uint32_t>());
-        MT_TRY(hipGetLastError());
-        MT_TRY(hipMemcpy(&first, d_first.p, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&first, d_first.p, 4, hipMemcpyDeviceToHost));
         g_link_bytes[1] += 4;
         if (first != 0xffffffffu) return set_error(VBM25_ERR_INVALID, "growing document %u: tf 0", first);
     }
@@ -465,37 +428,37 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
     };
 
     // relabel
-    DBuf d_del, d_keep, d_cnt, d_base, tmp;
-    MT_TRY(d_keep.alloc(8ull * W));
-    MT_TRY(d_cnt.alloc(4ull * (W + 1ull)));
-    MT_TRY(d_base.alloc(4ull * (W + 1ull)));
+    HbmArray d_del, d_keep, d_cnt, d_base, tmp;
+    HIP_TRY(d_keep.alloc(8ull * W));
+    HIP_TRY(d_cnt.alloc(4ull * (W + 1ull)));
+    HIP_TRY(d_base.alloc(4ull * (W + 1ull)));
     uint32_t K = 0;
     if (W) {
         const ull *del_words = dev ? dev->d_sealed_deleted.as<ull>() : nullptr;  // (the handle's words: read in place)
         if (sealed_deleted) {
-            MT_TRY(d_del.alloc(8ull * W));
-            MT_TRY(hipMemcpy(d_del.p, sealed_deleted, 8ull * W, hipMemcpyHostToDevice));
+            HIP_TRY(d_del.alloc(8ull * W));
+            HIP_TRY(hipMemcpy(d_del.p, sealed_deleted, 8ull * W, hipMemcpyHostToDevice));
             g_link_bytes[0] += 8.0 * W;
             del_words = d_del.as<ull>();
         }
-        MT_TRY(hipMemset(d_cnt.as<uint32_t>() + W, 0, 4));
+        HIP_TRY(hipMemset(d_cnt.as<uint32_t>() + W, 0, 4));
         mt_keep_kernel<<<grid_of(W), 256>>>(W, N, del_words, d_keep.as<ull>(), d_cnt.as<uint32_t>());
-        MT_TRY(hipGetLastError());
-        MT_TRY(exclusive_sum(d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), W + 1, tmp));
-        MT_TRY(hipMemcpy(&K, d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), (int)(W + 1)); }));
+        HIP_TRY(hipMemcpy(&K, d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
         g_link_bytes[1] += 4;
         d_del.release();
     }
-    MT_TRY(lap(0));
+    HIP_TRY(lap(0));
 
     // count (lengths of the kept sealed documents, kept postings per block)
-    DBuf d_len, d_pay, d_kept_blk, d_blk_base;
-    MT_TRY(d_len.alloc(4ull * (uint64_t(N) + G)));
-    MT_TRY(d_pay.alloc(6ull * (uint64_t(N) + G)));
-    MT_TRY(d_kept_blk.alloc(4ull * (B + 1ull)));
-    MT_TRY(d_blk_base.alloc(8ull * (B + 1ull)));
-    MT_TRY(hipMemset(d_len.p, 0, 4ull * (uint64_t(N) + G)));
-    MT_TRY(hipMemset(d_kept_blk.p, 0, 4ull * (B + 1ull)));
+    HbmArray d_len, d_pay, d_kept_blk, d_blk_base;
+    HIP_TRY(d_len.alloc(4ull * (uint64_t(N) + G)));
+    HIP_TRY(d_pay.alloc(6ull * (uint64_t(N) + G)));
+    HIP_TRY(d_kept_blk.alloc(4ull * (B + 1ull)));
+    HIP_TRY(d_blk_base.alloc(8ull * (B + 1ull)));
+    HIP_TRY(hipMemset(d_len.p, 0, 4ull * (uint64_t(N) + G)));
+    HIP_TRY(hipMemset(d_kept_blk.p, 0, 4ull * (B + 1ull)));
     SealedArgs sa{};
     sa.n_docs = N;
     sa.n_terms = T;
@@ -510,33 +473,33 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
     sa.blk_base = d_blk_base.as<ull>();
     if (B) {
         mt_count_kernel<<<(B + 3) / 4, 256>>>(sa);
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     {
         hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *> wide(d_kept_blk.as<uint32_t>(), WidenU32());
-        MT_TRY(exclusive_sum(wide, d_blk_base.as<ull>(), B + 1, tmp));
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, wide, d_blk_base.as<ull>(), (int)(B + 1)); }));
     }
-    MT_TRY(lap(1));
+    HIP_TRY(lap(1));
 
     // vocabulary
-    DBuf d_skey, d_shi, d_slo, d_start, d_gkey, d_ghi, d_glo, d_gtf, d_gdel, d_gpay, d_live, d_live_el, d_gnew, d_gel, d_ext, d_unk, d_nunk;
-    MT_TRY(d_skey.alloc(16ull * T));
-    MT_TRY(d_shi.alloc(8ull * T));
-    MT_TRY(d_slo.alloc(8ull * T));
+    HbmArray d_skey, d_shi, d_slo, d_start, d_gkey, d_ghi, d_glo, d_gtf, d_gdel, d_gpay, d_live, d_live_el, d_gnew, d_gel, d_ext, d_unk, d_nunk;
+    HIP_TRY(d_skey.alloc(16ull * T));
+    HIP_TRY(d_shi.alloc(8ull * T));
+    HIP_TRY(d_slo.alloc(8ull * T));
     if (T) {
-        MT_TRY(hipMemcpy(d_skey.p, s.term_key, 16ull * T, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_skey.p, s.term_key, 16ull * T, hipMemcpyHostToDevice));
         g_link_bytes[0] += 16.0 * T;
         mt_key_split_kernel<<<grid_of(T), 256>>>(T, d_skey.as<ulonglong2>(), d_shi.as<ull>(), d_slo.as<ull>());
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     d_skey.release();
     uint32_t Gk = 0, n_gel = 0, U = 0;
-    MT_TRY(d_gnew.alloc(4ull * (G + 1ull)));
-    MT_TRY(d_gel.alloc(4ull * (G + 1ull)));
-    MT_TRY(d_ext.alloc(4ull * n_el));
-    MT_TRY(d_unk.alloc(4ull * n_el));
-    MT_TRY(d_nunk.alloc(4));
-    MT_TRY(hipMemset(d_nunk.p, 0, 4));
+    HIP_TRY(d_gnew.alloc(4ull * (G + 1ull)));
+    HIP_TRY(d_gel.alloc(4ull * (G + 1ull)));
+    HIP_TRY(d_ext.alloc(4ull * n_el));
+    HIP_TRY(d_unk.alloc(4ull * n_el));
+    HIP_TRY(d_nunk.alloc(4));
+    HIP_TRY(hipMemset(d_nunk.p, 0, 4));
     GrowArgs ga{};
     if (G) {
         // the growing arrays: the handle's planes where they are (only read: nothing of the handle is freed or written), or the host
@@ -546,10 +509,10 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
         const uint32_t *g_tf = nullptr;
         const uint8_t *g_del = nullptr;
         const uint16_t *g_pay = nullptr;
-        MT_TRY(d_ghi.alloc(8ull * n_el));
-        MT_TRY(d_glo.alloc(8ull * n_el));
-        MT_TRY(d_live.alloc(4ull * (G + 1ull)));
-        MT_TRY(d_live_el.alloc(4ull * (G + 1ull)));
+        HIP_TRY(d_ghi.alloc(8ull * n_el));
+        HIP_TRY(d_glo.alloc(8ull * n_el));
+        HIP_TRY(d_live.alloc(4ull * (G + 1ull)));
+        HIP_TRY(d_live_el.alloc(4ull * (G + 1ull)));
         if (dev) {
             g_start = dev->d_start.as<uint64_t>();
             g_key = dev->d_key.as<ulonglong2>();
@@ -559,21 +522,21 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
         } else {
             std::vector<uint64_t> start(size_t(G) + 1);
             for (uint32_t g = 0; g <= G; ++g) start[g] = growing->start[g] - e_first;
-            MT_TRY(d_start.alloc(8ull * (G + 1ull)));
-            MT_TRY(hipMemcpy(d_start.p, start.data(), 8ull * (G + 1ull), hipMemcpyHostToDevice));
-            MT_TRY(d_gkey.alloc(16ull * n_el));
-            MT_TRY(d_gtf.alloc(4ull * n_el));
-            MT_TRY(d_gpay.alloc(6ull * G));
+            HIP_TRY(d_start.alloc(8ull * (G + 1ull)));
+            HIP_TRY(hipMemcpy(d_start.p, start.data(), 8ull * (G + 1ull), hipMemcpyHostToDevice));
+            HIP_TRY(d_gkey.alloc(16ull * n_el));
+            HIP_TRY(d_gtf.alloc(4ull * n_el));
+            HIP_TRY(d_gpay.alloc(6ull * G));
             if (n_el) {
-                MT_TRY(hipMemcpy(d_gkey.p, growing->key + 16ull * e_first, 16ull * n_el, hipMemcpyHostToDevice));
-                MT_TRY(hipMemcpy(d_gtf.p, growing->tf + e_first, 4ull * n_el, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(d_gkey.p, growing->key + 16ull * e_first, 16ull * n_el, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(d_gtf.p, growing->tf + e_first, 4ull * n_el, hipMemcpyHostToDevice));
             }
             if (growing->deleted) {
-                MT_TRY(d_gdel.alloc(G));
-                MT_TRY(hipMemcpy(d_gdel.p, growing->deleted, G, hipMemcpyHostToDevice));
+                HIP_TRY(d_gdel.alloc(G));
+                HIP_TRY(hipMemcpy(d_gdel.p, growing->deleted, G, hipMemcpyHostToDevice));
                 g_del = d_gdel.as<uint8_t>();
             }
-            MT_TRY(hipMemcpy(d_gpay.p, growing->payload, 6ull * G, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_gpay.p, growing->payload, 6ull * G, hipMemcpyHostToDevice));
             g_link_bytes[0] += 8.0 * (G + 1.0) + 20.0 * n_el + 6.0 * G + (growing->deleted ? G : 0);
             g_start = d_start.as<uint64_t>();
             g_key = d_gkey.as<ulonglong2>();
@@ -582,17 +545,17 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
         }
         if (n_el) {
             mt_key_split_kernel<<<grid_of(n_el), 256>>>(n_el, g_key, d_ghi.as<ull>(), d_glo.as<ull>());
-            MT_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         d_gkey.release();  // (after the split on the null stream: hipFree waits for it)
-        MT_TRY(hipMemset(d_live.as<uint32_t>() + G, 0, 4));
-        MT_TRY(hipMemset(d_live_el.as<uint32_t>() + G, 0, 4));
+        HIP_TRY(hipMemset(d_live.as<uint32_t>() + G, 0, 4));
+        HIP_TRY(hipMemset(d_live_el.as<uint32_t>() + G, 0, 4));
         mt_grow_live_kernel<<<grid_of(G), 256>>>(G, g_start, g_del, d_live.as<uint32_t>(), d_live_el.as<uint32_t>());
-        MT_TRY(hipGetLastError());
-        MT_TRY(exclusive_sum(d_live.as<uint32_t>(), d_gnew.as<uint32_t>(), G + 1, tmp));
-        MT_TRY(exclusive_sum(d_live_el.as<uint32_t>(), d_gel.as<uint32_t>(), G + 1, tmp));
-        MT_TRY(hipMemcpy(&Gk, d_gnew.as<uint32_t>() + G, 4, hipMemcpyDeviceToHost));
-        MT_TRY(hipMemcpy(&n_gel, d_gel.as<uint32_t>() + G, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_live.as<uint32_t>(), d_gnew.as<uint32_t>(), (int)(G + 1)); }));
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_live_el.as<uint32_t>(), d_gel.as<uint32_t>(), (int)(G + 1)); }));
+        HIP_TRY(hipMemcpy(&Gk, d_gnew.as<uint32_t>() + G, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&n_gel, d_gel.as<uint32_t>() + G, 4, hipMemcpyDeviceToHost));
         g_link_bytes[1] += 8;
         ga.n_grow = G;
         ga.n_terms = T;
@@ -612,7 +575,7 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
         ga.n_unk = d_nunk.as<uint32_t>();
         if (n_el) {
             mt_grow_lookup_kernel<<<grid_of(G), 256>>>(ga);
-            MT_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
     }
     if (uint64_t(K) + Gk > 0xffffffffull)  // io.rs:53-56: ids 0 .. 2^32 - 2, id u32::MAX is never given out
@@ -626,59 +589,54 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
         return VBM25_OK;
     }
     uint32_t n_unk = 0;
-    MT_TRY(hipMemcpy(&n_unk, d_nunk.p, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n_unk, d_nunk.p, 4, hipMemcpyDeviceToHost));
     g_link_bytes[1] += 4;
-    DBuf d_nhi, d_nlo;
+    HbmArray d_nhi, d_nlo;
     if (n_unk) {  // sort the unknown elements by key: low halves, then (stable) high halves
-        DBuf k1, k2, v2, fl, incl;
-        MT_TRY(k1.alloc(8ull * n_unk));
-        MT_TRY(k2.alloc(8ull * n_unk));
-        MT_TRY(v2.alloc(4ull * n_unk));
+        HbmArray k1, k2, v2, fl, incl;
+        HIP_TRY(k1.alloc(8ull * n_unk));
+        HIP_TRY(k2.alloc(8ull * n_unk));
+        HIP_TRY(v2.alloc(4ull * n_unk));
         mt_gather_u64_kernel<<<grid_of(n_unk), 256>>>(n_unk, d_unk.as<uint32_t>(), d_glo.as<ull>(), k1.as<ull>());
-        MT_TRY(hipGetLastError());
-        size_t tb = 0;
-        MT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k1.as<ull>(), k2.as<ull>(), d_unk.as<uint32_t>(), v2.as<uint32_t>(), (int)n_unk));
-        tmp.release();
-        MT_TRY(tmp.alloc(tb));
-        MT_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k1.as<ull>(), k2.as<ull>(), d_unk.as<uint32_t>(), v2.as<uint32_t>(), (int)n_unk));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) {
+            return hipcub::DeviceRadixSort::SortPairs(t, tb, k1.as<ull>(), k2.as<ull>(), d_unk.as<uint32_t>(), v2.as<uint32_t>(), (int)n_unk);
+        }));
         mt_gather_u64_kernel<<<grid_of(n_unk), 256>>>(n_unk, v2.as<uint32_t>(), d_ghi.as<ull>(), k1.as<ull>());
-        MT_TRY(hipGetLastError());
-        MT_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k1.as<ull>(), k2.as<ull>(), v2.as<uint32_t>(), d_unk.as<uint32_t>(), (int)n_unk));
-        MT_TRY(fl.alloc(4ull * n_unk));
-        MT_TRY(incl.alloc(4ull * n_unk));
+        HIP_TRY(hipGetLastError());
+        size_t tb = tmp.bytes;  // (the same sort with the value arrays exchanged: the first one's temporary storage serves it)
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k1.as<ull>(), k2.as<ull>(), v2.as<uint32_t>(), d_unk.as<uint32_t>(), (int)n_unk));
+        HIP_TRY(fl.alloc(4ull * n_unk));
+        HIP_TRY(incl.alloc(4ull * n_unk));
         mt_unique_flag_kernel<<<grid_of(n_unk), 256>>>(n_unk, d_unk.as<uint32_t>(), d_ghi.as<ull>(), d_glo.as<ull>(), fl.as<uint32_t>());
-        MT_TRY(hipGetLastError());
-        tb = 0;
-        MT_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, fl.as<uint32_t>(), incl.as<uint32_t>(), (int)n_unk));
-        tmp.release();
-        MT_TRY(tmp.alloc(tb));
-        MT_TRY(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, fl.as<uint32_t>(), incl.as<uint32_t>(), (int)n_unk));
-        MT_TRY(hipMemcpy(&U, incl.as<uint32_t>() + (n_unk - 1), 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, fl.as<uint32_t>(), incl.as<uint32_t>(), (int)n_unk); }));
+        HIP_TRY(hipMemcpy(&U, incl.as<uint32_t>() + (n_unk - 1), 4, hipMemcpyDeviceToHost));
         g_link_bytes[1] += 4;
-        MT_TRY(d_nhi.alloc(8ull * U));
-        MT_TRY(d_nlo.alloc(8ull * U));
+        HIP_TRY(d_nhi.alloc(8ull * U));
+        HIP_TRY(d_nlo.alloc(8ull * U));
         mt_unique_write_kernel<<<grid_of(n_unk), 256>>>(n_unk, T, d_unk.as<uint32_t>(), fl.as<uint32_t>(), incl.as<uint32_t>(), d_ghi.as<ull>(),
                                                         d_glo.as<ull>(), d_nhi.as<ull>(), d_nlo.as<ull>(), d_ext.as<uint32_t>());
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (uint64_t(T) + U > 0xfffffff0ull) return set_error(VBM25_ERR_UNSUPPORTED, "more than 2^32 tokens");
     const uint32_t M = T + U;
-    DBuf d_rank, d_src, d_mkey, d_gcnt, d_gscan, d_skept, d_total, d_ts_m, d_nz, d_fid, d_key_f, d_ts_f, d_sbase, d_gbase, d_mkey_tf, d_mtf;
-    MT_TRY(d_rank.alloc(4ull * M));
-    MT_TRY(d_src.alloc(4ull * M));
-    MT_TRY(d_mkey.alloc(16ull * M));
-    MT_TRY(d_gcnt.alloc(4ull * (M + 1ull)));
-    MT_TRY(hipMemset(d_gcnt.p, 0, 4ull * (M + 1ull)));
+    HbmArray d_rank, d_src, d_mkey, d_gcnt, d_gscan, d_skept, d_total, d_ts_m, d_nz, d_fid, d_key_f, d_ts_f, d_sbase, d_gbase, d_mkey_tf, d_mtf;
+    HIP_TRY(d_rank.alloc(4ull * M));
+    HIP_TRY(d_src.alloc(4ull * M));
+    HIP_TRY(d_mkey.alloc(16ull * M));
+    HIP_TRY(d_gcnt.alloc(4ull * (M + 1ull)));
+    HIP_TRY(hipMemset(d_gcnt.p, 0, 4ull * (M + 1ull)));
     if (M) {
         mt_merge_kernel<<<grid_of(M), 256>>>(T, U, d_shi.as<ull>(), d_slo.as<ull>(), d_nhi.as<ull>(), d_nlo.as<ull>(), d_rank.as<uint32_t>(),
                                               d_src.as<uint32_t>(), d_mkey.as<ulonglong2>());
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     // the growing mappings (rank << 32 | new id, tf), lengths, payloads, relabel entries
-    DBuf d_relabel;
-    if (relabel) MT_TRY(d_relabel.alloc(4ull * (uint64_t(N) + G)));
-    MT_TRY(d_mkey_tf.alloc(8ull * n_gel));
-    MT_TRY(d_mtf.alloc(4ull * n_gel));
+    HbmArray d_relabel;
+    if (relabel) HIP_TRY(d_relabel.alloc(4ull * (uint64_t(N) + G)));
+    HIP_TRY(d_mkey_tf.alloc(8ull * n_gel));
+    HIP_TRY(d_mtf.alloc(4ull * n_gel));
     if (G) {
         ga.rank_of_ext = d_rank.as<uint32_t>();
         ga.map_key = d_mkey_tf.as<ull>();
@@ -688,89 +646,85 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
         ga.new_payload = d_pay.as<uint16_t>();
         ga.relabel = relabel ? d_relabel.as<uint32_t>() + N : nullptr;
         mt_grow_map_kernel<<<grid_of(G), 256>>>(ga);
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    MT_TRY(d_skept.alloc(8ull * (M + 1ull)));
-    MT_TRY(d_total.alloc(8ull * (M + 1ull)));
-    MT_TRY(d_ts_m.alloc(8ull * (M + 1ull)));
-    MT_TRY(d_nz.alloc(4ull * (M + 1ull)));
-    MT_TRY(d_fid.alloc(4ull * (M + 1ull)));
-    MT_TRY(d_gscan.alloc(4ull * (M + 1ull)));
-    MT_TRY(hipMemset(d_total.as<ull>() + M, 0, 8));
-    MT_TRY(hipMemset(d_nz.as<uint32_t>() + M, 0, 4));
+    HIP_TRY(d_skept.alloc(8ull * (M + 1ull)));
+    HIP_TRY(d_total.alloc(8ull * (M + 1ull)));
+    HIP_TRY(d_ts_m.alloc(8ull * (M + 1ull)));
+    HIP_TRY(d_nz.alloc(4ull * (M + 1ull)));
+    HIP_TRY(d_fid.alloc(4ull * (M + 1ull)));
+    HIP_TRY(d_gscan.alloc(4ull * (M + 1ull)));
+    HIP_TRY(hipMemset(d_total.as<ull>() + M, 0, 8));
+    HIP_TRY(hipMemset(d_nz.as<uint32_t>() + M, 0, 4));
     if (M) {
         mt_term_count_kernel<<<grid_of(M), 256>>>(M, T, d_src.as<uint32_t>(), s.term_first_block, d_blk_base.as<ull>(), d_gcnt.as<uint32_t>(),
                                                    d_skept.as<ull>(), d_total.as<ull>(), d_nz.as<uint32_t>());
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    MT_TRY(exclusive_sum(d_total.as<ull>(), d_ts_m.as<ull>(), M + 1, tmp));
-    MT_TRY(exclusive_sum(d_nz.as<uint32_t>(), d_fid.as<uint32_t>(), M + 1, tmp));
-    MT_TRY(exclusive_sum(d_gcnt.as<uint32_t>(), d_gscan.as<uint32_t>(), M + 1, tmp));
+    HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_total.as<ull>(), d_ts_m.as<ull>(), (int)(M + 1)); }));
+    HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_nz.as<uint32_t>(), d_fid.as<uint32_t>(), (int)(M + 1)); }));
+    HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_gcnt.as<uint32_t>(), d_gscan.as<uint32_t>(), (int)(M + 1)); }));
     uint32_t F = 0;
     uint64_t P = 0;
-    MT_TRY(hipMemcpy(&F, d_fid.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost));
-    MT_TRY(hipMemcpy(&P, d_ts_m.as<ull>() + M, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&F, d_fid.as<uint32_t>() + M, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&P, d_ts_m.as<ull>() + M, 8, hipMemcpyDeviceToHost));
     g_link_bytes[1] += 12;
-    MT_TRY(d_key_f.alloc(16ull * F));
-    MT_TRY(d_ts_f.alloc(8ull * (F + 1ull)));
-    MT_TRY(d_sbase.alloc(8ull * T));
-    MT_TRY(d_gbase.alloc(8ull * M));
+    HIP_TRY(d_key_f.alloc(16ull * F));
+    HIP_TRY(d_ts_f.alloc(8ull * (F + 1ull)));
+    HIP_TRY(d_sbase.alloc(8ull * T));
+    HIP_TRY(d_gbase.alloc(8ull * M));
     mt_finalize_kernel<<<grid_of(M + 1ull), 256>>>(M, T, d_src.as<uint32_t>(), s.term_first_block, d_blk_base.as<ull>(), d_ts_m.as<ull>(),
                                                    d_skept.as<ull>(), d_total.as<ull>(), d_fid.as<uint32_t>(), d_gscan.as<uint32_t>(),
                                                    d_mkey.as<ulonglong2>(), d_key_f.as<ulonglong2>(), d_ts_f.as<ull>(), d_sbase.as<ull>(),
                                                    d_gbase.as<ull>());
-    MT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     std::vector<uint8_t> key_f(16ull * F);
     std::vector<uint64_t> ts_f(size_t(F) + 1);
-    if (F) MT_TRY(hipMemcpy(key_f.data(), d_key_f.p, 16ull * F, hipMemcpyDeviceToHost));
-    MT_TRY(hipMemcpy(ts_f.data(), d_ts_f.p, 8ull * (F + 1ull), hipMemcpyDeviceToHost));
+    if (F) HIP_TRY(hipMemcpy(key_f.data(), d_key_f.p, 16ull * F, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ts_f.data(), d_ts_f.p, 8ull * (F + 1ull), hipMemcpyDeviceToHost));
     g_link_bytes[1] += 16.0 * F + 8.0 * (F + 1.0);
-    for (DBuf *b : {&d_rank, &d_mkey, &d_skept, &d_total, &d_nz, &d_fid, &d_gscan, &d_key_f, &d_ts_f, &d_ghi, &d_glo, &d_shi, &d_slo, &d_ext,
+    for (HbmArray *b : {&d_rank, &d_mkey, &d_skept, &d_total, &d_nz, &d_fid, &d_gscan, &d_key_f, &d_ts_f, &d_ghi, &d_glo, &d_shi, &d_slo, &d_ext,
                     &d_unk, &d_gtf})
         b->release();
-    MT_TRY(lap(2));
+    HIP_TRY(lap(2));
 
     // scatter
-    DBuf d_doc, d_tf;
-    MT_TRY(d_doc.alloc(4ull * P));
-    MT_TRY(d_tf.alloc(4ull * P));
+    HbmArray d_doc, d_tf;
+    HIP_TRY(d_doc.alloc(4ull * P));
+    HIP_TRY(d_tf.alloc(4ull * P));
     sa.sbase = d_sbase.as<ull>();
     sa.post_doc = d_doc.as<uint32_t>();
     sa.post_tf = d_tf.as<uint32_t>();
     if (B) {
         mt_scatter_kernel<<<(B + 3) / 4, 256>>>(sa);
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (N) {
         mt_sealed_docs_kernel<<<grid_of(N), 256>>>(N, d_keep.as<ull>(), d_base.as<uint32_t>(), s.doc_payload, d_pay.as<uint16_t>(),
                                                    relabel ? d_relabel.as<uint32_t>() : nullptr);
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (n_gel) {
         int end_bit = 32;  // the new id and as much of the rank as M needs
         while (end_bit < 64 && (uint64_t(M) >> (end_bit - 32)) != 0) ++end_bit;
-        DBuf k2, v2;
-        MT_TRY(k2.alloc(8ull * n_gel));
-        MT_TRY(v2.alloc(4ull * n_gel));
+        HbmArray k2, v2;
+        HIP_TRY(k2.alloc(8ull * n_gel));
+        HIP_TRY(v2.alloc(4ull * n_gel));
         hipcub::DoubleBuffer<ull> keys(d_mkey_tf.as<ull>(), k2.as<ull>());
         hipcub::DoubleBuffer<uint32_t> vals(d_mtf.as<uint32_t>(), v2.as<uint32_t>());
-        size_t tb = 0;
-        MT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, vals, (int)n_gel, 0, end_bit));
-        tmp.release();
-        MT_TRY(tmp.alloc(tb));
-        MT_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys, vals, (int)n_gel, 0, end_bit));
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceRadixSort::SortPairs(t, tb, keys, vals, (int)n_gel, 0, end_bit); }));
         mt_grow_scatter_kernel<<<grid_of(n_gel), 256>>>(n_gel, keys.Current(), vals.Current(), d_gbase.as<ull>(), d_doc.as<uint32_t>(),
                                                         d_tf.as<uint32_t>());
-        MT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (relabel) {
-        MT_TRY(hipMemcpy(relabel, d_relabel.p, 4ull * (uint64_t(N) + G), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(relabel, d_relabel.p, 4ull * (uint64_t(N) + G), hipMemcpyDeviceToHost));
         g_link_bytes[1] += 4.0 * (double(N) + G);
     }
-    for (DBuf *b : {&d_keep, &d_cnt, &d_base, &d_kept_blk, &d_blk_base, &d_sbase, &d_gbase, &d_mkey_tf, &d_mtf, &d_relabel, &d_start, &d_gdel,
+    for (HbmArray *b : {&d_keep, &d_cnt, &d_base, &d_kept_blk, &d_blk_base, &d_sbase, &d_gbase, &d_mkey_tf, &d_mtf, &d_relabel, &d_start, &d_gdel,
                     &d_gpay, &d_live, &d_live_el, &d_gnew, &d_gel, &tmp, &d_src, &d_gcnt, &d_ts_m})
         b->release();
-    MT_TRY(lap(3));
+    HIP_TRY(lap(3));
 
     // encode
     std::unique_ptr<vbm25_device_segment> ds;
@@ -781,7 +735,7 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
     encode_link_bytes(encode);
     g_link_bytes[0] += encode[0];
     g_link_bytes[1] += encode[1];
-    MT_TRY(lap(4));
+    HIP_TRY(lap(4));
     *out = ds.release();
     return VBM25_OK;
 }
@@ -860,45 +814,45 @@ int filter_remap_device(int device, uint32_t n_bitmaps, uint32_t n_docs, const v
     if (!del.empty() && growing_deleted)
         for (uint32_t g = 0; g < n_grow; ++g)
             if (growing_deleted[g]) del[W + (g >> 6)] |= 1ull << (g & 63u);
-    MT_TRY(hipSetDevice(device));
-    DBuf d_del, d_keep, d_cnt, d_base, tmp;
+    HIP_TRY(hipSetDevice(device));
+    HbmArray d_del, d_keep, d_cnt, d_base, tmp;
     uint32_t got[2] = {0, 0};  // kept sealed documents, kept sealed + live growing
     if (TW) {
-        MT_TRY(d_keep.alloc(8ull * TW));
-        MT_TRY(d_cnt.alloc(4ull * (TW + 1ull)));
-        MT_TRY(d_base.alloc(4ull * (TW + 1ull)));
+        HIP_TRY(d_keep.alloc(8ull * TW));
+        HIP_TRY(d_cnt.alloc(4ull * (TW + 1ull)));
+        HIP_TRY(d_base.alloc(4ull * (TW + 1ull)));
         const ull *sealed_words = nullptr, *grow_words = nullptr;
         if (!del.empty()) {
-            MT_TRY(d_del.alloc(8ull * TW));
-            MT_TRY(hipMemcpy(d_del.p, del.data(), 8ull * TW, hipMemcpyHostToDevice));
+            HIP_TRY(d_del.alloc(8ull * TW));
+            HIP_TRY(hipMemcpy(d_del.p, del.data(), 8ull * TW, hipMemcpyHostToDevice));
             if (sealed_deleted) sealed_words = d_del.as<ull>();
             if (growing_deleted) grow_words = d_del.as<ull>() + W;
         } else if (deletions_on_device) {
             sealed_words = in.dev->d_sealed_deleted.as<ull>();
             if (GW) {
-                MT_TRY(d_del.alloc(8ull * GW));
+                HIP_TRY(d_del.alloc(8ull * GW));
                 mt_pack_deleted_kernel<<<(GW + 3) / 4, 256>>>(n_grow, in.dev->d_deleted.as<uint8_t>(), d_del.as<ull>());
-                MT_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
                 grow_words = d_del.as<ull>();
             }
         }
-        MT_TRY(hipMemset(d_cnt.as<uint32_t>() + TW, 0, 4));
+        HIP_TRY(hipMemset(d_cnt.as<uint32_t>() + TW, 0, 4));
         if (W) mt_keep_kernel<<<grid_of(W), 256>>>(W, n_docs, sealed_words, d_keep.as<ull>(), d_cnt.as<uint32_t>());
         if (GW) mt_keep_kernel<<<grid_of(GW), 256>>>(GW, n_grow, grow_words, d_keep.as<ull>() + W, d_cnt.as<uint32_t>() + W);
-        MT_TRY(hipGetLastError());
-        MT_TRY(exclusive_sum(d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), uint32_t(TW + 1ull), tmp));
-        MT_TRY(hipMemcpy(&got[0], d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
-        MT_TRY(hipMemcpy(&got[1], d_base.as<uint32_t>() + TW, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, d_cnt.as<uint32_t>(), d_base.as<uint32_t>(), (int)uint32_t(TW + 1ull)); }));
+        HIP_TRY(hipMemcpy(&got[0], d_base.as<uint32_t>() + W, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&got[1], d_base.as<uint32_t>() + TW, 4, hipMemcpyDeviceToHost));
     }
     if (got[1] != new_n_docs)
         return set_error(VBM25_ERR_INVALID, "%u kept sealed + %u live growing documents = %u, the new index holds %u: the filter is being "
                                             "remapped against another compaction", got[0], got[1] - got[0], got[1], new_n_docs);
     if (!OW) return VBM25_OK;
-    MT_TRY(hipMemset(out, 0, 8ull * n_bitmaps * OW));
+    HIP_TRY(hipMemset(out, 0, 8ull * n_bitmaps * OW));
     filter_remap_kernel<<<grid_of(TW), 256>>>(uint32_t(TW), W, d_keep.as<ull>(), d_base.as<uint32_t>(), static_cast<const ull *>(bits),
                                               static_cast<const ull *>(grow_bits), grow_stride, n_bitmaps, static_cast<ull *>(out), OW);
-    MT_TRY(hipGetLastError());
-    MT_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return VBM25_OK;
 }
 

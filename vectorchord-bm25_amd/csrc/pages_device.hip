@@ -36,53 +36,11 @@ namespace {
 using namespace vbm25;
 using namespace vbm25::pgs;
 
-#define PG_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-struct Pinned {
-    void *p = nullptr;
-    ~Pinned() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
-
-struct WidenU32 {
-    __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
-};
-
 // the last call's cost on this thread (vbm25_debug_pages_device_stats): kernels and scans between HIP events, bytes over the host
 // link in both directions, host memory the call allocated (pinned staging included)
 thread_local double g_stats[4];
 
 constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
-uint32_t grid_for(uint64_t units, uint32_t per_block) { return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block)); }
 
 // one wave per page of tape TAPE, lane i takes slot i + 1 (+ 64 ...)
 template <uint32_t TAPE>
@@ -124,35 +82,35 @@ __global__ void __launch_bounds__(WG_THREADS) gather_kernel(uint32_t n, const ui
 // Pinned staging of the host pass: pages fill one buffer while the other one's chunk is on its way up
 struct Stager {
     hipStream_t s = nullptr;
-    Pinned pin[2];
+    PinnedHost pin[2];
     Event ev[2];
     bool in_flight[2] = {false, false};
     int cur = 0;
     uint32_t fill = 0, tape = 0;
     uint64_t bytes_up = 0;
-    std::vector<std::unique_ptr<DBuf>> chunks[N_TAPES];
+    std::vector<std::unique_ptr<HbmArray>> chunks[N_TAPES];
 
     int init(hipStream_t stream) {
         s = stream;
         for (int i = 0; i < 2; ++i) {
-            PG_TRY(hipHostMalloc(&pin[i].p, (size_t)CHUNK_PAGES * BLCKSZ, hipHostMallocDefault));
-            PG_TRY(hipEventCreateWithFlags(&ev[i].e, hipEventDisableTiming));
+            HIP_TRY(hipHostMalloc(&pin[i].p, (size_t)CHUNK_PAGES * BLCKSZ, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&ev[i].e, hipEventDisableTiming));
         }
         return VBM25_OK;
     }
     int flush() {
         if (!fill) return VBM25_OK;
-        auto d = std::make_unique<DBuf>();
-        PG_TRY(d->alloc((size_t)fill * BLCKSZ));
-        PG_TRY(hipMemcpyAsync(d->p, pin[cur].p, (size_t)fill * BLCKSZ, hipMemcpyHostToDevice, s));
-        PG_TRY(hipEventRecord(ev[cur].e, s));
+        auto d = std::make_unique<HbmArray>();
+        HIP_TRY(d->alloc((size_t)fill * BLCKSZ));
+        HIP_TRY(hipMemcpyAsync(d->p, pin[cur].p, (size_t)fill * BLCKSZ, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev[cur].e, s));
         in_flight[cur] = true;
         bytes_up += (uint64_t)fill * BLCKSZ;
         chunks[tape].push_back(std::move(d));
         fill = 0;
         cur ^= 1;
         if (in_flight[cur]) {  // the buffer to fill next: its chunk had a whole chunk's walk to arrive
-            PG_TRY(hipEventSynchronize(ev[cur].e));
+            HIP_TRY(hipEventSynchronize(ev[cur].e));
             in_flight[cur] = false;
         }
         return VBM25_OK;
@@ -178,11 +136,11 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the device reader has no CPU fallback (vbm25_segment_from_pages is the host reader)");
     if (device < 0 || device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", device, n_dev);
-    PG_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     for (double &x : g_stats) x = 0.0;
 
     Stream stream;
-    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     hipStream_t s = stream.s;
     Stager st;
     if (int rc = st.init(s)) return rc;
@@ -201,21 +159,21 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     uint64_t host_bytes = 2ull * CHUNK_PAGES * BLCKSZ, bytes_down = 0;
 
     // ---- the tapes' tables
-    DBuf d_chunk[N_TAPES], d_pid[N_TAPES], d_pre[N_TAPES];
+    HbmArray d_chunk[N_TAPES], d_pid[N_TAPES], d_pre[N_TAPES];
     std::vector<const uint8_t *> chunk_ptr[N_TAPES];
     Planes c{};
     c.n_docs = n_docs;
     for (uint32_t t = 0; t < N_TAPES; ++t) {
         const size_t np = w.pid[t].size();
         for (const auto &d : st.chunks[t]) chunk_ptr[t].push_back(d->as<uint8_t>());
-        PG_TRY(d_chunk[t].alloc(sizeof(void *) * chunk_ptr[t].size()));
-        PG_TRY(d_pid[t].alloc(4 * np));
-        PG_TRY(d_pre[t].alloc(4 * (np + 1)));
+        HIP_TRY(d_chunk[t].alloc(sizeof(void *) * chunk_ptr[t].size()));
+        HIP_TRY(d_pid[t].alloc(4 * np));
+        HIP_TRY(d_pre[t].alloc(4 * (np + 1)));
         if (np) {
-            PG_TRY(hipMemcpyAsync(d_chunk[t].p, chunk_ptr[t].data(), sizeof(void *) * chunk_ptr[t].size(), hipMemcpyHostToDevice, s));
-            PG_TRY(hipMemcpyAsync(d_pid[t].p, w.pid[t].data(), 4 * np, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_chunk[t].p, chunk_ptr[t].data(), sizeof(void *) * chunk_ptr[t].size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_pid[t].p, w.pid[t].data(), 4 * np, hipMemcpyHostToDevice, s));
         }
-        PG_TRY(hipMemcpyAsync(d_pre[t].p, w.pre[t].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pre[t].p, w.pre[t].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
         st.bytes_up += 8 * chunk_ptr[t].size() + 8 * np + 4;
         host_bytes += 8 * np + 4 + 8 * chunk_ptr[t].size();
         c.tape[t] = TapeView{d_chunk[t].as<const uint8_t *>(), d_pid[t].as<uint32_t>(), d_pre[t].as<uint32_t>(), (uint32_t)np, w.pre[t].back()};
@@ -230,32 +188,32 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     ds->n_terms = n_tok;
     ds->n_blocks = n_sum;
     ds->sum_len = w.sum_len;
-    DBuf d_key, d_tok_page, d_tok_slot, d_tok_nb, d_tok_fb, d_sum_page, d_sum_slot, d_head, d_len8, d_err, d_total, d_tmp, d_bnd;
-    PG_TRY(ds->d_doc_fieldnorm.alloc(n_docs));
-    PG_TRY(ds->d_doc_payload.alloc(6ull * n_docs));
-    PG_TRY(ds->d_term_df.alloc(4ull * n_tok));
-    PG_TRY(ds->d_term_wand_fn.alloc(n_tok));
-    PG_TRY(ds->d_term_wand_tf.alloc(4ull * n_tok));
-    PG_TRY(ds->d_term_first_block.alloc(4ull * (n_tok + 1)));
-    PG_TRY(ds->d_blk_min.alloc(4ull * n_sum));
-    PG_TRY(ds->d_blk_max.alloc(4ull * n_sum));
-    PG_TRY(ds->d_blk_wand_tf.alloc(4ull * n_sum));
-    PG_TRY(ds->d_blk_n.alloc(n_sum));
-    PG_TRY(ds->d_blk_wand_fn.alloc(n_sum));
-    PG_TRY(ds->d_blk_meta_doc.alloc(n_sum));
-    PG_TRY(ds->d_blk_meta_tf.alloc(n_sum));
-    PG_TRY(ds->d_blk_off8.alloc(4ull * (n_sum + 1)));
-    PG_TRY(d_key.alloc(16ull * n_tok));
-    PG_TRY(d_tok_page.alloc(4ull * n_tok));
-    PG_TRY(d_tok_slot.alloc(2ull * n_tok));
-    PG_TRY(d_tok_nb.alloc(4ull * n_tok));
-    PG_TRY(d_tok_fb.alloc(8ull * n_tok));
-    PG_TRY(d_sum_page.alloc(4ull * n_sum));
-    PG_TRY(d_sum_slot.alloc(2ull * n_sum));
-    PG_TRY(d_head.alloc(n_sum + 1ull));
-    PG_TRY(d_len8.alloc(4ull * (n_sum + 1)));
-    PG_TRY(d_err.alloc(8));
-    PG_TRY(d_total.alloc(8));
+    HbmArray d_key, d_tok_page, d_tok_slot, d_tok_nb, d_tok_fb, d_sum_page, d_sum_slot, d_head, d_len8, d_err, d_total, d_tmp, d_bnd;
+    HIP_TRY(ds->d_doc_fieldnorm.alloc(n_docs));
+    HIP_TRY(ds->d_doc_payload.alloc(6ull * n_docs));
+    HIP_TRY(ds->d_term_df.alloc(4ull * n_tok));
+    HIP_TRY(ds->d_term_wand_fn.alloc(n_tok));
+    HIP_TRY(ds->d_term_wand_tf.alloc(4ull * n_tok));
+    HIP_TRY(ds->d_term_first_block.alloc(4ull * (n_tok + 1)));
+    HIP_TRY(ds->d_blk_min.alloc(4ull * n_sum));
+    HIP_TRY(ds->d_blk_max.alloc(4ull * n_sum));
+    HIP_TRY(ds->d_blk_wand_tf.alloc(4ull * n_sum));
+    HIP_TRY(ds->d_blk_n.alloc(n_sum));
+    HIP_TRY(ds->d_blk_wand_fn.alloc(n_sum));
+    HIP_TRY(ds->d_blk_meta_doc.alloc(n_sum));
+    HIP_TRY(ds->d_blk_meta_tf.alloc(n_sum));
+    HIP_TRY(ds->d_blk_off8.alloc(4ull * (n_sum + 1)));
+    HIP_TRY(d_key.alloc(16ull * n_tok));
+    HIP_TRY(d_tok_page.alloc(4ull * n_tok));
+    HIP_TRY(d_tok_slot.alloc(2ull * n_tok));
+    HIP_TRY(d_tok_nb.alloc(4ull * n_tok));
+    HIP_TRY(d_tok_fb.alloc(8ull * n_tok));
+    HIP_TRY(d_sum_page.alloc(4ull * n_sum));
+    HIP_TRY(d_sum_slot.alloc(2ull * n_sum));
+    HIP_TRY(d_head.alloc(n_sum + 1ull));
+    HIP_TRY(d_len8.alloc(4ull * (n_sum + 1)));
+    HIP_TRY(d_err.alloc(8));
+    HIP_TRY(d_total.alloc(8));
     c.doc_fieldnorm = ds->d_doc_fieldnorm.as<uint8_t>();
     c.doc_payload = ds->d_doc_payload.as<uint16_t>();
     c.term_key = d_key.as<uint8_t>();
@@ -282,45 +240,37 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     unsigned long long *err = d_err.as<unsigned long long>();
 
     Event ev[4];
-    for (Event &e : ev) PG_TRY(hipEventCreate(&e.e));
-    PG_TRY(hipEventRecord(ev[0].e, s));
-    PG_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
-    PG_TRY(hipMemsetAsync(d_total.p, 0, 8, s));
-    PG_TRY(hipMemsetAsync(d_head.p, 0, n_sum + 1ull, s));
-    PG_TRY(hipMemsetAsync(d_len8.p, 0, 4ull * (n_sum + 1), s));
-    PG_TRY(hipMemsetAsync(ds->d_term_first_block.p, 0, 4, s));
-    if (n_docs) tape_kernel<T_DOCS><<<grid_for(c.tape[T_DOCS].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
+    for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+    HIP_TRY(hipEventRecord(ev[0].e, s));
+    HIP_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
+    HIP_TRY(hipMemsetAsync(d_total.p, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(d_head.p, 0, n_sum + 1ull, s));
+    HIP_TRY(hipMemsetAsync(d_len8.p, 0, 4ull * (n_sum + 1), s));
+    HIP_TRY(hipMemsetAsync(ds->d_term_first_block.p, 0, 4, s));
+    if (n_docs) tape_kernel<T_DOCS><<<grid_for(c.tape[T_DOCS].n_pages, 4, MAX_GRID), WG_THREADS, 0, s>>>(c, err);
     if (n_tok) {
-        tape_kernel<T_TOKENS><<<grid_for(c.tape[T_TOKENS].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
+        tape_kernel<T_TOKENS><<<grid_for(c.tape[T_TOKENS].n_pages, 4, MAX_GRID), WG_THREADS, 0, s>>>(c, err);
         hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(c.tok_nb, WidenU32());
-        size_t tb = 0;
-        PG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, wide, d_tok_fb.as<unsigned long long>(), (int)n_tok, s));
-        PG_TRY(d_tmp.alloc(tb));
-        PG_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, wide, d_tok_fb.as<unsigned long long>(), (int)n_tok, s));
+        HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, wide, d_tok_fb.as<unsigned long long>(), (int)n_tok, s); }));
     }
-    if (n_sum) tape_kernel<T_SUMMARIES><<<grid_for(c.tape[T_SUMMARIES].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
-    if (n_tok) term_kernel<<<grid_for(n_tok, WG_THREADS), WG_THREADS, 0, s>>>(c, err);
-    DBuf d_tmp2, d_tmp3;
+    if (n_sum) tape_kernel<T_SUMMARIES><<<grid_for(c.tape[T_SUMMARIES].n_pages, 4, MAX_GRID), WG_THREADS, 0, s>>>(c, err);
+    if (n_tok) term_kernel<<<grid_for(n_tok, WG_THREADS, MAX_GRID), WG_THREADS, 0, s>>>(c, err);
+    HbmArray d_tmp2, d_tmp3;
     if (n_sum) {
-        tape_kernel<T_BLOCKS><<<grid_for(c.tape[T_BLOCKS].n_pages, 4), WG_THREADS, 0, s>>>(c, err);
-        size_t tb = 0;
-        PG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.len8, ds->d_blk_off8.as<uint32_t>(), (int)(n_sum + 1), s));
-        PG_TRY(d_tmp2.alloc(tb));
-        PG_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp2.p, tb, c.len8, ds->d_blk_off8.as<uint32_t>(), (int)(n_sum + 1), s));
+        tape_kernel<T_BLOCKS><<<grid_for(c.tape[T_BLOCKS].n_pages, 4, MAX_GRID), WG_THREADS, 0, s>>>(c, err);
+        HIP_TRY(with_cub_temp(d_tmp2, [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, c.len8, ds->d_blk_off8.as<uint32_t>(), (int)(n_sum + 1), s); }));
         // a 32-bit scan wraps silently beyond 2^32 units of 8 bytes: the total in 64 bits as well
         hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(c.len8, WidenU32());
-        PG_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, wide, d_total.as<unsigned long long>(), (int)n_sum, s));
-        PG_TRY(d_tmp3.alloc(tb));
-        PG_TRY(hipcub::DeviceReduce::Sum(d_tmp3.p, tb, wide, d_total.as<unsigned long long>(), (int)n_sum, s));
+        HIP_TRY(with_cub_temp(d_tmp3, [&](void *t, size_t &tb) { return hipcub::DeviceReduce::Sum(t, tb, wide, d_total.as<unsigned long long>(), (int)n_sum, s); }));
     } else {
-        PG_TRY(hipMemsetAsync(ds->d_blk_off8.p, 0, 4, s));
+        HIP_TRY(hipMemsetAsync(ds->d_blk_off8.p, 0, 4, s));
     }
-    PG_TRY(hipGetLastError());
-    PG_TRY(hipEventRecord(ev[1].e, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1].e, s));
     unsigned long long key = 0, total8 = 0;
-    PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
-    PG_TRY(hipMemcpyAsync(&total8, d_total.p, 8, hipMemcpyDeviceToHost, s));
-    PG_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&total8, d_total.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     bytes_down += 16;
 
     // ---- the verdict, in the host reader's order
@@ -328,7 +278,7 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     uint32_t unordered_at = 0;
     if (key == NO_ERROR || key_reason(key) >= R_DESC) {
         ds->term_key.resize(16ull * n_tok);
-        if (n_tok) PG_TRY(hipMemcpy(ds->term_key.data(), d_key.p, 16ull * n_tok, hipMemcpyDeviceToHost));
+        if (n_tok) HIP_TRY(hipMemcpy(ds->term_key.data(), d_key.p, 16ull * n_tok, hipMemcpyDeviceToHost));
         bytes_down += 16ull * n_tok;
         for (uint32_t t = 1; t < n_tok && ascending; ++t)
             if (std::memcmp(ds->term_key.data() + 16ull * (t - 1), ds->term_key.data() + 16ull * t, 16) >= 0) ascending = false, unordered_at = t;
@@ -343,32 +293,32 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
 
     // ---- the bodies, and what the host keeps of the tokens
     ds->blob_bytes = 8ull * total8;
-    PG_TRY(ds->d_blob.alloc(ds->blob_bytes));
+    HIP_TRY(ds->d_blob.alloc(ds->blob_bytes));
     c.blob = ds->d_blob.as<uint8_t>();
     ds->term_df.resize(n_tok);
     ds->term_first_block.assign(size_t(n_tok) + 1, 0);
     ds->term_bytes.assign(n_tok, 0);
-    PG_TRY(hipEventRecord(ev[2].e, s));
-    if (n_sum) copy_kernel<<<grid_for(c.tape[T_BLOCKS].n_pages, 4), WG_THREADS, 0, s>>>(c);
+    HIP_TRY(hipEventRecord(ev[2].e, s));
+    if (n_sum) copy_kernel<<<grid_for(c.tape[T_BLOCKS].n_pages, 4, MAX_GRID), WG_THREADS, 0, s>>>(c);
     if (n_tok) {
-        PG_TRY(d_bnd.alloc(4ull * (n_tok + 1)));
-        gather_kernel<<<grid_for(n_tok + 1ull, WG_THREADS), WG_THREADS, 0, s>>>(n_tok + 1, c.term_first_block, c.off8, d_bnd.as<uint32_t>());
+        HIP_TRY(d_bnd.alloc(4ull * (n_tok + 1)));
+        gather_kernel<<<grid_for(n_tok + 1ull, WG_THREADS, MAX_GRID), WG_THREADS, 0, s>>>(n_tok + 1, c.term_first_block, c.off8, d_bnd.as<uint32_t>());
     }
-    PG_TRY(hipGetLastError());
-    PG_TRY(hipEventRecord(ev[3].e, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3].e, s));
     std::vector<uint32_t> bnd(size_t(n_tok) + 1, 0);
     if (n_tok) {
-        PG_TRY(hipMemcpyAsync(ds->term_df.data(), ds->d_term_df.p, 4ull * n_tok, hipMemcpyDeviceToHost, s));
-        PG_TRY(hipMemcpyAsync(ds->term_first_block.data(), ds->d_term_first_block.p, 4ull * (n_tok + 1), hipMemcpyDeviceToHost, s));
-        PG_TRY(hipMemcpyAsync(bnd.data(), d_bnd.p, 4ull * (n_tok + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ds->term_df.data(), ds->d_term_df.p, 4ull * n_tok, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(ds->term_first_block.data(), ds->d_term_first_block.p, 4ull * (n_tok + 1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(bnd.data(), d_bnd.p, 4ull * (n_tok + 1), hipMemcpyDeviceToHost, s));
         bytes_down += 12ull * n_tok + 8;
     }
-    PG_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s));
     for (uint32_t t = 0; t < n_tok; ++t)
         ds->term_bytes[t] = 8ull * (bnd[t + 1] - bnd[t]) + 40ull * (ds->term_first_block[t + 1] - ds->term_first_block[t]) + ds->term_df[t];
     float ms_a = 0, ms_b = 0;
-    PG_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
-    PG_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
+    HIP_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
+    HIP_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
     host_bytes += 16ull * n_tok + 4ull * n_tok + 4ull * (n_tok + 1) + 8ull * n_tok + 4ull * (n_tok + 1);  // keys, df, first blocks, bytes, bnd
     g_stats[0] = (double)ms_a + (double)ms_b;
     g_stats[1] = (double)st.bytes_up;
@@ -483,23 +433,23 @@ int vectors_csr(hipStream_t s, Stager &st, uint32_t slot, vbm25_read_page_fn rea
 
     // ---- the tape's tables and the call's scratch.  From here on a failure returns through the buffers' destructors: hipFree waits
     // for the device, nothing is freed under a kernel or a copy in flight
-    DBuf d_chunk, d_pre, d_meta, d_cnt, d_mark, d_sum, d_last, d_fin, d_kept, d_eoff, d_err, d_tmp[3];
+    HbmArray d_chunk, d_pre, d_meta, d_cnt, d_mark, d_sum, d_last, d_fin, d_kept, d_eoff, d_err, d_tmp[3];
     std::vector<const uint8_t *> chunk_ptr;
     for (const auto &d : st.chunks[slot]) chunk_ptr.push_back(d->as<uint8_t>());
-    PG_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
-    PG_TRY(d_pre.alloc(4 * (np + 1)));
-    if (np) PG_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
-    PG_TRY(hipMemcpyAsync(d_pre.p, w.pre[0].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
+    HIP_TRY(d_pre.alloc(4 * (np + 1)));
+    if (np) HIP_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pre.p, w.pre[0].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
     st.bytes_up += 8 * chunk_ptr.size() + 4 * (np + 1);
-    PG_TRY(d_meta.alloc(4 * n));
-    PG_TRY(d_cnt.alloc(4 * n));
-    PG_TRY(d_mark.alloc(8 * n));
-    PG_TRY(d_sum.alloc(8 * n));
-    PG_TRY(d_last.alloc(8 * n));
-    PG_TRY(d_fin.alloc(n + 1));
-    PG_TRY(d_kept.alloc(4 * (n + 1)));
-    PG_TRY(d_eoff.alloc(8 * (n + 1)));
-    PG_TRY(d_err.alloc(8));
+    HIP_TRY(d_meta.alloc(4 * n));
+    HIP_TRY(d_cnt.alloc(4 * n));
+    HIP_TRY(d_mark.alloc(8 * n));
+    HIP_TRY(d_sum.alloc(8 * n));
+    HIP_TRY(d_last.alloc(8 * n));
+    HIP_TRY(d_fin.alloc(n + 1));
+    HIP_TRY(d_kept.alloc(4 * (n + 1)));
+    HIP_TRY(d_eoff.alloc(8 * (n + 1)));
+    HIP_TRY(d_err.alloc(8));
     VecPlanes c{};
     c.tape = TapeView{d_chunk.as<const uint8_t *>(), nullptr, d_pre.as<uint32_t>(), (uint32_t)np, (uint32_t)n};
     c.t_meta = d_meta.as<uint32_t>();
@@ -511,41 +461,33 @@ int vectors_csr(hipStream_t s, Stager &st, uint32_t slot, vbm25_read_page_fn rea
     c.t_kept = d_kept.as<uint32_t>();
     c.t_eoff = d_eoff.as<unsigned long long>();
     unsigned long long *err = d_err.as<unsigned long long>();
-    const uint32_t page_grid = grid_for(np, 4), tuple_grid = grid_for(n, WG_THREADS);
+    const uint32_t page_grid = grid_for(np, 4, MAX_GRID), tuple_grid = grid_for(n, WG_THREADS, MAX_GRID);
 
     Event ev[4];
-    for (Event &e : ev) PG_TRY(hipEventCreate(&e.e));
-    PG_TRY(hipEventRecord(ev[0].e, s));
-    PG_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
-    PG_TRY(hipMemsetAsync(d_fin.p, 0, n + 1, s));
-    PG_TRY(hipMemsetAsync(d_kept.p, 0, 4 * (n + 1), s));
+    for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+    HIP_TRY(hipEventRecord(ev[0].e, s));
+    HIP_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
+    HIP_TRY(hipMemsetAsync(d_fin.p, 0, n + 1, s));
+    HIP_TRY(hipMemsetAsync(d_kept.p, 0, 4 * (n + 1), s));
     if (n) {
         vec_classify_kernel<<<page_grid, WG_THREADS, 0, s>>>(c, err);
         hipcub::TransformInputIterator<unsigned long long, TupleIncrement, const uint32_t *> inc(c.t_meta, TupleIncrement());
-        size_t tb = 0;
-        PG_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, inc, d_sum.as<unsigned long long>(), (int)n, s));
-        PG_TRY(d_tmp[0].alloc(tb));
-        PG_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp[0].p, tb, inc, d_sum.as<unsigned long long>(), (int)n, s));
-        PG_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, tb, c.t_mark, d_last.as<unsigned long long>(), MaxU64(), 0ull, (int)n, s));
-        PG_TRY(d_tmp[1].alloc(tb));
-        PG_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp[1].p, tb, c.t_mark, d_last.as<unsigned long long>(), MaxU64(), 0ull, (int)n, s));
+        HIP_TRY(with_cub_temp(d_tmp[0], [&](void *t, size_t &tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, inc, d_sum.as<unsigned long long>(), (int)n, s); }));
+        HIP_TRY(with_cub_temp(d_tmp[1], [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveScan(t, tb, c.t_mark, d_last.as<unsigned long long>(), MaxU64(), 0ull, (int)n, s); }));
         vec_resolve_kernel<<<tuple_grid, WG_THREADS, 0, s>>>(c, err);
         vec_kept_kernel<<<tuple_grid, WG_THREADS, 0, s>>>(c);
     }
     {   // n + 1 entries: the last one is the total
         hipcub::TransformInputIterator<unsigned long long, WidenU32, const uint32_t *> wide(c.t_kept, WidenU32());
-        size_t tb = 0;
-        PG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, wide, d_eoff.as<unsigned long long>(), (int)(n + 1), s));
-        PG_TRY(d_tmp[2].alloc(tb));
-        PG_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp[2].p, tb, wide, d_eoff.as<unsigned long long>(), (int)(n + 1), s));
+        HIP_TRY(with_cub_temp(d_tmp[2], [&](void *t, size_t &tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, wide, d_eoff.as<unsigned long long>(), (int)(n + 1), s); }));
     }
-    PG_TRY(hipGetLastError());
-    PG_TRY(hipEventRecord(ev[1].e, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1].e, s));
     unsigned long long key = 0, counts = 0, n_el = 0;
-    PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
-    if (n) PG_TRY(hipMemcpyAsync(&counts, d_sum.as<unsigned long long>() + (n - 1), 8, hipMemcpyDeviceToHost, s));
-    PG_TRY(hipMemcpyAsync(&n_el, d_eoff.as<unsigned long long>() + n, 8, hipMemcpyDeviceToHost, s));
-    PG_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    if (n) HIP_TRY(hipMemcpyAsync(&counts, d_sum.as<unsigned long long>() + (n - 1), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&n_el, d_eoff.as<unsigned long long>() + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     bytes_down += 24;
 
     // ---- the verdict so far: the host reader's refusals, then vbm25_growing_upload's in its order
@@ -559,12 +501,12 @@ int vectors_csr(hipStream_t s, Stager &st, uint32_t slot, vbm25_read_page_fn rea
 
     // ---- the CSR
     HbmArray &d_start = *o.start, &d_key = *o.key, &d_tf = *o.tf, &d_fn = *o.fieldnorm, &d_del = *o.deleted, &d_payload = *o.payload;
-    PG_TRY(d_start.alloc(8ull * (n_docs + 1ull)));
-    PG_TRY(d_key.alloc(16ull * n_el));
-    PG_TRY(d_tf.alloc(4ull * n_el));
-    PG_TRY(d_fn.alloc(n_docs));
-    PG_TRY(d_del.alloc(n_docs));
-    PG_TRY(d_payload.alloc(6ull * n_docs));
+    HIP_TRY(d_start.alloc(8ull * (n_docs + 1ull)));
+    HIP_TRY(d_key.alloc(16ull * n_el));
+    HIP_TRY(d_tf.alloc(4ull * n_el));
+    HIP_TRY(d_fn.alloc(n_docs));
+    HIP_TRY(d_del.alloc(n_docs));
+    HIP_TRY(d_payload.alloc(6ull * n_docs));
     c.n_docs = n_docs;
     c.n_el = n_el;
     c.start = d_start.as<unsigned long long>();
@@ -573,23 +515,23 @@ int vectors_csr(hipStream_t s, Stager &st, uint32_t slot, vbm25_read_page_fn rea
     c.fieldnorm = d_fn.as<uint8_t>();
     c.deleted = d_del.as<uint8_t>();
     c.payload = d_payload.as<uint16_t>();
-    PG_TRY(hipEventRecord(ev[2].e, s));
-    PG_TRY(hipMemsetAsync(d_start.p, 0, 8, s));
+    HIP_TRY(hipEventRecord(ev[2].e, s));
+    HIP_TRY(hipMemsetAsync(d_start.p, 0, 8, s));
     if (n_docs) vec_finish_kernel<<<page_grid, WG_THREADS, 0, s>>>(c);
     if (n_el) {
         vec_copy_kernel<<<page_grid, WG_THREADS, 0, s>>>(c);
         vec_check_kernel<<<page_grid, WG_THREADS, 0, s>>>(c, err);
     }
-    PG_TRY(hipGetLastError());
-    PG_TRY(hipEventRecord(ev[3].e, s));
-    PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
-    PG_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3].e, s));
+    HIP_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     bytes_down += 8;
     if (key != NO_ERROR)
         return set_error(VBM25_ERR_INVALID, "growing document %u: keys must be strictly ascending", (uint32_t)key_pos(key));
     float ms_a = 0, ms_b = 0;
-    PG_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
-    PG_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
+    HIP_TRY(hipEventElapsedTime(&ms_a, ev[0].e, ev[1].e));
+    HIP_TRY(hipEventElapsedTime(&ms_b, ev[2].e, ev[3].e));
     o.n_docs = n_docs;
     o.n_el = n_el;
     o.kernel_ms = (double)ms_a + (double)ms_b;
@@ -608,11 +550,11 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
     int device = 0;
     uint32_t sealed_docs = 0;
     if (int rc = index_device_and_docs(index, &device, &sealed_docs)) return rc;
-    PG_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     for (double &x : g_vec_stats) x = 0.0;
 
     Stream stream;
-    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     hipStream_t s = stream.s;
     // (the planes before the stager: they go last, after the stream's work has been waited for)
     HbmArray d_start, d_key, d_tf, d_fn, d_del, d_payload;
@@ -635,17 +577,17 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
         host->fieldnorm.resize(n_docs);
         host->payload.resize(3ull * n_docs);
         host->deleted.resize(n_docs);
-        PG_TRY(hipMemcpyAsync(host->start.data(), d_start.p, 8ull * (n_docs + 1ull), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(host->start.data(), d_start.p, 8ull * (n_docs + 1ull), hipMemcpyDeviceToHost, s));
         if (n_el) {
-            PG_TRY(hipMemcpyAsync(host->key.data(), d_key.p, 16ull * n_el, hipMemcpyDeviceToHost, s));
-            PG_TRY(hipMemcpyAsync(host->tf.data(), d_tf.p, 4ull * n_el, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(host->key.data(), d_key.p, 16ull * n_el, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(host->tf.data(), d_tf.p, 4ull * n_el, hipMemcpyDeviceToHost, s));
         }
         if (n_docs) {
-            PG_TRY(hipMemcpyAsync(host->fieldnorm.data(), d_fn.p, n_docs, hipMemcpyDeviceToHost, s));
-            PG_TRY(hipMemcpyAsync(host->payload.data(), d_payload.p, 6ull * n_docs, hipMemcpyDeviceToHost, s));
-            PG_TRY(hipMemcpyAsync(host->deleted.data(), d_del.p, n_docs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(host->fieldnorm.data(), d_fn.p, n_docs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(host->payload.data(), d_payload.p, 6ull * n_docs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(host->deleted.data(), d_del.p, n_docs, hipMemcpyDeviceToHost, s));
         }
-        PG_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipStreamSynchronize(s));
         bytes_down += 8ull * (n_docs + 1ull) + 20ull * n_el + 8ull * n_docs;
     }
 
@@ -724,11 +666,11 @@ int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, voi
     int device = 0;
     uint32_t sealed_docs = 0;
     if (int rc = index_device_and_docs(index, &device, &sealed_docs)) return rc;
-    PG_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     for (double &x : g_vac_stats) x = 0.0;
 
     Stream stream;
-    PG_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     hipStream_t s = stream.s;
     auto dv = std::make_unique<vbm25_device_vacuum>();  // (before the stager: its planes go last)
     dv->device = device;
@@ -757,46 +699,43 @@ int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, voi
     // ---- the flags.  From here on a failure returns through the buffers' destructors (hipFree waits for the device)
     float ms_flags = 0;
     {
-        DBuf d_chunk, d_pre, d_err, d_cnt, d_tmp;
+        HbmArray d_chunk, d_pre, d_err, d_cnt, d_tmp;
         std::vector<const uint8_t *> chunk_ptr;
         for (const auto &d : st.chunks[T_DOCS]) chunk_ptr.push_back(d->as<uint8_t>());
-        PG_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
-        PG_TRY(d_pre.alloc(4 * (np + 1)));
-        PG_TRY(d_err.alloc(8));
-        PG_TRY(d_cnt.alloc(4));
-        PG_TRY(dv->d_sealed_deleted.alloc(8ull * W));
-        if (np) PG_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
-        PG_TRY(hipMemcpyAsync(d_pre.p, w.pre[T_DOCS].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
+        HIP_TRY(d_chunk.alloc(sizeof(void *) * chunk_ptr.size()));
+        HIP_TRY(d_pre.alloc(4 * (np + 1)));
+        HIP_TRY(d_err.alloc(8));
+        HIP_TRY(d_cnt.alloc(4));
+        HIP_TRY(dv->d_sealed_deleted.alloc(8ull * W));
+        if (np) HIP_TRY(hipMemcpyAsync(d_chunk.p, chunk_ptr.data(), sizeof(void *) * chunk_ptr.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pre.p, w.pre[T_DOCS].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
         st.bytes_up += 8 * chunk_ptr.size() + 4 * (np + 1);
         Event ev[2];
-        for (Event &e : ev) PG_TRY(hipEventCreate(&e.e));
-        PG_TRY(hipEventRecord(ev[0].e, s));
-        PG_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
-        PG_TRY(hipMemsetAsync(d_cnt.p, 0, 4, s));
-        PG_TRY(hipMemsetAsync(dv->d_sealed_deleted.p, 0, W ? 8ull * W : 16, s));
+        for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+        HIP_TRY(hipEventRecord(ev[0].e, s));
+        HIP_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
+        HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 4, s));
+        HIP_TRY(hipMemsetAsync(dv->d_sealed_deleted.p, 0, W ? 8ull * W : 16, s));
         const TapeView docs{d_chunk.as<const uint8_t *>(), nullptr, d_pre.as<uint32_t>(), (uint32_t)np, w.pre[T_DOCS].back()};
         if (np && docs.n_tuples)
             doc_deleted_kernel<<<(uint32_t)((np + 3) / 4), WG_THREADS, 0, s>>>(docs, n_docs, dv->d_sealed_deleted.as<unsigned long long>(),
                                                                                d_err.as<unsigned long long>());
         if (W) {
             hipcub::TransformInputIterator<uint32_t, PopCount64, const unsigned long long *> pop(dv->d_sealed_deleted.as<unsigned long long>(), PopCount64());
-            size_t tb = 0;
-            PG_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, pop, d_cnt.as<uint32_t>(), (int)W, s));
-            PG_TRY(d_tmp.alloc(tb));
-            PG_TRY(hipcub::DeviceReduce::Sum(d_tmp.p, tb, pop, d_cnt.as<uint32_t>(), (int)W, s));
+            HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceReduce::Sum(t, tb, pop, d_cnt.as<uint32_t>(), (int)W, s); }));
         }
-        PG_TRY(hipGetLastError());
-        PG_TRY(hipEventRecord(ev[1].e, s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1].e, s));
         unsigned long long key = 0;
-        PG_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
-        PG_TRY(hipMemcpyAsync(&dv->n_sealed_deleted, d_cnt.p, 4, hipMemcpyDeviceToHost, s));
-        PG_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(&key, d_err.p, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&dv->n_sealed_deleted, d_cnt.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         bytes_down += 12;
         // ---- the verdict on the documents tape, in vbm25_sealed_deleted_from_pages' order
         if (key != NO_ERROR) return corrupt(doc_reason_text(key_reason(key)), error_page(w, key));
         if (!walked) return corrupt(w.what, w.bad_page);
         if (w.pre[T_DOCS].back() != n_docs) return corrupt("document count differs from the Jump tuple", ptr_documents);
-        PG_TRY(hipEventElapsedTime(&ms_flags, ev[0].e, ev[1].e));
+        HIP_TRY(hipEventElapsedTime(&ms_flags, ev[0].e, ev[1].e));
     }
     st.chunks[T_DOCS].clear();  // (synchronised above: the documents tape's images are done with)
     dv->n_sealed = n_docs;
@@ -808,15 +747,12 @@ int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, voi
     dv->n_grow = v.n_docs;
     dv->n_elements = v.n_el;
     if (v.n_docs) {
-        DBuf d_cnt, d_tmp;
-        PG_TRY(d_cnt.alloc(4));
+        HbmArray d_cnt, d_tmp;
+        HIP_TRY(d_cnt.alloc(4));
         hipcub::TransformInputIterator<uint32_t, NonZeroByte, const uint8_t *> nz(dv->d_deleted.as<uint8_t>(), NonZeroByte());
-        size_t tb = 0;
-        PG_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, nz, d_cnt.as<uint32_t>(), (int)v.n_docs, s));
-        PG_TRY(d_tmp.alloc(tb));
-        PG_TRY(hipcub::DeviceReduce::Sum(d_tmp.p, tb, nz, d_cnt.as<uint32_t>(), (int)v.n_docs, s));
-        PG_TRY(hipMemcpyAsync(&dv->n_grow_deleted, d_cnt.p, 4, hipMemcpyDeviceToHost, s));
-        PG_TRY(hipStreamSynchronize(s));
+        HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceReduce::Sum(t, tb, nz, d_cnt.as<uint32_t>(), (int)v.n_docs, s); }));
+        HIP_TRY(hipMemcpyAsync(&dv->n_grow_deleted, d_cnt.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         bytes_down += 4;
     }
     if (n_docs != sealed_docs)
@@ -831,10 +767,10 @@ int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, voi
 
 int vacuum_read_impl(const vbm25_device_vacuum *v, uint64_t *sealed_deleted_words, uint8_t *growing_deleted) {
     if (!v) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    PG_TRY(hipSetDevice(v->device));
+    HIP_TRY(hipSetDevice(v->device));
     const uint64_t W = ((uint64_t)v->n_sealed + 63u) / 64u;
-    if (sealed_deleted_words && W) PG_TRY(hipMemcpy(sealed_deleted_words, v->d_sealed_deleted.p, 8ull * W, hipMemcpyDeviceToHost));
-    if (growing_deleted && v->n_grow) PG_TRY(hipMemcpy(growing_deleted, v->d_deleted.p, v->n_grow, hipMemcpyDeviceToHost));
+    if (sealed_deleted_words && W) HIP_TRY(hipMemcpy(sealed_deleted_words, v->d_sealed_deleted.p, 8ull * W, hipMemcpyDeviceToHost));
+    if (growing_deleted && v->n_grow) HIP_TRY(hipMemcpy(growing_deleted, v->d_deleted.p, v->n_grow, hipMemcpyDeviceToHost));
     return VBM25_OK;
 }
 

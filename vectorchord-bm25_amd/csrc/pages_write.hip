@@ -32,52 +32,10 @@ namespace {
 using namespace vbm25;
 using namespace vbm25::pge;
 
-#define PW_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-struct Pinned {
-    void *p = nullptr;
-    ~Pinned() {
-        if (p) (void)hipHostFree(p);
-    }
-};
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-struct Quiesce {  // declared behind the call's buffers, so destroyed before them: nothing is freed under a kernel or a copy in flight
-    hipStream_t s;
-    ~Quiesce() { (void)hipStreamSynchronize(s); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
-
 // the last call's cost on this thread (vbm25_debug_pages_write_stats)
 thread_local double g_stats[6];
 
 constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
-uint32_t grid_for(uint64_t units, uint32_t per_block) { return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block)); }
 
 struct CostOf {
     const uint8_t *n, *md, *mt;
@@ -138,17 +96,17 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return set_error(VBM25_ERR_DEVICE, "no HIP device: the device writer has no CPU fallback");
     if (seg->device < 0 || seg->device >= n_dev) return set_error(VBM25_ERR_INVALID, "device %d out of range (%d devices)", seg->device, n_dev);
-    PW_TRY(hipSetDevice(seg->device));
+    HIP_TRY(hipSetDevice(seg->device));
     for (double &x : g_stats) x = 0.0;
 
     Stream stream;
-    PW_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     hipStream_t s = stream.s;
-    DBuf d_cost, d_jump[2], d_start, d_count, d_tmp, d_ids, d_key, d_tok_pid, d_sum_pid, d_blk_pid, d_img, d_pid;
-    Pinned pin[2];
+    HbmArray d_cost, d_jump[2], d_start, d_count, d_tmp, d_ids, d_key, d_tok_pid, d_sum_pid, d_blk_pid, d_img, d_pid;
+    PinnedHost pin[2];
     Event ev_layout[2], ev[2][3];  // ev, per staging buffer: fill begins, fill ends, copies end
     Quiesce quiesce{s};
-    for (Event &e : ev_layout) PW_TRY(hipEventCreate(&e.e));
+    for (Event &e : ev_layout) HIP_TRY(hipEventCreate(&e.e));
 
     const uint32_t n_docs = seg->n_docs, n_terms = seg->n_terms, n = seg->n_blocks;
     Emit c{};
@@ -177,34 +135,31 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
 
     // ---- the blocks tape's page breaks
     const uint32_t cap = n / MIN_BLOCKS_PER_PAGE + 2;  // a page that is not the last holds at least MIN_BLOCKS_PER_PAGE tuples
-    PW_TRY(d_cost.alloc(8ull * (n + 1ull)));
-    PW_TRY(d_start.alloc(4ull * cap));
-    PW_TRY(hipEventRecord(ev_layout[0].e, s));
-    PW_TRY(hipMemsetAsync(d_cost.p, 0, 8, s));
-    PW_TRY(hipMemsetAsync(d_start.p, 0, 4ull * cap, s));  // n == 0: {0, 0}
+    HIP_TRY(d_cost.alloc(8ull * (n + 1ull)));
+    HIP_TRY(d_start.alloc(4ull * cap));
+    HIP_TRY(hipEventRecord(ev_layout[0].e, s));
+    HIP_TRY(hipMemsetAsync(d_cost.p, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(d_start.p, 0, 4ull * cap, s));  // n == 0: {0, 0}
     if (n) {
-        PW_TRY(d_jump[0].alloc(4ull * (n + 1ull)));
-        PW_TRY(d_jump[1].alloc(4ull * (n + 1ull)));
-        PW_TRY(d_count.alloc(4));
-        PW_TRY(hipMemsetAsync(d_count.p, 0, 4, s));
+        HIP_TRY(d_jump[0].alloc(4ull * (n + 1ull)));
+        HIP_TRY(d_jump[1].alloc(4ull * (n + 1ull)));
+        HIP_TRY(d_count.alloc(4));
+        HIP_TRY(hipMemsetAsync(d_count.p, 0, 4, s));
         hipcub::CountingInputIterator<uint32_t> idx(0);
         hipcub::TransformInputIterator<unsigned long long, CostOf, hipcub::CountingInputIterator<uint32_t>> costs(idx, CostOf{c.blk_n, c.blk_meta_doc, c.blk_meta_tf});
-        size_t tb = 0;
-        PW_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, costs, d_cost.as<unsigned long long>() + 1, (int)n, s));
-        PW_TRY(d_tmp.alloc(tb));
-        PW_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp.p, tb, costs, d_cost.as<unsigned long long>() + 1, (int)n, s));
-        next_kernel<<<grid_for(n + 1ull, WG_THREADS), WG_THREADS, 0, s>>>(d_cost.as<unsigned long long>(), n, d_jump[0].as<uint32_t>());
+        HIP_TRY(with_cub_temp(d_tmp, [&](void *t, size_t &tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, costs, d_cost.as<unsigned long long>() + 1, (int)n, s); }));
+        next_kernel<<<grid_for(n + 1ull, WG_THREADS, MAX_GRID), WG_THREADS, 0, s>>>(d_cost.as<unsigned long long>(), n, d_jump[0].as<uint32_t>());
         int cur = 0;
         for (uint64_t have = 1; have < cap; have *= 2, cur ^= 1) {
             const bool last = 2 * have >= cap;
-            double_kernel<<<grid_for(std::max<uint64_t>(n + 1ull, have), WG_THREADS), WG_THREADS, 0, s>>>(
+            double_kernel<<<grid_for(std::max<uint64_t>(n + 1ull, have), WG_THREADS, MAX_GRID), WG_THREADS, 0, s>>>(
                 d_jump[cur].as<uint32_t>(), last ? nullptr : d_jump[cur ^ 1].as<uint32_t>(), n, d_start.as<uint32_t>(), (uint32_t)have, cap);
         }
-        count_kernel<<<grid_for(cap, WG_THREADS), WG_THREADS, 0, s>>>(d_start.as<uint32_t>(), cap, n, d_count.as<uint32_t>());
-        PW_TRY(hipGetLastError());
+        count_kernel<<<grid_for(cap, WG_THREADS, MAX_GRID), WG_THREADS, 0, s>>>(d_start.as<uint32_t>(), cap, n, d_count.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
         uint32_t b = 0;
-        PW_TRY(hipMemcpyAsync(&b, d_count.p, 4, hipMemcpyDeviceToHost, s));
-        PW_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(&b, d_count.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         if (b == 0) return set_error(VBM25_ERR_CORRUPT, "the blocks tape's page breaks did not close: the segment's block metadata is inconsistent");
         c.n_pages[T_BLOCKS] = b;
     }
@@ -224,9 +179,9 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
         if (sorted.back() == NONE) return set_error(VBM25_ERR_INVALID, "page id 0xFFFFFFFF is not a page");
         for (size_t i = 1; i < sorted.size(); ++i)
             if (sorted[i] == sorted[i - 1]) return set_error(VBM25_ERR_INVALID, "page id %u is given twice", sorted[i]);
-        PW_TRY(d_ids.alloc(4ull * total));
-        PW_TRY(hipMemcpyAsync(d_ids.p, page_ids, 4ull * total, hipMemcpyHostToDevice, s));
-        PW_TRY(hipStreamSynchronize(s));  // the caller's array is pageable
+        HIP_TRY(d_ids.alloc(4ull * total));
+        HIP_TRY(hipMemcpyAsync(d_ids.p, page_ids, 4ull * total, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));  // the caller's array is pageable
         bytes_up += 4ull * total;
         c.page_ids = d_ids.as<uint32_t>();
     } else if ((uint64_t)first_page + total > 0xffffffffull) {
@@ -234,30 +189,30 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     }
     c.first_page = first_page;
     auto id_of = [&](uint32_t alloc) { return page_ids ? page_ids[alloc] : first_page + alloc; };
-    PW_TRY(d_key.alloc(16ull * n_terms));
+    HIP_TRY(d_key.alloc(16ull * n_terms));
     if (n_terms) {
-        PW_TRY(hipMemcpyAsync(d_key.p, seg->term_key.data(), 16ull * n_terms, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_key.p, seg->term_key.data(), 16ull * n_terms, hipMemcpyHostToDevice, s));
         bytes_up += 16ull * n_terms;
     }
     c.term_key = d_key.as<uint8_t>();
-    PW_TRY(d_tok_pid.alloc(4ull * c.n_pages[T_TOKENS]));
-    PW_TRY(d_sum_pid.alloc(4ull * c.n_pages[T_SUMMARIES]));
-    PW_TRY(d_blk_pid.alloc(4ull * c.n_pages[T_BLOCKS]));
+    HIP_TRY(d_tok_pid.alloc(4ull * c.n_pages[T_TOKENS]));
+    HIP_TRY(d_sum_pid.alloc(4ull * c.n_pages[T_SUMMARIES]));
+    HIP_TRY(d_blk_pid.alloc(4ull * c.n_pages[T_BLOCKS]));
     c.tok_pid = d_tok_pid.as<uint32_t>();
     c.sum_pid = d_sum_pid.as<uint32_t>();
     c.blk_pid = d_blk_pid.as<uint32_t>();
     const uint32_t id_units = std::max(c.n_pages[T_BLOCKS], std::max(c.n_pages[T_SUMMARIES], c.n_pages[T_TOKENS]));
-    ids_kernel<<<grid_for(id_units, WG_THREADS), WG_THREADS, 0, s>>>(c, id_units);
-    PW_TRY(hipGetLastError());
-    PW_TRY(hipEventRecord(ev_layout[1].e, s));
+    ids_kernel<<<grid_for(id_units, WG_THREADS, MAX_GRID), WG_THREADS, 0, s>>>(c, id_units);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev_layout[1].e, s));
 
     // ---- the images, a chunk at a time: chunk i's callbacks run while chunk i + 1 is filled and copied
     constexpr size_t IMG_BYTES = (size_t)CHUNK_PAGES * BLCKSZ, PID_BYTES = 4ull * CHUNK_PAGES;
-    PW_TRY(d_img.alloc(IMG_BYTES));
-    PW_TRY(d_pid.alloc(PID_BYTES));
+    HIP_TRY(d_img.alloc(IMG_BYTES));
+    HIP_TRY(d_pid.alloc(PID_BYTES));
     for (int i = 0; i < 2; ++i) {
-        PW_TRY(hipHostMalloc(&pin[i].p, IMG_BYTES + PID_BYTES, hipHostMallocDefault));
-        for (Event &e : ev[i]) PW_TRY(hipEventCreate(&e.e));
+        HIP_TRY(hipHostMalloc(&pin[i].p, IMG_BYTES + PID_BYTES, hipHostMallocDefault));
+        for (Event &e : ev[i]) HIP_TRY(hipEventCreate(&e.e));
     }
     Sink sink{fn, ctx};
     std::vector<uint32_t> tok_pid(c.n_pages[T_TOKENS]);
@@ -269,10 +224,10 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     auto drain = [&]() -> int {
         if (pending.buf < 0) return VBM25_OK;
         Event *e = ev[pending.buf];
-        PW_TRY(hipEventSynchronize(e[2].e));
+        HIP_TRY(hipEventSynchronize(e[2].e));
         float a = 0, b = 0;
-        PW_TRY(hipEventElapsedTime(&a, e[0].e, e[1].e));
-        PW_TRY(hipEventElapsedTime(&b, e[1].e, e[2].e));
+        HIP_TRY(hipEventElapsedTime(&a, e[0].e, e[1].e));
+        HIP_TRY(hipEventElapsedTime(&b, e[1].e, e[2].e));
         fill_ms += a;
         copy_ms += b;
         const uint8_t *img = static_cast<const uint8_t *>(pin[pending.buf].p);
@@ -286,20 +241,20 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     int buf = 0;
     for (uint32_t tape = 0; tape < N_TAPES; ++tape)
         for (uint32_t p0 = 0; p0 < c.n_pages[tape]; p0 += CHUNK_PAGES, buf ^= 1) {
-            const uint32_t np = std::min(CHUNK_PAGES, c.n_pages[tape] - p0), grid = grid_for(np, WG_THREADS / 64);
+            const uint32_t np = std::min(CHUNK_PAGES, c.n_pages[tape] - p0), grid = grid_for(np, WG_THREADS / 64, MAX_GRID);
             uint64_t *out = d_img.as<uint64_t>();
             uint32_t *pid_out = d_pid.as<uint32_t>();
-            PW_TRY(hipEventRecord(ev[buf][0].e, s));
+            HIP_TRY(hipEventRecord(ev[buf][0].e, s));
             if (tape == T_DOCS) fill_kernel<T_DOCS><<<grid, WG_THREADS, 0, s>>>(c, p0, np, out, pid_out);
             else if (tape == T_TOKENS) fill_kernel<T_TOKENS><<<grid, WG_THREADS, 0, s>>>(c, p0, np, out, pid_out);
             else if (tape == T_SUMMARIES) fill_kernel<T_SUMMARIES><<<grid, WG_THREADS, 0, s>>>(c, p0, np, out, pid_out);
             else fill_kernel<T_BLOCKS><<<grid, WG_THREADS, 0, s>>>(c, p0, np, out, pid_out);
-            PW_TRY(hipGetLastError());
-            PW_TRY(hipEventRecord(ev[buf][1].e, s));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ev[buf][1].e, s));
             uint8_t *h = static_cast<uint8_t *>(pin[buf].p);
-            PW_TRY(hipMemcpyAsync(h, d_img.p, (size_t)np * BLCKSZ, hipMemcpyDeviceToHost, s));
-            PW_TRY(hipMemcpyAsync(h + IMG_BYTES, d_pid.p, 4ull * np, hipMemcpyDeviceToHost, s));
-            PW_TRY(hipEventRecord(ev[buf][2].e, s));
+            HIP_TRY(hipMemcpyAsync(h, d_img.p, (size_t)np * BLCKSZ, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(h + IMG_BYTES, d_pid.p, 4ull * np, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipEventRecord(ev[buf][2].e, s));
             bytes_down += (uint64_t)np * (BLCKSZ + 4);
             if (int rc = drain()) return rc;
             pending.buf = buf;
@@ -316,7 +271,7 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     if (sink.pages != total) return set_error(VBM25_ERR_INVALID, "internal error: %llu pages written, %llu counted", (unsigned long long)sink.pages, (unsigned long long)total);
     *flushed = f;
     float layout_ms = 0;
-    PW_TRY(hipEventElapsedTime(&layout_ms, ev_layout[0].e, ev_layout[1].e));
+    HIP_TRY(hipEventElapsedTime(&layout_ms, ev_layout[0].e, ev_layout[1].e));
     g_stats[0] = layout_ms;
     g_stats[1] = fill_ms;
     g_stats[2] = copy_ms;

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "vbm25_internal.h"
+#include "hip_host.h"
 #include "resolve_lane.h"
 #include "lexeme_input.h"
 
@@ -47,38 +48,10 @@ using vbm25::lexin::NEEDS_SEED;
 using vbm25::lexin::Seed;
 using vbm25::lexin::seed_words;
 
-#define RS_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct DBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        bytes = n ? n : 16;
-        return hipMalloc(&p, bytes);
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-
 constexpr uint32_t INTERN_THREADS = 64;   // one wave a block: the LDS stack is 32 bytes a level a lane
 constexpr uint32_t INTERN_GRID = 1024;    // one wave a SIMD of the 256 CUs; more lexemes than 65536 stride the grid
 constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
 constexpr uint32_t WAVE_QUERY = 64;       // the wave path's longest query
-
-uint32_t grid_for(uint64_t units, uint32_t per_block) {
-    return (uint32_t)std::min<uint64_t>(MAX_GRID, std::max<uint64_t>(1, (units + per_block - 1) / per_block));
-}
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // keys_out and ids may each be NULL.  The pool is 4-byte aligned and ends on a multiple of 4 (WordLoad).
 __global__ void __launch_bounds__(INTERN_THREADS) intern_kernel(Seed seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex,
@@ -188,8 +161,8 @@ int launch_intern(hipStream_t st, const Seed &seed, const uint32_t *pool, const 
                   const Key *vocab, uint32_t n_terms, Key *keys_out, uint32_t *ids) {
     if (!n_lex) return VBM25_OK;
     const size_t lds = size_t(stack_levels(longest)) * 8 * sizeof(uint32_t) * INTERN_THREADS;
-    intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS)), INTERN_THREADS, lds, st>>>(seed, pool, lex_off, n_lex, vocab, n_terms, keys_out, ids);
-    RS_TRY(hipGetLastError());
+    intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS, MAX_GRID)), INTERN_THREADS, lds, st>>>(seed, pool, lex_off, n_lex, vocab, n_terms, keys_out, ids);
+    HIP_TRY(hipGetLastError());
     return VBM25_OK;
 }
 
@@ -211,18 +184,13 @@ struct vbm25_resolver {
     Seed seed{};
     hipStream_t stream = nullptr;
     size_t in_capacity = 0, cub_bytes = 0;
-    DBuf vocab, in_dev, ids, tmp, counts, q_off, sort_a, sort_b, cub;
+    HbmArray vocab, in_dev, ids, tmp, counts, q_off, sort_a, sort_b, cub;
     Slot slots[16];
     uint32_t head = 0, count = 0;  // the oldest slot in flight; slots in flight
     int last_collected = -1;
 };
 
 namespace {
-
-int use_device(int device) {
-    RS_TRY(hipSetDevice(device));
-    return VBM25_OK;
-}
 
 int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes,
                     vbm25_resolver **out) {
@@ -253,36 +221,37 @@ int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint
     r->n_terms = n_terms;
     r->has_seed = seed32 != nullptr;
     seed_words(seed32, &r->seed);
-    RS_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
     // the staged block: q_lex | lex_off | bytes (rounded up to 4), or q_key | keys
     const size_t head_bytes = align_up(align_up(4ull * (max_queries + 1), 8) + 8ull * (max_lexemes + 1), 16);
     r->in_capacity = head_bytes + std::max<size_t>(align_up(max_bytes, 4), 16ull * max_lexemes);
     const size_t n1 = size_t(max_lexemes) + 1;
     size_t scan_q = 0, scan_l = 0, sort_l = 0;
-    RS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_q, (uint32_t *)nullptr, (uint32_t *)nullptr, int(max_queries + 1), r->stream));
-    RS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_l, (uint32_t *)nullptr, (uint32_t *)nullptr, int(n1), r->stream));
-    RS_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_l, (unsigned long long *)nullptr, (unsigned long long *)nullptr, int(max_lexemes), 0, 64,
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_q, (uint32_t *)nullptr, (uint32_t *)nullptr, int(max_queries + 1), r->stream));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_l, (uint32_t *)nullptr, (uint32_t *)nullptr, int(n1), r->stream));
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_l, (unsigned long long *)nullptr, (unsigned long long *)nullptr, int(max_lexemes), 0, 64,
                                              r->stream));
     r->cub_bytes = std::max(scan_q, std::max(scan_l, sort_l));
-    RS_TRY(r->vocab.alloc(16ull * n_terms));
-    RS_TRY(r->in_dev.alloc(r->in_capacity));
-    RS_TRY(r->ids.alloc(4 * n1));       // ids; the general path's flags
-    RS_TRY(r->tmp.alloc(4 * n1));       // the wave path's packed ids; the general path's positions
-    RS_TRY(r->counts.alloc(4ull * (max_queries + 1)));
-    RS_TRY(r->q_off.alloc(4ull * (max_queries + 1)));
-    RS_TRY(r->sort_a.alloc(8ull * max_lexemes));
-    RS_TRY(r->sort_b.alloc(8ull * max_lexemes + 4 * n1));  // the sorted keys, then the general path's flags
-    RS_TRY(r->cub.alloc(r->cub_bytes));
-    for (const DBuf *b : {&r->vocab, &r->in_dev, &r->ids, &r->tmp, &r->counts, &r->q_off, &r->sort_a, &r->sort_b, &r->cub}) r->device_bytes += b->bytes;
-    if (n_terms) RS_TRY(hipMemcpyAsync(r->vocab.p, term_key, 16ull * n_terms, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(r->vocab.alloc(16ull * n_terms));
+    HIP_TRY(r->in_dev.alloc(r->in_capacity));
+    HIP_TRY(r->ids.alloc(4 * n1));       // ids; the general path's flags
+    HIP_TRY(r->tmp.alloc(4 * n1));       // the wave path's packed ids; the general path's positions
+    HIP_TRY(r->counts.alloc(4ull * (max_queries + 1)));
+    HIP_TRY(r->q_off.alloc(4ull * (max_queries + 1)));
+    HIP_TRY(r->sort_a.alloc(8ull * max_lexemes));
+    HIP_TRY(r->sort_b.alloc(8ull * max_lexemes + 4 * n1));  // the sorted keys, then the general path's flags
+    HIP_TRY(r->cub.alloc(r->cub_bytes));
+    for (const HbmArray *b : {&r->vocab, &r->in_dev, &r->ids, &r->tmp, &r->counts, &r->q_off, &r->sort_a, &r->sort_b, &r->cub})
+        r->device_bytes += b->footprint();  // (16 for a zero-length buffer: the vocabulary of an index without terms)
+    if (n_terms) HIP_TRY(hipMemcpyAsync(r->vocab.p, term_key, 16ull * n_terms, hipMemcpyHostToDevice, r->stream));
     for (uint32_t i = 0; i < depth; ++i) {
         Slot &s = r->slots[i];
-        RS_TRY(hipHostMalloc((void **)&s.in, r->in_capacity, hipHostMallocDefault));
-        RS_TRY(hipHostMalloc((void **)&s.out, 4ull * (max_queries + 1) + 4ull * max_lexemes, hipHostMallocDefault));
-        RS_TRY(hipEventCreate(&s.start));
-        RS_TRY(hipEventCreate(&s.done));
+        HIP_TRY(hipHostMalloc((void **)&s.in, r->in_capacity, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&s.out, 4ull * (max_queries + 1) + 4ull * max_lexemes, hipHostMallocDefault));
+        HIP_TRY(hipEventCreate(&s.start));
+        HIP_TRY(hipEventCreate(&s.done));
     }
-    RS_TRY(hipStreamSynchronize(r->stream));  // (the index's host keys are not read after create)
+    HIP_TRY(hipStreamSynchronize(r->stream));  // (the index's host keys are not read after create)
     *out = r;
     guard.r = nullptr;
     return VBM25_OK;
@@ -293,31 +262,31 @@ int enqueue_pack(vbm25_resolver *r, Slot &s, const uint32_t *q_lex_dev, uint32_t
     hipStream_t st = r->stream;
     uint32_t *out_q_off = s.out, *out_ids = s.out + (r->max_queries + 1);
     if (longest_query <= WAVE_QUERY) {
-        pack_wave_kernel<<<grid_for(nq, WG_THREADS / 64), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, r->tmp.as<uint32_t>(),
+        pack_wave_kernel<<<grid_for(nq, WG_THREADS / 64, MAX_GRID), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, r->tmp.as<uint32_t>(),
                                                                                 r->counts.as<uint32_t>());
-        RS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         size_t tb = r->cub_bytes;
-        RS_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, r->counts.as<uint32_t>(), r->q_off.as<uint32_t>(), int(nq + 1), st));
-        gather_kernel<<<grid_for(nq, WG_THREADS / 64), WG_THREADS, 0, st>>>(r->tmp.as<uint32_t>(), q_lex_dev, r->q_off.as<uint32_t>(), nq, out_ids,
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, r->counts.as<uint32_t>(), r->q_off.as<uint32_t>(), int(nq + 1), st));
+        gather_kernel<<<grid_for(nq, WG_THREADS / 64, MAX_GRID), WG_THREADS, 0, st>>>(r->tmp.as<uint32_t>(), q_lex_dev, r->q_off.as<uint32_t>(), nq, out_ids,
                                                                              out_q_off);
-        RS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     } else {
         unsigned long long *ka = r->sort_a.as<unsigned long long>(), *kb = r->sort_b.as<unsigned long long>();
         uint32_t *flags = reinterpret_cast<uint32_t *>(kb + r->max_lexemes), *pos = r->tmp.as<uint32_t>();
-        sortkey_kernel<<<grid_for(n_lex, WG_THREADS), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, n_lex, ka);
-        RS_TRY(hipGetLastError());
+        sortkey_kernel<<<grid_for(n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, n_lex, ka);
+        HIP_TRY(hipGetLastError());
         int q_bits = 0;
         while (q_bits < 32 && (uint64_t(nq) >> q_bits)) ++q_bits;
         size_t tb = r->cub_bytes;
-        RS_TRY(hipcub::DeviceRadixSort::SortKeys(r->cub.p, tb, ka, kb, int(n_lex), 0, 32 + q_bits, st));
-        flag_kernel<<<grid_for(n_lex, WG_THREADS), WG_THREADS, 0, st>>>(kb, n_lex, flags);
-        RS_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(r->cub.p, tb, ka, kb, int(n_lex), 0, 32 + q_bits, st));
+        flag_kernel<<<grid_for(n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(kb, n_lex, flags);
+        HIP_TRY(hipGetLastError());
         tb = r->cub_bytes;
-        RS_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, flags, pos, int(n_lex + 1), st));
-        emit_kernel<<<grid_for(std::max(n_lex, nq + 1), WG_THREADS), WG_THREADS, 0, st>>>(kb, flags, pos, q_lex_dev, nq, n_lex, out_ids, out_q_off);
-        RS_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, flags, pos, int(n_lex + 1), st));
+        emit_kernel<<<grid_for(std::max(n_lex, nq + 1), WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(kb, flags, pos, q_lex_dev, nq, n_lex, out_ids, out_q_off);
+        HIP_TRY(hipGetLastError());
     }
-    RS_TRY(hipEventRecord(s.done, st));
+    HIP_TRY(hipEventRecord(s.done, st));
     return VBM25_OK;
 }
 
@@ -341,8 +310,8 @@ int resolver_submit_lexemes(vbm25_resolver *r, const uint8_t *bytes, const uint6
     std::memcpy(s.in + o_lex, lex_off, 8ull * (sh.n_lex + 1));
     if (sh.n_bytes) std::memcpy(s.in + o_bytes, bytes, sh.n_bytes);
     uint8_t *d = r->in_dev.as<uint8_t>();
-    RS_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
-    RS_TRY(hipEventRecord(s.start, r->stream));
+    HIP_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(s.start, r->stream));
     const uint32_t *q_lex_dev = reinterpret_cast<const uint32_t *>(d);
     if (int rc = launch_intern(r->stream, r->seed, reinterpret_cast<const uint32_t *>(d + o_bytes), reinterpret_cast<const uint64_t *>(d + o_lex),
                                sh.n_lex, sh.longest_lexeme, r->vocab.as<Key>(), r->n_terms, nullptr, r->ids.as<uint32_t>()))
@@ -366,12 +335,12 @@ int resolver_submit_keys(vbm25_resolver *r, const uint8_t *keys16, const uint32_
     std::memcpy(s.in, q_key, 4ull * (nq + 1));
     if (sh.n_lex) std::memcpy(s.in + o_keys, keys16, 16ull * sh.n_lex);
     uint8_t *d = r->in_dev.as<uint8_t>();
-    RS_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
-    RS_TRY(hipEventRecord(s.start, r->stream));
+    HIP_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(s.start, r->stream));
     if (sh.n_lex) {
-        lookup_kernel<<<grid_for(sh.n_lex, WG_THREADS), WG_THREADS, 0, r->stream>>>(reinterpret_cast<const Key *>(d + o_keys), sh.n_lex, r->vocab.as<Key>(),
+        lookup_kernel<<<grid_for(sh.n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, r->stream>>>(reinterpret_cast<const Key *>(d + o_keys), sh.n_lex, r->vocab.as<Key>(),
                                                                                      r->n_terms, r->ids.as<uint32_t>());
-        RS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (int rc = enqueue_pack(r, s, reinterpret_cast<const uint32_t *>(d), nq, sh.n_lex, sh.longest_query)) return rc;
     s.nq = nq;
@@ -384,7 +353,7 @@ int resolver_collect(vbm25_resolver *r, uint32_t *term_ids, uint32_t *q_off, uin
     if (!r->count) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the resolver");
     if (int rc = use_device(r->device)) return rc;
     Slot &s = r->slots[r->head];
-    RS_TRY(hipEventSynchronize(s.done));
+    HIP_TRY(hipEventSynchronize(s.done));
     const uint32_t n_ids = s.out[s.nq];
     if (n_ids && !term_ids) return set_error(VBM25_ERR_INVALID, "NULL argument");
     std::memcpy(q_off, s.out, 4ull * (s.nq + 1));
@@ -409,26 +378,18 @@ int intern_batch_device(int device, const uint8_t *seed32, const uint8_t *bytes,
     std::vector<uint8_t> stage(total, 0);
     std::memcpy(stage.data(), lex_off, 8ull * (n_lex + 1));
     if (sh.n_bytes) std::memcpy(stage.data() + o_bytes, bytes, sh.n_bytes);
-    struct OwnStream {  // (a stream of its own: a launch on the null stream would wait for every other stream of the device)
-        hipStream_t s = nullptr;
-        ~OwnStream() {
-            if (s) {
-                (void)hipStreamSynchronize(s);
-                (void)hipStreamDestroy(s);
-            }
-        }
-    };
-    DBuf in, keys;
-    OwnStream st;  // (declared behind the buffers, so destroyed -- and waited for -- before they are freed)
-    RS_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    RS_TRY(in.alloc(total));
-    RS_TRY(keys.alloc(16ull * n_lex));
-    RS_TRY(hipMemcpyAsync(in.p, stage.data(), total, hipMemcpyHostToDevice, st.s));
+    HbmArray in, keys;
+    Stream st;  // (a stream of its own: a launch on the null stream would wait for every other stream of the device)
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    Quiesce quiesce(st.s);  // (behind the buffers and the stream: waited for before the one is destroyed and the others are freed)
+    HIP_TRY(in.alloc(total));
+    HIP_TRY(keys.alloc(16ull * n_lex));
+    HIP_TRY(hipMemcpyAsync(in.p, stage.data(), total, hipMemcpyHostToDevice, st.s));
     if (int rc = launch_intern(st.s, seed, reinterpret_cast<const uint32_t *>(in.as<uint8_t>() + o_bytes), in.as<uint64_t>(), n_lex, sh.longest_lexeme,
                                nullptr, 0, keys.as<Key>(), nullptr))
         return rc;
-    RS_TRY(hipMemcpyAsync(keys16, keys.p, 16ull * n_lex, hipMemcpyDeviceToHost, st.s));
-    RS_TRY(hipStreamSynchronize(st.s));
+    HIP_TRY(hipMemcpyAsync(keys16, keys.p, 16ull * n_lex, hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
     return VBM25_OK;
 }
 
@@ -502,7 +463,7 @@ int vbm25_search_batch_lexemes(vbm25_index *ix, const uint8_t *seed32, const uin
 int vbm25_debug_resolver_kernel_ms(vbm25_resolver *r, double *ms) {
     if (!r || !ms || r->last_collected < 0) return set_error(VBM25_ERR_INVALID, "no collected batch");
     float f = 0;
-    RS_TRY(hipEventElapsedTime(&f, r->slots[r->last_collected].start, r->slots[r->last_collected].done));
+    HIP_TRY(hipEventElapsedTime(&f, r->slots[r->last_collected].start, r->slots[r->last_collected].done));
     *ms = f;
     return VBM25_OK;
 }

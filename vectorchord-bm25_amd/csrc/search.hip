@@ -50,14 +50,6 @@ int set_error(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return set_error(VBM25_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr,               \
-                             hipGetErrorString(e_), __FILE__, __LINE__);                     \
-    } while (0)
-
 #include "device_types.h"
 #include "decode.h"
 #include "plan.h"
@@ -177,13 +169,10 @@ __global__ void __launch_bounds__(256) evaluate_kernel(EvalArgs a) {
 // ---------------------------------------------------------------------------
 // Host objects
 // ---------------------------------------------------------------------------
-struct DeviceBuffer {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~DeviceBuffer() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
+// An HbmArray whose alloc and upload return the library's codes and set the error text, for the `(rc = a.alloc(..)) || (rc = b.upload(..))`
+// chains of this file.  Nothing of its own to own: storage and destructor are HbmArray's.
+struct DeviceBuffer : HbmArray {
+    int alloc(size_t n) {  // (HbmArray::alloc, spelled out: a failure's text goes on naming hipMalloc and its size)
         bytes = n;
         HIP_TRY(hipMalloc(&p, n ? n : 16));
         return VBM25_OK;
@@ -192,10 +181,6 @@ struct DeviceBuffer {
         if (int rc = alloc(n)) return rc;
         if (n) HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
         return VBM25_OK;
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
     }
 };
 
@@ -471,11 +456,6 @@ void fill_dev(vbm25_index *ix) {
 
 namespace {
 
-int use_device(int device) {
-    HIP_TRY(hipSetDevice(device));
-    return VBM25_OK;
-}
-
 template <class F>
 int dispatch_k(uint32_t k, F &&f) {
     if (k <= 64) return f(std::integral_constant<int, 64>());
@@ -650,13 +630,11 @@ static int index_create_common(const RawSegment &r, int device, vbm25_index **ou
             // per term the 2^i-th largest block maximum, i = 0..8 (the scan kernels' first threshold: with block WAND pairs
             // every block maximum is the score of a posting of its block -- post_fn_kernel verifies that -- so k distinct
             // documents of the term score at least the k-th largest of them): a segmented sort of the maxima by term
-            size_t tb = 0;
             const uint32_t *seg = ix->term_first_block.as<uint32_t>();
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, tb, t_raw.as<double>(), t_sorted.as<double>(), (int)r.n_blocks,
-                                                                        (int)r.n_terms, seg, seg + 1));
-            if ((rc = t_tmp.alloc(tb))) return rc;
-            HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(t_tmp.p, tb, t_raw.as<double>(), t_sorted.as<double>(), (int)r.n_blocks,
-                                                                        (int)r.n_terms, seg, seg + 1));
+            HIP_TRY(with_cub_temp(t_tmp, [&](void *t, size_t &tb) {
+                return hipcub::DeviceSegmentedRadixSort::SortKeysDescending(t, tb, t_raw.as<double>(), t_sorted.as<double>(), (int)r.n_blocks,
+                                                                            (int)r.n_terms, seg, seg + 1);
+            }));
             kth_pick_kernel<<<(r.n_terms * KTH_LEVELS + 255) / 256, 256>>>(r.n_terms, seg, t_sorted.as<double>(), ix->term_kth_ub.as<double>());
             HIP_TRY(hipGetLastError());
         }
@@ -701,17 +679,11 @@ static int index_create_common(const RawSegment &r, int device, vbm25_index **ou
         ix->term_win_host = std::move(term_win);
         ix->n_win = n_win;
     } else {
-        for (DeviceBuffer *b : {&ix->post_id16, &ix->win_off, &ix->term_win}) {
-            if (b->p) (void)hipFree(b->p);
-            b->p = nullptr;
-            b->bytes = 0;
-        }
+        for (DeviceBuffer *b : {&ix->post_id16, &ix->win_off, &ix->term_win}) b->release();
     }
     ix->dev.blk_ub_attained = has_wand && !(flag & 4u) ? 1u : 0u;
     if (!ix->dev.blk_ub_attained && ix->term_kth_ub.p) {  // the k-th largest maxima bound nothing then: kept out of the index (and its replicas)
-        (void)hipFree(ix->term_kth_ub.p);
-        ix->term_kth_ub.p = nullptr;
-        ix->term_kth_ub.bytes = 0;
+        ix->term_kth_ub.release();
     }
     fill_dev(ix.get());
     ix->dev.blob_bytes = r.blob_bytes;
@@ -2238,12 +2210,10 @@ static int growing_build(vbm25_index *ix, const GrowingDeviceArrays &a, DeviceBu
                                                          cnt.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         // (term id, g) ascending: a stable order of the postings by term with g ascending inside a term (flush.hip's sort of the mappings)
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
-                                                   vals.as<uint32_t>(), vals2.as<uint32_t>(), (int)n_el));
-        if ((rc = tmp.alloc(tb))) return rc;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(),
-                                                   vals.as<uint32_t>(), vals2.as<uint32_t>(), (int)n_el));
+        HIP_TRY(with_cub_temp(tmp, [&](void *t, size_t &tb) {
+            return hipcub::DeviceRadixSort::SortPairs(t, tb, keys.as<unsigned long long>(), keys2.as<unsigned long long>(), vals.as<uint32_t>(),
+                                                      vals2.as<uint32_t>(), (int)n_el);
+        }));
         HIP_TRY(hipMemcpy(&n_post, cnt.p, 4, hipMemcpyDeviceToHost));
     }
     gs->n_post = n_post;
