@@ -1,0 +1,61 @@
+// evaluate_example.cpp -- the `<&>` operator from tsvector lexemes through the C++ host API: cast documents, the index ambuild makes of
+// them, a resolver, the bind and one batch of queries with candidate lists (then the same queries against every document).
+//   g++ -std=c++17 -Iinclude examples/evaluate_example.cpp -Lvectorchord-bm25_amd/csrc -lvbm25 -o /tmp/evaluate_example
+// Prints every score as a hexadecimal float; tests/test_cpp_evaluate_mirror.py compares them with the Python mirror's.
+#include <cstdio>
+#include <string>
+
+#include "vbm25.hpp"
+
+int main() {
+    try {
+        vbm25::Seed seed{};
+        for (size_t i = 0; i < seed.size(); ++i) seed[i] = uint8_t(7 + i);
+        // 40 documents over 12 lexemes (every third one of the hashed kind): document d holds lexeme j when (d + j) % (2 + j % 3) == 0
+        auto lexeme = [](int j) { return j % 3 ? "t" + std::to_string(j) : "a-lexeme-of-the-long-kind-" + std::to_string(j); };
+        vbm25::DocumentBatch batch;
+        for (int d = 0; d < 40; ++d) {
+            for (int j = 0; j < 12; ++j)
+                if ((d + j) % (2 + j % 3) == 0) batch.add(lexeme(j), uint32_t(1 + (d * 7 + j) % 4));
+            const uint16_t ctid[3] = {0, uint16_t(d), 1};
+            batch.end_document(ctid);
+        }
+        vbm25::Documents sealed(0, &seed, batch);
+        vbm25::DeviceSegment segment = vbm25::DeviceSegment::from_documents(sealed, 1.2, 0.75);
+        vbm25::Index index(segment.handle());
+        vbm25::Resolver resolver(index, &seed, 1, 8, 64, 4096);
+        // the rows to score: the same documents and one with a lexeme the index lacks
+        batch.add("t1", 2);
+        batch.add("not-in-the-index", 9);
+        const uint16_t ctid[3] = {0, 40, 1};
+        batch.end_document(ctid);
+        vbm25::Documents rows(0, &seed, batch);
+        vbm25::DocTerms bound = rows.bind(resolver);
+        std::printf("bound %u documents, %llu of %llu elements known\n", bound.docs(), (unsigned long long)bound.known(), (unsigned long long)rows.elements());
+        vbm25::LexemeBatch queries;
+        for (const char *t : {"t1", "t2", "unknown"}) queries.add(t);
+        queries.end_query();
+        queries.add(lexeme(0));
+        queries.add("t4");
+        queries.end_query();
+        queries.end_query();  // (a query without lexemes)
+        resolver.submit(queries);
+        std::vector<uint32_t> term_ids, q_off;
+        resolver.collect(term_ids, q_off);
+        const std::vector<uint64_t> q_cand{0, 3, 5, 6};
+        const std::vector<uint32_t> cand_doc{40, 0, 7, 39, 39, 2};
+        const std::vector<double> listed = bound.evaluate(term_ids, q_off, q_cand, cand_doc);
+        for (size_t i = 0; i < listed.size(); ++i) std::printf("listed %zu %a\n", i, listed[i]);
+        const std::vector<double> all = bound.evaluate(term_ids, q_off);
+        for (size_t i = 0; i < all.size(); ++i) std::printf("cross %zu %a\n", i, all[i]);
+        try {
+            bound.evaluate(term_ids, q_off, q_cand, {41, 0, 7, 39, 39, 2});
+        } catch (const vbm25::Error &e) {
+            std::printf("candidate out of range: error %d\n", e.code);
+        }
+    } catch (const vbm25::Error &e) {
+        std::printf("error %d: %s\n", e.code, e.what());
+        return 1;
+    }
+    return 0;
+}

@@ -812,6 +812,42 @@ void vbm25_documents_free(vbm25_documents *);
 int vbm25_device_segment_build_documents(const vbm25_documents *, double k1, double b, vbm25_device_segment **out);
 int vbm25_device_growing_append_documents(vbm25_device_growing *, const vbm25_documents *);
 
+/* The `<&>` operator from cast documents (csrc/evaluate.hip): bm25::evaluate (evaluate.rs:22-74) for a batch of queries, each
+ * against its own list of candidate documents -- the reranking form of `tsvector <&> bm25query` (src/index/operators.rs:22-55) --
+ * with the documents read from HBM.  Two steps.
+ *   vbm25_documents_bind   the handle's keys looked up in ONE index's vocabulary, which that index's resolver already keeps in HBM
+ *             (nothing is uploaded): per document the ascending term ids of the elements the vocabulary holds, with their tfs, and
+ *             the fieldnorm code the cast gave the document (elements the vocabulary lacks count for the length and never score).
+ *             The bound handle refers to the resolver's index, which must outlive it; the resolver and the vbm25_documents may be
+ *             freed after the bind.  It is valid for that index only: after a compaction the caller binds again.  A handle of 0
+ *             documents binds to a valid handle of 0 documents.  VBM25_ERR_INVALID, *out == NULL, nothing enqueued: NULL arguments,
+ *             a handle and a resolver on different devices.
+ *   info / download        n_docs, n_known (the elements kept) and the device; start (n_docs + 1 entries), term and tf (n_known
+ *             each; either may be NULL when n_known is 0) copied to the host.
+ *   vbm25_evaluate_documents   queries as the CSR term_ids / q_off every search entry point takes (vbm25_resolver_collect's output):
+ *             per query the ids strictly ascending, ids >= the index's term count ignored.  Query q scores the documents
+ *             cand_doc[q_cand[q] .. q_cand[q+1]) -- indices into the handle, any order, repeats allowed -- and scores is aligned
+ *             with cand_doc.  q_cand == NULL: every query scores every document, scores is nq x n_docs, row-major.
+ *             scores[i] is bit for bit what vbm25_evaluate returns for the pair (the document's keys and tfs as
+ *             vbm25_documents_download gives them, the query's keys): the sum, in query key order, of
+ *             idf * ((tf * (k1 + 1)) / (tf + s1[fieldnorm])) over the query's terms the document holds, with the idf and s1 tables of
+ *             vbm25_evaluate_batch.  The SQL operator negates the value; the library does not.
+ *             VBM25_ERR_INVALID with a message that names the first offender, before anything is enqueued: NULL term_ids, q_off or
+ *             scores (nq > 0), q_off[0] != 0 or q_cand[0] != 0, offsets that are not monotone, cand_doc NULL while q_cand is not, a
+ *             query whose ids do not ascend strictly, a candidate >= n_docs, an index without sealed documents.
+ *             VBM25_ERR_UNSUPPORTED for 2^31 pairs or more.  nq == 0 and queries without candidates are legal and write nothing.
+ * Both calls are synchronous, each on a stream of its own: no device-wide synchronisation is issued (freeing the call's buffers
+ * at return waits for the device's other streams, as every hipFree does).  The handle is only read: two threads may score on one
+ * handle at once.  One wave scores 64 candidates of one query; a lane finds each query term in its document's id run by bisection. */
+typedef struct vbm25_doc_terms vbm25_doc_terms;
+int vbm25_documents_bind(const vbm25_documents *, const vbm25_resolver *, vbm25_doc_terms **out);
+int vbm25_doc_terms_info(const vbm25_doc_terms *, uint32_t *n_docs, uint64_t *n_known, int *device);
+int vbm25_doc_terms_download(const vbm25_doc_terms *, uint64_t *start, uint32_t *term, uint32_t *tf);
+uint64_t vbm25_doc_terms_device_bytes(const vbm25_doc_terms *);
+void vbm25_doc_terms_free(vbm25_doc_terms *);
+int vbm25_evaluate_documents(const vbm25_doc_terms *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq,
+                             const uint64_t *q_cand, const uint32_t *cand_doc, double *scores);
+
 #ifdef __cplusplus
 }
 #endif

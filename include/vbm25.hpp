@@ -11,6 +11,7 @@
 //   vbm25::Segment::from_pages, vbm25::growing_from_pages   the relation's pages -> flat arrays (tape.rs, tuples.rs)
 //   vbm25::DeviceGrowing::from_pages, vbm25::sealed_deleted_from_pages   the vectors tape read on the device; the sealed deleted flags
 //   vbm25::DeviceVacuum::from_pages, ::maintain, DocFilter::remap(index, vacuum)   VACUUM's inputs read and consumed on the device
+//   vbm25::Documents::bind, vbm25::DocTerms::evaluate   crates/bm25/src/evaluate.rs:22-74 for query batches with candidate rows, on the device
 // Reference panics ("data corruption", "invalid data") and pgrx::error! become vbm25::Error.
 #ifndef VBM25_HPP
 #define VBM25_HPP
@@ -207,6 +208,7 @@ struct DocumentBatch {
 };
 
 struct GrowingDocs;
+class DocTerms;
 // The Document step on the device (RAII over vbm25_documents): cast_tsvector_to_document for a batch of tsvectors, the result kept in
 // HBM.  DeviceSegment::from_documents makes the index of it, DeviceGrowing::append appends it, download() brings the CSR back.
 class Documents {
@@ -232,11 +234,72 @@ class Documents {
     uint64_t device_bytes() const { return vbm25_documents_device_bytes(h_); }
     // the CSR (payload empty when the cast had none) and, when asked for, the documents' lengths
     inline GrowingDocs download(std::vector<uint32_t> *doc_len = nullptr) const;
+    // the documents' keys looked up in the vocabulary the resolver holds in HBM (vbm25_documents_bind): valid for its index only
+    inline DocTerms bind(const Resolver &resolver) const;
     const vbm25_documents *handle() const { return h_; }
 
   private:
     vbm25_documents *h_ = nullptr;
 };
+
+// Cast documents bound to one index's vocabulary (RAII over vbm25_doc_terms): per document the ascending term ids of its known
+// elements with their tfs, and its fieldnorm code, in HBM.  evaluate() is bm25::evaluate (evaluate.rs:22-74) for a batch of queries,
+// each against its own candidate documents; the SQL operator `<&>` returns the negation of these values.  The index must outlive it.
+class DocTerms {
+  public:
+    DocTerms(const Documents &documents, const Resolver &resolver) { check(vbm25_documents_bind(documents.handle(), resolver.handle(), &h_)); }
+    DocTerms(DocTerms &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DocTerms(const DocTerms &) = delete;
+    DocTerms &operator=(const DocTerms &) = delete;
+    ~DocTerms() { vbm25_doc_terms_free(h_); }
+    uint32_t docs() const {
+        uint32_t n = 0;
+        check(vbm25_doc_terms_info(h_, &n, nullptr, nullptr));
+        return n;
+    }
+    uint64_t known() const {
+        uint64_t n = 0;
+        check(vbm25_doc_terms_info(h_, nullptr, &n, nullptr));
+        return n;
+    }
+    uint64_t device_bytes() const { return vbm25_doc_terms_device_bytes(h_); }
+    void download(std::vector<uint64_t> &start, std::vector<uint32_t> &term, std::vector<uint32_t> &tf) const {
+        start.assign(size_t(docs()) + 1, 0);
+        term.assign(known() + 1, 0);
+        tf.assign(known() + 1, 0);
+        check(vbm25_doc_terms_download(h_, start.data(), term.data(), tf.data()));
+        term.pop_back();
+        tf.pop_back();
+    }
+    // query q (term_ids[q_off[q] .. q_off[q+1]), ascending) scores the documents cand_doc[q_cand[q] .. q_cand[q+1]): aligned with cand_doc
+    std::vector<double> evaluate(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, const std::vector<uint64_t> &q_cand,
+                                 const std::vector<uint32_t> &cand_doc) const {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        if (q_cand.size() != q_off.size()) throw Error(VBM25_ERR_INVALID, "one candidate range per query");
+        std::vector<double> scores(cand_doc.size() + 1);
+        std::vector<uint32_t> ids(term_ids), docs(cand_doc);
+        ids.push_back(0);  // (never NULL)
+        docs.push_back(0);
+        check(vbm25_evaluate_documents(h_, ids.data(), q_off.data(), nq, q_cand.data(), docs.data(), scores.data()));
+        scores.pop_back();
+        return scores;
+    }
+    // every query against every document: nq x docs(), row-major
+    std::vector<double> evaluate(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off) const {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        std::vector<double> scores(size_t(nq) * docs() + 1);
+        std::vector<uint32_t> ids(term_ids);
+        ids.push_back(0);
+        check(vbm25_evaluate_documents(h_, ids.data(), q_off.data(), nq, nullptr, nullptr, scores.data()));
+        scores.pop_back();
+        return scores;
+    }
+    const vbm25_doc_terms *handle() const { return h_; }
+
+  private:
+    vbm25_doc_terms *h_ = nullptr;
+};
+inline DocTerms Documents::bind(const Resolver &resolver) const { return DocTerms(*this, resolver); }
 
 class DeviceGrowing;
 class DeviceVacuum;

@@ -168,6 +168,12 @@ ABI = {
     "vbm25_documents_free": (None, [vp]),
     "vbm25_device_segment_build_documents": (i32, [vp, C.c_double, C.c_double, vp]),
     "vbm25_device_growing_append_documents": (i32, [vp, vp]),
+    "vbm25_documents_bind": (i32, [vp, vp, vp]),
+    "vbm25_doc_terms_info": (i32, [vp, vp, vp, vp]),
+    "vbm25_doc_terms_download": (i32, [vp, vp, vp, vp]),
+    "vbm25_doc_terms_device_bytes": (u64, [vp]),
+    "vbm25_doc_terms_free": (None, [vp]),
+    "vbm25_evaluate_documents": (i32, [vp, vp, vp, u32, vp, vp, vp]),
 }
 
 

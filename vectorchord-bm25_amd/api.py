@@ -1111,7 +1111,8 @@ def set_tuning(name, value):
     range_min_chunk, range_grid, dense_grid, fused_items, arith, win, win_force, win_items, win_grid, win_skew, win_guided,
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
-    and cast_group_max (the class bounds of Documents.cast, read at the start of each cast; 0 turns the class off).  No switch of
+    and cast_group_max (the class bounds of Documents.cast, read at the start of each cast; 0 turns the class off), eval_grid (the
+    most workgroups of the kernels of Documents.bind and DocTerms.evaluate, 1 .. 2048, read at the start of each call).  No switch of
     the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
     libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set
@@ -1240,10 +1241,77 @@ class Documents:
         out["length"] = length
         return out
 
+    def bind(self, resolver):
+        """vbm25_documents_bind: the documents' keys looked up in the vocabulary `resolver` holds in HBM -> DocTerms, what
+        DocTerms.evaluate scores.  Valid for the resolver's index only."""
+        out = C.c_void_p()
+        check(lib().vbm25_documents_bind(self.h, resolver.h, C.byref(out)))
+        return DocTerms(out, resolver.index)
+
     def __del__(self):
         try:
             if self.h:
                 lib().vbm25_documents_free(self.h)
+        except Exception:
+            pass
+
+
+def _at_least_one(a, dtype):
+    """contiguous, and never zero-sized: the library refuses NULL pointers, numpy gives an empty array's data no address to rely on"""
+    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    return a if a.size else np.zeros(1, dtype=dtype)
+
+
+class DocTerms:
+    """vbm25_doc_terms: cast documents bound to one index's vocabulary -- per document the ascending term ids of its known elements
+    with their tfs, and its fieldnorm code, in HBM.  evaluate() is the `<&>` operator (bm25::evaluate, evaluate.rs:22-74) for a batch
+    of queries, each against its own candidate documents; the SQL operator returns the negation of these values."""
+
+    def __init__(self, handle, index=None):
+        self.h = handle
+        self.index = index  # (kept alive: the handle refers to it)
+        nd, nk, dev = C.c_uint32(), C.c_uint64(), C.c_int()
+        check(lib().vbm25_doc_terms_info(self.h, C.byref(nd), C.byref(nk), C.byref(dev)))
+        self.n_docs, self.n_known, self.device = nd.value, nk.value, dev.value
+
+    def device_bytes(self):
+        return int(lib().vbm25_doc_terms_device_bytes(self.h))
+
+    def download(self):
+        """(start uint64 [n_docs + 1], term uint32 [n_known], tf uint32 [n_known])"""
+        start = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        term, tf = np.zeros(max(self.n_known, 1), dtype=np.uint32), np.zeros(max(self.n_known, 1), dtype=np.uint32)
+        check(lib().vbm25_doc_terms_download(self.h, start.ctypes.data, term.ctypes.data, tf.ctypes.data))
+        return start, term[:self.n_known], tf[:self.n_known]
+
+    def evaluate(self, term_ids, q_off, q_cand=None, cand_doc=None):
+        """vbm25_evaluate_documents: queries as the CSR (term_ids, q_off) Resolver.collect returns.  Query q scores the documents
+        cand_doc[q_cand[q]:q_cand[q+1]] (indices into this handle) -> float64 aligned with cand_doc; without q_cand every query
+        scores every document -> float64 [nq, n_docs]."""
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+        nq = len(q_off) - 1
+        term_ids = _at_least_one(term_ids, np.uint32)
+        if q_cand is None:
+            if cand_doc is not None:
+                raise ValueError("cand_doc without q_cand")
+            scores = np.zeros((nq, self.n_docs), dtype=np.float64)
+            qc = dc = None
+        else:
+            q_cand = np.ascontiguousarray(q_cand, dtype=np.uint64)
+            if len(q_cand) != nq + 1:
+                raise ValueError(f"{len(q_cand)} candidate offsets for {nq} queries")
+            scores = np.zeros(int(q_cand[nq]), dtype=np.float64)
+            qc = q_cand.ctypes.data
+            dc = None if cand_doc is None else _at_least_one(cand_doc, np.uint32)
+        out = scores if scores.size else np.zeros(1, dtype=np.float64)
+        check(lib().vbm25_evaluate_documents(self.h, term_ids.ctypes.data, q_off.ctypes.data, nq, qc, None if dc is None else dc.ctypes.data,
+                                             out.ctypes.data))
+        return scores
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().vbm25_doc_terms_free(self.h)
         except Exception:
             pass
 

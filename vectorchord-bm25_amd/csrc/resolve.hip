@@ -413,6 +413,13 @@ int search_batch_lexemes(vbm25_index *ix, const uint8_t *seed32, const uint8_t *
 
 }  // namespace
 
+namespace vbm25 {
+int resolver_vocabulary(const vbm25_resolver *r, ResolverVocabulary *out) {
+    *out = ResolverVocabulary{r->index, r->device, r->n_terms, r->vocab.p};
+    return VBM25_OK;
+}
+}  // namespace vbm25
+
 extern "C" {
 
 int vbm25_resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes,

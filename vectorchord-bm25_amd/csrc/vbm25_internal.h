@@ -83,6 +83,26 @@ int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vb
 // values over the built-in bounds refused) and their reset
 int cast_tuning_set(const char *name, long long value);
 void cast_tuning_reset();
+// What the evaluate operator on bound documents (evaluate.hip) reads of a resolver (resolve.hip fills it in): its index, the
+// index's device and the vocabulary's keys in HBM (16 bytes a term, ascending; complete once vbm25_resolver_create has returned)
+struct ResolverVocabulary {
+    const vbm25_index *index;
+    int device;
+    uint32_t n_terms;
+    const void *keys;
+};
+int resolver_vocabulary(const vbm25_resolver *r, ResolverVocabulary *out);
+// ... and of an index (search.hip fills it in): the per-term idf and the s1 table vbm25_evaluate_batch scores with, both in HBM
+struct EvaluateTables {
+    int device;
+    uint32_t n_docs, n_terms;
+    double k1;
+    const double *term_idf, *s1;
+};
+int index_evaluate_tables(const vbm25_index *ix, EvaluateTables *out);
+// vbm25_tuning_set's eval_grid (evaluate.hip keeps it: the most workgroups of a bind's or a score's kernels, 1 .. 2048) and its reset
+int evaluate_tuning_set(long long value);
+void evaluate_tuning_reset();
 
 }  // namespace vbm25
 
