@@ -39,6 +39,9 @@ win = p[:, 0].sum()
 print(f"windows per wave {p[:, 0].mean():.1f}; items per wave {p[:, 12].mean():.2f}; second arrivals per window {p[:, 10].sum() / win:.2f}")
 print(f"wave lifetime cycles mean {p[:, 15].mean():.0f} max {p[:, 15].max():.0f} min {p[:, 15].min():.0f}; in window loops {p[:, 9].mean():.0f}; "
       f"setup per item {p[:, 8].sum() / p[:, 12].sum():.0f}; item end (drain, cold pass, result) {p[:, 13].sum() / p[:, 12].sum():.0f}")
+mg = p[:, 14] > 0  # (the waves that merged a query: the ones that finished its last item)
+if mg.any():
+    print(f"in-kernel merge: {int(mg.sum())} waves, cycles mean {p[mg, 14].mean():.0f} max {p[mg, 14].max():.0f}")
 names = {1: "wait for the window's runs", 2: "marks phase 1 (stage, the group's atomics issued)", 3: "marks phase 2 (returned words -> second arrivals)",
          4: "wipe", 5: "wait for the last window's tf/fn words", 6: "C2 of the last window's open passes", 7: "C1 of this window (+ passes beyond two)",
          11: "threshold wait, loads issued"}

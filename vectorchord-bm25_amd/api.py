@@ -521,6 +521,14 @@ class Batch:
         f.argtypes = [C.c_void_p]
         return int(f(self.h))
 
+    def debug_win_handover(self):
+        """test aid: how the last run's scan_win_kernel handed a query's lists to the merging wave -- 2 = through the LDS (every query
+        but the last nq mod 4), 1 = through memory, 0 = it did not merge (three launches, or another route)"""
+        f = lib().vbm25_batch_debug_win_handover
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p]
+        return int(f(self.h))
+
     def debug_theta(self, nq):
         """test aid: the thresholds (as float64 scores) the last run ended with; None if the library lacks the entry"""
         f = getattr(lib(), "vbm25_batch_debug_theta", None)

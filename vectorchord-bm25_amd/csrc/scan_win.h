@@ -34,7 +34,8 @@
 // flight; (2) an asm load that takes its address from an SGPR pair starts with s_nop 4: the compiler does not pad the hazard between
 // a VALU write of an SGPR (v_readlane, an SGPR restored from its spill lane) and a VMEM read of it inside an asm statement.
 //
-// Results: one list per item at res_*[item] (bt.lpi == 1 on this route); merge_kernel merges a query's lists.  An item with a
+// Results: one list per item at res_*[item] (bt.lpi == 1 on this route); merge_kernel merges a query's lists -- or (win_fuse) the wave
+// that finishes the query's last item does, from memory or, where the query's items share a workgroup, from the LDS (WN_LQ_*).  An item with a
 // window that collects more than WN_LIST second arrivals or a term frequency above 255 in a second arrival is handed to
 // scan_many_kernel (item_failed).  A run thicker than one load per lane (WN_SLOT postings) takes a chunk loop on the spot.
 
@@ -50,8 +51,9 @@ constexpr int WN_T = 8;               // indexed terms per query
 #define VBM25_WIN_WAVES_MAX 12
 #endif
 constexpr int wn_wave_lds(int mt) { return 8192 + 512 * mt + 256; }  // a wave's filter, its staged runs, its list of second arrivals
+constexpr int WN_WG_LDS = 2048 + 16;  // the workgroup's own: the table S1 and the four queries' hand-over counters (WN_LQ_* below)
 constexpr int wn_waves(int mt, int rk) {
-    const int by_lds = (163840 - 2048) / wn_wave_lds(mt);
+    const int by_lds = (163840 - WN_WG_LDS) / wn_wave_lds(mt);
     const int by_regs = (rk == 1 && mt <= 5) || (rk == 2 && mt <= 4) ? 16 : 12;  // (<= 128 VGPRs: measured, `make resources`)
     const int n = by_lds < by_regs ? by_lds : by_regs;
     return n < VBM25_WIN_WAVES_MAX ? n : VBM25_WIN_WAVES_MAX;
@@ -225,6 +227,16 @@ struct WnPend {
     uint32_t cw;  // the filter word the claim got back (looked at a window later: nobody waits for the atomic where it is issued)
 };
 
+// The hand-over inside a workgroup (LQ: a launch that merges in the kernel and whose layout puts a query's three items into one
+// workgroup -- order_on == 2: C3's): a wave leaves its list in the upper half of its own filter, which is all zeros and idle after the
+// item's last wipe, and bumps the query's counter in the LDS; the wave that finds the others there merges from the LDS.  Words of
+// the filter: the lower half stays the merging wave's `map` (three lists of <= 256 entries: 768 words).
+constexpr uint32_t WN_LQ_SCORE = 1024;  // 256 scores
+constexpr uint32_t WN_LQ_DOC = 1536;    // 256 documents
+constexpr uint32_t WN_LQ_CNT = 1792;    // the list's length; + 1: the item was given up; + 2, + 3: the threshold the item ended with
+constexpr uint32_t WN_LQ_G = 3, WN_LQ_WAVES = 12, WN_LQ_STRIDE = 4;  // a query's part p is the item of the wave (slot & 3) + 4 p (search.hip, set_queries)
+static_assert(WN_LQ_G * 256 <= WN_LQ_SCORE && WN_LQ_CNT + 4 <= 2048, "map, lists and counts share a filter");
+
 // The query's hits from the lists of its items (merge.h's job, done here by the wave that finishes the query's LAST item: round 6 --
 // the batched route is one launch, as the one-launch route of scan_range_kernel<..., FUSED> already was; Results::into_sorted_vec,
 // search.rs:311-313).  The other waves' lists are read with loads that bypass this CU's vector cache; `map` (the wave's filter,
@@ -234,20 +246,36 @@ struct WnPend {
 // for the next launch and returns nothing: the 24-byte records and the count are written where merge_kernel would write them.  A
 // query with an item this kernel gave up gets the count NONE32: the host re-runs the batch with scan_many_kernel and merge_kernel
 // behind this kernel (vbm25_batch_fetch and the other entry points that hand records to the caller do).
-template <int RK>
+// LQ: the lists lie in the LDS (`lq`: the filter of the wave of the query's first item; the next item's WN_LQ_STRIDE filters on).  Nothing
+// of the query's per-launch state in memory was touched on the way here but its threshold word, which the last wave to leave sets
+// back (the kernel's item end): no list, count, flag or counter is read from or reset in memory.  The threshold is the largest one
+// an item ended with -- a lower bound of the final k-th score like the shared word.
+template <int RK, bool LQ>
 __device__ __forceinline__ void wn_merge_query(const DevIndex &ix, const uint32_t q, const uint32_t g, const uint32_t k, const uint32_t lane,
-                                            uint32_t *map, double *sv_score, uint32_t *sv_doc) {
+                                            uint32_t *map, double *sv_score, uint32_t *sv_doc, const uint32_t *lq) {
     const KernArgsP ca = cold_args();  // (every field of the batch is read from the kernarg segment where it is used)
     RegTopK<RK> rtop;
     rtop.init();
     const uint32_t L0 = q * g;
-    const unsigned long long theta = __hip_atomic_load(&ca->bt.theta[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    constexpr uint32_t LQS = WN_LQ_STRIDE * (uint32_t)WN_BM_WORDS;
+    unsigned long long theta = 0;
+    if constexpr (LQ) {
+        for (uint32_t i = 0; i < g; ++i) {
+            const unsigned long long ti = (unsigned long long)lq[i * LQS + WN_LQ_CNT + 3u] << 32 | lq[i * LQS + WN_LQ_CNT + 2u];
+            if (ti > theta) theta = ti;
+        }
+    } else {
+        theta = __hip_atomic_load(&ca->bt.theta[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     const uint32_t per_round = k <= 128u ? 16u : 2048u / k;  // (the map holds 2048 entries)
     uint32_t nsv = 0;
     bool ranked = true;
     for (uint32_t lb = 0; lb < g; lb += per_round) {
         uint32_t cnt = 0;
-        if (lane < per_round && lb + lane < g) cnt = min(__hip_atomic_load(&ca->bt.res_cnt[L0 + lb + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), k);
+        if (lane < per_round && lb + lane < g) {
+            if constexpr (LQ) cnt = min(lq[(lb + lane) * LQS + WN_LQ_CNT], k);
+            else cnt = min(__hip_atomic_load(&ca->bt.res_cnt[L0 + lb + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), k);
+        }
         const uint32_t incl = wave_incl_scan_u32(cnt), excl = incl - cnt;
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         for (uint32_t j = 0; j < cnt; ++j) map[excl + j] = lane << 16 | j;
@@ -258,10 +286,16 @@ __device__ __forceinline__ void wn_merge_query(const DevIndex &ix, const uint32_
             uint32_t d = 0;
             if (has) {
                 const uint32_t ds = map[e0 + lane];
-                const size_t at = (size_t)(L0 + lb + (ds >> 16)) * k + (ds & 0xffffu);
-                sc = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long *>(&ca->bt.res_score[at]), __ATOMIC_RELAXED,
-                                                                       __HIP_MEMORY_SCOPE_AGENT));
-                d = __hip_atomic_load(&ca->bt.res_doc[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (LQ) {
+                    const uint32_t *li = lq + (lb + (ds >> 16)) * LQS;
+                    sc = reinterpret_cast<const double *>(li + WN_LQ_SCORE)[ds & 0xffffu];
+                    d = li[WN_LQ_DOC + (ds & 0xffffu)];
+                } else {
+                    const size_t at = (size_t)(L0 + lb + (ds >> 16)) * k + (ds & 0xffffu);
+                    sc = __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long *>(&ca->bt.res_score[at]), __ATOMIC_RELAXED,
+                                                                           __HIP_MEMORY_SCOPE_AGENT));
+                    d = __hip_atomic_load(&ca->bt.res_doc[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
                 has = (unsigned long long)__double_as_longlong(sc) >= theta;
             }
             const unsigned long long hm = __ballot(has);
@@ -318,9 +352,13 @@ __device__ __forceinline__ void wn_merge_query(const DevIndex &ix, const uint32_
     // afterwards is kept aside
     uint32_t nf = 0;
     for (uint32_t i = lane; i < g; i += 64) {
-        nf += __hip_atomic_load(&ca->bt.item_failed[L0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1u : 0u;
-        __hip_atomic_store(&ca->bt.item_failed[L0 + i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ca->bt.res_cnt[L0 + i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (LQ) {  // (item_failed and res_cnt were never written: they are zero as the launch found them)
+            nf += lq[i * LQS + WN_LQ_CNT + 1u] != 0u ? 1u : 0u;
+        } else {
+            nf += __hip_atomic_load(&ca->bt.item_failed[L0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1u : 0u;
+            __hip_atomic_store(&ca->bt.item_failed[L0 + i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&ca->bt.res_cnt[L0 + i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o);
@@ -328,8 +366,10 @@ __device__ __forceinline__ void wn_merge_query(const DevIndex &ix, const uint32_
         ca->bt.n_hits[q] = nf ? NONE32 : n;
         ca->bt.q_failed[q] = nf;
         ca->bt.theta_last[q] = theta;
-        __hip_atomic_store(&ca->bt.theta[q], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ca->bt.fused_state[1 + q], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (!LQ) {  // (LQ: fused_state was never touched; the threshold word is set back at the item end, by the last wave to leave)
+            __hip_atomic_store(&ca->bt.theta[q], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&ca->bt.fused_state[1 + q], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 
@@ -346,6 +386,10 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
     __shared__ alignas(8192) uint32_t BM[WN_WAVES * WN_BM_WORDS];  // the waves' filters, 2^16 bits each
     __shared__ WinWave<MT> SW[WN_WAVES];
     __shared__ double S1[256];  // k1 (1 - b + b len(f) / avgdl) per fieldnorm (bm25.rs:349-352)
+    // the hand-over counters of the workgroup's four queries (WN_LQ_*): bits 0..7 the items whose list lies in the LDS, bits 8..15 the
+    // waves that have nothing in flight to the query's threshold word any more
+    __shared__ uint32_t MQ[4];
+    static_assert(sizeof(S1) + sizeof(MQ) == WN_WG_LDS, "wn_waves() knows the size");
     const uint32_t lane = threadIdx.x & 63;
     WinWave<MT> &S = SW[uni(threadIdx.x >> 6)];
     uint32_t *const bm = &BM[uni(threadIdx.x >> 6) * WN_BM_WORDS];
@@ -360,7 +404,48 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
     constexpr uint32_t dbg = 0;       // (the product has no switch that changes results: the experiments need make libvbm25_dev.so)
 #endif
     const uint16_t *ids16 = reinterpret_cast<const uint16_t *>(ix.post_id16);
+    // the work item behind a number drawn: the host's order (longest items first), or
+    // the skewed layout of a batch whose queries kept their order (C3), by arithmetic: a workgroup takes four queries, part k of
+    // them goes to the slots 4 k .. 4 k + 3 (search.hip, set_queries: the same formula fills item_order) -- one dependent
+    // round trip to memory less in every item's setup
+    auto item_of = [&](uint32_t item) -> uint32_t {
+        const KernArgsP ca = cold_args();
+        const uint32_t oo = ca->bt.order_on;
+        if (oo == 1u) item = uni(ca->bt.item_order[item]);
+        else if (oo == 2u) {
+            const uint32_t full12 = (ca->bt.nq >> 2) * 12u;
+            if (item < full12) {
+                const uint32_t wgi = item / 12u, r = item - wgi * 12u;
+                item = (wgi * 4u + (r & 3u)) * 3u + (r >> 2);
+            }
+        }
+        return item;
+    };
+    // the item setup's first loads: lane t = token t of query q, and its place in the batch's scratch plane of ids
+    // (the host sends queries of <= 64 terms this way; when they all have the same number of terms nobody waits for q_off)
+    auto query_terms = [&](const uint32_t q, uint32_t &tt, uint32_t &ti) {
+        const KernArgsP ca = cold_args();
+        const uint32_t qs = ca->bt.q_stride;
+        const uint32_t qb = qs ? qs * q : uni(ca->bt.q_off[q]), qe = qs ? qs * (q + 1u) : uni(ca->bt.q_off[q + 1]);
+        const uint32_t *idfb = ca->bt.id16_fb;
+        tt = lane < qe - qb ? ca->bt.term_ids[qb + lane] : NONE32;
+        ti = idfb && lane < qe - qb ? idfb[qb + lane] : NONE32;
+    };
+    // A wave's FIRST item is its own number (thousands of waves drawing from one counter at kernel start queued at that address for
+    // up to 33 us of a 270 us launch); further items -- only when the launch has more items than waves -- come from the counter, drawn
+    // at the END of the item before (the round trip hides behind the cold pass).  (The development switch 8 draws the first one from
+    // the counter too.)  Known without memory, the first item has its terms requested HERE: their round trip runs under the table's,
+    // in front of the barrier, where every wave of the launch waits at the same time.
+    const uint32_t n_waves = gridDim.x * (uint32_t)WN_WAVES;
+    uint32_t drawn = blockIdx.x * (uint32_t)WN_WAVES + uni(threadIdx.x >> 6);
+    bool pre = !(dbg & 8u) && drawn < n_items;
+    uint32_t pre_item = 0, pre_tt = NONE32, pre_ti = NONE32;
+    if (pre) {
+        pre_item = item_of(drawn);
+        query_terms(pre_item / g, pre_tt, pre_ti);
+    }
     for (uint32_t i = threadIdx.x; i < 256u; i += WN_WG) S1[i] = ix.s1[i];
+    if (threadIdx.x < 4u) MQ[threadIdx.x] = 0u;
 #pragma unroll
     for (int i = 0; i < WN_BM_WORDS / 4 / 64; ++i) reinterpret_cast<uint4 *>(bm)[lane + 64 * i] = make_uint4(0, 0, 0, 0);
     __syncthreads();  // (the table; the only workgroup barrier of the kernel -- from here on the waves go their own ways)
@@ -369,37 +454,17 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
     const unsigned long long prof_t0 = __builtin_readcyclecounter();
 #endif
 
-    // A wave's FIRST item is its own number (thousands of waves drawing from one counter at kernel start queued at that address for
-    // up to 33 us of a 270 us launch); further items -- only when the launch has more items than waves -- come from the counter, drawn
-    // at the END of the item before (the round trip hides behind the cold pass).  (The development switch 8 draws the first one from
-    // the counter too.)
-    const uint32_t n_waves = gridDim.x * (uint32_t)WN_WAVES;
-    uint32_t drawn = blockIdx.x * (uint32_t)WN_WAVES + uni(threadIdx.x >> 6);
     uint32_t merge_q = NONE32;  // (win_fuse: the query this wave finished the last item of)
+    bool merge_lq = false;      // ... whose lists lie in the LDS (WN_LQ_*)
     if (dbg & 8u) {
         uint32_t d0 = 0;
         if (lane == 0) d0 = atomicAdd(cold_args()->bt.work_ctr, 1u);
         drawn = uni(d0);
     }
     for (;;) {
-        uint32_t item = drawn;
-        if (item >= n_items) break;
+        if (drawn >= n_items) break;
+        const uint32_t item = pre ? pre_item : item_of(drawn);
         uint32_t w_lo, w_hi;
-        {
-            const KernArgsP ca = cold_args();
-            const uint32_t oo = ca->bt.order_on;
-            if (oo == 1u) item = uni(ca->bt.item_order[item]);  // the host's order: longest items first
-            else if (oo == 2u) {
-                // the skewed layout of a batch whose queries kept their order (C3), by arithmetic: a workgroup takes four queries, part k of
-                // them goes to the slots 4 k .. 4 k + 3 (search.hip, set_queries: the same formula fills item_order) -- one dependent
-                // round trip to memory less in every item's setup
-                const uint32_t full12 = (ca->bt.nq >> 2) * 12u;
-                if (item < full12) {
-                    const uint32_t wgi = item / 12u, r = item - wgi * 12u;
-                    item = (wgi * 4u + (r & 3u)) * 3u + (r >> 2);
-                }
-            }
-        }
         PROF_T(t_item);
         const uint32_t q = item / g, part = item - q * g;
         {
@@ -417,13 +482,9 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
         uint32_t m = 0, term = NONE32;
         uint32_t fbi = NONE32;  // the term's first block in the plane of ids: its own first block, or (an index without post_id16) its place in the batch's scratch plane
         {
-            const KernArgsP ca = cold_args();
-            // (the host sends queries of <= 64 terms this way; when they all have the same number of terms nobody waits for q_off)
-            const uint32_t qs = ca->bt.q_stride;
-            const uint32_t qb = qs ? qs * q : uni(ca->bt.q_off[q]), qe = qs ? qs * (q + 1u) : uni(ca->bt.q_off[q + 1]);
-            const uint32_t *idfb = ca->bt.id16_fb;
-            const uint32_t tt = lane < qe - qb ? ca->bt.term_ids[qb + lane] : NONE32;
-            const uint32_t ti = idfb && lane < qe - qb ? idfb[qb + lane] : NONE32;
+            uint32_t tt = pre_tt, ti = pre_ti;  // (the first item's: requested in front of the barrier)
+            if (!pre) query_terms(q, tt, ti);
+            pre = false;
             const bool ok = tt < ix.n_terms;  // search.rs:59-61
             const unsigned long long okm = __ballot(ok);
             if (ok) {
@@ -1064,7 +1125,17 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
                 }
             }
         }
-        if (rtop.cnt >= k) {  // the item's k-th score to the query's shared threshold
+        // The query's three items in this workgroup, every one its wave's own first (and only) item: the lists change hands in the
+        // LDS (WN_LQ_*).  Decided from the layout itself -- the arithmetic order above is what puts them here -- so that the waves of a
+        // query agree; every other item of the launch goes through memory as before.
+        bool lq = false;
+        if constexpr (WN_WAVES == (int)WN_LQ_WAVES) {
+            const KernArgsP ca = cold_args();
+            // (no more items than waves: a wave's only item is its own number, blockIdx.x WN_WAVES + its place in the workgroup)
+            lq = ca->bt.win_fuse != 0u && ca->bt.order_on == 2u && g == WN_LQ_G && n_items <= n_waves && !(dbg & 8u) &&
+                 blockIdx.x * (uint32_t)WN_WAVES + uni(threadIdx.x >> 6) < (ca->bt.nq >> 2) * WN_LQ_WAVES;
+        }
+        if (rtop.cnt >= k && !lq) {  // the item's k-th score to the query's shared threshold (LQ: below, unless the item is the query's last)
             const unsigned long long kb = (unsigned long long)__double_as_longlong(rtop.kth_s);
             if (kb > published && lane == 0) atomicMax(&bt.theta[q], kb);
         }
@@ -1081,34 +1152,84 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
         // ---- item result: one list
         const uint32_t nres = failed ? 0u : rtop.cnt;
         const KernArgsP ce = cold_args();
-        const size_t list = (size_t)item * ce->bt.lpi;
-        // (the list is read by another wave of this launch when the kernel merges: its stores go through to where every XCD sees them
-        // -- agent-scope stores -- and are waited for before the query's counter moves.  A release FENCE would write the whole L2 back,
-        // once per item: measured, 0.19 -> 0.28 ms on C3.)
+        if (lq) {
+            // In the LDS: the list, its length, whether the item was given up, the threshold it ended with -- then the query's counter
+            // (lgkmcnt(0) in front of it: the list is there before the counter moves).  Nothing goes to memory but fail_any, which
+            // the re-run's scan_many_kernel looks at; item_failed, res_cnt and fused_state stay zero, as the next launch expects them.
+            double *const ls = reinterpret_cast<double *>(bm + WN_LQ_SCORE);
 #pragma unroll
-        for (int r = 0; r < RK; ++r)
-            if (r * 64 + lane < nres) {
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(&ce->bt.res_score[list * k + r * 64 + lane]),
-                                   (unsigned long long)__double_as_longlong(rtop.score[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&ce->bt.res_doc[list * k + r * 64 + lane], rtop.doc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int r = 0; r < RK; ++r)
+                if (r * 64 + lane < nres) {
+                    ls[r * 64 + lane] = rtop.score[r];
+                    bm[WN_LQ_DOC + r * 64 + lane] = rtop.doc[r];
+                }
+            if (lane == 0) {
+                bm[WN_LQ_CNT] = nres;
+                bm[WN_LQ_CNT + 1u] = failed ? 1u : 0u;
+                bm[WN_LQ_CNT + 2u] = (uint32_t)th;
+                bm[WN_LQ_CNT + 3u] = (uint32_t)(th >> 32);
+                if (failed) *ce->bt.fail_any = 1u;
             }
-        if (lane == 0) {
-            __hip_atomic_store(&ce->bt.res_cnt[list], nres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ce->bt.item_failed[item], failed ? 0x101u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (failed) *ce->bt.fail_any = 1u;
-        }
-        if (ce->bt.win_fuse) {
-            // the wave that finishes the query's last item merges the query's lists and writes its records (a counter per query finds
-            // it) -- BEHIND the item loop: the host asks for the in-kernel merge only when no wave gets a second item
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            uint32_t *const mq = &MQ[uni(threadIdx.x >> 6) & 3u];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             uint32_t done = 0;
-            if (lane == 0) done = atomicAdd(&ce->bt.fused_state[1 + q], 1u);
-            if (uni(done) == g - 1u) merge_q = q;
+            if (lane == 0) done = __hip_atomic_fetch_add(mq, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            asm volatile("" ::: "memory");
+            if ((uni(done) & 0xffu) == g - 1u) {
+                // the query's last item: nobody is left to profit from its k-th score, and it has nothing in flight to the threshold
+                // word -- its second count waits behind the merge, so that the merge does not start behind a store
+                merge_q = q;
+                merge_lq = true;
+            } else {
+                // the item's k-th score to the query's shared threshold, for the items still running -- and ARRIVED there before
+                // the second count: the word is set back to zero by the last wave that has nothing in flight to it
+                if (rtop.cnt >= k && lane == 0) atomicMax(&bt.theta[q], (unsigned long long)__double_as_longlong(rtop.kth_s));
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                done = 0;
+                if (lane == 0) done = __hip_atomic_fetch_add(mq, 0x100u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (lane == 0 && (done >> 8) == g - 1u) __hip_atomic_store(&bt.theta[q], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        } else {
+            const size_t list = (size_t)item * ce->bt.lpi;
+            // (the list is read by another wave of this launch when the kernel merges: its stores go through to where every XCD sees them
+            // -- agent-scope stores -- and are waited for before the query's counter moves.  A release FENCE would write the whole L2 back,
+            // once per item: measured, 0.19 -> 0.28 ms on C3.)
+#pragma unroll
+            for (int r = 0; r < RK; ++r)
+                if (r * 64 + lane < nres) {
+                    __hip_atomic_store(reinterpret_cast<unsigned long long *>(&ce->bt.res_score[list * k + r * 64 + lane]),
+                                       (unsigned long long)__double_as_longlong(rtop.score[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&ce->bt.res_doc[list * k + r * 64 + lane], rtop.doc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            if (lane == 0) {
+                __hip_atomic_store(&ce->bt.res_cnt[list], nres, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&ce->bt.item_failed[item], failed ? 0x101u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (failed) *ce->bt.fail_any = 1u;
+            }
+            if (ce->bt.win_fuse) {
+                // the wave that finishes the query's last item merges the query's lists and writes its records (a counter per query finds
+                // it) -- BEHIND the item loop: the host asks for the in-kernel merge only when no wave gets a second item
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                uint32_t done = 0;
+                if (lane == 0) done = atomicAdd(&ce->bt.fused_state[1 + q], 1u);
+                if (uni(done) == g - 1u) merge_q = q;
+            }
         }
         drawn = ((dbg & 8u) ? 0u : n_waves) + uni(next_draw);
     }
-    if (merge_q != NONE32)
-        wn_merge_query<RK>(ix, merge_q, g, k, lane, bm, reinterpret_cast<double *>(&S.stage[0]), reinterpret_cast<uint32_t *>(&S.stage[256]));
+    if (merge_q != NONE32) {
+        PROF_T(t_m0);
+        double *const sv_score = reinterpret_cast<double *>(&S.stage[0]);
+        uint32_t *const sv_doc = reinterpret_cast<uint32_t *>(&S.stage[256]);
+        if (merge_lq) {
+            wn_merge_query<RK, true>(ix, merge_q, g, k, lane, bm, sv_score, sv_doc, &BM[(uni(threadIdx.x >> 6) & 3u) * WN_BM_WORDS]);
+            uint32_t done = 0;  // (the merging wave's second count)
+            if (lane == 0) done = __hip_atomic_fetch_add(&MQ[uni(threadIdx.x >> 6) & 3u], 0x100u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0 && (done >> 8) == g - 1u) __hip_atomic_store(&bt.theta[merge_q], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else wn_merge_query<RK, false>(ix, merge_q, g, k, lane, bm, sv_score, sv_doc, nullptr);
+        PROF_T(t_m1);
+        PROF_ADD(14, t_m0, t_m1);
+    }
 #ifdef VBM25_PROFILE
     if (bt.prof && lane == 0) {
         unsigned long long *o = bt.prof + ((size_t)blockIdx.x * WN_WAVES + (threadIdx.x >> 6)) * 16;

@@ -390,6 +390,7 @@ struct vbm25_batch {
     bool device_consumer = false; // vbm25_batch_device_results was called: every run leaves complete records on the device
     bool win_nofuse = false;      // the last run's in-kernel merge marked a query (an item was given up): this query set runs with scan_many_kernel and merge_kernel
     bool win_fused_run = false;   // the last run was a one-launch run of scan_win_kernel (a count of NONE32 means: re-run, see rerun_and_fetch)
+    uint32_t win_order_on = 0;    // ... and the item order it ran with (DevBatch::order_on; 2: a workgroup holds all three items of its four queries)
     bool state_clean = false;     // threshold / histogram / counters are zero (the routes without plan_kernel leave them so; the general one does not)
     uint32_t target_items = TARGET_ITEMS;
     uint32_t min_chunk = MIN_CHUNK_POSTINGS;
@@ -1463,6 +1464,7 @@ static int run_window(vbm25_batch *bt, hipStream_t st, DevBatch db) {
     const bool fuse = bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && !bt->growing && uint64_t(bt->nq) * plan.g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
     db.win_fuse = fuse ? 1u : 0u;
     bt->win_fused_run = fuse;
+    bt->win_order_on = db.order_on;
     if (plan.id16_decode) {
         // An index without the post_id16 plane: the ids of the batch's terms, unpacked from the blob into the batch's scratch
         // plane (decode_id16.h) -- inside the timed region: kernel_ms is the decode and the scan.
@@ -1864,6 +1866,15 @@ int vbm25_batch_debug_routes(vbm25_batch *bt, uint32_t *out6) {
 int vbm25_batch_debug_win_launches(vbm25_batch *bt) {
     if (!bt || bt->plan.route != Route::Window) return 0;
     return bt->win_fused_run ? 1 : 3;
+}
+
+// test aid (not declared in include/vbm25.h): how the last run of scan_win_kernel handed a query's lists to the merging wave -- 2: inside
+// the workgroup, through the LDS (the one-launch form in the arithmetic layout of three items per query: every query but the last
+// nq mod 4), 1: the one-launch form through memory, 0: merge_kernel merges, or another route.  The kernel decides the same from
+// win_fuse, order_on and win_g (scan_win.h, the item end).
+int vbm25_batch_debug_win_handover(vbm25_batch *bt) {
+    if (!bt || bt->plan.route != Route::Window || !bt->win_fused_run) return 0;
+    return bt->win_order_on == 2u && bt->plan.g == 3u && bt->nq >= 4u ? 2 : 1;
 }
 
 // -DVBM25_CHECK builds (not declared in include/vbm25.h): the first violated assertion of the scan kernels, then reset.
