@@ -45,8 +45,9 @@ constexpr int WN_T = 8;               // indexed terms per query
 // Independent waves per workgroup: ONE workgroup per CU holds all the LDS its waves need (three workgroups of four waves, 3 x 54 KB,
 // were never resident together: the third one ran after the others).  As many waves as the LDS holds -- a wave's share grows with
 // the run loads MT it is compiled for -- and the registers allow: up to 12 waves have 168 VGPRs each, 13 to 16 have 128.
-// (round 6: the instantiations that fit 128 VGPRs -- at most five run loads with one register row of the top-k, at most four with two --
-// COULD run four waves on two of the CU's SIMDs, 14 per workgroup; measured with -DVBM25_WIN_WAVES_MAX=13 / 14: slower)
+// (round 6: the instantiations that fit 128 VGPRs -- then at most five run loads with one register row of the top-k, at most four with
+// two; with the run addresses kept per lane (wn_lane_addr) at most three with either -- COULD run four waves on two of the CU's SIMDs,
+// 14 per workgroup; measured with -DVBM25_WIN_WAVES_MAX=13 / 14 on <5, 1> at 125 VGPRs: slower)
 #ifndef VBM25_WIN_WAVES_MAX
 #define VBM25_WIN_WAVES_MAX 12
 #endif
@@ -54,10 +55,14 @@ constexpr int wn_wave_lds(int mt) { return 8192 + 512 * mt + 256; }  // a wave's
 constexpr int WN_WG_LDS = 2048 + 16;  // the workgroup's own: the table S1 and the four queries' hand-over counters (WN_LQ_* below)
 constexpr int wn_waves(int mt, int rk) {
     const int by_lds = (163840 - WN_WG_LDS) / wn_wave_lds(mt);
-    const int by_regs = (rk == 1 && mt <= 5) || (rk == 2 && mt <= 4) ? 16 : 12;  // (<= 128 VGPRs: measured, `make resources`)
+    const int by_regs = rk <= 2 && mt <= 3 ? 16 : 12;  // (<= 128 VGPRs: measured, `make resources`; beyond the default cap of 12 only)
     const int n = by_lds < by_regs ? by_lds : by_regs;
     return n < VBM25_WIN_WAVES_MAX ? n : VBM25_WIN_WAVES_MAX;
 }
+// The instantiations that keep every term's run address in a VGPR pair of its own across the item (2 MT registers; the others
+// rebuild it per window from scalar registers): the ones that stay inside twelve waves' 168 VGPRs without a spill (`make resources`:
+// with four register rows of the top-k, seven run loads spilled one VGPR and eight run loads six)
+constexpr bool wn_lane_addr(int mt, int rk) { return !(rk == 4 && mt >= 7); }
 constexpr int WN_BM_WORDS = 2048;     // 2^16 bits
 constexpr int WN_SLOT = 256;          // staged ids per term: what one 8-byte load per lane covers
 constexpr int WN_LIST = 64;           // second arrivals per window
@@ -134,6 +139,10 @@ __device__ __forceinline__ void wn_pair(WinWave<MT> &S, const WnBm bmbase, const
 // the padding the kernel of eight run loads, which spills the pointer of the threshold word, faulted on a stale address.)
 __device__ __forceinline__ void wn_load_run(unsigned long long &dst, const uint32_t voff, const unsigned long long sbase) {
     asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase));
+}
+// (the run load from an address kept per lane: no SGPR is read, so no padding is needed in front of it)
+__device__ __forceinline__ void wn_load_run_at(unsigned long long &dst, const unsigned long long vaddr) {
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dst) : "v"(vaddr));
 }
 __device__ __forceinline__ void wn_load_word(uint32_t &dst, const uint32_t *addr) {
     asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(addr));
@@ -590,16 +599,33 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
         };
 
         // the run of every term in window w_lo + i, four postings per lane: R(w_lo + i)
+        // Where the registers allow (wn_lane_addr), every term's address of the lane's four postings of posting 0 -- the term's plane
+        // + 8 lane -- is built ONCE per item and kept in a VGPR pair (opaque, or the compiler rebuilds it from pbase inside the
+        // loop): a window's load is one readlane of the boundary, one 64-bit add and a load that reads no SGPR.  Rebuilt per window
+        // from pbase it took two more readlanes, the SALU add and, for the SGPR pair a VALU instruction had just written, s_nop 4.
         const uint32_t lane8 = 8u * lane, lane4 = 4u * lane;
+        unsigned long long vbase[wn_lane_addr(MT, RK) ? MT : 1];
+        if constexpr (wn_lane_addr(MT, RK)) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                vbase[t] = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pbase >> 32), t) << 32) |
+                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pbase, t)) + lane8;
+                asm volatile("" : "+v"(vbase[t]));
+            }
+        }
         auto load_runs = [&](unsigned long long (&dst)[MT], const uint32_t i) {
             const uint32_t ic = min(i, 63u);
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
                 // (exactly MT loads, whatever the query's number of terms: the waits count them)
-                const unsigned long long a = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pbase >> 32), t) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pbase, t)) +
-                                             2ull * ((uint32_t)__builtin_amdgcn_readlane((int)wo[t], (int)ic) & ~3u);
-                wn_load_run(dst[t], lane8, a);
+                const uint32_t o_al = (uint32_t)__builtin_amdgcn_readlane((int)wo[t], (int)ic) & ~3u;
+                if constexpr (wn_lane_addr(MT, RK)) {
+                    wn_load_run_at(dst[t], vbase[t] + 2ull * o_al);
+                } else {
+                    const unsigned long long a = (((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pbase >> 32), t) << 32) |
+                                                  (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pbase, t)) + 2ull * o_al;
+                    wn_load_run(dst[t], lane8, a);
+                }
             }
         };
         WnPend pa{}, pb{};  // the two open passes of the last window (entries 0 .. epp - 1 and epp .. 2 epp - 1)
