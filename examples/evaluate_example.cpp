@@ -1,7 +1,9 @@
 // evaluate_example.cpp -- the `<&>` operator from tsvector lexemes through the C++ host API: cast documents, the index ambuild makes of
 // them, a resolver, the bind and one batch of queries with candidate lists (then the same queries against every document).
 //   g++ -std=c++17 -Iinclude examples/evaluate_example.cpp -Lvectorchord-bm25_amd/csrc -lvbm25 -o /tmp/evaluate_example
-// Prints every score as a hexadecimal float; tests/test_cpp_evaluate_mirror.py compares them with the Python mirror's.
+// Then the rerank step: the same batch through a vbm25::Scorer, cut to the 3 best candidates a query.
+// Prints every score as a hexadecimal float; tests/test_cpp_evaluate_mirror.py and tests/test_cpp_rerank_mirror.py compare them with
+// the Python mirror's.
 #include <cstdio>
 #include <string>
 
@@ -48,6 +50,21 @@ int main() {
         for (size_t i = 0; i < listed.size(); ++i) std::printf("listed %zu %a\n", i, listed[i]);
         const std::vector<double> all = bound.evaluate(term_ids, q_off);
         for (size_t i = 0; i < all.size(); ++i) std::printf("cross %zu %a\n", i, all[i]);
+        // the rerank step: the same batch through a scorer, which keeps its buffers between calls, cut to the 3 best a query
+        vbm25::Scorer scorer = bound.scorer();
+        const std::vector<double> again = scorer.evaluate(term_ids, q_off, q_cand, cand_doc);
+        std::printf("scorer evaluate %s\n", again == listed ? "equal" : "DIFFERENT");
+        std::vector<vbm25_rank> ranks;
+        std::vector<uint32_t> n_ranks;
+        scorer.topk(term_ids, q_off, q_cand, cand_doc, 3, ranks, n_ranks);
+        for (size_t q = 0; q < n_ranks.size(); ++q)
+            for (uint32_t i = 0; i < 3; ++i)
+                std::printf("top listed %zu %u %u %u %u %a\n", q, i, n_ranks[q], ranks[q * 3 + i].pos, ranks[q * 3 + i].doc, ranks[q * 3 + i].score);
+        scorer.topk(term_ids, q_off, 3, ranks, n_ranks);
+        for (size_t q = 0; q < n_ranks.size(); ++q)
+            for (uint32_t i = 0; i < 3; ++i)
+                std::printf("top cross %zu %u %u %u %u %a\n", q, i, n_ranks[q], ranks[q * 3 + i].pos, ranks[q * 3 + i].doc, ranks[q * 3 + i].score);
+        std::printf("scorer holds %llu device bytes\n", (unsigned long long)scorer.device_bytes());
         try {
             bound.evaluate(term_ids, q_off, q_cand, {41, 0, 7, 39, 39, 2});
         } catch (const vbm25::Error &e) {

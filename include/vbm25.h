@@ -848,6 +848,35 @@ void vbm25_doc_terms_free(vbm25_doc_terms *);
 int vbm25_evaluate_documents(const vbm25_doc_terms *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq,
                              const uint64_t *q_cand, const uint32_t *cand_doc, double *scores);
 
+/* The rerank step (csrc/rerank.hip): a scorer handle over bound documents that keeps everything a scoring call needs between calls,
+ * and the `<&>` scores cut to each query's k best on the device -- `ORDER BY doc <&> query LIMIT k` over a candidate list.
+ *   vbm25_scorer_create    a handle on the vbm25_doc_terms, which must outlive it.  It owns one non-blocking stream, its events, one
+ *             pinned staging block and its device buffers; these grow geometrically when a call needs more and are freed by
+ *             vbm25_scorer_free only: a call of a shape already seen, or a smaller one, allocates and creates nothing.  A call's
+ *             inputs travel in one staged block with one upload, its results come back through the pinned block; no device-wide
+ *             synchronisation is issued.  A mutex inside serialises the calls on one scorer; several scorers on one
+ *             vbm25_doc_terms may run at once.  A call that fails leaves the scorer usable.  VBM25_ERR_INVALID for NULL arguments.
+ *   vbm25_scorer_device_bytes   what the handle holds of the device now (0 for NULL).
+ *   vbm25_scorer_evaluate  vbm25_evaluate_documents through the handle: the same arguments, checks, messages and bits.
+ *   vbm25_scorer_topk      the same inputs and checks, then k: 0 is VBM25_ERR_INVALID, more than 1024 VBM25_ERR_UNSUPPORTED (the limit
+ *             of the search's general path); NULL ranks or n_ranks (nq > 0) are refused as NULL scores are.  Every refusal comes
+ *             before anything is enqueued.  Every entry of query q's candidate list is eligible, zero scores and repeated documents
+ *             included (q_cand == NULL: every document of the handle).  n_ranks[q] = min(k, candidates of q); ranks is nq x k,
+ *             row-major, row q best first: score descending, then pos ascending.  pos is the entry's index within q's own list
+ *             (from q_cand[q]; the document index without q_cand), doc the handle's document index, score bit for bit what
+ *             vbm25_evaluate_documents gives the pair; entries at and beyond n_ranks[q] are all-zero bytes.  The rows equal a
+ *             stable descending sort of vbm25_evaluate_documents' scores cut at k.  The scores themselves never reach HBM: each
+ *             workgroup scores a part of one query's candidates and keeps the k best in LDS. */
+typedef struct vbm25_rank { double score; uint32_t pos; uint32_t doc; } vbm25_rank;   /* 16 bytes */
+typedef struct vbm25_scorer vbm25_scorer;
+int vbm25_scorer_create(const vbm25_doc_terms *, vbm25_scorer **out);
+void vbm25_scorer_free(vbm25_scorer *);
+uint64_t vbm25_scorer_device_bytes(const vbm25_scorer *);
+int vbm25_scorer_evaluate(vbm25_scorer *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
+                          const uint32_t *cand_doc, double *scores);
+int vbm25_scorer_topk(vbm25_scorer *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
+                      const uint32_t *cand_doc, uint32_t k, vbm25_rank *ranks, uint32_t *n_ranks);
+
 #ifdef __cplusplus
 }
 #endif

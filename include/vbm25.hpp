@@ -245,6 +245,7 @@ class Documents {
 // Cast documents bound to one index's vocabulary (RAII over vbm25_doc_terms): per document the ascending term ids of its known
 // elements with their tfs, and its fieldnorm code, in HBM.  evaluate() is bm25::evaluate (evaluate.rs:22-74) for a batch of queries,
 // each against its own candidate documents; the SQL operator `<&>` returns the negation of these values.  The index must outlive it.
+class Scorer;
 class DocTerms {
   public:
     DocTerms(const Documents &documents, const Resolver &resolver) { check(vbm25_documents_bind(documents.handle(), resolver.handle(), &h_)); }
@@ -294,12 +295,79 @@ class DocTerms {
         scores.pop_back();
         return scores;
     }
+    // the rerank step on this handle, with everything kept between calls (vbm25_scorer_create); this object must outlive it
+    inline Scorer scorer() const;
     const vbm25_doc_terms *handle() const { return h_; }
 
   private:
     vbm25_doc_terms *h_ = nullptr;
 };
 inline DocTerms Documents::bind(const Resolver &resolver) const { return DocTerms(*this, resolver); }
+
+// The rerank step on bound documents (RAII over vbm25_scorer): it keeps its stream, events, pinned staging and device buffers
+// between calls.  evaluate() is DocTerms::evaluate through the handle; topk() returns each query's k best candidates -- score
+// descending, then the position within the query's list ascending -- selected on the device.  One call at a time on a scorer (a
+// mutex inside serialises them); several scorers on one DocTerms may run at once.  Move-only.
+class Scorer {
+  public:
+    explicit Scorer(const DocTerms &documents) : docs_(documents.docs()) { check(vbm25_scorer_create(documents.handle(), &h_)); }
+    Scorer(Scorer &&o) noexcept : h_(o.h_), docs_(o.docs_) { o.h_ = nullptr; }
+    Scorer(const Scorer &) = delete;
+    Scorer &operator=(const Scorer &) = delete;
+    ~Scorer() { vbm25_scorer_free(h_); }
+    uint64_t device_bytes() const { return vbm25_scorer_device_bytes(h_); }
+    std::vector<double> evaluate(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, const std::vector<uint64_t> &q_cand,
+                                 const std::vector<uint32_t> &cand_doc) {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        if (q_cand.size() != q_off.size()) throw Error(VBM25_ERR_INVALID, "one candidate range per query");
+        std::vector<double> scores(cand_doc.size() + 1);
+        std::vector<uint32_t> ids(term_ids), docs(cand_doc);
+        ids.push_back(0);  // (never NULL)
+        docs.push_back(0);
+        check(vbm25_scorer_evaluate(h_, ids.data(), q_off.data(), nq, q_cand.data(), docs.data(), scores.data()));
+        scores.pop_back();
+        return scores;
+    }
+    std::vector<double> evaluate(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off) {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        std::vector<double> scores(size_t(nq) * docs_ + 1);
+        std::vector<uint32_t> ids(term_ids);
+        ids.push_back(0);
+        check(vbm25_scorer_evaluate(h_, ids.data(), q_off.data(), nq, nullptr, nullptr, scores.data()));
+        scores.pop_back();
+        return scores;
+    }
+    // ranks: nq x k, row-major, row q best first and zero behind n_ranks[q] = min(k, candidates of q)
+    void topk(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, const std::vector<uint64_t> &q_cand,
+              const std::vector<uint32_t> &cand_doc, uint32_t k, std::vector<vbm25_rank> &ranks, std::vector<uint32_t> &n_ranks) {
+        if (q_cand.size() != q_off.size()) throw Error(VBM25_ERR_INVALID, "one candidate range per query");
+        std::vector<uint32_t> docs(cand_doc);
+        docs.push_back(0);
+        topk_(term_ids, q_off, q_cand.data(), docs.data(), k, ranks, n_ranks);
+    }
+    // every document of the handle is a candidate of every query
+    void topk(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, uint32_t k, std::vector<vbm25_rank> &ranks,
+              std::vector<uint32_t> &n_ranks) {
+        topk_(term_ids, q_off, nullptr, nullptr, k, ranks, n_ranks);
+    }
+    vbm25_scorer *handle() const { return h_; }
+
+  private:
+    void topk_(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, const uint64_t *q_cand, const uint32_t *cand_doc, uint32_t k,
+               std::vector<vbm25_rank> &ranks, std::vector<uint32_t> &n_ranks) {
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        std::vector<uint32_t> ids(term_ids);
+        ids.push_back(0);
+        ranks.assign(size_t(nq) * k + 1, vbm25_rank{0.0, 0, 0});
+        n_ranks.assign(size_t(nq) + 1, 0);
+        check(vbm25_scorer_topk(h_, ids.data(), q_off.data(), nq, q_cand, cand_doc, k, ranks.data(), n_ranks.data()));
+        ranks.pop_back();
+        n_ranks.pop_back();
+    }
+    vbm25_scorer *h_ = nullptr;
+    uint32_t docs_ = 0;
+};
+inline Scorer DocTerms::scorer() const { return Scorer(*this); }
 
 class DeviceGrowing;
 class DeviceVacuum;

@@ -174,6 +174,11 @@ ABI = {
     "vbm25_doc_terms_device_bytes": (u64, [vp]),
     "vbm25_doc_terms_free": (None, [vp]),
     "vbm25_evaluate_documents": (i32, [vp, vp, vp, u32, vp, vp, vp]),
+    "vbm25_scorer_create": (i32, [vp, vp]),
+    "vbm25_scorer_free": (None, [vp]),
+    "vbm25_scorer_device_bytes": (u64, [vp]),
+    "vbm25_scorer_evaluate": (i32, [vp, vp, vp, u32, vp, vp, vp]),
+    "vbm25_scorer_topk": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
 }
 
 

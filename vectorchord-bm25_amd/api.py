@@ -14,6 +14,9 @@ HIT_DTYPE = np.dtype({"names": ["score", "doc_id", "payload"],
                       "formats": ["<f8", "<u4", ("<u2", (3,))],
                       "offsets": [0, 8, 12], "itemsize": 24})
 
+# vbm25_rank: one entry of Scorer.topk's rows
+RANK_DTYPE = np.dtype({"names": ["score", "pos", "doc"], "formats": ["<f8", "<u4", "<u4"], "offsets": [0, 8, 12], "itemsize": 16})
+
 WIDTH = 16  # crates/bm25/src/lib.rs:37
 
 _DESC_ARRAYS = [
@@ -1120,7 +1123,9 @@ def set_tuning(name, value):
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
     and cast_group_max (the class bounds of Documents.cast, read at the start of each cast; 0 turns the class off), eval_grid (the
-    most workgroups of the kernels of Documents.bind and DocTerms.evaluate, 1 .. 2048, read at the start of each call).  No switch of
+    most workgroups of the kernels of Documents.bind, DocTerms.evaluate and a Scorer, 1 .. 2048, read at the start of each call),
+    rerank_part (the candidates one workgroup of Scorer.topk selects from, 64 .. 2^20 in 64s) and rerank_buf (its selection buffer
+    as a multiple of k, 2 .. 8; both read at the start of each Scorer call).  No switch of
     the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
     libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set
@@ -1316,10 +1321,81 @@ class DocTerms:
                                              out.ctypes.data))
         return scores
 
+    def scorer(self):
+        """vbm25_scorer_create: a Scorer on this handle -- the rerank step with everything kept between calls"""
+        return Scorer(self)
+
     def __del__(self):
         try:
             if self.h:
                 lib().vbm25_doc_terms_free(self.h)
+        except Exception:
+            pass
+
+
+class Scorer:
+    """vbm25_scorer: the rerank step on a DocTerms.  It keeps its stream, events, pinned staging and device buffers between calls
+    (they grow when a call needs more and are freed by close() only).  evaluate() is DocTerms.evaluate through the handle; topk()
+    returns each query's k best candidates, selected on the device.  One call at a time on a scorer (a mutex inside serialises
+    them); several scorers on one DocTerms may run at once.  Also a context manager."""
+
+    def __init__(self, doc_terms):
+        self.doc_terms = doc_terms  # (kept alive: the handle refers to it)
+        self.h = C.c_void_p()
+        check(lib().vbm25_scorer_create(doc_terms.h, C.byref(self.h)))
+
+    def device_bytes(self):
+        return int(lib().vbm25_scorer_device_bytes(self.h))
+
+    def _inputs(self, term_ids, q_off, q_cand, cand_doc):
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+        nq = len(q_off) - 1
+        term_ids = _at_least_one(term_ids, np.uint32)
+        if q_cand is None:
+            if cand_doc is not None:
+                raise ValueError("cand_doc without q_cand")
+            return term_ids, q_off, nq, None, None
+        q_cand = np.ascontiguousarray(q_cand, dtype=np.uint64)
+        if len(q_cand) != nq + 1:
+            raise ValueError(f"{len(q_cand)} candidate offsets for {nq} queries")
+        return term_ids, q_off, nq, q_cand, None if cand_doc is None else _at_least_one(cand_doc, np.uint32)
+
+    def evaluate(self, term_ids, q_off, q_cand=None, cand_doc=None):
+        """vbm25_scorer_evaluate: DocTerms.evaluate's arguments, result, refusals and bits"""
+        term_ids, q_off, nq, qc, dc = self._inputs(term_ids, q_off, q_cand, cand_doc)
+        scores = np.zeros((nq, self.doc_terms.n_docs) if qc is None else int(qc[nq]), dtype=np.float64)
+        out = scores if scores.size else np.zeros(1, dtype=np.float64)
+        check(lib().vbm25_scorer_evaluate(self.h, term_ids.ctypes.data, q_off.ctypes.data, nq, None if qc is None else qc.ctypes.data,
+                                          None if dc is None else dc.ctypes.data, out.ctypes.data))
+        return scores
+
+    def topk(self, term_ids, q_off, k, q_cand=None, cand_doc=None):
+        """vbm25_scorer_topk -> (ranks [nq, k] of RANK_DTYPE, n_ranks uint32 [nq]).  Row q: the n_ranks[q] = min(k, candidates of q)
+        best entries of q's list, score descending then pos (the index within q's list) ascending, zeros behind them -- a stable
+        descending sort of evaluate()'s scores cut at k.  Zero scores and repeated documents are entries like any other."""
+        term_ids, q_off, nq, qc, dc = self._inputs(term_ids, q_off, q_cand, cand_doc)
+        ranks = np.zeros((nq, max(int(k), 0)), dtype=RANK_DTYPE)
+        n_ranks = np.zeros(nq, dtype=np.uint32)
+        r = ranks if ranks.size else np.zeros(1, dtype=RANK_DTYPE)
+        n = n_ranks if nq else np.zeros(1, dtype=np.uint32)
+        check(lib().vbm25_scorer_topk(self.h, term_ids.ctypes.data, q_off.ctypes.data, nq, None if qc is None else qc.ctypes.data,
+                                      None if dc is None else dc.ctypes.data, int(k), r.ctypes.data, n.ctypes.data))
+        return ranks, n_ranks
+
+    def close(self):
+        if self.h:
+            lib().vbm25_scorer_free(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

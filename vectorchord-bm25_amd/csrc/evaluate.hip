@@ -18,6 +18,8 @@
 //                          length; then score_step per term in query order.  A lane without a candidate has an empty run and reads
 //                          nothing (evaluate_lane.h: a position is read only inside a non-empty range).
 //   No kernel here has scratch memory or LDS.
+//   The argument checks of a scoring call, the kernel's arguments and its launch are declared in evaluate_shared.h: the scorer handle
+//   of rerank.hip makes the same checks and launches the same kernel.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -31,16 +33,7 @@
 #include "device_segment.h"
 #include "resolve_lane.h"
 #include "evaluate_lane.h"
-
-// Cast documents bound to one index's vocabulary: per document the ascending ids of its known elements with their tfs, and the
-// fieldnorm code the cast gave it.  Only ever read after it is made.
-struct vbm25_doc_terms {
-    const vbm25_index *index = nullptr;
-    int device = 0;
-    uint32_t n_docs = 0;
-    uint64_t n_known = 0;
-    vbm25::HbmArray d_start, d_term, d_tf, d_fieldnorm;
-};
+#include "evaluate_shared.h"
 
 namespace {
 
@@ -95,29 +88,6 @@ __global__ void __launch_bounds__(WG) bind_compact_kernel(const uint32_t *ids, c
     }
 }
 
-struct ScoreArgs {
-    const ull *start;            // n_docs + 1
-    const uint32_t *term, *tf;   // the known elements
-    const uint8_t *fieldnorm;    // n_docs
-    const double *term_idf, *s1; // the index's tables
-    double k1p1;
-    uint32_t n_terms;
-    const uint32_t *q_ids, *q_off;
-    const ull *q_cand;           // nq + 1; NULL: every query scores documents 0 .. cross_docs
-    const uint32_t *cand_doc;
-    uint32_t cross_docs;
-    const uint32_t *item_start;  // nq + 1: query q owns items item_start[q] .. item_start[q + 1], 64 candidates each
-    uint32_t nq, n_items;
-    double *scores;
-};
-
-// a double of lane `j` (the same j in every lane) to every lane, through the scalar unit
-__device__ __forceinline__ double lane_double(double v, uint32_t j) {
-    const ull b = ull(__double_as_longlong(v));
-    const uint32_t lo = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(b)), int(j))), hi = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(b >> 32)), int(j)));
-    return __longlong_as_double((long long)(ull(hi) << 32 | lo));
-}
-
 __global__ void __launch_bounds__(WG) eval_score_kernel(ScoreArgs a) {
     const uint32_t lane = threadIdx.x & 63u, n_waves = (gridDim.x * WG) >> 6;
     const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(int((blockIdx.x * WG + threadIdx.x) >> 6)));
@@ -155,13 +125,6 @@ __global__ void __launch_bounds__(WG) eval_score_kernel(ScoreArgs a) {
         }
         if (mine) a.scores[cand0 + c] = result;
     }
-}
-
-int use_eval_device(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
-        return set_error(VBM25_ERR_DEVICE, "no HIP device: the evaluate operator on bound documents has no host fallback (vbm25_evaluate is the host function)");
-    return use_device(device);
 }
 
 int documents_bind(const vbm25_documents *h, const vbm25_resolver *r, vbm25_doc_terms **out) {
@@ -241,10 +204,80 @@ int doc_terms_download(const vbm25_doc_terms *t, uint64_t *start, uint32_t *term
 
 int evaluate_documents(const vbm25_doc_terms *t, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
                        const uint32_t *cand_doc, double *scores) {
+    EvaluateTables ix;
+    uint64_t n_pairs = 0;
+    if (int rc = check_score_call(t, term_ids, q_off, nq, q_cand, cand_doc, scores, &ix, &n_pairs)) return rc;
+    if (n_pairs == 0) return VBM25_OK;
+    // the items: a scan of the candidate counts, 64 candidates an item
+    std::vector<uint32_t> item_start(size_t(nq) + 1, 0);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t n = q_cand ? q_cand[q + 1] - q_cand[q] : t->n_docs;
+        item_start[q + 1] = item_start[q] + uint32_t((n + 63) / 64);
+    }
+    const uint32_t n_items = item_start[nq], n_ids = q_off[nq];
+    if (int rc = use_eval_device(t->device)) return rc;
+    g_score_ms = -1.0;
+    HbmArray d_ids, d_off, d_cand, d_doc, d_items, d_scores;
+    Event ev_start, ev_done;
+    Stream st;  // (of the call's own, as the bind's)
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    Quiesce quiesce(st.s);
+    HIP_TRY(hipEventCreate(&ev_start.e));
+    HIP_TRY(hipEventCreate(&ev_done.e));
+    HIP_TRY(d_ids.alloc(4ull * n_ids));
+    HIP_TRY(d_off.alloc(4ull * (nq + 1ull)));
+    HIP_TRY(d_items.alloc(4ull * (nq + 1ull)));
+    HIP_TRY(d_scores.alloc(8ull * n_pairs));
+    if (n_ids) HIP_TRY(hipMemcpyAsync(d_ids.p, term_ids, 4ull * n_ids, hipMemcpyHostToDevice, st.s));
+    HIP_TRY(hipMemcpyAsync(d_off.p, q_off, 4ull * (nq + 1ull), hipMemcpyHostToDevice, st.s));
+    HIP_TRY(hipMemcpyAsync(d_items.p, item_start.data(), 4ull * (nq + 1ull), hipMemcpyHostToDevice, st.s));
+    if (q_cand) {
+        HIP_TRY(d_cand.alloc(8ull * (nq + 1ull)));
+        HIP_TRY(d_doc.alloc(4ull * n_pairs));
+        HIP_TRY(hipMemcpyAsync(d_cand.p, q_cand, 8ull * (nq + 1ull), hipMemcpyHostToDevice, st.s));
+        HIP_TRY(hipMemcpyAsync(d_doc.p, cand_doc, 4ull * n_pairs, hipMemcpyHostToDevice, st.s));
+    }
+    ScoreArgs a{};
+    fill_score_tables(t, ix, &a);
+    a.q_ids = d_ids.as<uint32_t>();
+    a.q_off = d_off.as<uint32_t>();
+    a.q_cand = q_cand ? d_cand.as<ull>() : nullptr;
+    a.cand_doc = q_cand ? d_doc.as<uint32_t>() : nullptr;
+    a.cross_docs = q_cand ? 0u : t->n_docs;
+    a.item_start = d_items.as<uint32_t>();
+    a.nq = nq;
+    a.n_items = n_items;
+    a.scores = d_scores.as<double>();
+    HIP_TRY(hipEventRecord(ev_start.e, st.s));
+    HIP_TRY(launch_eval_score(a, st.s));
+    HIP_TRY(hipEventRecord(ev_done.e, st.s));
+    HIP_TRY(hipMemcpyAsync(scores, d_scores.p, 8ull * n_pairs, hipMemcpyDeviceToHost, st.s));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev_start.e, ev_done.e));
+    g_score_ms = ms;
+    return VBM25_OK;
+}
+
+}  // namespace
+
+namespace vbm25 {
+namespace evl {
+
+int use_eval_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return set_error(VBM25_ERR_DEVICE, "no HIP device: the evaluate operator on bound documents has no host fallback (vbm25_evaluate is the host function)");
+    return use_device(device);
+}
+
+int check_score_call(const vbm25_doc_terms *t, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
+                     const uint32_t *cand_doc, const void *out, EvaluateTables *ixp, uint64_t *n_pairs_out) {
+    *n_pairs_out = 0;
     if (!t) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (nq == 0) return VBM25_OK;
-    if (!term_ids || !q_off || !scores) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    EvaluateTables ix;
+    if (!term_ids || !q_off || !out) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    EvaluateTables &ix = *ixp;
     if (int rc = index_evaluate_tables(t->index, &ix)) return rc;
     if (q_off[0] != 0) return set_error(VBM25_ERR_INVALID, "q_off[0] is %u, not 0", q_off[0]);
     for (uint32_t q = 0; q < nq; ++q)
@@ -273,68 +306,30 @@ int evaluate_documents(const vbm25_doc_terms *t, const uint32_t *term_ids, const
                 if (cand_doc[i] >= t->n_docs)
                     return set_error(VBM25_ERR_INVALID, "query %u: candidate %u is outside the handle's %u documents", q, cand_doc[i], t->n_docs);
     if (ix.n_docs == 0) return set_error(VBM25_ERR_INVALID, "evaluate on an index without sealed documents");
-    if (n_pairs == 0) return VBM25_OK;
-    // the items: a scan of the candidate counts, 64 candidates an item
-    std::vector<uint32_t> item_start(size_t(nq) + 1, 0);
-    for (uint32_t q = 0; q < nq; ++q) {
-        const uint64_t n = q_cand ? q_cand[q + 1] - q_cand[q] : t->n_docs;
-        item_start[q + 1] = item_start[q] + uint32_t((n + 63) / 64);
-    }
-    const uint32_t n_items = item_start[nq], n_ids = q_off[nq];
-    if (int rc = use_eval_device(t->device)) return rc;
-    g_score_ms = -1.0;
-    const uint32_t cap = g_eval_grid.load();
-    HbmArray d_ids, d_off, d_cand, d_doc, d_items, d_scores;
-    Event ev_start, ev_done;
-    Stream st;  // (of the call's own, as the bind's)
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    Quiesce quiesce(st.s);
-    HIP_TRY(hipEventCreate(&ev_start.e));
-    HIP_TRY(hipEventCreate(&ev_done.e));
-    HIP_TRY(d_ids.alloc(4ull * n_ids));
-    HIP_TRY(d_off.alloc(4ull * (nq + 1ull)));
-    HIP_TRY(d_items.alloc(4ull * (nq + 1ull)));
-    HIP_TRY(d_scores.alloc(8ull * n_pairs));
-    if (n_ids) HIP_TRY(hipMemcpyAsync(d_ids.p, term_ids, 4ull * n_ids, hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_off.p, q_off, 4ull * (nq + 1ull), hipMemcpyHostToDevice, st.s));
-    HIP_TRY(hipMemcpyAsync(d_items.p, item_start.data(), 4ull * (nq + 1ull), hipMemcpyHostToDevice, st.s));
-    if (q_cand) {
-        HIP_TRY(d_cand.alloc(8ull * (nq + 1ull)));
-        HIP_TRY(d_doc.alloc(4ull * n_pairs));
-        HIP_TRY(hipMemcpyAsync(d_cand.p, q_cand, 8ull * (nq + 1ull), hipMemcpyHostToDevice, st.s));
-        HIP_TRY(hipMemcpyAsync(d_doc.p, cand_doc, 4ull * n_pairs, hipMemcpyHostToDevice, st.s));
-    }
-    ScoreArgs a{};
-    a.start = t->d_start.as<ull>();
-    a.term = t->d_term.as<uint32_t>();
-    a.tf = t->d_tf.as<uint32_t>();
-    a.fieldnorm = t->d_fieldnorm.as<uint8_t>();
-    a.term_idf = ix.term_idf;
-    a.s1 = ix.s1;
-    a.k1p1 = ix.k1 + 1.0;
-    a.n_terms = ix.n_terms;
-    a.q_ids = d_ids.as<uint32_t>();
-    a.q_off = d_off.as<uint32_t>();
-    a.q_cand = q_cand ? d_cand.as<ull>() : nullptr;
-    a.cand_doc = q_cand ? d_doc.as<uint32_t>() : nullptr;
-    a.cross_docs = q_cand ? 0u : t->n_docs;
-    a.item_start = d_items.as<uint32_t>();
-    a.nq = nq;
-    a.n_items = n_items;
-    a.scores = d_scores.as<double>();
-    HIP_TRY(hipEventRecord(ev_start.e, st.s));
-    eval_score_kernel<<<capped_grid(n_items, WG / 64, cap), WG, 0, st.s>>>(a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev_done.e, st.s));
-    HIP_TRY(hipMemcpyAsync(scores, d_scores.p, 8ull * n_pairs, hipMemcpyDeviceToHost, st.s));
-    HIP_TRY(hipStreamSynchronize(st.s));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev_start.e, ev_done.e));
-    g_score_ms = ms;
+    *n_pairs_out = n_pairs;
     return VBM25_OK;
 }
 
-}  // namespace
+void fill_score_tables(const vbm25_doc_terms *t, const EvaluateTables &ix, ScoreArgs *a) {
+    a->start = t->d_start.as<ull>();
+    a->term = t->d_term.as<uint32_t>();
+    a->tf = t->d_tf.as<uint32_t>();
+    a->fieldnorm = t->d_fieldnorm.as<uint8_t>();
+    a->term_idf = ix.term_idf;
+    a->s1 = ix.s1;
+    a->k1p1 = ix.k1 + 1.0;
+    a->n_terms = ix.n_terms;
+}
+
+hipError_t launch_eval_score(const ScoreArgs &a, hipStream_t stream) {
+    eval_score_kernel<<<capped_grid(a.n_items, WG / 64, g_eval_grid.load()), WG, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+uint32_t eval_grid_cap() { return g_eval_grid.load(); }
+
+}  // namespace evl
+}  // namespace vbm25
 
 namespace vbm25 {
 int evaluate_tuning_set(long long value) {

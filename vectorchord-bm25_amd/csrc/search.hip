@@ -1749,7 +1749,8 @@ int vbm25_evaluate_batch(vbm25_index *ix, const uint32_t *q_terms, uint32_t n_q,
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg; cast_wave_max and cast_group_max (read
-// at the start of each vbm25_documents_cast); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents).
+// at the start of each vbm25_documents_cast); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
+// and each scorer call); rerank_part and rerank_buf (read at the start of each scorer call).
 int vbm25_tuning_set(const char *name, long long value) {
     if (!name) return set_error(VBM25_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> guard(g_tune_mutex);
@@ -1789,6 +1790,9 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "eval_grid") {  // (the grid cap of vbm25_documents_bind / vbm25_evaluate_documents: evaluate.hip keeps and reads it)
         if (int rc = vbm25::evaluate_tuning_set(value)) return rc;
     }
+    else if (n == "rerank_part" || n == "rerank_buf") {  // (the parts and the buffer of vbm25_scorer_topk: rerank.hip keeps and reads them)
+        if (int rc = vbm25::rerank_tuning_set(name, value)) return rc;
+    }
     else return set_error(VBM25_ERR_INVALID, "unknown tuning switch %s", name);
     ++g_tune.generation;
     return VBM25_OK;
@@ -1800,6 +1804,7 @@ void vbm25_tuning_reset(void) {
     g_tune.generation = gen;
     vbm25::cast_tuning_reset();
     vbm25::evaluate_tuning_reset();
+    vbm25::rerank_tuning_reset();
 }
 
 // the current queries' kernels make their work items themselves and merge_kernel cleans up behind them

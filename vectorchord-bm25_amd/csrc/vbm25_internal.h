@@ -103,6 +103,10 @@ int index_evaluate_tables(const vbm25_index *ix, EvaluateTables *out);
 // vbm25_tuning_set's eval_grid (evaluate.hip keeps it: the most workgroups of a bind's or a score's kernels, 1 .. 2048) and its reset
 int evaluate_tuning_set(long long value);
 void evaluate_tuning_reset();
+// vbm25_tuning_set's rerank_part (candidates a part of a scorer's top-k, 64 .. 2^20 in 64s) and rerank_buf (the selection buffer as a
+// multiple of k, 2 .. 8); rerank.hip keeps them and reads them at the start of each scorer call
+int rerank_tuning_set(const char *name, long long value);
+void rerank_tuning_reset();
 
 }  // namespace vbm25
 
