@@ -78,7 +78,7 @@ static void test_bisection() {
     checked += 2;
 }
 
-// evaluate_kernel's walk (search.hip), restated: a merge of the document's ids with the query's
+// evaluate_kernel's walk (index.hip), restated: a merge of the document's ids with the query's
 static double merge_walk(const std::vector<uint32_t> &term, const std::vector<uint32_t> &tf, uint32_t lo, uint32_t hi, const std::vector<uint32_t> &q,
                          const std::vector<double> &idf, double k1p1, double s1) {
     const uint32_t n_terms = uint32_t(idf.size());

@@ -11,7 +11,7 @@
 #include "../../oracle/oracle.h"
 
 namespace vbm25 {
-int set_error(int code, const char *, ...) { return code; }  // the library defines it in search.hip
+int set_error(int code, const char *, ...) { return code; }  // the library defines it in error.cpp
 }
 
 struct Rel {

@@ -20,7 +20,7 @@
 #include "../../vectorchord-bm25_amd/csrc/pages_emit.h"
 
 namespace vbm25 {
-int set_error(int code, const char *, ...) { return code; }  // the library defines it in search.hip
+int set_error(int code, const char *, ...) { return code; }  // the library defines it in error.cpp
 }
 
 using namespace vbm25::pge;

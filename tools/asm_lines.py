@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Where a kernel's instructions, SGPR spills (v_writelane/v_readlane) and scratch traffic come from, by source line.
-usage: tools/asm_lines.py <kernel name substring> [extra hipcc flags]   (compiles csrc/search.hip with -gline-tables-only -S)"""
+usage: tools/asm_lines.py <kernel name substring> [unit.hip] [extra hipcc flags]   (compiles the unit of csrc/ -- search.hip, which
+holds the scan kernels, unless one is named -- with -gline-tables-only -S)"""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vectorchord-bm25_amd", "csrc")
 kern = sys.argv[1]
+unit = next((a for a in sys.argv[2:] if a.endswith(".hip")), "search.hip")
 out = os.path.join(ROOT, "build", "scratch", "search_g.s")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-gline-tables-only",
-                "-S", "--cuda-device-only", "-o", out, "search.hip"] + sys.argv[2:], cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
+                "-S", "--cuda-device-only", "-o", out, unit] + [a for a in sys.argv[2:] if not a.endswith(".hip")], cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
 txt = open(out).read()
 files = {}
 for m in re.finditer(r'\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', txt):

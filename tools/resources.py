@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Compact table of `hipcc -Rpass-analysis=kernel-resource-usage` for search.hip (or the file given):
-kernel, SGPRs, VGPRs, spilled SGPRs / VGPRs, scratch bytes per lane, occupancy, LDS bytes.
-Usage: tools/resources.py [extra hipcc flags ...]   (run from anywhere; compiles csrc/search.hip)"""
+"""Compact table of `hipcc -Rpass-analysis=kernel-resource-usage` for one unit of csrc/: search.hip, which holds the scan kernels, or
+the .hip file given (scan_win.hip, index.hip, growing.hip, ...): kernel, SGPRs, VGPRs, spilled SGPRs / VGPRs, scratch bytes per lane,
+occupancy, LDS bytes.
+Usage: tools/resources.py [unit.hip] [extra hipcc flags ...]   (run from anywhere)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vectorchord-bm25_amd", "csrc")

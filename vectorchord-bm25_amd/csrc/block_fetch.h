@@ -1,5 +1,12 @@
 // block_fetch.h -- split decode: raw words fetched early, fields extracted later; DPP wave helpers.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25.
+// Included by search.hip and scan_win.hip.
+#ifndef VBM25_BLOCK_FETCH_H
+#define VBM25_BLOCK_FETCH_H
+
+#include "device_types.h"
+#include "decode.h"
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Split decode used by scan_kernel: the two dwords that hold a field are fetched early
@@ -148,3 +155,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {  // uniform resul
     x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x143, 0xc, 0xf, false));
     return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
+
+}  // namespace vbm25
+
+#endif

@@ -1,6 +1,12 @@
 // decode.h -- block decode (compression.rs:65-136 formats): one wave, two postings per lane.
-// Included inside namespace vbm25 by search.hip, in this order: device_types, decode, plan, topk_lds, block_fetch, topk_reg,
-// scan_range, scan_dense, scan_many, merge; and by maintain.hip (the compaction's count and scatter passes).
+// Included by search.hip, scan_win.hip, index.hip (index_derive.h) and maintain.hip (the compaction's count and scatter passes).
+#ifndef VBM25_DECODE_H
+#define VBM25_DECODE_H
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Block decode: one wave, two postings per lane (value indices 2*lane, 2*lane+1)
@@ -78,3 +84,7 @@ __device__ __forceinline__ void decode_doc_ids(const uint8_t *__restrict__ p, ui
     d0 = min_doc + (x - own) + v0;
     d1 = d0 + v1;
 }
+
+}  // namespace vbm25
+
+#endif

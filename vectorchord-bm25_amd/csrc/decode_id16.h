@@ -2,7 +2,7 @@
 // bit-packed blocks (compression.rs:65-92; the d1 delta streams of bitpacking_u32_ordered.rs:191-237) into the batch's scratch plane
 // ahead of scan_win_kernel.  The route of an index made WITHOUT the post_id16 plane (tuning id16_plane = 0: 2 bytes per posting less in
 // HBM): what index creation would have derived once for every posting is made per launch for the postings the batch's queries name.
-// Part of libvbm25's device code: included by search.hip inside namespace vbm25 after device_types.h, decode.h and topk_reg.h.
+// Included by search.hip only (a non-template kernel: one definition).
 //
 // One workgroup of four waves per term position of the batch (grid = q_off[nq]).  A wave takes the term's blocks TWO at a time: lanes
 // 0 .. 31 one block, lanes 32 .. 63 the next, FOUR postings per lane -- the four streams of the 4-lane vertical layout at one bit
@@ -13,6 +13,15 @@
 // Every lane loads its block's 16 bytes of metadata itself (32 lanes, one address: one request), two pairs ahead; the fields' rows
 // one pair ahead.  (Round 6's first version -- one block per 64 lanes, two postings per lane, the metadata through v_readlane: 45
 // instructions per block, 0.195 ms on C3; this one: tools/dec_variants_run.sh.)  Byte-packed tails and raw blocks take decode_doc_ids.
+#ifndef VBM25_DECODE_ID16_H
+#define VBM25_DECODE_ID16_H
+
+#include "device_types.h"
+#include "decode.h"
+#include "topk_reg.h"
+
+namespace vbm25 {
+
 constexpr int DI_WAVES = 4;
 __global__ void __launch_bounds__(DI_WAVES * 64) decode_id16_kernel(DevIndex ix, const uint32_t *term_ids, const uint32_t *id16_fb, uint32_t *dst) {
     const uint32_t lane = threadIdx.x & 63, wave = uni(threadIdx.x >> 6);
@@ -82,3 +91,7 @@ __global__ void __launch_bounds__(DI_WAVES * 64) decode_id16_kernel(DevIndex ix,
         }
     }
 }
+
+}  // namespace vbm25
+
+#endif

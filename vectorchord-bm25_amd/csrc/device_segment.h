@@ -1,5 +1,5 @@
 // device_segment.h -- a sealed segment whose arrays live in HBM (vbm25_device_segment): what csrc/flush.hip builds and
-// csrc/search.hip (vbm25_index_create_from_device) makes an index of without a round trip through the host.
+// csrc/index.hip (vbm25_index_create_from_device) makes an index of without a round trip through the host.
 // Shared by the two HIP translation units of libvbm25; not part of the ABI.
 #ifndef VBM25_DEVICE_SEGMENT_H
 #define VBM25_DEVICE_SEGMENT_H
@@ -61,7 +61,7 @@ int build_device_core(int device, double k1, double b, uint32_t n_docs, const ui
                       const uint64_t *term_start, const uint32_t *post_doc, const uint32_t *post_tf, const uint32_t *dev_doc,
                       const uint32_t *dev_tf, std::unique_ptr<vbm25_device_segment> &out);
 
-// What vbm25_index_maintain reads of an index (search.hip fills it in, csrc/maintain.hip compacts): the block metadata, the blob,
+// What vbm25_index_maintain reads of an index (index.hip fills it in, csrc/maintain.hip compacts): the block metadata, the blob,
 // term_first_block and the payloads in HBM, the keys on the host
 struct MaintainSource {
     int device;

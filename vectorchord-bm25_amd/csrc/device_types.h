@@ -1,7 +1,15 @@
 // device_types.h -- device-side views of the index and of one batch; constants of the kernels.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, in
-// this order: device_types, decode, plan, topk_lds, block_fetch, topk_reg, scan_range, scan_dense, scan_many, merge (scan_win.hip:
-// device_types, decode, topk_lds, block_fetch, topk_reg, scan_win).
+// Included by host_objects.h (every unit that sees a host object) and by every kernel header.
+#ifndef VBM25_DEVICE_TYPES_H
+#define VBM25_DEVICE_TYPES_H
+
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/vbm25.h"
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Device-side view of the index and of one batch
@@ -166,3 +174,49 @@ constexpr int CUR_HB = 256;            // score buckets of the per-query histogr
 constexpr int REG_K = 256;                // largest k whose running top-k lives in registers
 constexpr uint32_t NONE32 = 0xffffffffu;
 constexpr int KTH_LEVELS = 9;            // term_kth_ub: the 2^i-th largest block maximum of a term, i = 0..8
+
+// what of the scan kernels' launch shapes the host's tuning switches default to (host_objects.h: Tuning, QueryPlan)
+constexpr uint32_t R_TARGET_ITEMS = 1024;
+constexpr uint32_t R_MIN_CHUNK_POSTINGS = 16384;
+constexpr uint32_t R_GRID = 512;      // persistent workgroups: 256 CUs x 2 (KMAX <= 64; 1 per CU above)
+constexpr uint32_t D_GRID = 512;         // persistent workgroups: 256 CUs x 2
+constexpr uint32_t D_TARGET_ITEMS = 12288;   // items of a batch of dense queries: the launch ends with its slowest workgroup, and an item's setup is 24 k cycles of
+                                           // the 20 M an item of C5 takes at 4096 -- C5: 4096 items 72.9 ms, 8192 69.9, 12288 69.7, 24576 70.9 (search.hip caps a
+                                           // query's share where the corpus is small)
+
+// ---------------------------------------------------------------------------
+// Device-side view of the growing segment and of one batch's run over it (growing.h has the layout and the kernels)
+// ---------------------------------------------------------------------------
+constexpr uint32_t GT = 8192;        // documents per tile: 64 KB of f64 accumulators in LDS
+constexpr uint32_t GWG = 256;        // threads of growing_scan_kernel
+constexpr uint32_t G_MAX_WG = 512;   // workgroups of growing_scan_kernel a batch aims at (two per CU: LDS)
+
+struct DevGrowing {
+    const uint32_t *term_start;  // n_terms + 1: postings of term t are [term_start[t], term_start[t + 1])
+    const uint32_t *post_g;      // per posting: growing document index, ascending inside a term
+    const double *post_c;        // per posting: Cache::evaluate(fieldnorm[g], tf) of the term
+    const uint32_t *tab_idx;     // per term: first entry of its tile table, NONE32 = none (a short list: binary search)
+    const uint32_t *tab;         // a tabled term's n_tiles + 1 entries: entry j = its first posting with g >= j GT
+    const uint16_t *payload;     // n_grow x 3
+    uint32_t n_grow, n_tiles, n_terms;
+};
+
+struct GrowArgs {
+    const uint32_t *term_ids, *q_off;
+    uint32_t nq, k, gq;               // gq: workgroups (runs of tiles) per query
+    const vbm25_hit *sealed;          // the sealed records of the run (a copy: nq x k) and their counts
+    const uint32_t *sealed_cnt;
+    double *ls;                       // per list (query q, workgroup w, wave v: list (q gq + w) 4 + v): k entries
+    uint32_t *lg, *lc;
+    vbm25_hit *hits;                  // the batch's records: the merged result
+    uint32_t *n_hits;
+    // filtered batches only (FILT): growing bitmap s = filt_stride uint32 words at filt_words + s filt_stride (bit g % 32 of word
+    // g / 32: document g may be returned), filt_sel[q] = query q's selector (NONE32: none).  Unread by the unfiltered kernels.
+    const uint32_t *filt_words;
+    const uint32_t *filt_sel;
+    uint32_t filt_stride;
+};
+
+}  // namespace vbm25
+
+#endif

@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define EVL_HD __host__ __device__ __forceinline__
 #else
 #define EVL_HD inline __attribute__((always_inline))

@@ -1,5 +1,5 @@
-// growing.h -- the growing (unsealed) segment on the device: upload kernels and the query-time scan and merge.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, after merge.h.
+// growing.h -- the growing (unsealed) segment at query time: the scan and the merge (the upload kernels: growing_build.h).
+// Included by search.hip only (non-template kernels among them: one definition).
 //
 // search.rs:83-135 scores every unsealed document (a VectorTuple: elements of ascending key) with the SEALED segment's statistics
 // before the WAND loop.  The upload turns the documents into an inverted form: per sealed term id the postings (g, c) of the growing
@@ -17,107 +17,13 @@
 // growing_scan_kernel<KM, true> a lane's uint32 word of the bitmap covers exactly the 32 documents of its bits[] word, so a rejected
 // document is dropped where the touched documents are extracted (never read from acc, never offered); a tile whose bitmap words are
 // all zero is skipped by the whole workgroup before any posting is read.  k > 1024: bigk_mask_kernel zeroes the rejected scores.
+#ifndef VBM25_GROWING_H
+#define VBM25_GROWING_H
 
-constexpr uint32_t GT = 8192;        // documents per tile: 64 KB of f64 accumulators in LDS
-constexpr uint32_t GWG = 256;        // threads of growing_scan_kernel
-constexpr uint32_t G_MAX_WG = 512;   // workgroups of growing_scan_kernel a batch aims at (two per CU: LDS)
+#include "device_types.h"
+#include "topk_reg.h"
 
-struct DevGrowing {
-    const uint32_t *term_start;  // n_terms + 1: postings of term t are [term_start[t], term_start[t + 1])
-    const uint32_t *post_g;      // per posting: growing document index, ascending inside a term
-    const double *post_c;        // per posting: Cache::evaluate(fieldnorm[g], tf) of the term
-    const uint32_t *tab_idx;     // per term: first entry of its tile table, NONE32 = none (a short list: binary search)
-    const uint32_t *tab;         // a tabled term's n_tiles + 1 entries: entry j = its first posting with g >= j GT
-    const uint16_t *payload;     // n_grow x 3
-    uint32_t n_grow, n_tiles, n_terms;
-};
-
-struct GrowArgs {
-    const uint32_t *term_ids, *q_off;
-    uint32_t nq, k, gq;               // gq: workgroups (runs of tiles) per query
-    const vbm25_hit *sealed;          // the sealed records of the run (a copy: nq x k) and their counts
-    const uint32_t *sealed_cnt;
-    double *ls;                       // per list (query q, workgroup w, wave v: list (q gq + w) 4 + v): k entries
-    uint32_t *lg, *lc;
-    vbm25_hit *hits;                  // the batch's records: the merged result
-    uint32_t *n_hits;
-    // filtered batches only (FILT): growing bitmap s = filt_stride uint32 words at filt_words + s filt_stride (bit g % 32 of word
-    // g / 32: document g may be returned), filt_sel[q] = query q's selector (NONE32: none).  Unread by the unfiltered kernels.
-    const uint32_t *filt_words;
-    const uint32_t *filt_sel;
-    uint32_t filt_stride;
-};
-
-// 16-byte token keys compare as memcmp: two big-endian 64-bit words
-__device__ __forceinline__ int key_cmp(const ulonglong2 a, const ulonglong2 b) {
-    const unsigned long long a0 = __builtin_bswap64(a.x), b0 = __builtin_bswap64(b.x);
-    if (a0 != b0) return a0 < b0 ? -1 : 1;
-    const unsigned long long a1 = __builtin_bswap64(a.y), b1 = __builtin_bswap64(b.y);
-    return a1 < b1 ? -1 : a1 > b1 ? 1 : 0;
-}
-
-// upload 1: per element of a live document the sort key (term id << 32 | g), ~0 for a key the sealed segment lacks or a deleted
-// document; the value is the element's tf.  `n_valid` counts the postings.
-__global__ void __launch_bounds__(256) grow_map_kernel(const ulonglong2 *term_key, uint32_t n_terms, uint32_t n_grow,
-                                                       const uint64_t *start, const ulonglong2 *g_key, const uint32_t *g_tf,
-                                                       const uint8_t *deleted, unsigned long long *keys, uint32_t *vals,
-                                                       uint32_t *n_valid) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_grow) return;
-    const uint64_t e0 = start[g] - start[0], e1 = start[g + 1] - start[0];
-    const bool live = !(deleted && deleted[g]);
-    uint32_t found = 0;
-    for (uint64_t e = e0; e < e1; ++e) {
-        unsigned long long key = ~0ull;
-        if (live) {
-            const ulonglong2 x = g_key[e];
-            uint32_t lo = 0, hi = n_terms;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (key_cmp(term_key[mid], x) < 0) lo = mid + 1; else hi = mid;
-            }
-            if (lo < n_terms && key_cmp(term_key[lo], x) == 0) {
-                key = (unsigned long long)lo << 32 | g;
-                ++found;
-            }
-        }
-        keys[e] = key;
-        vals[e] = g_tf[e];
-    }
-    if (found) atomicAdd(n_valid, found);
-}
-
-// upload 2: the sorted postings -> (g, c) and the term starts.  c exactly as the host's Cache::evaluate (-ffp-contract=off).
-__global__ void __launch_bounds__(256) grow_post_kernel(const unsigned long long *keys, const uint32_t *tf, uint32_t n_post,
-                                                        uint32_t n_terms, const double *s0, const double *s1, const uint8_t *fieldnorm,
-                                                        uint32_t *post_g, double *post_c, uint32_t *term_start) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_post) return;
-    const unsigned long long key = keys[i];
-    const uint32_t t = uint32_t(key >> 32), g = uint32_t(key);
-    const double f = (double)tf[i];
-    post_g[i] = g;
-    post_c[i] = (f * s0[t]) / (f + s1[fieldnorm[g]]);  // Cache::evaluate, bm25.rs:355-358
-    const uint32_t tp = i ? uint32_t(keys[i - 1] >> 32) : 0u;
-    for (uint32_t u = i ? tp + 1 : 0u; u <= t; ++u) term_start[u] = i;  // (the terms without postings before t start here too)
-    if (i + 1 == n_post)
-        for (uint32_t u = t + 1; u <= n_terms; ++u) term_start[u] = n_post;
-}
-
-// upload 3: the tile tables of the terms with at least n_tiles postings
-__global__ void __launch_bounds__(256) grow_tab_kernel(const unsigned long long *keys, uint32_t n_post, DevGrowing G, uint32_t *tab) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_post) return;
-    const uint32_t t = uint32_t(keys[i] >> 32);
-    const uint32_t ti = G.tab_idx[t];
-    if (ti == NONE32) return;
-    const uint32_t p0 = G.term_start[t], p1 = G.term_start[t + 1];
-    const uint32_t j = G.post_g[i] / GT;
-    const uint32_t jp = i == p0 ? 0u : G.post_g[i - 1] / GT + 1u;
-    for (uint32_t u = jp; u <= j; ++u) tab[ti + u] = i;
-    if (i + 1 == p1)
-        for (uint32_t u = j + 1; u <= G.n_tiles; ++u) tab[ti + u] = p1;
-}
+namespace vbm25 {
 
 // postings of term t with g in tile j
 __device__ __forceinline__ uint2 grow_tile_range(const DevGrowing &G, uint32_t t, uint32_t j) {
@@ -370,28 +276,6 @@ __global__ void __launch_bounds__(256) growing_final_kernel(const vbm25_hit *sea
                     blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
-// vbm25_filter_extend_growing: the delta bitmaps (F x dw words, bit j of delta i = growing document n_old + j) merged into the
-// filter's growing bitmaps on the device.  One thread per (bitmap i, word w) with w0 <= w < w1: the word is what the bitmap held
-// (words below old_words, from src at stride src_stride) ORed with the delta funnel-shifted left by s = n_old % 64 -- delta word
-// j = w - n_old / 64 contributes its low 64 - s bits, word j - 1 its high s bits.  In place (src == dst, same stride) w0 is the
-// boundary word n_old / 64 and only the tail is touched; a growth step runs it from w0 = 0 into the new buffer at the new stride,
-// which re-strides all F bitmaps.  Every thread reads and writes its own word only.  delta NULL: all zero.
-__global__ void __launch_bounds__(256) filter_extend_growing_kernel(const unsigned long long *src, uint32_t src_stride, uint32_t old_words,
-                                                                    unsigned long long *dst, uint32_t dst_stride, uint32_t n_bitmaps,
-                                                                    uint32_t n_old, const unsigned long long *delta, uint32_t dw, uint32_t w0,
-                                                                    uint32_t w1) {
-    const uint32_t span = w1 - w0;
-    const unsigned long long total = (unsigned long long)n_bitmaps * span;
-    const uint32_t bw = n_old >> 6, s = n_old & 63u;
-    for (unsigned long long x = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (unsigned long long)gridDim.x * blockDim.x) {
-        const uint32_t i = uint32_t(x / span), w = w0 + uint32_t(x % span);
-        unsigned long long v = w < old_words ? src[size_t(i) * src_stride + w] : 0ull;
-        if (delta && w >= bw) {
-            const uint32_t j = w - bw;
-            const unsigned long long *d = delta + size_t(i) * dw;
-            if (j < dw) v |= d[j] << s;
-            if (s && j >= 1u && j - 1u < dw) v |= d[j - 1u] >> (64u - s);
-        }
-        dst[size_t(i) * dst_stride + w] = v;
-    }
-}
+}  // namespace vbm25
+
+#endif

@@ -1,5 +1,5 @@
 // growing_append.h -- the growing segment changed in place: vbm25_device_growing_append and vbm25_device_growing_delete.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, after growing.h.
+// Included by growing.hip only (non-template kernels: one definition); key_cmp is growing_build.h's.
 //
 // The layout stays growing.h's (term-major post_g / post_c, term_start, tab_idx / tab, payload), so no search kernel knows about
 // an append.  An append is a merge on the device.  The delta's elements become sorted (term << 32 | g) keys exactly as an upload's
@@ -13,6 +13,12 @@
 //
 // A delete zeroes the c of the deleted documents' postings.  Live postings are positive (idf = ln((N + 1) / (df + 0.5)) > 0), so such
 // a document sums to exactly 0.0: growing_scan_kernel admits only s > thr >= 0 and the k > 1024 path takes a zero key as no hit.
+#ifndef VBM25_GROWING_APPEND_H
+#define VBM25_GROWING_APPEND_H
+
+#include "growing_build.h"
+
+namespace vbm25 {
 
 constexpr uint32_t GA_ITEMS = 4;  // old postings per thread of grow_append_move_kernel
 
@@ -154,3 +160,7 @@ __global__ void __launch_bounds__(256) grow_delete_kernel(const uint32_t *post_g
     const uint32_t g = post_g[i];
     if ((bits[g >> 5] >> (g & 31u)) & 1u) post_c[i] = 0.0;
 }
+
+}  // namespace vbm25
+
+#endif

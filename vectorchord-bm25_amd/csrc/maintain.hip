@@ -23,10 +23,7 @@
 
 #include "vbm25_internal.h"
 #include "device_segment.h"
-
-namespace vbm25 {
 #include "decode.h"
-}
 
 namespace {
 
@@ -741,7 +738,7 @@ int maintain_device(const MaintainSource &s, const MaintainInput &in, uint32_t *
 }
 
 // ---------------------------------------------------------------------------
-// vbm25_filter_remap: a filter's bitmaps carried across the compaction (search.hip owns the filters and checks the arguments)
+// vbm25_filter_remap: a filter's bitmaps carried across the compaction (filter.hip owns the filters and checks the arguments)
 // ---------------------------------------------------------------------------
 // The old documents are one run of input words: the sealed bitmaps' W words, then the growing bitmaps' GW words.  keep / base are the
 // relabel's pair over that run (mt_keep_kernel per side, ONE exclusive scan over both), so base[w] is input word w's first OUTPUT BIT:

@@ -1,6 +1,13 @@
 // merge.h -- merge_kernel: per-chunk lists -> hits.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, in
-// this order: device_types, decode, plan, topk_lds, block_fetch, topk_reg, scan_range, scan_dense, scan_many, merge.
+// Included by search.hip.
+#ifndef VBM25_MERGE_H
+#define VBM25_MERGE_H
+
+#include "device_types.h"
+#include "topk_lds.h"
+#include "topk_reg.h"
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Merge of per-chunk lists -> hits
@@ -157,3 +164,7 @@ __global__ void __launch_bounds__(64) merge_kernel(DevIndex ix, DevBatch bt) {
         }
     }
 }
+
+}  // namespace vbm25
+
+#endif

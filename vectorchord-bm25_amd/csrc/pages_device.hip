@@ -339,7 +339,7 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
 //   vec_finish_kernel    one wave per page, lane per slot: fieldnorm from the _2; deleted, payload and start[g + 1] from the _0
 //   vec_copy_kernel      one wave per page, lanes over the page's ELEMENTS: 20 bytes -> the key plane (16) and the tf plane (4)
 //   vec_check_kernel     the same lanes: keys strictly ascending inside a document (vbm25_growing_upload's rule)
-// then the device half of vbm25_growing_upload (search.hip) on those arrays.
+// then the device half of vbm25_growing_upload (growing.hip) on those arrays.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct TupleIncrement {
     __host__ __device__ unsigned long long operator()(uint32_t meta) const { return tuple_increment(meta); }

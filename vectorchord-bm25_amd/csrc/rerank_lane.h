@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define RRK_HD __host__ __device__ __forceinline__
 #else
 #define RRK_HD inline __attribute__((always_inline))

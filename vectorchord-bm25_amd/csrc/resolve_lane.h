@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define RSV_HD __host__ __device__ __forceinline__
 #else
 #define RSV_HD inline __attribute__((always_inline))

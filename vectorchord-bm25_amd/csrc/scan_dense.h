@@ -1,6 +1,5 @@
 // scan_dense.h -- scan_dense_kernel: queries with many postings per document (Zipf head terms; BASELINE config
-// C5), <= D_T indexed terms, k <= REG_K.  Part of libvbm25's single device translation unit: included by
-// search.hip inside namespace vbm25, after scan_range.h (whose helpers it uses).
+// C5), <= D_T indexed terms, k <= REG_K.  Included by search.hip; uses scan_range.h's helpers.
 //
 // One 8-wave workgroup per work item (query x doc range), persistent, items from bt.work_ctr[1].  The item is
 // cut into WINDOWS of <= D_W consecutive documents with one 16-bit FIXED-POINT accumulator per document in LDS (two per word)
@@ -49,6 +48,12 @@
 //
 // The first window of a query whose threshold is still 0 is 256 documents wide and the width doubles from
 // there: the number of candidates per window stays near k ln 2 while the threshold warms up.
+#ifndef VBM25_SCAN_DENSE_H
+#define VBM25_SCAN_DENSE_H
+
+#include "scan_range.h"
+
+namespace vbm25 {
 
 constexpr int DNW = 8;
 static_assert(DNW <= RNW, "one result list per wave: bt.lpi is scan_range_kernel's");
@@ -66,10 +71,6 @@ constexpr int D_WCB = 128;               // candidate buffer entries per wave
 constexpr int D_UN = D_UN_V;                  // tasks per wave in flight
 constexpr uint32_t D_MAX_RESOLVED = 16384;  // exact re-scorings per item; beyond (masses of equal scores): scan_many_kernel
 constexpr uint32_t D_SPAN_TEST = 512;    // widest block span the skip test reads (8 accumulators per lane)
-constexpr uint32_t D_GRID = 512;         // persistent workgroups: 256 CUs x 2
-constexpr uint32_t D_TARGET_ITEMS = 12288;   // items of a batch of dense queries: the launch ends with its slowest workgroup, and an item's setup is 24 k cycles of
-                                           // the 20 M an item of C5 takes at 4096 -- C5: 4096 items 72.9 ms, 8192 69.9, 12288 69.7, 24576 70.9 (search.hip caps a
-                                           // query's share where the corpus is small)
 
 struct DenseLds {
     uint32_t acc[D_W / 2];    // 16-bit fixed point, two documents per word: scale x (upper bound of the document's score) < 2^16
@@ -888,3 +889,7 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
     }
 #endif
 }
+
+}  // namespace vbm25
+
+#endif

@@ -1,8 +1,17 @@
 // scan_many.h -- scan_many_kernel: more than 16 terms (up to MAX_TERMS), every query of 256 < k <= 1024, dense queries when
 // scan_dense_kernel is off, and the items the first-choice kernels gave up.  Exhaustive: term-phased exact f64 accumulation
 // in dense doc windows or an LDS hash, LDS top-k, the query's shared threshold.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, in
-// this order: device_types, decode, plan, topk_lds, block_fetch, topk_reg, scan_range, scan_dense, scan_many, merge.
+// Included by search.hip.
+#ifndef VBM25_SCAN_MANY_H
+#define VBM25_SCAN_MANY_H
+
+#include "device_types.h"
+#include "decode.h"
+#include "topk_lds.h"
+#include "block_fetch.h"
+#include "topk_reg.h"
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Posting scan
@@ -240,3 +249,7 @@ __global__ void __launch_bounds__(WG) scan_many_kernel(DevIndex ix, DevBatch bt)
         }
     }
 }
+
+}  // namespace vbm25
+
+#endif

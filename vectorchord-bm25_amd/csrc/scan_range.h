@@ -1,5 +1,5 @@
 // scan_range.h -- scan_range_kernel: the doc-range formulation (queries of <= RT indexed terms, k <= REG_K).
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25.
+// Included by search.hip.
 //
 // One 8-wave workgroup per work item (query x doc range), persistent, items from an atomic counter.  The
 // item is cut into TILES: a tile is a doc range [tlo, thi) that holds at most R_NBLK posting blocks of the
@@ -32,6 +32,16 @@
 // 64-bit atomicMax word and the 256-bucket histogram.  Lists go to res_* at
 // item * lpi + wave; merge_kernel merges them.  A tile whose rows overflow hands the item to
 // scan_many_kernel (item_failed).
+#ifndef VBM25_SCAN_RANGE_H
+#define VBM25_SCAN_RANGE_H
+
+#include "device_types.h"
+#include "decode.h"
+#include "topk_lds.h"
+#include "block_fetch.h"
+#include "topk_reg.h"
+
+namespace vbm25 {
 
 #ifndef VBM25_RNW
 #define VBM25_RNW 8
@@ -54,9 +64,6 @@ constexpr int R_HS_LOG2 = 10;  // > rows + every lane of the workers inserting a
 
 constexpr int R_HS = 1 << R_HS_LOG2;  // slots of the second-arrival hash set
 constexpr int R_ROWS = 192;           // rows (documents with a second arrival) per tile at RT = 8; 96 at RT = 16
-constexpr uint32_t R_TARGET_ITEMS = 1024;
-constexpr uint32_t R_MIN_CHUNK_POSTINGS = 16384;
-constexpr uint32_t R_GRID = 512;      // persistent workgroups: 256 CUs x 2 (KMAX <= 64; 1 per CU above)
 constexpr int R_PLAN_RING = 3;
 constexpr int R_LIST = VBM25_RLIST;   // second arrivals per wave per tile; more than that: scan_many_kernel
 constexpr int R_STAGE_STRIDE = 130;   // words between staged rows: 128 would put the same column of every row on one LDS bank (S2 probes columns)
@@ -1235,3 +1242,7 @@ __global__ void __launch_bounds__(RWG, KMAX > 64 ? VBM25_RWPS_BIGK : VBM25_RWPS)
     }
 #endif
 }
+
+}  // namespace vbm25
+
+#endif

@@ -1,6 +1,6 @@
 // scan_win.h -- scan_win_kernel: the document-WINDOW formulation of the sparse posting scan (queries of <= WN_T indexed terms
 // whose lists are of comparable length; k <= 256: one, two or four register rows of the top-k): the dominant kernel of C3.
-// Part of libvbm25's device code: included inside namespace vbm25 after device_types, decode, topk_lds, block_fetch, topk_reg.
+// Included by scan_win.hip only.
 //
 // Replaces the traversal of search.rs:149-280 (the WAND main loop) for these queries.  What the loop computes -- the k best sums of
 // Cache::evaluate over the query's terms (bm25.rs:355-358), ties by ascending document -- is reached differently:
@@ -38,6 +38,16 @@
 // that finishes the query's last item does, from memory or, where the query's items share a workgroup, from the LDS (WN_LQ_*).  An item with a
 // window that collects more than WN_LIST second arrivals or a term frequency above 255 in a second arrival is handed to
 // scan_many_kernel (item_failed).  A run thicker than one load per lane (WN_SLOT postings) takes a chunk loop on the spot.
+#ifndef VBM25_SCAN_WIN_H
+#define VBM25_SCAN_WIN_H
+
+#include "device_types.h"
+#include "decode.h"
+#include "topk_lds.h"
+#include "block_fetch.h"
+#include "topk_reg.h"
+
+namespace vbm25 {
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"  // (the wipe names M0 as clobbered: a reserved register)
@@ -1265,3 +1275,7 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
 #endif
 }
 #pragma clang diagnostic pop
+
+}  // namespace vbm25
+
+#endif

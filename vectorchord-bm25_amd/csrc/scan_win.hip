@@ -1,11 +1,9 @@
-// scan_win.hip -- translation unit of scan_win_kernel (scan_win.h): the device types and helpers of search.hip, the kernel, and the
-// launcher search.hip calls.  A unit of its own so that the dominant kernel of C3 compiles in seconds, not with the other eight.
+// scan_win.hip -- translation unit of scan_win_kernel (scan_win.h): the device types and helpers the scan kernels share, the kernel, and
+// the launcher search.hip calls.  A unit of its own so that the dominant kernel of C3 compiles in seconds, not with the other eight.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
 #include "vbm25_internal.h"
-
-namespace vbm25 {
 #include "device_types.h"
 #include "decode.h"
 #include "topk_lds.h"
@@ -13,6 +11,8 @@ namespace vbm25 {
 #include "topk_reg.h"
 #include "scan_win.h"
 #include "scan_win_launch.h"
+
+namespace vbm25 {
 
 // mt: the most indexed terms of a query of the batch; k: the top-k lives in 1, 2 or 4 register rows of 64 entries (beyond five run
 // loads the kernel has registers for one row only: scan_win_max_k)

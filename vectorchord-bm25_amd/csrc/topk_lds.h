@@ -1,6 +1,11 @@
 // topk_lds.h -- sorted top-k list in LDS kept by one wave (k > 256, scan_many_kernel).
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, in
-// this order: device_types, decode, plan, topk_lds, block_fetch, topk_reg, scan_range, scan_dense, scan_many, merge.
+// Included by search.hip and scan_win.hip.
+#ifndef VBM25_TOPK_LDS_H
+#define VBM25_TOPK_LDS_H
+
+#include "device_types.h"
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Sorted top-k list in LDS, maintained by ONE wave.
@@ -71,3 +76,7 @@ __device__ __forceinline__ void topk_offer(TopK<KMAX> &L, uint32_t k, bool has, 
         if ((int)lane == leader) has = false;
     }
 }
+
+}  // namespace vbm25
+
+#endif

@@ -1,6 +1,13 @@
 // topk_reg.h -- RegTopK (top-k in registers), wave helpers, profiling macros.
-// Part of libvbm25's single device translation unit: included by search.hip inside namespace vbm25, in
-// this order: device_types, decode, plan, topk_lds, block_fetch, topk_reg, scan_range, scan_dense, scan_many, merge.
+// Included by search.hip and scan_win.hip.
+#ifndef VBM25_TOPK_REG_H
+#define VBM25_TOPK_REG_H
+
+#include "device_types.h"
+#include "topk_lds.h"
+#include "block_fetch.h"
+
+namespace vbm25 {
 
 // ---------------------------------------------------------------------------
 // Running top-k of ONE wave held in registers: RK rows of 64 entries, sorted best first, entry e
@@ -100,4 +107,8 @@ __device__ __forceinline__ void lds_barrier() {
 #define PROF_T(var)
 #define PROF_MARK(var)
 #define PROF_ADD(slot, a, b)
+#endif
+
+}  // namespace vbm25
+
 #endif

@@ -1,8 +1,8 @@
-// vbm25_internal.h -- shared between the host (segment.cpp) and device (search.hip) halves
-// of libvbm25.  Not part of the ABI.
+// vbm25_internal.h -- shared between the host (.cpp) and device (.hip) units of libvbm25.  Not part of the ABI.
 #ifndef VBM25_INTERNAL_H
 #define VBM25_INTERNAL_H
 
+#include <cstddef>
 #include <cstdint>
 #include <exception>
 #include <new>
@@ -14,6 +14,11 @@ namespace vbm25 {
 
 // Thread-local error text; returns `code` so callers can `return set_error(...)`.
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// The calling thread's error text copied out and put back, ERROR_TEXT_BYTES either way (error.cpp keeps the text: a worker thread's
+// error becomes its caller's, multi.hip)
+constexpr size_t ERROR_TEXT_BYTES = 512;
+void error_text_read(char *out);
+void error_text_write(const char *in);
 
 // No C++ exception may cross the C ABI (the reference's crate is #![deny(ffi_unwind_calls)], src/lib.rs:16):
 // every entry point that allocates runs its body through this.
@@ -64,7 +69,7 @@ struct Segment {
 };
 
 // The growing segment's CSR in HBM on the index's device (vbm25_growing_desc's arrays, start[0] == 0): what the device reader of the
-// vectors tape (pages_device.hip) hands to the builder of the device growing segment (search.hip)
+// vectors tape (pages_device.hip) hands to the builder of the device growing segment (growing.hip)
 struct GrowingDeviceArrays {
     uint32_t n_docs;
     uint64_t n_elements;
@@ -92,7 +97,7 @@ struct ResolverVocabulary {
     const void *keys;
 };
 int resolver_vocabulary(const vbm25_resolver *r, ResolverVocabulary *out);
-// ... and of an index (search.hip fills it in): the per-term idf and the s1 table vbm25_evaluate_batch scores with, both in HBM
+// ... and of an index (index.hip fills it in): the per-term idf and the s1 table vbm25_evaluate_batch scores with, both in HBM
 struct EvaluateTables {
     int device;
     uint32_t n_docs, n_terms;
