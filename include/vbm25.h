@@ -812,6 +812,57 @@ void vbm25_documents_free(vbm25_documents *);
 int vbm25_device_segment_build_documents(const vbm25_documents *, double k1, double b, vbm25_device_segment **out);
 int vbm25_device_growing_append_documents(vbm25_device_growing *, const vbm25_documents *);
 
+/* A caster (csrc/cast.hip): the Document step as a ring that keeps everything a cast needs between calls, modelled on the resolver.
+ * `depth` slots (1 .. 16), each with its own non-blocking stream, two events, a pinned staging block, its device scratch and its
+ * result arrays, all allocated by vbm25_caster_create for the capacities given there: batches of up to max_docs documents,
+ * max_lexemes lexemes and max_bytes lexeme bytes, of which up to max_long_lexemes lexemes may sit in documents of the general class
+ * (more than 2048 lexemes; it sizes the radix scratch, 0 = none).  One host thread drives a caster; several casters, and a caster
+ * beside any other handle, may run at once.  submit, collect, info and in_flight issue no device-wide synchronisation; create and
+ * free allocate and free device and pinned memory, which waits for the device's other streams, as every hipMalloc and hipFree may.
+ *   device bytes   per slot, with D = max_docs, L = max_lexemes, B = max_bytes, G = max_long_lexemes; the staged input is one
+ *             array whose nine parts are each rounded up to a multiple of 16, every other term is an array of exactly that size:
+ *             staged input   4(D+1) + 8(L+1) + 4L + 4D + 4(D+1) + 1024 + 6D + 8D + B
+ *             scratch        16L (keys) + 16L + 4L (survivors) + 4(D+1) (counts) + hipcub's temporary storage
+ *                            + (G > 0: 44G + 4) (the general class)
+ *             results        8(D+1) + 16L + 4L + 4D + D + 6D
+ *             vbm25_caster_device_bytes = depth x that sum (0 for NULL); the pinned host block is the staged input's size.
+ *   vbm25_caster_info      depth, device and `allocations`: every allocation and creation (device, pinned, stream, event) the handle
+ *             has made.  It does not move after create: submit and collect allocate, create and free nothing.
+ *   vbm25_caster_submit    vbm25_documents_cast's input (the seed is the caster's).  Every refusal of that call comes first and in the
+ *             same words; then VBM25_ERR_INVALID for a full ring and for documents, lexemes, bytes or general-class lexemes over the
+ *             capacities, VBM25_ERR_UNSUPPORTED with max_long_lexemes == 0 for a batch with a document of the general class (the
+ *             message names the first).  A refused submit enqueues nothing and leaves the ring as it was.  Otherwise the input is
+ *             copied into the slot's pinned block (the caller's arrays are free at return), the batch is enqueued and the call
+ *             returns.  There is no wait in the middle: the slot's key / tf arrays have room for max_lexemes elements, and the
+ *             number of elements comes home with the batch.
+ *             The wave class (documents of <= 64 lexemes) is packed: the host plans runs of consecutive such documents with at
+ *             most 64 lexemes and 64 documents a run, one wave takes a run, one lane a lexeme; a key in two documents of a run
+ *             never merges.  A batch without a longer document interns its lexemes in the same lanes.
+ *   vbm25_caster_collect   waits for the oldest batch, first in first out, and hands out a vbm25_documents that belongs to its slot,
+ *             with n_docs, n_elements and has_payload of that batch.  Everything that takes a const vbm25_documents * takes it;
+ *             vbm25_documents_free on it does nothing.  Valid until the submit that takes its slot again -- `depth` submits
+ *             after its own -- or vbm25_caster_free.  Its bytes are vbm25_documents_cast's for the same input, array for array.
+ *             VBM25_ERR_INVALID, *out == NULL, on an empty ring.
+ *   vbm25_caster_in_flight   batches submitted and not collected (0 for NULL).
+ *   vbm25_caster_free      waits for what is in flight, then frees everything.
+ *   vbm25_documents_extend appends src's documents behind dst's on the device (start rebased by a kernel, the other arrays copied
+ *             device to device), so a bulk load cast in chunks still ends in one handle.  dst is an owned handle (a
+ *             vbm25_documents_cast of 0 documents makes an empty one, with or without payloads); its arrays grow geometrically.
+ *             The result equals one cast of the concatenated input.  Refused, dst as it was: VBM25_ERR_INVALID for a NULL
+ *             argument, dst == src, a dst that belongs to a caster, different devices, one handle with payloads and one without;
+ *             VBM25_ERR_UNSUPPORTED for 2^31 - 1 documents or 2^31 elements or more in the sum. */
+typedef struct vbm25_caster vbm25_caster;
+int vbm25_caster_create(int device, const uint8_t *seed32, uint32_t depth, uint32_t max_docs, uint32_t max_lexemes,
+                        uint64_t max_bytes, uint32_t max_long_lexemes, vbm25_caster **out);
+void vbm25_caster_free(vbm25_caster *);
+uint64_t vbm25_caster_device_bytes(const vbm25_caster *);
+int vbm25_caster_info(const vbm25_caster *, uint32_t *depth, int *device, uint64_t *allocations);
+int vbm25_caster_submit(vbm25_caster *, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count,
+                        const uint32_t *doc_lex, uint32_t n_docs, const uint16_t *doc_payload);
+int vbm25_caster_collect(vbm25_caster *, const vbm25_documents **out);
+int vbm25_caster_in_flight(const vbm25_caster *);
+int vbm25_documents_extend(vbm25_documents *dst, const vbm25_documents *src);
+
 /* The `<&>` operator from cast documents (csrc/evaluate.hip): bm25::evaluate (evaluate.rs:22-74) for a batch of queries, each
  * against its own list of candidate documents -- the reranking form of `tsvector <&> bm25query` (src/index/operators.rs:22-55) --
  * with the documents read from HBM.  Two steps.

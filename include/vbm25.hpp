@@ -217,10 +217,18 @@ class Documents {
         check(vbm25_documents_cast(device, seed ? seed->data() : nullptr, b.lexemes.bytes.data(), b.lexemes.lex_off.data(), b.lex_count.data(),
                                    b.lexemes.q_lex.data(), b.documents(), b.payload.empty() ? nullptr : b.payload.data(), &h_));
     }
+    // an owned handle of 0 documents, with or without payloads: what extend() grows
+    static Documents empty(int device = 0, bool payload = false) {
+        DocumentBatch b;
+        if (payload) b.payload.assign(3, 0);  // (a non-NULL pointer: the handle is one with payloads)
+        return Documents(device, nullptr, b);
+    }
     Documents(Documents &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     Documents(const Documents &) = delete;
     Documents &operator=(const Documents &) = delete;
-    ~Documents() { vbm25_documents_free(h_); }
+    ~Documents() { vbm25_documents_free(h_); }  // (nothing for a handle a Caster handed out: it is the caster's)
+    // vbm25_documents_extend: `src`'s documents behind this handle's, on the device.  This handle is an owned one.
+    void extend(const Documents &src) { check(vbm25_documents_extend(h_, src.handle())); }
     uint32_t docs() const {
         uint32_t n = 0;
         check(vbm25_documents_info(h_, &n, nullptr, nullptr));
@@ -239,7 +247,45 @@ class Documents {
     const vbm25_documents *handle() const { return h_; }
 
   private:
+    friend class Caster;
+    explicit Documents(const vbm25_documents *of_a_caster) : h_(const_cast<vbm25_documents *>(of_a_caster)) {}
     vbm25_documents *h_ = nullptr;
+};
+
+// The Document step as a ring (RAII over vbm25_caster): `depth` slots that keep their stream, events, pinned staging, device scratch
+// and result arrays between casts.  submit() copies a batch in and enqueues it; collect() waits for the oldest batch and returns its
+// Documents, which belongs to the slot: valid until the submit that takes the slot again (`depth` submits after its own) and no
+// longer than the caster.  One thread drives a caster.  Move-only.
+class Caster {
+  public:
+    Caster(int device, const Seed *seed, uint32_t depth, uint32_t max_docs, uint32_t max_lexemes, uint64_t max_bytes, uint32_t max_long_lexemes = 0) {
+        check(vbm25_caster_create(device, seed ? seed->data() : nullptr, depth, max_docs, max_lexemes, max_bytes, max_long_lexemes, &h_));
+    }
+    Caster(Caster &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Caster(const Caster &) = delete;
+    Caster &operator=(const Caster &) = delete;
+    ~Caster() { vbm25_caster_free(h_); }
+    void submit(const DocumentBatch &b) {
+        check(vbm25_caster_submit(h_, b.lexemes.bytes.data(), b.lexemes.lex_off.data(), b.lex_count.data(), b.lexemes.q_lex.data(), b.documents(),
+                                  b.payload.empty() ? nullptr : b.payload.data()));
+    }
+    Documents collect() {
+        const vbm25_documents *d = nullptr;
+        check(vbm25_caster_collect(h_, &d));
+        return Documents(d);
+    }
+    int in_flight() const { return vbm25_caster_in_flight(h_); }
+    uint64_t device_bytes() const { return vbm25_caster_device_bytes(h_); }
+    // every allocation and creation the handle has made: it does not move after the constructor
+    uint64_t allocations() const {
+        uint64_t n = 0;
+        check(vbm25_caster_info(h_, nullptr, nullptr, &n));
+        return n;
+    }
+    vbm25_caster *handle() const { return h_; }
+
+  private:
+    vbm25_caster *h_ = nullptr;
 };
 
 // Cast documents bound to one index's vocabulary (RAII over vbm25_doc_terms): per document the ascending term ids of its known

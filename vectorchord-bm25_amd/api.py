@@ -5,6 +5,7 @@ Names follow the reference (crates/bm25): `intern` (vector.rs:19-35), `Query`
 wrapper over the C ABI in include/vbm25.h; no computation happens in Python.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -1122,7 +1123,9 @@ def set_tuning(name, value):
     range_min_chunk, range_grid, dense_grid, fused_items, arith, win, win_force, win_items, win_grid, win_skew, win_guided,
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
-    and cast_group_max (the class bounds of Documents.cast, read at the start of each cast; 0 turns the class off), eval_grid (the
+    and cast_group_max (the class bounds of Documents.cast and Caster.submit, read at the start of each; 0 turns the class off),
+    cast_pack (a Caster's wave class: 0 one document a wave, 1 several a wave, 2 several a wave interning in the lanes where the batch
+    allows) and cast_grid (the most workgroups of a Caster's kernels, 0 .. 2048, 0 = no cap; both read at each submit), eval_grid (the
     most workgroups of the kernels of Documents.bind, DocTerms.evaluate and a Scorer, 1 .. 2048, read at the start of each call),
     rerank_part (the candidates one workgroup of Scorer.topk selects from, 64 .. 2^20 in 64s) and rerank_buf (its selection buffer
     as a multiple of k, 2 .. 8; both read at the start of each Scorer call).  No switch of
@@ -1208,15 +1211,26 @@ class Documents:
     distinct keys ascending with their saturating tf sums, the length and its fieldnorm code.  DeviceSegment.from_documents makes an
     index of it, GrowingSegment.append_documents appends it; download() brings the arrays back."""
 
-    def __init__(self, handle):
-        self.h = handle
+    def __init__(self, handle, caster=None):
+        self._h = handle
+        self.caster = caster  # (a collected handle is its caster's: kept alive, never freed from here)
+        self._refresh()
+
+    @property
+    def h(self):
+        """the library's handle; a Documents collected from a Caster loses it when that caster is closed"""
+        if self._h is None:
+            raise Vbm25Error(-1, "this Documents belonged to a Caster that has been closed: its arrays are freed")
+        return self._h
+
+    def _refresh(self):
         nd, ne, dev = C.c_uint32(), C.c_uint64(), C.c_int()
         check(lib().vbm25_documents_info(self.h, C.byref(nd), C.byref(ne), C.byref(dev)))
         self.n_docs, self.n_elements, self.device = nd.value, ne.value, dev.value
 
-    @classmethod
-    def cast(cls, docs_or_packed, payload=None, seed=None, device=0):
-        """`docs_or_packed`: a list of lists of (lexeme, count), or pack_documents' tuple.  payload: None or uint16 [n_docs, 3]."""
+    @staticmethod
+    def _input(docs_or_packed, payload):
+        """-> (bytes, lex_off, lex_count, doc_lex, n_docs, payload) as contiguous arrays of the library's types"""
         if isinstance(docs_or_packed, tuple) and len(docs_or_packed) == 4:
             data, lex_off, lex_count, doc_lex = docs_or_packed
             data, lex_off = np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(lex_off, dtype=np.uint64)
@@ -1230,10 +1244,28 @@ class Documents:
                 raise ValueError(f"{len(payload)} payload words for {n_docs} documents")
             if not n_docs:
                 payload = np.zeros(3, dtype=np.uint16)  # (a non-NULL pointer: the handle is one with payloads)
+        return data, lex_off, lex_count, doc_lex, n_docs, payload
+
+    @classmethod
+    def cast(cls, docs_or_packed, payload=None, seed=None, device=0):
+        """`docs_or_packed`: a list of lists of (lexeme, count), or pack_documents' tuple.  payload: None or uint16 [n_docs, 3]."""
+        data, lex_off, lex_count, doc_lex, n_docs, payload = cls._input(docs_or_packed, payload)
         out = C.c_void_p()
         check(lib().vbm25_documents_cast(device, _seed_arg(seed), _p(data), lex_off.ctypes.data, lex_count.ctypes.data, doc_lex.ctypes.data,
                                          n_docs, _p(payload), C.byref(out)))
         return cls(out)
+
+    @classmethod
+    def empty(cls, device=0, payload=False):
+        """An owned handle of 0 documents, with or without payloads: what extend() grows"""
+        return cls.cast([], payload=np.zeros((0, 3), dtype=np.uint16) if payload else None, device=device)
+
+    def extend(self, other):
+        """vbm25_documents_extend: `other`'s documents behind this handle's, on the device.  This handle is an owned one (cast,
+        empty), `other` any Documents of the same device and payload kind; the result equals one cast of the concatenated input."""
+        check(lib().vbm25_documents_extend(self.h, other.h))
+        self._refresh()
+        return self
 
     def device_bytes(self):
         return int(lib().vbm25_documents_device_bytes(self.h))
@@ -1263,8 +1295,69 @@ class Documents:
 
     def __del__(self):
         try:
-            if self.h:
-                lib().vbm25_documents_free(self.h)
+            if self._h and self.caster is None:
+                lib().vbm25_documents_free(self._h)
+        except Exception:
+            pass
+
+
+class Caster:
+    """vbm25_caster: the Document step as a ring of `depth` slots (1 .. 16) that keep their stream, events, pinned staging, device
+    scratch and result arrays between casts: submit() copies a batch in and enqueues it, collect() waits for the oldest batch and
+    returns its Documents -- valid until the submit that takes its slot again, `depth` submits after its own.  Capacities a batch:
+    max_docs documents, max_lexemes lexemes, max_bytes lexeme bytes, max_long_lexemes lexemes in documents of more than 2048.  One
+    thread drives a caster.  Also a context manager."""
+
+    def __init__(self, device, depth, max_docs, max_lexemes, max_bytes, max_long_lexemes=0, seed=None):
+        self.h = C.c_void_p()
+        check(lib().vbm25_caster_create(device, _seed_arg(seed), depth, max_docs, max_lexemes, max_bytes, max_long_lexemes, C.byref(self.h)))
+        self.device, self.depth = device, depth
+        self._collected = weakref.WeakSet()  # (the Documents handed out and still alive: close() takes their handles away)
+
+    def submit(self, docs_or_packed, payload=None):
+        """vbm25_caster_submit: Documents.cast's input"""
+        data, lex_off, lex_count, doc_lex, n_docs, payload = Documents._input(docs_or_packed, payload)
+        check(lib().vbm25_caster_submit(self.h, _p(data), lex_off.ctypes.data, lex_count.ctypes.data, doc_lex.ctypes.data, n_docs, _p(payload)))
+
+    def collect(self):
+        """The oldest batch in flight as a Documents that keeps this caster alive and never frees the handle"""
+        out = C.c_void_p()
+        check(lib().vbm25_caster_collect(self.h, C.byref(out)))
+        docs = Documents(out, caster=self)
+        self._collected.add(docs)
+        return docs
+
+    def in_flight(self):
+        return int(lib().vbm25_caster_in_flight(self.h))
+
+    def device_bytes(self):
+        return int(lib().vbm25_caster_device_bytes(self.h))
+
+    def allocations(self):
+        """every allocation and creation the handle has made: it does not move after the constructor"""
+        n = C.c_uint64()
+        check(lib().vbm25_caster_info(self.h, None, None, C.byref(n)))
+        return n.value
+
+    def close(self):
+        """vbm25_caster_free.  Every Documents this caster handed out is invalid from here on: using one raises instead of reading
+        freed memory."""
+        if self.h:
+            for docs in list(self._collected):
+                docs._h = None
+            self._collected.clear()
+            lib().vbm25_caster_free(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

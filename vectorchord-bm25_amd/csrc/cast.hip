@@ -23,6 +23,16 @@
 //   The classes write identical bytes: the order is memcmp's in all three and the saturating sum does not depend on the order.
 //   No kernel here has scratch memory.
 //
+//   the caster (vbm25_caster): the same cast as a ring of slots that keep stream, events, pinned block, scratch and result arrays.  A
+//   submit validates, writes the class lists, the general class's offsets and the packing plan straight into the slot's pinned block,
+//   copies the caller's arrays behind them and enqueues; nothing is allocated, created or freed, and nothing waits in the middle (key /
+//   tf have room for every lexeme, start[n_docs] comes home in pinned memory).  collect waits for the oldest batch's event.
+//     cast_pack_kernel    the wave class, several documents a wave (cast_pack 1, 2): one wave a run of the host's plan (<= 64 lexemes,
+//                         <= 64 documents), one lane a lexeme, the rank-and-merge confined to the lane's own document, in as many
+//                         steps as the run's longest document has lexemes.  <true>: the lanes intern their own lexemes (a batch
+//                         without a group- or general-class document, cast_pack 2): no cast_intern_kernel, the keys never reach HBM
+//     extend_start_kernel vbm25_documents_extend: src's start rebased behind dst's; the other arrays are device-to-device copies
+//
 //   the index from documents (document i = doc id i), on the handle's device:
 //     (radix sort)        all elements by key, stable: two 64-bit passes with the element index as the value.  Elements are in document
 //                         order, so every key's run comes out in ascending document order
@@ -58,6 +68,11 @@ constexpr uint32_t WG = 256, MAX_GRID = 2048;
 
 // cast_wave_max / cast_group_max of vbm25_tuning_set: read at the start of each cast
 std::atomic<uint32_t> g_wave_max{CAST_WAVE_MAX}, g_group_max{CAST_GROUP_MAX};
+// cast_pack / cast_grid: read at each vbm25_caster_submit.  cast_pack: the wave class of a caster's batch through cast_wave_kernel (0),
+// cast_pack_kernel on keys from HBM (1), cast_pack_kernel interning in its lanes where the batch has no other class (2).  cast_grid: the most
+// workgroups of a caster's kernels (0: no cap of its own).
+constexpr uint32_t CAST_PACK_DEFAULT = 2;
+std::atomic<uint32_t> g_cast_pack{CAST_PACK_DEFAULT}, g_cast_grid{0};
 // the calling thread's last cast: its kernels by HIP events -- upload excluded, and so is the host's allocation of key / tf between
 // the scan and the gather (two spans: upload's end .. the scan's end, the gather's start .. its end)
 thread_local double g_kernel_ms = -1.0;
@@ -81,7 +96,7 @@ struct SortArgs {
     uint32_t *tmp_tf, *counts;
 };
 
-// element j of the wave's document: lane j's registers (every lane of the wave calls with the same j)
+// element j of the wave's document: lane j's registers (every lane of the wave calls, cast_wave_kernel's with the same j)
 struct LaneAt {
     Key k;
     uint32_t c;
@@ -112,6 +127,55 @@ __global__ void __launch_bounds__(WG) cast_wave_kernel(SortArgs a, const uint32_
             a.tmp_tf[b + rank] = sum;
         }
         if (lane == 0) a.counts[d] = __popcll(heads);
+    }
+}
+
+// the wave class, several documents a wave: entry s of the host's plan is a run of consecutive documents with at most 64 lexemes
+// between them, one lane a lexeme.  A lane finds its document among the run's bounds of doc_lex; the rank-and-merge runs in the whole
+// wave at once, every lane against the elements of its own document only (cast_lane.h), in as many steps as the run's longest document
+// has lexemes.  FUSED: the lanes intern their own lexemes -- the batch
+// has no document of another class, nobody else needs the keys, they never reach HBM -- with the chaining-value stack in LDS, one
+// column a thread of the block (cast_intern_kernel's).  Otherwise a.keys is read.
+struct BoundAt {
+    uint32_t bound;  // lane j: where document j of the run begins, as a lane
+    __device__ uint32_t operator()(uint32_t j) const { return __shfl(bound, int(j)); }
+};
+template <bool FUSED>
+__global__ void __launch_bounds__(WG) cast_pack_kernel(SortArgs a, const PackEntry *plan, uint32_t n_plan, Seed seed, const uint32_t *pool,
+                                                       const uint64_t *lex_off) {
+    extern __shared__ uint32_t cv_stack[];
+    const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t s = wave; s < n_plan; s += n_waves) {
+        const PackEntry e = plan[s];
+        const uint32_t b = a.doc_lex[e.first], n = a.doc_lex[e.first + e.count] - b;  // n <= 64, e.count in 1 .. 64
+        const BoundAt bound{lane < e.count ? a.doc_lex[e.first + lane] - b : n};
+        const uint32_t doc = lane_document(bound, e.count, lane);  // (of the run; lanes at and beyond n get one they do not use)
+        const uint32_t next = bound((lane + 1u) & 63u);
+        const uint32_t sb = bound(doc), se_in = bound((doc + 1u) & 63u), se = doc + 1u < e.count ? se_in : n;
+        uint32_t longest = lane < e.count ? (lane + 1u < e.count ? next : n) - bound.bound : 0u;  // lane j < count: document j's lexemes
+#pragma unroll
+        for (int x = 32; x > 0; x >>= 1) longest = max(longest, uint32_t(__shfl_xor(longest, x)));
+        const bool mine = lane < n;
+        Key k{0, 0};
+        if (mine) {
+            if constexpr (FUSED) {
+                const uint64_t begin = lex_off[b + lane];
+                k = intern_lane(seed.w, WordLoad{pool}, begin, lex_off[b + lane + 1] - begin, cv_stack + threadIdx.x, blockDim.x);
+            } else {
+                k = a.keys[b + lane];
+            }
+        }
+        const LaneAt at{k, mine ? a.lex_count[b + lane] : 0u};
+        uint32_t sum;
+        const bool head = seg_head_and_sum(at, longest, lane, at.k, sb, se, sum) && mine;
+        const ull heads = __ballot(head);
+        const uint32_t rank = seg_rank_of(at, MaskHead{heads}, longest, lane, at.k, sb, se);
+        if (head) {
+            a.tmp_key[b + sb + rank] = at.k;
+            a.tmp_tf[b + sb + rank] = sum;
+        }
+        // lane j < count: document j of the run is lanes bound .. next (the last one ends at n)
+        if (lane < e.count) a.counts[e.first + lane] = __popcll(heads & lane_span(bound.bound, lane + 1u < e.count ? next : n));
     }
 }
 
@@ -337,6 +401,56 @@ int check_documents(bool has_seed, const uint8_t *bytes, const uint64_t *lex_off
     return has_seed ? VBM25_OK : lexin::check_pool(false, bytes, lex_off, s->n_lex, "cast", &s->n_bytes, &s->longest_lexeme);
 }
 
+// the most temporary storage hipcub asks for in one cast: the scan of n_docs + 1 counts and, with n_gen_el elements in the general
+// class, its sorts and scans
+int cast_cub_bytes(uint32_t n_docs, uint32_t n_gen_el, hipStream_t st, size_t *out) {
+    size_t cub_bytes = 0, tb = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
+                                            (ull *)nullptr, int(n_docs + 1), st));
+    cub_bytes = std::max(cub_bytes, tb);
+    if (n_gen_el) {
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                  int(n_gen_el), 0, 64, st));
+        cub_bytes = std::max(cub_bytes, tb);
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n_gen_el), st));
+        cub_bytes = std::max(cub_bytes, tb);
+        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, int(n_gen_el), st));
+        cub_bytes = std::max(cub_bytes, tb);
+    }
+    *out = cub_bytes;
+    return VBM25_OK;
+}
+
+// the general class of one cast, enqueued: g.n_el > 0 elements, `grid` workgroups for its own kernels
+int enqueue_general(hipStream_t st, const GenArgs &g, void *cub, size_t cub_bytes, uint32_t grid) {
+    const uint32_t n_gen = g.n_gen, n_gen_el = g.n_el;
+    int slot_bits = 1;
+    while (slot_bits < 32 && (uint64_t(n_gen - 1) >> slot_bits)) ++slot_bits;
+    size_t tb = cub_bytes;
+    gen_fill_kernel<<<grid, WG, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, 64, st));
+    gen_key_high_kernel<<<grid, WG, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    tb = cub_bytes;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, tb, g.ka, g.kb, g.vb, g.va, int(n_gen_el), 0, 64, st));
+    gen_key_slot_kernel<<<grid, WG, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    tb = cub_bytes;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, slot_bits, st));
+    gen_flag_kernel<<<grid, WG, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    tb = cub_bytes;
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub, tb, g.va, g.slot, int(n_gen_el), st));
+    tb = cub_bytes;
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub, tb, g.ka, g.prefix, int(n_gen_el), st));
+    gen_head_pos_kernel<<<grid, WG, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    gen_emit_kernel<<<grid, WG, 0, st>>>(g);
+    HIP_TRY(hipGetLastError());
+    return VBM25_OK;
+}
+
 uint64_t handle_bytes(const vbm25_documents *h) {
     uint64_t n = 0;
     for (const HbmArray *a : {&h->d_start, &h->d_key, &h->d_tf, &h->d_length, &h->d_fieldnorm, &h->d_payload}) n += a->bytes;
@@ -409,18 +523,7 @@ int documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, cons
     if (total > o_bytes + sh.n_bytes) std::memset(staged + o_bytes + sh.n_bytes, 0, total - o_bytes - sh.n_bytes);
 
     size_t cub_bytes = 0, tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
-                                            (ull *)nullptr, int(n_docs + 1), st.s));
-    cub_bytes = std::max(cub_bytes, tb);
-    if (n_gen_el) {
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                  int(n_gen_el), 0, 64, st.s));
-        cub_bytes = std::max(cub_bytes, tb);
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n_gen_el), st.s));
-        cub_bytes = std::max(cub_bytes, tb);
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const ull *)nullptr, (ull *)nullptr, int(n_gen_el), st.s));
-        cub_bytes = std::max(cub_bytes, tb);
-    }
+    if (int rc = cast_cub_bytes(n_docs, n_gen_el, st.s, &cub_bytes)) return rc;
     HIP_TRY(in.alloc(total));
     HIP_TRY(keys.alloc(16ull * n_lex));
     HIP_TRY(tmp_key.alloc(16ull * n_lex));
@@ -467,31 +570,7 @@ int documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, cons
     if (n_gen_el) {
         const GenArgs g{sa, d_list + n_wave + n_group, d_goff, n_gen, n_gen_el, g_src.as<uint32_t>(), g_slot.as<uint32_t>(), g_ka.as<ull>(), g_kb.as<ull>(),
                         g_va.as<uint32_t>(), g_vb.as<uint32_t>(), g_prefix.as<ull>(), g_head_pos.as<uint32_t>()};
-        const uint32_t grid = grid_for(n_gen_el, WG, MAX_GRID);
-        int slot_bits = 1;
-        while (slot_bits < 32 && (uint64_t(n_gen - 1) >> slot_bits)) ++slot_bits;
-        gen_fill_kernel<<<grid, WG, 0, st.s>>>(g);
-        HIP_TRY(hipGetLastError());
-        tb = cub_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, 64, st.s));
-        gen_key_high_kernel<<<grid, WG, 0, st.s>>>(g);
-        HIP_TRY(hipGetLastError());
-        tb = cub_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.vb, g.va, int(n_gen_el), 0, 64, st.s));
-        gen_key_slot_kernel<<<grid, WG, 0, st.s>>>(g);
-        HIP_TRY(hipGetLastError());
-        tb = cub_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, tb, g.ka, g.kb, g.va, g.vb, int(n_gen_el), 0, slot_bits, st.s));
-        gen_flag_kernel<<<grid, WG, 0, st.s>>>(g);
-        HIP_TRY(hipGetLastError());
-        tb = cub_bytes;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.va, g.slot, int(n_gen_el), st.s));
-        tb = cub_bytes;
-        HIP_TRY(hipcub::DeviceScan::InclusiveSum(cub.p, tb, g.ka, g.prefix, int(n_gen_el), st.s));
-        gen_head_pos_kernel<<<grid, WG, 0, st.s>>>(g);
-        HIP_TRY(hipGetLastError());
-        gen_emit_kernel<<<grid, WG, 0, st.s>>>(g);
-        HIP_TRY(hipGetLastError());
+        if (int rc = enqueue_general(st.s, g, cub.p, cub_bytes, grid_for(n_gen_el, WG, MAX_GRID))) return rc;
     }
     tb = cub_bytes;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub.p, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(counts.as<uint32_t>(), WidenU32()),
@@ -619,11 +698,386 @@ int build_documents(const vbm25_documents *h, double k1, double b, vbm25_device_
     return VBM25_OK;
 }
 
+
+// ---- the caster: a ring of slots that keep everything a cast needs ----
+// what one batch's staged block holds and where (every part on a multiple of 16 bytes).  The one layout serves a batch (its own
+// numbers) and the slot's capacity (the caster's maxima): every offset and the total grow with every number.
+struct StageLayout {
+    size_t o_doc, o_off, o_cnt, o_list, o_goff, o_fn, o_pay, o_plan, o_bytes, total;
+    StageLayout(uint64_t n_docs, uint64_t n_lex, uint64_t n_gen, uint64_t n_plan, uint64_t n_bytes) {
+        size_t at = 0;
+        auto take = [&](size_t n) {
+            const size_t o = at;
+            at = align_up(at + n, 16);
+            return o;
+        };
+        o_doc = take(4 * (n_docs + 1));
+        o_off = take(8 * (n_lex + 1));
+        o_cnt = take(4 * n_lex);
+        o_list = take(4 * n_docs);
+        o_goff = take(4 * (n_gen + 1));
+        o_fn = take(4 * 256);
+        o_pay = take(6 * n_docs);
+        o_plan = take(sizeof(PackEntry) * n_plan);
+        o_bytes = take(n_bytes);
+        total = at;
+    }
+};
+
+struct CastSlot {
+    hipStream_t stream = nullptr;
+    hipEvent_t start = nullptr, done = nullptr;
+    uint8_t *stage = nullptr;    // pinned: the staged block of one batch
+    ull *n_elements = nullptr;   // pinned: start[n_docs], copied back behind the scan
+    HbmArray in, keys, tmp_key, tmp_tf, counts, cub, g_src, g_slot, g_ka, g_kb, g_va, g_vb, g_prefix, g_head_pos;
+    vbm25_documents docs;        // the result arrays, at the caster's capacities; what collect hands out
+    uint32_t launched = 0;       // LAUNCHED_* of the slot's last batch
+};
+
+// the kernels a batch's lexemes and wave class went through, as vbm25_debug_caster_launched reports them
+enum : uint32_t { LAUNCHED_INTERN = 1, LAUNCHED_WAVE = 2, LAUNCHED_PACK = 4, LAUNCHED_PACK_FUSED = 8 };
+
+}  // namespace
+
+struct vbm25_caster {
+    int device = 0;
+    uint32_t depth = 0, max_docs = 0, max_lexemes = 0, max_long = 0;
+    uint64_t max_bytes = 0, device_bytes = 0, allocations = 0;
+    bool has_seed = false;
+    Seed seed{};
+    size_t in_capacity = 0, cub_bytes = 0;
+    CastSlot slots[16];
+    uint32_t head = 0, count = 0;  // the oldest slot in flight; slots in flight
+    int last_collected = -1;
+
+    // every allocation and creation of the handle goes through these: `allocations` is their number
+    hipError_t device_alloc(HbmArray &a, size_t n) {
+        ++allocations;
+        const hipError_t e = a.alloc(n);
+        if (e == hipSuccess) device_bytes += a.footprint();
+        return e;
+    }
+    hipError_t pinned_alloc(void **p, size_t n) {
+        ++allocations;
+        return hipHostMalloc(p, n ? n : 16, hipHostMallocDefault);
+    }
+    hipError_t stream_create(hipStream_t *st) {
+        ++allocations;
+        return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    }
+    hipError_t event_create(hipEvent_t *e) {
+        ++allocations;
+        return hipEventCreate(e);
+    }
+};
+
+namespace {
+
+int caster_create(int device, const uint8_t *seed32, uint32_t depth, uint32_t max_docs, uint32_t max_lexemes, uint64_t max_bytes,
+                  uint32_t max_long_lexemes, vbm25_caster **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (depth < 1 || depth > 16) return set_error(VBM25_ERR_INVALID, "depth %u is outside 1 .. 16", depth);
+    if (!max_docs || !max_lexemes) return set_error(VBM25_ERR_INVALID, "max_docs or max_lexemes is 0");
+    if (max_docs >= (1u << 31) - 1u || max_lexemes >= (1u << 31))
+        return set_error(VBM25_ERR_INVALID, "max_docs or max_lexemes is beyond one cast's limits (2^31 - 1 documents, 2^31 lexemes)");
+    if (max_long_lexemes > max_lexemes) return set_error(VBM25_ERR_INVALID, "max_long_lexemes %u exceeds max_lexemes %u", max_long_lexemes, max_lexemes);
+    if (max_bytes >= (1ull << 40)) return set_error(VBM25_ERR_INVALID, "max_bytes %llu is 2^40 or more", (unsigned long long)max_bytes);
+    if (int rc = use_cast_device(device)) return rc;
+    struct Guard {
+        vbm25_caster *c;
+        ~Guard() {
+            if (c) vbm25_caster_free(c);
+        }
+    } guard{new vbm25_caster};
+    vbm25_caster *c = guard.c;
+    c->device = device;
+    c->depth = depth;
+    c->max_docs = max_docs;
+    c->max_lexemes = max_lexemes;
+    c->max_bytes = max_bytes;
+    c->max_long = max_long_lexemes;
+    c->has_seed = seed32 != nullptr;
+    seed_words(seed32, &c->seed);
+    // (a batch has at most as many general-class documents and plan entries as documents)
+    c->in_capacity = StageLayout(max_docs, max_lexemes, max_docs, max_docs, max_bytes).total;
+    const uint64_t nd = max_docs, nl = max_lexemes, ng = max_long_lexemes;
+    for (uint32_t i = 0; i < depth; ++i) {
+        CastSlot &s = c->slots[i];
+        HIP_TRY(c->stream_create(&s.stream));
+        HIP_TRY(c->event_create(&s.start));
+        HIP_TRY(c->event_create(&s.done));
+        if (i == 0)
+            if (int rc = cast_cub_bytes(max_docs, max_long_lexemes, s.stream, &c->cub_bytes)) return rc;
+        HIP_TRY(c->pinned_alloc((void **)&s.stage, c->in_capacity));
+        HIP_TRY(c->pinned_alloc((void **)&s.n_elements, 8));
+        HIP_TRY(c->device_alloc(s.in, c->in_capacity));
+        HIP_TRY(c->device_alloc(s.keys, 16 * nl));
+        HIP_TRY(c->device_alloc(s.tmp_key, 16 * nl));
+        HIP_TRY(c->device_alloc(s.tmp_tf, 4 * nl));
+        HIP_TRY(c->device_alloc(s.counts, 4 * (nd + 1)));
+        HIP_TRY(c->device_alloc(s.cub, c->cub_bytes));
+        if (ng) {
+            HIP_TRY(c->device_alloc(s.g_src, 4 * ng));
+            HIP_TRY(c->device_alloc(s.g_slot, 4 * ng));
+            HIP_TRY(c->device_alloc(s.g_ka, 8 * ng));
+            HIP_TRY(c->device_alloc(s.g_kb, 8 * ng));
+            HIP_TRY(c->device_alloc(s.g_va, 4 * ng));
+            HIP_TRY(c->device_alloc(s.g_vb, 4 * ng));
+            HIP_TRY(c->device_alloc(s.g_prefix, 8 * ng));
+            HIP_TRY(c->device_alloc(s.g_head_pos, 4 * (ng + 1)));
+        }
+        s.docs.device = device;
+        s.docs.caster = c;
+        HIP_TRY(c->device_alloc(s.docs.d_start, 8 * (nd + 1)));
+        HIP_TRY(c->device_alloc(s.docs.d_key, 16 * nl));
+        HIP_TRY(c->device_alloc(s.docs.d_tf, 4 * nl));
+        HIP_TRY(c->device_alloc(s.docs.d_length, 4 * nd));
+        HIP_TRY(c->device_alloc(s.docs.d_fieldnorm, nd));
+        HIP_TRY(c->device_alloc(s.docs.d_payload, 6 * nd));
+    }
+    *out = c;
+    guard.c = nullptr;
+    return VBM25_OK;
+}
+
+int caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count, const uint32_t *doc_lex, uint32_t n_docs,
+                  const uint16_t *doc_payload) {
+    if (!c) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const uint32_t wave_max = g_wave_max.load(), group_max = g_group_max.load(), pack = g_cast_pack.load(), grid_cap = g_cast_grid.load();
+    Shape sh;
+    if (int rc = check_documents(c->has_seed, bytes, lex_off, lex_count, doc_lex, n_docs, &sh)) return rc;
+    if (c->count == c->depth) return set_error(VBM25_ERR_INVALID, "the caster's %u slots are all in flight: collect first", c->depth);
+    if (n_docs > c->max_docs) return set_error(VBM25_ERR_INVALID, "%u documents exceed the caster's max_docs %u", n_docs, c->max_docs);
+    if (sh.n_lex > c->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u lexemes exceed the caster's max_lexemes %u", sh.n_lex, c->max_lexemes);
+    if (sh.n_bytes > c->max_bytes)
+        return set_error(VBM25_ERR_INVALID, "%llu bytes exceed the caster's max_bytes %llu", (unsigned long long)sh.n_bytes, (unsigned long long)c->max_bytes);
+    // pass 1: the classes' sizes and the plan's
+    uint32_t n_class[3] = {0, 0, 0}, n_plan = 0, first_general = 0;
+    uint64_t gen_el = 0;
+    {
+        PackRun run;
+        PackEntry e;
+        for (uint32_t d = 0; d < n_docs; ++d) {
+            const uint32_t n = doc_lex[d + 1] - doc_lex[d];
+            const DocClass cl = doc_class(n, wave_max, group_max);
+            if (cl == CLASS_GENERAL && n && !gen_el) first_general = d;
+            if (cl == CLASS_GENERAL) gen_el += n;
+            ++n_class[cl];
+            n_plan += pack_step(run, d, n, cl == CLASS_WAVE, e) ? 1u : 0u;
+        }
+        n_plan += pack_flush(run, e) ? 1u : 0u;
+    }
+    if (gen_el > c->max_long) {
+        if (!c->max_long)
+            return set_error(VBM25_ERR_UNSUPPORTED, "document %u has %u lexemes: the caster was created with max_long_lexemes 0 and takes no document of the general class",
+                             first_general, doc_lex[first_general + 1] - doc_lex[first_general]);
+        return set_error(VBM25_ERR_INVALID, "%llu lexemes in documents of the general class exceed the caster's max_long_lexemes %u",
+                         (unsigned long long)gen_el, c->max_long);
+    }
+    const uint32_t n_lex = sh.n_lex, n_wave = n_class[0], n_group = n_class[1], n_gen = n_class[2], n_gen_el = uint32_t(gen_el);
+    if (int rc = use_device(c->device)) return rc;
+    CastSlot &s = c->slots[(c->head + c->count) % c->depth];
+    {  // (hipcub is asked again for this batch's sizes -- a question, nothing is enqueued: its answer for less is expected to be less)
+        size_t need = 0;
+        if (int rc = cast_cub_bytes(n_docs, n_gen_el, s.stream, &need)) return rc;
+        if (need > c->cub_bytes)
+            return set_error(VBM25_ERR_UNSUPPORTED, "hipcub asks for %zu bytes of temporary storage for this batch, the caster holds %zu", need, c->cub_bytes);
+    }
+    const StageLayout L(n_docs, n_lex, n_gen, n_plan, sh.n_bytes);
+    // pass 2: the lists, the general class's offsets and the plan, straight into the pinned block
+    uint8_t *const staged = s.stage;
+    std::memcpy(staged + L.o_doc, doc_lex, 4ull * (n_docs + 1ull));
+    std::memcpy(staged + L.o_off, lex_off, 8ull * (n_lex + 1ull));
+    if (n_lex) std::memcpy(staged + L.o_cnt, lex_count, 4ull * n_lex);
+    {
+        uint32_t *list = reinterpret_cast<uint32_t *>(staged + L.o_list), *goff = reinterpret_cast<uint32_t *>(staged + L.o_goff);
+        PackEntry *plan = reinterpret_cast<PackEntry *>(staged + L.o_plan);
+        uint32_t at[3] = {0, n_wave, n_wave + n_group}, n_goff = 0, n_done = 0, el = 0;
+        PackRun run;
+        PackEntry e;
+        goff[n_goff++] = 0;
+        for (uint32_t d = 0; d < n_docs; ++d) {
+            const uint32_t n = doc_lex[d + 1] - doc_lex[d];
+            const DocClass cl = doc_class(n, wave_max, group_max);
+            list[at[cl]++] = d;
+            if (cl == CLASS_GENERAL) goff[n_goff++] = (el += n);
+            if (pack_step(run, d, n, cl == CLASS_WAVE, e)) plan[n_done++] = e;
+        }
+        if (pack_flush(run, e)) plan[n_done++] = e;
+    }
+    std::memcpy(staged + L.o_fn, fieldnorm_lengths(), 4 * 256);
+    if (doc_payload && n_docs) std::memcpy(staged + L.o_pay, doc_payload, 6ull * n_docs);
+    if (sh.n_bytes) std::memcpy(staged + L.o_bytes, bytes, sh.n_bytes);
+    if (L.total > L.o_bytes + sh.n_bytes) std::memset(staged + L.o_bytes + sh.n_bytes, 0, L.total - L.o_bytes - sh.n_bytes);
+
+    hipStream_t st = s.stream;
+    vbm25_documents &h = s.docs;
+    uint8_t *d = s.in.as<uint8_t>();
+    // a HIP error from here on leaves the slot out of the ring but with work enqueued: wait for it before the refusal returns, so that
+    // the next submit, which takes this slot again, writes its pinned block under no copy in flight
+    struct Drain {
+        hipStream_t st;
+        bool armed;
+        ~Drain() {
+            if (armed) (void)hipStreamSynchronize(st);
+        }
+    } drain{st, true};
+    HIP_TRY(hipMemcpyAsync(d, staged, L.total, hipMemcpyHostToDevice, st));
+    if (doc_payload && n_docs) HIP_TRY(hipMemcpyAsync(h.d_payload.p, staged + L.o_pay, 6ull * n_docs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s.start, st));
+    HIP_TRY(hipMemsetAsync(s.counts.p, 0, 4ull * (n_docs + 1ull), st));
+    const uint32_t *d_doc = reinterpret_cast<const uint32_t *>(d + L.o_doc), *d_cnt = reinterpret_cast<const uint32_t *>(d + L.o_cnt),
+                   *d_list = reinterpret_cast<const uint32_t *>(d + L.o_list), *d_goff = reinterpret_cast<const uint32_t *>(d + L.o_goff),
+                   *d_fn = reinterpret_cast<const uint32_t *>(d + L.o_fn), *d_pool = reinterpret_cast<const uint32_t *>(d + L.o_bytes);
+    const uint64_t *d_off = reinterpret_cast<const uint64_t *>(d + L.o_off);
+    const PackEntry *d_plan = reinterpret_cast<const PackEntry *>(d + L.o_plan);
+    const SortArgs sa{s.keys.as<Key>(), d_cnt, d_doc, s.tmp_key.as<Key>(), s.tmp_tf.as<uint32_t>(), s.counts.as<uint32_t>()};
+    const uint32_t cap = grid_cap ? grid_cap : MAX_GRID;
+    const uint32_t levels = stack_levels(sh.longest_lexeme);
+    const bool fused = pack == 2 && n_lex && !n_group && !n_gen;  // (nobody but the packed waves needs the keys)
+    uint32_t launched = 0;  // (which of the intern's and the wave class's kernels this batch takes: vbm25_debug_caster_launched)
+    if (n_lex && !fused) {
+        launched |= LAUNCHED_INTERN;
+        const size_t lds = size_t(levels) * 8 * sizeof(uint32_t) * INTERN_THREADS;
+        cast_intern_kernel<<<std::min(INTERN_GRID, grid_for(n_lex, INTERN_THREADS, cap)), INTERN_THREADS, lds, st>>>(c->seed, d_pool, d_off, n_lex, s.keys.as<Key>());
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_wave && n_lex) {
+        if (fused) {  // a lexeme of several chunks: one wave a block, so that the stack (32 bytes a level a thread) fits the LDS
+            const uint32_t threads = levels ? INTERN_THREADS : WG;
+            launched |= LAUNCHED_PACK_FUSED;
+            cast_pack_kernel<true><<<grid_for(n_plan, threads / 64, cap), threads, size_t(levels) * 8 * sizeof(uint32_t) * threads, st>>>(sa, d_plan, n_plan, c->seed,
+                                                                                                                                   d_pool, d_off);
+        } else if (pack) {
+            launched |= LAUNCHED_PACK;
+            cast_pack_kernel<false><<<grid_for(n_plan, WG / 64, cap), WG, 0, st>>>(sa, d_plan, n_plan, c->seed, d_pool, d_off);
+        } else {
+            launched |= LAUNCHED_WAVE;
+            cast_wave_kernel<<<grid_for(n_wave, WG / 64, cap), WG, 0, st>>>(sa, d_list, n_wave);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_group && n_lex) {
+        cast_group_kernel<<<grid_for(n_group, 1, cap), WG, 0, st>>>(sa, d_list + n_wave, n_group);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_gen_el) {
+        const GenArgs g{sa, d_list + n_wave + n_group, d_goff, n_gen, n_gen_el, s.g_src.as<uint32_t>(), s.g_slot.as<uint32_t>(), s.g_ka.as<ull>(),
+                        s.g_kb.as<ull>(), s.g_va.as<uint32_t>(), s.g_vb.as<uint32_t>(), s.g_prefix.as<ull>(), s.g_head_pos.as<uint32_t>()};
+        if (int rc = enqueue_general(st, g, s.cub.p, c->cub_bytes, grid_for(n_gen_el, WG, cap))) return rc;
+    }
+    size_t tb = c->cub_bytes;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.cub.p, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(s.counts.as<uint32_t>(), WidenU32()),
+                                            h.d_start.as<ull>(), int(n_docs + 1), st));
+    // (key / tf have room for every lexeme: the gather goes straight behind the scan, and the number of elements travels home beside it)
+    HIP_TRY(hipMemcpyAsync(s.n_elements, h.d_start.as<ull>() + n_docs, 8, hipMemcpyDeviceToHost, st));
+    if (n_docs) {
+        cast_gather_kernel<<<grid_for(n_docs, WG / 64, cap), WG, 0, st>>>(s.tmp_key.as<Key>(), s.tmp_tf.as<uint32_t>(), d_doc, h.d_start.as<ull>(), n_docs, d_fn,
+                                                                          h.d_key.as<Key>(), h.d_tf.as<uint32_t>(), h.d_length.as<uint32_t>(),
+                                                                          h.d_fieldnorm.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(s.done, st));
+    h.n_docs = n_docs;
+    h.n_elements = 0;  // (known at collect)
+    h.has_payload = doc_payload != nullptr;
+    s.launched = launched;
+    drain.armed = false;
+    ++c->count;
+    return VBM25_OK;
+}
+
+int caster_collect(vbm25_caster *c, const vbm25_documents **out) {
+    if (!out) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (!c) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!c->count) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the caster");
+    if (int rc = use_device(c->device)) return rc;
+    CastSlot &s = c->slots[c->head];
+    HIP_TRY(hipEventSynchronize(s.done));
+    s.docs.n_elements = *s.n_elements;
+    *out = &s.docs;
+    c->last_collected = int(c->head);
+    c->head = (c->head + 1) % c->depth;
+    --c->count;
+    return VBM25_OK;
+}
+
+// ---- vbm25_documents_extend ----
+__global__ void __launch_bounds__(WG) extend_start_kernel(const ull *src_start, uint32_t n_src, ull base, ull *dst_start_at) {
+    for (uint32_t i = blockIdx.x * WG + threadIdx.x; i < n_src; i += gridDim.x * WG) dst_start_at[i + 1] = src_start[i + 1] + base;
+}
+
+int documents_extend(vbm25_documents *dst, const vbm25_documents *src) {
+    if (!dst || !src) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (dst == src) return set_error(VBM25_ERR_INVALID, "dst and src are the same handle");
+    if (dst->caster) return set_error(VBM25_ERR_INVALID, "dst belongs to a caster: only an owned handle is extended");
+    if (dst->device != src->device) return set_error(VBM25_ERR_INVALID, "dst is on device %d, src on device %d", dst->device, src->device);
+    if (dst->has_payload != src->has_payload) return set_error(VBM25_ERR_INVALID, "one handle has payloads and the other has none");
+    const uint64_t nd = uint64_t(dst->n_docs) + src->n_docs, ne = dst->n_elements + src->n_elements;
+    if (nd >= (1ull << 31) - 1ull) return set_error(VBM25_ERR_UNSUPPORTED, "%llu documents: one handle takes fewer than 2^31 - 1", (unsigned long long)nd);
+    if (ne >= (1ull << 31)) return set_error(VBM25_ERR_UNSUPPORTED, "%llu elements: one handle takes fewer than 2^31", (unsigned long long)ne);
+    if (int rc = use_cast_device(dst->device)) return rc;
+    if (!src->n_docs) return VBM25_OK;
+    // per array: (the array, the bytes in use, the bytes needed, src's array, src's bytes)
+    struct Part {
+        HbmArray *a;
+        uint64_t used, need;
+        const void *from;
+        uint64_t n_from;
+    } parts[6] = {{&dst->d_start, 8ull * (dst->n_docs + 1ull), 8 * (nd + 1), nullptr, 0},
+                  {&dst->d_key, 16 * dst->n_elements, 16 * ne, src->d_key.p, 16 * src->n_elements},
+                  {&dst->d_tf, 4 * dst->n_elements, 4 * ne, src->d_tf.p, 4 * src->n_elements},
+                  {&dst->d_length, 4ull * dst->n_docs, 4 * nd, src->d_length.p, 4ull * src->n_docs},
+                  {&dst->d_fieldnorm, dst->n_docs, nd, src->d_fieldnorm.p, src->n_docs},
+                  {&dst->d_payload, 6ull * dst->n_docs, 6 * nd, src->d_payload.p, 6ull * src->n_docs}};
+    const int n_parts = dst->has_payload ? 6 : 5;
+    HbmArray grown[6];
+    Stream st;  // (of the call's own, as the cast's)
+    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    Quiesce quiesce(st.s);
+    // every larger array first: a failure so far leaves dst as it was.  Capacities at least double, so appending n chunks copies O(n) bytes.
+    for (int i = 0; i < n_parts; ++i) {
+        const Part &p = parts[i];
+        if (p.need <= p.a->bytes) continue;
+        HIP_TRY(grown[i].alloc(std::max<uint64_t>(p.need, 2 * uint64_t(p.a->bytes))));
+    }
+    for (int i = 0; i < n_parts; ++i) {
+        const Part &p = parts[i];
+        if (grown[i].p && p.used) HIP_TRY(hipMemcpyAsync(grown[i].p, p.a->p, p.used, hipMemcpyDeviceToDevice, st.s));
+        uint8_t *to = static_cast<uint8_t *>(grown[i].p ? grown[i].p : p.a->p);
+        if (p.from && p.n_from) HIP_TRY(hipMemcpyAsync(to + p.used, p.from, p.n_from, hipMemcpyDeviceToDevice, st.s));
+    }
+    ull *start = static_cast<ull *>(grown[0].p ? grown[0].p : dst->d_start.p);
+    extend_start_kernel<<<grid_for(src->n_docs, WG, MAX_GRID), WG, 0, st.s>>>(src->d_start.as<ull>(), src->n_docs, dst->n_elements, start + dst->n_docs);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st.s));
+    for (int i = 0; i < n_parts; ++i)
+        if (grown[i].p) {
+            std::swap(grown[i].p, parts[i].a->p);  // (the old array goes with `grown`)
+            std::swap(grown[i].bytes, parts[i].a->bytes);
+        }
+    dst->n_docs = uint32_t(nd);
+    dst->n_elements = ne;
+    return VBM25_OK;
+}
+
 }  // namespace
 
 namespace vbm25 {
 int cast_tuning_set(const char *name, long long value) {
     const std::string n(name);
+    if (n == "cast_pack") {
+        if (value < 0 || value > 2) return set_error(VBM25_ERR_INVALID, "%s %lld is outside 0 .. 2", name, value);
+        g_cast_pack.store(uint32_t(value));
+        return VBM25_OK;
+    }
+    if (n == "cast_grid") {
+        if (value < 0 || value > (long long)MAX_GRID) return set_error(VBM25_ERR_INVALID, "%s %lld is outside 0 .. %u", name, value, MAX_GRID);
+        g_cast_grid.store(uint32_t(value));
+        return VBM25_OK;
+    }
     std::atomic<uint32_t> &slot = n == "cast_wave_max" ? g_wave_max : g_group_max;
     const uint32_t bound = n == "cast_wave_max" ? CAST_WAVE_MAX : CAST_GROUP_MAX;
     if (value < 0 || value > (long long)bound) return set_error(VBM25_ERR_INVALID, "%s %lld is outside 0 .. %u", name, value, bound);
@@ -633,6 +1087,8 @@ int cast_tuning_set(const char *name, long long value) {
 void cast_tuning_reset() {
     g_wave_max.store(CAST_WAVE_MAX);
     g_group_max.store(CAST_GROUP_MAX);
+    g_cast_pack.store(CAST_PACK_DEFAULT);
+    g_cast_grid.store(0);
 }
 }  // namespace vbm25
 
@@ -658,13 +1114,75 @@ int vbm25_documents_download(const vbm25_documents *h, vbm25_growing **csr, uint
 uint64_t vbm25_documents_device_bytes(const vbm25_documents *h) { return h ? handle_bytes(h) : 0; }
 
 void vbm25_documents_free(vbm25_documents *h) {
-    if (!h) return;
+    if (!h || h->caster) return;  // (a collected handle is its caster's)
     (void)hipSetDevice(h->device);
     delete h;
 }
 
 int vbm25_device_segment_build_documents(const vbm25_documents *h, double k1, double b, vbm25_device_segment **out) {
     return guarded([&] { return build_documents(h, k1, b, out); });
+}
+
+int vbm25_documents_extend(vbm25_documents *dst, const vbm25_documents *src) {
+    return guarded([&] { return documents_extend(dst, src); });
+}
+
+int vbm25_caster_create(int device, const uint8_t *seed32, uint32_t depth, uint32_t max_docs, uint32_t max_lexemes, uint64_t max_bytes,
+                        uint32_t max_long_lexemes, vbm25_caster **out) {
+    return guarded([&] { return caster_create(device, seed32, depth, max_docs, max_lexemes, max_bytes, max_long_lexemes, out); });
+}
+
+void vbm25_caster_free(vbm25_caster *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    for (CastSlot &s : c->slots)
+        if (s.stream) (void)hipStreamSynchronize(s.stream);  // nothing is freed under a kernel or a copy in flight
+    for (CastSlot &s : c->slots) {
+        if (s.stage) (void)hipHostFree(s.stage);
+        if (s.n_elements) (void)hipHostFree(s.n_elements);
+        if (s.start) (void)hipEventDestroy(s.start);
+        if (s.done) (void)hipEventDestroy(s.done);
+        if (s.stream) (void)hipStreamDestroy(s.stream);
+    }
+    delete c;
+}
+
+uint64_t vbm25_caster_device_bytes(const vbm25_caster *c) { return c ? c->device_bytes : 0; }
+
+int vbm25_caster_info(const vbm25_caster *c, uint32_t *depth, int *device, uint64_t *allocations) {
+    if (!c) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (depth) *depth = c->depth;
+    if (device) *device = c->device;
+    if (allocations) *allocations = c->allocations;
+    return VBM25_OK;
+}
+
+int vbm25_caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *lex_count, const uint32_t *doc_lex,
+                        uint32_t n_docs, const uint16_t *doc_payload) {
+    return guarded([&] { return caster_submit(c, bytes, lex_off, lex_count, doc_lex, n_docs, doc_payload); });
+}
+
+int vbm25_caster_collect(vbm25_caster *c, const vbm25_documents **out) {
+    return guarded([&] { return caster_collect(c, out); });
+}
+
+int vbm25_caster_in_flight(const vbm25_caster *c) { return c ? int(c->count) : 0; }
+
+// tools/caster_cost.py: the device time of the last collected batch's kernels (upload excluded), by the slot's HIP events.  Not in the header.
+int vbm25_debug_caster_kernel_ms(vbm25_caster *c, double *ms) {
+    if (!c || !ms || c->last_collected < 0) return set_error(VBM25_ERR_INVALID, "no collected batch");
+    float f = 0;
+    HIP_TRY(hipEventElapsedTime(&f, c->slots[c->last_collected].start, c->slots[c->last_collected].done));
+    *ms = f;
+    return VBM25_OK;
+}
+
+// tests/test_gpu_caster.py: which kernels the last collected batch's lexemes and wave class went through -- 1 cast_intern_kernel,
+// 2 cast_wave_kernel, 4 cast_pack_kernel with keys from HBM, 8 cast_pack_kernel interning in its lanes.  Not in the header.
+int vbm25_debug_caster_launched(const vbm25_caster *c, uint32_t *mask) {
+    if (!c || !mask || c->last_collected < 0) return set_error(VBM25_ERR_INVALID, "no collected batch");
+    *mask = c->slots[c->last_collected].launched;
+    return VBM25_OK;
 }
 
 // tools/cast_cost.py: the device time of the calling thread's last cast's kernels (upload and the host's allocation in front of the

@@ -40,12 +40,15 @@ struct vbm25_device_vacuum {
 
 // Cast documents in HBM (vbm25_documents_cast, csrc/cast.hip): the CSR cast_tsvector_to_document makes of a batch of tsvectors -- start
 // (n_docs + 1, start[0] == 0), per element the key and the tf (keys strictly ascending inside a document), per document the length, its
-// fieldnorm code and, when the caller gave them, the payload.  Only ever read after it is made.
+// fieldnorm code and, when the caller gave them, the payload.  Only ever read after it is made, except by vbm25_documents_extend, which
+// appends to an owned handle.  The arrays may be larger than the documents need (a caster's slot, a handle that was extended): their
+// `bytes` are capacities, and no consumer reads them for a length.  caster: the vbm25_caster whose slot the handle is (NULL: owned).
 struct vbm25_documents {
     int device = 0;
     uint32_t n_docs = 0;
     uint64_t n_elements = 0;
     bool has_payload = false;
+    const void *caster = nullptr;
     vbm25::HbmArray d_start, d_key, d_tf, d_length, d_fieldnorm, d_payload;
 };
 

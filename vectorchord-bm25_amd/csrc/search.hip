@@ -1307,7 +1307,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg; cast_wave_max and cast_group_max (read
-// at the start of each vbm25_documents_cast); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
+// at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); rerank_part and rerank_buf (read at the start of each scorer call).
 int vbm25_tuning_set(const char *name, long long value) {
     if (!name) return set_error(VBM25_ERR_INVALID, "NULL argument");
@@ -1342,7 +1342,7 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "win_cut2") g_tune.win_cut2 = int(std::min<long long>(std::max<long long>(value, 2), 999));
     else if (n == "win_fuse") g_tune.win_fuse = value != 0;
     else if (n == "id16_max_blocks") g_tune.id16_max_blocks = (uint32_t)std::min<long long>(std::max(2ll, value), 0x00ffffffll);
-    else if (n == "cast_wave_max" || n == "cast_group_max") {  // (vbm25_documents_cast's class bounds: cast.hip keeps and reads them)
+    else if (n == "cast_wave_max" || n == "cast_group_max" || n == "cast_pack" || n == "cast_grid") {  // (the cast's class bounds and the caster's kernel choice and grid cap: cast.hip keeps and reads them)
         if (int rc = vbm25::cast_tuning_set(name, value)) return rc;
     }
     else if (n == "eval_grid") {  // (the grid cap of vbm25_documents_bind / vbm25_evaluate_documents: evaluate.hip keeps and reads it)

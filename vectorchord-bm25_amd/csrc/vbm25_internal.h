@@ -85,7 +85,7 @@ int index_vocabulary(const vbm25_index *ix, int *device, uint32_t *n_terms, cons
 // the device half of vbm25_growing_upload; synchronous, the arrays may be freed when it returns
 int growing_from_device_arrays(vbm25_index *ix, const GrowingDeviceArrays &a, vbm25_device_growing **out);
 // vbm25_tuning_set's cast_wave_max / cast_group_max (cast.hip keeps them: the class bounds of vbm25_documents_cast, 0 = class off,
-// values over the built-in bounds refused) and their reset
+// values over the built-in bounds refused), cast_pack (0 .. 2) and cast_grid (0 .. 2048) of vbm25_caster_submit, and their reset
 int cast_tuning_set(const char *name, long long value);
 void cast_tuning_reset();
 // What the evaluate operator on bound documents (evaluate.hip) reads of a resolver (resolve.hip fills it in): its index, the
