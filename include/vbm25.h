@@ -682,7 +682,9 @@ int vbm25_filter_read(const vbm25_filter *, uint32_t i, int growing, uint64_t *w
 /* VACUUM's inputs read on the device.  A vbm25_device_vacuum holds a relation's compaction inputs in HBM on the index's device: the
  * sealed documents' deleted flags as ceil(n_docs / 64) words in DELETED polarity (what vbm25_sealed_deleted_from_pages gives, bits at
  * or beyond n_docs zero) and the growing segment's CSR (what vbm25_growing_from_pages gives: the six arrays of vbm25_growing_desc,
- * keys the sealed vocabulary lacks included).  It is only ever read: one handle serves any number of compactions and remaps.
+ * keys the sealed vocabulary lacks included).  It is only ever read, with one exception: vbm25_device_vacuum_bulkdelete (below) sets
+ * deletion flags in it and must not run beside a compaction or a remap that reads the handle.  Otherwise one handle serves any number
+ * of compactions and remaps.
  *   vbm25_device_vacuum_from_pages   index: the resident index of the relation's sealed segment (its device, its document count).
  *     The host reads Meta and Jump once and follows the documents tape, then the vectors tape, by Opaque.next: one header check and
  *     one copy into pinned staging per page, uploaded in chunks while the walk goes on; read_page is called once per page, from the
@@ -718,6 +720,59 @@ int vbm25_device_vacuum_read(const vbm25_device_vacuum *, uint64_t *sealed_delet
 void vbm25_device_vacuum_free(vbm25_device_vacuum *);
 int vbm25_index_maintain_device(const vbm25_index *index, const vbm25_device_vacuum *in, uint32_t *relabel, vbm25_device_segment **out);
 int vbm25_filter_remap_device(const vbm25_filter *old, const vbm25_device_vacuum *in, vbm25_index *new_index, vbm25_filter **out);
+
+/* TID sets (csrc/tid.hip): which documents does a set of heap rows refer to?  bulkdelete.rs:20-112 calls callback(payload) for every
+ * growing and every sealed document and search.rs:122,230 filter(payload) the same way; what PostgreSQL holds in both cases is a set
+ * of TIDs (VACUUM's dead-TID store, the TID bitmap of a bitmap heap scan).  A vbm25_tid_set keeps such a set in the HBM of one device
+ * as sorted distinct 48-bit keys -- payload[0] << 32 | payload[1] << 16 | payload[2], so ascending keys are ascending ctids
+ * (fetcher.rs:218-232) -- with a directory of evenly spaced keys; one kernel answers, for every document of a payload plane, one bit
+ * in the packing of the filters and the deletion words (bit d % 64 of word d / 64), a wave of 64 lanes one word with one ballot.
+ *   vbm25_tid_set_create   tids: n x 3 uint16_t in any order, repeats allowed; uploaded, packed, sorted and de-duplicated on the
+ *             device.  n == 0 is a valid empty set that matches nothing (tids may then be NULL).  n > 2^32 - 1 -> VBM25_ERR_UNSUPPORTED,
+ *             checked before tids is read or anything is allocated; NULL out, or NULL tids with n > 0 -> VBM25_ERR_INVALID; no HIP
+ *             device -> VBM25_ERR_DEVICE.  A failure leaves *out NULL and nothing allocated.  Synchronous.  The set is only ever read
+ *             afterwards: one set serves any number of calls and threads.
+ *   vbm25_tid_set_info     the distinct TIDs and the device (either pointer may be NULL).
+ *   vbm25_tid_set_read     the distinct TIDs back on the host, n_unique x 3, ascending.
+ *   vbm25_tid_set_device_bytes   what the set holds of the device (0 for NULL).
+ *   vbm25_tid_set_free     NULL is a no-op.
+ *   vbm25_tid_set_match_index / _match_growing   words: host memory for ceil(n / 64) words over the index's n_docs sealed documents
+ *             (the segment's n_grow growing documents); bit = 1: the document's payload is in the set; bits at or beyond n are zero.
+ *             *n_match: the documents matched.  Either output pointer may be NULL.  A growing document's payload is matched whether
+ *             or not the document is deleted.  0 documents give zero words and VBM25_OK.  A set on another device than the index's
+ *             (the segment's) -> VBM25_ERR_INVALID.  Synchronous.
+ *   vbm25_filter_set_tids  sealed bitmap i becomes the match words of the filter's index, complemented below n_docs when invert != 0:
+ *             exactly what vbm25_filter_update(f, i, words) with those words would leave, and no bitmap crosses the host link.
+ *             gs == NULL: the growing bitmaps are untouched.  gs != NULL: growing bitmap i is set likewise from the segment's
+ *             payloads (bits at or beyond n_grow stay zero); the filter must hold growing bitmaps of that upload at its current
+ *             document count, else the codes of vbm25_batch_set_filter: VBM25_ERR_UNSUPPORTED without growing bitmaps,
+ *             VBM25_ERR_INVALID for another upload or a stale count after an append.  i >= the filter's bitmaps, or a set on another
+ *             device -> VBM25_ERR_INVALID.  Every refusal leaves both bitmaps as they were.  Synchronous: it waits for the device
+ *             first, as vbm25_filter_extend_growing does.
+ *   vbm25_device_growing_delete_tids   afterwards the segment searches exactly as after vbm25_device_growing_delete of every g whose
+ *             payload is in the set.  *n_match (may be NULL): the documents matched -- the device does not know which of them were
+ *             deleted already, so this is not the number of documents newly deleted.  Synchronous; the threading rule of
+ *             vbm25_device_growing_delete.  A set on another device -> VBM25_ERR_INVALID.
+ *   vbm25_device_vacuum_bulkdelete   bulkdelete.rs on the handle: the sealed deleted words |= the match of index's payloads, the
+ *             growing deleted flags |= the match of the handle's growing payloads; the handle's counts follow.  *n_sealed_new /
+ *             *n_grow_new (either may be NULL): the documents that were live before and are deleted now (the reference skips tuples
+ *             already deleted).  index must be the one the handle was read for: another device or document count ->
+ *             VBM25_ERR_INVALID, as is a set on another device; a refusal leaves the handle as it was.  Every allocation comes
+ *             before the first word changes.  Afterwards vbm25_device_vacuum_read, _info, vbm25_index_maintain_device and
+ *             vbm25_filter_remap_device see the new flags.  The one call that writes a vbm25_device_vacuum: it must not run beside
+ *             a compaction or a remap that reads the handle.  The flags are not written back into page images. */
+typedef struct vbm25_tid_set vbm25_tid_set;
+int vbm25_tid_set_create(int device, const uint16_t *tids, uint64_t n, vbm25_tid_set **out);
+int vbm25_tid_set_info(const vbm25_tid_set *, uint64_t *n_unique, int *device);
+int vbm25_tid_set_read(const vbm25_tid_set *, uint16_t *tids);
+uint64_t vbm25_tid_set_device_bytes(const vbm25_tid_set *);
+void vbm25_tid_set_free(vbm25_tid_set *);
+int vbm25_tid_set_match_index(const vbm25_tid_set *, const vbm25_index *, uint64_t *words, uint32_t *n_match);
+int vbm25_tid_set_match_growing(const vbm25_tid_set *, const vbm25_device_growing *, uint64_t *words, uint32_t *n_match);
+int vbm25_filter_set_tids(vbm25_filter *, uint32_t i, const vbm25_tid_set *, int invert, const vbm25_device_growing *gs);
+int vbm25_device_growing_delete_tids(vbm25_device_growing *, const vbm25_tid_set *, uint32_t *n_match);
+int vbm25_device_vacuum_bulkdelete(vbm25_device_vacuum *, const vbm25_index *, const vbm25_tid_set *, uint32_t *n_sealed_new,
+                                   uint32_t *n_grow_new);
 
 /* ------------------------------------------------------------------------
  * Several GPUs of one node: independent queries shard

@@ -22,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 #include <string_view>
+#include <utility>
 #include <vector>
 
 #include "vbm25.h"
@@ -418,6 +419,52 @@ inline Scorer DocTerms::scorer() const { return Scorer(*this); }
 class DeviceGrowing;
 class DeviceVacuum;
 
+// A set of ctids in the HBM of one device (RAII over vbm25_tid_set): VACUUM's dead TIDs, the TID bitmap of a heap scan.  tids: n x 3
+// uint16_t ([bi_hi, bi_lo, ip_posid]) in any order, repeats allowed.  match() answers, for every document of an index or a growing
+// segment, whether its payload is in the set, in the filters' packing; DocFilter::set_tids, DeviceGrowing::erase(const TidSet &) and
+// DeviceVacuum::bulkdelete consume the set on the device.  Only ever read after it is made.
+class TidSet {
+  public:
+    explicit TidSet(const std::vector<uint16_t> &tids, int device = 0) {
+        if (tids.size() % 3) throw Error(VBM25_ERR_INVALID, "three uint16_t per TID");
+        check(vbm25_tid_set_create(device, tids.empty() ? nullptr : tids.data(), tids.size() / 3, &h_));
+    }
+    ~TidSet() { vbm25_tid_set_free(h_); }
+    TidSet(const TidSet &) = delete;
+    TidSet &operator=(const TidSet &) = delete;
+    TidSet(TidSet &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    uint64_t size() const {  // the distinct TIDs
+        uint64_t n = 0;
+        check(vbm25_tid_set_info(h_, &n, nullptr));
+        return n;
+    }
+    int device() const {
+        int d = 0;
+        check(vbm25_tid_set_info(h_, nullptr, &d));
+        return d;
+    }
+    // the distinct TIDs, size() x 3, ascending (vbm25_tid_set_read)
+    std::vector<uint16_t> read() const {
+        std::vector<uint16_t> t(3 * size());
+        check(vbm25_tid_set_read(h_, t.empty() ? nullptr : t.data()));
+        return t;
+    }
+    uint64_t device_bytes() const { return vbm25_tid_set_device_bytes(h_); }
+    // words_per_bitmap(n_docs) words: bit d = sealed document d's payload is in the set; n_match, when given, the documents matched
+    std::vector<uint64_t> match(const Index &index, uint32_t n_docs, uint32_t *n_match = nullptr) const {
+        std::vector<uint64_t> w((size_t(n_docs) + 63) / 64 + 1);
+        check(vbm25_tid_set_match_index(h_, index.handle(), w.data(), n_match));
+        w.pop_back();
+        return w;
+    }
+    // the same over a growing segment's documents, deleted ones included (vbm25_tid_set_match_growing)
+    inline std::vector<uint64_t> match(const DeviceGrowing &growing, uint32_t *n_match = nullptr) const;
+    const vbm25_tid_set *handle() const { return h_; }
+
+  private:
+    vbm25_tid_set *h_ = nullptr;
+};
+
 // F document bitmaps of one index in HBM (vbm25_filter): bit d % 64 of word d / 64 of bitmap i set = document d may be returned.
 // Optionally F growing bitmaps for one uploaded growing segment (set_growing): bit g = growing document g may be returned.
 class DocFilter {
@@ -470,6 +517,9 @@ class DocFilter {
     // words_per_bitmap(d) for the d new documents (bit j: growing document old count + j), or empty for all bits zero.  The
     // addresses growing_device_words returns may change.
     inline void extend_growing(const DeviceGrowing &growing, const std::vector<uint64_t> &words = {});
+    // sealed bitmap i = "the document's payload is in the set" (invert: "is not"), made on the device; with `growing` (the segment of
+    // this filter's growing bitmaps, at its current document count) growing bitmap i likewise (vbm25_filter_set_tids)
+    inline void set_tids(uint32_t i, const TidSet &tids, bool invert = false, const DeviceGrowing *growing = nullptr);
     void *growing_device_words(uint32_t i) {
         void *p = nullptr;
         check(vbm25_filter_growing_device_words(h_, i, &p));
@@ -703,6 +753,13 @@ class DeviceGrowing {
     void append(const Documents &delta) { check(vbm25_device_growing_append_documents(h_, delta.handle())); }
     // growing indices below docs(), any order (vbm25_device_growing_delete)
     void erase(const std::vector<uint32_t> &g) { check(vbm25_device_growing_delete(h_, g.data(), uint32_t(g.size()))); }
+    // every growing document whose payload is in the set, found on the device (vbm25_device_growing_delete_tids); returns the
+    // documents matched, those already deleted included
+    uint32_t erase(const TidSet &tids) {
+        uint32_t n = 0;
+        check(vbm25_device_growing_delete_tids(h_, tids.handle(), &n));
+        return n;
+    }
     uint32_t docs() const { return vbm25_device_growing_docs(h_); }
     ~DeviceGrowing() { vbm25_device_growing_free(h_); }
     DeviceGrowing(const DeviceGrowing &) = delete;
@@ -738,7 +795,8 @@ class DeviceGrowing {
 
 // A relation's compaction inputs in HBM on the index's device (RAII over vbm25_device_vacuum): the sealed documents' deleted words and
 // the growing segment's CSR, read from the pages by kernels.  maintain() is vbm25_index_maintain_device: VACUUM's compaction with
-// these inputs read in place; DocFilter::remap(new_index, vacuum) carries the filters across.  The handle is only read.
+// these inputs read in place; DocFilter::remap(new_index, vacuum) carries the filters across.  The handle is only read, except by
+// bulkdelete(), which must not run beside a maintain() or a remap() of the same handle.
 class DeviceVacuum {
   public:
     static DeviceVacuum from_pages(Index &index, vbm25_read_page_fn read_page, void *ctx) {
@@ -768,6 +826,15 @@ class DeviceVacuum {
         growing_deleted.assign(n_grow, 0);
         check(vbm25_device_vacuum_read(h_, sealed_deleted_words.data(), growing_deleted.data()));
     }
+    // bulkdelete.rs on the handle (vbm25_device_vacuum_bulkdelete): every sealed document of `index` (the one the handle was read
+    // for) and every growing document whose payload is in the set is flagged deleted.  Returns {sealed, growing}: the documents that
+    // were live before and are deleted now; the counts of this object follow.
+    std::pair<uint32_t, uint32_t> bulkdelete(const Index &index, const TidSet &tids) {
+        uint32_t ns = 0, ng = 0;
+        check(vbm25_device_vacuum_bulkdelete(h_, index.handle(), tids.handle(), &ns, &ng));
+        check(vbm25_device_vacuum_info(h_, nullptr, &n_sealed_deleted, nullptr, &n_grow_deleted, nullptr));
+        return {ns, ng};
+    }
     const vbm25_device_vacuum *handle() const { return h_; }
     uint32_t n_sealed = 0, n_sealed_deleted = 0, n_grow = 0, n_grow_deleted = 0;
     uint64_t n_elements = 0;
@@ -790,6 +857,17 @@ inline void DocFilter::set_growing(const DeviceGrowing *growing, const std::vect
 
 inline void DocFilter::extend_growing(const DeviceGrowing &growing, const std::vector<uint64_t> &words) {
     check(vbm25_filter_extend_growing(h_, growing.handle(), words.empty() ? nullptr : words.data()));
+}
+
+inline void DocFilter::set_tids(uint32_t i, const TidSet &tids, bool invert, const DeviceGrowing *growing) {
+    check(vbm25_filter_set_tids(h_, i, tids.handle(), invert ? 1 : 0, growing ? growing->handle() : nullptr));
+}
+
+inline std::vector<uint64_t> TidSet::match(const DeviceGrowing &growing, uint32_t *n_match) const {
+    std::vector<uint64_t> w((size_t(growing.docs()) + 63) / 64 + 1);
+    check(vbm25_tid_set_match_growing(h_, growing.handle(), w.data(), n_match));
+    w.pop_back();
+    return w;
 }
 
 // per query: the sealed and the growing records merged, query q taking bitmap q_filter[q] of `filter` on both segments

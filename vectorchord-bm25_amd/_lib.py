@@ -187,6 +187,16 @@ ABI = {
     "vbm25_caster_collect": (i32, [vp, vp]),
     "vbm25_caster_in_flight": (i32, [vp]),
     "vbm25_documents_extend": (i32, [vp, vp]),
+    "vbm25_tid_set_create": (i32, [i32, vp, u64, vp]),
+    "vbm25_tid_set_info": (i32, [vp, vp, vp]),
+    "vbm25_tid_set_read": (i32, [vp, vp]),
+    "vbm25_tid_set_device_bytes": (u64, [vp]),
+    "vbm25_tid_set_free": (None, [vp]),
+    "vbm25_tid_set_match_index": (i32, [vp, vp, vp, vp]),
+    "vbm25_tid_set_match_growing": (i32, [vp, vp, vp, vp]),
+    "vbm25_filter_set_tids": (i32, [vp, u32, vp, i32, vp]),
+    "vbm25_device_growing_delete_tids": (i32, [vp, vp, vp]),
+    "vbm25_device_vacuum_bulkdelete": (i32, [vp, vp, vp, vp, vp]),
 }
 
 

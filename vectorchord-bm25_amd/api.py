@@ -716,6 +716,12 @@ class DocFilter:
         words = self.pack(keep_i if isinstance(keep_i, np.ndarray) and keep_i.dtype == np.bool_ else [keep_i], n)
         check(lib().vbm25_filter_update_growing(self.h, i, _p(words)))
 
+    def set_tids(self, i, tid_set, invert=False, growing=None):
+        """vbm25_filter_set_tids: sealed bitmap i becomes "the document's payload is in `tid_set`" (invert: "is not"), computed on
+        the device from the index's payloads; with `growing` (the GrowingSegment of this filter's growing bitmaps, at its current
+        document count) growing bitmap i likewise.  No bitmap crosses the host link."""
+        check(lib().vbm25_filter_set_tids(self.h, i, tid_set.h, 1 if invert else 0, growing.h if growing is not None else None))
+
     def growing_device_words(self, i):
         """vbm25_filter_growing_device_words: the device address of growing bitmap i (ceil(n_grow / 64) uint64 words)."""
         dev = C.c_void_p()
@@ -866,6 +872,13 @@ class GrowingSegment:
         g = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
         check(lib().vbm25_device_growing_delete(self.h, _p(g), len(g)))
 
+    def delete_tids(self, tid_set):
+        """vbm25_device_growing_delete_tids: delete() of every growing document whose payload is in `tid_set`, found on the device.
+        Returns the documents matched (those already deleted included)."""
+        n = C.c_uint32()
+        check(lib().vbm25_device_growing_delete_tids(self.h, tid_set.h, C.byref(n)))
+        return n.value
+
     @property
     def device_bytes(self):
         return int(lib().vbm25_device_growing_bytes(self.h))
@@ -907,10 +920,85 @@ class DeviceVacuum:
         check(lib().vbm25_device_vacuum_read(self.h, words.ctypes.data_as(C.c_void_p), g_del.ctypes.data_as(C.c_void_p)))
         return words[:n_words], g_del[:self.n_grow]
 
+    def bulkdelete(self, index, tid_set):
+        """vbm25_device_vacuum_bulkdelete: bulkdelete.rs on the handle -- every sealed document of `index` (the GpuIndex the handle
+        was read for) and every growing document whose payload is in `tid_set` is flagged deleted.  Returns (sealed, growing): the
+        documents that were live before and are deleted now; the counts of this object follow."""
+        ns, ng = C.c_uint32(), C.c_uint32()
+        check(lib().vbm25_device_vacuum_bulkdelete(self.h, index.h, tid_set.h, C.byref(ns), C.byref(ng)))
+        nsd, ngd = C.c_uint32(), C.c_uint32()
+        check(lib().vbm25_device_vacuum_info(self.h, None, C.byref(nsd), None, C.byref(ngd), None))
+        self.n_sealed_deleted, self.n_grow_deleted = nsd.value, ngd.value
+        return ns.value, ng.value
+
     def __del__(self):
         try:
             if self.h:
                 lib().vbm25_device_vacuum_free(self.h)
+        except Exception:
+            pass
+
+
+class TidSet:
+    """vbm25_tid_set: a set of ctids in the HBM of one device -- VACUUM's dead TIDs, the TID bitmap of a heap scan.  `tids`: [n, 3]
+    uint16 payloads ([bi_hi, bi_lo, ip_posid]) in any order, repeats allowed; n_unique: the distinct ones.  match() / match_growing()
+    answer, for every document, whether its payload is in the set, as the words DocFilter.pack makes; DocFilter.set_tids,
+    GrowingSegment.delete_tids and DeviceVacuum.bulkdelete consume the set on the device.  Only ever read after it is made.  Also a
+    context manager."""
+
+    def __init__(self, tids, device=0):
+        tids = np.ascontiguousarray(tids, dtype=np.uint16).reshape(-1, 3)
+        self.h = C.c_void_p()
+        check(lib().vbm25_tid_set_create(device, _p(tids) if len(tids) else None, len(tids), C.byref(self.h)))
+        n, dev = C.c_uint64(), C.c_int()
+        check(lib().vbm25_tid_set_info(self.h, C.byref(n), C.byref(dev)))
+        self.n_unique, self.device = n.value, dev.value
+
+    @staticmethod
+    def keys(tids):
+        """the packed 48-bit keys of payloads [n, 3]: ascending keys are ascending ctids"""
+        t = np.asarray(tids, dtype=np.uint16).reshape(-1, 3).astype(np.uint64)
+        return t[:, 0] << np.uint64(32) | t[:, 1] << np.uint64(16) | t[:, 2]
+
+    def _match(self, fn, handle, n):
+        n_words = (n + 63) // 64
+        words = np.zeros(max(1, n_words), dtype=np.uint64)  # (never a NULL pointer, also for zero words)
+        n_match = C.c_uint32()
+        check(fn(self.h, handle, words.ctypes.data_as(C.c_void_p), C.byref(n_match)))
+        return words[:n_words], n_match.value
+
+    def match(self, index):
+        """vbm25_tid_set_match_index -> (uint64 words [ceil(n_docs / 64)], the documents matched): bit d = sealed document d's payload
+        is in the set"""
+        return self._match(lib().vbm25_tid_set_match_index, index.h, index.n_docs)
+
+    def match_growing(self, growing):
+        """vbm25_tid_set_match_growing: the same over a GrowingSegment's documents, deleted ones included"""
+        return self._match(lib().vbm25_tid_set_match_growing, growing.h, growing.n_docs)
+
+    def read(self):
+        """vbm25_tid_set_read: the distinct TIDs, [n_unique, 3] uint16, ascending"""
+        out = np.zeros((max(1, self.n_unique), 3), dtype=np.uint16)
+        check(lib().vbm25_tid_set_read(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out[:self.n_unique]
+
+    def device_bytes(self):
+        return int(lib().vbm25_tid_set_device_bytes(self.h))
+
+    def close(self):
+        if self.h:
+            lib().vbm25_tid_set_free(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -1128,7 +1216,8 @@ def set_tuning(name, value):
     allows) and cast_grid (the most workgroups of a Caster's kernels, 0 .. 2048, 0 = no cap; both read at each submit), eval_grid (the
     most workgroups of the kernels of Documents.bind, DocTerms.evaluate and a Scorer, 1 .. 2048, read at the start of each call),
     rerank_part (the candidates one workgroup of Scorer.topk selects from, 64 .. 2^20 in 64s) and rerank_buf (its selection buffer
-    as a multiple of k, 2 .. 8; both read at the start of each Scorer call).  No switch of
+    as a multiple of k, 2 .. 8; both read at the start of each Scorer call), tid_grid (the most workgroups of the TID match kernel,
+    1 .. 2048, read at each launch) and tid_dir (log2 of a TidSet's directory entries, 0 .. 12, read when a TidSet is made).  No switch of
     the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
     libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set

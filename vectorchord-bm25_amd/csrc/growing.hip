@@ -340,6 +340,16 @@ static int device_growing_delete_impl(vbm25_device_growing *gs, const uint32_t *
     return VBM25_OK;
 }
 
+// vbm25_device_growing_delete_tids (tid.hip): the deletion bitmap is already in HBM on the segment's device (bit g % 32 of word g / 32,
+// what grow_delete_bits_kernel writes), the caller has waited for the device and the current device is the segment's.  Enqueues
+// grow_delete_kernel; the caller synchronises.
+int growing_delete_by_bits(vbm25_device_growing *gs, const uint32_t *bits) {
+    if (!gs->n_post) return VBM25_OK;
+    grow_delete_kernel<<<(gs->n_post + 255) / 256, 256>>>(gs->post_g.as<uint32_t>(), gs->n_post, bits, gs->post_c.as<double>());
+    HIP_TRY(hipGetLastError());
+    return VBM25_OK;
+}
+
 }  // namespace vbm25
 
 using namespace vbm25;

@@ -1,6 +1,6 @@
 // host_objects.h -- the host objects behind the handles of include/vbm25.h, defined once: the index, the filter, the device growing
 // segment and the batch, with the tuning switches, the route and the staging layout a batch keeps, and the declarations of the functions
-// one unit calls in another.  Included by index.hip, search.hip, growing.hip, filter.hip, stream.hip and multi.hip.  Not part of the ABI.
+// one unit calls in another.  Included by index.hip, search.hip, growing.hip, filter.hip, stream.hip, multi.hip and tid.hip.  Not part of the ABI.
 // The layouts do not depend on VBM25_PROFILE, VBM25_DEV or VBM25_CHECK: a unit built with one of them links with the others built without.
 #ifndef VBM25_HOST_OBJECTS_H
 #define VBM25_HOST_OBJECTS_H
@@ -282,6 +282,8 @@ int vbm25_batch_enqueue_download(vbm25_batch *bt);
 int vbm25_batch_finish_download(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits);
 int batch_grow_buffer(DeviceBuffer &b, size_t bytes);
 int batch_growing_buffers(vbm25_batch *bt, const vbm25_device_growing *gs);
+// growing.hip: grow_delete_kernel over a deletion bitmap in HBM (tid.hip makes one from a TID set)
+int growing_delete_by_bits(vbm25_device_growing *gs, const uint32_t *bits);
 // filter.hip
 int filter_growing_count_check(const vbm25_filter *f, const vbm25_device_growing *gs);
 int filter_selector_check(const vbm25_filter *f, const uint32_t *sel, uint32_t n, bool *any);

@@ -1,0 +1,94 @@
+// tid_lane.h -- the per-document functions of the TID-set match (tid.hip): is a document's payload in a sorted set of ctids?
+// __host__ __device__, and plain C++ as well: tid_match_kernel is a loop over these, and tests/native/fuzz_tid.cpp compiles the same
+// text with g++ under AddressSanitizer and drives a model wave with them, against std::binary_search.
+//
+//   tid_key      a payload's three uint16_t -- [bi_hi, bi_lo, ip_posid], fetcher.rs:218-232 -- as one 48-bit integer, most significant
+//                field first: ascending keys are ascending ctids
+//   dir_shape    the directory of a set of n_keys sorted keys for a directory of at most 2^dir_log2 entries: entry j is key
+//                j x stride (dir_source).  A set no larger than the directory is its own directory (stride 1); a larger one is cut
+//                into runs of `stride` keys, the last one shorter, and the directory holds the first key of each.  The builder kernel
+//                and the harness both take the shape from here.
+//   tid_contains the lower-bound search in two stages.  Stage one finds the last directory entry <= key (the kernel holds the
+//                directory in LDS); stage two finishes inside that entry's run of the sorted keys (HBM).  With stride 1 stage one
+//                decides alone.  Exact for every n_keys >= 0.
+//   match_word   a wave's ballot as the word it writes: XOR the invert mask, the bits of documents at or beyond n forced to zero
+//   new_bits     the documents a word adds to an older one (the OR mode's count)
+#ifndef VBM25_TID_LANE_H
+#define VBM25_TID_LANE_H
+
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define TID_HD __host__ __device__ __forceinline__
+#else
+#define TID_HD inline __attribute__((always_inline))
+#endif
+
+namespace vbm25 {
+namespace tid {
+
+constexpr uint32_t MAX_DIR_LOG2 = 12;      // 4096 entries: 32 KB of LDS a workgroup
+// tools/tid_cost.py, profiles/tid_cost.json: 2048 entries are the fastest on documents in ctid order at every set size (what CREATE INDEX
+// and VACUUM leave); on a shuffled payload plane 4096 are faster from a million TIDs up, and staging them costs the ordered case more
+constexpr uint32_t DEFAULT_DIR_LOG2 = 11;
+constexpr uint64_t KEY_MAX = (1ull << 48) - 1ull;
+
+TID_HD uint64_t tid_key(const uint16_t p[3]) { return uint64_t(p[0]) << 32 | uint64_t(p[1]) << 16 | uint64_t(p[2]); }
+
+struct DirShape {
+    uint32_t n_dir;   // entries, <= 2^dir_log2 (0 for the empty set)
+    uint32_t stride;  // keys a run (1: the directory is the set)
+};
+
+TID_HD DirShape dir_shape(uint64_t n_keys, uint32_t dir_log2) {
+    const uint64_t cap = 1ull << (dir_log2 > MAX_DIR_LOG2 ? MAX_DIR_LOG2 : dir_log2);
+    if (n_keys <= cap) return DirShape{uint32_t(n_keys), 1u};
+    const uint64_t stride = (n_keys + cap - 1) / cap;
+    return DirShape{uint32_t((n_keys + stride - 1) / stride), uint32_t(stride)};
+}
+TID_HD uint64_t dir_source(uint32_t j, uint32_t stride) { return uint64_t(j) * stride; }
+
+TID_HD bool tid_contains(uint64_t key, const uint64_t *directory, uint32_t n_dir, const uint64_t *keys, uint64_t n_keys, uint32_t stride) {
+    // stage one: lo = the number of directory entries <= key
+    uint32_t lo = 0, hi = n_dir;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (directory[mid] <= key) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) return false;  // (below the smallest key, or the empty set)
+    const uint32_t j = lo - 1;
+    if (directory[j] == key) return true;
+    if (stride == 1) return false;
+    // stage two: the rest of run j, keys (j stride, min((j + 1) stride, n_keys)), all > directory[j]
+    uint64_t a = dir_source(j, stride) + 1, b = dir_source(j, stride) + stride;
+    if (b > n_keys) b = n_keys;
+    while (a < b) {
+        const uint64_t mid = a + ((b - a) >> 1);
+        if (keys[mid] < key) a = mid + 1;
+        else b = mid;
+    }
+    return a < n_keys && a < dir_source(j, stride) + stride && keys[a] == key;
+}
+
+// the word of documents first .. first + 63 of n from the wave's ballot (first < n, a multiple of 64)
+TID_HD uint64_t match_word(uint64_t ballot, uint64_t first, uint64_t n, uint64_t invert_mask) {
+    const uint64_t left = n - first;
+    const uint64_t valid = left >= 64 ? ~0ull : (1ull << left) - 1ull;
+    return (ballot ^ invert_mask) & valid;
+}
+
+TID_HD uint32_t popcount64(uint64_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return uint32_t(__popcll(w));
+#else
+    return uint32_t(__builtin_popcountll(w));
+#endif
+}
+TID_HD uint32_t new_bits(uint64_t old_word, uint64_t word) { return popcount64(word & ~old_word); }
+
+}  // namespace tid
+}  // namespace vbm25
+
+#endif

@@ -112,6 +112,10 @@ void evaluate_tuning_reset();
 // multiple of k, 2 .. 8); rerank.hip keeps them and reads them at the start of each scorer call
 int rerank_tuning_set(const char *name, long long value);
 void rerank_tuning_reset();
+// vbm25_tuning_set's tid_grid (the most workgroups of tid_match_kernel, 1 .. 2048, read at each launch) and tid_dir (log2 of a TID
+// set's directory entries, 0 .. 12, read at each vbm25_tid_set_create); tid.hip keeps them
+int tid_tuning_set(const char *name, long long value);
+void tid_tuning_reset();
 
 }  // namespace vbm25
 
