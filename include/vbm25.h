@@ -983,6 +983,58 @@ int vbm25_scorer_evaluate(vbm25_scorer *, const uint32_t *term_ids, const uint32
 int vbm25_scorer_topk(vbm25_scorer *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
                       const uint32_t *cand_doc, uint32_t k, vbm25_rank *ranks, uint32_t *n_ranks);
 
+/* The reranker (csrc/reranker.hip): the rerank step as a ring, modelled on the resolver and the caster.  Lexeme queries (or term ids)
+ * and candidate lists -- document indices, ctids, or none for the cross product -- go in; each query's k best rows come out, first in
+ * first out, byte for byte what vbm25_resolver_submit_lexemes / _collect followed by vbm25_scorer_topk give.  Between submit and
+ * collect the host touches nothing: the resolved ids stay in HBM, and ctids are mapped to document indices on the device.
+ *   vbm25_reranker_create   `depth` slots (1 .. 16) on the vbm25_doc_terms, with the vocabulary and the seed of the resolver (nothing is
+ *             uploaded again; both must outlive the reranker, sit on one device and belong to one index).  Every slot owns a
+ *             non-blocking stream with two events, a pinned block for the staged inputs and one for the rows, and in HBM the staged
+ *             block, the resolve scratch of a resolver of max_queries / max_lexemes, the resolved q_off / term_ids, the rows
+ *             (max_queries x max_k x 16 + 4 max_queries bytes), the part lists at the rerank_part in force now and -- with payloads --
+ *             max_candidates document indices.  Capacities a batch: max_queries queries, max_lexemes lexemes (or term ids),
+ *             max_bytes lexeme bytes, max_candidates candidates over all queries (the cross product counts nq x n_docs), k up to
+ *             max_k.  payloads, when not NULL, is a vbm25_documents with payloads of the same documents on the same device: the
+ *             reranker sorts (ctid, document) once into a directory of its own and the handle may be freed afterwards; without it
+ *             cand_tid is refused.  VBM25_ERR_INVALID, *out == NULL: NULL t or resolver, depth outside 1 .. 16, a zero capacity,
+ *             different devices or indexes, a payloads handle without payloads, of another document count or device, an index
+ *             without sealed documents (vbm25_evaluate_documents' words).  VBM25_ERR_UNSUPPORTED: max_k over 1024 (the scorer's words).
+ *   vbm25_reranker_info     depth, the documents, whether ctids are taken, and `allocations`: every allocation and creation (device,
+ *             pinned, stream, event) the handle has made.  It does not move after create: submit and collect allocate, create and
+ *             free nothing.  vbm25_reranker_device_bytes: what the handle holds of the device (0 for NULL).
+ *   vbm25_reranker_submit_lexemes   vbm25_resolver_submit_lexemes' arrays (its checks and messages), then the candidates: q_cand NULL
+ *             for the cross product, or nq + 1 offsets with EITHER cand_doc (vbm25_scorer_topk's indices) OR cand_tid (three uint16_t
+ *             a candidate, [bi_hi, bi_lo, ip_posid] as the payloads are).  The ids and the candidates pass the scorer's checks with its
+ *             messages.  A ctid no document carries is not eligible and still holds its pos; a ctid of several documents names the
+ *             lowest document index.  Everything is validated on the host, copied into the slot's pinned block (the caller's arrays
+ *             are free at return), uploaded in one copy and enqueued; the call returns at once.  A batch in which no query has a
+ *             candidate enqueues nothing and still takes a slot.  VBM25_ERR_INVALID, nothing enqueued, the ring as it was: NULL
+ *             arguments, cand_doc and cand_tid both given, either without q_cand, cand_tid on a reranker without payloads, a full
+ *             ring, counts over a capacity (the message names it), k == 0, k > max_k, a batch whose part lists need more scratch
+ *             than a slot has because rerank_part was lowered after create.  VBM25_ERR_UNSUPPORTED for 2^31 pairs or more.
+ *   vbm25_reranker_submit_ids   the same with the queries as vbm25_scorer_topk's term_ids / q_off (at most max_lexemes ids): no resolve.
+ *   vbm25_reranker_collect  waits for the OLDEST batch and copies its nq x k rows and nq counts out, with that batch's nq and k:
+ *             vbm25_scorer_topk's contract -- score descending, then pos ascending; n_ranks[q] = min(k, eligible entries of q); the
+ *             tail all-zero bytes.  pos is the entry's index within q's own list whatever the list's form, so a caller maps a row
+ *             back to its ctid by pos.  VBM25_ERR_INVALID on an empty ring and for NULL arguments (the batch stays in the ring).
+ *   vbm25_reranker_in_flight   batches submitted and not collected (0 for NULL).
+ *   vbm25_reranker_free     waits for what is in flight, then frees everything.
+ * One host thread drives a reranker; two threads take two rerankers, which may share the vbm25_doc_terms and the resolver.  No stream
+ * waits for another and no call issues a device-wide synchronisation (create and free allocate and free, as every hipMalloc may). */
+typedef struct vbm25_reranker vbm25_reranker;
+int vbm25_reranker_create(const vbm25_doc_terms *, const vbm25_resolver *, const vbm25_documents *payloads, uint32_t depth,
+                          uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k,
+                          vbm25_reranker **out);
+void vbm25_reranker_free(vbm25_reranker *);
+uint64_t vbm25_reranker_device_bytes(const vbm25_reranker *);
+int vbm25_reranker_info(const vbm25_reranker *, uint32_t *depth, uint32_t *n_docs, uint32_t *has_payloads, uint64_t *allocations);
+int vbm25_reranker_submit_lexemes(vbm25_reranker *, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq,
+                                  const uint64_t *q_cand, const uint32_t *cand_doc, const uint16_t *cand_tid, uint32_t k);
+int vbm25_reranker_submit_ids(vbm25_reranker *, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
+                              const uint32_t *cand_doc, const uint16_t *cand_tid, uint32_t k);
+int vbm25_reranker_collect(vbm25_reranker *, vbm25_rank *ranks, uint32_t *n_ranks, uint32_t *nq_out, uint32_t *k_out);
+int vbm25_reranker_in_flight(const vbm25_reranker *);
+
 #ifdef __cplusplus
 }
 #endif

@@ -416,6 +416,83 @@ class Scorer {
 };
 inline Scorer DocTerms::scorer() const { return Scorer(*this); }
 
+// The rerank step as a ring (RAII over vbm25_reranker): `depth` slots on a DocTerms, with the vocabulary and the seed of a resolver
+// (both must outlive it).  submit() takes lexeme queries and candidates -- document indices, ctids (needs `payloads`, a Documents
+// with payloads of the same documents, at construction; it may be freed afterwards) or none for the cross product -- and returns at
+// once; collect() waits for the oldest batch and hands out Scorer::topk's rows, byte for byte what Resolver::submit / collect
+// followed by Scorer::topk give.  Nothing is allocated after the constructor.  One thread drives a reranker.  Move-only.
+class Reranker {
+  public:
+    Reranker(const DocTerms &documents, const Resolver &resolver, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes,
+             uint64_t max_candidates, uint32_t max_k, const Documents *payloads = nullptr) {
+        check(vbm25_reranker_create(documents.handle(), resolver.handle(), payloads ? payloads->handle() : nullptr, depth, max_queries, max_lexemes,
+                                    max_bytes, max_candidates, max_k, &h_));
+    }
+    Reranker(Reranker &&o) noexcept : h_(o.h_), shape_(std::move(o.shape_)) { o.h_ = nullptr; }
+    Reranker(const Reranker &) = delete;
+    Reranker &operator=(const Reranker &) = delete;
+    ~Reranker() { vbm25_reranker_free(h_); }
+    // every document of the handle is a candidate of every query
+    void submit(const LexemeBatch &b, uint32_t k) { submit_(b, nullptr, nullptr, nullptr, k); }
+    // query q reranks the documents cand_doc[q_cand[q] .. q_cand[q+1])
+    void submit(const LexemeBatch &b, uint32_t k, const std::vector<uint64_t> &q_cand, const std::vector<uint32_t> &cand_doc) {
+        if (q_cand.size() != b.q_lex.size()) throw Error(VBM25_ERR_INVALID, "one candidate range per query");
+        std::vector<uint32_t> docs(cand_doc);
+        docs.push_back(0);  // (never NULL)
+        submit_(b, q_cand.data(), docs.data(), nullptr, k);
+    }
+    // ... the documents that carry the ctids cand_tid[3 q_cand[q] .. 3 q_cand[q+1]) ([bi_hi, bi_lo, ip_posid] each)
+    void submit_tids(const LexemeBatch &b, uint32_t k, const std::vector<uint64_t> &q_cand, const std::vector<uint16_t> &cand_tid) {
+        if (q_cand.size() != b.q_lex.size()) throw Error(VBM25_ERR_INVALID, "one candidate range per query");
+        if (cand_tid.size() % 3) throw Error(VBM25_ERR_INVALID, "three uint16_t per TID");
+        std::vector<uint16_t> tids(cand_tid);
+        tids.resize(tids.size() + 3, 0);
+        submit_(b, q_cand.data(), nullptr, tids.data(), k);
+    }
+    // the queries as Scorer::topk's term ids (vbm25_reranker_submit_ids); q_cand empty: the cross product
+    void submit_ids(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off, uint32_t k, const std::vector<uint64_t> &q_cand = {},
+                    const std::vector<uint32_t> &cand_doc = {}) {
+        if (!q_cand.empty() && q_cand.size() != q_off.size()) throw Error(VBM25_ERR_INVALID, "one candidate range per query");
+        std::vector<uint32_t> ids(term_ids), docs(cand_doc);
+        ids.push_back(0);
+        docs.push_back(0);
+        const uint32_t nq = uint32_t(q_off.size() - 1);
+        check(vbm25_reranker_submit_ids(h_, ids.data(), q_off.data(), nq, q_cand.empty() ? nullptr : q_cand.data(),
+                                        q_cand.empty() ? nullptr : docs.data(), nullptr, k));
+        shape_.push_back({nq, k});
+    }
+    // the oldest batch in flight (nothing in flight: the library's error): ranks is nq x k, row-major, row q best first and zero
+    // behind n_ranks[q] = min(k, eligible entries of q); returns that batch's k
+    uint32_t collect(std::vector<vbm25_rank> &ranks, std::vector<uint32_t> &n_ranks) {
+        const std::array<uint32_t, 2> shape = shape_.empty() ? std::array<uint32_t, 2>{0, 1} : shape_.front();
+        ranks.assign(size_t(shape[0]) * shape[1] + 1, vbm25_rank{0.0, 0, 0});
+        n_ranks.assign(size_t(shape[0]) + 1, 0);
+        uint32_t nq = 0, k = 0;
+        check(vbm25_reranker_collect(h_, ranks.data(), n_ranks.data(), &nq, &k));
+        shape_.erase(shape_.begin());
+        ranks.pop_back();
+        n_ranks.pop_back();
+        return k;
+    }
+    int in_flight() const { return vbm25_reranker_in_flight(h_); }
+    uint64_t device_bytes() const { return vbm25_reranker_device_bytes(h_); }
+    // every allocation and creation the handle has made: it does not move after the constructor
+    uint64_t allocations() const {
+        uint64_t n = 0;
+        check(vbm25_reranker_info(h_, nullptr, nullptr, nullptr, &n));
+        return n;
+    }
+    vbm25_reranker *handle() const { return h_; }
+
+  private:
+    void submit_(const LexemeBatch &b, const uint64_t *q_cand, const uint32_t *cand_doc, const uint16_t *cand_tid, uint32_t k) {
+        check(vbm25_reranker_submit_lexemes(h_, b.bytes.data(), b.lex_off.data(), b.q_lex.data(), b.queries(), q_cand, cand_doc, cand_tid, k));
+        shape_.push_back({b.queries(), k});  // (only a batch the library accepted is in the ring)
+    }
+    vbm25_reranker *h_ = nullptr;
+    std::vector<std::array<uint32_t, 2>> shape_;  // per batch in flight: queries, k
+};
+
 class DeviceGrowing;
 class DeviceVacuum;
 

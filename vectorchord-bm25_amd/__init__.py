@@ -9,5 +9,5 @@ from ._lib import build, lib, library_path, Vbm25Error  # noqa: F401
 from .api import (  # noqa: F401
     HIT_DTYPE, RANK_DTYPE, Segment, DeviceSegment, GpuIndex, Batch, Query, intern, search, search_batch, search_batch_filtered, search_batch_masked, DocFilter, NO_FILTER, GrowingSegment, DeviceVacuum, search_batch_growing, search_batch_growing_masked, growing_search, merge_hits,
     segment_from_pages, growing_from_pages, sealed_deleted_from_pages, evaluate, evaluate_batch, set_tuning, reset_tuning, MultiIndex, MultiBatch, Stream,
-    Resolver, intern_batch, pack_lexemes, search_batch_lexemes, Documents, pack_documents, DocTerms, Scorer, Caster, TidSet)
+    Resolver, intern_batch, pack_lexemes, search_batch_lexemes, Documents, pack_documents, DocTerms, Scorer, Reranker, Caster, TidSet)
 from . import api, sharded  # noqa: F401,E402

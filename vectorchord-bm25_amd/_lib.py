@@ -179,6 +179,14 @@ ABI = {
     "vbm25_scorer_device_bytes": (u64, [vp]),
     "vbm25_scorer_evaluate": (i32, [vp, vp, vp, u32, vp, vp, vp]),
     "vbm25_scorer_topk": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
+    "vbm25_reranker_create": (i32, [vp, vp, vp, u32, u32, u32, u64, u64, u32, vp]),
+    "vbm25_reranker_free": (None, [vp]),
+    "vbm25_reranker_device_bytes": (u64, [vp]),
+    "vbm25_reranker_info": (i32, [vp, vp, vp, vp, vp]),
+    "vbm25_reranker_submit_lexemes": (i32, [vp, vp, vp, vp, u32, vp, vp, vp, u32]),
+    "vbm25_reranker_submit_ids": (i32, [vp, vp, vp, u32, vp, vp, vp, u32]),
+    "vbm25_reranker_collect": (i32, [vp, vp, vp, vp, vp]),
+    "vbm25_reranker_in_flight": (i32, [vp]),
     "vbm25_caster_create": (i32, [i32, vp, u32, u32, u32, u64, u32, vp]),
     "vbm25_caster_free": (None, [vp]),
     "vbm25_caster_device_bytes": (u64, [vp]),

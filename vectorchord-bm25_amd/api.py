@@ -1217,7 +1217,9 @@ def set_tuning(name, value):
     most workgroups of the kernels of Documents.bind, DocTerms.evaluate and a Scorer, 1 .. 2048, read at the start of each call),
     rerank_part (the candidates one workgroup of Scorer.topk selects from, 64 .. 2^20 in 64s) and rerank_buf (its selection buffer
     as a multiple of k, 2 .. 8; both read at the start of each Scorer call), tid_grid (the most workgroups of the TID match kernel,
-    1 .. 2048, read at each launch) and tid_dir (log2 of a TidSet's directory entries, 0 .. 12, read when a TidSet is made).  No switch of
+    1 .. 2048, read at each launch) and tid_dir (log2 of a TidSet's directory entries, 0 .. 12, read when a TidSet is made).  A
+    Reranker reads eval_grid, rerank_part and rerank_buf at each submit, and rerank_part (the size of its part-list scratch) and tid_dir
+    (its payload directory) when it is made.  No switch of
     the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
     libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set
@@ -1507,6 +1509,10 @@ class DocTerms:
         """vbm25_scorer_create: a Scorer on this handle -- the rerank step with everything kept between calls"""
         return Scorer(self)
 
+    def reranker(self, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None):
+        """vbm25_reranker_create: a Reranker on this handle -- the rerank step as a pipelined ring, from lexemes and ctids"""
+        return Reranker(self, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents)
+
     def __del__(self):
         try:
             if self.h:
@@ -1567,6 +1573,92 @@ class Scorer:
     def close(self):
         if self.h:
             lib().vbm25_scorer_free(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Reranker:
+    """vbm25_reranker: the rerank step as a ring of `depth` slots (1 .. 16) on a DocTerms, with the vocabulary and the seed of
+    `resolver`.  submit() takes lexeme queries and candidate lists -- document indices (cand_doc), ctids (cand_tid, uint16 [n, 3];
+    needs `documents`, a Documents with payloads of the same documents, at construction) or none for the cross product -- and
+    returns at once; collect() waits for the oldest batch and returns Scorer.topk's (ranks, n_ranks), byte for byte what
+    Resolver.submit / collect followed by Scorer.topk give.  A ctid no document carries is not eligible and keeps its pos; a ctid of
+    several documents names the lowest index.  Nothing is allocated after the constructor.  One thread drives a reranker.  Also a
+    context manager."""
+
+    def __init__(self, doc_terms, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None):
+        self.doc_terms, self.resolver = doc_terms, resolver  # (kept alive: the handle refers to both)
+        self.h = C.c_void_p()
+        check(lib().vbm25_reranker_create(doc_terms.h, resolver.h, None if documents is None else documents.h, depth, max_queries,
+                                          max_lexemes, max_bytes, max_candidates, max_k, C.byref(self.h)))
+        self.depth = depth
+        self._shapes = []  # per batch in flight: (queries, k)
+
+    @staticmethod
+    def _candidates(nq, q_cand, cand_doc, cand_tid):
+        """-> the three arrays (None stays None) as contiguous arrays of the library's types; the library refuses the bad pairings"""
+        if q_cand is not None:
+            q_cand = np.ascontiguousarray(q_cand, dtype=np.uint64)
+            if len(q_cand) != nq + 1:
+                raise ValueError(f"{len(q_cand)} candidate offsets for {nq} queries")
+        return (q_cand, None if cand_doc is None else _at_least_one(cand_doc, np.uint32),
+                None if cand_tid is None else _at_least_one(np.ascontiguousarray(cand_tid, dtype=np.uint16).reshape(-1), np.uint16))
+
+    def submit(self, queries_or_packed, k, q_cand=None, cand_doc=None, cand_tid=None):
+        """vbm25_reranker_submit_lexemes: Resolver.submit's queries, then Scorer.topk's candidates or ctids"""
+        data, lex_off, q_lex = _packed(queries_or_packed)
+        nq = len(q_lex) - 1
+        qc, dc, tc = self._candidates(nq, q_cand, cand_doc, cand_tid)
+        check(lib().vbm25_reranker_submit_lexemes(self.h, _p(data), lex_off.ctypes.data, q_lex.ctypes.data, nq, _p(qc), _p(dc), _p(tc), int(k)))
+        self._shapes.append((nq, int(k)))  # (only a batch the library accepted is in the ring)
+
+    def submit_ids(self, term_ids, q_off, k, q_cand=None, cand_doc=None, cand_tid=None):
+        """vbm25_reranker_submit_ids: the queries as the CSR (term_ids, q_off) Scorer.topk takes"""
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+        nq = len(q_off) - 1
+        term_ids = _at_least_one(term_ids, np.uint32)
+        qc, dc, tc = self._candidates(nq, q_cand, cand_doc, cand_tid)
+        check(lib().vbm25_reranker_submit_ids(self.h, term_ids.ctypes.data, q_off.ctypes.data, nq, _p(qc), _p(dc), _p(tc), int(k)))
+        self._shapes.append((nq, int(k)))
+
+    def collect(self):
+        """The oldest batch in flight: (ranks [nq, k] of RANK_DTYPE, n_ranks uint32 [nq])"""
+        nq, k = self._shapes[0] if self._shapes else (0, 1)  # (an empty ring: the library's own error)
+        ranks, n_ranks = np.zeros((nq, k), dtype=RANK_DTYPE), np.zeros(nq, dtype=np.uint32)
+        r = ranks if ranks.size else np.zeros(1, dtype=RANK_DTYPE)
+        n = n_ranks if nq else np.zeros(1, dtype=np.uint32)
+        got_nq, got_k = C.c_uint32(), C.c_uint32()
+        check(lib().vbm25_reranker_collect(self.h, r.ctypes.data, n.ctypes.data, C.byref(got_nq), C.byref(got_k)))
+        self._shapes.pop(0)
+        assert (got_nq.value, got_k.value) == (nq, k)
+        return ranks, n_ranks
+
+    def in_flight(self):
+        return int(lib().vbm25_reranker_in_flight(self.h))
+
+    def device_bytes(self):
+        return int(lib().vbm25_reranker_device_bytes(self.h))
+
+    def allocations(self):
+        """every allocation and creation the handle has made: it does not move after the constructor"""
+        n = C.c_uint64()
+        check(lib().vbm25_reranker_info(self.h, None, None, None, C.byref(n)))
+        return n.value
+
+    def close(self):
+        if self.h:
+            lib().vbm25_reranker_free(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):

@@ -272,7 +272,7 @@ int use_eval_device(int device) {
 }
 
 int check_score_call(const vbm25_doc_terms *t, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
-                     const uint32_t *cand_doc, const void *out, EvaluateTables *ixp, uint64_t *n_pairs_out) {
+                     const uint32_t *cand_doc, const void *out, EvaluateTables *ixp, uint64_t *n_pairs_out, bool docs_later) {
     *n_pairs_out = 0;
     if (!t) return set_error(VBM25_ERR_INVALID, "NULL argument");
     if (nq == 0) return VBM25_OK;
@@ -283,7 +283,7 @@ int check_score_call(const vbm25_doc_terms *t, const uint32_t *term_ids, const u
     for (uint32_t q = 0; q < nq; ++q)
         if (q_off[q + 1] < q_off[q]) return set_error(VBM25_ERR_INVALID, "q_off is not monotone at query %u", q);
     if (q_cand) {
-        if (!cand_doc) return set_error(VBM25_ERR_INVALID, "cand_doc is NULL while q_cand is not");
+        if (!cand_doc && !docs_later) return set_error(VBM25_ERR_INVALID, "cand_doc is NULL while q_cand is not");
         if (q_cand[0] != 0) return set_error(VBM25_ERR_INVALID, "q_cand[0] is %llu, not 0", (ull)q_cand[0]);
         for (uint32_t q = 0; q < nq; ++q)
             if (q_cand[q + 1] < q_cand[q]) return set_error(VBM25_ERR_INVALID, "q_cand is not monotone at query %u", q);
@@ -300,7 +300,7 @@ int check_score_call(const vbm25_doc_terms *t, const uint32_t *term_ids, const u
             have = true;
         }
     }
-    if (q_cand)
+    if (q_cand && !docs_later)
         for (uint32_t q = 0; q < nq; ++q)
             for (uint64_t i = q_cand[q]; i < q_cand[q + 1]; ++i)
                 if (cand_doc[i] >= t->n_docs)

@@ -49,8 +49,10 @@ __device__ __forceinline__ double lane_double(double v, uint32_t j) {
 
 // The checks of vbm25_evaluate_documents, in its order and with its messages, before anything is enqueued.  `out` is the call's
 // result array (only looked at for NULL).  VBM25_OK with *n_pairs == 0: nothing to score (nq == 0, or no query has a candidate).
+// docs_later: the candidates' document indices are made on the device behind the call (the reranker's ctid lists), so cand_doc is
+// not looked at; everything else is checked alike.
 int check_score_call(const vbm25_doc_terms *t, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, const uint64_t *q_cand,
-                     const uint32_t *cand_doc, const void *out, EvaluateTables *ix, uint64_t *n_pairs);
+                     const uint32_t *cand_doc, const void *out, EvaluateTables *ix, uint64_t *n_pairs, bool docs_later = false);
 // the handle's arrays and the index's tables into `a` (the call's own arrays are the caller's to fill)
 void fill_score_tables(const vbm25_doc_terms *t, const EvaluateTables &ix, ScoreArgs *a);
 // eval_score_kernel on `stream`, its grid capped by eval_grid as read now

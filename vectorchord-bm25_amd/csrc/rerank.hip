@@ -36,6 +36,7 @@
 #include "evaluate_lane.h"
 #include "evaluate_shared.h"
 #include "rerank_lane.h"
+#include "rerank_shared.h"
 
 struct vbm25_scorer {
     const vbm25_doc_terms *t = nullptr;
@@ -64,27 +65,6 @@ static_assert(sizeof(vbm25_rank) == 16, "vbm25_rank is 16 bytes");
 std::atomic<uint32_t> g_part{PART_DEFAULT}, g_buf{MIN_MULTIPLE};
 // the calling thread's last scorer calls: the kernels by HIP events
 thread_local double g_evaluate_ms = -1.0, g_topk_ms = -1.0;
-
-// What a unit reads once at its start (the first three) and where its result goes (the rest): fetched from the staged block where
-// they are used, so that these pointers do not sit in scalar registers through the scoring loop (with all of them as kernel
-// arguments the compiler spilled eleven SGPRs)
-struct TopkOut {
-    const uint32_t *unit_start;   // nq + 1: query q owns units unit_start[q] .. unit_start[q + 1], at least one
-    const uint32_t *q_off;        // = ScoreArgs::q_off
-    const ull *q_cand;            // = ScoreArgs::q_cand
-    const uint32_t *scr_start;    // nq: the first part list of a query of several units
-    ull *scr_key;                 // part lists: k entries each, best first
-    uint32_t *scr_pos, *scr_cnt;
-    vbm25_rank *ranks;
-    uint32_t *n_ranks;
-};
-
-struct TopkArgs {
-    ScoreArgs s;                  // (item_start and scores unused)
-    const uint32_t *multi_q;      // n_multi: the queries of several units
-    const TopkOut *out;
-    uint32_t n_units, n_multi, k, buf, part;
-};
 
 // the selection buffer of a workgroup, the whole of its LDS: key[buf], thr_key, pos[buf], cnt, thr_pos
 extern __shared__ ull rerank_lds[];
@@ -225,12 +205,12 @@ __global__ void __launch_bounds__(WG) rerank_part_kernel(TopkArgs a) {
         sel_reset(s);
         for (uint32_t c0 = c_lo; c0 < c_hi; c0 += WG) {
             const uint32_t c = c0 + threadIdx.x;
-            const bool mine = c < c_hi;
+            const uint32_t d = c >= c_hi ? NO_DOC : a.s.cand_doc ? a.s.cand_doc[cand0 + c] : c;
+            const bool mine = d != NO_DOC;  // (a list entry that names no document is not eligible; its pos still counts)
             // a lane without a candidate: the empty run 0 .. 0, which score_step never reads
             uint32_t cursor = 0, hi = 0;
             double s1 = 1.0;
             if (mine) {
-                const uint32_t d = a.s.cand_doc ? a.s.cand_doc[cand0 + c] : c;
                 cursor = uint32_t(a.s.start[d]);
                 hi = uint32_t(a.s.start[d + 1]);
                 s1 = a.s.s1[a.s.fieldnorm[d]];
@@ -408,36 +388,19 @@ int scorer_topk(vbm25_scorer *sc, const uint32_t *term_ids, const uint32_t *q_of
     }
     if (int rc = use_eval_device(sc->device)) return rc;
     g_topk_ms = -1.0;
-    const uint32_t part = g_part.load(), buf = buffer_entries(k, g_buf.load()), cap = std::max(1u, eval_grid_cap());
-    // the units: a scan of the parts per query, at least one a query; the queries of several parts get part lists
-    uint32_t n_units = 0, n_multi = 0, n_lists = 0;
-    auto parts_of = [&](uint32_t q) {
-        const uint64_t n = q_cand ? q_cand[q + 1] - q_cand[q] : t->n_docs;
-        return uint32_t(std::max<uint64_t>(1, (n + part - 1) / part));
-    };
-    for (uint32_t q = 0; q < nq; ++q) {
-        const uint32_t p = parts_of(q);
-        n_units += p;
-        if (p > 1) ++n_multi, n_lists += p;
-    }
+    const uint32_t part = g_part.load(), buf = buffer_entries(k, g_buf.load());
+    const UnitPlan plan = count_units(q_cand, t->n_docs, part, nq);
+    const uint32_t n_units = plan.n_units, n_multi = plan.n_multi, n_lists = plan.n_lists;
     const Stage g(nq, q_cand != nullptr, true, n_multi, q_off[nq], n_pairs);
-    const size_t list_entries = size_t(n_lists) * k, scr_bytes = 12ull * list_entries + 4ull * n_lists;
+    const size_t list_entries = size_t(n_lists) * k, scr_bytes = part_list_bytes(n_lists, k);
     if (int rc = grow_pinned(sc, std::max(g.bytes, out_bytes))) return rc;
     if (int rc = grow(sc->d_in, g.bytes)) return rc;
     if (int rc = grow(sc->d_out, out_bytes)) return rc;
     if (int rc = grow(sc->d_scr, scr_bytes)) return rc;
     uint8_t *host = sc->pin.as<uint8_t>();
     stage_common(g, host, term_ids, q_off, nq, q_cand, cand_doc, n_pairs);
-    uint32_t *unit_start = reinterpret_cast<uint32_t *>(host + g.unit), *scr_start = reinterpret_cast<uint32_t *>(host + g.scr);
-    uint32_t *multi_q = reinterpret_cast<uint32_t *>(host + g.multi);
-    unit_start[0] = 0;
-    for (uint32_t q = 0, m = 0, l = 0; q < nq; ++q) {
-        const uint32_t p = parts_of(q);
-        unit_start[q + 1] = unit_start[q] + p;
-        scr_start[q] = l;
-        if (p > 1) multi_q[m++] = q, l += p;
-    }
-    scr_start[nq] = n_lists;
+    fill_units(q_cand, t->n_docs, part, nq, reinterpret_cast<uint32_t *>(host + g.unit), reinterpret_cast<uint32_t *>(host + g.scr),
+               reinterpret_cast<uint32_t *>(host + g.multi));
     TopkArgs a{};
     fill_score_tables(t, ix, &a.s);
     const uint8_t *dev = sc->d_in.as<uint8_t>();
@@ -463,12 +426,7 @@ int scorer_topk(vbm25_scorer *sc, const uint32_t *term_ids, const uint32_t *q_of
     Quiesce quiesce(sc->st.s);
     HIP_TRY(hipMemcpyAsync(sc->d_in.p, host, g.bytes, hipMemcpyHostToDevice, sc->st.s));
     HIP_TRY(hipEventRecord(sc->ev_start.e, sc->st.s));
-    rerank_part_kernel<<<std::min(std::min(n_units, MAX_GRID), cap), WG, sel_lds_bytes(buf), sc->st.s>>>(a);
-    HIP_TRY(hipGetLastError());
-    if (n_multi) {
-        rerank_merge_kernel<<<std::min(std::min(n_multi, MAX_GRID), cap), WG, sel_lds_bytes(buf), sc->st.s>>>(a);
-        HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(launch_topk(a, sc->st.s));
     HIP_TRY(hipEventRecord(sc->ev_done.e, sc->st.s));
     HIP_TRY(hipMemcpyAsync(host, sc->d_out.p, out_bytes, hipMemcpyDeviceToHost, sc->st.s));
     HIP_TRY(hipStreamSynchronize(sc->st.s));
@@ -498,6 +456,20 @@ int scorer_create(const vbm25_doc_terms *t, vbm25_scorer **out) {
 }  // namespace
 
 namespace vbm25 {
+namespace rrk {
+uint32_t rerank_part_now() { return g_part.load(); }
+uint32_t rerank_buf_now() { return g_buf.load(); }
+hipError_t launch_topk(const TopkArgs &a, hipStream_t stream) {
+    const uint32_t cap = std::max(1u, eval_grid_cap());
+    rerank_part_kernel<<<std::min(std::min(a.n_units, MAX_GRID), cap), WG, sel_lds_bytes(a.buf), stream>>>(a);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (a.n_multi) {
+        rerank_merge_kernel<<<std::min(std::min(a.n_multi, MAX_GRID), cap), WG, sel_lds_bytes(a.buf), stream>>>(a);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+}  // namespace rrk
 int rerank_tuning_set(const char *name, long long value) {
     if (std::string(name) == "rerank_part")
         g_part.store(uint32_t(std::min<long long>(std::max<long long>(value, PART_MIN), PART_MAX)) / 64u * 64u);

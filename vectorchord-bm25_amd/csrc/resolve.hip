@@ -38,6 +38,7 @@
 #include "hip_host.h"
 #include "resolve_lane.h"
 #include "lexeme_input.h"
+#include "resolve_shared.h"
 
 namespace {
 
@@ -51,7 +52,6 @@ using vbm25::lexin::seed_words;
 constexpr uint32_t INTERN_THREADS = 64;   // one wave a block: the LDS stack is 32 bytes a level a lane
 constexpr uint32_t INTERN_GRID = 1024;    // one wave a SIMD of the 256 CUs; more lexemes than 65536 stride the grid
 constexpr uint32_t WG_THREADS = 256, MAX_GRID = 2048;
-constexpr uint32_t WAVE_QUERY = 64;       // the wave path's longest query
 
 // keys_out and ids may each be NULL.  The pool is 4-byte aligned and ends on a multiple of 4 (WordLoad).
 __global__ void __launch_bounds__(INTERN_THREADS) intern_kernel(Seed seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex,
@@ -137,11 +137,11 @@ __global__ void __launch_bounds__(WG_THREADS) emit_kernel(const unsigned long lo
     }
 }
 
-// what a lexeme batch is, checked before anything is allocated or enqueued
-struct LexShape {
-    uint32_t n_lex = 0, longest_query = 0;
-    uint64_t n_bytes = 0, longest_lexeme = 0;
-};
+}  // namespace
+
+namespace vbm25 {
+namespace rsv {
+
 int check_offsets32(const uint32_t *q, uint32_t nq, const char *what, LexShape *s) {
     if (q[0] != 0) return set_error(VBM25_ERR_INVALID, "%s[0] is %u, not 0", what, q[0]);
     for (uint32_t i = 0; i < nq; ++i) {
@@ -157,6 +157,15 @@ int check_lexemes(bool has_seed, const uint8_t *bytes, const uint64_t *lex_off, 
     return lexin::check_pool(has_seed, bytes, lex_off, s->n_lex, "resolver", &s->n_bytes, &s->longest_lexeme);
 }
 
+int pack_cub_bytes(uint32_t max_queries, uint32_t max_lexemes, hipStream_t st, size_t *bytes) {
+    size_t scan_q = 0, scan_l = 0, sort_l = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_q, (uint32_t *)nullptr, (uint32_t *)nullptr, int(max_queries + 1), st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_l, (uint32_t *)nullptr, (uint32_t *)nullptr, int(size_t(max_lexemes) + 1), st));
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_l, (unsigned long long *)nullptr, (unsigned long long *)nullptr, int(max_lexemes), 0, 64, st));
+    *bytes = std::max(scan_q, std::max(scan_l, sort_l));
+    return VBM25_OK;
+}
+
 int launch_intern(hipStream_t st, const Seed &seed, const uint32_t *pool, const uint64_t *lex_off, uint32_t n_lex, uint64_t longest,
                   const Key *vocab, uint32_t n_terms, Key *keys_out, uint32_t *ids) {
     if (!n_lex) return VBM25_OK;
@@ -165,6 +174,39 @@ int launch_intern(hipStream_t st, const Seed &seed, const uint32_t *pool, const 
     HIP_TRY(hipGetLastError());
     return VBM25_OK;
 }
+
+int enqueue_pack(hipStream_t st, const PackScratch &s, const uint32_t *q_lex_dev, uint32_t nq, uint32_t n_lex, uint32_t longest_query,
+                 uint32_t *out_ids, uint32_t *out_q_off) {
+    if (longest_query <= WAVE_QUERY) {
+        pack_wave_kernel<<<grid_for(nq, WG_THREADS / 64, MAX_GRID), WG_THREADS, 0, st>>>(s.ids, q_lex_dev, nq, s.tmp, s.counts);
+        HIP_TRY(hipGetLastError());
+        size_t tb = s.cub_bytes;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.cub, tb, s.counts, s.q_off, int(nq + 1), st));
+        gather_kernel<<<grid_for(nq, WG_THREADS / 64, MAX_GRID), WG_THREADS, 0, st>>>(s.tmp, q_lex_dev, s.q_off, nq, out_ids, out_q_off);
+        HIP_TRY(hipGetLastError());
+    } else {
+        unsigned long long *ka = s.sort_a, *kb = s.sort_b;
+        uint32_t *flags = reinterpret_cast<uint32_t *>(kb + s.max_lexemes), *pos = s.tmp;
+        sortkey_kernel<<<grid_for(n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(s.ids, q_lex_dev, nq, n_lex, ka);
+        HIP_TRY(hipGetLastError());
+        int q_bits = 0;
+        while (q_bits < 32 && (uint64_t(nq) >> q_bits)) ++q_bits;
+        size_t tb = s.cub_bytes;
+        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(s.cub, tb, ka, kb, int(n_lex), 0, 32 + q_bits, st));
+        flag_kernel<<<grid_for(n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(kb, n_lex, flags);
+        HIP_TRY(hipGetLastError());
+        tb = s.cub_bytes;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.cub, tb, flags, pos, int(n_lex + 1), st));
+        emit_kernel<<<grid_for(std::max(n_lex, nq + 1), WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(kb, flags, pos, q_lex_dev, nq, n_lex, out_ids, out_q_off);
+        HIP_TRY(hipGetLastError());
+    }
+    return VBM25_OK;
+}
+
+}  // namespace rsv
+}  // namespace vbm25
+
+namespace {
 
 struct Slot {
     uint8_t *in = nullptr;    // pinned: the staged block of one batch
@@ -226,12 +268,7 @@ int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint
     const size_t head_bytes = align_up(align_up(4ull * (max_queries + 1), 8) + 8ull * (max_lexemes + 1), 16);
     r->in_capacity = head_bytes + std::max<size_t>(align_up(max_bytes, 4), 16ull * max_lexemes);
     const size_t n1 = size_t(max_lexemes) + 1;
-    size_t scan_q = 0, scan_l = 0, sort_l = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_q, (uint32_t *)nullptr, (uint32_t *)nullptr, int(max_queries + 1), r->stream));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_l, (uint32_t *)nullptr, (uint32_t *)nullptr, int(n1), r->stream));
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_l, (unsigned long long *)nullptr, (unsigned long long *)nullptr, int(max_lexemes), 0, 64,
-                                             r->stream));
-    r->cub_bytes = std::max(scan_q, std::max(scan_l, sort_l));
+    if (int rc = pack_cub_bytes(max_queries, max_lexemes, r->stream, &r->cub_bytes)) return rc;
     HIP_TRY(r->vocab.alloc(16ull * n_terms));
     HIP_TRY(r->in_dev.alloc(r->in_capacity));
     HIP_TRY(r->ids.alloc(4 * n1));       // ids; the general path's flags
@@ -259,34 +296,10 @@ int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint
 
 // step (c) and the slot's completion, after the ids are in r->ids
 int enqueue_pack(vbm25_resolver *r, Slot &s, const uint32_t *q_lex_dev, uint32_t nq, uint32_t n_lex, uint32_t longest_query) {
-    hipStream_t st = r->stream;
-    uint32_t *out_q_off = s.out, *out_ids = s.out + (r->max_queries + 1);
-    if (longest_query <= WAVE_QUERY) {
-        pack_wave_kernel<<<grid_for(nq, WG_THREADS / 64, MAX_GRID), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, r->tmp.as<uint32_t>(),
-                                                                                r->counts.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        size_t tb = r->cub_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, r->counts.as<uint32_t>(), r->q_off.as<uint32_t>(), int(nq + 1), st));
-        gather_kernel<<<grid_for(nq, WG_THREADS / 64, MAX_GRID), WG_THREADS, 0, st>>>(r->tmp.as<uint32_t>(), q_lex_dev, r->q_off.as<uint32_t>(), nq, out_ids,
-                                                                             out_q_off);
-        HIP_TRY(hipGetLastError());
-    } else {
-        unsigned long long *ka = r->sort_a.as<unsigned long long>(), *kb = r->sort_b.as<unsigned long long>();
-        uint32_t *flags = reinterpret_cast<uint32_t *>(kb + r->max_lexemes), *pos = r->tmp.as<uint32_t>();
-        sortkey_kernel<<<grid_for(n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(r->ids.as<uint32_t>(), q_lex_dev, nq, n_lex, ka);
-        HIP_TRY(hipGetLastError());
-        int q_bits = 0;
-        while (q_bits < 32 && (uint64_t(nq) >> q_bits)) ++q_bits;
-        size_t tb = r->cub_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(r->cub.p, tb, ka, kb, int(n_lex), 0, 32 + q_bits, st));
-        flag_kernel<<<grid_for(n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(kb, n_lex, flags);
-        HIP_TRY(hipGetLastError());
-        tb = r->cub_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(r->cub.p, tb, flags, pos, int(n_lex + 1), st));
-        emit_kernel<<<grid_for(std::max(n_lex, nq + 1), WG_THREADS, MAX_GRID), WG_THREADS, 0, st>>>(kb, flags, pos, q_lex_dev, nq, n_lex, out_ids, out_q_off);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(s.done, st));
+    const PackScratch scratch{r->ids.as<uint32_t>(), r->tmp.as<uint32_t>(), r->counts.as<uint32_t>(), r->q_off.as<uint32_t>(),
+                              r->sort_a.as<unsigned long long>(), r->sort_b.as<unsigned long long>(), r->cub.p, r->cub_bytes, r->max_lexemes};
+    if (int rc = rsv::enqueue_pack(r->stream, scratch, q_lex_dev, nq, n_lex, longest_query, s.out + (r->max_queries + 1), s.out)) return rc;
+    HIP_TRY(hipEventRecord(s.done, r->stream));
     return VBM25_OK;
 }
 
@@ -418,6 +431,12 @@ int resolver_vocabulary(const vbm25_resolver *r, ResolverVocabulary *out) {
     *out = ResolverVocabulary{r->index, r->device, r->n_terms, r->vocab.p};
     return VBM25_OK;
 }
+namespace rsv {
+int resolver_seed(const vbm25_resolver *r, ResolverSeed *out) {
+    *out = ResolverSeed{r->has_seed, r->seed};
+    return VBM25_OK;
+}
+}  // namespace rsv
 }  // namespace vbm25
 
 extern "C" {

@@ -319,6 +319,7 @@ int tid_tuning_set(const char *name, long long value) {
     else return set_error(VBM25_ERR_INVALID, "unknown tuning switch %s", name);
     return VBM25_OK;
 }
+uint32_t tid_dir_now() { return g_tid_dir.load(); }
 void tid_tuning_reset() {
     g_tid_grid.store(MAX_GRID);
     g_tid_dir.store(DEFAULT_DIR_LOG2);

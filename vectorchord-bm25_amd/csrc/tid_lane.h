@@ -11,6 +11,8 @@
 //   tid_contains the lower-bound search in two stages.  Stage one finds the last directory entry <= key (the kernel holds the
 //                directory in LDS); stage two finishes inside that entry's run of the sorted keys (HBM).  With stride 1 stage one
 //                decides alone.  Exact for every n_keys >= 0.
+//   tid_find     the same search over keys that may repeat, returning the first position of the key (reranker.hip's ctid -> document
+//                lookup; tests/native/fuzz_tid_find.cpp checks it against std::lower_bound)
 //   match_word   a wave's ballot as the word it writes: XOR the invert mask, the bits of documents at or beyond n forced to zero
 //   new_bits     the documents a word adds to an older one (the OR mode's count)
 #ifndef VBM25_TID_LANE_H
@@ -70,6 +72,33 @@ TID_HD bool tid_contains(uint64_t key, const uint64_t *directory, uint32_t n_dir
         else b = mid;
     }
     return a < n_keys && a < dir_source(j, stride) + stride && keys[a] == key;
+}
+
+constexpr uint64_t NOT_THERE = ~0ull;
+
+// The same two stages over sorted keys that may REPEAT (reranker.hip: the payloads of a handle's documents, two documents may share
+// a ctid): the FIRST position whose key equals `key`, or NOT_THERE.  Stage one finds the last directory entry < key: the first equal
+// key lies in that entry's run or is the first key of the next one, so stage two is a lower bound over
+// (j stride, min((j + 1) stride, n_keys)] -- one position more than a run, still a read inside keys[0 .. n_keys).  With stride 1 the
+// directory is the keys and stage one decides alone.  Exact for every n_keys >= 0.
+TID_HD uint64_t tid_find(uint64_t key, const uint64_t *directory, uint32_t n_dir, const uint64_t *keys, uint64_t n_keys, uint32_t stride) {
+    // stage one: lo = the number of directory entries < key
+    uint32_t lo = 0, hi = n_dir;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (directory[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    if (stride == 1) return lo < n_dir && directory[lo] == key ? uint64_t(lo) : NOT_THERE;
+    // stage two: every key up to position a - 1 is < key, position b (when it exists) holds a key >= key
+    uint64_t a = lo ? dir_source(lo - 1, stride) + 1 : 0, b = dir_source(lo, stride);
+    if (b > n_keys) b = n_keys;
+    while (a < b) {
+        const uint64_t mid = a + ((b - a) >> 1);
+        if (keys[mid] < key) a = mid + 1;
+        else b = mid;
+    }
+    return a < n_keys && keys[a] == key ? a : NOT_THERE;
 }
 
 // the word of documents first .. first + 63 of n from the wave's ballot (first < n, a multiple of 64)

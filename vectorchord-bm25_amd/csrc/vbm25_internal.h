@@ -116,6 +116,8 @@ void rerank_tuning_reset();
 // set's directory entries, 0 .. 12, read at each vbm25_tid_set_create); tid.hip keeps them
 int tid_tuning_set(const char *name, long long value);
 void tid_tuning_reset();
+// tid_dir as it stands (the reranker's payload directory is built under it, as a TID set's is)
+uint32_t tid_dir_now();
 
 }  // namespace vbm25
 
