@@ -1035,6 +1035,30 @@ int vbm25_reranker_submit_ids(vbm25_reranker *, const uint32_t *term_ids, const 
 int vbm25_reranker_collect(vbm25_reranker *, vbm25_rank *ranks, uint32_t *n_ranks, uint32_t *nq_out, uint32_t *k_out);
 int vbm25_reranker_in_flight(const vbm25_reranker *);
 
+/* The forward index of an index's own documents (csrc/forward.hip): the rerank stack on an index that arrived without its tsvectors --
+ * read from pages, built from mappings, produced by a compaction.
+ *   vbm25_index_bind       the transpose of the index's postings, made on the index's device from the arrays the index keeps in HBM
+ *             (nothing is uploaded): a vbm25_doc_terms of the index's n_docs sealed documents in the index's document order -- per
+ *             document the ascending term ids of its postings with their tfs, and the fieldnorm code its postings carry.  It is what
+ *             vbm25_documents_bind gives for the documents the index was built from, array for array; a document without a posting
+ *             has an empty run and the fieldnorm code 0, and never scores.  vbm25_doc_terms_*, vbm25_evaluate_documents, the scorer
+ *             and the reranker take the handle as they take any other; document index d is sealed document d, the one whose ctid is
+ *             the index's payload d.  The handle refers to the index, which must outlive it, and is valid for that index only: after
+ *             a compaction the caller binds the new index.  The growing segment is not part of it.  An index of 0 documents binds to
+ *             a valid handle of 0 documents.  The result costs 8 bytes a posting and 9 a document; the scratch beyond it is a few
+ *             words a document plus a double buffer of the runs longer than 2048 postings, never a sort of all postings.
+ *             Synchronous, on a stream of its own, no device-wide synchronisation; the index is only read, so two threads may bind
+ *             at once.  VBM25_ERR_INVALID, *out == NULL, nothing enqueued: NULL arguments.  VBM25_ERR_UNSUPPORTED: 2^31 postings or
+ *             more in runs longer than 2048.
+ *   vbm25_reranker_create_from_index   vbm25_reranker_create on a handle made by vbm25_index_bind, with the ctid directory built from
+ *             the index's own payload plane: cand_tid names the rows of the indexed table.  VBM25_ERR_INVALID for a handle that
+ *             vbm25_index_bind did not make; every other check and message is vbm25_reranker_create's.  (vbm25_reranker_create
+ *             itself takes an index-bound handle as any other; with payloads == NULL it gives a ring without ctids.) */
+int vbm25_index_bind(const vbm25_index *, vbm25_doc_terms **out);
+int vbm25_reranker_create_from_index(const vbm25_doc_terms *, const vbm25_resolver *, uint32_t depth, uint32_t max_queries,
+                                     uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k,
+                                     vbm25_reranker **out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,7 @@ class Query {
 };
 
 // HBM-resident sealed segment.
+class DocTerms;
 class Index {
   public:
     Index(const vbm25_index_desc &desc, int device = 0) { check(vbm25_index_create(&desc, device, &h_)); }
@@ -113,6 +114,9 @@ class Index {
         n_hits.resize(nq);
         check(vbm25_search_batch(h_, term_ids.data(), q_off.data(), nq, uint32_t(k), hits.data(), n_hits.data()));
     }
+    // the forward index of the index's own sealed documents, made on the device from the index's arrays (vbm25_index_bind): document d
+    // of the result is sealed document d.  Valid for this index only, which must outlive it; bind again after a compaction.
+    inline DocTerms bind() const;
     vbm25_index *handle() const { return h_; }
 
   private:
@@ -296,6 +300,8 @@ class Scorer;
 class DocTerms {
   public:
     DocTerms(const Documents &documents, const Resolver &resolver) { check(vbm25_documents_bind(documents.handle(), resolver.handle(), &h_)); }
+    // the index's own sealed documents (vbm25_index_bind)
+    explicit DocTerms(const Index &index) { check(vbm25_index_bind(index.handle(), &h_)); }
     DocTerms(DocTerms &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     DocTerms(const DocTerms &) = delete;
     DocTerms &operator=(const DocTerms &) = delete;
@@ -350,6 +356,7 @@ class DocTerms {
     vbm25_doc_terms *h_ = nullptr;
 };
 inline DocTerms Documents::bind(const Resolver &resolver) const { return DocTerms(*this, resolver); }
+inline DocTerms Index::bind() const { return DocTerms(*this); }
 
 // The rerank step on bound documents (RAII over vbm25_scorer): it keeps its stream, events, pinned staging and device buffers
 // between calls.  evaluate() is DocTerms::evaluate through the handle; topk() returns each query's k best candidates -- score
@@ -421,8 +428,16 @@ inline Scorer DocTerms::scorer() const { return Scorer(*this); }
 // with payloads of the same documents, at construction; it may be freed afterwards) or none for the cross product -- and returns at
 // once; collect() waits for the oldest batch and hands out Scorer::topk's rows, byte for byte what Resolver::submit / collect
 // followed by Scorer::topk give.  Nothing is allocated after the constructor.  One thread drives a reranker.  Move-only.
+// With the tag from_index, on a DocTerms made by Index::bind, the ctids are the index's own payloads (vbm25_reranker_create_from_index).
+struct FromIndex {};
+constexpr FromIndex from_index{};
 class Reranker {
   public:
+    Reranker(const DocTerms &documents, const Resolver &resolver, FromIndex, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes,
+             uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k) {
+        check(vbm25_reranker_create_from_index(documents.handle(), resolver.handle(), depth, max_queries, max_lexemes, max_bytes, max_candidates,
+                                               max_k, &h_));
+    }
     Reranker(const DocTerms &documents, const Resolver &resolver, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes,
              uint64_t max_candidates, uint32_t max_k, const Documents *payloads = nullptr) {
         check(vbm25_reranker_create(documents.handle(), resolver.handle(), payloads ? payloads->handle() : nullptr, depth, max_queries, max_lexemes,

@@ -205,6 +205,8 @@ ABI = {
     "vbm25_filter_set_tids": (i32, [vp, u32, vp, i32, vp]),
     "vbm25_device_growing_delete_tids": (i32, [vp, vp, vp]),
     "vbm25_device_vacuum_bulkdelete": (i32, [vp, vp, vp, vp, vp]),
+    "vbm25_index_bind": (i32, [vp, vp]),
+    "vbm25_reranker_create_from_index": (i32, [vp, vp, u32, u32, u32, u64, u64, u32, vp]),
 }
 
 

@@ -407,6 +407,14 @@ class GpuIndex:
     def device_bytes(self):
         return int(lib().vbm25_index_device_bytes(self.h))
 
+    def bind(self):
+        """vbm25_index_bind: the forward index of the index's own sealed documents, made on the device from the index's arrays in HBM
+        -> DocTerms of n_docs documents in the index's order (document d is sealed document d).  What Documents.bind gives for the
+        documents the index was built from; valid for this index only (bind again after a compaction)."""
+        out = C.c_void_p()
+        check(lib().vbm25_index_bind(self.h, C.byref(out)))
+        return DocTerms(out, index=self)
+
     def lookup_terms(self, keys):
         """address_tokens::read for a list of 16-byte keys -> term ids (0xffffffff = absent)."""
         buf = np.frombuffer(b"".join(keys), dtype=np.uint8) if keys else np.zeros(0, np.uint8)
@@ -1215,6 +1223,8 @@ def set_tuning(name, value):
     cast_pack (a Caster's wave class: 0 one document a wave, 1 several a wave, 2 several a wave interning in the lanes where the batch
     allows) and cast_grid (the most workgroups of a Caster's kernels, 0 .. 2048, 0 = no cap; both read at each submit), eval_grid (the
     most workgroups of the kernels of Documents.bind, DocTerms.evaluate and a Scorer, 1 .. 2048, read at the start of each call),
+    fwd_grid (the most workgroups of GpuIndex.bind's kernels, 0 .. 2048, 0 = no cap), fwd_wave_max and fwd_group_max (the class bounds
+    of its per-document sort, up to 64 and 2048, 0 turns the class off; all three read at the start of each bind),
     rerank_part (the candidates one workgroup of Scorer.topk selects from, 64 .. 2^20 in 64s) and rerank_buf (its selection buffer
     as a multiple of k, 2 .. 8; both read at the start of each Scorer call), tid_grid (the most workgroups of the TID match kernel,
     1 .. 2048, read at each launch) and tid_dir (log2 of a TidSet's directory entries, 0 .. 12, read when a TidSet is made).  A
@@ -1509,9 +1519,10 @@ class DocTerms:
         """vbm25_scorer_create: a Scorer on this handle -- the rerank step with everything kept between calls"""
         return Scorer(self)
 
-    def reranker(self, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None):
-        """vbm25_reranker_create: a Reranker on this handle -- the rerank step as a pipelined ring, from lexemes and ctids"""
-        return Reranker(self, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents)
+    def reranker(self, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None, from_index=False):
+        """vbm25_reranker_create: a Reranker on this handle -- the rerank step as a pipelined ring, from lexemes and ctids.
+        from_index=True (vbm25_reranker_create_from_index, a handle from GpuIndex.bind only): the ctids are the index's own payloads"""
+        return Reranker(self, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents, from_index)
 
     def __del__(self):
         try:
@@ -1591,17 +1602,25 @@ class Scorer:
 class Reranker:
     """vbm25_reranker: the rerank step as a ring of `depth` slots (1 .. 16) on a DocTerms, with the vocabulary and the seed of
     `resolver`.  submit() takes lexeme queries and candidate lists -- document indices (cand_doc), ctids (cand_tid, uint16 [n, 3];
-    needs `documents`, a Documents with payloads of the same documents, at construction) or none for the cross product -- and
+    needs `documents`, a Documents with payloads of the same documents, or from_index=True on a DocTerms from GpuIndex.bind, at
+    construction) or none for the cross product -- and
     returns at once; collect() waits for the oldest batch and returns Scorer.topk's (ranks, n_ranks), byte for byte what
     Resolver.submit / collect followed by Scorer.topk give.  A ctid no document carries is not eligible and keeps its pos; a ctid of
     several documents names the lowest index.  Nothing is allocated after the constructor.  One thread drives a reranker.  Also a
     context manager."""
 
-    def __init__(self, doc_terms, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None):
+    def __init__(self, doc_terms, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None,
+                 from_index=False):
         self.doc_terms, self.resolver = doc_terms, resolver  # (kept alive: the handle refers to both)
         self.h = C.c_void_p()
-        check(lib().vbm25_reranker_create(doc_terms.h, resolver.h, None if documents is None else documents.h, depth, max_queries,
-                                          max_lexemes, max_bytes, max_candidates, max_k, C.byref(self.h)))
+        if from_index:
+            if documents is not None:
+                raise ValueError("from_index takes the index's own payloads: documents must be None")
+            check(lib().vbm25_reranker_create_from_index(doc_terms.h, resolver.h, depth, max_queries, max_lexemes, max_bytes,
+                                                         max_candidates, max_k, C.byref(self.h)))
+        else:
+            check(lib().vbm25_reranker_create(doc_terms.h, resolver.h, None if documents is None else documents.h, depth, max_queries,
+                                              max_lexemes, max_bytes, max_candidates, max_k, C.byref(self.h)))
         self.depth = depth
         self._shapes = []  # per batch in flight: (queries, k)
 

@@ -1,5 +1,6 @@
 // decode.h -- block decode (compression.rs:65-136 formats): one wave, two postings per lane.
-// Included by search.hip, scan_win.hip, index.hip (index_derive.h) and maintain.hip (the compaction's count and scatter passes).
+// Included by search.hip, scan_win.hip, index.hip (index_derive.h), maintain.hip (the compaction's count and scatter passes) and
+// forward.hip (the bind of an index's own documents: its count and scatter passes).
 #ifndef VBM25_DECODE_H
 #define VBM25_DECODE_H
 

@@ -18,6 +18,7 @@ struct vbm25_doc_terms {
     int device = 0;
     uint32_t n_docs = 0;
     uint64_t n_known = 0;
+    bool from_index = false;  // made by vbm25_index_bind: its documents are the index's own sealed documents, in the index's order
     vbm25::HbmArray d_start, d_term, d_tf, d_fieldnorm;
 };
 

@@ -1,6 +1,6 @@
 // host_objects.h -- the host objects behind the handles of include/vbm25.h, defined once: the index, the filter, the device growing
 // segment and the batch, with the tuning switches, the route and the staging layout a batch keeps, and the declarations of the functions
-// one unit calls in another.  Included by index.hip, search.hip, growing.hip, filter.hip, stream.hip, multi.hip and tid.hip.  Not part of the ABI.
+// one unit calls in another.  Included by index.hip, search.hip, growing.hip, filter.hip, stream.hip, multi.hip, tid.hip and forward.hip.  Not part of the ABI.
 // The layouts do not depend on VBM25_PROFILE, VBM25_DEV or VBM25_CHECK: a unit built with one of them links with the others built without.
 #ifndef VBM25_HOST_OBJECTS_H
 #define VBM25_HOST_OBJECTS_H

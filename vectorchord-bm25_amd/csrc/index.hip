@@ -538,6 +538,11 @@ int index_evaluate_tables(const vbm25_index *ix, EvaluateTables *out) {
     *out = EvaluateTables{ix->device, ix->n_docs, ix->n_terms, ix->k1, ix->term_idf.as<double>(), ix->dev.s1};
     return VBM25_OK;
 }
+int index_payloads(const vbm25_index *ix, const uint16_t **payload, uint32_t *n_docs) {
+    *payload = ix->doc_payload.as<uint16_t>();
+    *n_docs = ix->n_docs;
+    return VBM25_OK;
+}
 
 }  // namespace vbm25
 

@@ -14,7 +14,8 @@
 //                          document carries.  Grid-stride under the eval_grid cap.
 //     rerank_part_kernel (+ rerank_merge_kernel)   with the resolved ids; a NO_DOC entry is not eligible, its pos still counts
 //     download             the rows and counts into the slot's pinned block, then the done event
-//   The payload directory (built once at create when a vbm25_documents with payloads is given): (tid_key(payload[d]), d) sorted by the
+//   The payload directory (built once at create, from the payloads of a vbm25_documents or, for vbm25_reranker_create_from_index,
+//   from the doc_payload plane of the index the handle was bound from): (tid_key(payload[d]), d) sorted by the
 //   48 key bits -- the sort is stable, equal keys keep ascending d, so a ctid of several documents resolves to the lowest -- and
 //   tid_lane.h's directory of evenly spaced keys over them, under the tid_dir switch.
 //   No stream waits for another: a slot is reused only after its collect, and the doc_terms, the vocabulary and the directory are
@@ -161,9 +162,8 @@ struct vbm25_reranker {
 
 namespace {
 
-// the payload directory, on slot 0's stream; synchronous
-int build_directory(vbm25_reranker *r, const vbm25_documents *h) {
-    const uint32_t n = h->n_docs;
+// the payload directory over `n` payloads in HBM (a vbm25_documents' or an index's), on slot 0's stream; synchronous
+int build_directory(vbm25_reranker *r, const uint16_t *payload, uint32_t n) {
     const DirShape shape = dir_shape(n, tid_dir_now());
     r->n_dir = shape.n_dir;
     r->stride = shape.stride;
@@ -184,7 +184,7 @@ int build_directory(vbm25_reranker *r, const vbm25_documents *h) {
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                                   int(n), 0, 48, st));
         HIP_TRY(r->device_alloc(cub, cub_bytes, false));
-        payload_key_kernel<<<grid_for(n, WG, MAX_GRID), WG, 0, st>>>(h->d_payload.as<uint16_t>(), n, keys_in.as<ull>(), docs_in.as<uint32_t>());
+        payload_key_kernel<<<grid_for(n, WG, MAX_GRID), WG, 0, st>>>(payload, n, keys_in.as<ull>(), docs_in.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, cub_bytes, keys_in.as<ull>(), r->dir_keys.as<ull>(), docs_in.as<uint32_t>(),
                                                   r->dir_docs.as<uint32_t>(), int(n), 0, 48, st));
@@ -199,11 +199,14 @@ int build_directory(vbm25_reranker *r, const vbm25_documents *h) {
     return VBM25_OK;
 }
 
-int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vbm25_documents *payloads, uint32_t depth, uint32_t max_queries,
-                    uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k, vbm25_reranker **out) {
+// from_index: the ctids are the index's own (vbm25_reranker_create_from_index; `payloads` is NULL then)
+int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vbm25_documents *payloads, bool from_index, uint32_t depth,
+                    uint32_t max_queries, uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k, vbm25_reranker **out) {
     if (!out) return set_error(VBM25_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!t || !rs) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (from_index && !t->from_index)
+        return set_error(VBM25_ERR_INVALID, "the bound documents were not made by vbm25_index_bind: their ctids are not the index's");
     if (depth < 1 || depth > 16) return set_error(VBM25_ERR_INVALID, "depth %u is outside 1 .. 16", depth);
     if (!max_queries || !max_lexemes || !max_candidates || !max_k)
         return set_error(VBM25_ERR_INVALID, "max_queries, max_lexemes, max_candidates or max_k is 0");
@@ -247,14 +250,15 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
     r->vocab = static_cast<const Key *>(v.keys);
     r->has_seed = sd.has_seed;
     r->seed = sd.seed;
-    r->has_payloads = payloads != nullptr;
+    const bool has_payloads = payloads != nullptr || from_index;
+    r->has_payloads = has_payloads;
     r->zero_off.assign(size_t(max_queries) + 1, 0u);
     // a query of several parts has more than `part` candidates, so its ceil(n / part) lists are fewer than 2 n / part; and every
     // query adds at most one list to the quotient of the whole
     const uint64_t part = rerank_part_now();
     r->max_lists = std::min(2 * (max_candidates / part) + 1, max_candidates / part + max_queries);
     const uint64_t nq1 = uint64_t(max_queries) + 1, nl1 = uint64_t(max_lexemes) + 1;
-    r->in_capacity = Layout(max_queries, true, max_queries, max_lexemes, max_lexemes, max_candidates, payloads ? CAND_TID : CAND_DOC, max_bytes).bytes;
+    r->in_capacity = Layout(max_queries, true, max_queries, max_lexemes, max_lexemes, max_candidates, has_payloads ? CAND_TID : CAND_DOC, max_bytes).bytes;
     const size_t out_bytes = size_t(max_queries) * max_k * sizeof(vbm25_rank) + 4ull * max_queries;
     for (uint32_t i = 0; i < depth; ++i) {
         RerankSlot &s = r->slots[i];
@@ -275,12 +279,18 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
         HIP_TRY(r->device_alloc(s.cub, r->cub_bytes));
         HIP_TRY(r->device_alloc(s.res_q_off, 4 * nq1));
         HIP_TRY(r->device_alloc(s.res_ids, 4ull * max_lexemes));
-        if (payloads) HIP_TRY(r->device_alloc(s.cand_doc, 4 * max_candidates));
+        if (has_payloads) HIP_TRY(r->device_alloc(s.cand_doc, 4 * max_candidates));
         HIP_TRY(r->device_alloc(s.out, out_bytes));
         HIP_TRY(r->device_alloc(s.scr, part_list_bytes(r->max_lists, max_k)));
     }
-    if (payloads)
-        if (int rc = build_directory(r, payloads)) return rc;
+    if (payloads) {
+        if (int rc = build_directory(r, payloads->d_payload.as<uint16_t>(), payloads->n_docs)) return rc;
+    } else if (from_index) {  // (an index-bound handle has the index's n_docs documents, in its order)
+        const uint16_t *plane = nullptr;
+        uint32_t n = 0;
+        if (int rc = index_payloads(t->index, &plane, &n)) return rc;
+        if (int rc = build_directory(r, plane, n)) return rc;
+    }
     *out = r;
     guard.r = nullptr;
     return VBM25_OK;
@@ -446,7 +456,12 @@ extern "C" {
 
 int vbm25_reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vbm25_documents *payloads, uint32_t depth, uint32_t max_queries,
                           uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k, vbm25_reranker **out) {
-    return guarded([&] { return reranker_create(t, rs, payloads, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, out); });
+    return guarded([&] { return reranker_create(t, rs, payloads, false, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, out); });
+}
+
+int vbm25_reranker_create_from_index(const vbm25_doc_terms *t, const vbm25_resolver *rs, uint32_t depth, uint32_t max_queries, uint32_t max_lexemes,
+                                     uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k, vbm25_reranker **out) {
+    return guarded([&] { return reranker_create(t, rs, nullptr, true, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, out); });
 }
 
 void vbm25_reranker_free(vbm25_reranker *r) {

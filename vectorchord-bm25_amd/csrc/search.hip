@@ -1308,7 +1308,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
-// and each scorer call); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
+// and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create).
 int vbm25_tuning_set(const char *name, long long value) {
     if (!name) return set_error(VBM25_ERR_INVALID, "NULL argument");
@@ -1349,6 +1349,9 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "eval_grid") {  // (the grid cap of vbm25_documents_bind / vbm25_evaluate_documents: evaluate.hip keeps and reads it)
         if (int rc = vbm25::evaluate_tuning_set(value)) return rc;
     }
+    else if (n == "fwd_grid" || n == "fwd_wave_max" || n == "fwd_group_max") {  // (the grid cap and the class bounds of vbm25_index_bind: forward.hip keeps and reads them)
+        if (int rc = vbm25::forward_tuning_set(name, value)) return rc;
+    }
     else if (n == "rerank_part" || n == "rerank_buf") {  // (the parts and the buffer of vbm25_scorer_topk: rerank.hip keeps and reads them)
         if (int rc = vbm25::rerank_tuning_set(name, value)) return rc;
     }
@@ -1366,6 +1369,7 @@ void vbm25_tuning_reset(void) {
     g_tune.generation = gen;
     vbm25::cast_tuning_reset();
     vbm25::evaluate_tuning_reset();
+    vbm25::forward_tuning_reset();
     vbm25::rerank_tuning_reset();
     vbm25::tid_tuning_reset();
 }

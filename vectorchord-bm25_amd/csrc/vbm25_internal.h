@@ -105,6 +105,14 @@ struct EvaluateTables {
     const double *term_idf, *s1;
 };
 int index_evaluate_tables(const vbm25_index *ix, EvaluateTables *out);
+// ... and the index's payload plane in HBM (6 bytes a sealed document): what a reranker made on an index-bound handle builds its
+// ctid directory from (reranker.hip)
+int index_payloads(const vbm25_index *ix, const uint16_t **payload, uint32_t *n_docs);
+// vbm25_tuning_set's fwd_grid (the most workgroups of vbm25_index_bind's kernels, 0 .. 2048, 0 = no cap), fwd_wave_max and
+// fwd_group_max (its class bounds, 0 = class off, values over the built-in bounds refused); forward.hip keeps them and reads them at
+// the start of each bind
+int forward_tuning_set(const char *name, long long value);
+void forward_tuning_reset();
 // vbm25_tuning_set's eval_grid (evaluate.hip keeps it: the most workgroups of a bind's or a score's kernels, 1 .. 2048) and its reset
 int evaluate_tuning_set(long long value);
 void evaluate_tuning_reset();
