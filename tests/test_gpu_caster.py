@@ -128,6 +128,32 @@ def test_ring(depth):
             c.collect()
 
 
+@pytest.mark.parametrize("depth", (1, 16))
+def test_ring_wraps_at_the_extreme_depths(depth):
+    """2 * depth + 1 batches of two to four documents through a ring of `depth` slots: full, then collect one and submit one until
+    none is left, then drained -- the cursor passes its end twice; every batch against the one-shot Documents.cast"""
+    rng = np.random.default_rng(depth)
+    batches = [cd.docs_of(rng.integers(0, 9, 2 + i % 3).tolist(), seed=100 + i) for i in range(2 * depth + 1)]
+    pays = [cm.payloads(len(b), seed=i) if i % 3 else None for i, b in enumerate(batches)]
+    want = [vb.Documents.cast(b, p, seed=cm.SEED).download() for b, p in zip(batches, pays)]
+    with vb.Caster(0, depth, 4, 64, 2048, seed=cm.SEED) as c:
+        made = (c.allocations(), c.device_bytes())
+        got = []
+        for i, (b, p) in enumerate(zip(batches, pays)):
+            if c.in_flight() == depth:
+                got.append(c.collect().download())  # (downloaded before the slot is taken again)
+            c.submit(b, p)
+            assert c.in_flight() == min(i + 1, depth)
+        while c.in_flight():
+            got.append(c.collect().download())
+        assert len(got) == len(batches)
+        for i, (g, w) in enumerate(zip(got, want)):
+            cm.assert_same(g, w, f"depth {depth} batch {i}")
+        assert (c.allocations(), c.device_bytes()) == made and made[0] == depth * (3 + 2 + 12)  # (max_long_lexemes 0: no general scratch)
+        with pytest.raises(vb.Vbm25Error, match="nothing is in flight"):
+            c.collect()
+
+
 def test_refusals_of_the_cast_word_for_word_and_the_casters_own():
     data = np.frombuffer(b"abc" + b"x" * 17 + b"d\0e", dtype=np.uint8)
     lex_off = np.array([0, 3, 20, 23], dtype=np.uint64)

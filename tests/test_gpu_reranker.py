@@ -172,6 +172,44 @@ def test_the_ring_first_in_first_out(rr, ring_batches, depth):
         assert r.allocations() == made and r.device_bytes() == held
 
 
+@pytest.mark.parametrize("depth", [1, 16])
+def test_the_ring_wraps_at_the_extreme_depths(rr, depth):
+    """2 * depth + 1 batches of two to four queries through a ring of `depth` slots: full, then collect one and submit one until none
+    is left, then drained -- the cursor passes its end twice.  Lists, the cross product and a batch that enqueues nothing in turns,
+    every batch against Resolver + Scorer.topk"""
+    m = rr
+    rng = np.random.default_rng(40 + depth)
+    qs = m["queries"]
+    batches = []
+    for i in range(2 * depth + 1):
+        nq, k = 2 + i % 3, (10, 3, 7)[i % 3]
+        at = int(rng.integers(0, len(qs) - nq))
+        if i % 7 == 3:  # (no query has a candidate: the batch keeps its place and collects as zero rows)
+            qc, cd = np.zeros(nq + 1, np.uint64), np.zeros(0, np.uint32)
+        elif i % 4 == 1:
+            qc, cd = None, None
+        else:
+            qc, cd = lists_csr([rng.integers(0, m["n_docs"], int(n)) for n in rng.integers(0, 80, nq)])
+        batches.append((qs[at:at + nq], k, qc, cd))
+    want = [reference(m, *b) for b in batches]
+    with m["dt"].reranker(m["world"].resolver, depth, max_queries=4, max_lexemes=4096, max_bytes=1 << 18, max_candidates=4096, max_k=10) as r:
+        made = (r.allocations(), r.device_bytes())
+        got = []
+        for i, b in enumerate(batches):
+            if r.in_flight() == depth:
+                got.append(r.collect())
+            r.submit(*b)
+            assert r.in_flight() == min(i + 1, depth)
+        while r.in_flight():
+            got.append(r.collect())
+        assert len(got) == len(batches)
+        for i, (g, w) in enumerate(zip(got, want)):
+            same(g, w, f"depth {depth}, batch {i}")
+        assert (r.allocations(), r.device_bytes()) == made
+        with pytest.raises(vb.Vbm25Error, match="nothing is in flight on the reranker"):
+            r.collect()
+
+
 # ---- 3. term ids
 
 

@@ -278,6 +278,36 @@ def test_ring_50_rounds_on_one_resolver():
         assert np.array_equal(ids, want[0]) and np.array_equal(off, want[1])
 
 
+@pytest.mark.parametrize("depth", [1, 16])
+def test_ring_wraps_at_the_extreme_depths(depth):
+    """2 * depth + 1 batches through a ring of `depth` slots: full, then collect one and submit one until none is left, then drained
+    -- the cursor passes its end twice; the lexeme and the keys entry in turns, every batch against the host's query step"""
+    gix, keys = index_of(1000)
+    r = vb.Resolver(gix, depth, 8, 256, 8192, seed=SEED)
+    bytes_at_create = r.device_bytes
+    rng = np.random.default_rng(200 + depth)  # two to four queries of 0 .. 8 lexemes a batch, some of them unknown
+    batches = [[[vocab_lexeme(int(t)) for t in rng.integers(0, 1030, int(rng.integers(0, 9)))] for _ in range(2 + i % 3)]
+               for i in range(2 * depth + 1)]
+    want = [expected(gix, b) for b in batches]
+    got = []
+    for i, b in enumerate(batches):
+        if r.in_flight == depth:
+            got.append(r.collect())
+        if i % 2:
+            r.submit_keys(*keys_of(b))
+        else:
+            r.submit(b)
+        assert r.in_flight == min(i + 1, depth)
+    while r.in_flight:
+        got.append(r.collect())
+    assert len(got) == len(batches)
+    for i, ((ids, off), (want_ids, want_off)) in enumerate(zip(got, want)):
+        assert np.array_equal(ids, want_ids) and np.array_equal(off, want_off), f"depth {depth}, batch {i}"
+    assert r.device_bytes == bytes_at_create
+    with pytest.raises(vb.Vbm25Error, match="nothing is in flight"):
+        r.collect()
+
+
 def test_refused_submit_then_a_good_one():
     gix, keys = index_of(1000)
     r = vb.Resolver(gix, 2, 4, 16, 64, seed=None)

@@ -133,6 +133,30 @@ def test_snapshot_rule():
     assert n_growing > 0
 
 
+@pytest.mark.parametrize("depth", [1, 16])
+def test_ring_wraps_at_the_extreme_depths(depth):
+    """2 * depth + 1 batches of two to four queries through a ring of `depth` batches: full, then collect one and submit one until
+    none is left, then drained -- the cursor passes its end twice; every batch against vbm25_search_batch"""
+    c, seg, gix, _ = _base()
+    k = 10
+    batches = [make_queries(c, 2 + i % 3, 4, seed=700 + 40 * depth + i) for i in range(2 * depth + 1)]
+    want = [vb.search_batch(gix, terms, off, k) for terms, off in batches]
+    st = vb.Stream(gix, depth, 4, max(len(t) for t, _ in batches), k)
+    _raise(INVALID, st.collect_raw)
+    got = []
+    for i, (terms, off) in enumerate(batches):
+        if st.in_flight == depth:
+            got.append(st.collect())
+        st.submit(terms, off)
+        assert st.in_flight == min(i + 1, depth)
+    while st.in_flight:
+        got.append(st.collect())
+    assert len(got) == len(batches)
+    for i, (w, g) in enumerate(zip(want, got)):
+        same(w, g, f"depth {depth}, batch {i}")
+    _raise(INVALID, st.collect_raw)
+
+
 MODES = ["segment", "filter", "both"]
 
 

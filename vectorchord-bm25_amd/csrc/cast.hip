@@ -45,11 +45,13 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "vbm25_internal.h"
 #include "device_segment.h"
+#include "ring.h"
 #include "cast_lane.h"
 #include "lexeme_input.h"
 
@@ -498,13 +500,13 @@ int documents_cast(int device, const uint8_t *seed32, const uint8_t *bytes, cons
     // buffers and waited for by `quiesce` behind it: the stream is idle before it is destroyed, and both before anything is freed
     Event ev_start, ev_mid, ev_resume, ev_done;
     Stream st;
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(st.create());
     Quiesce quiesce(st.s);
-    HIP_TRY(hipEventCreate(&ev_start.e));
-    HIP_TRY(hipEventCreate(&ev_done.e));
-    HIP_TRY(hipEventCreate(&ev_mid.e));
-    HIP_TRY(hipEventCreate(&ev_resume.e));
-    HIP_TRY(hipHostMalloc((void **)&stage.p, total, hipHostMallocDefault));
+    HIP_TRY(ev_start.create());
+    HIP_TRY(ev_done.create());
+    HIP_TRY(ev_mid.create());
+    HIP_TRY(ev_resume.create());
+    HIP_TRY(stage.alloc(total));
     uint8_t *const staged = stage.as<uint8_t>();
     std::memcpy(staged + o_doc, doc_lex, 4ull * (n_docs + 1ull));
     std::memcpy(staged + o_off, lex_off, 8ull * (n_lex + 1ull));
@@ -646,7 +648,7 @@ int build_documents(const vbm25_documents *h, double k1, double b, vbm25_device_
     Stream st;  // (of the call's own, as the cast's)
     Quiesce quiesce;
     if (n) {
-        HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+        HIP_TRY(st.create());
         quiesce.s = st.s;
         size_t sort_b = 0, scan_b = 0;
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, int(n),
@@ -725,10 +727,10 @@ struct StageLayout {
 };
 
 struct CastSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t start = nullptr, done = nullptr;
-    uint8_t *stage = nullptr;    // pinned: the staged block of one batch
-    ull *n_elements = nullptr;   // pinned: start[n_docs], copied back behind the scan
+    Stream stream;
+    Event start, done;
+    PinnedHost stage;            // the staged block of one batch
+    PinnedHost n_elements;       // one ull: start[n_docs], copied back behind the scan
     HbmArray in, keys, tmp_key, tmp_tf, counts, cub, g_src, g_slot, g_ka, g_kb, g_va, g_vb, g_prefix, g_head_pos;
     vbm25_documents docs;        // the result arrays, at the caster's capacities; what collect hands out
     uint32_t launched = 0;       // LAUNCHED_* of the slot's last batch
@@ -739,36 +741,18 @@ enum : uint32_t { LAUNCHED_INTERN = 1, LAUNCHED_WAVE = 2, LAUNCHED_PACK = 4, LAU
 
 }  // namespace
 
+// vbm25_caster_free waits for every slot's stream before it deletes: the order of the members below does not matter to their destructors.
 struct vbm25_caster {
     int device = 0;
-    uint32_t depth = 0, max_docs = 0, max_lexemes = 0, max_long = 0;
-    uint64_t max_bytes = 0, device_bytes = 0, allocations = 0;
+    uint32_t max_docs = 0, max_lexemes = 0, max_long = 0;
+    uint64_t max_bytes = 0;
     bool has_seed = false;
     Seed seed{};
     size_t in_capacity = 0, cub_bytes = 0;
+    ResourceTally tally;  // every allocation and creation of the handle goes through it
     CastSlot slots[16];
-    uint32_t head = 0, count = 0;  // the oldest slot in flight; slots in flight
+    RingCursor ring;
     int last_collected = -1;
-
-    // every allocation and creation of the handle goes through these: `allocations` is their number
-    hipError_t device_alloc(HbmArray &a, size_t n) {
-        ++allocations;
-        const hipError_t e = a.alloc(n);
-        if (e == hipSuccess) device_bytes += a.footprint();
-        return e;
-    }
-    hipError_t pinned_alloc(void **p, size_t n) {
-        ++allocations;
-        return hipHostMalloc(p, n ? n : 16, hipHostMallocDefault);
-    }
-    hipError_t stream_create(hipStream_t *st) {
-        ++allocations;
-        return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    }
-    hipError_t event_create(hipEvent_t *e) {
-        ++allocations;
-        return hipEventCreate(e);
-    }
 };
 
 namespace {
@@ -784,15 +768,11 @@ int caster_create(int device, const uint8_t *seed32, uint32_t depth, uint32_t ma
     if (max_long_lexemes > max_lexemes) return set_error(VBM25_ERR_INVALID, "max_long_lexemes %u exceeds max_lexemes %u", max_long_lexemes, max_lexemes);
     if (max_bytes >= (1ull << 40)) return set_error(VBM25_ERR_INVALID, "max_bytes %llu is 2^40 or more", (unsigned long long)max_bytes);
     if (int rc = use_cast_device(device)) return rc;
-    struct Guard {
-        vbm25_caster *c;
-        ~Guard() {
-            if (c) vbm25_caster_free(c);
-        }
-    } guard{new vbm25_caster};
-    vbm25_caster *c = guard.c;
+    std::unique_ptr<vbm25_caster, void (*)(vbm25_caster *)> guard(new vbm25_caster, vbm25_caster_free);
+    vbm25_caster *c = guard.get();
+    ResourceTally &ta = c->tally;
     c->device = device;
-    c->depth = depth;
+    c->ring.depth = depth;
     c->max_docs = max_docs;
     c->max_lexemes = max_lexemes;
     c->max_bytes = max_bytes;
@@ -804,40 +784,39 @@ int caster_create(int device, const uint8_t *seed32, uint32_t depth, uint32_t ma
     const uint64_t nd = max_docs, nl = max_lexemes, ng = max_long_lexemes;
     for (uint32_t i = 0; i < depth; ++i) {
         CastSlot &s = c->slots[i];
-        HIP_TRY(c->stream_create(&s.stream));
-        HIP_TRY(c->event_create(&s.start));
-        HIP_TRY(c->event_create(&s.done));
+        HIP_TRY(ta.stream_create(s.stream));
+        HIP_TRY(ta.event_create(s.start));
+        HIP_TRY(ta.event_create(s.done));
         if (i == 0)
-            if (int rc = cast_cub_bytes(max_docs, max_long_lexemes, s.stream, &c->cub_bytes)) return rc;
-        HIP_TRY(c->pinned_alloc((void **)&s.stage, c->in_capacity));
-        HIP_TRY(c->pinned_alloc((void **)&s.n_elements, 8));
-        HIP_TRY(c->device_alloc(s.in, c->in_capacity));
-        HIP_TRY(c->device_alloc(s.keys, 16 * nl));
-        HIP_TRY(c->device_alloc(s.tmp_key, 16 * nl));
-        HIP_TRY(c->device_alloc(s.tmp_tf, 4 * nl));
-        HIP_TRY(c->device_alloc(s.counts, 4 * (nd + 1)));
-        HIP_TRY(c->device_alloc(s.cub, c->cub_bytes));
+            if (int rc = cast_cub_bytes(max_docs, max_long_lexemes, s.stream.s, &c->cub_bytes)) return rc;
+        HIP_TRY(ta.pinned_alloc(s.stage, c->in_capacity));
+        HIP_TRY(ta.pinned_alloc(s.n_elements, 8));
+        HIP_TRY(ta.device_alloc(s.in, c->in_capacity));
+        HIP_TRY(ta.device_alloc(s.keys, 16 * nl));
+        HIP_TRY(ta.device_alloc(s.tmp_key, 16 * nl));
+        HIP_TRY(ta.device_alloc(s.tmp_tf, 4 * nl));
+        HIP_TRY(ta.device_alloc(s.counts, 4 * (nd + 1)));
+        HIP_TRY(ta.device_alloc(s.cub, c->cub_bytes));
         if (ng) {
-            HIP_TRY(c->device_alloc(s.g_src, 4 * ng));
-            HIP_TRY(c->device_alloc(s.g_slot, 4 * ng));
-            HIP_TRY(c->device_alloc(s.g_ka, 8 * ng));
-            HIP_TRY(c->device_alloc(s.g_kb, 8 * ng));
-            HIP_TRY(c->device_alloc(s.g_va, 4 * ng));
-            HIP_TRY(c->device_alloc(s.g_vb, 4 * ng));
-            HIP_TRY(c->device_alloc(s.g_prefix, 8 * ng));
-            HIP_TRY(c->device_alloc(s.g_head_pos, 4 * (ng + 1)));
+            HIP_TRY(ta.device_alloc(s.g_src, 4 * ng));
+            HIP_TRY(ta.device_alloc(s.g_slot, 4 * ng));
+            HIP_TRY(ta.device_alloc(s.g_ka, 8 * ng));
+            HIP_TRY(ta.device_alloc(s.g_kb, 8 * ng));
+            HIP_TRY(ta.device_alloc(s.g_va, 4 * ng));
+            HIP_TRY(ta.device_alloc(s.g_vb, 4 * ng));
+            HIP_TRY(ta.device_alloc(s.g_prefix, 8 * ng));
+            HIP_TRY(ta.device_alloc(s.g_head_pos, 4 * (ng + 1)));
         }
         s.docs.device = device;
         s.docs.caster = c;
-        HIP_TRY(c->device_alloc(s.docs.d_start, 8 * (nd + 1)));
-        HIP_TRY(c->device_alloc(s.docs.d_key, 16 * nl));
-        HIP_TRY(c->device_alloc(s.docs.d_tf, 4 * nl));
-        HIP_TRY(c->device_alloc(s.docs.d_length, 4 * nd));
-        HIP_TRY(c->device_alloc(s.docs.d_fieldnorm, nd));
-        HIP_TRY(c->device_alloc(s.docs.d_payload, 6 * nd));
+        HIP_TRY(ta.device_alloc(s.docs.d_start, 8 * (nd + 1)));
+        HIP_TRY(ta.device_alloc(s.docs.d_key, 16 * nl));
+        HIP_TRY(ta.device_alloc(s.docs.d_tf, 4 * nl));
+        HIP_TRY(ta.device_alloc(s.docs.d_length, 4 * nd));
+        HIP_TRY(ta.device_alloc(s.docs.d_fieldnorm, nd));
+        HIP_TRY(ta.device_alloc(s.docs.d_payload, 6 * nd));
     }
-    *out = c;
-    guard.c = nullptr;
+    *out = guard.release();
     return VBM25_OK;
 }
 
@@ -847,7 +826,7 @@ int caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off
     const uint32_t wave_max = g_wave_max.load(), group_max = g_group_max.load(), pack = g_cast_pack.load(), grid_cap = g_cast_grid.load();
     Shape sh;
     if (int rc = check_documents(c->has_seed, bytes, lex_off, lex_count, doc_lex, n_docs, &sh)) return rc;
-    if (c->count == c->depth) return set_error(VBM25_ERR_INVALID, "the caster's %u slots are all in flight: collect first", c->depth);
+    if (c->ring.full()) return set_error(VBM25_ERR_INVALID, "the caster's %u slots are all in flight: collect first", c->ring.depth);
     if (n_docs > c->max_docs) return set_error(VBM25_ERR_INVALID, "%u documents exceed the caster's max_docs %u", n_docs, c->max_docs);
     if (sh.n_lex > c->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u lexemes exceed the caster's max_lexemes %u", sh.n_lex, c->max_lexemes);
     if (sh.n_bytes > c->max_bytes)
@@ -877,16 +856,16 @@ int caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off
     }
     const uint32_t n_lex = sh.n_lex, n_wave = n_class[0], n_group = n_class[1], n_gen = n_class[2], n_gen_el = uint32_t(gen_el);
     if (int rc = use_device(c->device)) return rc;
-    CastSlot &s = c->slots[(c->head + c->count) % c->depth];
+    CastSlot &s = c->slots[c->ring.tail()];
     {  // (hipcub is asked again for this batch's sizes -- a question, nothing is enqueued: its answer for less is expected to be less)
         size_t need = 0;
-        if (int rc = cast_cub_bytes(n_docs, n_gen_el, s.stream, &need)) return rc;
+        if (int rc = cast_cub_bytes(n_docs, n_gen_el, s.stream.s, &need)) return rc;
         if (need > c->cub_bytes)
             return set_error(VBM25_ERR_UNSUPPORTED, "hipcub asks for %zu bytes of temporary storage for this batch, the caster holds %zu", need, c->cub_bytes);
     }
     const StageLayout L(n_docs, n_lex, n_gen, n_plan, sh.n_bytes);
     // pass 2: the lists, the general class's offsets and the plan, straight into the pinned block
-    uint8_t *const staged = s.stage;
+    uint8_t *const staged = s.stage.as<uint8_t>();
     std::memcpy(staged + L.o_doc, doc_lex, 4ull * (n_docs + 1ull));
     std::memcpy(staged + L.o_off, lex_off, 8ull * (n_lex + 1ull));
     if (n_lex) std::memcpy(staged + L.o_cnt, lex_count, 4ull * n_lex);
@@ -911,21 +890,15 @@ int caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off
     if (sh.n_bytes) std::memcpy(staged + L.o_bytes, bytes, sh.n_bytes);
     if (L.total > L.o_bytes + sh.n_bytes) std::memset(staged + L.o_bytes + sh.n_bytes, 0, L.total - L.o_bytes - sh.n_bytes);
 
-    hipStream_t st = s.stream;
+    hipStream_t st = s.stream.s;
     vbm25_documents &h = s.docs;
     uint8_t *d = s.in.as<uint8_t>();
     // a HIP error from here on leaves the slot out of the ring but with work enqueued: wait for it before the refusal returns, so that
-    // the next submit, which takes this slot again, writes its pinned block under no copy in flight
-    struct Drain {
-        hipStream_t st;
-        bool armed;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(st);
-        }
-    } drain{st, true};
+    // the next submit, which takes this slot again, writes its pinned block under no copy in flight.  Let go of on success.
+    Quiesce quiesce(st);
     HIP_TRY(hipMemcpyAsync(d, staged, L.total, hipMemcpyHostToDevice, st));
     if (doc_payload && n_docs) HIP_TRY(hipMemcpyAsync(h.d_payload.p, staged + L.o_pay, 6ull * n_docs, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(s.start, st));
+    HIP_TRY(hipEventRecord(s.start.e, st));
     HIP_TRY(hipMemsetAsync(s.counts.p, 0, 4ull * (n_docs + 1ull), st));
     const uint32_t *d_doc = reinterpret_cast<const uint32_t *>(d + L.o_doc), *d_cnt = reinterpret_cast<const uint32_t *>(d + L.o_cnt),
                    *d_list = reinterpret_cast<const uint32_t *>(d + L.o_list), *d_goff = reinterpret_cast<const uint32_t *>(d + L.o_goff),
@@ -971,20 +944,20 @@ int caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.cub.p, tb, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(s.counts.as<uint32_t>(), WidenU32()),
                                             h.d_start.as<ull>(), int(n_docs + 1), st));
     // (key / tf have room for every lexeme: the gather goes straight behind the scan, and the number of elements travels home beside it)
-    HIP_TRY(hipMemcpyAsync(s.n_elements, h.d_start.as<ull>() + n_docs, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s.n_elements.p, h.d_start.as<ull>() + n_docs, 8, hipMemcpyDeviceToHost, st));
     if (n_docs) {
         cast_gather_kernel<<<grid_for(n_docs, WG / 64, cap), WG, 0, st>>>(s.tmp_key.as<Key>(), s.tmp_tf.as<uint32_t>(), d_doc, h.d_start.as<ull>(), n_docs, d_fn,
                                                                           h.d_key.as<Key>(), h.d_tf.as<uint32_t>(), h.d_length.as<uint32_t>(),
                                                                           h.d_fieldnorm.as<uint8_t>());
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(s.done, st));
+    HIP_TRY(hipEventRecord(s.done.e, st));
     h.n_docs = n_docs;
     h.n_elements = 0;  // (known at collect)
     h.has_payload = doc_payload != nullptr;
     s.launched = launched;
-    drain.armed = false;
-    ++c->count;
+    c->ring.push();
+    quiesce.s = nullptr;
     return VBM25_OK;
 }
 
@@ -992,15 +965,13 @@ int caster_collect(vbm25_caster *c, const vbm25_documents **out) {
     if (!out) return set_error(VBM25_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (!c) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (!c->count) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the caster");
+    if (c->ring.empty()) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the caster");
     if (int rc = use_device(c->device)) return rc;
-    CastSlot &s = c->slots[c->head];
-    HIP_TRY(hipEventSynchronize(s.done));
-    s.docs.n_elements = *s.n_elements;
+    CastSlot &s = c->slots[c->ring.head];
+    HIP_TRY(hipEventSynchronize(s.done.e));
+    s.docs.n_elements = *s.n_elements.as<ull>();
     *out = &s.docs;
-    c->last_collected = int(c->head);
-    c->head = (c->head + 1) % c->depth;
-    --c->count;
+    c->last_collected = int(c->ring.pop());
     return VBM25_OK;
 }
 
@@ -1035,7 +1006,7 @@ int documents_extend(vbm25_documents *dst, const vbm25_documents *src) {
     const int n_parts = dst->has_payload ? 6 : 5;
     HbmArray grown[6];
     Stream st;  // (of the call's own, as the cast's)
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(st.create());
     Quiesce quiesce(st.s);
     // every larger array first: a failure so far leaves dst as it was.  Capacities at least double, so appending n chunks copies O(n) bytes.
     for (int i = 0; i < n_parts; ++i) {
@@ -1136,24 +1107,17 @@ void vbm25_caster_free(vbm25_caster *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (CastSlot &s : c->slots)
-        if (s.stream) (void)hipStreamSynchronize(s.stream);  // nothing is freed under a kernel or a copy in flight
-    for (CastSlot &s : c->slots) {
-        if (s.stage) (void)hipHostFree(s.stage);
-        if (s.n_elements) (void)hipHostFree(s.n_elements);
-        if (s.start) (void)hipEventDestroy(s.start);
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
-    delete c;
+        if (s.stream.s) (void)hipStreamSynchronize(s.stream.s);  // nothing is freed under a kernel or a copy in flight
+    delete c;  // (with the slots' vbm25_documents: a collected handle is not used after this)
 }
 
-uint64_t vbm25_caster_device_bytes(const vbm25_caster *c) { return c ? c->device_bytes : 0; }
+uint64_t vbm25_caster_device_bytes(const vbm25_caster *c) { return c ? c->tally.device_bytes : 0; }
 
 int vbm25_caster_info(const vbm25_caster *c, uint32_t *depth, int *device, uint64_t *allocations) {
     if (!c) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (depth) *depth = c->depth;
+    if (depth) *depth = c->ring.depth;
     if (device) *device = c->device;
-    if (allocations) *allocations = c->allocations;
+    if (allocations) *allocations = c->tally.allocations;
     return VBM25_OK;
 }
 
@@ -1166,14 +1130,13 @@ int vbm25_caster_collect(vbm25_caster *c, const vbm25_documents **out) {
     return guarded([&] { return caster_collect(c, out); });
 }
 
-int vbm25_caster_in_flight(const vbm25_caster *c) { return c ? int(c->count) : 0; }
+int vbm25_caster_in_flight(const vbm25_caster *c) { return c ? int(c->ring.count) : 0; }
 
 // tools/caster_cost.py: the device time of the last collected batch's kernels (upload excluded), by the slot's HIP events.  Not in the header.
 int vbm25_debug_caster_kernel_ms(vbm25_caster *c, double *ms) {
     if (!c || !ms || c->last_collected < 0) return set_error(VBM25_ERR_INVALID, "no collected batch");
-    float f = 0;
-    HIP_TRY(hipEventElapsedTime(&f, c->slots[c->last_collected].start, c->slots[c->last_collected].done));
-    *ms = f;
+    const CastSlot &s = c->slots[c->last_collected];
+    HIP_TRY(elapsed_ms(s.start, s.done, ms));
     return VBM25_OK;
 }
 

@@ -145,9 +145,9 @@ int documents_bind(const vbm25_documents *h, const vbm25_resolver *r, vbm25_doc_
     HbmArray ids, counts, cub;
     Event ev_start, ev_mid, ev_resume, ev_done;
     Stream st;  // (of the call's own: a launch on the null stream would wait for every other stream of the device)
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(st.create());
     Quiesce quiesce(st.s);
-    for (Event *e : {&ev_start, &ev_mid, &ev_resume, &ev_done}) HIP_TRY(hipEventCreate(&e->e));
+    for (Event *e : {&ev_start, &ev_mid, &ev_resume, &ev_done}) HIP_TRY(e->create());
     size_t cub_bytes = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
                                             (ull *)nullptr, int(n_docs + 1), st.s));
@@ -220,10 +220,10 @@ int evaluate_documents(const vbm25_doc_terms *t, const uint32_t *term_ids, const
     HbmArray d_ids, d_off, d_cand, d_doc, d_items, d_scores;
     Event ev_start, ev_done;
     Stream st;  // (of the call's own, as the bind's)
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(st.create());
     Quiesce quiesce(st.s);
-    HIP_TRY(hipEventCreate(&ev_start.e));
-    HIP_TRY(hipEventCreate(&ev_done.e));
+    HIP_TRY(ev_start.create());
+    HIP_TRY(ev_done.create());
     HIP_TRY(d_ids.alloc(4ull * n_ids));
     HIP_TRY(d_off.alloc(4ull * (nq + 1ull)));
     HIP_TRY(d_items.alloc(4ull * (nq + 1ull)));

@@ -270,9 +270,9 @@ int index_bind(const vbm25_index *ix, vbm25_doc_terms **out) {
     HbmArray counts, cub, cls, group_doc, long_doc, long_begin, long_end, buf_term, buf_tf, buf_term2, buf_tf2, seg_cub;
     Event ev_start, ev_mid, ev_resume, ev_done;
     Stream st;  // (of the call's own: a launch on the null stream would wait for every other stream of the device)
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(st.create());
     Quiesce quiesce(st.s);
-    for (Event *e : {&ev_start, &ev_mid, &ev_resume, &ev_done}) HIP_TRY(hipEventCreate(&e->e));
+    for (Event *e : {&ev_start, &ev_mid, &ev_resume, &ev_done}) HIP_TRY(e->create());
     size_t cub_bytes = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(nullptr, WidenU32()),
                                             (ull *)nullptr, int(n_docs + 1), st.s));

@@ -1,5 +1,6 @@
 // hip_host.h -- the host plumbing around every kernel launch of libvbm25, once: the error macro, the owners of an HBM allocation, of
-// pinned host memory, of a stream and of an event, launch-grid and layout arithmetic, and the hipcub calling convention.
+// pinned host memory, of a stream and of an event, the tally of what a handle took at create, launch-grid and layout arithmetic, and
+// the hipcub calling convention.
 // Host-side and HIP-only: every .hip translation unit includes it (device_segment.h does so for them) and defines none of this
 // itself; the lane and parse headers that plain g++ compiles for the harnesses under tests/native/ must not.  Not part of the ABI.
 #ifndef VBM25_HIP_HOST_H
@@ -61,6 +62,8 @@ struct PinnedHost {
     ~PinnedHost() {
         if (p) (void)hipHostFree(p);
     }
+    // (a zero-length request still allocates 16 bytes, as HbmArray's.)  alloc() on a block that holds memory leaks it.
+    hipError_t alloc(size_t n) { return hipHostMalloc(&p, n ? n : 16, hipHostMallocDefault); }
     template <class T>
     T *as() const {
         return static_cast<T *>(p);
@@ -75,6 +78,8 @@ struct Stream {
     ~Stream() {
         if (s) (void)hipStreamDestroy(s);
     }
+    // a stream of the handle's or the call's own, which waits for no other: work on the null stream would wait for every stream of the device
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 };
 
 struct Event {
@@ -85,6 +90,7 @@ struct Event {
     ~Event() {
         if (e) (void)hipEventDestroy(e);
     }
+    hipError_t create() { return hipEventCreate(&e); }  // (with timing)
 };
 
 // Waits for a stream when it goes out of scope.  Declared behind a call's buffers and its Stream, so destroyed before them: nothing is
@@ -99,6 +105,39 @@ struct Quiesce {
         if (s) (void)hipStreamSynchronize(s);
     }
 };
+
+// What a handle that allocates nothing per call took at create: every allocation and creation of such a handle goes through its
+// tally.  `allocations` is their number, `device_bytes` the footprint of the HBM arrays the handle keeps (kept = false: a temporary
+// of create, counted as an allocation and freed before create returns).
+struct ResourceTally {
+    uint64_t allocations = 0, device_bytes = 0;
+    hipError_t device_alloc(HbmArray &a, size_t n, bool kept = true) {
+        ++allocations;
+        const hipError_t e = a.alloc(n);
+        if (e == hipSuccess && kept) device_bytes += a.footprint();
+        return e;
+    }
+    hipError_t pinned_alloc(PinnedHost &h, size_t n) {
+        ++allocations;
+        return h.alloc(n);
+    }
+    hipError_t stream_create(Stream &st) {
+        ++allocations;
+        return st.create();
+    }
+    hipError_t event_create(Event &ev) {
+        ++allocations;
+        return ev.create();
+    }
+};
+
+// the device time between two events of a stream, both reached (a collected slot's start and done)
+inline hipError_t elapsed_ms(const Event &from, const Event &to, double *ms) {
+    float f = 0;
+    const hipError_t e = hipEventElapsedTime(&f, from.e, to.e);
+    *ms = f;
+    return e;
+}
 
 static_assert(!std::is_copy_constructible_v<HbmArray> && !std::is_copy_assignable_v<HbmArray>, "an owner is never copied");
 static_assert(!std::is_copy_constructible_v<PinnedHost> && !std::is_copy_assignable_v<PinnedHost>, "an owner is never copied");

@@ -93,7 +93,7 @@ struct Stager {
     int init(hipStream_t stream) {
         s = stream;
         for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipHostMalloc(&pin[i].p, (size_t)CHUNK_PAGES * BLCKSZ, hipHostMallocDefault));
+            HIP_TRY(pin[i].alloc((size_t)CHUNK_PAGES * BLCKSZ));
             HIP_TRY(hipEventCreateWithFlags(&ev[i].e, hipEventDisableTiming));
         }
         return VBM25_OK;
@@ -140,7 +140,7 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     for (double &x : g_stats) x = 0.0;
 
     Stream stream;
-    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(stream.create());
     hipStream_t s = stream.s;
     Stager st;
     if (int rc = st.init(s)) return rc;
@@ -240,7 +240,7 @@ int from_pages_impl(vbm25_read_page_fn read_page, void *ctx, int device, vbm25_d
     unsigned long long *err = d_err.as<unsigned long long>();
 
     Event ev[4];
-    for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+    for (Event &e : ev) HIP_TRY(e.create());
     HIP_TRY(hipEventRecord(ev[0].e, s));
     HIP_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
     HIP_TRY(hipMemsetAsync(d_total.p, 0, 8, s));
@@ -464,7 +464,7 @@ int vectors_csr(hipStream_t s, Stager &st, uint32_t slot, vbm25_read_page_fn rea
     const uint32_t page_grid = grid_for(np, 4, MAX_GRID), tuple_grid = grid_for(n, WG_THREADS, MAX_GRID);
 
     Event ev[4];
-    for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+    for (Event &e : ev) HIP_TRY(e.create());
     HIP_TRY(hipEventRecord(ev[0].e, s));
     HIP_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
     HIP_TRY(hipMemsetAsync(d_fin.p, 0, n + 1, s));
@@ -554,7 +554,7 @@ int growing_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, vo
     for (double &x : g_vec_stats) x = 0.0;
 
     Stream stream;
-    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(stream.create());
     hipStream_t s = stream.s;
     // (the planes before the stager: they go last, after the stream's work has been waited for)
     HbmArray d_start, d_key, d_tf, d_fn, d_del, d_payload;
@@ -670,7 +670,7 @@ int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, voi
     for (double &x : g_vac_stats) x = 0.0;
 
     Stream stream;
-    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(stream.create());
     hipStream_t s = stream.s;
     auto dv = std::make_unique<vbm25_device_vacuum>();  // (before the stager: its planes go last)
     dv->device = device;
@@ -711,7 +711,7 @@ int vacuum_from_pages_impl(vbm25_index *index, vbm25_read_page_fn read_page, voi
         HIP_TRY(hipMemcpyAsync(d_pre.p, w.pre[T_DOCS].data(), 4 * (np + 1), hipMemcpyHostToDevice, s));
         st.bytes_up += 8 * chunk_ptr.size() + 4 * (np + 1);
         Event ev[2];
-        for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+        for (Event &e : ev) HIP_TRY(e.create());
         HIP_TRY(hipEventRecord(ev[0].e, s));
         HIP_TRY(hipMemsetAsync(d_err.p, 0xff, 8, s));
         HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 4, s));

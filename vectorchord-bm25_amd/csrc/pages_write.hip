@@ -100,13 +100,13 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     for (double &x : g_stats) x = 0.0;
 
     Stream stream;
-    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
+    HIP_TRY(stream.create());
     hipStream_t s = stream.s;
     HbmArray d_cost, d_jump[2], d_start, d_count, d_tmp, d_ids, d_key, d_tok_pid, d_sum_pid, d_blk_pid, d_img, d_pid;
     PinnedHost pin[2];
     Event ev_layout[2], ev[2][3];  // ev, per staging buffer: fill begins, fill ends, copies end
     Quiesce quiesce{s};
-    for (Event &e : ev_layout) HIP_TRY(hipEventCreate(&e.e));
+    for (Event &e : ev_layout) HIP_TRY(e.create());
 
     const uint32_t n_docs = seg->n_docs, n_terms = seg->n_terms, n = seg->n_blocks;
     Emit c{};
@@ -211,8 +211,8 @@ int write_impl(const vbm25_device_segment *seg, const uint32_t *page_ids, uint32
     HIP_TRY(d_img.alloc(IMG_BYTES));
     HIP_TRY(d_pid.alloc(PID_BYTES));
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipHostMalloc(&pin[i].p, IMG_BYTES + PID_BYTES, hipHostMallocDefault));
-        for (Event &e : ev[i]) HIP_TRY(hipEventCreate(&e.e));
+        HIP_TRY(pin[i].alloc(IMG_BYTES + PID_BYTES));
+        for (Event &e : ev[i]) HIP_TRY(e.create());
     }
     Sink sink{fn, ctx};
     std::vector<uint32_t> tok_pid(c.n_pages[T_TOKENS]);

@@ -279,10 +279,9 @@ int grow(HbmArray &a, size_t need) {
 int grow_pinned(vbm25_scorer *sc, size_t need) {
     if (sc->pin.p && sc->pin_bytes >= need) return VBM25_OK;
     const size_t cap = std::max(need, 2 * sc->pin_bytes);
-    void *p = nullptr;
-    HIP_TRY(hipHostMalloc(&p, cap ? cap : 16, hipHostMallocDefault));
-    if (sc->pin.p) (void)hipHostFree(sc->pin.p);
-    sc->pin.p = p;
+    PinnedHost next;
+    HIP_TRY(next.alloc(cap));
+    std::swap(sc->pin.p, next.p);  // (the old block goes with `next`, as in grow)
     sc->pin_bytes = cap;
     return VBM25_OK;
 }
@@ -446,9 +445,9 @@ int scorer_create(const vbm25_doc_terms *t, vbm25_scorer **out) {
     auto sc = std::make_unique<vbm25_scorer>();
     sc->t = t;
     sc->device = t->device;
-    HIP_TRY(hipStreamCreateWithFlags(&sc->st.s, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc->ev_start.e));
-    HIP_TRY(hipEventCreate(&sc->ev_done.e));
+    HIP_TRY(sc->st.create());
+    HIP_TRY(sc->ev_start.create());
+    HIP_TRY(sc->ev_done.create());
     *out = sc.release();
     return VBM25_OK;
 }

@@ -25,10 +25,12 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "vbm25_internal.h"
 #include "device_segment.h"
+#include "ring.h"
 #include "resolve_shared.h"
 #include "evaluate_shared.h"
 #include "rerank_shared.h"
@@ -85,9 +87,9 @@ __global__ void __launch_bounds__(WG) cand_lookup_kernel(LookupArgs a) {
 }
 
 struct RerankSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t start = nullptr, done = nullptr;
-    uint8_t *pin_in = nullptr, *pin_out = nullptr;       // pinned: the staged block of one batch; its rows and counts
+    Stream stream;
+    Event start, done;
+    PinnedHost pin_in, pin_out;                           // the staged block of one batch; its rows and counts
     HbmArray in;                                          // the staged block
     HbmArray ids, tmp, counts, q_off, sort_a, sort_b, cub;  // the resolve scratch (resolve_shared.h: PackScratch)
     HbmArray res_q_off, res_ids;                          // the resolved queries
@@ -120,11 +122,12 @@ struct Layout {
 
 }  // namespace
 
+// vbm25_reranker_free waits for every slot's stream before it deletes: the order of the members below does not matter to their destructors.
 struct vbm25_reranker {
     const vbm25_doc_terms *t = nullptr;
     int device = 0;
-    uint32_t depth = 0, max_queries = 0, max_lexemes = 0, max_k = 0, n_terms = 0;
-    uint64_t max_bytes = 0, max_candidates = 0, max_lists = 0, device_bytes = 0, allocations = 0;
+    uint32_t max_queries = 0, max_lexemes = 0, max_k = 0, n_terms = 0;
+    uint64_t max_bytes = 0, max_candidates = 0, max_lists = 0;
     const Key *vocab = nullptr;  // the resolver's, in HBM
     bool has_seed = false;
     Seed seed{};
@@ -134,30 +137,11 @@ struct vbm25_reranker {
     double directory_ms = -1.0;
     size_t in_capacity = 0, cub_bytes = 0;
     std::vector<uint32_t> zero_off;  // max_queries + 1 zeros: the q_off of a lexeme batch before it is resolved
+    ResourceTally tally;  // every allocation and creation of the handle goes through it
     RerankSlot slots[16];
-    uint32_t head = 0, count = 0;  // the oldest slot in flight; slots in flight
+    RingCursor ring;
     int last_collected = -1;
     uint32_t last_path = PATH_NONE;
-
-    // every allocation and creation of the handle goes through these: `allocations` is their number
-    hipError_t device_alloc(HbmArray &a, size_t n, bool kept = true) {
-        ++allocations;
-        const hipError_t e = a.alloc(n);
-        if (e == hipSuccess && kept) device_bytes += a.footprint();
-        return e;
-    }
-    hipError_t pinned_alloc(uint8_t **p, size_t n) {
-        ++allocations;
-        return hipHostMalloc((void **)p, n ? n : 16, hipHostMallocDefault);
-    }
-    hipError_t stream_create(hipStream_t *st) {
-        ++allocations;
-        return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    }
-    hipError_t event_create(hipEvent_t *e) {
-        ++allocations;
-        return hipEventCreate(e);
-    }
 };
 
 namespace {
@@ -167,23 +151,24 @@ int build_directory(vbm25_reranker *r, const uint16_t *payload, uint32_t n) {
     const DirShape shape = dir_shape(n, tid_dir_now());
     r->n_dir = shape.n_dir;
     r->stride = shape.stride;
-    hipStream_t st = r->slots[0].stream;
+    hipStream_t st = r->slots[0].stream.s;
+    ResourceTally &ta = r->tally;
     HbmArray keys_in, docs_in, cub;
     Event ev_start, ev_done;
-    HIP_TRY(r->event_create(&ev_start.e));
-    HIP_TRY(r->event_create(&ev_done.e));
+    HIP_TRY(ta.event_create(ev_start));
+    HIP_TRY(ta.event_create(ev_done));
     Quiesce quiesce(st);  // (behind the temporaries: waited for before they are freed)
-    HIP_TRY(r->device_alloc(r->dir_keys, 8ull * n));
-    HIP_TRY(r->device_alloc(r->dir_docs, 4ull * n));
-    HIP_TRY(r->device_alloc(r->dir, 8ull * r->n_dir));
+    HIP_TRY(ta.device_alloc(r->dir_keys, 8ull * n));
+    HIP_TRY(ta.device_alloc(r->dir_docs, 4ull * n));
+    HIP_TRY(ta.device_alloc(r->dir, 8ull * r->n_dir));
     HIP_TRY(hipEventRecord(ev_start.e, st));
     if (n) {
-        HIP_TRY(r->device_alloc(keys_in, 8ull * n, false));
-        HIP_TRY(r->device_alloc(docs_in, 4ull * n, false));
+        HIP_TRY(ta.device_alloc(keys_in, 8ull * n, false));
+        HIP_TRY(ta.device_alloc(docs_in, 4ull * n, false));
         size_t cub_bytes = 0;
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                                   int(n), 0, 48, st));
-        HIP_TRY(r->device_alloc(cub, cub_bytes, false));
+        HIP_TRY(ta.device_alloc(cub, cub_bytes, false));
         payload_key_kernel<<<grid_for(n, WG, MAX_GRID), WG, 0, st>>>(payload, n, keys_in.as<ull>(), docs_in.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, cub_bytes, keys_in.as<ull>(), r->dir_keys.as<ull>(), docs_in.as<uint32_t>(),
@@ -193,9 +178,7 @@ int build_directory(vbm25_reranker *r, const uint16_t *payload, uint32_t n) {
     }
     HIP_TRY(hipEventRecord(ev_done.e, st));
     HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev_start.e, ev_done.e));
-    r->directory_ms = ms;
+    HIP_TRY(elapsed_ms(ev_start, ev_done, &r->directory_ms));
     return VBM25_OK;
 }
 
@@ -231,16 +214,12 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
     if (int rc = index_evaluate_tables(t->index, &ix)) return rc;
     if (ix.n_docs == 0) return set_error(VBM25_ERR_INVALID, "evaluate on an index without sealed documents");
     if (int rc = use_eval_device(t->device)) return rc;
-    struct Guard {
-        vbm25_reranker *r;
-        ~Guard() {
-            if (r) vbm25_reranker_free(r);
-        }
-    } guard{new vbm25_reranker};
-    vbm25_reranker *r = guard.r;
+    std::unique_ptr<vbm25_reranker, void (*)(vbm25_reranker *)> guard(new vbm25_reranker, vbm25_reranker_free);
+    vbm25_reranker *r = guard.get();
+    ResourceTally &ta = r->tally;
     r->t = t;
     r->device = t->device;
-    r->depth = depth;
+    r->ring.depth = depth;
     r->max_queries = max_queries;
     r->max_lexemes = max_lexemes;
     r->max_bytes = max_bytes;
@@ -262,26 +241,26 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
     const size_t out_bytes = size_t(max_queries) * max_k * sizeof(vbm25_rank) + 4ull * max_queries;
     for (uint32_t i = 0; i < depth; ++i) {
         RerankSlot &s = r->slots[i];
-        HIP_TRY(r->stream_create(&s.stream));
-        HIP_TRY(r->event_create(&s.start));
-        HIP_TRY(r->event_create(&s.done));
+        HIP_TRY(ta.stream_create(s.stream));
+        HIP_TRY(ta.event_create(s.start));
+        HIP_TRY(ta.event_create(s.done));
         if (i == 0)
-            if (int rc = pack_cub_bytes(max_queries, max_lexemes, s.stream, &r->cub_bytes)) return rc;
-        HIP_TRY(r->pinned_alloc(&s.pin_in, r->in_capacity));
-        HIP_TRY(r->pinned_alloc(&s.pin_out, out_bytes));
-        HIP_TRY(r->device_alloc(s.in, r->in_capacity));
-        HIP_TRY(r->device_alloc(s.ids, 4 * nl1));
-        HIP_TRY(r->device_alloc(s.tmp, 4 * nl1));
-        HIP_TRY(r->device_alloc(s.counts, 4 * nq1));
-        HIP_TRY(r->device_alloc(s.q_off, 4 * nq1));
-        HIP_TRY(r->device_alloc(s.sort_a, 8ull * max_lexemes));
-        HIP_TRY(r->device_alloc(s.sort_b, 8ull * max_lexemes + 4 * nl1));
-        HIP_TRY(r->device_alloc(s.cub, r->cub_bytes));
-        HIP_TRY(r->device_alloc(s.res_q_off, 4 * nq1));
-        HIP_TRY(r->device_alloc(s.res_ids, 4ull * max_lexemes));
-        if (has_payloads) HIP_TRY(r->device_alloc(s.cand_doc, 4 * max_candidates));
-        HIP_TRY(r->device_alloc(s.out, out_bytes));
-        HIP_TRY(r->device_alloc(s.scr, part_list_bytes(r->max_lists, max_k)));
+            if (int rc = pack_cub_bytes(max_queries, max_lexemes, s.stream.s, &r->cub_bytes)) return rc;
+        HIP_TRY(ta.pinned_alloc(s.pin_in, r->in_capacity));
+        HIP_TRY(ta.pinned_alloc(s.pin_out, out_bytes));
+        HIP_TRY(ta.device_alloc(s.in, r->in_capacity));
+        HIP_TRY(ta.device_alloc(s.ids, 4 * nl1));
+        HIP_TRY(ta.device_alloc(s.tmp, 4 * nl1));
+        HIP_TRY(ta.device_alloc(s.counts, 4 * nq1));
+        HIP_TRY(ta.device_alloc(s.q_off, 4 * nq1));
+        HIP_TRY(ta.device_alloc(s.sort_a, 8ull * max_lexemes));
+        HIP_TRY(ta.device_alloc(s.sort_b, 8ull * max_lexemes + 4 * nl1));
+        HIP_TRY(ta.device_alloc(s.cub, r->cub_bytes));
+        HIP_TRY(ta.device_alloc(s.res_q_off, 4 * nq1));
+        HIP_TRY(ta.device_alloc(s.res_ids, 4ull * max_lexemes));
+        if (has_payloads) HIP_TRY(ta.device_alloc(s.cand_doc, 4 * max_candidates));
+        HIP_TRY(ta.device_alloc(s.out, out_bytes));
+        HIP_TRY(ta.device_alloc(s.scr, part_list_bytes(r->max_lists, max_k)));
     }
     if (payloads) {
         if (int rc = build_directory(r, payloads->d_payload.as<uint16_t>(), payloads->n_docs)) return rc;
@@ -291,8 +270,7 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
         if (int rc = index_payloads(t->index, &plane, &n)) return rc;
         if (int rc = build_directory(r, plane, n)) return rc;
     }
-    *out = r;
-    guard.r = nullptr;
+    *out = guard.release();
     return VBM25_OK;
 }
 
@@ -314,7 +292,7 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     LexShape sh;
     if (in.lexemes)
         if (int rc = check_lexemes(r->has_seed, in.bytes, in.lex_off, in.q32, nq, &sh)) return rc;
-    if (r->count == r->depth) return set_error(VBM25_ERR_INVALID, "the reranker's %u slots are all in flight: collect first", r->depth);
+    if (r->ring.full()) return set_error(VBM25_ERR_INVALID, "the reranker's %u slots are all in flight: collect first", r->ring.depth);
     if (nq > r->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the reranker's max_queries %u", nq, r->max_queries);
     if (sh.n_lex > r->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u lexemes exceed the reranker's max_lexemes %u", sh.n_lex, r->max_lexemes);
     if (sh.n_bytes > r->max_bytes)
@@ -333,13 +311,13 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     if (k > r->max_k) return set_error(VBM25_ERR_INVALID, "k %u exceeds the reranker's max_k %u", k, r->max_k);
     if (n_pairs > r->max_candidates)
         return set_error(VBM25_ERR_INVALID, "%llu candidates exceed the reranker's max_candidates %llu", (ull)n_pairs, (ull)r->max_candidates);
-    RerankSlot &s = r->slots[(r->head + r->count) % r->depth];
+    RerankSlot &s = r->slots[r->ring.tail()];
     if (n_pairs == 0) {  // no query has a candidate: nothing to enqueue, the batch keeps its place in the ring
         s.nq = nq;
         s.k = k;
         s.enqueued = false;
         r->last_path = PATH_NONE;
-        ++r->count;
+        r->ring.push();
         return VBM25_OK;
     }
     const uint32_t part = rerank_part_now(), buf = buffer_entries(k, rerank_buf_now());
@@ -350,7 +328,7 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     if (int rc = use_eval_device(r->device)) return rc;
     const uint32_t kind = cand_tid ? CAND_TID : q_cand ? CAND_DOC : CAND_CROSS;
     const Layout g(nq, q_cand != nullptr, plan.n_multi, in.lexemes ? sh.n_lex : ~0ull, n_ids, n_pairs, kind, sh.n_bytes);
-    uint8_t *host = s.pin_in;
+    uint8_t *host = s.pin_in.as<uint8_t>();
     const uint8_t *dev = s.in.as<uint8_t>();
     if (q_cand) std::memcpy(host + g.cand, q_cand, 8ull * (nq + 1ull));
     if (kind == CAND_DOC) std::memcpy(host + g.docs, cand_doc, 4ull * n_pairs);
@@ -392,10 +370,10 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     o.ranks = s.out.as<vbm25_rank>();
     o.n_ranks = reinterpret_cast<uint32_t *>(s.out.as<uint8_t>() + rank_bytes);
     std::memcpy(host + g.out, &o, sizeof o);
-    hipStream_t st = s.stream;
+    hipStream_t st = s.stream.s;
     Quiesce quiesce(st);  // (a failed step below leaves nothing in flight on the slot; let go of on success)
     HIP_TRY(hipMemcpyAsync(s.in.p, host, g.bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(s.start, st));
+    HIP_TRY(hipEventRecord(s.start.e, st));
     uint32_t path = PATH_NONE;
     if (in.lexemes) {
         if (int rc = launch_intern(st, r->seed, reinterpret_cast<const uint32_t *>(dev + g.pool), reinterpret_cast<const uint64_t *>(dev + g.lex_off),
@@ -416,37 +394,36 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(launch_topk(a, st));
-    HIP_TRY(hipMemcpyAsync(s.pin_out, s.out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(s.done, st));
-    quiesce.s = nullptr;
+    HIP_TRY(hipMemcpyAsync(s.pin_out.p, s.out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(s.done.e, st));
     s.nq = nq;
     s.k = k;
     s.enqueued = true;
     r->last_path = path;
-    ++r->count;
+    r->ring.push();
+    quiesce.s = nullptr;
     return VBM25_OK;
 }
 
 int reranker_collect(vbm25_reranker *r, vbm25_rank *ranks, uint32_t *n_ranks, uint32_t *nq_out, uint32_t *k_out) {
     if (!r || !nq_out || !k_out) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (!r->count) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the reranker");
-    RerankSlot &s = r->slots[r->head];
+    if (r->ring.empty()) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the reranker");
+    RerankSlot &s = r->slots[r->ring.head];
     if (s.nq && (!ranks || !n_ranks)) return set_error(VBM25_ERR_INVALID, "NULL argument");
     const size_t rank_bytes = size_t(s.nq) * s.k * sizeof(vbm25_rank);
     if (s.enqueued) {
         if (int rc = use_eval_device(r->device)) return rc;
-        HIP_TRY(hipEventSynchronize(s.done));
-        std::memcpy(ranks, s.pin_out, rank_bytes);
-        std::memcpy(n_ranks, s.pin_out + rank_bytes, 4ull * s.nq);
+        HIP_TRY(hipEventSynchronize(s.done.e));
+        std::memcpy(ranks, s.pin_out.p, rank_bytes);
+        std::memcpy(n_ranks, s.pin_out.as<uint8_t>() + rank_bytes, 4ull * s.nq);
     } else if (s.nq) {
         std::memset(ranks, 0, rank_bytes);
         std::memset(n_ranks, 0, 4ull * s.nq);
     }
     *nq_out = s.nq;
     *k_out = s.k;
-    r->last_collected = s.enqueued ? int(r->head) : -1;
-    r->head = (r->head + 1) % r->depth;
-    --r->count;
+    const int released = int(r->ring.pop());
+    r->last_collected = s.enqueued ? released : -1;
     return VBM25_OK;
 }
 
@@ -468,25 +445,18 @@ void vbm25_reranker_free(vbm25_reranker *r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     for (RerankSlot &s : r->slots)
-        if (s.stream) (void)hipStreamSynchronize(s.stream);  // nothing is freed under a kernel or a copy in flight
-    for (RerankSlot &s : r->slots) {
-        if (s.pin_in) (void)hipHostFree(s.pin_in);
-        if (s.pin_out) (void)hipHostFree(s.pin_out);
-        if (s.start) (void)hipEventDestroy(s.start);
-        if (s.done) (void)hipEventDestroy(s.done);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
+        if (s.stream.s) (void)hipStreamSynchronize(s.stream.s);  // nothing is freed under a kernel or a copy in flight
     delete r;
 }
 
-uint64_t vbm25_reranker_device_bytes(const vbm25_reranker *r) { return r ? r->device_bytes : 0; }
+uint64_t vbm25_reranker_device_bytes(const vbm25_reranker *r) { return r ? r->tally.device_bytes : 0; }
 
 int vbm25_reranker_info(const vbm25_reranker *r, uint32_t *depth, uint32_t *n_docs, uint32_t *has_payloads, uint64_t *allocations) {
     if (!r) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (depth) *depth = r->depth;
+    if (depth) *depth = r->ring.depth;
     if (n_docs) *n_docs = r->t->n_docs;
     if (has_payloads) *has_payloads = r->has_payloads ? 1u : 0u;
-    if (allocations) *allocations = r->allocations;
+    if (allocations) *allocations = r->tally.allocations;
     return VBM25_OK;
 }
 
@@ -504,7 +474,7 @@ int vbm25_reranker_collect(vbm25_reranker *r, vbm25_rank *ranks, uint32_t *n_ran
     return guarded([&] { return reranker_collect(r, ranks, n_ranks, nq_out, k_out); });
 }
 
-int vbm25_reranker_in_flight(const vbm25_reranker *r) { return r ? int(r->count) : 0; }
+int vbm25_reranker_in_flight(const vbm25_reranker *r) { return r ? int(r->ring.count) : 0; }
 
 // tools/reranker_cost.py and the tests of the pack paths: the device time of the last collected batch between its slot's events (the
 // upload excluded, the rows' download included; -1 when that batch enqueued nothing), the pack path of the last accepted submit (0 none,
@@ -514,9 +484,8 @@ int vbm25_debug_reranker(const vbm25_reranker *r, double *batch_ms, uint32_t *pa
     if (batch_ms) {
         *batch_ms = -1.0;
         if (r->last_collected >= 0) {
-            float f = 0;
-            HIP_TRY(hipEventElapsedTime(&f, r->slots[r->last_collected].start, r->slots[r->last_collected].done));
-            *batch_ms = f;
+            const RerankSlot &s = r->slots[r->last_collected];
+            HIP_TRY(elapsed_ms(s.start, s.done, batch_ms));
         }
     }
     if (pack_path) *pack_path = r->last_path;

@@ -32,10 +32,12 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "vbm25_internal.h"
 #include "hip_host.h"
+#include "ring.h"
 #include "resolve_lane.h"
 #include "lexeme_input.h"
 #include "resolve_shared.h"
@@ -209,26 +211,28 @@ int enqueue_pack(hipStream_t st, const PackScratch &s, const uint32_t *q_lex_dev
 namespace {
 
 struct Slot {
-    uint8_t *in = nullptr;    // pinned: the staged block of one batch
-    uint32_t *out = nullptr;  // pinned: q_off (max_queries + 1) then term_ids (max_lexemes)
-    hipEvent_t start = nullptr, done = nullptr;
+    PinnedHost in;   // the staged block of one batch
+    PinnedHost out;  // q_off (max_queries + 1) then term_ids (max_lexemes), as uint32_t
+    Event start, done;
     uint32_t nq = 0;
 };
 
 }  // namespace
 
+// vbm25_resolver_destroy waits for the stream before it deletes: the order of the members below does not matter to their destructors.
 struct vbm25_resolver {
     const vbm25_index *index = nullptr;
     int device = 0;
-    uint32_t depth = 0, max_queries = 0, max_lexemes = 0, n_terms = 0;
-    uint64_t max_bytes = 0, device_bytes = 0;
+    uint32_t max_queries = 0, max_lexemes = 0, n_terms = 0;
+    uint64_t max_bytes = 0;
     bool has_seed = false;
     Seed seed{};
-    hipStream_t stream = nullptr;
+    Stream stream;  // the one stream of every slot
     size_t in_capacity = 0, cub_bytes = 0;
+    ResourceTally tally;
     HbmArray vocab, in_dev, ids, tmp, counts, q_off, sort_a, sort_b, cub;
     Slot slots[16];
-    uint32_t head = 0, count = 0;  // the oldest slot in flight; slots in flight
+    RingCursor ring;
     int last_collected = -1;
 };
 
@@ -247,50 +251,43 @@ int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint
     const uint8_t *term_key = nullptr;
     if (int rc = index_vocabulary(ix, &device, &n_terms, &term_key)) return rc;
     if (int rc = use_device(device)) return rc;
-    struct Guard {
-        vbm25_resolver *r;
-        ~Guard() {
-            if (r) vbm25_resolver_destroy(r);
-        }
-    } guard{new vbm25_resolver};
-    vbm25_resolver *r = guard.r;
+    std::unique_ptr<vbm25_resolver, void (*)(vbm25_resolver *)> guard(new vbm25_resolver, vbm25_resolver_destroy);
+    vbm25_resolver *r = guard.get();
     r->index = ix;
     r->device = device;
-    r->depth = depth;
+    r->ring.depth = depth;
     r->max_queries = max_queries;
     r->max_lexemes = max_lexemes;
     r->max_bytes = max_bytes;
     r->n_terms = n_terms;
     r->has_seed = seed32 != nullptr;
     seed_words(seed32, &r->seed);
-    HIP_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    ResourceTally &ta = r->tally;
+    HIP_TRY(ta.stream_create(r->stream));
     // the staged block: q_lex | lex_off | bytes (rounded up to 4), or q_key | keys
     const size_t head_bytes = align_up(align_up(4ull * (max_queries + 1), 8) + 8ull * (max_lexemes + 1), 16);
     r->in_capacity = head_bytes + std::max<size_t>(align_up(max_bytes, 4), 16ull * max_lexemes);
     const size_t n1 = size_t(max_lexemes) + 1;
-    if (int rc = pack_cub_bytes(max_queries, max_lexemes, r->stream, &r->cub_bytes)) return rc;
-    HIP_TRY(r->vocab.alloc(16ull * n_terms));
-    HIP_TRY(r->in_dev.alloc(r->in_capacity));
-    HIP_TRY(r->ids.alloc(4 * n1));       // ids; the general path's flags
-    HIP_TRY(r->tmp.alloc(4 * n1));       // the wave path's packed ids; the general path's positions
-    HIP_TRY(r->counts.alloc(4ull * (max_queries + 1)));
-    HIP_TRY(r->q_off.alloc(4ull * (max_queries + 1)));
-    HIP_TRY(r->sort_a.alloc(8ull * max_lexemes));
-    HIP_TRY(r->sort_b.alloc(8ull * max_lexemes + 4 * n1));  // the sorted keys, then the general path's flags
-    HIP_TRY(r->cub.alloc(r->cub_bytes));
-    for (const HbmArray *b : {&r->vocab, &r->in_dev, &r->ids, &r->tmp, &r->counts, &r->q_off, &r->sort_a, &r->sort_b, &r->cub})
-        r->device_bytes += b->footprint();  // (16 for a zero-length buffer: the vocabulary of an index without terms)
-    if (n_terms) HIP_TRY(hipMemcpyAsync(r->vocab.p, term_key, 16ull * n_terms, hipMemcpyHostToDevice, r->stream));
+    if (int rc = pack_cub_bytes(max_queries, max_lexemes, r->stream.s, &r->cub_bytes)) return rc;
+    HIP_TRY(ta.device_alloc(r->vocab, 16ull * n_terms));  // (a footprint of 16 for the vocabulary of an index without terms)
+    HIP_TRY(ta.device_alloc(r->in_dev, r->in_capacity));
+    HIP_TRY(ta.device_alloc(r->ids, 4 * n1));       // ids; the general path's flags
+    HIP_TRY(ta.device_alloc(r->tmp, 4 * n1));       // the wave path's packed ids; the general path's positions
+    HIP_TRY(ta.device_alloc(r->counts, 4ull * (max_queries + 1)));
+    HIP_TRY(ta.device_alloc(r->q_off, 4ull * (max_queries + 1)));
+    HIP_TRY(ta.device_alloc(r->sort_a, 8ull * max_lexemes));
+    HIP_TRY(ta.device_alloc(r->sort_b, 8ull * max_lexemes + 4 * n1));  // the sorted keys, then the general path's flags
+    HIP_TRY(ta.device_alloc(r->cub, r->cub_bytes));
+    if (n_terms) HIP_TRY(hipMemcpyAsync(r->vocab.p, term_key, 16ull * n_terms, hipMemcpyHostToDevice, r->stream.s));
     for (uint32_t i = 0; i < depth; ++i) {
         Slot &s = r->slots[i];
-        HIP_TRY(hipHostMalloc((void **)&s.in, r->in_capacity, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc((void **)&s.out, 4ull * (max_queries + 1) + 4ull * max_lexemes, hipHostMallocDefault));
-        HIP_TRY(hipEventCreate(&s.start));
-        HIP_TRY(hipEventCreate(&s.done));
+        HIP_TRY(ta.pinned_alloc(s.in, r->in_capacity));
+        HIP_TRY(ta.pinned_alloc(s.out, 4ull * (max_queries + 1) + 4ull * max_lexemes));
+        HIP_TRY(ta.event_create(s.start));
+        HIP_TRY(ta.event_create(s.done));
     }
-    HIP_TRY(hipStreamSynchronize(r->stream));  // (the index's host keys are not read after create)
-    *out = r;
-    guard.r = nullptr;
+    HIP_TRY(hipStreamSynchronize(r->stream.s));  // (the index's host keys are not read after create)
+    *out = guard.release();
     return VBM25_OK;
 }
 
@@ -298,13 +295,14 @@ int resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth, uint
 int enqueue_pack(vbm25_resolver *r, Slot &s, const uint32_t *q_lex_dev, uint32_t nq, uint32_t n_lex, uint32_t longest_query) {
     const PackScratch scratch{r->ids.as<uint32_t>(), r->tmp.as<uint32_t>(), r->counts.as<uint32_t>(), r->q_off.as<uint32_t>(),
                               r->sort_a.as<unsigned long long>(), r->sort_b.as<unsigned long long>(), r->cub.p, r->cub_bytes, r->max_lexemes};
-    if (int rc = rsv::enqueue_pack(r->stream, scratch, q_lex_dev, nq, n_lex, longest_query, s.out + (r->max_queries + 1), s.out)) return rc;
-    HIP_TRY(hipEventRecord(s.done, r->stream));
+    uint32_t *out = s.out.as<uint32_t>();
+    if (int rc = rsv::enqueue_pack(r->stream.s, scratch, q_lex_dev, nq, n_lex, longest_query, out + (r->max_queries + 1), out)) return rc;
+    HIP_TRY(hipEventRecord(s.done.e, r->stream.s));
     return VBM25_OK;
 }
 
 int submit_common(vbm25_resolver *r, uint32_t nq) {
-    if (r->count == r->depth) return set_error(VBM25_ERR_INVALID, "the resolver's %u slots are all in flight: collect first", r->depth);
+    if (r->ring.full()) return set_error(VBM25_ERR_INVALID, "the resolver's %u slots are all in flight: collect first", r->ring.depth);
     if (nq > r->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the resolver's max_queries %u", nq, r->max_queries);
     return VBM25_OK;
 }
@@ -317,21 +315,24 @@ int resolver_submit_lexemes(vbm25_resolver *r, const uint8_t *bytes, const uint6
     if (sh.n_lex > r->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u lexemes exceed the resolver's max_lexemes %u", sh.n_lex, r->max_lexemes);
     if (sh.n_bytes > r->max_bytes) return set_error(VBM25_ERR_INVALID, "%llu bytes exceed the resolver's max_bytes %llu", (unsigned long long)sh.n_bytes, (unsigned long long)r->max_bytes);
     if (int rc = use_device(r->device)) return rc;
-    Slot &s = r->slots[(r->head + r->count) % r->depth];
+    Slot &s = r->slots[r->ring.tail()];
     const size_t o_lex = align_up(4ull * (nq + 1), 8), o_bytes = align_up(o_lex + 8ull * (sh.n_lex + 1), 16), total = o_bytes + align_up(sh.n_bytes, 4);
-    std::memcpy(s.in, q_lex, 4ull * (nq + 1));
-    std::memcpy(s.in + o_lex, lex_off, 8ull * (sh.n_lex + 1));
-    if (sh.n_bytes) std::memcpy(s.in + o_bytes, bytes, sh.n_bytes);
+    uint8_t *in = s.in.as<uint8_t>();
+    std::memcpy(in, q_lex, 4ull * (nq + 1));
+    std::memcpy(in + o_lex, lex_off, 8ull * (sh.n_lex + 1));
+    if (sh.n_bytes) std::memcpy(in + o_bytes, bytes, sh.n_bytes);
     uint8_t *d = r->in_dev.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(s.start, r->stream));
+    Quiesce quiesce(r->stream.s);  // (a failed step below leaves nothing in flight on the slot; let go of on success)
+    HIP_TRY(hipMemcpyAsync(d, in, total, hipMemcpyHostToDevice, r->stream.s));
+    HIP_TRY(hipEventRecord(s.start.e, r->stream.s));
     const uint32_t *q_lex_dev = reinterpret_cast<const uint32_t *>(d);
-    if (int rc = launch_intern(r->stream, r->seed, reinterpret_cast<const uint32_t *>(d + o_bytes), reinterpret_cast<const uint64_t *>(d + o_lex),
+    if (int rc = launch_intern(r->stream.s, r->seed, reinterpret_cast<const uint32_t *>(d + o_bytes), reinterpret_cast<const uint64_t *>(d + o_lex),
                                sh.n_lex, sh.longest_lexeme, r->vocab.as<Key>(), r->n_terms, nullptr, r->ids.as<uint32_t>()))
         return rc;
     if (int rc = enqueue_pack(r, s, q_lex_dev, nq, sh.n_lex, sh.longest_query)) return rc;
     s.nq = nq;
-    ++r->count;
+    r->ring.push();
+    quiesce.s = nullptr;
     return VBM25_OK;
 }
 
@@ -343,38 +344,39 @@ int resolver_submit_keys(vbm25_resolver *r, const uint8_t *keys16, const uint32_
     if (int rc = submit_common(r, nq)) return rc;
     if (sh.n_lex > r->max_lexemes) return set_error(VBM25_ERR_INVALID, "%u keys exceed the resolver's max_lexemes %u", sh.n_lex, r->max_lexemes);
     if (int rc = use_device(r->device)) return rc;
-    Slot &s = r->slots[(r->head + r->count) % r->depth];
+    Slot &s = r->slots[r->ring.tail()];
     const size_t o_keys = align_up(4ull * (nq + 1), 16), total = o_keys + 16ull * sh.n_lex;
-    std::memcpy(s.in, q_key, 4ull * (nq + 1));
-    if (sh.n_lex) std::memcpy(s.in + o_keys, keys16, 16ull * sh.n_lex);
+    uint8_t *in = s.in.as<uint8_t>();
+    std::memcpy(in, q_key, 4ull * (nq + 1));
+    if (sh.n_lex) std::memcpy(in + o_keys, keys16, 16ull * sh.n_lex);
     uint8_t *d = r->in_dev.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(d, s.in, total, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(s.start, r->stream));
+    Quiesce quiesce(r->stream.s);  // (as in resolver_submit_lexemes)
+    HIP_TRY(hipMemcpyAsync(d, in, total, hipMemcpyHostToDevice, r->stream.s));
+    HIP_TRY(hipEventRecord(s.start.e, r->stream.s));
     if (sh.n_lex) {
-        lookup_kernel<<<grid_for(sh.n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, r->stream>>>(reinterpret_cast<const Key *>(d + o_keys), sh.n_lex, r->vocab.as<Key>(),
+        lookup_kernel<<<grid_for(sh.n_lex, WG_THREADS, MAX_GRID), WG_THREADS, 0, r->stream.s>>>(reinterpret_cast<const Key *>(d + o_keys), sh.n_lex, r->vocab.as<Key>(),
                                                                                      r->n_terms, r->ids.as<uint32_t>());
         HIP_TRY(hipGetLastError());
     }
     if (int rc = enqueue_pack(r, s, reinterpret_cast<const uint32_t *>(d), nq, sh.n_lex, sh.longest_query)) return rc;
     s.nq = nq;
-    ++r->count;
+    r->ring.push();
+    quiesce.s = nullptr;
     return VBM25_OK;
 }
 
 int resolver_collect(vbm25_resolver *r, uint32_t *term_ids, uint32_t *q_off, uint32_t *nq_out) {
     if (!r || !q_off || !nq_out) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (!r->count) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the resolver");
+    if (r->ring.empty()) return set_error(VBM25_ERR_INVALID, "nothing is in flight on the resolver");
     if (int rc = use_device(r->device)) return rc;
-    Slot &s = r->slots[r->head];
-    HIP_TRY(hipEventSynchronize(s.done));
-    const uint32_t n_ids = s.out[s.nq];
+    Slot &s = r->slots[r->ring.head];
+    HIP_TRY(hipEventSynchronize(s.done.e));
+    const uint32_t *out = s.out.as<uint32_t>(), n_ids = out[s.nq];
     if (n_ids && !term_ids) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    std::memcpy(q_off, s.out, 4ull * (s.nq + 1));
-    if (n_ids) std::memcpy(term_ids, s.out + (r->max_queries + 1), 4ull * n_ids);
+    std::memcpy(q_off, out, 4ull * (s.nq + 1));
+    if (n_ids) std::memcpy(term_ids, out + (r->max_queries + 1), 4ull * n_ids);
     *nq_out = s.nq;
-    r->last_collected = int(r->head);
-    r->head = (r->head + 1) % r->depth;
-    --r->count;
+    r->last_collected = int(r->ring.pop());
     return VBM25_OK;
 }
 
@@ -393,7 +395,7 @@ int intern_batch_device(int device, const uint8_t *seed32, const uint8_t *bytes,
     if (sh.n_bytes) std::memcpy(stage.data() + o_bytes, bytes, sh.n_bytes);
     HbmArray in, keys;
     Stream st;  // (a stream of its own: a launch on the null stream would wait for every other stream of the device)
-    HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    HIP_TRY(st.create());
     Quiesce quiesce(st.s);  // (behind the buffers and the stream: waited for before the one is destroyed and the others are freed)
     HIP_TRY(in.alloc(total));
     HIP_TRY(keys.alloc(16ull * n_lex));
@@ -413,10 +415,7 @@ int search_batch_lexemes(vbm25_index *ix, const uint8_t *seed32, const uint8_t *
     if (int rc = check_lexemes(seed32 != nullptr, bytes, lex_off, q_lex, nq, &sh)) return rc;
     vbm25_resolver *r = nullptr;
     if (int rc = resolver_create(ix, seed32, 1, std::max(nq, 1u), std::max(sh.n_lex, 1u), sh.n_bytes, &r)) return rc;
-    struct Free {
-        vbm25_resolver *r;
-        ~Free() { vbm25_resolver_destroy(r); }
-    } free_it{r};
+    std::unique_ptr<vbm25_resolver, void (*)(vbm25_resolver *)> free_it(r, vbm25_resolver_destroy);
     std::vector<uint32_t> term_ids(std::max(sh.n_lex, 1u)), q_off(size_t(nq) + 1);
     uint32_t got = 0;
     if (int rc = resolver_submit_lexemes(r, bytes, lex_off, q_lex, nq)) return rc;
@@ -449,18 +448,11 @@ int vbm25_resolver_create(vbm25_index *ix, const uint8_t *seed32, uint32_t depth
 void vbm25_resolver_destroy(vbm25_resolver *r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
-    if (r->stream) (void)hipStreamSynchronize(r->stream);  // nothing is freed under a kernel or a copy in flight
-    for (Slot &s : r->slots) {
-        if (s.in) (void)hipHostFree(s.in);
-        if (s.out) (void)hipHostFree(s.out);
-        if (s.start) (void)hipEventDestroy(s.start);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (r->stream) (void)hipStreamDestroy(r->stream);
+    if (r->stream.s) (void)hipStreamSynchronize(r->stream.s);  // nothing is freed under a kernel or a copy in flight
     delete r;
 }
 
-uint64_t vbm25_resolver_device_bytes(const vbm25_resolver *r) { return r ? r->device_bytes : 0; }
+uint64_t vbm25_resolver_device_bytes(const vbm25_resolver *r) { return r ? r->tally.device_bytes : 0; }
 
 int vbm25_resolver_submit_lexemes(vbm25_resolver *r, const uint8_t *bytes, const uint64_t *lex_off, const uint32_t *q_lex, uint32_t nq) {
     return guarded([&] { return resolver_submit_lexemes(r, bytes, lex_off, q_lex, nq); });
@@ -474,7 +466,7 @@ int vbm25_resolver_collect(vbm25_resolver *r, uint32_t *term_ids, uint32_t *q_of
     return guarded([&] { return resolver_collect(r, term_ids, q_off, nq_out); });
 }
 
-int vbm25_resolver_in_flight(const vbm25_resolver *r) { return r ? int(r->count) : 0; }
+int vbm25_resolver_in_flight(const vbm25_resolver *r) { return r ? int(r->ring.count) : 0; }
 
 int vbm25_intern_batch_device(int device, const uint8_t *seed32, const uint8_t *bytes, const uint64_t *lex_off, uint32_t n_lex, uint8_t *keys16) {
     return guarded([&] { return intern_batch_device(device, seed32, bytes, lex_off, n_lex, keys16); });
@@ -488,9 +480,8 @@ int vbm25_search_batch_lexemes(vbm25_index *ix, const uint8_t *seed32, const uin
 // tools/resolve_cost.py: the device time of the last collected batch's kernels (upload excluded), by the slot's HIP events.  Not in the header.
 int vbm25_debug_resolver_kernel_ms(vbm25_resolver *r, double *ms) {
     if (!r || !ms || r->last_collected < 0) return set_error(VBM25_ERR_INVALID, "no collected batch");
-    float f = 0;
-    HIP_TRY(hipEventElapsedTime(&f, r->slots[r->last_collected].start, r->slots[r->last_collected].done));
-    *ms = f;
+    const Slot &s = r->slots[r->last_collected];
+    HIP_TRY(elapsed_ms(s.start, s.done, ms));
     return VBM25_OK;
 }
 

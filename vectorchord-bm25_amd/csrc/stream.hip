@@ -9,6 +9,7 @@
 
 #include "vbm25_internal.h"
 #include "host_objects.h"
+#include "ring.h"
 
 // ---------------------------------------------------------------------------
 // The pipelined boundary (include/vbm25.h): a ring of batch objects, each with its own stream and pinned staging.  submit =
@@ -21,7 +22,7 @@
 // ---------------------------------------------------------------------------
 struct vbm25_stream {
     std::vector<vbm25_batch *> slots;
-    uint32_t head = 0, in_flight = 0;  // the oldest batch in flight, their number
+    vbm25::RingCursor ring;  // over the slots: ring.count batches are in flight
     vbm25_index *index = nullptr;
     // what the next submit takes (vbm25_stream_set_growing / _set_filter): a slot picks them up when it is idle, at its next submit --
     // the batches in flight keep what they were submitted with, and the setters wait for nobody
@@ -94,6 +95,7 @@ static int stream_create_impl(vbm25_index *ix, uint32_t depth, uint32_t max_quer
         b->pinned_results = true;
         s->slots.push_back(b);
     }
+    s->ring.depth = depth;
     s->index = ix;
     *out = s.release();
     return VBM25_OK;
@@ -113,27 +115,26 @@ static int stream_set_filter_impl(vbm25_stream *s, const vbm25_filter *f) {
 static int stream_submit_impl(vbm25_stream *s, bool filtered, const uint32_t *q_filter, const uint32_t *term_ids, const uint32_t *q_off,
                               uint32_t nq) {
     if (!s || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
-    if (s->in_flight == s->slots.size()) return set_error(VBM25_ERR_INVALID, "%u batches in flight: collect one first", s->in_flight);
+    if (s->ring.full()) return set_error(VBM25_ERR_INVALID, "%u batches in flight: collect one first", s->ring.count);
     if (filtered && !s->filter) return set_error(VBM25_ERR_INVALID, "the stream has no filter set");
     if (filtered && !q_filter && nq) return set_error(VBM25_ERR_INVALID, "q_filter is NULL");
-    vbm25_batch *b = s->slots[(s->head + s->in_flight) % s->slots.size()];
+    vbm25_batch *b = s->slots[s->ring.tail()];
     if (nq > b->max_queries) return set_error(VBM25_ERR_INVALID, "%u queries exceed the batch capacity %u", nq, b->max_queries);
     bool on = false;
     if (int rc = batch_attach_check(b, s->growing, filtered ? s->filter : nullptr, q_filter, nq, &on)) return rc;
     if (int rc = batch_attach(b, s->growing, s->filter, q_filter, nq, on)) return rc;
     if (int rc = batch_submit(b, term_ids, q_off, nq)) return rc;
-    ++s->in_flight;
+    s->ring.push();
     return VBM25_OK;
 }
 static int stream_collect_impl(vbm25_stream *s, vbm25_hit *hits, uint32_t *n_hits, uint32_t *nq_out) {
     if (!s) return set_error(VBM25_ERR_INVALID, "stream is NULL");
-    if (!s->in_flight) return set_error(VBM25_ERR_INVALID, "no batch in flight");
-    vbm25_batch *b = s->slots[s->head];
+    if (s->ring.empty()) return set_error(VBM25_ERR_INVALID, "no batch in flight");
+    vbm25_batch *b = s->slots[s->ring.head];
     if ((!hits || !n_hits) && b->nq) return set_error(VBM25_ERR_INVALID, "NULL argument");
     const int rc = vbm25_batch_finish_download(b, hits, n_hits);
     if (nq_out) *nq_out = b->nq;
-    s->head = (s->head + 1) % uint32_t(s->slots.size());
-    --s->in_flight;
+    s->ring.pop();
     return rc;
 }
 
@@ -162,6 +163,6 @@ int vbm25_stream_set_filter(vbm25_stream *s, const vbm25_filter *f) {
 int vbm25_stream_collect(vbm25_stream *s, vbm25_hit *hits, uint32_t *n_hits, uint32_t *nq_out) {
     return guarded([&] { return stream_collect_impl(s, hits, n_hits, nq_out); });
 }
-int vbm25_stream_in_flight(const vbm25_stream *s) { return s ? int(s->in_flight) : 0; }
+int vbm25_stream_in_flight(const vbm25_stream *s) { return s ? int(s->ring.count) : 0; }
 
 }  // extern "C"

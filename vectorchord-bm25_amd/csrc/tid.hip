@@ -206,7 +206,7 @@ int match_plane(const vbm25_tid_set *s, int device, const char *what, const uint
     if ((rc = d_words.alloc(8ull * n_words)) || (rc = d_count.alloc(4))) return rc;
     HIP_TRY(hipMemsetAsync(d_count.p, 0, 4));
     Event ev[2];
-    for (Event &e : ev) HIP_TRY(hipEventCreate(&e.e));
+    for (Event &e : ev) HIP_TRY(e.create());
     HIP_TRY(hipEventRecord(ev[0].e, nullptr));
     match_launch(s, payload, n, d_words.as<unsigned long long>(), false, STORE_COUNT, d_count.as<uint32_t>());
     HIP_TRY(hipGetLastError());
