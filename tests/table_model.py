@@ -10,7 +10,11 @@ The rules:
     summed in ascending key order from 0.0, and enters with a score > 0 as doc_id 0xFFFFFFFF - g (search.rs:83-135);
   * order: score descending; on equal scores sealed before growing, sealed by id, growing by g (DESIGN.md);
   * VACUUM keeps the live sealed rows in order, then the live growing rows in order; a kept sealed row's new length is its number
-    of postings (maintain.rs:344-362), a growing row keeps its length; everything is flushed again from scratch."""
+    of postings (maintain.rs:344-362), a growing row keeps its length; everything is flushed again from scratch;
+  * a delete by ctid (bulkdelete.rs) kills every row of both segments that carries one of the ctids;
+  * the rerank step scores a candidate with the `<&>` operator (evaluate.rs: idf * tf per shared key, ascending, from 0.0; the
+    fieldnorm of the row's stored length), names a ctid's lowest row and knows nothing of deletion (Table.rerank).
+Table.ops_ctid draws the same life in lexemes and ctids for tests/test_gpu_table_ctid_fuzz.py."""
 import struct
 
 import numpy as np
@@ -23,6 +27,10 @@ KS = (1, 10, 100, 300, 1025)
 NO_ROW_KEY = b"~no row".ljust(16, b"\0")
 INSERT_KEYS = (1, 3, 30, 250)
 INSERT_ROWS = (1, 4, 16)
+# one row of a rerank result: the score, the position in the query's candidate list, the row index (the library's vbm25_rank)
+RANK_DTYPE = np.dtype({"names": ["score", "pos", "doc"], "formats": ["<f8", "<u4", "<u4"], "offsets": [0, 8, 12], "itemsize": 16})
+RERANK_KS = (1, 10, 64, 65, 1024)   # 1024: the scorer's maximum
+NO_ROW_LEXEME = b"~no row"          # (shorter than 16 bytes: its key is NO_ROW_KEY, vector.rs:21-24)
 
 
 def new_key(i):
@@ -30,12 +38,13 @@ def new_key(i):
     return (b"n%06d" % i).ljust(16, b"\0")
 
 
-def random_rows(n_docs, vocab, seed, mean_len=40):
+def random_rows(n_docs, vocab, seed, mean_len=40, keys=None):
     """n_docs rows of lognormal length (mean about mean_len) over `vocab` Zipf(1) tokens (tests/fuzz:168-205 of the reference: a row
-    is its length in token draws, tf the multiplicity); token t's key is its decimal digits, zero padded (vector.rs:21-24).
-    Returns (rows, the keys of all `vocab` tokens)."""
+    is its length in token draws, tf the multiplicity); token t's key is its decimal digits, zero padded (vector.rs:21-24), or
+    keys[t] where `keys` is given (interned lexemes).  Returns (rows, the keys of all `vocab` tokens)."""
     rng = np.random.default_rng(seed)
-    keys = [str(t).encode().ljust(16, b"\0") for t in range(vocab)]
+    keys = [str(t).encode().ljust(16, b"\0") for t in range(vocab)] if keys is None else [bytes(key) for key in keys]
+    assert len(keys) == vocab
     lens = np.clip(np.rint(rng.lognormal(np.log(mean_len * 0.8), 0.6, n_docs)), 8, 2000).astype(np.int64)
     p = 1.0 / np.arange(1, vocab + 1)
     rows = []
@@ -59,6 +68,10 @@ class Table:
         self.k1, self.b, self.seed = float(k1), float(b), bytes(seed32)
         self.vacuums = []   # per VACUUM: (sealed rows deleted, growing rows deleted, keys the sealed vocabulary lacked)
         self.stats = dict(selects=0, both=0, nothing=0, deleted_shown=0, mixed_ties=0)
+        # what the ctid life counts (delete_tids with `what`, rerank_op); assert_coverage_ctid of tests/test_table_model.py reads it
+        self.cstats = dict(bulk_full=0, delete_batches=0, reranks=0, rerank_both=0, ineligible_sealed=0, ineligible_growing=0,
+                           rerank_short=0, rerank_cut=0)
+        self._n_batches = 0
         self._seal([(tuple(p), dict(kt), int(ln)) for p, kt, ln in rows])
 
     # ---- state
@@ -68,6 +81,8 @@ class Table:
         self.sealed = rows
         self.sealed_deleted = np.zeros(len(rows), bool)
         self.growing, self.growing_deleted = [], []
+        self.growing_batch = []   # per growing row: the number of the insert (insert's `batch`) that appended it
+        self._first = {}          # side -> (rows covered, {payload: lowest row index}), see first_rows
         self.ginv = {}     # key -> [(g, tf)] of the growing rows, g ascending
         vocab = sorted({key for _, kt, _ in rows for key in kt})
         self.vocab, self.rank = vocab, {key: t for t, key in enumerate(vocab)}
@@ -110,12 +125,18 @@ class Table:
 
     # ---- mutations
 
-    def insert(self, payload, kt):
+    def new_batch(self):
+        """a number for insert's `batch`: the rows of one INSERT statement share one"""
+        self._n_batches += 1
+        return self._n_batches
+
+    def insert(self, payload, kt, batch=None):
         keys = sorted(kt)
         self.pages.insert(np.array(payload, np.uint16), keys, [kt[key] for key in keys])
         g = len(self.growing)
         self.growing.append((tuple(int(x) for x in payload), dict(kt), length_of(kt)))
         self.growing_deleted.append(False)
+        self.growing_batch.append(self.new_batch() if batch is None else batch)
         for key in keys:
             self.ginv.setdefault(key, []).append((g, kt[key]))
         return g
@@ -128,6 +149,27 @@ class Table:
     def delete_growing(self, g):
         self.pages.mark_deleted_growing(g)
         self.growing_deleted[g] = True
+
+    def delete_tids(self, tids, what=None):
+        """every sealed and growing row whose payload is among the ctids `tids` ([n, 3], repeats and ctids of no row allowed) is
+        deleted (bulkdelete.rs).  Returns (sealed rows newly dead, growing rows newly dead, growing rows matched, the already dead
+        ones included).  what: "bulkdelete" or "delete" counts the call for the ctid life's coverage conditions."""
+        want = {tuple(int(x) for x in t) for t in tids}
+        held = {p for p, _, _ in self.sealed} | {p for p, _, _ in self.growing}
+        dead_named = any(p in want for d, (p, _, _) in enumerate(self.sealed) if self.sealed_deleted[d]) or \
+            any(p in want for g, (p, _, _) in enumerate(self.growing) if self.growing_deleted[g])
+        new_s = [d for d, (p, _, _) in enumerate(self.sealed) if p in want and not self.sealed_deleted[d]]
+        hit_g = [g for g, (p, _, _) in enumerate(self.growing) if p in want]
+        new_g = [g for g in hit_g if not self.growing_deleted[g]]
+        for d in new_s:
+            self.delete_sealed(d)
+        for g in new_g:
+            self.delete_growing(g)
+        if what == "bulkdelete":
+            self.cstats["bulk_full"] += bool(new_s and new_g and dead_named and want - held)
+        elif what == "delete":
+            self.cstats["delete_batches"] += len({self.growing_batch[g] for g in hit_g}) > 1
+        return len(new_s), len(new_g), len(hit_g)
 
     # ---- what a filter built from the rows holds
 
@@ -222,6 +264,92 @@ class Table:
             s["mixed_ties"] += tie
         return out
 
+    # ---- the forward index and the rerank step
+
+    def forward(self):
+        """the sealed rows as a forward index: (start uint64 [n + 1], term uint32, tf uint32, fieldnorm uint8 [n]) -- per row its
+        term ranks ascending with their tf, and the fieldnorm code of its STORED length (after a VACUUM a kept sealed row's length
+        is its number of postings, _seal's rows carry it)"""
+        L = orc.lib()
+        start, term, tf, fn = [0], [], [], []
+        for _, kt, ln in self.sealed:
+            for key in sorted(kt):
+                term.append(self.rank[key])
+                tf.append(kt[key])
+            start.append(len(term))
+            fn.append(L.orc_length_to_fieldnorm(ln))
+        return np.array(start, np.uint64), np.array(term, np.uint32), np.array(tf, np.uint32), np.array(fn, np.uint8)
+
+    def _operator(self, t, fieldnorm, tf):
+        """one term of the `<&>` operator: idf * tf (evaluate.rs:22-74 with bm25.rs:285-295).  NOT _evaluate: the search multiplies
+        tf into the cached idf * (k1 + 1) before it divides (Cache::evaluate, bm25.rs:355-358), the operator divides first, and the
+        two differ in the last bit for some postings."""
+        at = ("<&>", t, fieldnorm, tf)
+        if at not in self._eval:
+            o, L = self.oix, orc.lib()
+            self._eval[at] = L.orc_idf(o.n_docs, int(o.arrays["term_df"][t])) * L.orc_tf(fieldnorm, tf, o.k1, o.b, o.sum_len / o.n_docs)
+        return self._eval[at]
+
+    def first_rows(self, side):
+        """{payload: the lowest row index of `side` that carries it}"""
+        rows = self.sealed if side == "sealed" else self.growing
+        n, first = self._first.get(side, (0, {}))
+        for i in range(n, len(rows)):   # (rows are only ever appended between two _seal)
+            first.setdefault(rows[i][0], i)
+        self._first[side] = (len(rows), first)
+        return first
+
+    def rerank(self, query_keys, cand_tids, k, side):
+        """the rerank step (`<&>` over a candidate list, top k) on the rows of one side, "sealed" or "growing" -> (ranks [k] of
+        RANK_DTYPE, n_ranks, eligible candidates).  A ctid names the lowest row index of the side that carries it; one no row of the
+        side carries is not eligible, and the others keep their positions in the list.  DELETION IS NOT CONSULTED: the reranker
+        knows the documents it was bound to, not their deleted flags, so a dead row scores like a live one.  A row's score is the
+        sum of _operator(rank, its fieldnorm, tf) from 0.0 in ascending key order over the distinct query keys that the sealed
+        vocabulary and the row hold; growing rows take the sealed statistics and their own length (what binding cast documents to
+        the index's vocabulary keeps).  The result is the stable descending sort of the eligible entries cut at k: (score, pos in
+        the list, row index), zeros behind them."""
+        assert side in ("sealed", "growing")
+        L = orc.lib()
+        rows, first = (self.sealed if side == "sealed" else self.growing), self.first_rows(side)
+        qkeys = [key for key in sorted(set(query_keys)) if key in self.rank]
+        entries = []
+        for pos, tid in enumerate(cand_tids):
+            i = first.get(tuple(int(x) for x in tid))
+            if i is None:
+                continue
+            _, kt, ln = rows[i]
+            fn, s = L.orc_length_to_fieldnorm(ln), 0.0
+            for key in qkeys:
+                if key in kt:
+                    s += self._operator(self.rank[key], fn, kt[key])
+            entries.append((s, pos, i))
+        best = sorted(entries, key=lambda e: -e[0])[:k]   # (sorted is stable: equal scores stay in list order)
+        ranks = np.zeros(k, RANK_DTYPE)
+        for r, e in enumerate(best):
+            ranks[r] = e
+        return ranks, len(best), len(entries)
+
+    def rerank_op(self, queries, lists, k, count=True):
+        """rerank of every (query keys, ctid list) pair on both sides -> {side: (ranks [nq, k], n_ranks uint32 [nq])}"""
+        out, seen = {}, {}
+        for side in ("sealed", "growing"):
+            got = [self.rerank(keys, tids, k, side) for keys, tids in zip(queries, lists)]
+            ranks = np.stack([g[0] for g in got]) if got else np.zeros((0, k), RANK_DTYPE)
+            out[side] = (ranks, np.array([g[1] for g in got], np.uint32))
+            first = self.first_rows(side)
+            seen[side] = dict(nonzero=bool((ranks["score"] != 0).any()),
+                              ineligible=any(tuple(int(x) for x in t) not in first for tids in lists for t in list(tids)[:k]),
+                              short=any(g[1] < k for g in got), cut=any(g[1] == k < g[2] for g in got))
+        if count:
+            c = self.cstats
+            c["reranks"] += 1
+            c["rerank_both"] += seen["sealed"]["nonzero"] and seen["growing"]["nonzero"]
+            c["ineligible_sealed"] += seen["sealed"]["ineligible"]
+            c["ineligible_growing"] += seen["growing"]["ineligible"]
+            c["rerank_short"] += seen["sealed"]["short"] or seen["growing"]["short"]
+            c["rerank_cut"] += seen["sealed"]["cut"] or seen["growing"]["cut"]
+        return out
+
     # ---- VACUUM
 
     def vacuum(self):
@@ -301,3 +429,131 @@ class Table:
                 yield ("delete", where, [int(x) for x in rng.integers(0, n_rows, many)] if n_rows else [])
             else:
                 yield ("vacuum",)
+
+    # ---- the same life by lexeme and ctid
+
+    def keys_of(self, lexemes):
+        """a query's lexemes -> its sorted distinct keys (cast_tsvector_to_query)"""
+        return sorted({self.key_of[t] for t in lexemes})
+
+    def cast(self, lexrow):
+        """a row [(lexeme, count)] -> {key: tf}: the counts of equal lexemes add up (cast_tsvector_to_document)"""
+        kt = {}
+        for t, c in lexrow:
+            kt[self.key_of[t]] = min(kt.get(self.key_of[t], 0) + c, 2 ** 32 - 1)
+        return kt
+
+    def ops_ctid(self, seed, n, universe):
+        """ops' mix and ("reopen",) cadence, in the terms a serving process is handed: lexemes and ctids.  `universe` is a list of
+        (lexeme, key) with key = intern(lexeme) under the index's seed, every key of the table's rows among them; self.key_of maps
+        every lexeme the sequence has named to its key (new lexemes and NO_ROW_LEXEME are shorter than 16 bytes: zero padded).
+          ("insert", [(payload, [(lexeme, count)])])   ops' rows, each key's tf split over 1 to 3 entries of its lexeme, shuffled;
+                                                  payloads have field 0 < 0xFFFF and field 2 >= 1 (so the ctids below that no row
+                                                  carries are certain); one row in ten takes the ctid of a live row of the table
+          ("delete_tids", tids)                   the ctids of 1, 3 or 40 rows of both segments, dead ones included, one more of a
+                                                  dead row where there is one, one that no row carries, one of them twice; shuffled
+          ("select", queries, selectors, k, front end)   ops' selects, the queries as lexemes, some lexeme twice
+          ("rerank", queries, lists, k)           after every other select on average: its queries, each with a ctid list -- in
+                                                  turn the payloads of the first 5, 30 or 100 rows the select returns now (sealed and
+                                                  growing mixed), those of 1, 20 or 200 random rows of either segment, and an edge:
+                                                  a ctid no row carries in front, behind or alone, a repeated ctid, the empty list;
+                                                  k from RERANK_KS
+          ("vacuum", tids)                        "the dead TIDs the heap reports": delete_tids' mix, empty one time in three"""
+        rng = np.random.default_rng(seed)
+        self.key_of = {lexeme: key for lexeme, key in universe}
+        self.key_of[NO_ROW_LEXEME] = NO_ROW_KEY
+        lexeme_of = {key: lexeme for lexeme, key in universe}
+        ukeys = [key for _, key in universe]
+        assert all(key in lexeme_of for key in self.vocab)
+        recent, serial, n_selects, n_reranks = [], 0, 0, 0
+
+        def absent():
+            return (int(rng.integers(0, 65536)), int(rng.integers(0, 65536)), 0)
+
+        def any_row():
+            n_s, n_g = len(self.sealed), len(self.growing)
+            if n_g and (not n_s or rng.random() < 0.4):
+                return self.growing[int(rng.integers(n_g))][0]
+            return self.sealed[int(rng.integers(n_s))][0] if n_s else absent()
+
+        def ctid_mix():
+            tids = [any_row() for _ in range(int(rng.choice((1, 3, 40))))]
+            dead = [p for d, (p, _, _) in enumerate(self.sealed) if self.sealed_deleted[d]] + \
+                   [p for g, (p, _, _) in enumerate(self.growing) if self.growing_deleted[g]]
+            if dead:
+                tids.append(dead[int(rng.integers(len(dead)))])
+            tids.append(absent())
+            tids.append(tids[int(rng.integers(len(tids)))])
+            return [tids[i] for i in rng.permutation(len(tids))]
+
+        def as_lexemes(keys):
+            q = [lexeme_of[key] for key in keys]
+            if rng.random() < 0.3:
+                q.append(q[int(rng.integers(len(q)))])
+            return [q[i] for i in rng.permutation(len(q))]
+
+        for i in range(n):
+            if i and i % 10 == 0:
+                yield ("reopen",)
+            kind = int(rng.choice(4, p=[0.2, 0.4, 0.3, 0.1]))
+            if kind == 0:
+                docs = []
+                for _ in range(int(rng.choice(INSERT_ROWS))):
+                    nk = int(rng.choice(INSERT_KEYS))
+                    keys = [ukeys[j] for j in rng.choice(len(ukeys), min(nk, len(ukeys)), replace=False)]
+                    if rng.random() < 0.2:
+                        keys[0] = new_key(seed * 1000 + serial)
+                        lexeme_of[keys[0]] = keys[0].rstrip(b"\0")
+                        self.key_of[lexeme_of[keys[0]]] = keys[0]
+                        serial += 1
+                    row = []
+                    for key, tf in zip(keys, rng.integers(1, 9, len(keys))):
+                        cuts = sorted(int(c) for c in rng.integers(1, int(tf) + 1, int(rng.integers(0, 3))))
+                        row += [(lexeme_of[key], b - a) for a, b in zip([0] + cuts, cuts + [int(tf)]) if b > a]
+                    recent = (recent + [keys])[-8:]
+                    payload = (int(rng.integers(0, 65535)), int(rng.integers(0, 65536)), int(rng.integers(1, 65536)))
+                    if rng.random() < 0.1:   # (a live row's: a heap hands a dead row's ctid out again only after the VACUUM)
+                        live = [p for d, (p, _, _) in enumerate(self.sealed) if not self.sealed_deleted[d]] + \
+                               [p for g, (p, _, _) in enumerate(self.growing) if not self.growing_deleted[g]]
+                        if live:
+                            payload = live[int(rng.integers(len(live)))]
+                    docs.append((payload, [row[j] for j in rng.permutation(len(row))]))
+                yield ("insert", docs)
+            elif kind == 1:
+                queries = []
+                for _ in range(8):
+                    pool_r = [key for keys in recent for key in keys]
+                    q = []
+                    for _ in range(int(rng.integers(1, 7))):
+                        pool = pool_r if pool_r and (rng.random() < 0.5 or not self.vocab) else self.vocab
+                        if pool:
+                            q.append(pool[int(rng.integers(len(pool)))])
+                    if not q or rng.random() < 1 / 3:
+                        q.append(NO_ROW_KEY)
+                        lexeme_of[NO_ROW_KEY] = NO_ROW_LEXEME
+                    queries.append(as_lexemes(sorted(set(q))))
+                selectors = [(NONE, 0, 1)[(q + n_selects) % 3] for q in range(8)]
+                k, front = int(rng.choice(KS)), n_selects % 3
+                yield ("select", queries, selectors, k if front == 0 else self.epoch_k(), front)
+                n_selects += 1
+                if rng.random() < 0.5:
+                    lists = []
+                    for q, lexemes in enumerate(queries):
+                        shown = [tuple(int(x) for x in p) for p in
+                                 self.select(self.keys_of(lexemes), int(rng.choice((5, 30, 100))), None, count=False)["payload"]]
+                        source = (q + n_reranks) % 3
+                        if source == 0:
+                            tids = shown
+                        elif source == 1:
+                            tids = [any_row() for _ in range(int(rng.choice((1, 20, 200))))]
+                        else:
+                            edge = int(rng.integers(5))
+                            tids = ([absent()] + shown, shown + [absent()], [absent()],
+                                    shown + shown[:1] + [any_row()] * 2, [])[edge]
+                        lists.append(tids)
+                    yield ("rerank", queries, lists, int(rng.choice(RERANK_KS)))
+                    n_reranks += 1
+            elif kind == 2:
+                yield ("delete_tids", ctid_mix())
+            else:
+                yield ("vacuum", [] if rng.random() < 1 / 3 else ctid_mix())

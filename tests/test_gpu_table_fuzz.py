@@ -152,11 +152,13 @@ class Life:
 
     # ---- VACUUM
 
-    def vacuum(self, seed32=SEED32):
+    def vacuum(self, seed32=SEED32, dv=None):
+        """dv: the compaction inputs of the relation as it is now, where the caller holds them already (default: read from the pages)"""
         self.reopen()
         m = self.m
         pl = m.page_list()
-        dv = vb.DeviceVacuum.from_pages(self.gix, pl)
+        if dv is None:
+            dv = vb.DeviceVacuum.from_pages(self.gix, pl)
         assert (dv.n_sealed, dv.n_sealed_deleted, dv.n_grow, dv.n_grow_deleted, dv.n_elements) == m.counts()
         ds, relabel = vb.DeviceSegment.maintain_device(self.gix, dv, return_relabel=True)
         want_relabel = m.vacuum()
