@@ -56,11 +56,11 @@ def index_of(n_terms):
     return _INDEX[n_terms][:2]
 
 
-def expected(gix, queries, seed=SEED):
-    """Query.from_tokens + lookup_terms + drop, per query -> (term_ids, q_off)"""
+def expected(gix, queries, seed=SEED, interned=False):
+    """Query.from_tokens + lookup_terms + drop, per query -> (term_ids, q_off); interned: the queries hold 16-byte keys, not lexemes"""
     ids, off = [], [0]
     for q in queries:
-        keys = sorted({host_intern(t, seed) for t in q})
+        keys = sorted({bytes(t) if interned else host_intern(t, seed) for t in q})
         assert vb.Query(keys).keys == keys
         got = gix.lookup_terms(keys)
         got = got[got != MISS]
