@@ -61,7 +61,23 @@ constexpr int WN_T = 8;               // indexed terms per query
 #ifndef VBM25_WIN_WAVES_MAX
 #define VBM25_WIN_WAVES_MAX 12
 #endif
-constexpr int wn_wave_lds(int mt) { return 8192 + 512 * mt + 256; }  // a wave's filter, its staged runs, its list of second arrivals
+// The window boundaries of an item, three steps that can be taken out one by one (tools/win_variant.sh <name> -DVBM25_WB_LEN=0 ...):
+// LEN the run lengths per lane (wl below), TAB the boundary table in the LDS (WinTab), ZSHL the row sum's shift with zero fill
+#ifndef VBM25_WB_LEN
+#define VBM25_WB_LEN 1
+#endif
+#ifndef VBM25_WB_TAB
+#define VBM25_WB_TAB 1
+#endif
+#ifndef VBM25_WB_ZSHL
+#define VBM25_WB_ZSHL 1
+#endif
+// The instantiations whose waves keep the item's window boundaries in a table in the LDS as well (64 words per run load; a completion
+// lane reads its term's upper boundary there instead of selecting it from MT scalars): the ones where twelve waves still fit
+constexpr bool wn_lds_tab(int mt) { return VBM25_WB_TAB && mt <= 6; }
+constexpr int wn_wave_lds(int mt) {  // a wave's filter, its staged runs, its list of second arrivals, its table of boundaries
+    return 8192 + 512 * mt + 256 + (wn_lds_tab(mt) ? 256 * mt : 0);
+}
 constexpr int WN_WG_LDS = 2048 + 16;  // the workgroup's own: the table S1 and the four queries' hand-over counters (WN_LQ_* below)
 constexpr int wn_waves(int mt, int rk) {
     const int by_lds = (163840 - WN_WG_LDS) / wn_wave_lds(mt);
@@ -73,6 +89,10 @@ constexpr int wn_waves(int mt, int rk) {
 // rebuild it per window from scalar registers): the ones that stay inside twelve waves' 168 VGPRs without a spill (`make resources`:
 // with four register rows of the top-k, seven run loads spilled one VGPR and eight run loads six)
 constexpr bool wn_lane_addr(int mt, int rk) { return !(rk == 4 && mt >= 7); }
+// ... and the ones that keep every term's run LENGTH per window in a VGPR as well (MT registers: lane i = the postings from the aligned
+// start of window i's first load to the window's end, what the marks compare 4 lane with)
+// (`make resources`: with four register rows six run loads spilled three VGPRs, with one or two rows eight run loads one and six)
+constexpr bool wn_lane_len(int mt, int rk) { return VBM25_WB_LEN && wn_lane_addr(mt, rk) && (rk == 4 ? mt <= 5 : mt <= 7); }
 constexpr int WN_BM_WORDS = 2048;     // 2^16 bits
 constexpr int WN_SLOT = 256;          // staged ids per term: what one 8-byte load per lane covers
 constexpr int WN_LIST = 64;           // second arrivals per window
@@ -91,8 +111,14 @@ __device__ __forceinline__ uint32_t wn_or_rtn(const WnBm bm, const uint32_t x, c
 __device__ __forceinline__ void wn_or(const WnBm bm, const uint32_t x, const uint32_t bit) {
     (void)__hip_atomic_fetch_or((wn_lds_u32 *)(((x >> 3) & bm.mask) | bm.base), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+template <int N>
+struct WinTab {
+    uint32_t wtab[N];                 // [t][i]: term t's postings below the item's window boundary i (wo[t] of the kernel, lane i)
+};
+template <>
+struct WinTab<0> {};
 template <int MT>
-struct WinWave {
+struct WinWave : WinTab<wn_lds_tab(MT) ? MT * 64 : 0> {
     alignas(16) uint16_t stage[MT * WN_SLOT];
     uint32_t list[WN_LIST];           // the window's second arrivals: a slot of the staged runs, or (bit 31) an id
 };
@@ -234,11 +260,21 @@ __device__ __forceinline__ void wn_drain(unsigned long long (&a)[MT], unsigned l
     if constexpr (MT == 7) asm volatile("s_waitcnt vmcnt(0)" : WN_OPS7(a), WN_OPS7(b), "+v"(g), "+v"(g2), "+v"(p));
     if constexpr (MT == 8) asm volatile("s_waitcnt vmcnt(0)" : WN_OPS8(a), WN_OPS8(b), "+v"(g), "+v"(g2), "+v"(p));
 }
+#if VBM25_WB_ZSHL
+// lane l gets lane l + 1, lane 63 zero (bound_ctrl: the destination has no old value to keep, so no copy of the source in front of
+// the shift; a row of a completion pass never reaches beyond lane 63, and + 0.0 is what an absent term adds anyway)
+__device__ __forceinline__ double wave_shl1_f64(double v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);  // wave_shl:1
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
+    return __hiloint2double((int)hi, (int)lo);
+}
+#else
 __device__ __forceinline__ double wave_shl1_f64(double v) {  // lane l gets lane l + 1 (lane 63: itself)
     const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), 0x130, 0xf, 0xf, false);  // wave_shl:1
     const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), 0x130, 0xf, 0xf, false);
     return __hiloint2double((int)hi, (int)lo);
 }
+#endif
 // an open pass of second arrivals: what C1 found for the lane's (entry, term), the word requested for it
 struct WnPend {
     bool valid, found, task;
@@ -557,6 +593,20 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
 #pragma unroll
         for (int t = 0; t < MT; ++t)
             wo[t] = ix.win_off[(uint32_t)__builtin_amdgcn_readlane((int)wbs, t) + min(w_lo + lane, NWIN)];
+        // (wn_lane_len) lane i = what window w_lo + i marks of the term: from the aligned start of its first load to its end -- built once
+        // per item, so that a window reads ONE lane per term where it read both boundaries and subtracted (lane 63 is nobody's window)
+        uint32_t wl[wn_lane_len(MT, RK) ? MT : 1];
+        if constexpr (wn_lane_len(MT, RK)) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+                wl[t] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)wo[t], 0x130, 0xf, 0xf, true) - (wo[t] & ~3u);  // wave_shl:1
+        }
+        // (wn_lds_tab) the boundaries once more in the LDS, where a completion lane can read its own term's with one address
+        if constexpr (wn_lds_tab(MT)) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t) S.wtab[t * 64 + lane] = wo[t];
+            __builtin_amdgcn_wave_barrier();
+        }
         uint32_t wS = 0, wE = 0;  // lane = term: its postings below the item's two ends
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
@@ -862,6 +912,9 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
             // LDS instead of five.  The last window's open pass of second arrivals (C2) is finished between the two phases.
             uint32_t nd = 0;
             wA = wB;  // (the last window's upper boundaries)
+            // (wn_lds_tab: this window's -- of the lane's term -- from the table, requested in front of the marks' LDS traffic and looked at
+            // behind it; the same values the selects below give: T[tl][i] is wo[tl] lane i, all zeros for a null term)
+            if constexpr (wn_lds_tab(MT)) wB = S.wtab[tl * 64u + (w - w_lo + 1u)];
             PROF_T(t_0);
             wn_wait_runs<MT>(cur);
             PROF_T(t_1);
@@ -894,11 +947,17 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
                         const int t = GT * gq + u;
                         en[u] = 0;
                         if (t < MT) {
-                            const uint32_t o_lo = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo));
-                            const uint32_t o_hi = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo + 1u));
-                            const uint32_t o_al = o_lo & ~3u;
-                            en[u] = o_hi - o_al;
-                            wB = tl == (uint32_t)t ? o_hi : wB;  // (lane = (entry, term) of a completion pass: its term's boundary)
+                            if constexpr (wn_lane_len(MT, RK)) {
+                                en[u] = (uint32_t)__builtin_amdgcn_readlane((int)wl[t < MT ? t : 0], (int)(w - w_lo));
+                            } else {
+                                const uint32_t o_lo = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo));
+                                const uint32_t o_hi = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo + 1u));
+                                en[u] = o_hi - (o_lo & ~3u);
+                            }
+                            if constexpr (!wn_lds_tab(MT)) {  // (lane = (entry, term) of a completion pass: its term's boundary)
+                                const uint32_t o_hi = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo + 1u));
+                                wB = tl == (uint32_t)t ? o_hi : wB;
+                            }
                             const uint2 run = make_uint2((uint32_t)cur[t < MT ? t : 0], (uint32_t)(cur[t < MT ? t : 0] >> 32));
                             *reinterpret_cast<uint2 *>(&S.stage[t * WN_SLOT + 4u * lane]) = run;
                             if (lane4 < en[u] && !(dbg & 32u)) {
@@ -921,6 +980,10 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
                                 }
                             }
                             if (en[u] > (uint32_t)WN_SLOT) {  // a run that one load per lane does not hold: the rest, not staged (C1 reads it from memory)
+                                // (the boundaries themselves are read here only)
+                                const uint32_t o_lo = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo));
+                                const uint32_t o_hi = (uint32_t)__builtin_amdgcn_readlane((int)wo[t < MT ? t : 0], (int)(w - w_lo + 1u));
+                                const uint32_t o_al = o_lo & ~3u;
                                 const uint16_t *rest = ids16 + 128ull * (uint32_t)__builtin_amdgcn_readlane((int)fbi, t) + 4u * lane;
                                 const uint32_t n = o_hi - o_lo;
 #pragma nounroll
