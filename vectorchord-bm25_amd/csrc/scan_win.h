@@ -72,6 +72,15 @@ constexpr int WN_T = 8;               // indexed terms per query
 #ifndef VBM25_WB_ZSHL
 #define VBM25_WB_ZSHL 1
 #endif
+// The list of second arrivals, two steps that can be taken out the same way (-DVBM25_SL_ONE=0 -DVBM25_SL_ADDR=0):
+// ONE a lane's first two flags appended in one step, ADDR the entry is the staged posting's byte offset (C1 decodes nothing)
+#ifndef VBM25_SL_ONE
+#define VBM25_SL_ONE 1
+#endif
+#ifndef VBM25_SL_ADDR
+#define VBM25_SL_ADDR 1
+#endif
+constexpr bool wn_list_one = VBM25_SL_ONE != 0, wn_list_addr = VBM25_SL_ADDR != 0;
 // The instantiations whose waves keep the item's window boundaries in a table in the LDS as well (64 words per run load; a completion
 // lane reads its term's upper boundary there instead of selecting it from MT scalars): the ones where twelve waves still fit
 constexpr bool wn_lds_tab(int mt) { return VBM25_WB_TAB && mt <= 6; }
@@ -120,8 +129,21 @@ struct WinTab<0> {};
 template <int MT>
 struct WinWave : WinTab<wn_lds_tab(MT) ? MT * 64 : 0> {
     alignas(16) uint16_t stage[MT * WN_SLOT];
-    uint32_t list[WN_LIST];           // the window's second arrivals: a slot of the staged runs, or (bit 31) an id
+    uint32_t list[WN_LIST];           // the window's second arrivals: a posting of the staged runs, or (bit 31) an id
 };
+// An entry of the list (wn_list_addr): the BYTE OFFSET of the staged posting inside `stage` -- posting j of lane l of term t is
+// 512 t + 8 l + 2 j, 13 bits -- which C1 reads the id at as it stands; or bit 31 and the id itself in the bits above the offset's,
+// whose offset part is zero (a chunk's posting of a thick run: not staged).  Every word of the list is of one of the two forms
+// at any time the window loop runs (the item setup, which borrows the list, leaves zeros), so that a lane without an entry can
+// read any of them.  Without wn_list_addr: a slot (term of the group, posting of the lane; lane; group) that C1 decodes.
+constexpr uint32_t WN_ENT_OFF = 0x1fffu, WN_ENT_ID_SHIFT = 13;
+__device__ __forceinline__ uint32_t wn_ent_id(const uint32_t x, const uint32_t t) {
+    return wn_list_addr ? x << WN_ENT_ID_SHIFT | 0x80000000u : x | t << 16 | 0x80000000u;
+}
+// (sl = 4 u + j: posting j of the lane's four of the group's term u; lane_off = 8 lane + 2560 group, the lane's own)
+__device__ __forceinline__ uint32_t wn_ent_slot(const uint32_t sl, const uint32_t lane, const uint32_t lane_off, const uint32_t gq) {
+    return wn_list_addr ? (((sl << 7) & 0xfe00u) | (sl & 3u) << 1) + lane_off : sl | lane << 5 | gq << 11;
+}
 
 __device__ __forceinline__ uint32_t wn_mbcnt(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -157,7 +179,7 @@ __device__ __forceinline__ void wn_pair(WinWave<MT> &S, const WnBm bmbase, const
             const uint32_t x = j == 0u ? x0 : j == 1u ? x1 : j == 2u ? x2 : x3;
             const unsigned long long mk = __ballot(has);
             const uint32_t pos = nd + wn_mbcnt(mk);
-            if (has && pos < (uint32_t)WN_LIST) S.list[pos] = x | t << 16 | 0x80000000u;  // (bit 31: the id itself, not a slot of the staged run)
+            if (has && pos < (uint32_t)WN_LIST) S.list[pos] = wn_ent_id(x, t);  // (bit 31: the id itself, not a posting of the staged run)
             nd += (uint32_t)__popcll(mk);
         } while (__ballot(hm != 0u));
     }
@@ -553,6 +575,11 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
                 fbi = S.list[32u + lane];
             }
             __builtin_amdgcn_wave_barrier();
+            // (wn_list_addr: the term ids are no entries -- C1 reads the id at whatever offset a word of the list names)
+            if constexpr (wn_list_addr) {
+                S.list[lane] = 0u;
+                __builtin_amdgcn_wave_barrier();
+            }
         }
         const bool act = lane < min(m, (uint32_t)MT);
         uint32_t fb = 0, wb = 0;
@@ -727,10 +754,17 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
             C1S r;
             const bool task = el < epp && e0 + el < nd;
             const uint32_t ent = S.list[task ? e0 + el : 0u];
-            // the entry's id: of a slot (group, term of the group, lane, posting of the lane) of the staged runs, or the id itself (bit 31)
-            const uint32_t esl = ent & 31u;
-            const uint32_t xs = S.stage[(task && !(ent >> 31) ? ((esl >> 2) + 5u * ((ent >> 11) & 1u)) * (uint32_t)WN_SLOT + ((ent >> 5) & 63u) * 4u + (esl & 3u) : 0u)];
-            const uint32_t x = (ent >> 31) ? ent & 0xffffu : xs;
+            // the entry's id: at the entry's offset in the staged runs (zero where the entry is the id itself, bit 31; a lane without a task
+            // reads entry 0, which is an entry of either form or zero) -- no decoding and no lane condition in front of the read
+            uint32_t x;
+            if constexpr (wn_list_addr) {
+                const uint32_t xs = *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(&S.stage[0]) + (ent & WN_ENT_OFF));
+                x = (ent >> 31) ? (ent >> WN_ENT_ID_SHIFT) & 0xffffu : xs;
+            } else {  // of a slot (group, term of the group, lane, posting of the lane)
+                const uint32_t esl = ent & 31u;
+                const uint32_t xs = S.stage[(task && !(ent >> 31) ? ((esl >> 2) + 5u * ((ent >> 11) & 1u)) * (uint32_t)WN_SLOT + ((ent >> 5) & 63u) * 4u + (esl & 3u) : 0u)];
+                x = (ent >> 31) ? ent & 0xffffu : xs;
+            }
             const uint32_t plo = wA, phi = wB;
             const uint32_t pal = plo & ~3u, len = phi - plo;
             const uint16_t *sb = &S.stage[tl * WN_SLOT + (plo - pal)];
@@ -1020,13 +1054,28 @@ __global__ void __launch_bounds__(wn_waves(MT, RK) * 64, (wn_waves(MT, RK) + 3) 
                             }
                         }
                     }
+                    const uint32_t lane_off = lane8 + 2560u * (uint32_t)gq;  // (the group's first term is 5 gq: 512 bytes of stage a term)
+                    if constexpr (wn_list_one) {
+                        // A lane's first TWO flags in one step: with m1 the lanes that hold a flag and m2 the ones that hold a second, the
+                        // lane's entries go to the places behind everything the lanes below it append.  The list comes out lane by lane where
+                        // the loop below makes it round by round; the order is nobody's concern: every entry computes its document's whole
+                        // row, and the document is offered by whichever of its entries claims it.  nd counts every flag, beyond the list's end
+                        // too (the give-up below).  A third flag in a lane is rare: the loop takes what is left.
+                        const uint32_t f2 = flags & (flags - 1u);
+                        const unsigned long long m1 = __ballot(flags != 0u), m2 = __ballot(f2 != 0u);
+                        const uint32_t pos = nd + wn_mbcnt(m1) + wn_mbcnt(m2);
+                        if (flags != 0u && pos < (uint32_t)WN_LIST) S.list[pos] = wn_ent_slot((uint32_t)__ffs((int)flags) - 1u, lane, lane_off, (uint32_t)gq);
+                        if (f2 != 0u && pos + 1u < (uint32_t)WN_LIST) S.list[pos + 1u] = wn_ent_slot((uint32_t)__ffs((int)f2) - 1u, lane, lane_off, (uint32_t)gq);
+                        nd += (uint32_t)__popcll(m1) + (uint32_t)__popcll(m2);
+                        flags = f2 & (f2 - 1u);
+                    }
                     while (__ballot(flags != 0u)) {
                         const bool has = flags != 0u;
                         const uint32_t sl = (uint32_t)__ffs((int)flags) - 1u;
                         flags &= flags - 1u;
                         const unsigned long long mk = __ballot(has);
                         const uint32_t pos = nd + wn_mbcnt(mk);
-                        if (has && pos < (uint32_t)WN_LIST) S.list[pos] = sl | lane << 5 | (uint32_t)gq << 11;  // (the slot: C1 reads the id from the staged run)
+                        if (has && pos < (uint32_t)WN_LIST) S.list[pos] = wn_ent_slot(sl, lane, lane_off, (uint32_t)gq);  // (the posting: C1 reads the id from the staged run)
                         nd += (uint32_t)__popcll(mk);
                     }
                 }
