@@ -1044,7 +1044,8 @@ int vbm25_reranker_in_flight(const vbm25_reranker *);
  *             has an empty run and the fieldnorm code 0, and never scores.  vbm25_doc_terms_*, vbm25_evaluate_documents, the scorer
  *             and the reranker take the handle as they take any other; document index d is sealed document d, the one whose ctid is
  *             the index's payload d.  The handle refers to the index, which must outlive it, and is valid for that index only: after
- *             a compaction the caller binds the new index.  The growing segment is not part of it.  An index of 0 documents binds to
+ *             a compaction the caller binds the new index.  The growing segment is not part of it at the bind; vbm25_doc_terms_append*
+ *             (below) put its documents behind the sealed ones.  An index of 0 documents binds to
  *             a valid handle of 0 documents.  The result costs 8 bytes a posting and 9 a document; the scratch beyond it is a few
  *             words a document plus a double buffer of the runs longer than 2048 postings, never a sort of all postings.
  *             Synchronous, on a stream of its own, no device-wide synchronisation; the index is only read, so two threads may bind
@@ -1058,6 +1059,59 @@ int vbm25_index_bind(const vbm25_index *, vbm25_doc_terms **out);
 int vbm25_reranker_create_from_index(const vbm25_doc_terms *, const vbm25_resolver *, uint32_t depth, uint32_t max_queries,
                                      uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k,
                                      vbm25_reranker **out);
+
+/* The rerank stack on a live table (csrc/live.hip, csrc/reranker.hip): a bound handle grows in place from a delta, and a reranker's ctid
+ * directory takes the new rows by a merge on the device.  Neither repeats what was done before.
+ *   vbm25_doc_terms_append_documents   the bind of `delta` (cast documents in HBM on the handle's device) written behind the handle's
+ *             documents: document i of the delta becomes document n_docs + i.  On a handle from vbm25_index_bind, document
+ *             n_sealed + g is then growing document g -- the one a search hit names as doc_id = 0xFFFFFFFF - g -- when the growing
+ *             segment is fed the same deltas; the handle stays an index-bound one.  Nothing but the delta's own arrays is read and
+ *             nothing is uploaded.  start, term, tf and the fieldnorm codes keep room to spare: a capacity that is outgrown at least
+ *             DOUBLES (vbm25_documents_extend's factor), and a growth step copies device to device.
+ *             Payloads: a delta's payloads are kept in a tail array of the handle that covers the appended documents only (the
+ *             index's plane, or the vbm25_documents given to vbm25_reranker_create, serves the documents the handle was bound with).
+ *             An index-bound handle refuses a delta without payloads; on any other handle the first append decides whether the
+ *             appended documents carry payloads, and later deltas must agree (vbm25_documents_extend's rule).
+ *             The call is synchronous.  Every check and every allocation comes first; then it waits for the DEVICE, and only then
+ *             writes -- so a reranker batch or a scorer call enqueued before the append ends on the old arrays, and a call made
+ *             after it takes the new documents as document indices (cand_doc, the cross product) with no further call.  A refused
+ *             or failed append leaves the handle byte for byte as it was.  The caller does not append while another thread is inside
+ *             a call on the same handle (a scorer's, a reranker's, a download): the handle holds no lock.
+ *             VBM25_ERR_INVALID, nothing changed: NULL arguments, a delta that belongs to a caster slot which is in flight again
+ *             (submitted since the delta's collect and not yet collected: its arrays are being rewritten -- this is all that is
+ *             detected: once that batch is collected the same pointer is the new batch's documents, a valid delta, so a collected
+ *             handle is appended before the submit that takes its slot again), a delta, a handle and a resolver on different devices, a resolver of another index than the handle's, the
+ *             payload rules above.  VBM25_ERR_UNSUPPORTED: 2^32 - 1 documents or more (a document index is 32 bits and 0xFFFFFFFF
+ *             names no document), or known elements that could reach 2^32 (a run's bounds are read as 32 bits).  A delta of 0
+ *             documents that passes the checks returns VBM25_OK and changes nothing.
+ *   vbm25_doc_terms_append   the same from a host CSR in the form vbm25_device_growing_append takes (what vbm25_growing_from_pages
+ *             hands back for the rows that were unsealed when the process came up): keys, tfs, fieldnorm codes and payloads are staged
+ *             to the device once, then the step above.  payload == NULL: a delta without payloads.  The CSR is validated as an upload's:
+ *             keys that do not ascend strictly and a start that is not monotone are VBM25_ERR_INVALID, naming the document.  A
+ *             document whose `deleted` flag is set is appended with an empty run (its fieldnorm code and payload as given), so the
+ *             numbering stays the growing segment's.
+ *   vbm25_doc_terms_base_docs   the documents the handle was bound with (0 for NULL): on an index-bound handle the sealed ones.
+ *             vbm25_doc_terms_info, _download and _device_bytes report the grown handle (the bytes with the room to spare).
+ *   vbm25_reranker_sync     brings the ctid directory up to the handle's n_docs.  On slot 0's stream: the payloads of the documents the
+ *             directory lacks become (ctid, document) pairs in ctid order, equal ctids by ascending document -- a delta of up to
+ *             live_sort_max rows (vbm25_tuning_set, 0 .. 4096, default 4096) sorted by one workgroup in LDS, a larger one by the radix
+ *             sort create uses; old and new entries go to their ranks in the merged order in spare arrays (the new documents'
+ *             indices exceed the old ones', so a ctid of several documents still names the lowest); the evenly spaced directory is
+ *             sampled again, its stride may change.  The call then waits for every slot of the reranker and swaps the spare arrays
+ *             in: a batch submitted before the sync resolves its ctids against the old directory whenever it is collected, one
+ *             submitted after it against the new one.  The sorted arrays and the delta's scratch keep room to spare that at least
+ *             doubles when outgrown: a sync that fits allocates nothing, `allocations` moves only in a sync that grows, submit and
+ *             collect still allocate nothing.  max_candidates is unchanged: a cross product that outgrows it is refused at submit.
+ *             VBM25_ERR_INVALID, the directory unchanged: NULL, a reranker without payloads, appended documents without payloads.
+ *             Nothing new: VBM25_OK.  vbm25_reranker_info's n_docs stays the handle's count;
+ *             vbm25_reranker_directory_docs is the count the directory covers (0 for NULL).
+ *             vbm25_reranker_create and _create_from_index on a handle that has grown build the directory over everything at once
+ *             -- the base payloads, then the handle's tail -- and compare `payloads` with vbm25_doc_terms_base_docs. */
+int vbm25_doc_terms_append_documents(vbm25_doc_terms *, const vbm25_documents *delta, const vbm25_resolver *);
+int vbm25_doc_terms_append(vbm25_doc_terms *, const vbm25_growing_desc *delta, const vbm25_resolver *);
+uint32_t vbm25_doc_terms_base_docs(const vbm25_doc_terms *);
+int vbm25_reranker_sync(vbm25_reranker *);
+uint32_t vbm25_reranker_directory_docs(const vbm25_reranker *);
 
 #ifdef __cplusplus
 }

@@ -296,6 +296,8 @@ class Caster {
 // Cast documents bound to one index's vocabulary (RAII over vbm25_doc_terms): per document the ascending term ids of its known
 // elements with their tfs, and its fieldnorm code, in HBM.  evaluate() is bm25::evaluate (evaluate.rs:22-74) for a batch of queries,
 // each against its own candidate documents; the SQL operator `<&>` returns the negation of these values.  The index must outlive it.
+// append() writes the bind of a delta behind the handle's documents (a live table's new rows; on a handle from Index::bind document
+// base_docs() + g is growing document g); nobody else is inside a call on the handle meanwhile.
 class Scorer;
 class DocTerms {
   public:
@@ -317,6 +319,12 @@ class DocTerms {
         return n;
     }
     uint64_t device_bytes() const { return vbm25_doc_terms_device_bytes(h_); }
+    // the documents the handle was bound with (from Index::bind: the sealed ones)
+    uint32_t base_docs() const { return vbm25_doc_terms_base_docs(h_); }
+    // cast documents in HBM on the handle's device become documents docs() .. (vbm25_doc_terms_append_documents)
+    void append(const Documents &delta, const Resolver &resolver) { check(vbm25_doc_terms_append_documents(h_, delta.handle(), resolver.handle())); }
+    // the same from a host CSR; a document flagged deleted gets an empty run (vbm25_doc_terms_append)
+    inline void append(const GrowingDocs &delta, const Resolver &resolver);
     void download(std::vector<uint64_t> &start, std::vector<uint32_t> &term, std::vector<uint32_t> &tf) const {
         start.assign(size_t(docs()) + 1, 0);
         term.assign(known() + 1, 0);
@@ -364,8 +372,8 @@ inline DocTerms Index::bind() const { return DocTerms(*this); }
 // mutex inside serialises them); several scorers on one DocTerms may run at once.  Move-only.
 class Scorer {
   public:
-    explicit Scorer(const DocTerms &documents) : docs_(documents.docs()) { check(vbm25_scorer_create(documents.handle(), &h_)); }
-    Scorer(Scorer &&o) noexcept : h_(o.h_), docs_(o.docs_) { o.h_ = nullptr; }
+    explicit Scorer(const DocTerms &documents) : t_(documents.handle()) { check(vbm25_scorer_create(documents.handle(), &h_)); }
+    Scorer(Scorer &&o) noexcept : h_(o.h_), t_(o.t_) { o.h_ = nullptr; }
     Scorer(const Scorer &) = delete;
     Scorer &operator=(const Scorer &) = delete;
     ~Scorer() { vbm25_scorer_free(h_); }
@@ -384,7 +392,9 @@ class Scorer {
     }
     std::vector<double> evaluate(const std::vector<uint32_t> &term_ids, const std::vector<uint32_t> &q_off) {
         const uint32_t nq = uint32_t(q_off.size() - 1);
-        std::vector<double> scores(size_t(nq) * docs_ + 1);
+        uint32_t docs = 0;  // (as of now: the handle may have grown)
+        check(vbm25_doc_terms_info(t_, &docs, nullptr, nullptr));
+        std::vector<double> scores(size_t(nq) * docs + 1);
         std::vector<uint32_t> ids(term_ids);
         ids.push_back(0);
         check(vbm25_scorer_evaluate(h_, ids.data(), q_off.data(), nq, nullptr, nullptr, scores.data()));
@@ -419,7 +429,7 @@ class Scorer {
         n_ranks.pop_back();
     }
     vbm25_scorer *h_ = nullptr;
-    uint32_t docs_ = 0;
+    const vbm25_doc_terms *t_ = nullptr;
 };
 inline Scorer DocTerms::scorer() const { return Scorer(*this); }
 
@@ -427,7 +437,8 @@ inline Scorer DocTerms::scorer() const { return Scorer(*this); }
 // (both must outlive it).  submit() takes lexeme queries and candidates -- document indices, ctids (needs `payloads`, a Documents
 // with payloads of the same documents, at construction; it may be freed afterwards) or none for the cross product -- and returns at
 // once; collect() waits for the oldest batch and hands out Scorer::topk's rows, byte for byte what Resolver::submit / collect
-// followed by Scorer::topk give.  Nothing is allocated after the constructor.  One thread drives a reranker.  Move-only.
+// followed by Scorer::topk give.  Nothing is allocated after the constructor, except by a sync() that outgrows its room to spare.
+// sync() brings the ctid directory up to the DocTerms' documents after DocTerms::append.  One thread drives a reranker.  Move-only.
 // With the tag from_index, on a DocTerms made by Index::bind, the ctids are the index's own payloads (vbm25_reranker_create_from_index).
 struct FromIndex {};
 constexpr FromIndex from_index{};
@@ -490,8 +501,12 @@ class Reranker {
         return k;
     }
     int in_flight() const { return vbm25_reranker_in_flight(h_); }
+    // the ctids of the documents appended since create or the last sync merged into the directory on the device (vbm25_reranker_sync)
+    void sync() { check(vbm25_reranker_sync(h_)); }
+    // the documents the directory covers
+    uint32_t directory_docs() const { return vbm25_reranker_directory_docs(h_); }
     uint64_t device_bytes() const { return vbm25_reranker_device_bytes(h_); }
-    // every allocation and creation the handle has made: it does not move after the constructor
+    // every allocation and creation the handle has made: it moves only in a sync() that grows
     uint64_t allocations() const {
         uint64_t n = 0;
         check(vbm25_reranker_info(h_, nullptr, nullptr, nullptr, &n));
@@ -777,6 +792,19 @@ inline GrowingDocs growing_docs_of(vbm25_growing *g) {
     vbm25_growing_free(g);
     check(rc);
     return out;
+}
+using GrowingDesc = GrowingDocs;
+inline void DocTerms::append(const GrowingDocs &delta, const Resolver &resolver) {
+    vbm25_growing_desc d{};
+    d.n_docs = uint32_t(delta.size());
+    d.n_elements = delta.tf.size();
+    d.start = delta.start.data();
+    d.key = delta.key.empty() ? nullptr : delta.key[0].data();
+    d.tf = delta.tf.data();
+    d.fieldnorm = delta.fieldnorm.data();
+    d.payload = delta.payload.empty() ? nullptr : delta.payload.data();  // (none: a delta without payloads)
+    d.deleted = delta.deleted.empty() ? nullptr : delta.deleted.data();
+    check(vbm25_doc_terms_append(h_, &d, resolver.handle()));
 }
 inline GrowingDocs Documents::download(std::vector<uint32_t> *doc_len) const {
     vbm25_growing *g = nullptr;

@@ -207,6 +207,11 @@ ABI = {
     "vbm25_device_vacuum_bulkdelete": (i32, [vp, vp, vp, vp, vp]),
     "vbm25_index_bind": (i32, [vp, vp]),
     "vbm25_reranker_create_from_index": (i32, [vp, vp, u32, u32, u32, u64, u64, u32, vp]),
+    "vbm25_doc_terms_append_documents": (i32, [vp, vp, vp]),
+    "vbm25_doc_terms_append": (i32, [vp, vp, vp]),
+    "vbm25_doc_terms_base_docs": (u32, [vp]),
+    "vbm25_reranker_sync": (i32, [vp]),
+    "vbm25_reranker_directory_docs": (u32, [vp]),
 }
 
 

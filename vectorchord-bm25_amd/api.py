@@ -1229,7 +1229,8 @@ def set_tuning(name, value):
     as a multiple of k, 2 .. 8; both read at the start of each Scorer call), tid_grid (the most workgroups of the TID match kernel,
     1 .. 2048, read at each launch) and tid_dir (log2 of a TidSet's directory entries, 0 .. 12, read when a TidSet is made).  A
     Reranker reads eval_grid, rerank_part and rerank_buf at each submit, and rerank_part (the size of its part-list scratch) and tid_dir
-    (its payload directory) when it is made.  No switch of
+    (its payload directory) when it is made; Reranker.sync() reads tid_dir again (the directory's new shape) and live_sort_max (the most
+    rows of a delta that it sorts in one workgroup's LDS, 0 .. 4096, 0 = always the radix sort).  No switch of
     the product library changes results (`dbg`, the timing experiments of scan_win_kernel, exists only in the development build
     libvbm25_dev.so)."""
     f = lib().vbm25_tuning_set
@@ -1477,9 +1478,49 @@ class DocTerms:
     def __init__(self, handle, index=None):
         self.h = handle
         self.index = index  # (kept alive: the handle refers to it)
+        self._refresh()
+
+    def _refresh(self):
         nd, nk, dev = C.c_uint32(), C.c_uint64(), C.c_int()
         check(lib().vbm25_doc_terms_info(self.h, C.byref(nd), C.byref(nk), C.byref(dev)))
         self.n_docs, self.n_known, self.device = nd.value, nk.value, dev.value
+
+    @property
+    def base_docs(self):
+        """vbm25_doc_terms_base_docs: the documents the handle was bound with (from GpuIndex.bind: the sealed ones)"""
+        return int(lib().vbm25_doc_terms_base_docs(self.h))
+
+    def append_documents(self, documents, resolver):
+        """vbm25_doc_terms_append_documents: the bind of cast `documents` written behind this handle's, on the device -- document i
+        of the delta becomes document n_docs + i; on a handle from GpuIndex.bind, document base_docs + g is growing document g when
+        the GrowingSegment is fed the same deltas.  Synchronous; a scorer or a reranker on the handle takes the new documents as
+        indices at its next call, a reranker's ctids after Reranker.sync().  Nobody else is inside a call on the handle meanwhile."""
+        try:
+            check(lib().vbm25_doc_terms_append_documents(self.h, documents.h, resolver.h))
+        finally:
+            self._refresh()
+        return self
+
+    def append(self, g_start, g_key, g_tf, g_fieldnorm, g_payload, resolver, g_deleted=None):
+        """vbm25_doc_terms_append: append_documents from the host CSR GrowingSegment.append takes (g_payload None: a delta without
+        payloads); a document whose g_deleted is set gets an empty run and keeps its place in the numbering."""
+        g_start = np.ascontiguousarray(g_start, dtype=np.uint64)
+        g_key = np.ascontiguousarray(g_key, dtype=np.uint8).reshape(-1)
+        g_tf = np.ascontiguousarray(g_tf, dtype=np.uint32)
+        g_fieldnorm = np.ascontiguousarray(g_fieldnorm, dtype=np.uint8)
+        g_payload = None if g_payload is None else _at_least_one(g_payload, np.uint16)
+        g_deleted = None if g_deleted is None else np.ascontiguousarray(g_deleted, dtype=np.uint8)
+        if len(g_key) != 16 * len(g_tf):
+            raise ValueError(f"{len(g_key)} key bytes for {len(g_tf)} elements")
+        d = GrowingDesc()
+        d.n_docs, d.n_elements = max(len(g_start) - 1, 0), len(g_tf)
+        d.start, d.key, d.tf = _p(g_start), _p(g_key), _p(g_tf)
+        d.fieldnorm, d.payload, d.deleted = _p(g_fieldnorm), _p(g_payload), _p(g_deleted)
+        try:
+            check(lib().vbm25_doc_terms_append(self.h, C.byref(d), resolver.h))
+        finally:
+            self._refresh()
+        return self
 
     def device_bytes(self):
         return int(lib().vbm25_doc_terms_device_bytes(self.h))
@@ -1606,7 +1647,8 @@ class Reranker:
     construction) or none for the cross product -- and
     returns at once; collect() waits for the oldest batch and returns Scorer.topk's (ranks, n_ranks), byte for byte what
     Resolver.submit / collect followed by Scorer.topk give.  A ctid no document carries is not eligible and keeps its pos; a ctid of
-    several documents names the lowest index.  Nothing is allocated after the constructor.  One thread drives a reranker.  Also a
+    several documents names the lowest index.  Nothing is allocated after the constructor, except by a sync() that outgrows its room
+    to spare.  One thread drives a reranker.  Also a
     context manager."""
 
     def __init__(self, doc_terms, resolver, depth, max_queries, max_lexemes, max_bytes, max_candidates, max_k, documents=None,
@@ -1662,6 +1704,16 @@ class Reranker:
         self._shapes.pop(0)
         assert (got_nq.value, got_k.value) == (nq, k)
         return ranks, n_ranks
+
+    def sync(self):
+        """vbm25_reranker_sync: the ctid directory brought up to the DocTerms' n_docs after appends, by a merge on the device.
+        Batches already submitted resolve their ctids against the old directory, later ones against the new one."""
+        check(lib().vbm25_reranker_sync(self.h))
+
+    @property
+    def directory_docs(self):
+        """vbm25_reranker_directory_docs: the documents the ctid directory covers (the DocTerms' n_docs as of create or the last sync)"""
+        return int(lib().vbm25_reranker_directory_docs(self.h))
 
     def in_flight(self):
         return int(lib().vbm25_reranker_in_flight(self.h))

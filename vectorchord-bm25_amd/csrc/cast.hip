@@ -955,6 +955,7 @@ int caster_submit(vbm25_caster *c, const uint8_t *bytes, const uint64_t *lex_off
     h.n_docs = n_docs;
     h.n_elements = 0;  // (known at collect)
     h.has_payload = doc_payload != nullptr;
+    h.in_flight = true;
     s.launched = launched;
     c->ring.push();
     quiesce.s = nullptr;
@@ -970,6 +971,7 @@ int caster_collect(vbm25_caster *c, const vbm25_documents **out) {
     CastSlot &s = c->slots[c->ring.head];
     HIP_TRY(hipEventSynchronize(s.done.e));
     s.docs.n_elements = *s.n_elements.as<ull>();
+    s.docs.in_flight = false;
     *out = &s.docs;
     c->last_collected = int(c->ring.pop());
     return VBM25_OK;

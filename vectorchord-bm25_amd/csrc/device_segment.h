@@ -49,6 +49,7 @@ struct vbm25_documents {
     uint64_t n_elements = 0;
     bool has_payload = false;
     const void *caster = nullptr;
+    bool in_flight = false;  // a caster's slot between the submit that takes it and its collect: the arrays are being written
     vbm25::HbmArray d_start, d_key, d_tf, d_length, d_fieldnorm, d_payload;
 };
 

@@ -137,11 +137,11 @@ int documents_bind(const vbm25_documents *h, const vbm25_resolver *r, vbm25_doc_
         return set_error(VBM25_ERR_INVALID, "the documents are on device %d, the resolver's index is on device %d", h->device, v.device);
     if (int rc = use_eval_device(h->device)) return rc;
     g_bind_ms = -1.0;
-    const uint32_t cap = g_eval_grid.load(), n_docs = h->n_docs, n_el = uint32_t(h->n_elements);  // (fewer than 2^31: a cast takes no more)
+    const uint32_t n_docs = h->n_docs, n_el = uint32_t(h->n_elements);  // (fewer than 2^31: a cast takes no more)
     auto t = std::make_unique<vbm25_doc_terms>();
     t->index = v.index;
     t->device = h->device;
-    t->n_docs = n_docs;
+    t->n_docs = t->base_docs = n_docs;
     HbmArray ids, counts, cub;
     Event ev_start, ev_mid, ev_resume, ev_done;
     Stream st;  // (of the call's own: a launch on the null stream would wait for every other stream of the device)
@@ -161,10 +161,8 @@ int documents_bind(const vbm25_documents *h, const vbm25_resolver *r, vbm25_doc_
     if (n_docs) HIP_TRY(hipMemcpyAsync(t->d_fieldnorm.p, h->d_fieldnorm.p, n_docs, hipMemcpyDeviceToDevice, st.s));
     const ull *doc_start = h->d_start.as<ull>();
     if (n_el) {
-        bind_lookup_kernel<<<capped_grid(n_el, WG, cap), WG, 0, st.s>>>(h->d_key.as<Key>(), n_el, static_cast<const Key *>(v.keys), v.n_terms, ids.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        bind_count_kernel<<<capped_grid(n_docs, WG / 64, cap), WG, 0, st.s>>>(ids.as<uint32_t>(), doc_start, n_docs, counts.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_bind_lookup(h->d_key.p, n_el, v.keys, v.n_terms, ids.as<uint32_t>(), st.s));
+        HIP_TRY(launch_bind_count(ids.as<uint32_t>(), doc_start, n_docs, counts.as<uint32_t>(), st.s));
     }
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub.p, cub_bytes, hipcub::TransformInputIterator<ull, WidenU32, const uint32_t *>(counts.as<uint32_t>(), WidenU32()),
                                             t->d_start.as<ull>(), int(n_docs + 1), st.s));
@@ -177,9 +175,8 @@ int documents_bind(const vbm25_documents *h, const vbm25_resolver *r, vbm25_doc_
     HIP_TRY(t->d_tf.alloc(4ull * n_known));
     HIP_TRY(hipEventRecord(ev_resume.e, st.s));
     if (n_known) {
-        bind_compact_kernel<<<capped_grid(n_docs, WG / 64, cap), WG, 0, st.s>>>(ids.as<uint32_t>(), h->d_tf.as<uint32_t>(), doc_start, t->d_start.as<ull>(), n_docs,
-                                                                          t->d_term.as<uint32_t>(), t->d_tf.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_bind_compact(ids.as<uint32_t>(), h->d_tf.as<uint32_t>(), doc_start, t->d_start.as<ull>(), n_docs, t->d_term.as<uint32_t>(),
+                                    t->d_tf.as<uint32_t>(), st.s));
     }
     HIP_TRY(hipEventRecord(ev_done.e, st.s));
     HIP_TRY(hipStreamSynchronize(st.s));
@@ -328,6 +325,23 @@ hipError_t launch_eval_score(const ScoreArgs &a, hipStream_t stream) {
 
 uint32_t eval_grid_cap() { return g_eval_grid.load(); }
 
+hipError_t launch_bind_lookup(const void *keys, uint32_t n_el, const void *vocab, uint32_t n_terms, uint32_t *ids, hipStream_t stream) {
+    bind_lookup_kernel<<<capped_grid(n_el, WG, g_eval_grid.load()), WG, 0, stream>>>(static_cast<const Key *>(keys), n_el, static_cast<const Key *>(vocab),
+                                                                                     n_terms, ids);
+    return hipGetLastError();
+}
+
+hipError_t launch_bind_count(const uint32_t *ids, const ull *doc_start, uint32_t n_docs, uint32_t *counts, hipStream_t stream) {
+    bind_count_kernel<<<capped_grid(n_docs, WG / 64, g_eval_grid.load()), WG, 0, stream>>>(ids, doc_start, n_docs, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_bind_compact(const uint32_t *ids, const uint32_t *tf, const ull *doc_start, const ull *start, uint32_t n_docs, uint32_t *out_term,
+                               uint32_t *out_tf, hipStream_t stream) {
+    bind_compact_kernel<<<capped_grid(n_docs, WG / 64, g_eval_grid.load()), WG, 0, stream>>>(ids, tf, doc_start, start, n_docs, out_term, out_tf);
+    return hipGetLastError();
+}
+
 }  // namespace evl
 }  // namespace vbm25
 
@@ -360,7 +374,7 @@ int vbm25_doc_terms_download(const vbm25_doc_terms *t, uint64_t *start, uint32_t
 uint64_t vbm25_doc_terms_device_bytes(const vbm25_doc_terms *t) {
     uint64_t n = 0;
     if (t)
-        for (const HbmArray *a : {&t->d_start, &t->d_term, &t->d_tf, &t->d_fieldnorm}) n += a->bytes;
+        for (const HbmArray *a : {&t->d_start, &t->d_term, &t->d_tf, &t->d_fieldnorm, &t->d_tail_payload}) n += a->bytes;  // (the room to spare included)
     return n;
 }
 

@@ -12,14 +12,22 @@
 #include "hip_host.h"
 
 // Cast documents bound to one index's vocabulary: per document the ascending ids of its known elements with their tfs, and the
-// fieldnorm code the cast gave it.  Only ever read after it is made.
+// fieldnorm code the cast gave it.  Only ever read after it is made, except by vbm25_doc_terms_append / _append_documents (live.hip),
+// which write behind the documents it holds: from the first append on the arrays' `bytes` are capacities, and no consumer reads them
+// for a length.
 struct vbm25_doc_terms {
     const vbm25_index *index = nullptr;
     int device = 0;
     uint32_t n_docs = 0;
     uint64_t n_known = 0;
-    bool from_index = false;  // made by vbm25_index_bind: its documents are the index's own sealed documents, in the index's order
+    bool from_index = false;  // made by vbm25_index_bind: its first base_docs documents are the index's own sealed documents, in the index's order
     vbm25::HbmArray d_start, d_term, d_tf, d_fieldnorm;
+    // the documents the handle was bound with; documents base_docs .. n_docs were appended
+    uint32_t base_docs = 0;
+    // the appended documents' payloads, 6 bytes each (document base_docs + i at 3 i), when the appends carry them.  tail_decided: the
+    // first append has been made, and tail_payload says whether it -- and so every later one -- carried payloads.
+    bool tail_decided = false, tail_payload = false;
+    vbm25::HbmArray d_tail_payload;
 };
 
 namespace vbm25 {
@@ -60,6 +68,15 @@ void fill_score_tables(const vbm25_doc_terms *t, const EvaluateTables &ix, Score
 hipError_t launch_eval_score(const ScoreArgs &a, hipStream_t stream);
 // eval_grid of vbm25_tuning_set as it stands
 uint32_t eval_grid_cap();
+// The bind's steps on `stream`, grids capped by eval_grid as read now: vbm25_documents_bind and the appends of live.hip run the same
+// kernels.  keys / doc_start / tf are a cast's arrays; ids has one entry an element, counts one a document.
+//   lookup   ids[e] = the term id of key e in the vocabulary, or NOT_FOUND
+//   count    counts[d] = the known elements of document d
+//   compact  (id, tf) of document d's known elements to out_term / out_tf at start[d] .., in element order
+hipError_t launch_bind_lookup(const void *keys, uint32_t n_el, const void *vocab, uint32_t n_terms, uint32_t *ids, hipStream_t stream);
+hipError_t launch_bind_count(const uint32_t *ids, const unsigned long long *doc_start, uint32_t n_docs, uint32_t *counts, hipStream_t stream);
+hipError_t launch_bind_compact(const uint32_t *ids, const uint32_t *tf, const unsigned long long *doc_start, const unsigned long long *start,
+                               uint32_t n_docs, uint32_t *out_term, uint32_t *out_tf, hipStream_t stream);
 int use_eval_device(int device);
 
 }  // namespace evl

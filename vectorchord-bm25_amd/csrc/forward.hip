@@ -265,7 +265,7 @@ int index_bind(const vbm25_index *ix, vbm25_doc_terms **out) {
     auto t = std::make_unique<vbm25_doc_terms>();
     t->index = ix;
     t->device = ix->device;
-    t->n_docs = n_docs;
+    t->n_docs = t->base_docs = n_docs;
     t->from_index = true;
     HbmArray counts, cub, cls, group_doc, long_doc, long_begin, long_end, buf_term, buf_tf, buf_term2, buf_tf2, seg_cub;
     Event ev_start, ev_mid, ev_resume, ev_done;

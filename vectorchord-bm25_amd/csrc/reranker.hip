@@ -18,8 +18,13 @@
 //   from the doc_payload plane of the index the handle was bound from): (tid_key(payload[d]), d) sorted by the
 //   48 key bits -- the sort is stable, equal keys keep ascending d, so a ctid of several documents resolves to the lowest -- and
 //   tid_lane.h's directory of evenly spaced keys over them, under the tid_dir switch.
+//   vbm25_reranker_sync (after vbm25_doc_terms_append*): the ctids of the documents the directory lacks, sorted (live_sort_kernel in
+//   LDS up to live_sort_max rows, else payload_key_kernel + the radix sort), merged by rank with the old entries into spare arrays
+//   (live_merge_kernel; live_shared.h) and the directory sampled again, on slot 0's stream; the spares are swapped in once every
+//   slot has finished, so a batch submitted before the sync reads the old directory to its end.  cand_lookup_kernel's n_keys is the
+//   count the directory covers (dir_n), not the handle's n_docs.
 //   No stream waits for another: a slot is reused only after its collect, and the doc_terms, the vocabulary and the directory are
-//   only read.  No kernel here has scratch memory.
+//   only read between syncs.  No kernel here has scratch memory.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -35,6 +40,7 @@
 #include "evaluate_shared.h"
 #include "rerank_shared.h"
 #include "tid_lane.h"
+#include "live_shared.h"
 
 namespace {
 
@@ -50,12 +56,13 @@ constexpr uint32_t WG = 256, MAX_GRID = 2048;
 enum CandKind : uint32_t { CAND_CROSS = 0, CAND_DOC = 1, CAND_TID = 2 };
 enum PackPath : uint32_t { PATH_NONE = 0, PATH_WAVE = 1, PATH_RADIX = 2 };
 
-__global__ void __launch_bounds__(WG) payload_key_kernel(const uint16_t *payload, uint32_t n, ull *keys, uint32_t *docs) {
+// payload: the ctids of documents first .. first + n; keys / docs: where their entries go
+__global__ void __launch_bounds__(WG) payload_key_kernel(const uint16_t *payload, uint32_t n, uint32_t first, ull *keys, uint32_t *docs) {
     for (uint32_t d = blockIdx.x * WG + threadIdx.x; d < n; d += gridDim.x * WG) {
         const uint16_t *p = payload + 3ull * d;
         const uint16_t p3[3] = {p[0], p[1], p[2]};
         keys[d] = tid_key(p3);
-        docs[d] = d;
+        docs[d] = first + d;
     }
 }
 
@@ -133,8 +140,16 @@ struct vbm25_reranker {
     Seed seed{};
     bool has_payloads = false;
     uint32_t n_dir = 0, stride = 1;
-    HbmArray dir_keys, dir_docs, dir;  // the payload directory: n_docs sorted keys, their documents, n_dir evenly spaced keys
-    double directory_ms = -1.0;
+    uint32_t dir_n = 0;  // the documents the directory covers: the handle's n_docs at create or at the last vbm25_reranker_sync
+    HbmArray dir_keys, dir_docs, dir;  // the payload directory: dir_n sorted keys, their documents, n_dir evenly spaced keys
+    // vbm25_reranker_sync: the spare arrays a merge writes and the sync swaps in (dir_keys / dir_docs and their spares hold room to
+    // spare, in entries: dir_cap; the spare directory has MAX_DIR_LOG2's 4096 entries), and the delta's scratch -- its sorted keys
+    // and documents, the radix sort's input and temporary storage -- for delta_cap rows.  All empty until the first sync that grows.
+    HbmArray dir_keys2, dir_docs2, dir2, delta_keys, delta_docs, delta_keys_in, delta_docs_in, delta_cub;
+    uint64_t dir_cap = 0, delta_cap = 0;
+    size_t delta_cub_bytes = 0;
+    Event sync_start, sync_done;  // around a sync's kernels (made by the first sync)
+    double directory_ms = -1.0, sync_ms = -1.0;
     size_t in_capacity = 0, cub_bytes = 0;
     std::vector<uint32_t> zero_off;  // max_queries + 1 zeros: the q_off of a lexeme batch before it is resolved
     ResourceTally tally;  // every allocation and creation of the handle goes through it
@@ -146,8 +161,12 @@ struct vbm25_reranker {
 
 namespace {
 
-// the payload directory over `n` payloads in HBM (a vbm25_documents' or an index's), on slot 0's stream; synchronous
-int build_directory(vbm25_reranker *r, const uint16_t *payload, uint32_t n) {
+// the payload directory over `n` payloads in HBM (a vbm25_documents' or an index's) and, behind them, the `n_tail` payloads of the
+// documents the handle was appended (n_tail == 0: a handle that has not grown), on slot 0's stream; synchronous
+int build_directory(vbm25_reranker *r, const uint16_t *payload, uint32_t n_base, const uint16_t *tail, uint32_t n_tail) {
+    const uint32_t n = n_base + n_tail;
+    r->dir_n = n;
+    r->dir_cap = n;
     const DirShape shape = dir_shape(n, tid_dir_now());
     r->n_dir = shape.n_dir;
     r->stride = shape.stride;
@@ -169,7 +188,10 @@ int build_directory(vbm25_reranker *r, const uint16_t *payload, uint32_t n) {
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                                   int(n), 0, 48, st));
         HIP_TRY(ta.device_alloc(cub, cub_bytes, false));
-        payload_key_kernel<<<grid_for(n, WG, MAX_GRID), WG, 0, st>>>(payload, n, keys_in.as<ull>(), docs_in.as<uint32_t>());
+        if (n_base) payload_key_kernel<<<grid_for(n_base, WG, MAX_GRID), WG, 0, st>>>(payload, n_base, 0u, keys_in.as<ull>(), docs_in.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        if (n_tail)
+            payload_key_kernel<<<grid_for(n_tail, WG, MAX_GRID), WG, 0, st>>>(tail, n_tail, n_base, keys_in.as<ull>() + n_base, docs_in.as<uint32_t>() + n_base);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub.p, cub_bytes, keys_in.as<ull>(), r->dir_keys.as<ull>(), docs_in.as<uint32_t>(),
                                                   r->dir_docs.as<uint32_t>(), int(n), 0, 48, st));
@@ -204,12 +226,15 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
     if (v.index != t->index) return set_error(VBM25_ERR_INVALID, "the documents are bound to another index than the resolver's");
     if (payloads) {
         if (!payloads->has_payload) return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup carry no payloads");
-        if (payloads->n_docs != t->n_docs)
-            return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup are %u, the bound documents %u", payloads->n_docs, t->n_docs);
+        if (payloads->n_docs != t->base_docs)  // (a handle that has grown: the appended documents' ctids are in its tail)
+            return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup are %u, the bound documents %u", payloads->n_docs, t->base_docs);
         if (payloads->device != t->device)
             return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup are on device %d, the bound documents on device %d",
                              payloads->device, t->device);
     }
+    const uint32_t n_tail = t->n_docs - t->base_docs;
+    if ((payloads || from_index) && n_tail && !t->tail_payload)
+        return set_error(VBM25_ERR_INVALID, "the %u documents appended to the bound documents carry no payloads: no ctid names them", n_tail);
     EvaluateTables ix;
     if (int rc = index_evaluate_tables(t->index, &ix)) return rc;
     if (ix.n_docs == 0) return set_error(VBM25_ERR_INVALID, "evaluate on an index without sealed documents");
@@ -263,12 +288,13 @@ int reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vb
         HIP_TRY(ta.device_alloc(s.scr, part_list_bytes(r->max_lists, max_k)));
     }
     if (payloads) {
-        if (int rc = build_directory(r, payloads->d_payload.as<uint16_t>(), payloads->n_docs)) return rc;
+        if (int rc = build_directory(r, payloads->d_payload.as<uint16_t>(), payloads->n_docs, t->d_tail_payload.as<uint16_t>(), n_tail)) return rc;
     } else if (from_index) {  // (an index-bound handle has the index's n_docs documents, in its order)
         const uint16_t *plane = nullptr;
         uint32_t n = 0;
         if (int rc = index_payloads(t->index, &plane, &n)) return rc;
-        if (int rc = build_directory(r, plane, n)) return rc;
+        if (n != t->base_docs) return set_error(VBM25_ERR_INVALID, "the index has %u documents, the handle was bound with %u", n, t->base_docs);
+        if (int rc = build_directory(r, plane, n, t->d_tail_payload.as<uint16_t>(), n_tail)) return rc;
     }
     *out = guard.release();
     return VBM25_OK;
@@ -388,7 +414,7 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     }
     if (kind == CAND_TID) {
         const LookupArgs la{reinterpret_cast<const uint16_t *>(dev + g.docs), n_pairs, r->dir.as<ull>(), r->dir_keys.as<ull>(),
-                            r->dir_docs.as<uint32_t>(), t->n_docs, r->n_dir, r->stride, s.cand_doc.as<uint32_t>()};
+                            r->dir_docs.as<uint32_t>(), r->dir_n, r->n_dir, r->stride, s.cand_doc.as<uint32_t>()};
         const uint32_t cap = std::min(MAX_GRID, std::max(1u, eval_grid_cap()));
         cand_lookup_kernel<<<grid_for(n_pairs, WG, cap), WG, 8ull * std::max(1u, r->n_dir), st>>>(la);
         HIP_TRY(hipGetLastError());
@@ -427,9 +453,115 @@ int reranker_collect(vbm25_reranker *r, vbm25_rank *ranks, uint32_t *n_ranks, ui
     return VBM25_OK;
 }
 
+// vbm25_reranker_sync: the ctids of documents dir_n .. t->n_docs (the handle's tail) sorted, merged by rank into the spare arrays and the
+// directory sampled again, all on slot 0's stream; the spares swapped in once every slot has finished
+int reranker_sync(vbm25_reranker *r) {
+    if (!r) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (!r->has_payloads) return set_error(VBM25_ERR_INVALID, "sync on a reranker created without payloads: it has no ctid directory");
+    const vbm25_doc_terms *t = r->t;
+    const uint32_t n_old = r->dir_n, n_new = t->n_docs, m = n_new - n_old;
+    if (!m) return VBM25_OK;
+    if (!t->tail_payload)
+        return set_error(VBM25_ERR_INVALID, "the %u documents appended to the bound documents carry no payloads: no ctid names them", m);
+    if (int rc = use_eval_device(r->device)) return rc;
+    hipStream_t st = r->slots[0].stream.s;
+    ResourceTally &ta = r->tally;
+    const uint32_t sort_max = live::live_sort_max_now();
+    const bool radix = m > sort_max;
+    // Everything the sync needs, before anything is enqueued.  Capacities at least double (vbm25_documents_extend's factor).  What a
+    // growth step replaces is only ever written by a sync (the spares, the scratch): nothing is copied.
+    auto regrow = [&](HbmArray &a, size_t bytes) -> hipError_t {
+        ta.device_bytes -= a.footprint();
+        a.release();
+        return ta.device_alloc(a, bytes);
+    };
+    constexpr size_t DIR_BYTES = 8ull << MAX_DIR_LOG2;  // (a directory of any shape)
+    const uint64_t cap = n_new > r->dir_cap ? std::max<uint64_t>(n_new, 2 * r->dir_cap) : r->dir_cap;
+    if (!r->dir_keys2.p || 8 * cap > r->dir_keys2.bytes) {
+        HIP_TRY(regrow(r->dir_keys2, 8 * cap));
+        HIP_TRY(regrow(r->dir_docs2, 4 * cap));
+    }
+    if (r->dir2.bytes < DIR_BYTES) HIP_TRY(regrow(r->dir2, DIR_BYTES));
+    if (!r->sync_start.e) {
+        HIP_TRY(ta.event_create(r->sync_start));
+        HIP_TRY(ta.event_create(r->sync_done));
+    }
+    if (m > r->delta_cap) {  // the delta's scratch, the radix sort's included whichever sort this delta takes: a later sync that fits allocates nothing
+        const uint64_t dcap = std::max<uint64_t>({m, 2 * r->delta_cap, live::LIVE_SORT_CAP});
+        // hipcub's temporary storage is asked for dcap items and used for every m <= dcap: the requirement of a radix sort does not shrink
+        // with its input (SortPairs refuses storage smaller than it needs, it does not write past it)
+        size_t cub_bytes = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (const ull *)nullptr, (ull *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                  int(dcap), 0, 48, st));
+        HIP_TRY(regrow(r->delta_keys, 8 * dcap));
+        HIP_TRY(regrow(r->delta_docs, 4 * dcap));
+        HIP_TRY(regrow(r->delta_keys_in, 8 * dcap));
+        HIP_TRY(regrow(r->delta_docs_in, 4 * dcap));
+        HIP_TRY(regrow(r->delta_cub, cub_bytes));
+        r->delta_cub_bytes = cub_bytes;
+        r->delta_cap = dcap;
+    }
+    const DirShape shape = dir_shape(n_new, tid_dir_now());
+    const uint16_t *tail = t->d_tail_payload.as<uint16_t>() + 3ull * (n_old - t->base_docs);
+    Quiesce quiesce(st);  // (a failed step below leaves nothing in flight that reads the scratch)
+    HIP_TRY(hipEventRecord(r->sync_start.e, st));
+    if (radix) {
+        payload_key_kernel<<<grid_for(m, WG, MAX_GRID), WG, 0, st>>>(tail, m, n_old, r->delta_keys_in.as<ull>(), r->delta_docs_in.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        size_t cub_bytes = r->delta_cub_bytes;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(r->delta_cub.p, cub_bytes, r->delta_keys_in.as<ull>(), r->delta_keys.as<ull>(),
+                                                  r->delta_docs_in.as<uint32_t>(), r->delta_docs.as<uint32_t>(), int(m), 0, 48, st));
+    } else {
+        HIP_TRY(live::launch_live_sort(tail, m, n_old, r->delta_keys.as<ull>(), r->delta_docs.as<uint32_t>(), st));
+    }
+    const live::MergeArgs ma{r->dir_keys.as<ull>(), r->dir_docs.as<uint32_t>(), n_old, r->dir.as<ull>(), r->n_dir, r->stride, r->delta_keys.as<ull>(),
+                             r->delta_docs.as<uint32_t>(), m, r->dir_keys2.as<ull>(), r->dir_docs2.as<uint32_t>()};
+    HIP_TRY(live::launch_live_merge(ma, st));
+    payload_dir_kernel<<<(shape.n_dir + WG - 1) / WG, WG, 0, st>>>(r->dir_keys2.as<ull>(), shape.n_dir, shape.stride, r->dir2.as<ull>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r->sync_done.e, st));
+    // a batch submitted before the sync reads the old arrays to its end: every slot has finished before the spares become the directory
+    for (RerankSlot &s : r->slots)
+        if (s.stream.s) HIP_TRY(hipStreamSynchronize(s.stream.s));
+    HIP_TRY(elapsed_ms(r->sync_start, r->sync_done, &r->sync_ms));
+    for (auto pr : {std::make_pair(&r->dir_keys, &r->dir_keys2), std::make_pair(&r->dir_docs, &r->dir_docs2), std::make_pair(&r->dir, &r->dir2)}) {
+        std::swap(pr.first->p, pr.second->p);
+        std::swap(pr.first->bytes, pr.second->bytes);
+    }
+    r->dir_n = n_new;
+    r->dir_cap = cap;
+    r->n_dir = shape.n_dir;
+    r->stride = shape.stride;
+    // the old arrays, now the spares, may be smaller than their partners: made again in this sync, so that the next one that fits
+    // allocates nothing.  The sync has taken effect: an allocation that fails here leaves a spare empty, which the next sync makes
+    // again (and reports, if it fails again) -- this one returns VBM25_OK.
+    if (8 * cap > r->dir_keys2.bytes && (regrow(r->dir_keys2, 8 * cap) != hipSuccess || regrow(r->dir_docs2, 4 * cap) != hipSuccess))
+        for (HbmArray *a : {&r->dir_keys2, &r->dir_docs2}) {
+            ta.device_bytes -= a->p ? a->footprint() : 0;
+            a->release();
+        }
+    if (r->dir2.bytes < DIR_BYTES && regrow(r->dir2, DIR_BYTES) != hipSuccess) r->dir2.release();
+    (void)hipGetLastError();  // (a failed allocation above is not the next call's error)
+    return VBM25_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vbm25_reranker_sync(vbm25_reranker *r) {
+    return guarded([&] { return reranker_sync(r); });
+}
+
+uint32_t vbm25_reranker_directory_docs(const vbm25_reranker *r) { return r ? r->dir_n : 0; }
+
+// tools/live_rerank_cost.py: the device time of the last sync's kernels between its events (-1: no sync has enqueued anything).  Not in
+// the header.
+int vbm25_debug_reranker_sync_ms(const vbm25_reranker *r, double *ms) {
+    if (!r || !ms) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    *ms = r->sync_ms;
+    return VBM25_OK;
+}
 
 int vbm25_reranker_create(const vbm25_doc_terms *t, const vbm25_resolver *rs, const vbm25_documents *payloads, uint32_t depth, uint32_t max_queries,
                           uint32_t max_lexemes, uint64_t max_bytes, uint64_t max_candidates, uint32_t max_k, vbm25_reranker **out) {

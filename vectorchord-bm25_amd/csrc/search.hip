@@ -1309,7 +1309,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
-// tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create).
+// tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
 int vbm25_tuning_set(const char *name, long long value) {
     if (!name) return set_error(VBM25_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> guard(g_tune_mutex);
@@ -1358,6 +1358,9 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "tid_grid" || n == "tid_dir") {  // (the match kernel's grid cap and a TID set's directory size: tid.hip keeps and reads them)
         if (int rc = vbm25::tid_tuning_set(name, value)) return rc;
     }
+    else if (n == "live_sort_max") {  // (where vbm25_reranker_sync changes from the LDS sort of a delta to the radix sort: live.hip keeps and reads it)
+        if (int rc = vbm25::live_tuning_set(value)) return rc;
+    }
     else return set_error(VBM25_ERR_INVALID, "unknown tuning switch %s", name);
     ++g_tune.generation;
     return VBM25_OK;
@@ -1372,6 +1375,7 @@ void vbm25_tuning_reset(void) {
     vbm25::forward_tuning_reset();
     vbm25::rerank_tuning_reset();
     vbm25::tid_tuning_reset();
+    vbm25::live_tuning_reset();
 }
 
 // tuning / test aid (not declared in include/vbm25.h): work items of the last run and how many of them the

@@ -13,6 +13,9 @@
 //                decides alone.  Exact for every n_keys >= 0.
 //   tid_find     the same search over keys that may repeat, returning the first position of the key (reranker.hip's ctid -> document
 //                lookup; tests/native/fuzz_tid_find.cpp checks it against std::lower_bound)
+//   live_rank_old, live_rank_delta   where an old and a new entry go when a sorted delta is merged into the sorted keys (live.hip's
+//                merge kernel; tests/native/fuzz_live_merge.cpp checks them against std::merge), and live_sort_word / live_sort_step,
+//                the word and the network of the delta's sort in LDS
 //   match_word   a wave's ballot as the word it writes: XOR the invert mask, the bits of documents at or beyond n forced to zero
 //   new_bits     the documents a word adds to an older one (the OR mode's count)
 #ifndef VBM25_TID_LANE_H
@@ -99,6 +102,62 @@ TID_HD uint64_t tid_find(uint64_t key, const uint64_t *directory, uint32_t n_dir
         else b = mid;
     }
     return a < n_keys && keys[a] == key ? a : NOT_THERE;
+}
+
+// ---- the merge of a sorted delta into the sorted keys (live.hip: vbm25_reranker_sync; tests/native/fuzz_live_merge.cpp) ----
+// Old entries (key, doc) and delta entries (key, doc) are each sorted by key, equal keys by ascending doc, and every delta doc
+// exceeds every old doc.  The merged order by (key, doc) then puts old entry i at i + #{delta keys < key_i} and delta entry j at
+// j + #{old keys <= key_j}: a stable merge with the old entries first among equals, by ranks alone, one lane an entry.
+
+// #{delta keys < key}: a lower bound over the delta's sorted keys
+TID_HD uint64_t live_rank_old(uint64_t key, const uint64_t *delta_keys, uint64_t n_delta) {
+    uint64_t a = 0, b = n_delta;
+    while (a < b) {
+        const uint64_t mid = a + ((b - a) >> 1);
+        if (delta_keys[mid] < key) a = mid + 1;
+        else b = mid;
+    }
+    return a;
+}
+
+// #{old keys <= key}: an upper bound in tid_find's two stages.  Stage one counts the directory entries <= key; the last of them
+// opens the run in which the bound lies, and stage two finishes over (j stride, min((j + 1) stride, n_keys)] -- every key at or in
+// front of position j stride is <= key, the key at (j + 1) stride (directory entry j + 1, when it exists) is > key.  With stride 1
+// the directory is the keys and stage one decides alone.  Exact for every n_keys >= 0, repeated keys included.
+TID_HD uint64_t live_rank_delta(uint64_t key, const uint64_t *directory, uint32_t n_dir, const uint64_t *keys, uint64_t n_keys, uint32_t stride) {
+    uint32_t lo = 0, hi = n_dir;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (directory[mid] <= key) lo = mid + 1;
+        else hi = mid;
+    }
+    if (stride == 1 || lo == 0) return lo;
+    uint64_t a = dir_source(lo - 1, stride) + 1, b = dir_source(lo - 1, stride) + stride;
+    if (b > n_keys) b = n_keys;
+    while (a < b) {
+        const uint64_t mid = a + ((b - a) >> 1);
+        if (keys[mid] <= key) a = mid + 1;
+        else b = mid;
+    }
+    return a;
+}
+
+// A delta of at most 2^LIVE_SORT_LOG2 rows sorted in LDS: row j's word is its key above its 12-bit position, so distinct words order
+// the rows by (key, position) -- the stable order -- under any comparison sort.  The padding word exceeds every row's.
+constexpr uint32_t LIVE_SORT_LOG2 = 12;
+constexpr uint64_t LIVE_SORT_PAD = ~0ull;
+TID_HD uint64_t live_sort_word(uint64_t key, uint32_t j) { return key << LIVE_SORT_LOG2 | uint64_t(j); }
+TID_HD uint64_t live_sort_key(uint64_t word) { return word >> LIVE_SORT_LOG2; }
+TID_HD uint32_t live_sort_row(uint64_t word) { return uint32_t(word) & ((1u << LIVE_SORT_LOG2) - 1u); }
+// one compare-exchange of the bitonic network over `n` (a power of two) words: step (k, j) for pair index t in 0 .. n / 2
+TID_HD void live_sort_step(uint64_t *w, uint32_t t, uint32_t k, uint32_t j) {
+    const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), p = i | j;
+    const bool up = (i & k) == 0;
+    const uint64_t a = w[i], b = w[p];
+    if ((a > b) == up) {
+        w[i] = b;
+        w[p] = a;
+    }
 }
 
 // the word of documents first .. first + 63 of n from the wave's ballot (first < n, a multiple of 64)

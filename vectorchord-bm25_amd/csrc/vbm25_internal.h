@@ -124,6 +124,10 @@ void rerank_tuning_reset();
 // set's directory entries, 0 .. 12, read at each vbm25_tid_set_create); tid.hip keeps them
 int tid_tuning_set(const char *name, long long value);
 void tid_tuning_reset();
+// vbm25_tuning_set's live_sort_max (the most rows of a delta that vbm25_reranker_sync sorts in one workgroup's LDS, 0 .. 4096, 0 = always
+// the radix sort; read at each sync); live.hip keeps it
+int live_tuning_set(long long value);
+void live_tuning_reset();
 // tid_dir as it stands (the reranker's payload directory is built under it, as a TID set's is)
 uint32_t tid_dir_now();
 
