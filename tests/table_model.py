@@ -13,8 +13,11 @@ The rules:
     of postings (maintain.rs:344-362), a growing row keeps its length; everything is flushed again from scratch;
   * a delete by ctid (bulkdelete.rs) kills every row of both segments that carries one of the ctids;
   * the rerank step scores a candidate with the `<&>` operator (evaluate.rs: idf * tf per shared key, ascending, from 0.0; the
-    fieldnorm of the row's stored length), names a ctid's lowest row and knows nothing of deletion (Table.rerank).
-Table.ops_ctid draws the same life in lexemes and ctids for tests/test_gpu_table_ctid_fuzz.py."""
+    fieldnorm of the row's stored length), names a ctid's lowest row and knows nothing of deletion (Table.rerank);
+  * on the rerank stack that follows the table (one index-bound handle that every insert is appended to, side "live") the rows
+    are sealed + growing in that order, so a ctid of a sealed and a growing row names the sealed one, dead or not; the ctid
+    directory covers the rows of its last sync (Table.rerank_op syncs when a rerank finds rows pending).
+Table.ops_ctid draws the same life in lexemes and ctids for tests/test_gpu_table_ctid_fuzz.py and tests/test_gpu_table_live_fuzz.py."""
 import struct
 
 import numpy as np
@@ -31,6 +34,8 @@ INSERT_ROWS = (1, 4, 16)
 RANK_DTYPE = np.dtype({"names": ["score", "pos", "doc"], "formats": ["<f8", "<u4", "<u4"], "offsets": [0, 8, 12], "itemsize": 16})
 RERANK_KS = (1, 10, 64, 65, 1024)   # 1024: the scorer's maximum
 NO_ROW_LEXEME = b"~no row"          # (shorter than 16 bytes: its key is NO_ROW_KEY, vector.rs:21-24)
+HITS_K = 100                        # the records a search returns for the rerank of its hits (rerank_op's "hits")
+CAST_DOCS = 4                       # the rows of one cast handle of the ctid lives: an INSERT of n rows is ceil(n / 4) appends
 
 
 def new_key(i):
@@ -71,6 +76,9 @@ class Table:
         # what the ctid life counts (delete_tids with `what`, rerank_op); assert_coverage_ctid of tests/test_table_model.py reads it
         self.cstats = dict(bulk_full=0, delete_batches=0, reranks=0, rerank_both=0, ineligible_sealed=0, ineligible_growing=0,
                            rerank_short=0, rerank_cut=0)
+        # what the live side counts (live_append, rerank_op); assert_coverage_live reads it
+        self.cstats.update(live_both=0, live_shared=0, sync_multi=0, sync_one=0, ab_differ=0, unknown_handle=0, live_short=0, live_cut=0,
+                           live_hits=0)
         self._n_batches = 0
         self._seal([(tuple(p), dict(kt), int(ln)) for p, kt, ln in rows])
 
@@ -83,6 +91,9 @@ class Table:
         self.growing, self.growing_deleted = [], []
         self.growing_batch = []   # per growing row: the number of the insert (insert's `batch`) that appended it
         self._first = {}          # side -> (rows covered, {payload: lowest row index}), see first_rows
+        # the live side (rerank_op): the rows its ctid directory covers, the growing rows appended to its handle and in how many
+        # appends since the last sync, whether the epoch's search hits have been reranked
+        self._live_covered, self._live_appended, self._live_pending, self._live_hits_done = len(rows), 0, 0, False
         self.ginv = {}     # key -> [(g, tf)] of the growing rows, g ascending
         vocab = sorted({key for _, kt, _ in rows for key in kt})
         self.vocab, self.rank = vocab, {key: t for t, key in enumerate(vocab)}
@@ -299,7 +310,39 @@ class Table:
         self._first[side] = (len(rows), first)
         return first
 
-    def rerank(self, query_keys, cand_tids, k, side):
+    def live_row(self, i):
+        """row i of sealed + growing, the documents of an index-bound handle that every insert was appended to"""
+        n_sealed = len(self.sealed)
+        return self.sealed[i] if i < n_sealed else self.growing[i - n_sealed]
+
+    def live_index(self, tid, covered=None):
+        """the lowest index of sealed + growing (its first `covered` rows; default: all) that carries the ctid, or None.  A sealed
+        row beats a growing one, dead or not: every growing index exceeds every sealed one (live_merge_kernel's stable merge on
+        (key, doc))."""
+        tid = tuple(int(x) for x in tid)
+        i = self.first_rows("sealed").get(tid)
+        if i is None:
+            g = self.first_rows("growing").get(tid)
+            i = None if g is None else len(self.sealed) + g
+        return i if i is None or covered is None or i < covered else None
+
+    def _row_score(self, row, qkeys):
+        _, kt, ln = row
+        fn, s = orc.lib().orc_length_to_fieldnorm(ln), 0.0
+        for key in qkeys:
+            if key in kt:
+                s += self._operator(self.rank[key], fn, kt[key])
+        return s
+
+    @staticmethod
+    def _top(entries, k):
+        best = sorted(entries, key=lambda e: -e[0])[:k]   # (sorted is stable: equal scores stay in list order)
+        ranks = np.zeros(k, RANK_DTYPE)
+        for r, e in enumerate(best):
+            ranks[r] = e
+        return ranks, len(best), len(entries)
+
+    def rerank(self, query_keys, cand_tids, k, side, covered=None):
         """the rerank step (`<&>` over a candidate list, top k) on the rows of one side, "sealed" or "growing" -> (ranks [k] of
         RANK_DTYPE, n_ranks, eligible candidates).  A ctid names the lowest row index of the side that carries it; one no row of the
         side carries is not eligible, and the others keep their positions in the list.  DELETION IS NOT CONSULTED: the reranker
@@ -307,31 +350,104 @@ class Table:
         sum of _operator(rank, its fieldnorm, tf) from 0.0 in ascending key order over the distinct query keys that the sealed
         vocabulary and the row hold; growing rows take the sealed statistics and their own length (what binding cast documents to
         the index's vocabulary keeps).  The result is the stable descending sort of the eligible entries cut at k: (score, pos in
-        the list, row index), zeros behind them."""
-        assert side in ("sealed", "growing")
-        L = orc.lib()
-        rows, first = (self.sealed if side == "sealed" else self.growing), self.first_rows(side)
+        the list, row index), zeros behind them.
+        side "live": the rows are sealed + growing in that order, indexed 0 .. n_sealed + n_growing - 1 (live_index); `covered`
+        (default: all) is the number of them that the ctid directory knows.  So a dead sealed row's ctid, inserted again before the
+        VACUUM, still names the sealed row: DESIGN section 6, "Not in: deleting documents from a bound handle"."""
+        assert side in ("sealed", "growing", "live") and (covered is None or side == "live")
         qkeys = [key for key in sorted(set(query_keys)) if key in self.rank]
         entries = []
+        if side == "live":
+            for pos, tid in enumerate(cand_tids):
+                i = self.live_index(tid, covered)
+                if i is not None:
+                    entries.append((self._row_score(self.live_row(i), qkeys), pos, i))
+            return self._top(entries, k)
+        rows, first = (self.sealed if side == "sealed" else self.growing), self.first_rows(side)
         for pos, tid in enumerate(cand_tids):
             i = first.get(tuple(int(x) for x in tid))
-            if i is None:
-                continue
-            _, kt, ln = rows[i]
-            fn, s = L.orc_length_to_fieldnorm(ln), 0.0
-            for key in qkeys:
-                if key in kt:
-                    s += self._operator(self.rank[key], fn, kt[key])
-            entries.append((s, pos, i))
-        best = sorted(entries, key=lambda e: -e[0])[:k]   # (sorted is stable: equal scores stay in list order)
-        ranks = np.zeros(k, RANK_DTYPE)
-        for r, e in enumerate(best):
-            ranks[r] = e
-        return ranks, len(best), len(entries)
+            if i is not None:
+                entries.append((self._row_score(rows[i], qkeys), pos, i))
+        return self._top(entries, k)
+
+    def rerank_docs(self, query_keys, doc_indices, k):
+        """rerank's "live" side for a list of indices into sealed + growing (the cand_doc route): pos is the position in the list,
+        and every index is eligible"""
+        qkeys = [key for key in sorted(set(query_keys)) if key in self.rank]
+        return self._top([(self._row_score(self.live_row(int(i)), qkeys), pos, int(i)) for pos, i in enumerate(doc_indices)], k)
+
+    def forward_live(self, drop_deleted=False):
+        """sealed + growing as a forward index: forward()'s four arrays, continued by the growing rows -- each the ranks of those of
+        its keys that the sealed vocabulary holds, ascending, with their tf, and the fieldnorm code of its own stored length (keys
+        outside the vocabulary counted).  drop_deleted: a growing row flagged deleted has an empty run and keeps its code, what
+        vbm25_doc_terms_append documents for a CSR with `deleted` flags."""
+        L = orc.lib()
+        start, term, tf, fn = (list(a) for a in self.forward())
+        for g, (_, kt, ln) in enumerate(self.growing):
+            if not (drop_deleted and self.growing_deleted[g]):
+                known = sorted((self.rank[key], kt[key]) for key in kt if key in self.rank)
+                term += [t for t, _ in known]
+                tf += [c for _, c in known]
+            start.append(len(term))
+            fn.append(L.orc_length_to_fieldnorm(ln))
+        return np.array(start, np.uint64), np.array(term, np.uint32), np.array(tf, np.uint32), np.array(fn, np.uint8)
+
+    def live_append(self, n_rows):
+        """the driver appended one cast handle of the next n_rows growing rows to the live handle (rows the model already holds)"""
+        lo = self._live_appended
+        assert 0 < n_rows <= len(self.growing) - lo
+        self._live_appended, self._live_pending = lo + n_rows, self._live_pending + 1
+        self.cstats["unknown_handle"] += not any(key in self.rank for _, kt, _ in self.growing[lo:lo + n_rows] for key in kt)
+
+    def growing_hits(self, queries, k):
+        """per query the live indices of the first k records a search returns (deleted growing rows are skipped, a deleted sealed row is
+        shown): a hit 0xFFFFFFFF - g is document n_sealed + g"""
+        n_sealed = len(self.sealed)
+        hits = [self.select(keys, k, None, count=False)["doc_id"].astype(np.int64) for keys in queries]
+        return [np.where(h >= n_sealed, n_sealed + (NONE - h), h).astype(np.uint32) for h in hits]
 
     def rerank_op(self, queries, lists, k, count=True):
-        """rerank of every (query keys, ctid list) pair on both sides -> {side: (ranks [nq, k], n_ranks uint32 [nq])}"""
+        """rerank of every (query keys, ctid list) pair on both sides -> {side: (ranks [nq, k], n_ranks uint32 [nq])}, and on the
+        live side as a ring on ONE index-bound handle answers it, which is synced only here, when a rerank needs it:
+          "live"           the result over all rows (after the sync)
+          "live_before"    the result over the rows the directory covered before this rerank, "live_covered" of them; None where
+                           nothing was pending (or the table has no sealed row: no ring exists)
+          "live_docs"      per query the live indices of the eligible candidates, in list order; "live_by_doc": rerank_docs of them
+          "hits"           once per epoch, at the first rerank that finds a deleted growing row: growing_hits(queries, HITS_K), with
+                           "hits_by_doc" rerank_docs of them; else None"""
         out, seen = {}, {}
+        stack = lambda got: (np.stack([g[0] for g in got]) if got else np.zeros((0, k), RANK_DTYPE), np.array([g[1] for g in got], np.uint32))
+        n_sealed, n_rows = len(self.sealed), len(self.sealed) + len(self.growing)
+        if self._live_appended < len(self.growing):   # (a driver without a live handle reports no appends: one delta)
+            self._live_appended, self._live_pending = len(self.growing), self._live_pending + 1
+        covered, pending = self._live_covered, self._live_pending
+        out["live_before"], out["live_covered"] = None, covered
+        if n_sealed and covered != n_rows:
+            out["live_before"] = stack([self.rerank(keys, tids, k, "live", covered) for keys, tids in zip(queries, lists)])
+            self._live_covered, self._live_pending = n_rows, 0
+        got_live = [self.rerank(keys, tids, k, "live") for keys, tids in zip(queries, lists)]
+        out["live"] = stack(got_live)
+        out["live_docs"] = [np.array([i for i in (self.live_index(t) for t in tids) if i is not None], np.uint32) for tids in lists]
+        out["live_by_doc"] = stack([self.rerank_docs(keys, docs, k) for keys, docs in zip(queries, out["live_docs"])])
+        out["hits"] = None
+        if n_sealed and not self._live_hits_done and any(self.growing_deleted):
+            self._live_hits_done = True
+            out["hits"] = self.growing_hits(queries, HITS_K)
+            out["hits_by_doc"] = stack([self.rerank_docs(keys, docs, k) for keys, docs in zip(queries, out["hits"])])
+        if count and n_sealed:
+            c, (ranks, n_ranks) = self.cstats, out["live"]
+            scored = [ranks["doc"][q, :n][ranks["score"][q, :n] != 0] for q, n in enumerate(n_ranks)]
+            c["live_both"] += any((d < n_sealed).any() and (d >= n_sealed).any() for d in scored)
+            first_s, first_g = self.first_rows("sealed"), self.first_rows("growing")
+            c["live_shared"] += any(tuple(int(x) for x in t) in first_s and tuple(int(x) for x in t) in first_g for tids in lists for t in tids)
+            c["live_short"] += any(g[1] < k for g in got_live)
+            c["live_cut"] += any(g[1] == k < g[2] for g in got_live)
+            if out["live_before"] is not None:
+                c["sync_multi"] += pending >= 2
+                c["sync_one"] += n_rows - covered == 1
+                c["ab_differ"] += out["live_before"][0].tobytes() != ranks.tobytes()
+            if out["hits"] is not None:
+                c["live_hits"] += any((h >= n_sealed).any() for h in out["hits"])
         for side in ("sealed", "growing"):
             got = [self.rerank(keys, tids, k, side) for keys, tids in zip(queries, lists)]
             ranks = np.stack([g[0] for g in got]) if got else np.zeros((0, k), RANK_DTYPE)

@@ -117,6 +117,11 @@ class CtidLife(Life):
 
     # ---- INSERT: through the caster
 
+    def keep(self, cast):
+        """one collected cast handle goes to everything that holds the epoch's inserts"""
+        self.grow.append_documents(cast)
+        self.epoch_docs.extend(cast)
+
     def insert_rows(self, docs, host_bits=False):
         """docs: [(payload, [(lexeme, count)])], one INSERT statement"""
         m, batch, pending = self.m, self.m.new_batch(), 0
@@ -124,9 +129,7 @@ class CtidLife(Life):
             m.insert(payload, m.cast(lexrow), batch)
 
         def take():
-            cast = self.caster.collect()
-            self.grow.append_documents(cast)   # (before the slot is taken again)
-            self.epoch_docs.extend(cast)
+            self.keep(self.caster.collect())   # (before the slot is taken again)
 
         for lo in range(0, len(docs), self.cast_docs):
             if pending == 2:
