@@ -1113,6 +1113,51 @@ uint32_t vbm25_doc_terms_base_docs(const vbm25_doc_terms *);
 int vbm25_reranker_sync(vbm25_reranker *);
 uint32_t vbm25_reranker_directory_docs(const vbm25_reranker *);
 
+/* Deletes on a bound handle (csrc/live.hip): the rows a DELETE or a bulkdelete killed leave the rerank, as they leave the search
+ * (vbm25_device_growing_delete_tids, vbm25_filter_set_tids, vbm25_device_vacuum_bulkdelete).  The handle gets a deletion bitmap: one
+ * bit a document, packed as the filters and the deletion words are -- uint64_t words, document d at bit d & 63 of word d >> 6, set =
+ * dead.  The bitmap is allocated by the first delete that names a document and never before: a handle nobody deleted from holds
+ * none, reports the vbm25_doc_terms_device_bytes it always did, and runs every kernel as before.  Bits at and beyond n_docs are zero.
+ *   vbm25_doc_terms_delete   `docs`: n document indices of the handle (on an index-bound handle sealed document d is index d, growing
+ *             document g is vbm25_doc_terms_base_docs + g).  Repeats and documents already dead are allowed; *n_new (may be NULL) is
+ *             the number of documents that were live before the call and are dead after it.  The indices are uploaded once; one
+ *             lane handles one index with an atomicOr on its word, and the new bits are counted from the word the atomic returns, so
+ *             a repeat within one call counts once.  VBM25_ERR_INVALID, checked on the host before anything is enqueued: NULL
+ *             arguments, an index at or beyond n_docs (the message names the entry).
+ *   vbm25_doc_terms_delete_tids   every document whose ctid is in the set dies.  The ctids of documents 0 .. base_docs are the index's
+ *             doc_payload plane on an index-bound handle (`payloads` must be NULL), else those of `payloads` -- the handle
+ *             vbm25_reranker_create takes, under its checks: with payloads, base_docs documents, on the handle's device; a
+ *             documents-bound handle with base_docs > 0 needs it.  The ctids of the appended documents are the handle's tail; a
+ *             handle whose appended documents carry no payloads is refused, as is a set on another device.  One kernel: wave w
+ *             answers word w of the bitmap, each lane reading its document's ctid from the base plane or the tail (the split falls
+ *             inside a word whenever base_docs % 64 != 0), the set's directory in LDS, one ballot a word; lane 0 ORs the word in
+ *             and counts the new bits.  Grid-stride under the tid_grid cap.  Documents that share a ctid die together.
+ *   Both deletes keep the append's contract.  They are synchronous.  Every check and every allocation comes first; then the call
+ *             waits for the DEVICE, and only then writes -- so a scorer call or a reranker batch enqueued before the delete ends on
+ *             the old bits, and one made after it sees the new bits with no further call.  A refused or failed delete leaves the
+ *             words and the count as they were.  A delete of nothing (n == 0, an empty set, a set that matches nothing on a handle
+ *             without a bitmap) returns VBM25_OK and leaves the handle without a bitmap.  The caller does not delete while another
+ *             thread is inside a call on the handle.  There is no undelete, and ctids of the set that match no document are not
+ *             counted.
+ *   vbm25_doc_terms_dead_docs   the dead documents now (0 for NULL).
+ *   vbm25_doc_terms_read_dead   ceil(n_docs / 64) words to the host, all zero on a handle without a bitmap.
+ *   What a dead document changes: in vbm25_scorer_topk and in a reranker batch -- cand_doc lists, the cross product and ctid lists
+ *             alike -- a candidate whose document is dead is not eligible, exactly as an entry that names no document is not: its
+ *             pos still counts and it takes no rank, n_ranks[q] = min(k, the live eligible entries of q).  A ctid of several
+ *             documents resolves to the lowest LIVE one (the lookup walks forward over the ctid's entries, which lie by ascending
+ *             document), or to none when all are dead: once a reused ctid's new row is appended and synced, the ctid names that
+ *             row.  Reranker `allocations` never moves on a delete.
+ *   What it does not change: vbm25_evaluate_documents, vbm25_scorer_evaluate and vbm25_doc_terms_download -- `<&>` is a function of
+ *             the pair -- and vbm25_reranker_sync, vbm25_reranker_create*: the ctid directory keeps the dead documents' entries
+ *             (nothing compacts them out) until the VACUUM drops the handle.  vbm25_doc_terms_append still gives a document flagged
+ *             `deleted` an empty run and leaves it live; a caller that restarts from a growing CSR calls vbm25_doc_terms_delete on
+ *             those documents afterwards.  An append carries the bitmap along: its capacity follows the fieldnorm array's, the old
+ *             words are copied, the appended documents are live, a refused append leaves it untouched. */
+int vbm25_doc_terms_delete(vbm25_doc_terms *, const uint32_t *docs, uint64_t n, uint32_t *n_new);
+int vbm25_doc_terms_delete_tids(vbm25_doc_terms *, const vbm25_tid_set *, const vbm25_documents *payloads, uint32_t *n_new);
+uint32_t vbm25_doc_terms_dead_docs(const vbm25_doc_terms *);
+int vbm25_doc_terms_read_dead(const vbm25_doc_terms *, uint64_t *words);
+
 #ifdef __cplusplus
 }
 #endif

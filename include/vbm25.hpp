@@ -297,8 +297,10 @@ class Caster {
 // elements with their tfs, and its fieldnorm code, in HBM.  evaluate() is bm25::evaluate (evaluate.rs:22-74) for a batch of queries,
 // each against its own candidate documents; the SQL operator `<&>` returns the negation of these values.  The index must outlive it.
 // append() writes the bind of a delta behind the handle's documents (a live table's new rows; on a handle from Index::bind document
-// base_docs() + g is growing document g); nobody else is inside a call on the handle meanwhile.
+// base_docs() + g is growing document g); erase() marks documents dead, by index or by ctid, so that the rerank leaves them out;
+// nobody else is inside a call on the handle meanwhile.
 class Scorer;
+class TidSet;
 class DocTerms {
   public:
     DocTerms(const Documents &documents, const Resolver &resolver) { check(vbm25_documents_bind(documents.handle(), resolver.handle(), &h_)); }
@@ -325,6 +327,24 @@ class DocTerms {
     void append(const Documents &delta, const Resolver &resolver) { check(vbm25_doc_terms_append_documents(h_, delta.handle(), resolver.handle())); }
     // the same from a host CSR; a document flagged deleted gets an empty run (vbm25_doc_terms_append)
     inline void append(const GrowingDocs &delta, const Resolver &resolver);
+    // the documents docs[0 .. n) are dead (vbm25_doc_terms_delete): Scorer::topk and a Reranker leave them out, and a ctid names the
+    // lowest live document that carries it; evaluate() and download() are unchanged.  Returns the documents that were live before.
+    uint32_t erase(const uint32_t *docs, uint64_t n) {
+        uint32_t n_new = 0;
+        check(vbm25_doc_terms_delete(h_, docs, n, &n_new));
+        return n_new;
+    }
+    // every document whose ctid is in the set is dead (vbm25_doc_terms_delete_tids).  payloads: the Documents whose payloads name the
+    // documents the handle was bound with; none on a handle from Index::bind, whose ctids are the index's own.
+    inline uint32_t erase(const TidSet &tids, const Documents *payloads = nullptr);
+    uint32_t dead_docs() const { return vbm25_doc_terms_dead_docs(h_); }
+    // the deletion bitmap, ceil(docs() / 64) words: document d at bit d & 63 of word d >> 6 (vbm25_doc_terms_read_dead)
+    std::vector<uint64_t> read_dead() const {
+        std::vector<uint64_t> w((size_t(docs()) + 63) / 64 + 1);
+        check(vbm25_doc_terms_read_dead(h_, w.data()));
+        w.pop_back();
+        return w;
+    }
     void download(std::vector<uint64_t> &start, std::vector<uint32_t> &term, std::vector<uint32_t> &tf) const {
         start.assign(size_t(docs()) + 1, 0);
         term.assign(known() + 1, 0);
@@ -571,6 +591,11 @@ class TidSet {
   private:
     vbm25_tid_set *h_ = nullptr;
 };
+inline uint32_t DocTerms::erase(const TidSet &tids, const Documents *payloads) {
+    uint32_t n_new = 0;
+    check(vbm25_doc_terms_delete_tids(h_, tids.handle(), payloads ? payloads->handle() : nullptr, &n_new));
+    return n_new;
+}
 
 // F document bitmaps of one index in HBM (vbm25_filter): bit d % 64 of word d / 64 of bitmap i set = document d may be returned.
 // Optionally F growing bitmaps for one uploaded growing segment (set_growing): bit g = growing document g may be returned.

@@ -212,6 +212,10 @@ ABI = {
     "vbm25_doc_terms_base_docs": (u32, [vp]),
     "vbm25_reranker_sync": (i32, [vp]),
     "vbm25_reranker_directory_docs": (u32, [vp]),
+    "vbm25_doc_terms_delete": (i32, [vp, vp, u64, vp]),
+    "vbm25_doc_terms_delete_tids": (i32, [vp, vp, vp, vp]),
+    "vbm25_doc_terms_dead_docs": (u32, [vp]),
+    "vbm25_doc_terms_read_dead": (i32, [vp, vp]),
 }
 
 

@@ -1522,6 +1522,37 @@ class DocTerms:
             self._refresh()
         return self
 
+    def delete(self, docs):
+        """vbm25_doc_terms_delete: the documents `docs` (indices into this handle; on a handle from GpuIndex.bind sealed document d
+        is d, growing document g is base_docs + g; repeats and dead ones allowed) are dead: Scorer.topk and a Reranker leave them
+        out, and a ctid names the lowest live document that carries it.  evaluate() and download() are unchanged.  Synchronous, with
+        the append's contract.  -> the documents that were live before the call."""
+        docs = np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+        n_new = C.c_uint32()
+        check(lib().vbm25_doc_terms_delete(self.h, _p(docs) if len(docs) else None, len(docs), C.byref(n_new)))
+        return n_new.value
+
+    def delete_tids(self, tid_set, documents=None):
+        """vbm25_doc_terms_delete_tids: every document whose ctid is in the TidSet is dead.  `documents`: the Documents whose payloads
+        name the documents the handle was bound with (what Reranker takes); None on a handle from GpuIndex.bind, whose ctids are the
+        index's own.  -> the documents that were live before the call."""
+        n_new = C.c_uint32()
+        check(lib().vbm25_doc_terms_delete_tids(self.h, tid_set.h, None if documents is None else documents.h, C.byref(n_new)))
+        return n_new.value
+
+    @property
+    def dead_docs(self):
+        """vbm25_doc_terms_dead_docs: the dead documents now"""
+        return int(lib().vbm25_doc_terms_dead_docs(self.h))
+
+    def read_dead(self):
+        """vbm25_doc_terms_read_dead: the deletion bitmap, uint64 [ceil(n_docs / 64)] -- document d at bit d & 63 of word d >> 6; all
+        zero on a handle nobody deleted from"""
+        n_words = (self.n_docs + 63) // 64
+        words = np.zeros(max(1, n_words), dtype=np.uint64)
+        check(lib().vbm25_doc_terms_read_dead(self.h, words.ctypes.data))
+        return words[:n_words]
+
     def device_bytes(self):
         return int(lib().vbm25_doc_terms_device_bytes(self.h))
 

@@ -374,7 +374,8 @@ int vbm25_doc_terms_download(const vbm25_doc_terms *t, uint64_t *start, uint32_t
 uint64_t vbm25_doc_terms_device_bytes(const vbm25_doc_terms *t) {
     uint64_t n = 0;
     if (t)
-        for (const HbmArray *a : {&t->d_start, &t->d_term, &t->d_tf, &t->d_fieldnorm, &t->d_tail_payload}) n += a->bytes;  // (the room to spare included)
+        for (const HbmArray *a : {&t->d_start, &t->d_term, &t->d_tf, &t->d_fieldnorm, &t->d_tail_payload, &t->d_dead})
+            n += a->bytes;  // (the room to spare included; the deletion bitmap from the first delete that names a document)
     return n;
 }
 

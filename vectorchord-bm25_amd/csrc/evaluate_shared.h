@@ -28,6 +28,11 @@ struct vbm25_doc_terms {
     // first append has been made, and tail_payload says whether it -- and so every later one -- carried payloads.
     bool tail_decided = false, tail_payload = false;
     vbm25::HbmArray d_tail_payload;
+    // the deletion bitmap (vbm25_doc_terms_delete*, live.hip): one bit a document, document d at bit d & 63 of word d >> 6, set = dead.
+    // NULL until the first delete that names a document; then words for the fieldnorm array's capacity, the bits at and beyond n_docs
+    // zero.  Read by rerank_part_kernel and cand_lookup_kernel only.
+    vbm25::HbmArray d_dead;
+    uint32_t n_dead = 0;
 };
 
 namespace vbm25 {

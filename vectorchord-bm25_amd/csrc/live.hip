@@ -18,6 +18,14 @@
 //                          bitonic network over them
 //     live_merge_kernel    one lane an entry of the old directory or of the delta: its place in the merged arrays by rank.  The old
 //                          directory's evenly spaced keys staged in LDS once per workgroup, as cand_lookup_kernel stages them.
+//
+//   the deletes (vbm25_doc_terms_delete, vbm25_doc_terms_delete_tids): a bitmap of one bit a document on the handle, made by the first
+//   delete that names a document; rerank_part_kernel and cand_lookup_kernel leave a dead document out.  Checks and allocations, the
+//   wait for the device, then one kernel on the null stream and the count read back -- the append's contract.
+//     live_dead_docs_kernel   one lane a document index: atomicOr of its bit, the new bits counted from the word the atomic returns
+//     live_dead_tids_kernel   tid_match_kernel's OR_COUNT mode over a grown handle: wave w answers word w, each lane's ctid from the
+//                             base plane or the handle's tail, tid_contains with the set's directory in LDS, one ballot a word
+//   An append carries the bitmap along (append_core's parts): capacity for the fieldnorm array's, new words zero.
 //   No kernel here has scratch memory.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -94,6 +102,167 @@ __global__ void __launch_bounds__(WG) live_merge_kernel(live::MergeArgs a) {
     }
 }
 
+// ---- the deletion bitmap ----
+constexpr uint32_t WAVES = WG / 64;
+// the bitmap's words for n documents, in bytes
+uint64_t dead_bytes(uint64_t n) { return 8 * ((n + 63) / 64); }
+
+// docs: n document indices below the handle's n_docs, repeats allowed.  One lane an index: the bit ORed into its word, and the word
+// the atomic returns says whether this lane was the one that set it -- a repeat within the call counts once.
+__global__ void __launch_bounds__(WG) live_dead_docs_kernel(const uint32_t *docs, ull n, ull *words, uint32_t *count) {
+    uint32_t counted = 0;
+    for (ull i = ull(blockIdx.x) * WG + threadIdx.x; i < n; i += ull(gridDim.x) * WG) {
+        const uint32_t d = docs[i];
+        const ull bit = 1ull << (d & 63u);
+        if (!(atomicOr(&words[d >> 6], bit) & bit)) ++counted;
+    }
+    if (counted) atomicAdd(count, counted);
+}
+
+struct DeadTidArgs {
+    const uint16_t *base, *tail;  // the ctids of documents 0 .. base_docs, and of base_docs .. n
+    uint32_t base_docs, n;
+    const ull *dir, *keys;  // the set
+    uint64_t n_keys;
+    uint32_t n_dir, stride;
+    ull *words;  // ceil(n / 64): the handle's bitmap
+    uint32_t *count;
+};
+
+// tid_match_kernel (tid.hip) over a grown handle, in its OR_COUNT mode: wave w answers word w, each lane with its document's ctid
+// from the base plane or the tail (the split falls inside a word whenever base_docs % 64 != 0), one ballot a word, and lane 0 ORs
+// the word in and counts the bits that were not set.  No word has two writers: the waves take distinct words.
+__global__ void __launch_bounds__(WG) live_dead_tids_kernel(DeadTidArgs a) {
+    extern __shared__ ull s_set_dir[];
+    for (uint32_t i = threadIdx.x; i < a.n_dir; i += WG) s_set_dir[i] = a.dir[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, n_words = uint32_t((uint64_t(a.n) + 63u) >> 6);
+    uint32_t counted = 0;
+    for (uint64_t w = uint64_t(blockIdx.x) * WAVES + (threadIdx.x >> 6); w < n_words; w += uint64_t(gridDim.x) * WAVES) {
+        const uint64_t d = (w << 6) + lane;
+        bool hit = false;
+        if (d < a.n) {
+            const uint16_t *p = split_payload(a.base, a.tail, a.base_docs, d);
+            const uint16_t p3[3] = {p[0], p[1], p[2]};
+            hit = tid_contains(tid_key(p3), (const uint64_t *)s_set_dir, a.n_dir, (const uint64_t *)a.keys, a.n_keys, a.stride);
+        }
+        const uint64_t word = match_word(__ballot(hit), w << 6, a.n, 0);
+        if (lane == 0) {
+            const uint64_t old = a.words[w];
+            counted += new_bits(old, word);
+            if (word & ~old) a.words[w] = old | word;
+        }
+    }
+    if (lane == 0 && counted) atomicAdd(a.count, counted);
+}
+
+// What both deletes share.  `bitmap`: the handle's, or -- a handle nobody deleted from -- one made for this call, all zero, words for
+// the fieldnorm array's capacity; it becomes the handle's only when the call set a bit.
+struct DeadTarget {
+    HbmArray fresh, count;
+    ull *words = nullptr;
+};
+int dead_prepare(const vbm25_doc_terms *t, DeadTarget *dt) {
+    HIP_TRY(dt->count.alloc(4));
+    if (t->d_dead.p) {
+        dt->words = t->d_dead.as<ull>();
+        return VBM25_OK;
+    }
+    HIP_TRY(dt->fresh.alloc(dead_bytes(std::max<uint64_t>(t->d_fieldnorm.bytes, t->n_docs))));
+    dt->words = dt->fresh.as<ull>();
+    return VBM25_OK;
+}
+// behind the kernel: the count read back, the new bitmap kept if it holds a bit
+int dead_finish(vbm25_doc_terms *t, DeadTarget *dt, uint32_t *n_new) {
+    uint32_t fresh = 0;
+    HIP_TRY(hipMemcpy(&fresh, dt->count.p, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
+    if (dt->fresh.p && fresh) {
+        std::swap(t->d_dead.p, dt->fresh.p);
+        std::swap(t->d_dead.bytes, dt->fresh.bytes);
+    }
+    t->n_dead += fresh;
+    if (n_new) *n_new = fresh;
+    return VBM25_OK;
+}
+
+int delete_docs(vbm25_doc_terms *t, const uint32_t *docs, uint64_t n, uint32_t *n_new) {
+    if (!t || (n && !docs)) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (n_new) *n_new = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        if (docs[i] >= t->n_docs)
+            return set_error(VBM25_ERR_INVALID, "docs[%llu] is %u: outside the handle's %u documents", (ull)i, docs[i], t->n_docs);
+    if (!n) return VBM25_OK;
+    if (int rc = use_eval_device(t->device)) return rc;
+    // every allocation and the upload first; then the wait for the device, and only then the words change
+    DeadTarget dt;
+    HbmArray d_docs;
+    HIP_TRY(d_docs.alloc(4 * n));
+    if (int rc = dead_prepare(t, &dt)) return rc;
+    HIP_TRY(hipMemcpy(d_docs.p, docs, 4 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    if (dt.fresh.p) HIP_TRY(hipMemsetAsync(dt.fresh.p, 0, dt.fresh.bytes));
+    HIP_TRY(hipMemsetAsync(dt.count.p, 0, 4));
+    live_dead_docs_kernel<<<grid_for(n, WG, std::min(MAX_GRID, std::max(1u, eval_grid_cap()))), WG>>>(d_docs.as<uint32_t>(), n, dt.words,
+                                                                                                     dt.count.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    return dead_finish(t, &dt, n_new);
+}
+
+int delete_tids(vbm25_doc_terms *t, const vbm25_tid_set *s, const vbm25_documents *payloads, uint32_t *n_new) {
+    if (!t || !s) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    if (n_new) *n_new = 0;
+    TidSetView v;
+    tid_set_view(s, &v);
+    if (v.device != t->device) return set_error(VBM25_ERR_INVALID, "the TID set is on device %d, the bound documents on device %d", v.device, t->device);
+    const uint32_t n_tail = t->n_docs - t->base_docs;
+    const uint16_t *base = nullptr;
+    if (t->from_index) {
+        if (payloads) return set_error(VBM25_ERR_INVALID, "payloads are given and the handle is bound to an index: its ctids are the index's own");
+        uint32_t n = 0;
+        if (int rc = index_payloads(t->index, &base, &n)) return rc;
+        if (n != t->base_docs) return set_error(VBM25_ERR_INVALID, "the index has %u documents, the handle was bound with %u", n, t->base_docs);
+    } else if (payloads) {  // vbm25_reranker_create's checks of the same handle
+        if (!payloads->has_payload) return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup carry no payloads");
+        if (payloads->n_docs != t->base_docs)
+            return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup are %u, the bound documents %u", payloads->n_docs, t->base_docs);
+        if (payloads->device != t->device)
+            return set_error(VBM25_ERR_INVALID, "the documents given for the ctid lookup are on device %d, the bound documents on device %d",
+                             payloads->device, t->device);
+        base = payloads->d_payload.as<uint16_t>();
+    } else if (t->base_docs) {
+        return set_error(VBM25_ERR_INVALID, "payloads is NULL: the %u documents the handle was bound with have their ctids in the vbm25_documents", t->base_docs);
+    }
+    if (n_tail && !t->tail_payload)
+        return set_error(VBM25_ERR_INVALID, "the %u documents appended to the bound documents carry no payloads: no ctid names them", n_tail);
+    if (!t->n_docs || !v.n_keys) return VBM25_OK;
+    if (int rc = use_eval_device(t->device)) return rc;
+    DeadTarget dt;
+    if (int rc = dead_prepare(t, &dt)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (dt.fresh.p) HIP_TRY(hipMemsetAsync(dt.fresh.p, 0, dt.fresh.bytes));
+    HIP_TRY(hipMemsetAsync(dt.count.p, 0, 4));
+    const DeadTidArgs a{base, t->d_tail_payload.as<uint16_t>(), t->base_docs, t->n_docs, v.dir, v.keys, v.n_keys, v.n_dir, v.stride, dt.words,
+                        dt.count.as<uint32_t>()};
+    const uint32_t n_words = uint32_t((uint64_t(t->n_docs) + 63u) / 64u);
+    live_dead_tids_kernel<<<grid_for(n_words, WAVES, tid_grid_now()), WG, 8ull * std::max(1u, v.n_dir)>>>(a);
+    HIP_TRY(hipGetLastError());
+    return dead_finish(t, &dt, n_new);
+}
+
+int read_dead(const vbm25_doc_terms *t, uint64_t *words) {
+    if (!t || (t->n_docs && !words)) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    const uint64_t bytes = dead_bytes(t->n_docs);
+    if (!bytes) return VBM25_OK;
+    if (!t->d_dead.p) {
+        std::memset(words, 0, bytes);
+        return VBM25_OK;
+    }
+    if (int rc = use_eval_device(t->device)) return rc;
+    HIP_TRY(hipMemcpy(words, t->d_dead.p, bytes, hipMemcpyDeviceToHost));
+    return VBM25_OK;
+}
+
 // a delta's arrays in HBM on the handle's device (a cast's, or the staged CSR's); payload NULL: none
 struct Delta {
     uint32_t n_docs;
@@ -134,7 +303,7 @@ int append_core(vbm25_doc_terms *t, const Delta &d, const ResolverVocabulary &v)
     g_append_ms = -1.0;
     if (!n) return VBM25_OK;
     if (int rc = use_eval_device(t->device)) return rc;
-    HbmArray ids, counts, sums, cub, grown[5];
+    HbmArray ids, counts, sums, cub, grown[6];
     Event ev_start, ev_mid, ev_resume, ev_done;
     Stream st;  // (of the call's own, as the bind's)
     HIP_TRY(st.create());
@@ -166,18 +335,27 @@ int append_core(vbm25_doc_terms *t, const Delta &d, const ResolverVocabulary &v)
     struct Part {
         HbmArray *a;
         uint64_t used, need;
-    } parts[5] = {{&t->d_start, 8ull * (n0 + 1ull), 8 * (nd + 1)},
+    } parts[6] = {{&t->d_start, 8ull * (n0 + 1ull), 8 * (nd + 1)},
                   {&t->d_term, 4 * t->n_known, 4 * nk},
                   {&t->d_tf, 4 * t->n_known, 4 * nk},
                   {&t->d_fieldnorm, n0, nd},
-                  {&t->d_tail_payload, 6ull * (n0 - t->base_docs), 6 * n_tail}};
+                  {&t->d_tail_payload, 6ull * (n0 - t->base_docs), 6 * n_tail},
+                  {&t->d_dead, dead_bytes(n0), 0}};
+    constexpr int FIELDNORM = 3, DEAD = 5, n_swap = 6;
     const int n_parts = has_payload ? 5 : 4;
     for (int i = 0; i < n_parts; ++i)
         if (parts[i].need > parts[i].a->bytes || !parts[i].a->p) HIP_TRY(grown[i].alloc(std::max<uint64_t>(parts[i].need, 2 * uint64_t(parts[i].a->bytes))));
+    // a handle somebody deleted from: the bitmap's capacity follows the fieldnorm array's (a handle without a bitmap stays without)
+    if (t->d_dead.p) {
+        parts[DEAD].need = dead_bytes(grown[FIELDNORM].p ? grown[FIELDNORM].bytes : t->d_fieldnorm.bytes);
+        if (parts[DEAD].need > t->d_dead.bytes) HIP_TRY(grown[DEAD].alloc(parts[DEAD].need));
+    }
     // from here on the handle's arrays are written or replaced: whatever was enqueued before the call ends on the old ones
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipEventRecord(ev_resume.e, st.s));
-    for (int i = 0; i < n_parts; ++i)
+    // (a larger bitmap: new words zero -- the appended documents are live -- and the old words copied in front of them)
+    if (grown[DEAD].p) HIP_TRY(hipMemsetAsync(grown[DEAD].p, 0, grown[DEAD].bytes, st.s));
+    for (int i = 0; i < n_swap; ++i)
         if (grown[i].p && parts[i].used) HIP_TRY(hipMemcpyAsync(grown[i].p, parts[i].a->p, parts[i].used, hipMemcpyDeviceToDevice, st.s));
     auto now = [&](int i) { return static_cast<uint8_t *>(grown[i].p ? grown[i].p : parts[i].a->p); };
     ull *start = reinterpret_cast<ull *>(now(0));
@@ -194,7 +372,7 @@ int append_core(vbm25_doc_terms *t, const Delta &d, const ResolverVocabulary &v)
     HIP_TRY(hipEventElapsedTime(&ms, ev_start.e, ev_mid.e));
     HIP_TRY(hipEventElapsedTime(&ms2, ev_resume.e, ev_done.e));
     g_append_ms = double(ms) + ms2;
-    for (int i = 0; i < n_parts; ++i)
+    for (int i = 0; i < n_swap; ++i)
         if (grown[i].p) {
             std::swap(grown[i].p, parts[i].a->p);  // (the old array goes with `grown`)
             std::swap(grown[i].bytes, parts[i].a->bytes);
@@ -313,6 +491,20 @@ int vbm25_doc_terms_append(vbm25_doc_terms *t, const vbm25_growing_desc *delta, 
 }
 
 uint32_t vbm25_doc_terms_base_docs(const vbm25_doc_terms *t) { return t ? t->base_docs : 0; }
+
+int vbm25_doc_terms_delete(vbm25_doc_terms *t, const uint32_t *docs, uint64_t n, uint32_t *n_new) {
+    return guarded([&] { return delete_docs(t, docs, n, n_new); });
+}
+
+int vbm25_doc_terms_delete_tids(vbm25_doc_terms *t, const vbm25_tid_set *s, const vbm25_documents *payloads, uint32_t *n_new) {
+    return guarded([&] { return delete_tids(t, s, payloads, n_new); });
+}
+
+uint32_t vbm25_doc_terms_dead_docs(const vbm25_doc_terms *t) { return t ? t->n_dead : 0; }
+
+int vbm25_doc_terms_read_dead(const vbm25_doc_terms *t, uint64_t *words) {
+    return guarded([&] { return read_dead(t, words); });
+}
 
 // tools/live_rerank_cost.py: the device time of the calling thread's last append's kernels and copies, by HIP events.  Not in the header.
 int vbm25_debug_append_kernel_ms(double *ms) {

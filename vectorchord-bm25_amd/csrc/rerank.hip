@@ -8,7 +8,8 @@
 //   vbm25_scorer_topk       score and select fused; the nq x n_cand scores never reach HBM.  A unit is (query, part of at most
 //                           rerank_part candidates); every query has at least one unit, so every row of the result has a writer.
 //     rerank_part_kernel    one workgroup a unit, the workgroups stride the units.  A round: each of the four waves scores 64
-//                           candidates as eval_score_kernel does (the query's (id, idf) pairs 64 at a time through v_readlane,
+//                           candidates (one whose document is dead in the handle's deletion bitmap is left out as a NO_DOC entry
+//                           is: no score, no rank, its pos still counts) as eval_score_kernel does (the query's (id, idf) pairs 64 at a time through v_readlane,
 //                           score_step per term in query order -- the same operations in the same order, so the same bits), then
 //                           every lane offers (score key, pos) to the selection buffer in LDS if it beats the workgroup's threshold.
 //                           A full buffer is sorted (bitonic, in place) and cut to k; the k-th entry is the new threshold.  A lane
@@ -206,7 +207,10 @@ __global__ void __launch_bounds__(WG) rerank_part_kernel(TopkArgs a) {
         for (uint32_t c0 = c_lo; c0 < c_hi; c0 += WG) {
             const uint32_t c = c0 + threadIdx.x;
             const uint32_t d = c >= c_hi ? NO_DOC : a.s.cand_doc ? a.s.cand_doc[cand0 + c] : c;
-            const bool mine = d != NO_DOC;  // (a list entry that names no document is not eligible; its pos still counts)
+            bool mine = d != NO_DOC;  // (a list entry that names no document is not eligible; its pos still counts)
+            // ... and neither is one whose document is dead.  The pointer is the same in every lane: a handle nobody deleted from
+            // runs the line above and nothing more.
+            if (a.dead && mine) mine = !((a.dead[d >> 6] >> (d & 63u)) & 1ull);
             // a lane without a candidate: the empty run 0 .. 0, which score_step never reads
             uint32_t cursor = 0, hi = 0;
             double s1 = 1.0;
@@ -410,6 +414,7 @@ int scorer_topk(vbm25_scorer *sc, const uint32_t *term_ids, const uint32_t *q_of
     a.k = k;
     a.buf = buf;
     a.part = part;
+    a.dead = t->d_dead.as<ull>();
     a.out = reinterpret_cast<const TopkOut *>(dev + g.out);
     TopkOut o;
     o.unit_start = reinterpret_cast<const uint32_t *>(dev + g.unit);

@@ -37,6 +37,9 @@ struct TopkArgs {
     const uint32_t *multi_q;      // n_multi: the queries of several units
     const TopkOut *out;
     uint32_t n_units, n_multi, k, buf, part;
+    // the handle's deletion bitmap as the call found it (NULL: nobody deleted from the handle): a candidate whose document's bit is
+    // set is not eligible, as a NO_DOC entry is not
+    const unsigned long long *dead;
 };
 
 // The units of a batch: a scan of the parts per query, at least one a query; the queries of several parts get part lists.  They

@@ -11,7 +11,9 @@
 //                          the ids in the staged block instead
 //     cand_lookup_kernel   candidates given as ctids: one lane a candidate, tid_find in the payload directory (its directory staged
 //                          in LDS once per workgroup, its sorted keys in HBM) -> the document index, or NO_DOC for a ctid no
-//                          document carries.  Grid-stride under the eval_grid cap.
+//                          document carries.  On a handle with a deletion bitmap (vbm25_doc_terms_delete*) the position is walked
+//                          forward over the ctid's entries to the lowest document that is not dead (tid_first_live), NO_DOC when
+//                          all are.  Grid-stride under the eval_grid cap.
 //     rerank_part_kernel (+ rerank_merge_kernel)   with the resolved ids; a NO_DOC entry is not eligible, its pos still counts
 //     download             the rows and counts into the slot's pinned block, then the done event
 //   The payload directory (built once at create, from the payloads of a vbm25_documents or, for vbm25_reranker_create_from_index,
@@ -79,7 +81,9 @@ struct LookupArgs {
     ull n_keys;
     uint32_t n_dir, stride;
     uint32_t *cand_doc;  // n
+    const ull *dead;     // the handle's deletion bitmap as the submit found it (NULL: nobody deleted from the handle)
 };
+static_assert(NO_LIVE_DOC == NO_DOC, "a ctid whose documents are all dead is an entry that names no document");
 
 __global__ void __launch_bounds__(WG) cand_lookup_kernel(LookupArgs a) {
     extern __shared__ ull s_dir[];
@@ -88,8 +92,12 @@ __global__ void __launch_bounds__(WG) cand_lookup_kernel(LookupArgs a) {
     for (ull i = ull(blockIdx.x) * WG + threadIdx.x; i < a.n; i += ull(gridDim.x) * WG) {
         const uint16_t *p = a.tids + 3 * i;
         const uint16_t p3[3] = {p[0], p[1], p[2]};
-        const uint64_t at = tid_find(tid_key(p3), (const uint64_t *)s_dir, a.n_dir, (const uint64_t *)a.keys, a.n_keys, a.stride);
-        a.cand_doc[i] = at == NOT_THERE ? NO_DOC : a.docs[at];
+        const uint64_t key = tid_key(p3);
+        const uint64_t at = tid_find(key, (const uint64_t *)s_dir, a.n_dir, (const uint64_t *)a.keys, a.n_keys, a.stride);
+        uint32_t doc = at == NOT_THERE ? NO_DOC : a.docs[at];
+        // with a bitmap (the same pointer in every lane): the lowest LIVE document of the ctid -- a reused ctid names the new row
+        if (a.dead && at != NOT_THERE) doc = tid_first_live(at, key, (const uint64_t *)a.keys, a.docs, a.n_keys, (const uint64_t *)a.dead);
+        a.cand_doc[i] = doc;
     }
 }
 
@@ -385,6 +393,7 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     a.k = k;
     a.buf = buf;
     a.part = part;
+    a.dead = t->d_dead.as<ull>();
     TopkOut o;
     o.unit_start = reinterpret_cast<const uint32_t *>(dev + g.unit);
     o.q_off = a.s.q_off;
@@ -414,7 +423,7 @@ int reranker_submit(vbm25_reranker *r, const Queries &in, const uint64_t *q_cand
     }
     if (kind == CAND_TID) {
         const LookupArgs la{reinterpret_cast<const uint16_t *>(dev + g.docs), n_pairs, r->dir.as<ull>(), r->dir_keys.as<ull>(),
-                            r->dir_docs.as<uint32_t>(), r->dir_n, r->n_dir, r->stride, s.cand_doc.as<uint32_t>()};
+                            r->dir_docs.as<uint32_t>(), r->dir_n, r->n_dir, r->stride, s.cand_doc.as<uint32_t>(), t->d_dead.as<ull>()};
         const uint32_t cap = std::min(MAX_GRID, std::max(1u, eval_grid_cap()));
         cand_lookup_kernel<<<grid_for(n_pairs, WG, cap), WG, 8ull * std::max(1u, r->n_dir), st>>>(la);
         HIP_TRY(hipGetLastError());

@@ -320,6 +320,10 @@ int tid_tuning_set(const char *name, long long value) {
     return VBM25_OK;
 }
 uint32_t tid_dir_now() { return g_tid_dir.load(); }
+uint32_t tid_grid_now() { return std::max(1u, g_tid_grid.load()); }
+void tid_set_view(const vbm25_tid_set *s, TidSetView *out) {
+    *out = TidSetView{s->device, s->n_keys, s->n_dir, s->stride, s->keys.as<unsigned long long>(), s->dir.as<unsigned long long>()};
+}
 void tid_tuning_reset() {
     g_tid_grid.store(MAX_GRID);
     g_tid_dir.store(DEFAULT_DIR_LOG2);

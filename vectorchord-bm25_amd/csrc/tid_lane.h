@@ -13,6 +13,8 @@
 //                decides alone.  Exact for every n_keys >= 0.
 //   tid_find     the same search over keys that may repeat, returning the first position of the key (reranker.hip's ctid -> document
 //                lookup; tests/native/fuzz_tid_find.cpp checks it against std::lower_bound)
+//   tid_first_live  tid_find's position walked forward over the entries of one ctid to the lowest document that is not dead, and
+//                split_payload, where a document of a grown handle keeps its ctid (tests/native/fuzz_live_dead.cpp checks both)
 //   live_rank_old, live_rank_delta   where an old and a new entry go when a sorted delta is merged into the sorted keys (live.hip's
 //                merge kernel; tests/native/fuzz_live_merge.cpp checks them against std::merge), and live_sort_word / live_sort_step,
 //                the word and the network of the delta's sort in LDS
@@ -102,6 +104,29 @@ TID_HD uint64_t tid_find(uint64_t key, const uint64_t *directory, uint32_t n_dir
         else b = mid;
     }
     return a < n_keys && keys[a] == key ? a : NOT_THERE;
+}
+
+// ---- dead documents (live.hip: vbm25_doc_terms_delete*; reranker.hip: cand_lookup_kernel; tests/native/fuzz_live_dead.cpp) ----
+// A handle's deletion bitmap: one bit a document, document d at bit d & 63 of word d >> 6, set = dead.
+constexpr uint32_t NO_LIVE_DOC = 0xFFFFFFFFu;  // (rerank_shared.h's NO_DOC: the entry names no document)
+
+TID_HD bool dead_bit(const uint64_t *dead, uint32_t d) { return (dead[d >> 6] >> (d & 63u)) & 1ull; }
+
+// From tid_find's position `at` (the FIRST entry of `key`, at < n_keys) forward over the entries of the same key while their document
+// is dead: equal keys lie by ascending document, so the first live one is the lowest live document of the ctid.  NO_LIVE_DOC when the
+// run has none.
+TID_HD uint32_t tid_first_live(uint64_t at, uint64_t key, const uint64_t *keys, const uint32_t *docs, uint64_t n_keys, const uint64_t *dead) {
+    for (; at < n_keys && keys[at] == key; ++at) {
+        const uint32_t d = docs[at];
+        if (!dead_bit(dead, d)) return d;
+    }
+    return NO_LIVE_DOC;
+}
+
+// Where document d of a grown handle keeps its ctid: the plane of the documents it was bound with (d < base_docs), or the tail array
+// of the appended ones.  A wave's 64 documents may straddle the split: each lane decides for itself.
+TID_HD const uint16_t *split_payload(const uint16_t *base, const uint16_t *tail, uint32_t base_docs, uint64_t d) {
+    return d < base_docs ? base + 3 * d : tail + 3 * (d - base_docs);
 }
 
 // ---- the merge of a sorted delta into the sorted keys (live.hip: vbm25_reranker_sync; tests/native/fuzz_live_merge.cpp) ----

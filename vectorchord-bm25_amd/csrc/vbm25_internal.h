@@ -130,6 +130,16 @@ int live_tuning_set(long long value);
 void live_tuning_reset();
 // tid_dir as it stands (the reranker's payload directory is built under it, as a TID set's is)
 uint32_t tid_dir_now();
+// tid_grid as it stands, and what a match kernel outside tid.hip reads of a TID set (tid.hip fills it in; live.hip's
+// vbm25_doc_terms_delete_tids): the sorted distinct keys and the directory over them, in HBM on `device`
+uint32_t tid_grid_now();
+struct TidSetView {
+    int device;
+    uint64_t n_keys;
+    uint32_t n_dir, stride;
+    const unsigned long long *keys, *dir;
+};
+void tid_set_view(const vbm25_tid_set *s, TidSetView *out);
 
 }  // namespace vbm25
 
