@@ -552,6 +552,19 @@ class Batch:
         check(f(self.h, out.ctypes.data))
         return out.view(np.float64)
 
+    def debug_lists(self, q):
+        """test aid (not in include/vbm25.h), after a run on the general route: per list of query q's work items, in merge_kernel's
+        order, (the entries merge_kernel loads, those of them at or above the query's threshold -- the survivors it ranks)"""
+        f = lib().vbm25_batch_debug_lists
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        n = C.c_uint32()
+        cap = 1 << 16
+        cnt, surv = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        check(f(self.h, int(q), cnt.ctypes.data, surv.ctypes.data, cap, C.byref(n)))
+        assert n.value <= cap
+        return cnt[:n.value].copy(), surv[:n.value].copy()
+
     def debug_check(self):
         """-DVBM25_CHECK builds (tools/dense_stress.py): (code, value, item, thread) of the first violated device
         assertion since the last call; code 0 = none.  A library without the entry point reports None."""

@@ -1476,6 +1476,38 @@ int vbm25_batch_debug_theta(vbm25_batch *bt, unsigned long long *out) {
     return VBM25_OK;
 }
 
+// test aid (not declared in include/vbm25.h): what merge_kernel read of query q after a run on the general route (the only route that
+// keeps the lists: the others' merges clean them, and this entry refuses them) -- per list of the query's items, in merge_kernel's
+// order, cnt[l] = min(res_cnt, k), the entries it loads, and surv[l] = those of them at or above the query's threshold, the ones it
+// ranks.  *n_lists = the query's lists (items x lists per item); more than cap of them is an error.
+int vbm25_batch_debug_lists(vbm25_batch *bt, uint32_t q, uint32_t *cnt, uint32_t *surv, uint32_t cap, uint32_t *n_lists) {
+    if (!bt || !cnt || !surv || !n_lists) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    *n_lists = 0;
+    if (bt->bigk || bt->plan.route != Route::General) return set_error(VBM25_ERR_INVALID, "the lists are kept on the general route only");
+    if (q >= bt->nq) return set_error(VBM25_ERR_INVALID, "query %u of %u", q, bt->nq);
+    if (int rc = use_device(bt->index->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    uint32_t base[2] = {0, 0};
+    unsigned long long theta = 0;
+    HIP_TRY(hipMemcpy(base, bt->q_item_base.as<uint32_t>() + q, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&theta, bt->theta.as<unsigned long long>() + q, 8, hipMemcpyDeviceToHost));
+    if (base[1] < base[0] || base[1] > bt->max_items) return set_error(VBM25_ERR_DEVICE, "query %u: items %u .. %u", q, base[0], base[1]);
+    const size_t L0 = size_t(base[0]) * bt->lpi, NL = size_t(base[1] - base[0]) * bt->lpi;
+    if (NL > cap) return set_error(VBM25_ERR_INVALID, "query %u has %zu lists, the caller's arrays hold %u", q, NL, cap);
+    *n_lists = uint32_t(NL);
+    if (!NL) return VBM25_OK;
+    std::vector<uint32_t> rc(NL);
+    std::vector<unsigned long long> sc(NL * bt->k);  // (the query's lists lie side by side: one copy)
+    HIP_TRY(hipMemcpy(rc.data(), bt->res_cnt.as<uint32_t>() + L0, 4 * NL, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sc.data(), bt->res_score.as<double>() + L0 * bt->k, 8 * NL * bt->k, hipMemcpyDeviceToHost));
+    for (size_t l = 0; l < NL; ++l) {
+        cnt[l] = std::min(rc[l], bt->k);
+        surv[l] = 0;
+        for (uint32_t i = 0; i < cnt[l]; ++i) surv[l] += sc[l * bt->k + i] >= theta;
+    }
+    return VBM25_OK;
+}
+
 int vbm25_batch_set_timing(vbm25_batch *bt, int enabled) {
     if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
     bt->timing = enabled != 0;
