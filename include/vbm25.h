@@ -288,6 +288,11 @@ int vbm25_batch_set_queries(vbm25_batch *, const uint32_t *term_ids, const uint3
                             uint32_t nq);
 int vbm25_batch_run(vbm25_batch *, void *hip_stream);
 int vbm25_batch_fetch(vbm25_batch *, vbm25_hit *hits, uint32_t *n_hits);
+/* k > 1024: how many queries of the last run took the batched path for sparse queries (the document frequencies of the
+ * query's terms sum to at most the tuning value bigk_cand_max: scan, select and sort cost what its postings cost) and how
+ * many the per-query path over every document of the index.  The records are the same bytes either way.  Both 0 for a
+ * batch of k <= 1024 or a NULL batch; either pointer may be NULL. */
+int vbm25_batch_bigk_queries(const vbm25_batch *, uint32_t *sparse, uint32_t *fallback);
 /* Device address of the nq x k vbm25_hit array / the nq counts (valid after run; a batch object whose device
  * addresses were asked for leaves complete records there after EVERY run -- without this call a run may leave a
  * query to vbm25_batch_fetch, which then repeats the scan for it before it returns). */

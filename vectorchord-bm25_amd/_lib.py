@@ -86,6 +86,7 @@ ABI = {
     "vbm25_batch_set_queries": (i32, [vp, vp, vp, u32]),
     "vbm25_batch_run": (i32, [vp, vp]),
     "vbm25_batch_fetch": (i32, [vp, vp, vp]),
+    "vbm25_batch_bigk_queries": (i32, [vp, vp, vp]),
     "vbm25_batch_device_results": (i32, [vp, vp, vp]),
     "vbm25_batch_set_timing": (i32, [vp, i32]),
     "vbm25_batch_kernel_ms": (i32, [vp, vp, vp]),

@@ -462,6 +462,13 @@ class Batch:
                                       _p(n_hits) if self.nq else None))
         return hits, n_hits
 
+    def bigk_queries(self):
+        """vbm25_batch_bigk_queries: (queries of the last run on the batched sparse path of k > 1024, queries on the per-query
+        path); (0, 0) for k <= 1024."""
+        sparse, fallback = C.c_uint32(), C.c_uint32()
+        check(lib().vbm25_batch_bigk_queries(self.h, C.byref(sparse), C.byref(fallback)))
+        return sparse.value, fallback.value
+
     def set_timing(self, enabled=True):
         check(lib().vbm25_batch_set_timing(self.h, int(enabled)))
 

@@ -63,6 +63,11 @@ struct Tuning {
     int win_skew = 1;              // one item per wave: a query's three runs of windows sized for the three kinds of waves of a SIMD
     uint32_t id16_max_blocks = 0x00ffffff;  // an index without post_id16: the most 256-byte blocks of a batch's terms its scratch plane takes
                                    // (a larger batch takes scan_range_kernel; tests lower it to cross the limit on a small corpus)
+    int bigk_sparse = 1;           // k > 1024: sparse queries take the batched path of bigk.hip (0: every query the per-query path)
+    uint64_t bigk_cand_max = 1ull << 20;   // ... a query is sparse when its terms' document frequencies sum to at most this: its candidate
+                                   // segment (12 bytes an entry) is then at most 12 MB, and four such queries share a chunk
+    uint64_t bigk_chunk_cand = 1ull << 22; // ... candidate entries a chunk of queries may ask for: the batch's candidate scratch, 48 MB
+    uint32_t bigk_item_win = 0;    // ... windows of 8192 documents per work item (0: cut for about 2048 items a batch)
     uint32_t generation = 0;       // bumped by every vbm25_tuning_set / reset: vbm25_search_batch's batch object is rebuilt when it is stale
 };
 // the switches of the moment (search.hip owns them and their lock: vbm25_tuning_set / _reset write, this copies)
@@ -117,6 +122,35 @@ struct QueryPlan {
     uint32_t n_term_pos = 0;      // term positions (q_off[nq])
     StagedLayout staged;
     uint32_t range_rt() const { return range_mt == 0 ? 0u : range_mt <= 8u ? 8u : 16u; }  // scan_range_kernel's row stride
+};
+
+// The sparse k > 1024 path (bigk.hip).  A sparse query's descriptor, a work item, a chunk of queries, and the batch's state: the
+// switches as the batch took them, the scratch (sized when the batch is made), the current query set's plan (set_queries) and the
+// last run's tally.
+struct BigkQuery {
+    uint32_t q;                  // the query's number in the batch
+    uint32_t term_lo, term_hi;   // its indexed terms with postings, in query order, in BigkState::terms
+    uint32_t cand_base, cand_cap;  // its candidate segment in the chunk's scratch: the sum of its document frequencies
+};
+struct BigkItem {
+    uint32_t s, win_lo, win_hi;  // sparse query (index into the descriptors), windows [win_lo, win_hi)
+};
+struct BigkChunk {
+    uint32_t s0, s1, item0, item1;
+};
+constexpr uint64_t BIGK_SURV_ENTRIES = 1ull << 22;  // survivor entries a chunk holds at most (k rounded up to tiles per query): 48 MB
+struct BigkState {
+    bool on = false;
+    uint64_t cand_max = 0, chunk_cand = 0, max_items = 0;
+    uint32_t chunk_q = 0, surv_stride = 0, wpi = 0;
+    DeviceBuffer cand_key, cand_doc, surv_key, surv_doc, cursor, surv_cnt, sel, qd, terms, items;
+    std::vector<uint8_t> sparse;  // per query of the current set: takes the sparse path
+    std::vector<BigkQuery> h_qd;
+    std::vector<uint32_t> h_terms;
+    std::vector<BigkItem> h_items;
+    std::vector<BigkChunk> chunks;
+    uint32_t n_sparse = 0;
+    uint32_t ran_sparse = 0, ran_fallback = 0;  // queries of the last run by path (vbm25_batch_bigk_queries)
 };
 
 }  // namespace vbm25
@@ -200,6 +234,7 @@ struct vbm25_batch {
     vbm25::DeviceBuffer bk_acc, bk_keys, bk_iota, bk_docs, bk_tmp;
     size_t bk_tmp_bytes = 0;
     std::vector<uint32_t> h_terms, h_off;  // host copy of the queries (bigk launches per term)
+    vbm25::BigkState bg;          // k > 1024: the sparse queries' path (bigk.hip)
     // filtered search (vbm25_batch_set_filter): the filter and per query the bitmap it takes (max_queries selectors, on the device and,
     // for the k > 1024 path, on the host); filt_on: some selector names a bitmap (else the kernels see no filter at all)
     const vbm25_filter *filter = nullptr;
@@ -282,6 +317,10 @@ int vbm25_batch_enqueue_download(vbm25_batch *bt);
 int vbm25_batch_finish_download(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits);
 int batch_grow_buffer(DeviceBuffer &b, size_t bytes);
 int batch_growing_buffers(vbm25_batch *bt, const vbm25_device_growing *gs);
+// bigk.hip: the sparse queries of a k > 1024 batch -- scratch at create, chunks and items at set_queries, the launches of a run
+int bigk_create(vbm25_batch *bt);
+int bigk_plan(vbm25_batch *bt);
+int bigk_run(vbm25_batch *bt, hipStream_t st);
 // growing.hip: grow_delete_kernel over a deletion bitmap in HBM (tid.hip makes one from a TID set)
 int growing_delete_by_bits(vbm25_device_growing *gs, const uint32_t *bits);
 // filter.hip

@@ -164,6 +164,7 @@ static int vbm25_batch_create_impl(vbm25_index *ix, uint32_t max_queries, uint32
         HIP_TRY(hipMemset(bt->error_flag.p, 0, 4));
         bigk_iota_kernel<<<1024, 256>>>(bt->bk_iota.as<uint32_t>(), (uint32_t)n);
         HIP_TRY(hipGetLastError());
+        if ((rc = bigk_create(bt.get()))) return rc;  // the sparse queries' scratch
         *out = bt.release();
         return VBM25_OK;
     }
@@ -428,6 +429,7 @@ static int commit_queries(vbm25_batch *bt, const uint32_t *term_ids, const uint3
     if (plan.route == Route::Exhaustive) {
         bt->h_terms.assign(term_ids, term_ids + q_off[nq]);
         bt->h_off.assign(q_off, q_off + nq + 1);
+        if (int rc = bigk_plan(bt)) return rc;  // which queries are sparse, their chunks and work items
     } else {
         if (plan.id16_decode) {  // (the scratch plane grows with the largest batch it has held)
             const size_t need = 256ull * plan.id16_blocks + 1024;
@@ -530,6 +532,8 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
 // set's descriptors and the new one's count.  Filter and growing segment stay attached.
 void batch_clear_queries(vbm25_batch *bt) {
     bt->nq = 0;
+    bt->bg.n_sparse = 0;
+    bt->bg.chunks.clear();
     bt->plan = QueryPlan{};
     bt->qin_live = false;
     bt->win_nofuse = false;
@@ -646,11 +650,17 @@ static DevBatch dev_batch(const vbm25_batch *bt) {
     return db;
 }
 
-// k > 1024: per query, one accumulation launch per term, the filter's mask, a radix sort of the scores, the first k of them
+// k > 1024: the sparse queries batched (bigk.hip); every other query on its own -- one accumulation launch per term, the filter's
+// mask, a radix sort of the scores, the first k of them
 static int run_exhaustive(vbm25_batch *bt, hipStream_t st) {
     const DevIndex &dix = bt->index->dev;
     const uint32_t n = bt->index->n_docs;
+    bt->bg.ran_sparse = bt->bg.ran_fallback = 0;
+    if (int rc = bigk_run(bt, st)) return rc;
+    bt->bg.ran_sparse = bt->bg.n_sparse;
     for (uint32_t q = 0; q < bt->nq; ++q) {
+        if (bt->bg.n_sparse && bt->bg.sparse[q]) continue;
+        ++bt->bg.ran_fallback;
         HIP_TRY(hipMemsetAsync(bt->bk_acc.p, 0, 8ull * n, st));
         for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p) {
             const uint32_t t = bt->h_terms[p];
@@ -1306,7 +1316,8 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
-// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, dbg; cast_wave_max and cast_group_max (read
+// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
+// bigk_item_win, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
@@ -1342,6 +1353,10 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "win_cut1") g_tune.win_cut1 = int(std::min<long long>(std::max<long long>(value, 1), 998));
     else if (n == "win_cut2") g_tune.win_cut2 = int(std::min<long long>(std::max<long long>(value, 2), 999));
     else if (n == "win_fuse") g_tune.win_fuse = value != 0;
+    else if (n == "bigk_sparse") g_tune.bigk_sparse = value != 0;
+    else if (n == "bigk_cand_max") g_tune.bigk_cand_max = (uint64_t)std::min<long long>(std::max(0ll, value), 1ll << 30);
+    else if (n == "bigk_chunk_cand") g_tune.bigk_chunk_cand = (uint64_t)std::min<long long>(std::max(1ll, value), 1ll << 30);
+    else if (n == "bigk_item_win") g_tune.bigk_item_win = (uint32_t)std::min<long long>(std::max(0ll, value), 1ll << 20);
     else if (n == "id16_max_blocks") g_tune.id16_max_blocks = (uint32_t)std::min<long long>(std::max(2ll, value), 0x00ffffffll);
     else if (n == "cast_wave_max" || n == "cast_group_max" || n == "cast_pack" || n == "cast_grid") {  // (the cast's class bounds and the caster's kernel choice and grid cap: cast.hip keeps and reads them)
         if (int rc = vbm25::cast_tuning_set(name, value)) return rc;
@@ -1539,6 +1554,12 @@ int vbm25_batch_profile(vbm25_batch *bt, unsigned long long *out, uint32_t n_wor
     return VBM25_OK;
 }
 #endif
+
+int vbm25_batch_bigk_queries(const vbm25_batch *bt, uint32_t *sparse, uint32_t *fallback) {
+    if (sparse) *sparse = bt && bt->bigk ? bt->bg.ran_sparse : 0u;
+    if (fallback) *fallback = bt && bt->bigk ? bt->bg.ran_fallback : 0u;
+    return VBM25_OK;
+}
 
 int vbm25_batch_create(vbm25_index *ix, uint32_t max_queries, uint32_t max_total_terms, uint32_t k,
                        vbm25_batch **out) {
