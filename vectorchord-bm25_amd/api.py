@@ -515,6 +515,18 @@ class Batch:
         check(f(self.h, C.byref(ni), C.byref(nf)))
         return ni.value, nf.value
 
+    def debug_given_up(self):
+        """tool aid: why scan_dense_kernel<1024> gave items of the last run up -- (a window's task list full, the survivor list
+        overflowed, the re-scoring cap); None on a library without the entry point"""
+        f = getattr(lib(), "vbm25_batch_debug_given_up", None)
+        if f is None:
+            return None
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_uint32 * 3)()
+        check(f(self.h, out))
+        return tuple(int(x) for x in out)
+
     def debug_route(self):
         """test aid: 0 general route (plan_kernel), 1 one launch, 2 plan-free scan_range_kernel, 3 scan_win_kernel, 4 exhaustive"""
         f = lib().vbm25_batch_debug_route
@@ -524,7 +536,8 @@ class Batch:
 
     def debug_routes(self):
         """bench / test aid: (queries classed sparse, dense, many-term by the host; work items of the last run on the general route
-        that went to the sparse, the dense and the many-term kernel)"""
+        that went to the sparse, the dense and the many-term kernel).  256 < k <= 1024 with dense_big on: [4] = the items that went
+        to scan_dense_kernel<1024>, [5] = all the others (scan_many_kernel's), [3] = 0"""
         f = lib().vbm25_batch_debug_routes
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.c_void_p]
@@ -1237,6 +1250,8 @@ def set_tuning(name, value):
     """test / tuning aid (vbm25_tuning_set, not in include/vbm25.h): process-wide switch read when a Batch / GpuIndex
     scratch batch is created.  Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items,
     range_min_chunk, range_grid, dense_grid, fused_items, arith, win, win_force, win_items, win_grid, win_skew, win_guided,
+    dense_big (256 < k <= 1024: dense queries of <= 16 terms take scan_dense_kernel's survivor-list instantiation, the default; 0 leaves
+    every query of such a batch to scan_many_kernel) and dense_big_min_docs (the smallest index that route takes, 65536 documents),
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
     and cast_group_max (the class bounds of Documents.cast and Caster.submit, read at the start of each; 0 turns the class off),

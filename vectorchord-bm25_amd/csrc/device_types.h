@@ -61,6 +61,8 @@ struct Item {
     uint32_t q, doc_lo, doc_hi, m;  // m = number of indexed terms of query q | ITEM_DENSE
 };
 constexpr uint32_t ITEM_DENSE = 0x80000000u;  // postings per document high: dense-window path
+constexpr uint32_t ITEM_OTHER = 0x40000000u;  // 256 < k <= 1024 with the dense-window kernel on: an item that is NOT that kernel's (a sparse query,
+                                              // more than D_T terms) -- its term count reads as "many" and scan_many_kernel takes it
 
 struct DevBatch {
     const uint32_t *term_ids;

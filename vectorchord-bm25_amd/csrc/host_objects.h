@@ -68,6 +68,10 @@ struct Tuning {
                                    // segment (12 bytes an entry) is then at most 12 MB, and four such queries share a chunk
     uint64_t bigk_chunk_cand = 1ull << 22; // ... candidate entries a chunk of queries may ask for: the batch's candidate scratch, 48 MB
     uint32_t bigk_item_win = 0;    // ... windows of 8192 documents per work item (0: cut for about 2048 items a batch)
+    int dense_big = 1;             // 256 < k <= 1024: dense queries of <= D_T terms take scan_dense_kernel<1024> (the survivor list in LDS);
+                                   // 0: every query of such a batch takes scan_many_kernel.  On: profiles/dense_big_cost.json (C5, k = 1000: 270 -> 67 ms)
+    uint32_t dense_big_min_docs = 65536;  // ... on an index of at least this many documents (four full windows: below, nothing is skipped
+                                   // before the threshold is warm)
     uint32_t generation = 0;       // bumped by every vbm25_tuning_set / reset: vbm25_search_batch's batch object is rebuilt when it is stale
 };
 // the switches of the moment (search.hip owns them and their lock: vbm25_tuning_set / _reset write, this copies)
@@ -258,7 +262,8 @@ struct vbm25_batch {
     bool use_range = false;       // k <= REG_K: sparse queries of <= 16 terms take scan_range_kernel, dense ones scan_dense_kernel
     uint32_t lpi = 1;             // result lists per work item
     bool use_dense = false;       // dense queries of <= D_T terms take scan_dense_kernel
-    vbm25::QueryPlan plan;               // the current queries' route (set_queries)
+    bool dense_big = false;       // 256 < k <= 1024: they take its survivor-list instantiation (one list per item: lpi stays 1)
+    vbm25::QueryPlan plan;              // the current queries' route (set_queries)
     // an index without the post_id16 plane: the batch's scratch plane (the low 16 bits of the ids of the current queries' terms, made by
     // decode_id16_kernel ahead of every scan_win_kernel launch) and, per term position, the term's first 256-byte block in it
     vbm25::DeviceBuffer id16_tmp, id16_fb;

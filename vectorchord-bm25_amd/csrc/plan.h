@@ -35,8 +35,9 @@ __device__ __forceinline__ unsigned long long plan_incl_scan(unsigned long long 
 
 // dense_c != 0: every dense query (q_dense) is cut into dense_c items of equal document counts -- the dense-window kernel's
 // work per item goes with its windows, not with its postings -- and does not count towards the other queries' chunk size.
+// other_mark: 0, or ITEM_OTHER (below, where the items are written).
 __global__ void __launch_bounds__(PLAN_WG) plan_kernel(DevIndex ix, DevBatch bt, uint32_t max_items,
-                                                       uint32_t target_items, uint32_t min_chunk, uint32_t dense_c) {
+                                                       uint32_t target_items, uint32_t min_chunk, uint32_t dense_c, uint32_t other_mark) {
     __shared__ unsigned long long s_wave[PLAN_WG / 64];
     __shared__ uint32_t s_bucket[PLAN_BUCKETS];
     const uint32_t tid = threadIdx.x;
@@ -125,6 +126,9 @@ __global__ void __launch_bounds__(PLAN_WG) plan_kernel(DevIndex ix, DevBatch bt,
         const uint32_t c = chunks_of(q);
         uint32_t nterms = 0;
         for (uint32_t p = bt.q_off[q]; p < bt.q_off[q + 1]; ++p) nterms += bt.term_ids[p] < ix.n_terms;
+        // (other_mark = ITEM_OTHER where scan_many_kernel has no term-count class of its own, 256 < k <= 1024: every item but a dense
+        // query's of at most range_max_terms terms is marked as its)
+        if (other_mark && !(bt.q_dense[q] && nterms <= bt.range_max_terms)) nterms |= other_mark;
         if (bt.q_dense[q]) nterms |= ITEM_DENSE;
         bt.q_item_base[q] = min(base, max_items);
         const uint32_t pos = c ? atomicAdd(&s_bucket[bucket_of(one ? own_postings : postings_of(q), c)], c) : 0u;

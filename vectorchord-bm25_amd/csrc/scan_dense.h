@@ -52,6 +52,7 @@
 #define VBM25_SCAN_DENSE_H
 
 #include "scan_range.h"
+#include "dense_list_lane.h"
 
 namespace vbm25 {
 
@@ -71,6 +72,9 @@ constexpr int D_WCB = 128;               // candidate buffer entries per wave
 constexpr int D_UN = D_UN_V;                  // tasks per wave in flight
 constexpr uint32_t D_MAX_RESOLVED = 16384;  // exact re-scorings per item; beyond (masses of equal scores): scan_many_kernel
 constexpr uint32_t D_SPAN_TEST = 512;    // widest block span the skip test reads (8 accumulators per lane)
+constexpr int D_BIG_K = 1024;            // the instantiation for 256 < k <= 1024: the survivor list in LDS (below) instead of a register top-k
+constexpr uint32_t D_MAX_RESOLVED_BIG = 4 * D_MAX_RESOLVED;  // ... its exact re-scorings per item: the candidates of the warm-up go with k (k ln 2 a
+                                                             // window while the width doubles), and k is up to four times the register variant's
 
 struct DenseLds {
     uint32_t acc[D_W / 2];    // 16-bit fixed point, two documents per word: scale x (upper bound of the document's score) < 2^16
@@ -99,6 +103,27 @@ struct DenseLds {
     uint32_t scratch[64];
 };
 
+// The SURVIVOR LIST of the KMAX = D_BIG_K instantiation (256 < k <= 1024): one buffer of dlist::CAP = 2 x 1024 (score bits, document)
+// entries per workgroup -- 24 KB beside the 76 KB of DenseLds, one workgroup per CU.  A wave that has re-scored candidates exactly APPENDS
+// the ones the threshold does not strictly beat: one LDS atomic on `cur` per wave, the lane's slot by its rank in the ballot.  An append
+// past the buffer writes nothing and gives the item up (S.fail: scan_many_kernel redoes it).  When `cur` has passed k, all eight waves
+// CUT behind the next window's P0 barrier (nobody appends between a window's P0 and P3 barriers, so that is the one point of the loop
+// where the cursor stands still for every wave), and before and after the last re-scoring at the item's end: a bitonic sort over the live entries (rerank_lane.h's
+// schedule; every wave keeps the pairs of its own eighth of the buffer, so only the strides that leave it need the workgroup's barrier),
+// the first k stay, the k-th score goes to the query's threshold.  Between two cuts lie one re-scoring by all waves (up to 8 x 128
+// appends) and whatever single waves re-score with a full buffer: CAP - k >= 1024 entries hold the first, and at k near 1024 little of
+// the second -- 4 to 8 % of C5's items are given up that way.  dense_list_lane.h has the per-lane functions (host-compilable: tests/native/fuzz_dense_big.cpp).
+struct DenseList {
+    unsigned long long key[dlist::CAP];
+    uint32_t doc[dlist::CAP];
+    uint32_t cur;  // entries appended (beyond CAP: appends that found the buffer full)
+};
+// (a function's own LDS: only the instantiation that calls it carries the 24 KB)
+__device__ __forceinline__ DenseList &dense_list() {
+    __shared__ DenseList L;
+    return L;
+}
+
 // Register budget: at 128 registers (two workgroups per CU) the four-row instantiation spills 53 registers, and a build of
 // this kernel under that pressure returned incomplete lists / faulted on the codec corner-case index (round 2).  The same
 // source compiled for 256 registers is correct in every run, so is the present source at 128 (tools/dense_stress.py, 360
@@ -108,8 +133,9 @@ struct DenseLds {
 // by the repetition test of tests/test_gpu_dense.py.
 template <int KMAX>
 __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(DevIndex ix, DevBatch bt) {
-    static_assert(KMAX <= D_KMAX, "register top-k of at most four rows");
-    constexpr int RK = KMAX / 64;
+    static_assert(KMAX <= D_KMAX || KMAX == D_BIG_K, "register top-k of at most four rows, or the survivor list in LDS");
+    constexpr bool BIG = KMAX > D_KMAX;
+    constexpr int RK = BIG ? 1 : KMAX / 64;
     __shared__ DenseLds S;
 
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
@@ -137,6 +163,7 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             S.resolved = 0;
             S.h_ne = 0;
             S.nlo[0] = S.nlo[1] = S.nhi[0] = S.nhi[1] = S.cfl[0] = S.cfl[1] = 0;
+            if constexpr (BIG) dense_list().cur = 0;
         }
         __syncthreads();
         const uint32_t item = uni(S.item);
@@ -205,7 +232,8 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             }
             const bool act = lane < m;
             double s0 = 0.0, tub = 0.0, kth = 0.0;
-            const double *kub = query_filter(q) ? nullptr : ca->ix.term_kth_ub;  // (a filtered query: no theta0)
+            // (a filtered query: no theta0; k > 256: term_kth_ub has no level for it -- the item starts at the query's shared threshold)
+            const double *kub = BIG || query_filter(q) ? nullptr : ca->ix.term_kth_ub;
             if (act && kub) {  // theta0: the term's 2^i-th largest block maximum, 2^i >= k (k documents of the term score that much)
                 uint32_t kidx = 0;
                 while ((1u << kidx) < k) ++kidx;
@@ -291,7 +319,7 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             return x >= 4294967295.0 ? 0xffffffffu : (uint32_t)x;
         };
 
-        RegTopK<RK> rtop;
+        RegTopK<RK> rtop;  // (BIG: unused)
         rtop.init();
         unsigned long long published = 0;
         auto theta_now = [&]() -> unsigned long long {
@@ -300,6 +328,26 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
         };
         auto offer = [&](bool has, double sc, uint32_t d) {
             const unsigned long long th = theta_now();
+            if constexpr (BIG) {  // append to the workgroup's survivor list
+                DenseList &L = dense_list();
+                const unsigned long long key = (unsigned long long)__double_as_longlong(sc);
+                has = has && dlist::keeps(key, th);
+                const unsigned long long hm = __ballot(has);
+                if (!hm) return;
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(&L.cur, (uint32_t)__popcll(hm));
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                const uint32_t slot = rrk::offer_slot(base, __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u)));
+                if (has) {
+                    if (dlist::fits(slot)) {
+                        L.key[slot] = key;
+                        L.doc[slot] = d;
+                    } else {
+                        S.fail = 2;  // the buffer is full before the next cut: seen behind the next barrier (2: told apart at the item's end)
+                    }
+                }
+                return;
+            }
             has = has && (unsigned long long)__double_as_longlong(sc) >= th &&
                   (rtop.cnt < k || better(sc, d, rtop.kth_s, rtop.kth_d));
             if (!__ballot(has)) return;
@@ -613,6 +661,54 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             PROF_ADD(7, t_fb, t_fc);
         };
 
+        // ---- BIG: the cut of the survivor list -- all eight waves, behind a barrier that everybody has passed with no append in flight
+        // (nobody re-scores between a window's P0 barrier and its P3).  Sort, keep the first k, raise the threshold.
+        auto list_cut = [&]() {
+            if constexpr (BIG) {
+                DenseList &L = dense_list();
+                const uint32_t live = min(uni(L.cur), dlist::CAP);
+                const uint32_t n = dlist::sort_entries(live), ppw = dlist::wave_pairs(n);
+                for (uint32_t i = live + wave * 64u + lane; i < n; i += DWG) {
+                    L.key[i] = dlist::PAD_KEY;
+                    L.doc[i] = dlist::PAD_DOC;
+                }
+                bool wide_before = true;  // (the padding is other waves')
+                for (uint32_t size = 2; size <= n; size <<= 1)
+                    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+                        const bool local = dlist::stage_local(stride, n);
+                        if (!local || wide_before) lds_barrier();
+                        else __builtin_amdgcn_wave_barrier();  // (the wave's own entries: its LDS operations complete in order)
+                        wide_before = !local;
+                        for (uint32_t p = lane; p < ppw; p += 64) {
+                            uint32_t i, j;
+                            bool best_first;
+                            dlist::wave_pair(wave, p, n, size, stride, i, j, best_first);
+                            const unsigned long long ka0 = L.key[i], kb0 = L.key[j];
+                            const uint32_t da0 = L.doc[i], db0 = L.doc[j];
+                            uint64_t ka = ka0, kb = kb0;
+                            uint32_t da = da0, db = db0;
+                            rrk::exchange(ka, da, kb, db, best_first);
+                            if (ka != ka0 || da != da0) {  // swapped (two entries never hold the same document)
+                                L.key[i] = ka;
+                                L.doc[i] = da;
+                                L.key[j] = kb;
+                                L.doc[j] = db;
+                            }
+                        }
+                    }
+                lds_barrier();
+                if (wave == 0 && lane == 0) {
+                    L.cur = dlist::cut_count(live, k);
+                    if (live >= k) {
+                        const unsigned long long kb = L.key[k - 1u];
+                        atomicMax(&S.theta, kb);
+                        atomicMax(&bt.theta[q], kb);
+                    }
+                }
+                lds_barrier();
+            }
+        };
+
         // =====================================================================
         // Window loop.  The metadata of window n + 1 is requested before P3 of window n (enum_request) and
         // consumed at the top of window n + 1: the round trip hides behind P3, the flag barrier and a flush.
@@ -748,11 +844,13 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             }
             lds_barrier();  // tasks, counts, split and threshold visible
             const uint32_t cnt1 = uni(S.nlo[par]), cnth = uni(S.nhi[par]);
-            if (uni(S.fail) || cnt1 + cnth > (uint32_t)D_TCAP || uni(S.resolved) > D_MAX_RESOLVED) {
+            if (uni(S.fail) || cnt1 + cnth > (uint32_t)D_TCAP || uni(S.resolved) > (BIG ? D_MAX_RESOLVED_BIG : D_MAX_RESOLVED)) {
                 failed = true;  // (too many re-scorings: the sums cannot tell masses of equal scores apart -- exhaustive kernel)
                 break;
             }
             if (uni(S.p_ne) >= m) break;  // no document can reach the threshold any more (search.rs:153-169 with every term)
+            if constexpr (BIG)
+                if (uni(dense_list().cur) > k) list_cut();  // (the threshold below is the cut's)
             const uint32_t h_new = uni(S.h_ne);
             bool flush_due = uni(S.cfl[par ^ 1u]) != 0;  // some wave's buffer was half full after the last window: everybody re-scores before P3
             const uint32_t theta_i = theta_fix(theta_now());
@@ -845,7 +943,19 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             W = min(2u * W, wmax);
             h_lay = h_new;
         }
+        if constexpr (BIG) {  // the item's end: the last window's appends are cut before the waves' buffers follow (up to 1024 entries more).
+            // Every wave reads the cursor between two barriers: no wave appends (flush, below) before all have decided.
+            __syncthreads();
+            const bool cut_now = !failed && uni(dense_list().cur) > k;
+            if (cut_now) list_cut();  // (ends with a barrier)
+            else __syncthreads();
+        }
         if (!failed) flush();
+        if constexpr (BIG) {  // ... every wave's last survivors are in: one more sort and cut (an append may have found the buffer full)
+            __syncthreads();
+            if (!failed && uni(S.fail)) failed = true;
+            if (!failed) list_cut();
+        }
 #ifdef VBM25_PROFILE
         prof[12] += 1;
         prof[9] += __builtin_readcyclecounter() - t_loop;
@@ -859,8 +969,23 @@ __global__ void __launch_bounds__(DWG, KMAX > 128 ? 2 : 4) scan_dense_kernel(Dev
             if (t0 < (uint32_t)D_W / 64) S.bmax[t0] = 0u;
         }
 
-        // ---- item result: one list per wave
-        {
+        // ---- item result: one list per wave (BIG: the workgroup's one list, sorted, as scan_many_kernel writes its own)
+        if constexpr (BIG) {
+            const DenseList &L = dense_list();
+            const uint32_t n = failed ? 0u : min(uni(L.cur), k);
+            const KernArgsP ce = cold_args();
+            VCHK(item < ce->bt.max_items && ce->bt.lpi == 1u, 9, item);
+            for (uint32_t i = wave * 64u + lane; i < n; i += DWG) {
+                ce->bt.res_score[(size_t)item * k + i] = __longlong_as_double((long long)L.key[i]);
+                ce->bt.res_doc[(size_t)item * k + i] = L.doc[i];
+            }
+            if (wave == 0 && lane == 0) {
+                ce->bt.res_cnt[item] = n;
+                // why the item was given up, in the low bits (vbm25_batch_debug_given_up): 2 the list overflowed, 4 the re-scoring cap, 1 the task list
+                ce->bt.item_failed[item] = !failed ? 0u : 0x140u | (S.fail == 2u ? 2u : S.resolved > D_MAX_RESOLVED_BIG ? 4u : 1u);
+                if (failed) *ce->bt.fail_any = 1u;
+            }
+        } else {
             const uint32_t n = failed ? 0u : rtop.cnt;
             const KernArgsP ce = cold_args();
             const size_t list = (size_t)item * ce->bt.lpi + wave;

@@ -5,8 +5,9 @@
 //   scan_win.h     scan_win_kernel (its own translation unit, scan_win.hip): sparse queries of <= 8 terms of comparable length, k <= 256
 //                  (k <= 64 beyond five terms) -- the document-window formulation, the dominant kernel of C3
 //   scan_range.h   scan_range_kernel: every other sparse query of <= 16 terms, k <= 256; the one-launch route of vbm25_search_batch (C2)
-//   scan_dense.h   scan_dense_kernel: queries with many postings per document (Zipf head terms; C5), <= 16 terms, k <= 256
-//   scan_many.h    scan_many_kernel: up to 1024 terms, 256 < k <= 1024, items the others gave up (exhaustive)
+//   scan_dense.h   scan_dense_kernel: queries with many postings per document (Zipf head terms; C5), <= 16 terms, k <= 256 (a register top-k
+//                  per wave); with the switch dense_big also 256 < k <= 1024 (one survivor list per workgroup in LDS; dense_list_lane.h)
+//   scan_many.h    scan_many_kernel: up to 1024 terms, 256 < k <= 1024 (but the dense queries under dense_big), items the others gave up (exhaustive)
 //   merge.h        merge_kernel: per-item top-k lists -> hits with payloads
 //   decode.h / block_fetch.h / topk_lds.h / topk_reg.h / device_types.h   shared pieces
 // This file: vbm25_batch and nothing else -- create, routing, set_queries, the run_* routes, the growing segment's part of a run, fetch,
@@ -138,21 +139,25 @@ static int vbm25_batch_create_impl(vbm25_index *ix, uint32_t max_queries, uint32
     bt->h_dense.resize(max_queries);
     bt->h_postings.resize(max_queries);
     // Routing by k: k <= 256 -- sparse queries of <= 16 terms: scan_range_kernel, dense ones: scan_dense_kernel, the rest and
-    // whatever those two give up: scan_many_kernel; 256 < k <= 1024: scan_many_kernel (LDS top-k); above: the exhaustive path
+    // whatever those two give up: scan_many_kernel; 256 < k <= 1024: scan_many_kernel (LDS top-k) -- with the switch dense_big, on an
+    // index of at least dense_big_min_docs documents, the dense queries of <= 16 terms take scan_dense_kernel<1024> (a survivor list in
+    // LDS; lpi stays 1) and hand what they give up to scan_many_kernel; above: the exhaustive path
     bt->use_range = k <= (uint32_t)REG_K;
     bt->lpi = bt->use_range ? (uint32_t)RNW : 1u;
     // (scan_dense_kernel reads post_rel16 unconditionally: an index made without the plane sends its dense queries to scan_many_kernel)
     bt->use_dense = bt->use_range && k <= (uint32_t)D_KMAX && bt->tune.dense != 0 && ix->post_rel16.p != nullptr;
     bt->target_items = bt->use_range ? std::max(256u, bt->tune.range_items) : TARGET_ITEMS;
     bt->min_chunk = bt->use_range ? std::max(128u, bt->tune.range_min_chunk) : MIN_CHUNK_POSTINGS;
-    bt->max_items = max_queries + bt->target_items + (bt->use_dense ? std::max(256u, bt->tune.dense_items) : 0u);
+    bt->dense_big = !bt->use_range && k <= (uint32_t)D_BIG_K && bt->tune.dense != 0 && bt->tune.dense_big != 0 &&
+                    ix->post_rel16.p != nullptr && ix->n_docs >= bt->tune.dense_big_min_docs;
+    bt->max_items = max_queries + bt->target_items + (bt->use_dense || bt->dense_big ? std::max(256u, bt->tune.dense_items) : 0u);
     // scan_win_kernel's items are one wave's work each (a few per query): room for them
     if (bt->use_range && k <= scan_win_max_k(1) && bt->tune.win && !ix->term_win_host.empty())
         bt->max_items = std::max(bt->max_items, std::max(8192u, 8u * max_queries));
     int rc = 0;
     if (k > 1024) {  // exhaustive path: query buffers, results and an accumulator per document
         bt->bigk = true;
-        bt->use_range = bt->use_dense = false;
+        bt->use_range = bt->use_dense = bt->dense_big = false;
         const size_t n = ix->n_docs ? ix->n_docs : 1;
         (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bt->bk_tmp_bytes, (const unsigned long long *)nullptr,
                                                      (unsigned long long *)nullptr, (const uint32_t *)nullptr,
@@ -513,6 +518,7 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
             if (!dense[q] && valid <= 16u) plan.range_mt = std::max(plan.range_mt, valid);
         } else {
             many = true;
+            plan.has_dense |= bt->dense_big && dense[q] && valid <= (uint32_t)D_T;  // (256 < k <= 1024: scan_dense_kernel<1024>)
         }
         if (valid > MAX_TERMS)
             return set_error(VBM25_ERR_UNSUPPORTED, "query %u has %u indexed terms; the GPU path handles up to %d", q, valid, MAX_TERMS);
@@ -833,13 +839,23 @@ static int run_plan_free(vbm25_batch *bt, hipStream_t st, DevBatch db) {
 }
 
 // plan_kernel makes the work items; the sparse, dense and many-term kernels scan them; merge_kernel merges every query's lists
-static int run_general(vbm25_batch *bt, hipStream_t st, const DevBatch &db) {
+static int run_general(vbm25_batch *bt, hipStream_t st, const DevBatch &db_in) {
     const QueryPlan &plan = bt->plan;
     const DevIndex &ix = bt->index->dev;
     const bool range = bt->use_range;
+    // 256 < k <= 1024 with dense queries for scan_dense_kernel<1024>: the kernels see the dense kernel on and a term-count class of <= D_T
+    // terms that is its alone -- plan_kernel marks every other item ITEM_OTHER, so scan_many_kernel takes those and, of the dense
+    // kernel's, only the ones it gave up
+    const bool big = bt->dense_big && plan.has_dense;
+    DevBatch dbb = db_in;
+    if (big) {
+        dbb.dense_on = 1;
+        dbb.range_max_terms = (uint32_t)D_T;
+    }
+    const DevBatch &db = dbb;
     bt->state_clean = false;
-    if (range) HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->nq, st));
-    plan_kernel<<<1, PLAN_WG, 0, st>>>(ix, db, bt->max_items, bt->target_items, bt->min_chunk, plan.dense_c);
+    if (range || big) HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->nq, st));
+    plan_kernel<<<1, PLAN_WG, 0, st>>>(ix, db, bt->max_items, bt->target_items, bt->min_chunk, plan.dense_c, big ? ITEM_OTHER : 0u);
     hipEvent_t e1;
     if (int rc = take_events(bt, st, e1)) return rc;
     const uint32_t grid = std::min<uint32_t>(bt->max_items, TARGET_ITEMS);
@@ -853,8 +869,10 @@ static int run_general(vbm25_batch *bt, hipStream_t st, const DevBatch &db) {
         }
         if constexpr (KM <= D_KMAX) {
             if (plan.has_dense) scan_dense_kernel<KM><<<plan.dense_grid, DWG, 0, st>>>(ix, db);
+        } else {
+            if (big) scan_dense_kernel<D_BIG_K><<<plan.dense_grid, DWG, 0, st>>>(ix, db);
         }
-        // many-term queries, every query of 256 < k <= 1024, and items the first-choice kernel gave up on (empty launch: 5 us)
+        // many-term queries, every query of 256 < k <= 1024 (but the dense kernel's), and items the first-choice kernel gave up on (empty launch: 5 us)
         scan_many_kernel<decltype(kmax)::value><<<grid, WG, 0, st>>>(ix, db);
         if (bt->timing) HIP_TRY(hipEventRecord(e1, st));  // the events bracket every posting-scan kernel of the step
         merge_kernel<decltype(kmax)::value><<<bt->nq, 64, 0, st>>>(ix, db);
@@ -1317,7 +1335,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
-// bigk_item_win, dbg; cast_wave_max and cast_group_max (read
+// bigk_item_win, dense_big, dense_big_min_docs, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
@@ -1357,6 +1375,8 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "bigk_cand_max") g_tune.bigk_cand_max = (uint64_t)std::min<long long>(std::max(0ll, value), 1ll << 30);
     else if (n == "bigk_chunk_cand") g_tune.bigk_chunk_cand = (uint64_t)std::min<long long>(std::max(1ll, value), 1ll << 30);
     else if (n == "bigk_item_win") g_tune.bigk_item_win = (uint32_t)std::min<long long>(std::max(0ll, value), 1ll << 20);
+    else if (n == "dense_big") g_tune.dense_big = value != 0;
+    else if (n == "dense_big_min_docs") g_tune.dense_big_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "id16_max_blocks") g_tune.id16_max_blocks = (uint32_t)std::min<long long>(std::max(2ll, value), 0x00ffffffll);
     else if (n == "cast_wave_max" || n == "cast_group_max" || n == "cast_pack" || n == "cast_grid") {  // (the cast's class bounds and the caster's kernel choice and grid cap: cast.hip keeps and reads them)
         if (int rc = vbm25::cast_tuning_set(name, value)) return rc;
@@ -1417,6 +1437,23 @@ int vbm25_batch_debug_counts(vbm25_batch *bt, uint32_t *n_items, uint32_t *n_fai
     return VBM25_OK;
 }
 
+// tool aid (not declared in include/vbm25.h): why scan_dense_kernel<1024> gave items of the last run on the general route up --
+// out[0] the task list of a window was full, out[1] the survivor list overflowed between two cuts, out[2] the re-scoring cap
+int vbm25_batch_debug_given_up(vbm25_batch *bt, uint32_t *out3) {
+    if (!bt || !out3) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    out3[0] = out3[1] = out3[2] = 0;
+    if (bt->bigk || bt->plan.route != Route::General) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, bt->n_items.p, 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> f(std::min(n, bt->max_items));
+    if (!f.empty()) HIP_TRY(hipMemcpy(f.data(), bt->item_failed.p, 4ull * f.size(), hipMemcpyDeviceToHost));
+    for (uint32_t x : f)
+        if ((x & ~7u) == 0x140u && (x & 7u)) out3[x & 4u ? 2 : x & 2u ? 1 : 0]++;
+    return VBM25_OK;
+}
+
 // test aid (not declared in include/vbm25.h): the route the current queries take -- 0 general (plan_kernel), 1 one launch,
 // 2 plan-free scan_range_kernel, 3 scan_win_kernel, 4 exhaustive k > 1024
 int vbm25_batch_debug_route(vbm25_batch *bt) {
@@ -1427,7 +1464,8 @@ int vbm25_batch_debug_route(vbm25_batch *bt) {
 // test / bench aid (not declared in include/vbm25.h): which kernel the current queries' work goes to.  out[0..2] = queries the host
 // classed sparse (scan_win_kernel / scan_range_kernel), dense (scan_dense_kernel: postings >= 0.1 n_docs), many-term (> 16 indexed
 // terms: scan_many_kernel); out[3..5] = work items of the last run on the general route by the same classes (0 on the routes whose
-// kernels make their items themselves: all of them are the sparse kernel's)
+// kernels make their items themselves: all of them are the sparse kernel's).  256 < k <= 1024 with scan_dense_kernel<1024> in the run
+// (dense_big): out[4] = the items that went to it, out[5] = every other item (ITEM_OTHER: scan_many_kernel's), out[3] = 0.
 int vbm25_batch_debug_routes(vbm25_batch *bt, uint32_t *out6) {
     if (!bt || !out6) return set_error(VBM25_ERR_INVALID, "NULL argument");
     for (int i = 0; i < 6; ++i) out6[i] = 0;
