@@ -527,6 +527,16 @@ class Batch:
         check(f(self.h, out))
         return tuple(int(x) for x in out)
 
+    def debug_sparse_big(self):
+        """test / tool aid: what scan_sparse_big_kernel did in the last run -- (items it took, items it gave up for a term frequency
+        wider than a byte, tiles on the slow path, cuts of the survivor list); zeros when the run did not launch it"""
+        f = lib().vbm25_batch_debug_sparse_big
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_uint32 * 4)()
+        check(f(self.h, out))
+        return tuple(int(x) for x in out)
+
     def debug_route(self):
         """test aid: 0 general route (plan_kernel), 1 one launch, 2 plan-free scan_range_kernel, 3 scan_win_kernel, 4 exhaustive"""
         f = lib().vbm25_batch_debug_route
@@ -1252,6 +1262,8 @@ def set_tuning(name, value):
     range_min_chunk, range_grid, dense_grid, fused_items, arith, win, win_force, win_items, win_grid, win_skew, win_guided,
     dense_big (256 < k <= 1024: dense queries of <= 16 terms take scan_dense_kernel's survivor-list instantiation, the default; 0 leaves
     every query of such a batch to scan_many_kernel) and dense_big_min_docs (the smallest index that route takes, 65536 documents),
+    sparse_big (256 < k <= 1024: sparse queries of 1 .. 16 terms that all have a window table take scan_sparse_big_kernel) and
+    sparse_big_min_docs (the smallest index that route takes, 65536 documents),
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
     and cast_group_max (the class bounds of Documents.cast and Caster.submit, read at the start of each; 0 turns the class off),

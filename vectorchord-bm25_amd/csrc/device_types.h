@@ -58,11 +58,13 @@ __device__ __forceinline__ bool rel16_block(uint32_t min_doc, uint32_t max_doc, 
 __device__ __forceinline__ bool tfn_block(uint32_t w) { return (w & 0xffu) == 128u && ((w >> 16) & 0xffu) <= 7u; }
 
 struct Item {
-    uint32_t q, doc_lo, doc_hi, m;  // m = number of indexed terms of query q | ITEM_DENSE
+    uint32_t q, doc_lo, doc_hi, m;  // m = number of indexed terms of query q | ITEM_DENSE | ITEM_OTHER | ITEM_SPARSE_BIG
 };
 constexpr uint32_t ITEM_DENSE = 0x80000000u;  // postings per document high: dense-window path
 constexpr uint32_t ITEM_OTHER = 0x40000000u;  // 256 < k <= 1024 with the dense-window kernel on: an item that is NOT that kernel's (a sparse query,
                                               // more than D_T terms) -- its term count reads as "many" and scan_many_kernel takes it
+constexpr uint32_t ITEM_SPARSE_BIG = 0x20000000u;  // 256 < k <= 1024: an item of a sparse query the host gave to scan_sparse_big_kernel; scan_many_kernel
+                                                   // takes it only when that kernel gave it up (item_failed)
 
 struct DevBatch {
     const uint32_t *term_ids;

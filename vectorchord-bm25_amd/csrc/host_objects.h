@@ -72,6 +72,10 @@ struct Tuning {
                                    // 0: every query of such a batch takes scan_many_kernel.  On: profiles/dense_big_cost.json (C5, k = 1000: 270 -> 67 ms)
     uint32_t dense_big_min_docs = 65536;  // ... on an index of at least this many documents (four full windows: below, nothing is skipped
                                    // before the threshold is warm)
+    int sparse_big = 1;            // 256 < k <= 1024: sparse queries of 1 .. 16 indexed terms, every one with a window table, take
+                                   // scan_sparse_big_kernel (the rank-addressed window scan); 0: scan_many_kernel.  On: profiles/sparse_big_cost.json
+                                   // (C3, 1024 queries, k = 1000: 103.8 -> 20.6 ms, a gain at every k of the table)
+    uint32_t sparse_big_min_docs = 65536;  // ... on an index of at least this many documents
     uint32_t generation = 0;       // bumped by every vbm25_tuning_set / reset: vbm25_search_batch's batch object is rebuilt when it is stale
 };
 // the switches of the moment (search.hip owns them and their lock: vbm25_tuning_set / _reset write, this copies)
@@ -87,17 +91,18 @@ enum class Route {
 };
 
 // The staged descriptors, one block in pinned memory (pin_in) and on the device (qin): term ids at 0, then the byte offsets of the
-// query offsets, the dense flags (padded to 8), the host's item order, the id16 block starts and the filter selectors (stage_sel), and
+// query offsets, the dense flags and the sparse_big flags (together padded to 8), the host's item order, the id16 block starts and the filter selectors (stage_sel), and
 // the end of the block
 struct StagedLayout {
     size_t off = 0, dense = 0, order = 0, id16 = 0, end = 0;
     size_t sel = 0;  // the filter selectors of a staged filtered query set (nq words in front of `end`), 0: none staged
+    size_t sbig(uint32_t nq) const { return dense + nq; }  // per query: its items are scan_sparse_big_kernel's (256 < k <= 1024)
 };
 inline StagedLayout staged_layout(uint32_t nq, uint32_t n_term_pos, size_t n_order, bool id16) {
     StagedLayout L;
     L.off = 4ull * n_term_pos;
     L.dense = L.off + 4ull * (nq + 1);
-    L.order = L.dense + ((size_t(nq) + 7) & ~size_t(7));
+    L.order = L.dense + ((2 * size_t(nq) + 7) & ~size_t(7));  // (behind the dense flags: the nq sparse_big flags, sbig())
     L.id16 = L.order + 4 * n_order;
     L.end = L.id16 + (id16 ? 4ull * n_term_pos : 0);
     return L;
@@ -117,6 +122,7 @@ struct QueryPlan {
     uint32_t q_stride = 0;        // != 0: every query has this many terms
     uint32_t range_mt = 0;        // the most indexed terms of a sparse query of <= 16 (0: none, or k > REG_K)
     bool has_dense = false;       // some query takes scan_dense_kernel
+    bool has_sparse_big = false;  // some query takes scan_sparse_big_kernel
     bool need_many = true;        // some query has items for scan_many_kernel (more than 16 terms, 256 < k, dense without the dense kernel)
     uint32_t dense_c = 0;         // items per dense query (0: chunks by postings, as the other queries)
     uint32_t range_grid = R_GRID, dense_grid = D_GRID;
@@ -233,7 +239,7 @@ struct vbm25_batch {
     int device = 0;  // the index's device ordinal: the batch can be destroyed after its index
     uint32_t max_queries = 0, max_terms = 0, k = 0, nq = 0, max_items = 0;
     vbm25::DeviceBuffer term_ids, q_off, items, n_items, q_item_base, theta, res_score, res_doc, res_cnt,
-        hits, n_hits, error_flag, prof, q_dense, item_failed, item_order, work_ctr, hist, fused_state, dbg, fail_any, q_failed, theta_last;
+        hits, n_hits, error_flag, prof, q_dense, q_sparse_big, sb_stats, item_failed, item_order, work_ctr, hist, fused_state, dbg, fail_any, q_failed, theta_last;
     bool bigk = false;            // k > 1024: exhaustive path, one query at a time
     vbm25::DeviceBuffer bk_acc, bk_keys, bk_iota, bk_docs, bk_tmp;
     size_t bk_tmp_bytes = 0;
@@ -255,6 +261,7 @@ struct vbm25_batch {
     size_t gr_tmp_bytes = 0;
     uint32_t gr_n = 0;  // growing documents the k > 1024 scratch holds
     std::vector<uint8_t> h_dense;          // per query: dense (scratch of set_queries, sized once)
+    std::vector<uint8_t> h_sparse_big;     // per query: takes scan_sparse_big_kernel (sized once, when the batch's route exists)
     std::vector<unsigned long long> h_postings;
     std::vector<uint32_t> h_order, h_order_q;  // set_queries: the longest-first item order of the routes without plan_kernel
     vbm25::Tuning tune;                  // the switches of the moment the batch was created
@@ -263,6 +270,8 @@ struct vbm25_batch {
     uint32_t lpi = 1;             // result lists per work item
     bool use_dense = false;       // dense queries of <= D_T terms take scan_dense_kernel
     bool dense_big = false;       // 256 < k <= 1024: they take its survivor-list instantiation (one list per item: lpi stays 1)
+    bool sparse_big = false;      // 256 < k <= 1024: eligible sparse queries take scan_sparse_big_kernel (switch, index size, planes)
+    bool sb_ran = false;          // ... the last run launched it (vbm25_batch_debug_sparse_big)
     vbm25::QueryPlan plan;              // the current queries' route (set_queries)
     // an index without the post_id16 plane: the batch's scratch plane (the low 16 bits of the ids of the current queries' terms, made by
     // decode_id16_kernel ahead of every scan_win_kernel launch) and, per term position, the term's first 256-byte block in it

@@ -36,8 +36,11 @@ __device__ __forceinline__ unsigned long long plan_incl_scan(unsigned long long 
 // dense_c != 0: every dense query (q_dense) is cut into dense_c items of equal document counts -- the dense-window kernel's
 // work per item goes with its windows, not with its postings -- and does not count towards the other queries' chunk size.
 // other_mark: 0, or ITEM_OTHER (below, where the items are written).
+// q_sparse_big: NULL, or per query 1 = its items are scan_sparse_big_kernel's (host decided): they get the mark ITEM_SPARSE_BIG and
+// nothing else about them changes; sb_stats: that kernel's four counters of the run, zeroed here.
 __global__ void __launch_bounds__(PLAN_WG) plan_kernel(DevIndex ix, DevBatch bt, uint32_t max_items,
-                                                       uint32_t target_items, uint32_t min_chunk, uint32_t dense_c, uint32_t other_mark) {
+                                                       uint32_t target_items, uint32_t min_chunk, uint32_t dense_c, uint32_t other_mark,
+                                                       const uint8_t *q_sparse_big, uint32_t *sb_stats) {
     __shared__ unsigned long long s_wave[PLAN_WG / 64];
     __shared__ uint32_t s_bucket[PLAN_BUCKETS];
     const uint32_t tid = threadIdx.x;
@@ -58,6 +61,7 @@ __global__ void __launch_bounds__(PLAN_WG) plan_kernel(DevIndex ix, DevBatch bt,
         bt.work_ctr[1] = 0;
         *bt.fail_any = 0;
     }
+    if (sb_stats && tid < 4u) sb_stats[tid] = 0;
 
     auto postings_of = [&](uint32_t q) {
         unsigned long long t = 0;
@@ -130,6 +134,7 @@ __global__ void __launch_bounds__(PLAN_WG) plan_kernel(DevIndex ix, DevBatch bt,
         // query's of at most range_max_terms terms is marked as its)
         if (other_mark && !(bt.q_dense[q] && nterms <= bt.range_max_terms)) nterms |= other_mark;
         if (bt.q_dense[q]) nterms |= ITEM_DENSE;
+        if (q_sparse_big && q_sparse_big[q]) nterms |= ITEM_SPARSE_BIG;
         bt.q_item_base[q] = min(base, max_items);
         const uint32_t pos = c ? atomicAdd(&s_bucket[bucket_of(one ? own_postings : postings_of(q), c)], c) : 0u;
         for (uint32_t i = 0; i < c && base + i < max_items; ++i) {

@@ -1,5 +1,5 @@
-// scan_many.h -- scan_many_kernel: more than 16 terms (up to MAX_TERMS), every query of 256 < k <= 1024, dense queries when
-// scan_dense_kernel is off, and the items the first-choice kernels gave up.  Exhaustive: term-phased exact f64 accumulation
+// scan_many.h -- scan_many_kernel: more than 16 terms (up to MAX_TERMS), every query of 256 < k <= 1024 that neither scan_dense_kernel<1024>
+// nor scan_sparse_big_kernel takes, dense queries when scan_dense_kernel is off, and the items the first-choice kernels gave up.  Exhaustive: term-phased exact f64 accumulation
 // in dense doc windows or an LDS hash, LDS top-k, the query's shared threshold.
 // Included by search.hip.
 #ifndef VBM25_SCAN_MANY_H
@@ -38,9 +38,13 @@ __global__ void __launch_bounds__(WG) scan_many_kernel(DevIndex ix, DevBatch bt)
         const Item it = bt.items[item];
         const uint32_t others_max = bt.range_max_terms;  // up to that many terms: the other kernels' (0: everything is this kernel's)
         const uint32_t mt_item = bt.dense_on ? (it.m & ~ITEM_DENSE) : it.m;  // dense items: scan_dense_kernel's
-        const bool failed = mt_item <= others_max && bt.item_failed[item] != 0;
-        if (mt_item <= others_max && !failed) continue;
-        const bool force_dense = failed || (it.m & ITEM_DENSE) != 0;
+        // (ITEM_SPARSE_BIG: scan_sparse_big_kernel's item, whatever its other marks say; redone here -- in the mode it would have had
+        // without that kernel -- when it was given up)
+        const bool sparse_big = (it.m & ITEM_SPARSE_BIG) != 0;
+        const bool first_choice = sparse_big || mt_item <= others_max;
+        const bool failed = first_choice && bt.item_failed[item] != 0;
+        if (first_choice && !failed) continue;
+        const bool force_dense = (failed && !sparse_big) || (it.m & ITEM_DENSE) != 0;
         const uint32_t q = it.q, clo = it.doc_lo, chi = it.doc_hi;
         __syncthreads();  // previous item fully done with LDS
         if (tid == 0) {

@@ -7,7 +7,10 @@
 //   scan_range.h   scan_range_kernel: every other sparse query of <= 16 terms, k <= 256; the one-launch route of vbm25_search_batch (C2)
 //   scan_dense.h   scan_dense_kernel: queries with many postings per document (Zipf head terms; C5), <= 16 terms, k <= 256 (a register top-k
 //                  per wave); with the switch dense_big also 256 < k <= 1024 (one survivor list per workgroup in LDS; dense_list_lane.h)
-//   scan_many.h    scan_many_kernel: up to 1024 terms, 256 < k <= 1024 (but the dense queries under dense_big), items the others gave up (exhaustive)
+//   scan_sparse_big.h   scan_sparse_big_kernel (its own translation unit, scan_sparse_big.hip): with the switch sparse_big the sparse queries of
+//                  1 .. 16 terms at 256 < k <= 1024, every term with a window table -- the rank-addressed window scan (sparse_big_lane.h)
+//   scan_many.h    scan_many_kernel: up to 1024 terms, 256 < k <= 1024 (but the dense queries under dense_big and the sparse ones under
+//                  sparse_big), items the others gave up (exhaustive)
 //   merge.h        merge_kernel: per-item top-k lists -> hits with payloads
 //   decode.h / block_fetch.h / topk_lds.h / topk_reg.h / device_types.h   shared pieces
 // This file: vbm25_batch and nothing else -- create, routing, set_queries, the run_* routes, the growing segment's part of a run, fetch,
@@ -40,6 +43,7 @@
 #include "scan_range.h"
 #include "scan_win_launch.h"
 #include "scan_dense.h"
+#include "scan_sparse_big_launch.h"
 #include "scan_many.h"
 #include "merge.h"
 #include "growing.h"
@@ -150,6 +154,11 @@ static int vbm25_batch_create_impl(vbm25_index *ix, uint32_t max_queries, uint32
     bt->min_chunk = bt->use_range ? std::max(128u, bt->tune.range_min_chunk) : MIN_CHUNK_POSTINGS;
     bt->dense_big = !bt->use_range && k <= (uint32_t)D_BIG_K && bt->tune.dense != 0 && bt->tune.dense_big != 0 &&
                     ix->post_rel16.p != nullptr && ix->n_docs >= bt->tune.dense_big_min_docs;
+    // ... and, with the switch sparse_big on an index of at least sparse_big_min_docs documents that holds the window planes, the sparse
+    // queries of 1 .. 16 indexed terms that all have a window table take scan_sparse_big_kernel (decided per query in set_queries)
+    bt->sparse_big = !bt->use_range && k <= (uint32_t)D_BIG_K && bt->tune.sparse_big != 0 && ix->n_docs >= bt->tune.sparse_big_min_docs &&
+                     ix->post_id16.p != nullptr && ix->win_off.p != nullptr && ix->post_tfn.p != nullptr && !ix->term_win_host.empty();
+    if (bt->sparse_big) bt->h_sparse_big.resize(max_queries);
     bt->max_items = max_queries + bt->target_items + (bt->use_dense || bt->dense_big ? std::max(256u, bt->tune.dense_items) : 0u);
     // scan_win_kernel's items are one wave's work each (a few per query): room for them
     if (bt->use_range && k <= scan_win_max_k(1) && bt->tune.win && !ix->term_win_host.empty())
@@ -157,7 +166,7 @@ static int vbm25_batch_create_impl(vbm25_index *ix, uint32_t max_queries, uint32
     int rc = 0;
     if (k > 1024) {  // exhaustive path: query buffers, results and an accumulator per document
         bt->bigk = true;
-        bt->use_range = bt->use_dense = bt->dense_big = false;
+        bt->use_range = bt->use_dense = bt->dense_big = bt->sparse_big = false;
         const size_t n = ix->n_docs ? ix->n_docs : 1;
         (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bt->bk_tmp_bytes, (const unsigned long long *)nullptr,
                                                      (unsigned long long *)nullptr, (const uint32_t *)nullptr,
@@ -184,7 +193,8 @@ static int vbm25_batch_create_impl(vbm25_index *ix, uint32_t max_queries, uint32
         (rc = bt->hits.alloc(sizeof(vbm25_hit) * size_t(max_queries) * k)) ||
         (rc = bt->n_hits.alloc(4ull * max_queries)) || (rc = bt->error_flag.alloc(4)) ||
         (rc = bt->q_dense.alloc(max_queries)) ||
-        (rc = bt->qin.alloc(8ull * max_total_terms + 4ull * (max_queries + 1) + max_queries + 8 + 4ull * bt->max_items + 4ull * max_queries + 64)) ||
+        (bt->sparse_big && ((rc = bt->q_sparse_big.alloc(max_queries)) || (rc = bt->sb_stats.alloc(16)))) ||
+        (rc = bt->qin.alloc(8ull * max_total_terms + 4ull * (max_queries + 1) + 2ull * max_queries + 8 + 4ull * bt->max_items + 4ull * max_queries + 64)) ||
         (rc = bt->id16_fb.alloc(4ull * max_total_terms)) ||
         (rc = bt->item_failed.alloc(4ull * bt->max_items)) || (rc = bt->item_order.alloc(4ull * bt->max_items)) || (rc = bt->work_ctr.alloc(8)) ||
         (rc = bt->hist.alloc(4ull * CUR_HB * max_queries)) || (rc = bt->fused_state.alloc(4ull * (max_queries + 1))) ||
@@ -461,6 +471,7 @@ static int commit_queries(vbm25_batch *bt, const uint32_t *term_ids, const uint3
             if (L.off) std::memcpy(bt->pin_in, term_ids, L.off);
             std::memcpy(bt->pin_in + L.off, q_off, L.dense - L.off);
             if (nq) std::memcpy(bt->pin_in + L.dense, bt->h_dense.data(), nq);
+            if (nq && bt->sparse_big) std::memcpy(bt->pin_in + L.sbig(nq), bt->h_sparse_big.data(), nq);
             if (L.id16 > L.order) std::memcpy(bt->pin_in + L.order, bt->h_order.data(), L.id16 - L.order);
             if (L.sel) {
                 if (L.sel > L.id16) std::memcpy(bt->pin_in + L.id16, bt->h_id16_fb.data(), L.sel - L.id16);
@@ -473,6 +484,7 @@ static int commit_queries(vbm25_batch *bt, const uint32_t *term_ids, const uint3
             if (q_off[nq]) HIP_TRY(hipMemcpy(bt->term_ids.p, term_ids, 4ull * q_off[nq], hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(bt->q_off.p, q_off, 4ull * (nq + 1), hipMemcpyHostToDevice));
             if (nq) HIP_TRY(hipMemcpy(bt->q_dense.p, bt->h_dense.data(), nq, hipMemcpyHostToDevice));
+            if (nq && bt->sparse_big) HIP_TRY(hipMemcpy(bt->q_sparse_big.p, bt->h_sparse_big.data(), nq, hipMemcpyHostToDevice));
         }
         bt->win_nofuse = false;
     }
@@ -519,6 +531,13 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
         } else {
             many = true;
             plan.has_dense |= bt->dense_big && dense[q] && valid <= (uint32_t)D_T;  // (256 < k <= 1024: scan_dense_kernel<1024>)
+            if (bt->sparse_big) {  // a sparse query of 1 .. 16 indexed terms, every one with a window table: scan_sparse_big_kernel
+                bool ok = !dense[q] && valid >= 1u && valid <= scan_sparse_big_max_terms();
+                for (uint32_t p = q_off[q]; p < q_off[q + 1] && ok; ++p)
+                    if (term_ids[p] < bt->index->n_terms) ok = bt->index->term_win_host[term_ids[p]] != UINT32_MAX;
+                bt->h_sparse_big[q] = ok ? 1 : 0;
+                plan.has_sparse_big |= ok;
+            }
         }
         if (valid > MAX_TERMS)
             return set_error(VBM25_ERR_UNSUPPORTED, "query %u has %u indexed terms; the GPU path handles up to %d", q, valid, MAX_TERMS);
@@ -855,7 +874,14 @@ static int run_general(vbm25_batch *bt, hipStream_t st, const DevBatch &db_in) {
     const DevBatch &db = dbb;
     bt->state_clean = false;
     if (range || big) HIP_TRY(hipMemsetAsync(bt->hist.p, 0, 4ull * CUR_HB * bt->nq, st));
-    plan_kernel<<<1, PLAN_WG, 0, st>>>(ix, db, bt->max_items, bt->target_items, bt->min_chunk, plan.dense_c, big ? ITEM_OTHER : 0u);
+    // ... and with sparse queries for scan_sparse_big_kernel: plan_kernel adds ITEM_SPARSE_BIG to their items' marks (nothing else about
+    // the items changes), that kernel takes them, scan_many_kernel the ones it gave up.  A batch without such a query launches nothing new.
+    const bool sbig = bt->sparse_big && plan.has_sparse_big;
+    const uint8_t *q_sbig = nullptr;
+    if (sbig) q_sbig = bt->qin_live ? bt->qin.as<uint8_t>() + plan.staged.sbig(bt->nq) : bt->q_sparse_big.as<uint8_t>();
+    bt->sb_ran = sbig;
+    plan_kernel<<<1, PLAN_WG, 0, st>>>(ix, db, bt->max_items, bt->target_items, bt->min_chunk, plan.dense_c, big ? ITEM_OTHER : 0u, q_sbig,
+                                       sbig ? bt->sb_stats.as<uint32_t>() : nullptr);
     hipEvent_t e1;
     if (int rc = take_events(bt, st, e1)) return rc;
     const uint32_t grid = std::min<uint32_t>(bt->max_items, TARGET_ITEMS);
@@ -871,6 +897,9 @@ static int run_general(vbm25_batch *bt, hipStream_t st, const DevBatch &db_in) {
             if (plan.has_dense) scan_dense_kernel<KM><<<plan.dense_grid, DWG, 0, st>>>(ix, db);
         } else {
             if (big) scan_dense_kernel<D_BIG_K><<<plan.dense_grid, DWG, 0, st>>>(ix, db);
+            if (sbig)
+                if (scan_sparse_big_launch(ix, db, bt->sb_stats.as<uint32_t>(), std::min(plan.range_grid, scan_sparse_big_grid()), st) != hipSuccess)
+                    return set_error(VBM25_ERR_DEVICE, "scan_sparse_big_kernel: launch failed");
         }
         // many-term queries, every query of 256 < k <= 1024 (but the dense kernel's), and items the first-choice kernel gave up on (empty launch: 5 us)
         scan_many_kernel<decltype(kmax)::value><<<grid, WG, 0, st>>>(ix, db);
@@ -1335,7 +1364,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
-// bigk_item_win, dense_big, dense_big_min_docs, dbg; cast_wave_max and cast_group_max (read
+// bigk_item_win, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
@@ -1377,6 +1406,8 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "bigk_item_win") g_tune.bigk_item_win = (uint32_t)std::min<long long>(std::max(0ll, value), 1ll << 20);
     else if (n == "dense_big") g_tune.dense_big = value != 0;
     else if (n == "dense_big_min_docs") g_tune.dense_big_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
+    else if (n == "sparse_big") g_tune.sparse_big = value != 0;
+    else if (n == "sparse_big_min_docs") g_tune.sparse_big_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "id16_max_blocks") g_tune.id16_max_blocks = (uint32_t)std::min<long long>(std::max(2ll, value), 0x00ffffffll);
     else if (n == "cast_wave_max" || n == "cast_group_max" || n == "cast_pack" || n == "cast_grid") {  // (the cast's class bounds and the caster's kernel choice and grid cap: cast.hip keeps and reads them)
         if (int rc = vbm25::cast_tuning_set(name, value)) return rc;
@@ -1465,7 +1496,8 @@ int vbm25_batch_debug_route(vbm25_batch *bt) {
 // classed sparse (scan_win_kernel / scan_range_kernel), dense (scan_dense_kernel: postings >= 0.1 n_docs), many-term (> 16 indexed
 // terms: scan_many_kernel); out[3..5] = work items of the last run on the general route by the same classes (0 on the routes whose
 // kernels make their items themselves: all of them are the sparse kernel's).  256 < k <= 1024 with scan_dense_kernel<1024> in the run
-// (dense_big): out[4] = the items that went to it, out[5] = every other item (ITEM_OTHER: scan_many_kernel's), out[3] = 0.
+// (dense_big): out[4] = the items that went to it, out[5] = every other item (ITEM_OTHER: scan_many_kernel's), out[3] = 0.  The items
+// of scan_sparse_big_kernel (sparse_big) are among out[5]; vbm25_batch_debug_sparse_big counts them.
 int vbm25_batch_debug_routes(vbm25_batch *bt, uint32_t *out6) {
     if (!bt || !out6) return set_error(VBM25_ERR_INVALID, "NULL argument");
     for (int i = 0; i < 6; ++i) out6[i] = 0;
@@ -1484,6 +1516,19 @@ int vbm25_batch_debug_routes(vbm25_batch *bt, uint32_t *out6) {
             out6[3 + (m > 16u ? 2 : (it.m & ITEM_DENSE) ? 1 : 0)]++;
         }
     }
+    return VBM25_OK;
+}
+
+// test / tool aid (not declared in include/vbm25.h): what scan_sparse_big_kernel did in the last run -- out[0] the items it took, out[1] the
+// items it gave up for a term frequency wider than a byte (scan_many_kernel redid them), out[2] the tiles on the slow path (not a whole
+// window), out[3] the cuts of the survivor list.  Zeros when the run did not launch it.
+int vbm25_batch_debug_sparse_big(vbm25_batch *bt, uint32_t *out4) {
+    if (!bt || !out4) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (bt->bigk || !bt->sb_ran || !bt->sb_stats.p) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    HIP_TRY(hipMemcpy(out4, bt->sb_stats.p, 16, hipMemcpyDeviceToHost));
     return VBM25_OK;
 }
 
