@@ -537,6 +537,16 @@ class Batch:
         check(f(self.h, out))
         return tuple(int(x) for x in out)
 
+    def debug_bigk_win(self):
+        """test / tool aid: the sparse path of the last k > 1024 run -- (work items bigk_scan_win_kernel took, work items
+        bigk_scan_kernel took, the window scan's tiles on the slow path, wide term frequencies it decoded); zeros at k <= 1024"""
+        f = lib().vbm25_batch_debug_bigk_win
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_uint32 * 4)()
+        check(f(self.h, out))
+        return tuple(int(x) for x in out)
+
     def debug_route(self):
         """test aid: 0 general route (plan_kernel), 1 one launch, 2 plan-free scan_range_kernel, 3 scan_win_kernel, 4 exhaustive"""
         f = lib().vbm25_batch_debug_route
@@ -1264,6 +1274,9 @@ def set_tuning(name, value):
     every query of such a batch to scan_many_kernel) and dense_big_min_docs (the smallest index that route takes, 65536 documents),
     sparse_big (256 < k <= 1024: sparse queries of 1 .. 16 terms that all have a window table take scan_sparse_big_kernel) and
     sparse_big_min_docs (the smallest index that route takes, 65536 documents),
+    bigk_win (k > 1024: sparse queries of 1 .. 16 terms that all have a window table take bigk_scan_win_kernel, the candidate scan
+    fed from the window planes; 0 leaves them to bigk_scan_kernel), bigk_win_min_docs (the smallest index it takes, 65536 documents)
+    and bigk_win_tile (whole windows a tile of it spans at most; 0: the kernel's maximum),
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
     and cast_group_max (the class bounds of Documents.cast and Caster.submit, read at the start of each; 0 turns the class off),

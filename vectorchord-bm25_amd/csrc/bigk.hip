@@ -1,8 +1,10 @@
 // bigk.hip -- the sparse half of the k > 1024 route (run_exhaustive, search.hip): batched over queries, its cost grows with the
 // postings the queries touch, not with the index.  A query whose document frequencies sum to at most bigk_cand_max takes it; the
 // others of the batch keep the per-query path of search.hip (an accumulator per document, one launch per term, a radix sort of every
-// document).  Records are byte for byte that path's.  Per chunk of queries (their candidate segments fit the batch's scratch) four
-// launches, whatever the queries:
+// document).  Records are byte for byte that path's.  Per chunk of queries (their candidate segments fit the batch's scratch) at most
+// one launch of each scan kernel and three more, whatever the queries:
+//   bigk_scan_win_kernel   the queries of 1 .. 16 terms that all have a window table (switch bigk_win): work item = (query, run of
+//                          2^16-document windows); the candidate scan fed from post_id16 / post_tfn / win_off -- its comment below
 //   bigk_scan_kernel       work item = (query, run of 8192-document windows), one workgroup of 8 waves.  Per window the query's terms
 //                          in ascending position; per term the waves take the term's blocks that intersect the window (a 64-ary
 //                          search of the wave over the blocks' last ids), decode them with decode_doc_ids / decode_fields and add
@@ -32,8 +34,11 @@
 #include "vbm25_internal.h"
 #include "host_objects.h"
 #include "decode.h"
+#include "block_fetch.h"
+#include "topk_reg.h"
 #include "rerank_lane.h"
 #include "bigk_lane.h"
+#include "bigk_win_lane.h"
 
 namespace vbm25 {
 
@@ -196,6 +201,308 @@ __global__ void __launch_bounds__(bgk::SCAN_THREADS) bigk_scan_kernel(DevIndex i
             if (lane == 0) s_bits[wi] = 0ull;
         }
         __syncthreads();  // the next window's adds find zeros
+    }
+}
+
+// bigk_scan_win_kernel -- bigk_scan_kernel's contract (the candidates of a work item appended to the query's segment, arrival order
+// arbitrary, error flag 8 past cand_cap) fed from the window planes: no block decode, no block search, no hash.  A work item is a
+// sparse query of 1 .. 16 indexed terms, every one with a window table, and a run of whole 2^16-document windows; one workgroup of 8
+// waves.  bigk_win_lane.h and sparse_big_lane.h have the per-lane functions.
+//   plan   wave 0, lane t = term t.  FAST PATH: the longest run of up to g_tile <= MAX_G whole windows [w, w + g) whose slices hold at
+//          most 4096 postings in at most 512 chunks of 8.  A term's postings of consecutive windows are contiguous, so its slice is
+//          the single run [win_off[w], win_off[w + g]); the g - 1 inner entries go to LDS.  SLOW PATH (one window does not fit): the
+//          window in power-of-two aligned parts, the lane bisecting its run, the width halving until the part fits (width 1 does).
+//          Empty tiles are passed over by wave 0 alone.
+//   load   thread c owns chunk c: 8 ids from post_id16, 8 (tf, tf, fieldnorm, fieldnorm) bytes from post_tfn, one 16-byte load each.
+//   mark   a posting's window inside the tile = the inner entries at or below its posting number; its bit in the bitmap of
+//          MAX_G x 2^16 bits is window << 16 | id.  Barrier.
+//   rank   every thread counts 4 MAX_G consecutive words; a wave scan and one LDS hop give every word the bits before it.  A
+//          document's accumulator slot is its rank in the bitmap.  Two barriers.
+//   add    term after term in ascending query position, (tf * s0) / (tf + s1[fn]) in f64 without contraction, ONE BARRIER BEHIND
+//          EVERY TERM THAT HAS A POSTING IN THE TILE.  Within a term no two postings share a document, so no two threads share a slot
+//          between two barriers; across terms the barrier orders the adds.  Every document's sum is therefore formed term after term
+//          from 0.0, as acc[d] is by the per-query path's per-term launches (0.0 + x is exact): the keys are bit for bit that path's,
+//          whatever the tiles -- the argument bigk_scan_kernel and scan_sparse_big_kernel rest on.  A zero word in post_tfn (a term
+//          frequency wider than a byte in the pair): the owning lane reads the exact tf of posting p from block
+//          term_first_block + p / 128 (one field, bwin::field_at) and the fieldnorm from post_fn.  Nothing is given up.
+//   sweep  a thread a slot: the sum read and cleared, the query's filter bit applied, zeros dropped, (key, doc) appended with one
+//          atomic on cursor[s] per wave and round (ballot ranks).  Every thread clears the bitmap words it counted: the LDS is clean
+//          for the next tile.
+struct BigkWinLds {
+    double acc[sbig::CAP];               // 32 KB: a slot's sum, zero between tiles
+    uint32_t bm[bwin::BM_WORDS];         // MAX_G x 8 KB: the tile's bitmap, zero between tiles
+    uint16_t pre[bwin::BM_WORDS];        // MAX_G x 4 KB: bits set before every word (<= 4096)
+    uint32_t sid[sbig::CAP];             // 16 KB: a slot's tile id
+    double s1[256];
+    double t_s0[sbig::MAX_T];
+    uint32_t t_fb[sbig::MAX_T];
+    uint32_t p_a[sbig::MAX_T], p_b[sbig::MAX_T], p_cb[sbig::MAX_T + 1];  // the tile's plan: slices and chunk prefix
+    uint32_t p_in[sbig::MAX_T][bwin::INNER];                              // ... and the terms' inner window bounds
+    uint32_t wsum[SCAN_WAVES];
+    uint32_t bad, p_win, p_g, p_done;
+};
+static_assert(sbig::THREADS == bgk::SCAN_THREADS, "a chunk a thread");
+
+// stats: [0] tiles on the slow path, [1] wide postings decoded (vbm25_batch_debug_bigk_win)
+__global__ void __launch_bounds__(bgk::SCAN_THREADS, 4) bigk_scan_win_kernel(DevIndex ix, Args a, uint32_t item0, uint32_t g_tile, uint32_t *stats) {
+    __shared__ BigkWinLds S;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
+    const BigkItem it = a.items[item0 + blockIdx.x];
+    const BigkQuery qd = a.qd[it.s];
+    const uint32_t m = qd.term_hi - qd.term_lo;
+    const uint32_t win_hi = min(it.win_hi, ix.n_win);
+    for (uint32_t i = tid; i < 256u; i += bgk::SCAN_THREADS) S.s1[i] = ix.s1[i];
+    for (uint32_t i = tid; i < sbig::CAP; i += bgk::SCAN_THREADS) S.acc[i] = 0.0;
+    for (uint32_t i = tid; i < bwin::BM_WORDS; i += bgk::SCAN_THREADS) S.bm[i] = 0u;
+    const uint16_t *id16 = reinterpret_cast<const uint16_t *>(ix.post_id16);
+    uint32_t st_slow = 0, st_wide = 0;
+
+    // ---- item setup (wave 0, lane t = term t): the terms' tables, first blocks and s0
+    uint32_t tw = 0, fb = 0;  // (wave 0's plan registers)
+    bool act = false;
+    if (wave == 0) {
+        act = lane < m && m <= sbig::MAX_T;
+        if (act) {
+            const uint32_t term = a.terms[qd.term_lo + lane];
+            tw = ix.term_win[term];
+            fb = ix.term_first_block[term];
+            S.t_fb[lane] = fb;
+            S.t_s0[lane] = ix.term_s0[term];
+        }
+        const bool no_table = __ballot(act && tw == NONE32) != 0ull;  // (never: the host gives this kernel queries whose terms all have one)
+        if (lane == 0) S.bad = (m == 0u || m > sbig::MAX_T || no_table) ? 1u : 0u;
+    }
+    __syncthreads();
+    if (uni(S.bad)) {
+        if (tid == 0) atomicOr(a.error_flag, 8u);
+        return;
+    }
+    const ull *filt = nullptr;
+    if (a.filt_words) {
+        const uint32_t sel = a.filt_sel[qd.q];
+        if (sel != UINT32_MAX) filt = a.filt_words + size_t(sel) * a.filt_stride;
+    }
+    uint64_t *ckey = a.cand_key + qd.cand_base;
+    uint32_t *cdoc = a.cand_doc + qd.cand_base;
+
+    // wave 0's cursor over the item: the next window w; inside a window on the slow path: document cur, the width to try, the end of
+    // the lane's run and its slice start at cur
+    uint32_t w = it.win_lo, cur = 0, W = sbig::WIN, wo1 = 0, sa = 0, part_hi = 0;
+    bool slow = false;
+    auto id_at = [&](uint32_t i) { return id16[128ull * fb + i]; };
+    for (;;) {
+        // ---- plan (wave 0): the next tile with a posting in it
+        if (wave == 0) {
+            bool found = false, unfit = false;
+            uint32_t ta = 0, tb = 0, ch = 0, incl = 0, g = 1, pw = 0;
+            uint32_t o[bwin::MAX_G + 1u] = {};  // the lane's win_off entries of the windows w .. w + MAX_G
+            while (!found && !unfit && (slow || w < win_hi)) {
+                if (!slow) {
+                    const uint32_t gmax = bwin::tile_windows(g_tile, win_hi - w);
+#pragma unroll
+                    for (uint32_t i = 0; i <= bwin::MAX_G; ++i) o[i] = act ? ix.win_off[tw + w + min(i, gmax)] : 0u;
+                    uint32_t posts_all = 0;
+                    auto totals = [&](uint32_t n, uint32_t &posts, uint32_t &chunks) {
+                        tb = o[0];
+#pragma unroll
+                        for (uint32_t i = 1; i <= bwin::MAX_G; ++i) tb = i == n ? o[i] : tb;
+                        ch = act ? sbig::chunks_of(o[0], tb) : 0u;
+                        incl = wave_incl_scan_u32(ch);
+                        posts = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(act ? tb - o[0] : 0u), 63);
+                        chunks = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                        posts_all = posts;
+                    };
+                    g = uni(bwin::fit_windows(totals, gmax));
+                    if (g) {
+                        if (posts_all) {
+                            found = true;
+                            ta = o[0];
+                            pw = w;
+                        }
+                        w += g;
+                        continue;
+                    }
+                    slow = true;  // the window alone does not fit: its halves first
+                    cur = w << 16;
+                    part_hi = sbig::part_end(w, ix.n_docs);
+                    W = sbig::WIN >> 1;
+                    sa = o[0];
+                    wo1 = o[1];
+                }
+                uint32_t tend = cur, sb = sa, posts = 0;
+                for (;;) {
+                    tend = sbig::tile_end(cur, W, part_hi);
+                    sb = tend == part_hi || !act ? wo1 : sbig::run_lower_bound(id_at, sa, wo1, tend & (sbig::WIN - 1u));
+                    ch = act ? sbig::chunks_of(sa, sb) : 0u;
+                    incl = wave_incl_scan_u32(ch);
+                    posts = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(act ? sb - sa : 0u), 63);
+                    if (sbig::tile_fits(posts, (uint32_t)__builtin_amdgcn_readlane((int)incl, 63))) break;
+                    if (W == 1u) {  // (never: one document holds at most MAX_T postings -- the index's ids ascend strictly)
+                        unfit = true;
+                        break;
+                    }
+                    W = sbig::halve(W);
+                }
+                if (unfit) break;
+                if (posts) {
+                    found = true;
+                    ta = sa;
+                    tb = sb;
+                    g = 1;
+                    pw = w;
+                    ++st_slow;
+                }
+                cur = tend;
+                sa = sb;
+                W = sbig::widen(W);
+                if (cur >= part_hi) {
+                    slow = false;
+                    ++w;
+                }
+            }
+            if (found && act) {
+                S.p_a[lane] = ta;
+                S.p_b[lane] = tb;
+                S.p_cb[lane] = incl - ch;
+#pragma unroll
+                for (uint32_t i = 0; i + 1u < bwin::MAX_G; ++i) S.p_in[lane][i] = o[i + 1u];
+            }
+            if (lane == 0) {
+                S.p_cb[m] = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                S.p_win = pw;
+                S.p_g = g;
+                S.p_done = found ? 0u : 1u;
+                if (unfit) S.bad = 1u;
+            }
+        }
+        __syncthreads();  // the plan, and the bitmap clean
+        if (uni(S.p_done)) break;
+        const uint32_t nch = uni(S.p_cb[m]), win = uni(S.p_win), g = uni(S.p_g);
+        // the terms with a posting in the tile, read here: wave 0 may write the next plan while another wave is still in the sweep
+        uint32_t has = 0;
+        for (uint32_t tt = 0; tt < m; ++tt) has |= (S.p_cb[tt + 1u] != S.p_cb[tt] ? 1u : 0u) << tt;
+        has = uni(has);
+
+        // ---- load: the thread's chunk
+        const bool own = tid < nch;
+        uint32_t t = 0, mask = 0, start = 0;
+        uint32_t idw[4] = {0, 0, 0, 0}, tfw[4] = {0, 0, 0, 0}, inner[bwin::INNER] = {0, 0, 0};
+        if (own) {
+            t = sbig::chunk_term(S.p_cb, m, tid);
+            const uint32_t sl_a = S.p_a[t], sl_b = S.p_b[t];
+            start = sbig::chunk_start(sl_a, S.p_cb[t], tid);
+            mask = sbig::chunk_mask(start, sl_a, sl_b);
+            const size_t v = 16ull * S.t_fb[t] + (start >> 3);  // (16 chunks a block; the planes are 256 bytes a block)
+            const uint4 i4 = reinterpret_cast<const uint4 *>(ix.post_id16)[v];
+            const uint4 f4 = reinterpret_cast<const uint4 *>(ix.post_tfn)[v];
+            idw[0] = i4.x, idw[1] = i4.y, idw[2] = i4.z, idw[3] = i4.w;
+            tfw[0] = f4.x, tfw[1] = f4.y, tfw[2] = f4.z, tfw[3] = f4.w;
+#pragma unroll
+            for (uint32_t i = 0; i + 1u < bwin::MAX_G; ++i) inner[i] = S.p_in[t][i];
+        }
+        // ---- mark
+        uint32_t rid[sbig::CHUNK];
+#pragma unroll
+        for (uint32_t e = 0; e < sbig::CHUNK; ++e) {
+            rid[e] = bwin::tile_id(bwin::posting_window(start + e, inner, g), sbig::chunk_id(idw, e));
+            if ((mask >> e) & 1u) atomicOr(&S.bm[rid[e] >> 5], 1u << (rid[e] & 31u));
+        }
+        __syncthreads();
+        // ---- rank: bits before every word, documents of the tile
+        uint32_t n_slots;
+        {
+            uint32_t c[bwin::RANK_WORDS], own_c = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < bwin::RANK_WORDS; j += 4) {
+                const uint4 bw = *reinterpret_cast<const uint4 *>(&S.bm[bwin::RANK_WORDS * tid + j]);
+                c[j] = sbig::popc(bw.x), c[j + 1] = sbig::popc(bw.y), c[j + 2] = sbig::popc(bw.z), c[j + 3] = sbig::popc(bw.w);
+                own_c += c[j] + c[j + 1] + c[j + 2] + c[j + 3];
+            }
+            const uint32_t incl = wave_incl_scan_u32(own_c);
+            if (lane == 63u) S.wsum[wave] = incl;
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+#pragma unroll
+            for (uint32_t w2 = 0; w2 < SCAN_WAVES; ++w2) {
+                const uint32_t x = S.wsum[w2];
+                before += w2 < wave ? x : 0u;
+                all += x;
+            }
+            n_slots = uni(all);
+            uint32_t ex = before + incl - own_c;  // (<= CAP: 16 bits hold it)
+#pragma unroll
+            for (uint32_t j = 0; j < bwin::RANK_WORDS; j += 2) {
+                reinterpret_cast<uint32_t *>(S.pre)[(bwin::RANK_WORDS * tid + j) >> 1] = ex | (ex + c[j]) << 16;
+                ex += c[j] + c[j + 1];
+            }
+        }
+        __syncthreads();
+        uint32_t slot[sbig::CHUNK];
+#pragma unroll
+        for (uint32_t e = 0; e < sbig::CHUNK; ++e) {
+            slot[e] = 0;
+            if ((mask >> e) & 1u) slot[e] = sbig::slot_of(S.pre[rid[e] >> 5], S.bm[rid[e] >> 5], rid[e] & 31u);
+        }
+        // ---- add: term after term in ascending query position, a barrier behind every term that has a posting in the tile
+        for (uint32_t tt = 0; tt < m; ++tt) {
+            if (!((has >> tt) & 1u)) continue;
+            if (own && t == tt) {
+                const double s0 = S.t_s0[tt];
+#pragma unroll
+                for (uint32_t e = 0; e < sbig::CHUNK; ++e)
+                    if ((mask >> e) & 1u) {
+                        uint32_t tfv = sbig::chunk_tf(tfw, e), fn = sbig::chunk_fn(tfw, e);
+                        if (bwin::wide_pair(tfw, e)) {  // rare: the posting's own field of its block, its fieldnorm from post_fn
+                            const uint32_t p = start + e, j = S.t_fb[tt] + (p >> 7), i = p & 127u;
+                            const uint4 bm = ix.blk_meta[j];
+                            const uint32_t n = bm.w & 0xffu, md = (bm.w >> 8) & 0xffu, mt = (bm.w >> 16) & 0xffu;
+                            tfv = bwin::field_at(bwin::tf_fields(ix.blob + 8ull * bm.z, md, n), mt, i);
+                            fn = ix.post_fn[128ull * j + i];
+                            ++st_wide;
+                        }
+                        const double tf = (double)tfv;
+                        const double sc = (tf * s0) / (tf + S.s1[fn]);  // Cache::evaluate, bm25.rs:355-358
+                        S.acc[slot[e]] = S.acc[slot[e]] + sc;
+                        S.sid[slot[e]] = rid[e];
+                    }
+            }
+            __syncthreads();  // the next term's adds see this term's sums
+        }
+        // ---- sweep: a thread a slot; whole waves take every round (the ballot)
+        const uint32_t doc0 = win << 16;
+        for (uint32_t r0 = 0; r0 < n_slots; r0 += bgk::SCAN_THREADS) {
+            const uint32_t s = r0 + tid;
+            ull key = 0;
+            uint32_t d = 0;
+            if (s < n_slots) {
+                key = (ull)__double_as_longlong(S.acc[s]);
+                S.acc[s] = 0.0;
+                d = doc0 + S.sid[s];
+                if (filt && !((filt[d >> 6] >> (d & 63u)) & 1ull)) key = 0;  // (bigk_mask_kernel's word and bit)
+            }
+            const ull hm = __ballot(key != 0ull);
+            if (hm) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(a.cursor + it.s, (uint32_t)__popcll(hm));
+                base = __shfl(base, 0);
+                const uint32_t at = base + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull));
+                if (key != 0ull) {
+                    if (at < qd.cand_cap) {
+                        ckey[at] = key;
+                        cdoc[at] = d;
+                    } else {
+                        atomicOr(a.error_flag, 8u);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < bwin::RANK_WORDS; j += 4) *reinterpret_cast<uint4 *>(&S.bm[bwin::RANK_WORDS * tid + j]) = make_uint4(0, 0, 0, 0);
+    }
+    if (uni(S.bad) && tid == 0) atomicOr(a.error_flag, 8u);
+    if (stats) {
+        if (tid == 0 && st_slow) atomicAdd(&stats[0], st_slow);
+        if (st_wide) atomicAdd(&stats[1], st_wide);
     }
 }
 
@@ -374,11 +681,16 @@ int bigk_create(vbm25_batch *bt) {
     int rc = 0;
     if ((rc = g.cand_key.alloc(8 * g.chunk_cand)) || (rc = g.cand_doc.alloc(4 * g.chunk_cand)) ||
         (rc = g.surv_key.alloc(8ull * g.chunk_q * g.surv_stride)) || (rc = g.surv_doc.alloc(4ull * g.chunk_q * g.surv_stride)) ||
-        (rc = g.cursor.alloc(4ull * bt->max_queries)) || (rc = g.surv_cnt.alloc(4ull * bt->max_queries)) ||
+        (rc = g.cursor.alloc(4ull * (BIGK_STAT_WORDS + bt->max_queries))) || (rc = g.surv_cnt.alloc(4ull * bt->max_queries)) ||
         (rc = g.sel.alloc(4ull * bt->max_queries)) || (rc = g.qd.alloc(sizeof(BigkQuery) * size_t(bt->max_queries))) ||
         (rc = g.terms.alloc(4ull * std::max(bt->max_terms, 1u))) || (rc = g.items.alloc(sizeof(BigkItem) * g.max_items)))
         return rc;
     g.sparse.assign(bt->max_queries, 0);
+    // the window scan's gate: the switch, the index's size, and the planes the kernel reads
+    g.win_on = bt->tune.bigk_win != 0 && ix->n_docs >= bt->tune.bigk_win_min_docs && ix->dev.post_id16 && ix->dev.win_off &&
+               ix->dev.term_win && ix->dev.post_tfn && !ix->term_win_host.empty();
+    g.win_tile = bwin::tile_windows(bt->tune.bigk_win_tile ? bt->tune.bigk_win_tile : bwin::MAX_G, bwin::MAX_G);
+    g.h_win.reserve(bt->max_queries);
     g.h_qd.reserve(bt->max_queries);
     g.h_terms.reserve(bt->max_terms);
     return VBM25_OK;
@@ -399,26 +711,39 @@ int bigk_plan(vbm25_batch *bt) {
     g.h_terms.clear();
     g.h_items.clear();
     std::fill(g.sparse.begin(), g.sparse.end(), uint8_t(0));
-    uint32_t n_scanned = 0;  // sparse queries with a posting: the others make no item
+    g.h_win.clear();
+    g.items_win = g.items_blk = 0;
+    uint32_t n_scanned = 0, n_scanned_win = 0;  // sparse queries with a posting, by scan kernel: the others make no item
     for (uint32_t q = 0; q < nq; ++q) {
         if (bt->h_postings[q] > g.cand_max) continue;
         g.sparse[q] = 1;
         BigkQuery d{};
         d.q = q;
         d.term_lo = uint32_t(g.h_terms.size());
+        bool tables = true;
         for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p)
-            if (bt->h_terms[p] < ix->n_terms && ix->term_df_host[bt->h_terms[p]]) g.h_terms.push_back(bt->h_terms[p]);  // search.rs:59-61
+            if (bt->h_terms[p] < ix->n_terms && ix->term_df_host[bt->h_terms[p]]) {  // search.rs:59-61
+                g.h_terms.push_back(bt->h_terms[p]);
+                tables = tables && g.win_on && ix->term_win_host[bt->h_terms[p]] != UINT32_MAX;
+            }
         d.term_hi = uint32_t(g.h_terms.size());
         d.cand_cap = uint32_t(bt->h_postings[q]);
-        n_scanned += d.cand_cap != 0;
+        // the window scan's queries: 1 .. 16 indexed terms, every one with a window table
+        const bool win = g.win_on && tables && d.term_hi > d.term_lo && d.term_hi - d.term_lo <= sbig::MAX_T;
+        (win ? n_scanned_win : n_scanned) += d.cand_cap != 0;
+        g.h_win.push_back(win ? 1 : 0);
         g.h_qd.push_back(d);
     }
     g.n_sparse = uint32_t(g.h_qd.size());
     if (!g.n_sparse) return VBM25_OK;
-    const uint32_t n_win = (ix->n_docs + bgk::WINDOW - 1u) / bgk::WINDOW;
-    const uint32_t wpi = bgk::item_windows(n_win, n_scanned, bt->tune.bigk_item_win, ITEM_TARGET, g.max_items);
+    // the item cuts, per scan kernel over its own windows; with both kinds in the batch each gets half the item buffer
+    const uint64_t cap = n_scanned && n_scanned_win ? g.max_items / 2 : g.max_items;
+    const uint32_t n_win = (ix->n_docs + bgk::WINDOW - 1u) / bgk::WINDOW, n_win16 = ix->dev.n_win;
+    const uint32_t wpi = bgk::item_windows(n_win, n_scanned, bt->tune.bigk_item_win, ITEM_TARGET, cap);
+    const uint32_t wpi16 = bgk::item_windows(n_win16, n_scanned_win, bt->tune.bigk_item_win, ITEM_TARGET, cap);
     g.wpi = wpi;
-    // chunks: queries in order while their candidate segments fit the scratch and their survivors the survivor buffers
+    // chunks: queries in order while their candidate segments fit the scratch and their survivors the survivor buffers; a chunk's
+    // items the window scan's first, then the block scan's: one launch of each
     for (uint32_t s = 0; s < g.n_sparse;) {
         BigkChunk c{};
         c.s0 = s;
@@ -427,13 +752,20 @@ int bigk_plan(vbm25_batch *bt) {
         while (s < g.n_sparse && s - c.s0 < g.chunk_q && used + g.h_qd[s].cand_cap <= g.chunk_cand) {
             g.h_qd[s].cand_base = uint32_t(used);
             used += g.h_qd[s].cand_cap;
-            if (g.h_qd[s].cand_cap)
-                for (uint32_t w = 0; w < n_win; w += wpi) g.h_items.push_back(BigkItem{s, w, std::min(w + wpi, n_win)});
             ++s;
         }
         if (s == c.s0) return set_error(VBM25_ERR_INVALID, "internal error: a sparse query exceeds the candidate scratch");
         c.s1 = s;
+        for (uint32_t i = c.s0; i < c.s1; ++i)
+            if (g.h_win[i] && g.h_qd[i].cand_cap)
+                for (uint32_t w = 0; w < n_win16; w += wpi16) g.h_items.push_back(BigkItem{i, w, std::min(w + wpi16, n_win16)});
+        c.item_mid = uint32_t(g.h_items.size());
+        for (uint32_t i = c.s0; i < c.s1; ++i)
+            if (!g.h_win[i] && g.h_qd[i].cand_cap)
+                for (uint32_t w = 0; w < n_win; w += wpi) g.h_items.push_back(BigkItem{i, w, std::min(w + wpi, n_win)});
         c.item1 = uint32_t(g.h_items.size());
+        g.items_win += c.item_mid - c.item0;
+        g.items_blk += c.item1 - c.item_mid;
         g.chunks.push_back(c);
     }
     if (g.h_items.size() > g.max_items) return set_error(VBM25_ERR_INVALID, "internal error: %zu work items exceed the buffer", g.h_items.size());
@@ -446,13 +778,15 @@ int bigk_plan(vbm25_batch *bt) {
 // the sparse queries of the current set, on st: one clear, then four launches a chunk
 int bigk_run(vbm25_batch *bt, hipStream_t st) {
     BigkState &g = bt->bg;
+    g.ran = false;
     if (!g.n_sparse) return VBM25_OK;
     const DevIndex &dix = bt->index->dev;
     Args a{};
     a.qd = g.qd.as<BigkQuery>();
     a.items = g.items.as<BigkItem>();
     a.terms = g.terms.as<uint32_t>();
-    a.cursor = g.cursor.as<uint32_t>();
+    uint32_t *stats = g.cursor.as<uint32_t>();  // (the window scan's counters, then the cursors)
+    a.cursor = stats + BIGK_STAT_WORDS;
     a.surv_cnt = g.surv_cnt.as<uint32_t>();
     a.cand_key = g.cand_key.as<uint64_t>();
     a.cand_doc = g.cand_doc.as<uint32_t>();
@@ -469,16 +803,31 @@ int bigk_run(vbm25_batch *bt, hipStream_t st) {
         a.filt_sel = g.sel.as<uint32_t>();
         a.filt_stride = bt->filter->words;
     }
-    bigk_clear_kernel<<<(g.n_sparse + 255) / 256, 256, 0, st>>>(a.cursor, g.n_sparse);
+    bigk_clear_kernel<<<(BIGK_STAT_WORDS + g.n_sparse + 255) / 256, 256, 0, st>>>(stats, BIGK_STAT_WORDS + g.n_sparse);
     const uint32_t k_tiles = g.surv_stride / bgk::TILE;
     for (const BigkChunk &c : g.chunks) {
         const uint32_t cq = c.s1 - c.s0;
-        if (c.item1 > c.item0) bigk_scan_kernel<<<c.item1 - c.item0, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item0);
+        if (c.item_mid > c.item0) bigk_scan_win_kernel<<<c.item_mid - c.item0, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item0, g.win_tile, stats);
+        if (c.item1 > c.item_mid) bigk_scan_kernel<<<c.item1 - c.item_mid, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item_mid);
         bigk_select_kernel<<<cq, SELECT_THREADS, 0, st>>>(a, c.s0);
         bigk_sort_kernel<<<dim3(k_tiles, cq), SORT_THREADS, 0, st>>>(a, c.s0);
         bigk_rank_emit_kernel<<<dim3((bt->k + EMIT_THREADS - 1) / EMIT_THREADS, cq), EMIT_THREADS, 0, st>>>(dix, a, c.s0);
     }
     HIP_TRY(hipGetLastError());
+    g.ran_items_win = g.items_win;
+    g.ran_items_blk = g.items_blk;
+    g.ran = true;
+    return VBM25_OK;
+}
+
+// vbm25_batch_debug_bigk_win: the last run's items by scan kernel (the host's cut) and the window scan's two device counters
+int bigk_debug_win(vbm25_batch *bt, uint32_t *out4) {
+    BigkState &g = bt->bg;
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!g.on || !g.ran || !g.n_sparse) return VBM25_OK;
+    out4[0] = g.ran_items_win;
+    out4[1] = g.ran_items_blk;
+    HIP_TRY(hipMemcpy(out4 + 2, g.cursor.p, 8, hipMemcpyDeviceToHost));
     return VBM25_OK;
 }
 

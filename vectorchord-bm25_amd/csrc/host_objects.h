@@ -67,7 +67,13 @@ struct Tuning {
     uint64_t bigk_cand_max = 1ull << 20;   // ... a query is sparse when its terms' document frequencies sum to at most this: its candidate
                                    // segment (12 bytes an entry) is then at most 12 MB, and four such queries share a chunk
     uint64_t bigk_chunk_cand = 1ull << 22; // ... candidate entries a chunk of queries may ask for: the batch's candidate scratch, 48 MB
-    uint32_t bigk_item_win = 0;    // ... windows of 8192 documents per work item (0: cut for about 2048 items a batch)
+    uint32_t bigk_item_win = 0;    // ... windows per work item, of whichever scan kernel takes the query: 8192 documents (bigk_scan_kernel),
+                                   // 65536 (bigk_scan_win_kernel); 0: cut for about 2048 items a batch
+    int bigk_win = 1;              // ... sparse queries of 1 .. 16 indexed terms, every one with a window table, take bigk_scan_win_kernel
+                                   // (the candidate scan fed from post_id16 / post_tfn / win_off); 0: every sparse query bigk_scan_kernel.
+                                   // The default follows profiles/bigk_win_cost.json
+    uint32_t bigk_win_min_docs = 65536;  // ... on an index of at least this many documents
+    uint32_t bigk_win_tile = 0;    // ... whole windows a tile of that kernel spans at most (1 .. its compile-time maximum; 0: the maximum)
     int dense_big = 1;             // 256 < k <= 1024: dense queries of <= D_T terms take scan_dense_kernel<1024> (the survivor list in LDS);
                                    // 0: every query of such a batch takes scan_many_kernel.  On: profiles/dense_big_cost.json (C5, k = 1000: 270 -> 67 ms)
     uint32_t dense_big_min_docs = 65536;  // ... on an index of at least this many documents (four full windows: below, nothing is skipped
@@ -146,7 +152,7 @@ struct BigkItem {
     uint32_t s, win_lo, win_hi;  // sparse query (index into the descriptors), windows [win_lo, win_hi)
 };
 struct BigkChunk {
-    uint32_t s0, s1, item0, item1;
+    uint32_t s0, s1, item0, item_mid, item1;  // the chunk's items: [item0, item_mid) bigk_scan_win_kernel's, [item_mid, item1) bigk_scan_kernel's
 };
 constexpr uint64_t BIGK_SURV_ENTRIES = 1ull << 22;  // survivor entries a chunk holds at most (k rounded up to tiles per query): 48 MB
 struct BigkState {
@@ -161,7 +167,16 @@ struct BigkState {
     std::vector<BigkChunk> chunks;
     uint32_t n_sparse = 0;
     uint32_t ran_sparse = 0, ran_fallback = 0;  // queries of the last run by path (vbm25_batch_bigk_queries)
+    // bigk_scan_win_kernel (the window scan): the gate as the batch took it, which sparse queries of the current set take it, and
+    // the last run's items by scan kernel (vbm25_batch_debug_bigk_win).  Its two device counters are the four words in front of the
+    // cursors: one clear covers both.
+    bool win_on = false;
+    uint32_t win_tile = 1;
+    std::vector<uint8_t> h_win;   // per sparse query
+    uint32_t items_win = 0, items_blk = 0, ran_items_win = 0, ran_items_blk = 0;
+    bool ran = false;
 };
+constexpr uint32_t BIGK_STAT_WORDS = 4;
 
 }  // namespace vbm25
 
@@ -335,6 +350,7 @@ int batch_growing_buffers(vbm25_batch *bt, const vbm25_device_growing *gs);
 int bigk_create(vbm25_batch *bt);
 int bigk_plan(vbm25_batch *bt);
 int bigk_run(vbm25_batch *bt, hipStream_t st);
+int bigk_debug_win(vbm25_batch *bt, uint32_t *out4);
 // growing.hip: grow_delete_kernel over a deletion bitmap in HBM (tid.hip makes one from a TID set)
 int growing_delete_by_bits(vbm25_device_growing *gs, const uint32_t *bits);
 // filter.hip

@@ -1364,7 +1364,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
-// bigk_item_win, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
+// bigk_item_win, bigk_win, bigk_win_min_docs, bigk_win_tile, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
@@ -1404,6 +1404,9 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "bigk_cand_max") g_tune.bigk_cand_max = (uint64_t)std::min<long long>(std::max(0ll, value), 1ll << 30);
     else if (n == "bigk_chunk_cand") g_tune.bigk_chunk_cand = (uint64_t)std::min<long long>(std::max(1ll, value), 1ll << 30);
     else if (n == "bigk_item_win") g_tune.bigk_item_win = (uint32_t)std::min<long long>(std::max(0ll, value), 1ll << 20);
+    else if (n == "bigk_win") g_tune.bigk_win = value != 0;
+    else if (n == "bigk_win_min_docs") g_tune.bigk_win_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
+    else if (n == "bigk_win_tile") g_tune.bigk_win_tile = (uint32_t)std::min<long long>(std::max(0ll, value), 4ll);
     else if (n == "dense_big") g_tune.dense_big = value != 0;
     else if (n == "dense_big_min_docs") g_tune.dense_big_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "sparse_big") g_tune.sparse_big = value != 0;
@@ -1530,6 +1533,18 @@ int vbm25_batch_debug_sparse_big(vbm25_batch *bt, uint32_t *out4) {
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     HIP_TRY(hipMemcpy(out4, bt->sb_stats.p, 16, hipMemcpyDeviceToHost));
     return VBM25_OK;
+}
+
+// test / tool aid (not declared in include/vbm25.h): the sparse path of the last k > 1024 run -- out[0] the work items bigk_scan_win_kernel
+// took (the window scan), out[1] the items bigk_scan_kernel took (the block scan), out[2] the window scan's tiles on the slow path (a part
+// of one window), out[3] the postings whose wide term frequency it decoded from their blocks.  Zeros at k <= 1024 and before a run.
+int vbm25_batch_debug_bigk_win(vbm25_batch *bt, uint32_t *out4) {
+    if (!bt || !out4) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!bt->bigk) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    return bigk_debug_win(bt, out4);
 }
 
 // test aid (not declared in include/vbm25.h): launches of the last run's scan -- 1: scan_win_kernel merged the queries' lists itself
