@@ -286,6 +286,19 @@ void vbm25_batch_destroy(vbm25_batch *);
  * segment stay attached). */
 int vbm25_batch_set_queries(vbm25_batch *, const uint32_t *term_ids, const uint32_t *q_off,
                             uint32_t nq);
+/* A run starts after the work enqueued on `hip_stream` before the call, and it is complete for the caller when
+ * vbm25_batch_fetch returns.  Whether later work on `hip_stream` waits for it depends on the batch:
+ *  - a batch with a document filter, a growing segment, or whose device addresses were asked for
+ *    (vbm25_batch_device_results) runs in the order of `hip_stream`, and so does every run that is not a single launch
+ *    of the window kernel: what is enqueued on the stream behind the run sees its records;
+ *  - every other run of the window kernel goes to a stream the batch object owns, and nothing joins it back to
+ *    `hip_stream`: runs of the same batch object are ordered among themselves, runs of different batch objects are not
+ *    ordered at all and overlap on the device (the next batch's workgroups take the compute units as this one's leave
+ *    them).  A caller that needs the records in stream order asks for their device addresses once; that call waits for
+ *    a run in flight, and from then on the object runs in stream order.
+ * vbm25_batch_destroy, vbm25_batch_set_queries, vbm25_batch_set_filter, vbm25_batch_set_growing and
+ * vbm25_index_maintain wait for such a run themselves.  (The tuning value run_overlap = 0, read when a batch object is
+ * created, keeps every run on `hip_stream`.) */
 int vbm25_batch_run(vbm25_batch *, void *hip_stream);
 int vbm25_batch_fetch(vbm25_batch *, vbm25_hit *hits, uint32_t *n_hits);
 /* k > 1024: how many queries of the last run took the batched path for sparse queries (the document frequencies of the
@@ -299,7 +312,14 @@ int vbm25_batch_bigk_queries(const vbm25_batch *, uint32_t *sparse, uint32_t *fa
 int vbm25_batch_device_results(vbm25_batch *, void **hits, void **n_hits);
 /* When enabled, run() brackets the posting-scan kernel with HIP events on the
  * launch stream; kernel_ms() synchronises and returns the average duration of
- * the launches recorded since the last call. */
+ * the launches recorded since the last call.
+ * A run on the batch object's own stream (vbm25_batch_run) overlaps its predecessor, and the span between its own two
+ * events would include the time its workgroups waited for compute units.  Such a run counts from the LATER of its own
+ * start event and the end event of the timed run the library enqueued before it, on a stream of its own, for the same
+ * index (kernel_ms takes the smaller of the two elapsed times; the own start event stands when that predecessor was
+ * not timed): the run's exclusive share.  Over a sequence of runs that end in the order they were enqueued the shares
+ * add up to the time that went by, so bytes over kernel_ms is a rate per step, not per kernel.  Timing changes
+ * nothing about where a run is enqueued.  For every other run the number is the span between its two events. */
 int vbm25_batch_set_timing(vbm25_batch *, int enabled);
 int vbm25_batch_kernel_ms(vbm25_batch *, double *avg_ms, uint32_t *n_launches);
 

@@ -9,6 +9,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -82,6 +83,8 @@ struct Tuning {
                                    // scan_sparse_big_kernel (the rank-addressed window scan); 0: scan_many_kernel.  On: profiles/sparse_big_cost.json
                                    // (C3, 1024 queries, k = 1000: 103.8 -> 20.6 ms, a gain at every k of the table)
     uint32_t sparse_big_min_docs = 65536;  // ... on an index of at least this many documents
+    int run_overlap = 1;           // vbm25_batch_run: a one-launch run of scan_win_kernel of a batch without a filter goes to a stream the batch
+                                   // owns, so that runs of different batch objects overlap (0: every run on the caller's stream)
     uint32_t generation = 0;       // bumped by every vbm25_tuning_set / reset: vbm25_search_batch's batch object is rebuilt when it is stale
 };
 // the switches of the moment (search.hip owns them and their lock: vbm25_tuning_set / _reset write, this copies)
@@ -178,6 +181,24 @@ struct BigkState {
 };
 constexpr uint32_t BIGK_STAT_WORDS = 4;
 
+// An event more than one object refers to: the end of a timed detached run (vbm25_batch_run on the batch's own stream) belongs to its
+// batch and is the start of the next such run's exclusive share (vbm25_batch_kernel_ms), whichever of the two objects goes first
+struct SharedEvent {
+    hipEvent_t ev = nullptr;
+    SharedEvent() = default;
+    SharedEvent(const SharedEvent &) = delete;
+    SharedEvent &operator=(const SharedEvent &) = delete;
+    ~SharedEvent() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+// one timed run of a batch: the events that bracket its scan, and (detached runs) the end of the timed detached run the library
+// enqueued before it on the same index
+struct TimedRun {
+    hipEvent_t start = nullptr;
+    std::shared_ptr<SharedEvent> end, prev;
+};
+
 }  // namespace vbm25
 
 struct vbm25_index {
@@ -188,6 +209,7 @@ struct vbm25_index {
     std::vector<uint32_t> term_df_host;  // host copy for query routing
     vbm25_batch *scratch = nullptr;      // batch object re-used by vbm25_search_batch
     vbm25_batch *scratch_grow = nullptr; // ... and by vbm25_search_batch_growing
+    std::shared_ptr<vbm25::SharedEvent> ov_last_end;  // the end of the last detached run of any batch of this index, if it was timed (search.hip, under its lock)
     vbm25::DeviceBuffer term_wand_tf, term_wand_fn, term_df, term_first_block, term_s0, blk_min_doc, blk_max_doc, blk_meta, blk_ub, blob,
         post_fn, post_rel16, post_tfn, doc_payload, s1, term_idf, fn_len, term_kth_ub, post_id16, win_off, term_win;
     std::vector<uint32_t> term_win_host;  // host copy of term_win (query routing); empty: the index has no window planes
@@ -301,12 +323,18 @@ struct vbm25_batch {
     bool state_clean = false;     // threshold / histogram / counters are zero (the routes without plan_kernel leave them so; the general one does not)
     uint32_t target_items = vbm25::TARGET_ITEMS;
     uint32_t min_chunk = vbm25::MIN_CHUNK_POSTINGS;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    std::vector<vbm25::TimedRun> events;
     size_t events_used = 0;
     // vbm25_search_batch's low-latency route: pinned staging buffers and a private stream -- queries go up and
     // hits come down with asynchronous copies and ONE stream synchronisation
     hipStream_t lat_stream = nullptr;
     hipStream_t last_stream = nullptr;  // the stream of the last run: what fetch waits for (not the whole device)
+    // vbm25_batch_run, detached (search.hip, batch_run_entry): the batch's own non-blocking stream, made at the first such run -- not
+    // lat_stream, whose users test for its presence; the event that carries the caller's pending work over to it; and whether a run
+    // on it may still be in flight while the caller's stream knows nothing of it
+    hipStream_t own_stream = nullptr;
+    hipEvent_t own_wait = nullptr;
+    bool detached = false;
     bool download_enqueued = false;     // the last run's records are already on their way to pin_out (vbm25_multi_batch_run)
     // vbm25_stream_*: merge_kernel writes counts and records straight into the pinned output buffer (posted writes over PCIe, no
     // download command on the step: only the 4-byte flag is copied); results_pinned_now: the last run did so.  With a growing segment
@@ -315,13 +343,16 @@ struct vbm25_batch {
     uint8_t *pin_in = nullptr, *pin_out = nullptr;
     size_t pin_in_bytes = 0, pin_out_bytes = 0;
     ~vbm25_batch() {
+        if (own_stream) {  // (a detached run reads the buffers the members' destructors free)
+            (void)hipStreamSynchronize(own_stream);
+            (void)hipStreamDestroy(own_stream);
+        }
+        if (own_wait) (void)hipEventDestroy(own_wait);
         if (lat_stream) (void)hipStreamDestroy(lat_stream);
         if (pin_in) (void)hipHostFree(pin_in);
         if (pin_out) (void)hipHostFree(pin_out);
-        for (auto &e : events) {
-            (void)hipEventDestroy(e.first);
-            (void)hipEventDestroy(e.second);
-        }
+        for (auto &e : events)
+            if (e.start) (void)hipEventDestroy(e.start);
     }
 };
 

@@ -439,8 +439,11 @@ static void plan_route(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t
 
 // The decided query set to the batch: the scratch plane, then the descriptors -- staged in pinned memory (fast) or copied to the
 // separate device buffers -- and the plan last.  A failure on the way leaves a half-committed set: the caller clears it.
+static int batch_leave_detached(vbm25_batch *bt);
 static int commit_queries(vbm25_batch *bt, const uint32_t *term_ids, const uint32_t *q_off, uint32_t nq, bool fast, const QueryPlan &plan) {
     if (int rc = use_device(bt->index->device)) return rc;
+    // a detached run (batch_run_entry) still reads the descriptors: the copies below are ordered behind the caller's streams at most
+    if (int rc = batch_leave_detached(bt)) return rc;
     if (plan.route == Route::Exhaustive) {
         bt->h_terms.assign(term_ids, term_ids + q_off[nq]);
         bt->h_off.assign(q_off, q_off + nq + 1);
@@ -599,17 +602,34 @@ static int reset_launch_state(vbm25_batch *bt, hipStream_t st, bool one_launch) 
 
 // timing on: the batch's next event pair, the first one recorded on st now; e1 is the second, for the caller to record where the timed
 // region ends (nullptr with timing off)
+// A run on the batch's own stream (detached: batch_run_entry) also takes the end event of the timed detached run enqueued before it on
+// the same index, and leaves its own end event there for the next one: vbm25_batch_kernel_ms counts a run from the later of its start
+// and that end.  An end event somebody else still refers to (the index, a later run of another batch) is not recorded again: the slot
+// gets a new one.
+static std::mutex g_ov_mutex;  // vbm25_index::ov_last_end, of every index
 static int take_events(vbm25_batch *bt, hipStream_t st, hipEvent_t &e1) {
     e1 = nullptr;
     if (!bt->timing) return VBM25_OK;
     if (bt->events_used == bt->events.size()) {
-        hipEvent_t a = nullptr, b = nullptr;
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        bt->events.emplace_back(a, b);
+        TimedRun r;
+        HIP_TRY(hipEventCreate(&r.start));
+        bt->events.push_back(std::move(r));
     }
-    e1 = bt->events[bt->events_used].second;
-    HIP_TRY(hipEventRecord(bt->events[bt->events_used++].first, st));
+    TimedRun &r = bt->events[bt->events_used];
+    r.prev.reset();
+    if (!r.end || r.end.use_count() > 1) {
+        auto e = std::make_shared<SharedEvent>();
+        HIP_TRY(hipEventCreate(&e->ev));
+        r.end = std::move(e);
+    }
+    if (bt->own_stream && st == bt->own_stream) {
+        std::lock_guard<std::mutex> guard(g_ov_mutex);
+        r.prev = bt->index->ov_last_end;
+        bt->index->ov_last_end = r.end;
+    }
+    e1 = r.end->ev;
+    ++bt->events_used;
+    HIP_TRY(hipEventRecord(r.start, st));
     return VBM25_OK;
 }
 
@@ -751,6 +771,15 @@ static int run_one_launch(vbm25_batch *bt, hipStream_t st, DevBatch db) {
     return VBM25_OK;
 }
 
+// The window route's next run of this batch is ONE launch: scan_win_kernel merges the queries' lists itself (only when every wave has
+// at most one item: the kernel's merge sits behind its item loop).  run_window launches by it; batch_run_entry detaches by it.
+static bool window_one_launch(const vbm25_batch *bt) {
+    const QueryPlan &plan = bt->plan;
+    const uint32_t wmt = std::min(plan.range_mt, 8u);
+    return bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && !bt->growing &&
+           uint64_t(bt->nq) * plan.g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
+}
+
 // Every query sparse, <= 8 terms of comparable length: scan_win_kernel (its waves make their work items themselves), then as on the
 // plan-free route: scan_many_kernel leaves at once unless an item was given up, merge_kernel merges and cleans.
 static int run_window(vbm25_batch *bt, hipStream_t st, DevBatch db) {
@@ -793,7 +822,7 @@ static int run_window(vbm25_batch *bt, hipStream_t st, DevBatch db) {
     // the per-launch state zero.  A query with an item the kernel gave up comes back with the count NONE32: whoever hands the
     // records to the caller (vbm25_batch_fetch_impl) re-runs the batch with scan_many_kernel and merge_kernel behind the scan.
     // (only when every wave has at most one item: the kernel's merge sits behind its item loop)
-    const bool fuse = bt->tune.win_fuse && !bt->win_nofuse && !bt->device_consumer && !bt->growing && uint64_t(bt->nq) * plan.g <= scan_win_resident_waves(wmt, bt->k) && !bt->tune.win_grid;
+    const bool fuse = window_one_launch(bt);
     db.win_fuse = fuse ? 1u : 0u;
     bt->win_fused_run = fuse;
     bt->win_order_on = db.order_on;
@@ -1303,6 +1332,56 @@ int batch_run_growing_impl(vbm25_batch *bt, void *hip_stream) {
     return VBM25_OK;
 }
 
+// The batch leaves the detached form: the last run on its own stream is waited for, so that whatever follows -- a run in the caller's
+// stream order, a caller reading the records on the device, a new query set -- finds it complete
+static int batch_leave_detached(vbm25_batch *bt) {
+    if (!bt->detached) return VBM25_OK;
+    if (int rc = use_device(bt->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->own_stream));
+    bt->detached = false;
+    return VBM25_OK;
+}
+
+// vbm25_batch_run, the public entry (the ring, the multi-device parts and vbm25_search_batch bring their own streams and call the
+// implementations).  A one-launch run of scan_win_kernel of a batch without a filter is DETACHED: it goes to a non-blocking stream the
+// batch owns, behind whatever the caller's stream holds at the call, and nothing joins it back -- the next batch object's workgroups
+// take the CUs as this one's leave them, instead of waiting for its slowest wave.  fetch, the re-run after a given-up item and every
+// other wait of the batch go through last_stream, which is that stream then.  Everything else runs in the caller's stream order, after
+// the batch's last detached run.
+static int batch_run_entry(vbm25_batch *bt, void *hip_stream) {
+    if (!bt) return set_error(VBM25_ERR_INVALID, "batch is NULL");
+    hipStream_t caller = static_cast<hipStream_t>(hip_stream);
+    bool detach = bt->tune.run_overlap && bt->nq && bt->index->n_docs && bt->plan.route == Route::Window && !bt->filt_on && window_one_launch(bt);
+    if (detach) {
+        if (int rc = use_device(bt->index->device)) return rc;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;  // (a stream being captured is neither queried nor left)
+        if (hipStreamIsCapturing(caller, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            detach = false;
+        }
+    }
+    if (!detach) {
+        if (int rc = batch_leave_detached(bt)) return rc;
+        return bt->growing ? batch_run_growing_impl(bt, hip_stream) : vbm25_batch_run_impl(bt, hip_stream);
+    }
+    if (!bt->own_stream) HIP_TRY(hipStreamCreateWithFlags(&bt->own_stream, hipStreamNonBlocking));
+    // no earlier than the work enqueued on the caller's stream: nothing to wait for when that stream is idle (the usual case)
+    const hipError_t pending = hipStreamQuery(caller);
+    if (pending == hipErrorNotReady) {
+        (void)hipGetLastError();  // (not an error: the run's own hipGetLastError must not find it)
+        if (!bt->own_wait) HIP_TRY(hipEventCreateWithFlags(&bt->own_wait, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(bt->own_wait, caller));
+        HIP_TRY(hipStreamWaitEvent(bt->own_stream, bt->own_wait, 0));
+    } else
+        HIP_TRY(pending);
+    if (!bt->timing) {  // (the next timed detached run has no timed predecessor: its own start event stands)
+        std::lock_guard<std::mutex> guard(g_ov_mutex);
+        bt->index->ov_last_end.reset();
+    }
+    bt->detached = true;
+    return vbm25_batch_run_impl(bt, bt->own_stream);
+}
+
 static int vbm25_search_batch_growing_impl(vbm25_index *ix, const vbm25_device_growing *gs, const uint32_t *term_ids, const uint32_t *q_off,
                                            uint32_t nq, uint32_t k, vbm25_hit *hits, uint32_t *n_hits) {
     if (!ix || !gs || !q_off) return set_error(VBM25_ERR_INVALID, "NULL argument");
@@ -1358,12 +1437,13 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
     // (whoever reads the records on the device gets them complete after every run: the one-launch form of scan_win_kernel, which
     // leaves a query whose item it gave up to vbm25_batch_fetch, is not used for this batch object any more)
     bt->device_consumer = true;
-    return VBM25_OK;
+    // ... and in the caller's stream order: a detached run (batch_run_entry) is waited for here, later runs are not detached
+    return batch_leave_detached(bt);
 }
 
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
-// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
+// win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, run_overlap, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
 // bigk_item_win, bigk_win, bigk_win_min_docs, bigk_win_tile, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
@@ -1400,6 +1480,7 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "win_cut1") g_tune.win_cut1 = int(std::min<long long>(std::max<long long>(value, 1), 998));
     else if (n == "win_cut2") g_tune.win_cut2 = int(std::min<long long>(std::max<long long>(value, 2), 999));
     else if (n == "win_fuse") g_tune.win_fuse = value != 0;
+    else if (n == "run_overlap") g_tune.run_overlap = value != 0;
     else if (n == "bigk_sparse") g_tune.bigk_sparse = value != 0;
     else if (n == "bigk_cand_max") g_tune.bigk_cand_max = (uint64_t)std::min<long long>(std::max(0ll, value), 1ll << 30);
     else if (n == "bigk_chunk_cand") g_tune.bigk_chunk_cand = (uint64_t)std::min<long long>(std::max(1ll, value), 1ll << 30);
@@ -1633,9 +1714,20 @@ int vbm25_batch_kernel_ms(vbm25_batch *bt, double *avg_ms, uint32_t *n_launches)
     if (int rc = use_device(bt->index->device)) return rc;
     double sum = 0;
     for (size_t i = 0; i < bt->events_used; ++i) {
-        HIP_TRY(hipEventSynchronize(bt->events[i].second));
+        TimedRun &r = bt->events[i];
+        HIP_TRY(hipEventSynchronize(r.end->ev));
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, bt->events[i].first, bt->events[i].second));
+        HIP_TRY(hipEventElapsedTime(&ms, r.start, r.end->ev));
+        if (r.prev) {
+            // a detached run: its exclusive share, from the later of its own start and the end of the timed detached run enqueued
+            // before it on this index (that one overlapped this run's wait for the CUs; nothing is left when it also ended later)
+            float after_prev = 0;
+            if (hipEventSynchronize(r.prev->ev) == hipSuccess && hipEventElapsedTime(&after_prev, r.prev->ev, r.end->ev) == hipSuccess)
+                ms = std::max(0.0f, std::min(ms, after_prev));
+            else
+                (void)hipGetLastError();  // (a predecessor whose enqueue failed before its end was recorded: the own start stands)
+            r.prev.reset();
+        }
         sum += ms;
     }
     *avg_ms = bt->events_used ? sum / double(bt->events_used) : 0.0;
@@ -1670,7 +1762,7 @@ int vbm25_batch_set_queries(vbm25_batch *bt, const uint32_t *term_ids, const uin
 }
 
 int vbm25_batch_run(vbm25_batch *bt, void *hip_stream) {
-    return guarded([&] { return bt && bt->growing ? batch_run_growing_impl(bt, hip_stream) : vbm25_batch_run_impl(bt, hip_stream); });
+    return guarded([&] { return batch_run_entry(bt, hip_stream); });
 }
 
 int vbm25_batch_fetch(vbm25_batch *bt, vbm25_hit *hits, uint32_t *n_hits) {
