@@ -301,10 +301,12 @@ int vbm25_batch_set_queries(vbm25_batch *, const uint32_t *term_ids, const uint3
  * created, keeps every run on `hip_stream`.) */
 int vbm25_batch_run(vbm25_batch *, void *hip_stream);
 int vbm25_batch_fetch(vbm25_batch *, vbm25_hit *hits, uint32_t *n_hits);
-/* k > 1024: how many queries of the last run took the batched path for sparse queries (the document frequencies of the
- * query's terms sum to at most the tuning value bigk_cand_max: scan, select and sort cost what its postings cost) and how
- * many the per-query path over every document of the index.  The records are the same bytes either way.  Both 0 for a
- * batch of k <= 1024 or a NULL batch; either pointer may be NULL. */
+/* k > 1024: how many queries of the last run took a batched path -- the sparse queries' (the document frequencies of the
+ * query's terms sum to at most the tuning value bigk_cand_max: scan, select and sort cost what its postings cost) or,
+ * with the tuning value bigk_dense on an index of at least bigk_dense_min_docs documents, the dense queries' (scans of
+ * its postings find a threshold, one more lists the candidates above it) -- counted together in `sparse`, and how many
+ * the per-query path over every document of the index.  The records are the same bytes either way.  Both 0 for a batch
+ * of k <= 1024 or a NULL batch; either pointer may be NULL. */
 int vbm25_batch_bigk_queries(const vbm25_batch *, uint32_t *sparse, uint32_t *fallback);
 /* Device address of the nq x k vbm25_hit array / the nq counts (valid after run; a batch object whose device
  * addresses were asked for leaves complete records there after EVERY run -- without this call a run may leave a

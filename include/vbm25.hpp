@@ -123,8 +123,8 @@ class Index {
     vbm25_index *h_ = nullptr;
 };
 
-// k > 1024 (vbm25_batch_bigk_queries): {queries of the batch's last run on the batched path for sparse queries, queries on the
-// per-query path over every document}; {0, 0} for a batch of k <= 1024
+// k > 1024 (vbm25_batch_bigk_queries): {queries of the batch's last run on a batched path, the sparse queries' or the dense
+// queries', queries on the per-query path over every document}; {0, 0} for a batch of k <= 1024
 inline std::pair<uint32_t, uint32_t> bigk_queries(const vbm25_batch *batch) {
     std::pair<uint32_t, uint32_t> n{0, 0};
     check(vbm25_batch_bigk_queries(batch, &n.first, &n.second));

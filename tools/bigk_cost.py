@@ -5,8 +5,10 @@ device as bench.py does) and the first --queries (64,1024: one section of the fi
   --step parent   the yardstick: ANOTHER build of the library -- the parent commit's, given with --library
   --step new      this build; Batch.bigk_queries() and Batch.debug_bigk_win() (items of the window scan, items of the block scan,
                   slow-path tiles, wide postings decoded) are recorded beside the times, and the records' CRC must be the parent's.
-                  --dense on both steps: C5's shape (50 M documents, Zipf(1) vocabulary of 100 000, the first 8 ten-term queries) at
-                  k = 2000 -- dense queries keep the per-query path, the figure shows that it costs what it did.
+                  --dense on both steps: C5's shape (50 M documents, Zipf(1) vocabulary of 100 000, the first 8 and the first 64
+                  ten-term queries) at the same four k -- the dense queries of bigk_dense.h against the per-query path they had;
+                  Batch.debug_bigk_dense() (dense queries batched, levels, clip-bin boundaries, candidates listed) is recorded.
+                  --skip-c3: only that part.
   --step tile     a build with another compile-time tile span of bigk_scan_win_kernel (make variant UNIT=bigk.hip
                   EXTRA=-DVBM25_BIGK_WIN_G=n, given with --library; without: this build), recorded under --label
 Host clock around run + fetch (synchronous), one untimed and --reps (5) timed; median / min / max in ms.  A gain is stated per k only
@@ -42,7 +44,8 @@ def main():
     p.add_argument("--label", help="--step tile: the name of the build in the file, e.g. g4")
     p.add_argument("--queries", default="64,1024")
     p.add_argument("--reps", type=int, default=5)
-    p.add_argument("--dense", action="store_true", help="also C5's shape at k = 2000 (a minute of generation)")
+    p.add_argument("--dense", action="store_true", help="also C5's shape, 8 and 64 queries (a minute of generation)")
+    p.add_argument("--skip-c3", action="store_true", help="with --dense: C5's shape only")
     a = p.parse_args()
     if (a.step == "parent" and not a.library) or (a.step == "new" and a.library) or (a.step == "tile") != bool(a.label):
         raise SystemExit("--library goes with --step parent (and may with tile), --label with --step tile")
@@ -90,6 +93,7 @@ def main():
                                 queries_sparse_fallback=list(b.bigk_queries()))
                 if a.step != "parent":
                     row[who]["items_win_blk_slowtiles_wide"] = list(b.debug_bigk_win())
+                    row[who]["dense_queries_levels_clips_candidates"] = list(b.debug_bigk_dense())
                 if "parent" in row and "new" in row:
                     spread = row["parent"]["max"] - row["parent"]["min"]
                     margin = row["parent"]["median"] - row["new"]["median"]
@@ -100,9 +104,10 @@ def main():
                 save()
                 del b
 
-    measure("C3", [int(x) for x in a.queries.split(",")], KS, "c3_{}_queries")
+    if not (a.dense and a.skip_c3):
+        measure("C3", [int(x) for x in a.queries.split(",")], KS, "c3_{}_queries")
     if a.dense:
-        measure("C5", [8], (2000,), "c5_dense_{}_queries")
+        measure("C5", [8, 64], KS, "c5_dense_{}_queries")
     print(json.dumps(res))
 
 

@@ -463,8 +463,8 @@ class Batch:
         return hits, n_hits
 
     def bigk_queries(self):
-        """vbm25_batch_bigk_queries: (queries of the last run on the batched sparse path of k > 1024, queries on the per-query
-        path); (0, 0) for k <= 1024."""
+        """vbm25_batch_bigk_queries: (queries of the last run on a batched path of k > 1024 -- the sparse queries' or, with the
+        tuning value bigk_dense, the dense queries' --, queries on the per-query path); (0, 0) for k <= 1024."""
         sparse, fallback = C.c_uint32(), C.c_uint32()
         check(lib().vbm25_batch_bigk_queries(self.h, C.byref(sparse), C.byref(fallback)))
         return sparse.value, fallback.value
@@ -541,6 +541,17 @@ class Batch:
         """test / tool aid: the sparse path of the last k > 1024 run -- (work items bigk_scan_win_kernel took, work items
         bigk_scan_kernel took, the window scan's tiles on the slow path, wide term frequencies it decoded); zeros at k <= 1024"""
         f = lib().vbm25_batch_debug_bigk_win
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_uint32 * 4)()
+        check(f(self.h, out))
+        return tuple(int(x) for x in out)
+
+    def debug_bigk_dense(self):
+        """test / tool aid: the dense half of the last k > 1024 run -- (dense queries batched, the highest level of the threshold
+        search any of them needed plus one, queries whose level-0 boundary was the clip bin, candidates the emit scans listed);
+        zeros at k <= 1024"""
+        f = lib().vbm25_batch_debug_bigk_dense
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.c_void_p]
         out = (C.c_uint32 * 4)()
@@ -1277,6 +1288,10 @@ def set_tuning(name, value):
     bigk_win (k > 1024: sparse queries of 1 .. 16 terms that all have a window table take bigk_scan_win_kernel, the candidate scan
     fed from the window planes; 0 leaves them to bigk_scan_kernel), bigk_win_min_docs (the smallest index it takes, 65536 documents)
     and bigk_win_tile (whole windows a tile of it spans at most; 0: the kernel's maximum),
+    bigk_dense (k > 1024 with bigk_sparse on: the dense queries are batched too -- histogram scans find a threshold, an emit scan lists
+    the candidates above it; 0 leaves them to the per-query path), bigk_dense_min_docs (the smallest index that takes, 2^20 documents:
+    the per-query path costs what the index holds and the crossover has not been measured) and bigk_dense_seg (candidate entries of a
+    dense query's segment at most, 2^20; never below k rounded up to 4096),
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
     and cast_group_max (the class bounds of Documents.cast and Caster.submit, read at the start of each; 0 turns the class off),

@@ -23,8 +23,12 @@
 //   bigk_rank_emit_kernel  a thread a survivor: its rank is its index in its tile plus, per other tile of the query, the entries of
 //                          that tile that beat it (bisection); the record goes to its rank as bigk_emit_kernel writes it, and
 //                          n_hits[q] is the survivor count.
+// The dense half (switch bigk_dense, an index of at least bigk_dense_min_docs documents): the other queries of the batch, in chunks of
+// their own behind the sparse chunks.  Their candidate lists cannot hold every touched document, so bigk_dense_scan_kernel finds a
+// threshold first -- histogram scans and bigk_dense_walk_kernel, level after level -- and its emit instantiation lists the entries above
+// it; the select, the sort and the emit above take it from there (bigk_dense.h).  No query of it goes back to the per-query path.
 // Host: bigk_create sizes the scratch when the batch is made, bigk_plan cuts queries into chunks and items at set_queries (no device
-// planning pass), bigk_run enqueues.  Nothing is allocated in a run.
+// planning pass), bigk_run enqueues.  Nothing is allocated in a run, and nothing in it waits for the device.
 
 #include <hip/hip_runtime.h>
 
@@ -39,6 +43,7 @@
 #include "rerank_lane.h"
 #include "bigk_lane.h"
 #include "bigk_win_lane.h"
+#include "bigk_dense.h"
 
 namespace vbm25 {
 
@@ -69,22 +74,7 @@ struct Args {
     uint32_t *error_flag;
 };
 
-// first j in [lo, hi) with v[j] >= x, hi when none; v ascending.  The whole wave calls it with the same arguments: 64 samples a step.
-__device__ __forceinline__ uint32_t wave_lower_bound(const uint32_t *__restrict__ v, uint32_t lo, uint32_t hi, uint32_t x, uint32_t lane) {
-    while (lo < hi) {
-        const uint32_t n = hi - lo, step = (n + 63u) / 64u;
-        const uint32_t idx = min(lo + (lane + 1u) * step - 1u, hi - 1u);
-        const ull m = __ballot(v[idx] >= x);
-        if (!m) return hi;  // (the last lane sampled hi - 1)
-        const uint32_t f = (uint32_t)__ffsll((long long)m) - 1u;
-        if (step == 1u) return lo + f;
-        const uint32_t top = min(lo + (f + 1u) * step - 1u, hi - 1u);  // v[top] >= x, v[lo + f step - 1] < x
-        lo += f * step;
-        hi = top + 1u;
-        if (hi - lo == 1u) return lo;
-    }
-    return hi;
-}
+// (wave_lower_bound, the wave's 64-ary search over the blocks' last ids: block_fetch.h -- bigk_dense.h's scan uses it too)
 
 __global__ void __launch_bounds__(256) bigk_clear_kernel(uint32_t *v, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) v[i] = 0;
@@ -678,12 +668,24 @@ int bigk_create(vbm25_batch *bt) {
     g.surv_stride = (bt->k + bgk::TILE - 1u) / bgk::TILE * bgk::TILE;
     g.chunk_q = (uint32_t)std::min<uint64_t>(bt->max_queries, std::max<uint64_t>(1, BIGK_SURV_ENTRIES / g.surv_stride));
     g.max_items = std::max<uint64_t>(4096, 4ull * bt->max_queries);
+    // the dense half's gate.  A dense query's segment: bigk_dense_seg entries, no more than its postings can fill, never below k
+    // rounded up to tiles (the emit scan brings at least k whenever there are k), and the chunk's scratch holds at least one
+    g.dense_on = bt->tune.bigk_dense != 0 && ix->n_docs >= bt->tune.bigk_dense_min_docs;
+    if (g.dense_on) {
+        const uint64_t room = std::max<uint64_t>(chunk, g.surv_stride);
+        g.dense_seg = (uint32_t)std::min<uint64_t>(room, std::max<uint64_t>(g.surv_stride, std::min<uint64_t>(bt->tune.bigk_dense_seg, postings)));
+        g.chunk_cand = std::min<uint64_t>(room, std::max<uint64_t>(1, uint64_t(bt->max_queries) * std::max<uint64_t>(g.cand_max, g.dense_seg)));
+        g.dense_chunk_q = (uint32_t)std::min<uint64_t>(g.chunk_q, std::max<uint64_t>(1, g.chunk_cand / g.surv_stride));
+    }
     int rc = 0;
+    if (g.dense_on && ((rc = g.dstate.alloc(sizeof(bgd::State) * size_t(bt->max_queries))) ||
+                       (rc = g.dhist.alloc(4ull * bgd::BINS * g.dense_chunk_q))))
+        return rc;
     if ((rc = g.cand_key.alloc(8 * g.chunk_cand)) || (rc = g.cand_doc.alloc(4 * g.chunk_cand)) ||
         (rc = g.surv_key.alloc(8ull * g.chunk_q * g.surv_stride)) || (rc = g.surv_doc.alloc(4ull * g.chunk_q * g.surv_stride)) ||
         (rc = g.cursor.alloc(4ull * (BIGK_STAT_WORDS + bt->max_queries))) || (rc = g.surv_cnt.alloc(4ull * bt->max_queries)) ||
         (rc = g.sel.alloc(4ull * bt->max_queries)) || (rc = g.qd.alloc(sizeof(BigkQuery) * size_t(bt->max_queries))) ||
-        (rc = g.terms.alloc(4ull * std::max(bt->max_terms, 1u))) || (rc = g.items.alloc(sizeof(BigkItem) * g.max_items)))
+        (rc = g.terms.alloc(4ull * std::max(bt->max_terms, 1u))) || (rc = g.items.alloc(sizeof(BigkItem) * g.max_items * (g.dense_on ? 2u : 1u))))  // (the dense queries' items: max_items of their own)
         return rc;
     g.sparse.assign(bt->max_queries, 0);
     // the window scan's gate: the switch, the index's size, and the planes the kernel reads
@@ -702,7 +704,7 @@ int bigk_create(vbm25_batch *bt) {
 // synchronous before, stays so.
 int bigk_plan(vbm25_batch *bt) {
     BigkState &g = bt->bg;
-    g.n_sparse = 0;
+    g.n_sparse = g.n_dense = 0;
     g.chunks.clear();
     if (!g.on) return VBM25_OK;
     const vbm25_index *ix = bt->index;
@@ -714,19 +716,24 @@ int bigk_plan(vbm25_batch *bt) {
     g.h_win.clear();
     g.items_win = g.items_blk = 0;
     uint32_t n_scanned = 0, n_scanned_win = 0;  // sparse queries with a posting, by scan kernel: the others make no item
-    for (uint32_t q = 0; q < nq; ++q) {
-        if (bt->h_postings[q] > g.cand_max) continue;
-        g.sparse[q] = 1;
+    // the descriptor of query q with its indexed terms that have postings, in query order; whether every one has a window table
+    auto describe = [&](uint32_t q, bool &tables) {
         BigkQuery d{};
         d.q = q;
         d.term_lo = uint32_t(g.h_terms.size());
-        bool tables = true;
         for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p)
             if (bt->h_terms[p] < ix->n_terms && ix->term_df_host[bt->h_terms[p]]) {  // search.rs:59-61
                 g.h_terms.push_back(bt->h_terms[p]);
                 tables = tables && g.win_on && ix->term_win_host[bt->h_terms[p]] != UINT32_MAX;
             }
         d.term_hi = uint32_t(g.h_terms.size());
+        return d;
+    };
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (bt->h_postings[q] > g.cand_max) continue;
+        g.sparse[q] = 1;
+        bool tables = true;
+        BigkQuery d = describe(q, tables);
         d.cand_cap = uint32_t(bt->h_postings[q]);
         // the window scan's queries: 1 .. 16 indexed terms, every one with a window table
         const bool win = g.win_on && tables && d.term_hi > d.term_lo && d.term_hi - d.term_lo <= sbig::MAX_T;
@@ -735,7 +742,17 @@ int bigk_plan(vbm25_batch *bt) {
         g.h_qd.push_back(d);
     }
     g.n_sparse = uint32_t(g.h_qd.size());
-    if (!g.n_sparse) return VBM25_OK;
+    // the dense queries behind them: batched too (g.sparse says "not the per-query path"), their descriptors behind the sparse ones
+    for (uint32_t q = 0; g.dense_on && q < nq; ++q) {
+        if (g.sparse[q]) continue;
+        g.sparse[q] = 1;
+        bool tables = true;
+        BigkQuery d = describe(q, tables);
+        d.cand_cap = (uint32_t)std::min<uint64_t>(g.dense_seg, std::max<uint64_t>(g.surv_stride, bt->h_postings[q]));
+        g.h_qd.push_back(d);
+    }
+    g.n_dense = uint32_t(g.h_qd.size()) - g.n_sparse;
+    if (g.h_qd.empty()) return VBM25_OK;
     // the item cuts, per scan kernel over its own windows; with both kinds in the batch each gets half the item buffer
     const uint64_t cap = n_scanned && n_scanned_win ? g.max_items / 2 : g.max_items;
     const uint32_t n_win = (ix->n_docs + bgk::WINDOW - 1u) / bgk::WINDOW, n_win16 = ix->dev.n_win;
@@ -769,17 +786,52 @@ int bigk_plan(vbm25_batch *bt) {
         g.chunks.push_back(c);
     }
     if (g.h_items.size() > g.max_items) return set_error(VBM25_ERR_INVALID, "internal error: %zu work items exceed the buffer", g.h_items.size());
+    // the dense chunks: queries in order while their segments fit the scratch, their survivors the survivor buffers and their
+    // histograms the rows; then the items -- cut for ITEM_TARGET items a chunk (a chunk is a launch), all of them within max_items
+    const size_t first_dense_chunk = g.chunks.size(), sparse_items = g.h_items.size();
+    uint32_t most = 0;
+    for (uint32_t s = g.n_sparse, end = g.n_sparse + g.n_dense; s < end;) {
+        BigkChunk c{};
+        c.dense = true;
+        c.s0 = s;
+        uint64_t used = 0;
+        while (s < end && s - c.s0 < g.dense_chunk_q && used + g.h_qd[s].cand_cap <= g.chunk_cand) {
+            g.h_qd[s].cand_base = uint32_t(used);
+            used += g.h_qd[s].cand_cap;
+            ++s;
+        }
+        if (s == c.s0) return set_error(VBM25_ERR_INVALID, "internal error: a dense query exceeds the candidate scratch");
+        c.s1 = s;
+        most = std::max(most, c.s1 - c.s0);
+        g.chunks.push_back(c);
+    }
+    if (g.n_dense) {
+        const uint32_t wpd = bgk::item_windows(n_win, most, bt->tune.bigk_item_win, ITEM_TARGET, uint64_t(most) * (g.max_items / g.n_dense));
+        for (size_t ci = first_dense_chunk; ci < g.chunks.size(); ++ci) {
+            BigkChunk &c = g.chunks[ci];
+            c.item0 = c.item_mid = uint32_t(g.h_items.size());
+            for (uint32_t i = c.s0; i < c.s1; ++i)
+                for (uint32_t w = 0; w < n_win; w += wpd) g.h_items.push_back(BigkItem{i, w, std::min(w + wpd, n_win)});
+            c.item1 = uint32_t(g.h_items.size());
+        }
+        if (g.h_items.size() - sparse_items > g.max_items)
+            return set_error(VBM25_ERR_INVALID, "internal error: %zu work items of dense queries exceed the buffer", g.h_items.size() - sparse_items);
+    }
     HIP_TRY(hipMemcpy(g.qd.p, g.h_qd.data(), sizeof(BigkQuery) * g.h_qd.size(), hipMemcpyHostToDevice));
     if (!g.h_terms.empty()) HIP_TRY(hipMemcpy(g.terms.p, g.h_terms.data(), 4ull * g.h_terms.size(), hipMemcpyHostToDevice));
     if (!g.h_items.empty()) HIP_TRY(hipMemcpy(g.items.p, g.h_items.data(), sizeof(BigkItem) * g.h_items.size(), hipMemcpyHostToDevice));
     return VBM25_OK;
 }
 
-// the sparse queries of the current set, on st: one clear, then four launches a chunk
+// the batched queries of the current set, on st: one clear, then four launches a sparse chunk; a dense chunk: its histograms cleared,
+// every level's scan and walk whether a query still needs it or not (the host does not wait to know: a level nobody needs is two
+// grids that return at once), the emit scan and the same three launches
 int bigk_run(vbm25_batch *bt, hipStream_t st) {
     BigkState &g = bt->bg;
     g.ran = false;
-    if (!g.n_sparse) return VBM25_OK;
+    g.ran_dense = 0;
+    const uint32_t n_batched = g.n_sparse + g.n_dense;
+    if (!n_batched) return VBM25_OK;
     const DevIndex &dix = bt->index->dev;
     Args a{};
     a.qd = g.qd.as<BigkQuery>();
@@ -803,12 +855,33 @@ int bigk_run(vbm25_batch *bt, hipStream_t st) {
         a.filt_sel = g.sel.as<uint32_t>();
         a.filt_stride = bt->filter->words;
     }
-    bigk_clear_kernel<<<(BIGK_STAT_WORDS + g.n_sparse + 255) / 256, 256, 0, st>>>(stats, BIGK_STAT_WORDS + g.n_sparse);
+    bigk_clear_kernel<<<(BIGK_STAT_WORDS + n_batched + 255) / 256, 256, 0, st>>>(stats, BIGK_STAT_WORDS + n_batched);
+    BigkDenseArgs da{};
+    if (g.n_dense) {
+        da.qd = a.qd, da.items = a.items, da.terms = a.terms, da.cursor = a.cursor, da.cand_key = a.cand_key, da.cand_doc = a.cand_doc;
+        da.filt_words = a.filt_words, da.filt_sel = a.filt_sel, da.filt_stride = a.filt_stride;
+        da.k = a.k;
+        da.d0 = g.n_sparse;
+        da.state = g.dstate.as<bgd::State>();
+        da.hist = g.dhist.as<uint32_t>();
+        da.stats = stats + 2;
+        da.error_flag = a.error_flag;
+        bigk_dense_init_kernel<<<(g.n_dense + 255) / 256, 256, 0, st>>>(dix, da, g.n_dense);
+    }
     const uint32_t k_tiles = g.surv_stride / bgk::TILE;
     for (const BigkChunk &c : g.chunks) {
         const uint32_t cq = c.s1 - c.s0;
-        if (c.item_mid > c.item0) bigk_scan_win_kernel<<<c.item_mid - c.item0, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item0, g.win_tile, stats);
-        if (c.item1 > c.item_mid) bigk_scan_kernel<<<c.item1 - c.item_mid, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item_mid);
+        if (c.dense) {
+            const uint32_t items = c.item1 - c.item0;
+            bigk_clear_kernel<<<std::min<uint32_t>((cq * bgd::BINS + 255) / 256, 1024u), 256, 0, st>>>(da.hist, cq * bgd::BINS);
+            for (uint32_t level = 0; level < bgd::MAX_LEVELS; ++level) {
+                bigk_dense_scan_kernel<false><<<items, bgk::SCAN_THREADS, 0, st>>>(dix, da, c.item0, c.s0);
+                bigk_dense_walk_kernel<<<cq, bgd::WALK_THREADS, 0, st>>>(da, c.s0);
+            }
+            bigk_dense_scan_kernel<true><<<items, bgk::SCAN_THREADS, 0, st>>>(dix, da, c.item0, c.s0);
+        }
+        if (!c.dense && c.item_mid > c.item0) bigk_scan_win_kernel<<<c.item_mid - c.item0, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item0, g.win_tile, stats);
+        if (!c.dense && c.item1 > c.item_mid) bigk_scan_kernel<<<c.item1 - c.item_mid, bgk::SCAN_THREADS, 0, st>>>(dix, a, c.item_mid);
         bigk_select_kernel<<<cq, SELECT_THREADS, 0, st>>>(a, c.s0);
         bigk_sort_kernel<<<dim3(k_tiles, cq), SORT_THREADS, 0, st>>>(a, c.s0);
         bigk_rank_emit_kernel<<<dim3((bt->k + EMIT_THREADS - 1) / EMIT_THREADS, cq), EMIT_THREADS, 0, st>>>(dix, a, c.s0);
@@ -816,6 +889,8 @@ int bigk_run(vbm25_batch *bt, hipStream_t st) {
     HIP_TRY(hipGetLastError());
     g.ran_items_win = g.items_win;
     g.ran_items_blk = g.items_blk;
+    g.ran_d0 = g.n_sparse;
+    g.ran_dense = g.n_dense;
     g.ran = true;
     return VBM25_OK;
 }
@@ -828,6 +903,22 @@ int bigk_debug_win(vbm25_batch *bt, uint32_t *out4) {
     out4[0] = g.ran_items_win;
     out4[1] = g.ran_items_blk;
     HIP_TRY(hipMemcpy(out4 + 2, g.cursor.p, 8, hipMemcpyDeviceToHost));
+    return VBM25_OK;
+}
+
+// vbm25_batch_debug_bigk_dense: the dense queries batched in the last run, the highest level any of them needed plus one, the queries
+// whose level-0 boundary was the clip bin, and the candidates their emit scans listed (the sum of their cursors)
+int bigk_debug_dense(vbm25_batch *bt, uint32_t *out4) {
+    BigkState &g = bt->bg;
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!g.on || !g.ran || !g.ran_dense) return VBM25_OK;
+    out4[0] = g.ran_dense;
+    HIP_TRY(hipMemcpy(out4 + 1, g.cursor.as<uint32_t>() + 2, 8, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> cur(g.ran_dense);
+    HIP_TRY(hipMemcpy(cur.data(), g.cursor.as<uint32_t>() + BIGK_STAT_WORDS + g.ran_d0, 4ull * g.ran_dense, hipMemcpyDeviceToHost));
+    uint64_t sum = 0;
+    for (uint32_t c : cur) sum += c;
+    out4[3] = (uint32_t)std::min<uint64_t>(sum, UINT32_MAX);
     return VBM25_OK;
 }
 

@@ -156,6 +156,23 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {  // uniform resul
     return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 
+// first j in [lo, hi) with v[j] >= x, hi when none; v ascending.  The whole wave calls it with the same arguments: 64 samples a step.
+__device__ __forceinline__ uint32_t wave_lower_bound(const uint32_t *__restrict__ v, uint32_t lo, uint32_t hi, uint32_t x, uint32_t lane) {
+    while (lo < hi) {
+        const uint32_t n = hi - lo, step = (n + 63u) / 64u;
+        const uint32_t idx = min(lo + (lane + 1u) * step - 1u, hi - 1u);
+        const unsigned long long m = __ballot(v[idx] >= x);
+        if (!m) return hi;  // (the last lane sampled hi - 1)
+        const uint32_t f = (uint32_t)__ffsll((long long)m) - 1u;
+        if (step == 1u) return lo + f;
+        const uint32_t top = min(lo + (f + 1u) * step - 1u, hi - 1u);  // v[top] >= x, v[lo + f step - 1] < x
+        lo += f * step;
+        hi = top + 1u;
+        if (hi - lo == 1u) return lo;
+    }
+    return hi;
+}
+
 }  // namespace vbm25
 
 #endif

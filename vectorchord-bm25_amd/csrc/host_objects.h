@@ -75,6 +75,12 @@ struct Tuning {
                                    // The default follows profiles/bigk_win_cost.json
     uint32_t bigk_win_min_docs = 65536;  // ... on an index of at least this many documents
     uint32_t bigk_win_tile = 0;    // ... whole windows a tile of that kernel spans at most (1 .. its compile-time maximum; 0: the maximum)
+    int bigk_dense = 1;            // k > 1024, bigk_sparse on: the other (dense) queries are batched too -- histogram scans find a threshold, an
+                                   // emit scan lists the candidates above it (bigk_dense.h); 0: they keep the per-query path.  The default
+                                   // follows profiles/bigk_dense_cost.json
+    uint32_t bigk_dense_min_docs = 1u << 20;  // ... on an index of at least this many documents.  The per-query path costs what the index
+                                   // holds (about 0.1 ms a query at 2^20 documents); the crossover itself has not been measured
+    uint64_t bigk_dense_seg = 1ull << 20;  // ... candidate entries of a dense query's segment at most (never below k rounded up to a tile)
     int dense_big = 1;             // 256 < k <= 1024: dense queries of <= D_T terms take scan_dense_kernel<1024> (the survivor list in LDS);
                                    // 0: every query of such a batch takes scan_many_kernel.  On: profiles/dense_big_cost.json (C5, k = 1000: 270 -> 67 ms)
     uint32_t dense_big_min_docs = 65536;  // ... on an index of at least this many documents (four full windows: below, nothing is skipped
@@ -156,6 +162,7 @@ struct BigkItem {
 };
 struct BigkChunk {
     uint32_t s0, s1, item0, item_mid, item1;  // the chunk's items: [item0, item_mid) bigk_scan_win_kernel's, [item_mid, item1) bigk_scan_kernel's
+    bool dense;                               // a chunk of dense queries: every item is bigk_dense_scan_kernel's
 };
 constexpr uint64_t BIGK_SURV_ENTRIES = 1ull << 22;  // survivor entries a chunk holds at most (k rounded up to tiles per query): 48 MB
 struct BigkState {
@@ -178,6 +185,13 @@ struct BigkState {
     std::vector<uint8_t> h_win;   // per sparse query
     uint32_t items_win = 0, items_blk = 0, ran_items_win = 0, ran_items_blk = 0;
     bool ran = false;
+    // the dense half (bigk_dense.h): the gate as the batch took it, a dense query's segment at most, the queries a dense chunk holds
+    // at most (the histogram rows), and the dense queries of the current set -- their descriptors, cursors and survivor counts follow
+    // the sparse queries' ([n_sparse, n_sparse + n_dense)).  Its two device counters are the stat words 2 and 3.
+    bool dense_on = false;
+    uint32_t dense_seg = 0, dense_chunk_q = 0;
+    uint32_t n_dense = 0, ran_d0 = 0, ran_dense = 0;
+    DeviceBuffer dstate, dhist;
 };
 constexpr uint32_t BIGK_STAT_WORDS = 4;
 
@@ -382,6 +396,7 @@ int bigk_create(vbm25_batch *bt);
 int bigk_plan(vbm25_batch *bt);
 int bigk_run(vbm25_batch *bt, hipStream_t st);
 int bigk_debug_win(vbm25_batch *bt, uint32_t *out4);
+int bigk_debug_dense(vbm25_batch *bt, uint32_t *out4);
 // growing.hip: grow_delete_kernel over a deletion bitmap in HBM (tid.hip makes one from a TID set)
 int growing_delete_by_bits(vbm25_device_growing *gs, const uint32_t *bits);
 // filter.hip

@@ -560,7 +560,7 @@ static int batch_set_queries_body(vbm25_batch *bt, const uint32_t *term_ids, con
 // set's descriptors and the new one's count.  Filter and growing segment stay attached.
 void batch_clear_queries(vbm25_batch *bt) {
     bt->nq = 0;
-    bt->bg.n_sparse = 0;
+    bt->bg.n_sparse = bt->bg.n_dense = 0;
     bt->bg.chunks.clear();
     bt->plan = QueryPlan{};
     bt->qin_live = false;
@@ -695,16 +695,16 @@ static DevBatch dev_batch(const vbm25_batch *bt) {
     return db;
 }
 
-// k > 1024: the sparse queries batched (bigk.hip); every other query on its own -- one accumulation launch per term, the filter's
-// mask, a radix sort of the scores, the first k of them
+// k > 1024: the sparse queries batched, and with the switch bigk_dense the dense ones too (bigk.hip); every other query on its own --
+// one accumulation launch per term, the filter's mask, a radix sort of the scores, the first k of them
 static int run_exhaustive(vbm25_batch *bt, hipStream_t st) {
     const DevIndex &dix = bt->index->dev;
     const uint32_t n = bt->index->n_docs;
     bt->bg.ran_sparse = bt->bg.ran_fallback = 0;
     if (int rc = bigk_run(bt, st)) return rc;
-    bt->bg.ran_sparse = bt->bg.n_sparse;
+    bt->bg.ran_sparse = bt->bg.n_sparse + bt->bg.n_dense;
     for (uint32_t q = 0; q < bt->nq; ++q) {
-        if (bt->bg.n_sparse && bt->bg.sparse[q]) continue;
+        if (bt->bg.ran_sparse && bt->bg.sparse[q]) continue;
         ++bt->bg.ran_fallback;
         HIP_TRY(hipMemsetAsync(bt->bk_acc.p, 0, 8ull * n, st));
         for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p) {
@@ -1444,7 +1444,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, run_overlap, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
-// bigk_item_win, bigk_win, bigk_win_min_docs, bigk_win_tile, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
+// bigk_item_win, bigk_win, bigk_win_min_docs, bigk_win_tile, bigk_dense, bigk_dense_min_docs, bigk_dense_seg, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
@@ -1488,6 +1488,9 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "bigk_win") g_tune.bigk_win = value != 0;
     else if (n == "bigk_win_min_docs") g_tune.bigk_win_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "bigk_win_tile") g_tune.bigk_win_tile = (uint32_t)std::min<long long>(std::max(0ll, value), 4ll);
+    else if (n == "bigk_dense") g_tune.bigk_dense = value != 0;
+    else if (n == "bigk_dense_min_docs") g_tune.bigk_dense_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
+    else if (n == "bigk_dense_seg") g_tune.bigk_dense_seg = (uint64_t)std::min<long long>(std::max(1ll, value), 1ll << 30);
     else if (n == "dense_big") g_tune.dense_big = value != 0;
     else if (n == "dense_big_min_docs") g_tune.dense_big_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "sparse_big") g_tune.sparse_big = value != 0;
@@ -1626,6 +1629,18 @@ int vbm25_batch_debug_bigk_win(vbm25_batch *bt, uint32_t *out4) {
     if (int rc = use_device(bt->index->device)) return rc;
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     return bigk_debug_win(bt, out4);
+}
+
+// test / tool aid (not declared in include/vbm25.h): the dense half of the last k > 1024 run -- out[0] the dense queries it batched, out[1]
+// the highest level any of them needed, plus one, out[2] the queries whose level-0 boundary was the clip bin, out[3] the candidates the
+// emit scans listed.  Zeros at k <= 1024 and before a run.
+int vbm25_batch_debug_bigk_dense(vbm25_batch *bt, uint32_t *out4) {
+    if (!bt || !out4) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!bt->bigk) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    return bigk_debug_dense(bt, out4);
 }
 
 // test aid (not declared in include/vbm25.h): launches of the last run's scan -- 1: scan_win_kernel merged the queries' lists itself
