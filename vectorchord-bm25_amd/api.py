@@ -547,6 +547,17 @@ class Batch:
         check(f(self.h, out))
         return tuple(int(x) for x in out)
 
+    def debug_bigk_grow(self):
+        """test / tool aid: the growing segment's part of the last k > 1024 run on the batched route (tuning value bigk_grow) --
+        (work items of growing_bigk_scan_kernel, candidates it appended, candidates the sealed k-th score pruned, chunks); zeros at
+        k <= 1024, with no segment attached and under bigk_grow=0"""
+        f = lib().vbm25_batch_debug_bigk_grow
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_uint32 * 4)()
+        check(f(self.h, out))
+        return tuple(int(x) for x in out)
+
     def debug_bigk_dense(self):
         """test / tool aid: the dense half of the last k > 1024 run -- (dense queries batched, the highest level of the threshold
         search any of them needed plus one, queries whose level-0 boundary was the clip bin, candidates the emit scans listed);
@@ -1292,6 +1303,8 @@ def set_tuning(name, value):
     the candidates above it; 0 leaves them to the per-query path), bigk_dense_min_docs (the smallest index that takes, 2^20 documents:
     the per-query path costs what the index holds and the crossover has not been measured) and bigk_dense_seg (candidate entries of a
     dense query's segment at most, 2^20; never below k rounded up to 4096),
+    bigk_grow (k > 1024 with a growing segment attached: its part of a run is batched -- one candidate scan of the growing postings,
+    the select and tile sort of the sealed route, one merge; 0 keeps the per-query branch, a radix sort of the segment per query),
     id16_max_blocks (an index without post_id16: the most 256-byte blocks of a batch's terms that scan_win_kernel's scratch plane
     takes; a larger batch takes scan_range_kernel), win_planes, rel16_plane and id16_plane (read at index creation), cast_wave_max
     and cast_group_max (the class bounds of Documents.cast and Caster.submit, read at the start of each; 0 turns the class off),

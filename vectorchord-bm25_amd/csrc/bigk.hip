@@ -27,6 +27,8 @@
 // their own behind the sparse chunks.  Their candidate lists cannot hold every touched document, so bigk_dense_scan_kernel finds a
 // threshold first -- histogram scans and bigk_dense_walk_kernel, level after level -- and its emit instantiation lists the entries above
 // it; the select, the sort and the emit above take it from there (bigk_dense.h).  No query of it goes back to the per-query path.
+// The growing segment of such a batch (switch bigk_grow): growing_bigk.h's scan and merge around the select and the sort here, on
+// candidate segments of their own -- growing_bigk_scratch / growing_bigk_run at the end of this file.
 // Host: bigk_create sizes the scratch when the batch is made, bigk_plan cuts queries into chunks and items at set_queries (no device
 // planning pass), bigk_run enqueues.  Nothing is allocated in a run, and nothing in it waits for the device.
 
@@ -44,6 +46,7 @@
 #include "bigk_lane.h"
 #include "bigk_win_lane.h"
 #include "bigk_dense.h"
+#include "growing_bigk.h"
 
 namespace vbm25 {
 
@@ -919,6 +922,137 @@ int bigk_debug_dense(vbm25_batch *bt, uint32_t *out4) {
     uint64_t sum = 0;
     for (uint32_t c : cur) sum += c;
     out4[3] = (uint32_t)std::min<uint64_t>(sum, UINT32_MAX);
+    return VBM25_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The growing segment's part of a k > 1024 run, batched (growing_bigk.h; switch bigk_grow).  It serves every query of the batch,
+// whichever sealed path the query took, and does not depend on bigk_sparse: the scratch below is its own.
+// ---------------------------------------------------------------------------
+// The scratch for a segment of n_grow documents: candidate entries for a chunk (bigk_chunk_cand, no more than max_queries queries of
+// n_grow candidates can ask for, never less than one query's n_grow), survivor rows within BIGK_SURV_ENTRIES, cursors, descriptors.
+// No run of the batch may be in flight.
+int growing_bigk_scratch(vbm25_batch *bt, uint32_t n_grow) {
+    GrowBigkState &g = bt->gb;
+    const uint64_t n = std::max<uint64_t>(std::max(n_grow, bt->gr_n), 1), mq = std::max(bt->max_queries, 1u);
+    g.surv_stride = (bt->k + bgk::TILE - 1u) / bgk::TILE * bgk::TILE;
+    g.chunk_q = (uint32_t)std::min<uint64_t>(mq, std::max<uint64_t>(1, BIGK_SURV_ENTRIES / g.surv_stride));
+    g.chunk_cand = std::max<uint64_t>(n, std::min<uint64_t>(std::max<uint64_t>(1, bt->tune.bigk_chunk_cand), mq * n));
+    int rc = 0;
+    if ((rc = batch_grow_buffer(g.cand_key, 8 * g.chunk_cand)) || (rc = batch_grow_buffer(g.cand_doc, 4 * g.chunk_cand)) ||
+        (rc = batch_grow_buffer(g.surv_key, 8ull * g.chunk_q * g.surv_stride)) || (rc = batch_grow_buffer(g.surv_doc, 4ull * g.chunk_q * g.surv_stride)) ||
+        (rc = batch_grow_buffer(g.cursor, 4ull * (BIGK_STAT_WORDS + mq))) || (rc = batch_grow_buffer(g.surv_cnt, 4ull * mq)) ||
+        (rc = batch_grow_buffer(g.sel, 4ull * mq)) || (rc = batch_grow_buffer(g.qd, sizeof(BigkQuery) * size_t(mq))) ||
+        (rc = batch_grow_buffer(g.terms, 4ull * std::max(bt->max_terms, 1u))))
+        return rc;
+    g.h_qd.reserve(mq);
+    g.h_terms.reserve(bt->max_terms);
+    g.h_cap.reserve(mq);
+    g.h_base.reserve(mq);
+    g.h_chunk.reserve(mq + 1);
+    bt->gr_n = uint32_t(n);
+    return VBM25_OK;
+}
+
+// on st behind the sealed scan and the copy of its records: the descriptors, one clear, four launches a chunk
+int growing_bigk_run(vbm25_batch *bt, const vbm25_hit *sealed, const uint32_t *sealed_cnt, hipStream_t st) {
+    GrowBigkState &g = bt->gb;
+    const vbm25_device_growing *gs = bt->growing;
+    const uint32_t nq = bt->nq, n_terms = bt->index->n_terms;
+    g.ran = false;
+    if (!nq) return VBM25_OK;
+    // a query's terms and capacity from the segment's postings of the moment (it may have been appended to since set_queries; the
+    // batch's queries are on the host only), then the chunks
+    g.h_qd.resize(nq);
+    g.h_cap.resize(nq);
+    g.h_base.resize(nq);
+    g.h_chunk.clear();
+    g.h_terms.clear();
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint64_t postings = 0;
+        g.h_qd[q].term_lo = uint32_t(g.h_terms.size());
+        for (uint32_t p = bt->h_off[q]; p < bt->h_off[q + 1]; ++p) {
+            const uint32_t t = bt->h_terms[p];
+            const uint32_t df = t < n_terms ? gs->term_start_host[t + 1] - gs->term_start_host[t] : 0u;
+            if (df) g.h_terms.push_back(t);
+            postings += df;
+        }
+        g.h_qd[q].term_hi = uint32_t(g.h_terms.size());
+        g.h_cap[q] = gbk::query_cap(gs->n_grow, postings);
+    }
+    for (uint32_t q = 0; q < nq;) {
+        const uint32_t q1 = gbk::chunk_end(g.h_cap.data(), nq, q, g.chunk_q, g.chunk_cand, g.h_base.data());
+        if (q1 == q) return set_error(VBM25_ERR_INVALID, "internal error: a query's growing candidates exceed the scratch");
+        g.h_chunk.push_back(q);
+        q = q1;
+    }
+    g.h_chunk.push_back(nq);
+    for (uint32_t q = 0; q < nq; ++q) g.h_qd[q] = BigkQuery{q, g.h_qd[q].term_lo, g.h_qd[q].term_hi, g.h_base[q], g.h_cap[q]};
+    HIP_TRY(hipMemcpyAsync(g.qd.p, g.h_qd.data(), sizeof(BigkQuery) * size_t(nq), hipMemcpyHostToDevice, st));
+    if (!g.h_terms.empty()) HIP_TRY(hipMemcpyAsync(g.terms.p, g.h_terms.data(), 4ull * g.h_terms.size(), hipMemcpyHostToDevice, st));
+    const DevGrowing G = gs->dev();
+    uint32_t *stats = g.cursor.as<uint32_t>();  // (the two counters, then the cursors: one clear covers both)
+    GrowBigkArgs ga{};
+    ga.qd = g.qd.as<BigkQuery>();
+    ga.terms = g.terms.as<uint32_t>();
+    ga.cursor = stats + BIGK_STAT_WORDS;
+    ga.stats = stats;
+    ga.cand_key = g.cand_key.as<uint64_t>();
+    ga.cand_doc = g.cand_doc.as<uint32_t>();
+    if (bt->filt_on) {  // (batch_run_growing_impl checked that the growing bitmaps are this segment's)
+        HIP_TRY(hipMemcpyAsync(g.sel.p, bt->h_filt_sel.data(), 4ull * nq, hipMemcpyHostToDevice, st));
+        ga.filt_words = bt->filter->grow_bits.as<uint32_t>();
+        ga.filt_sel = g.sel.as<uint32_t>();
+        ga.filt_stride = 2u * bt->filter->grow_stride;
+    }
+    ga.sealed = sealed;
+    ga.sealed_cnt = sealed_cnt;
+    ga.surv_cnt = g.surv_cnt.as<uint32_t>();
+    ga.surv_key = g.surv_key.as<uint64_t>();
+    ga.surv_doc = g.surv_doc.as<uint32_t>();
+    ga.k = bt->k;
+    ga.surv_stride = g.surv_stride;
+    ga.hits = bt->hits.as<vbm25_hit>();
+    ga.n_hits = bt->n_hits.as<uint32_t>();
+    ga.error_flag = bt->error_flag.as<uint32_t>();
+    Args a{};  // the select's and the sort's view of the same scratch
+    a.qd = ga.qd;
+    a.cursor = ga.cursor;
+    a.surv_cnt = g.surv_cnt.as<uint32_t>();
+    a.cand_key = ga.cand_key;
+    a.cand_doc = ga.cand_doc;
+    a.surv_key = g.surv_key.as<uint64_t>();
+    a.surv_doc = g.surv_doc.as<uint32_t>();
+    a.k = bt->k;
+    a.surv_stride = g.surv_stride;
+    a.error_flag = ga.error_flag;
+    bigk_clear_kernel<<<(BIGK_STAT_WORDS + nq + 255) / 256, 256, 0, st>>>(stats, BIGK_STAT_WORDS + nq);
+    const uint32_t k_tiles = g.surv_stride / bgk::TILE;
+    uint32_t items = 0;
+    for (size_t c = 0; c + 1 < g.h_chunk.size(); ++c) {
+        const uint32_t q0 = g.h_chunk[c], cq = g.h_chunk[c + 1] - q0;
+        const uint32_t ipq = gbk::items_per_query(G.n_tiles, cq, gbk::ITEM_TARGET);
+        growing_bigk_scan_kernel<<<cq * ipq, GWG, 0, st>>>(G, ga, q0, ipq);
+        bigk_select_kernel<<<cq, SELECT_THREADS, 0, st>>>(a, q0);
+        bigk_sort_kernel<<<dim3(k_tiles, cq), SORT_THREADS, 0, st>>>(a, q0);
+        growing_bigk_merge_kernel<<<dim3((bt->k + 255) / 256, cq), 256, 0, st>>>(G, ga, q0);
+        items += cq * ipq;
+    }
+    HIP_TRY(hipGetLastError());
+    g.ran_items = items;
+    g.ran_chunks = uint32_t(g.h_chunk.size()) - 1u;
+    g.ran = true;
+    return VBM25_OK;
+}
+
+// vbm25_batch_debug_bigk_grow: the last run's work items of the growing scan, its two device counters and the chunks
+int growing_bigk_debug(vbm25_batch *bt, uint32_t *out4) {
+    GrowBigkState &g = bt->gb;
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!g.ran) return VBM25_OK;
+    out4[0] = g.ran_items;
+    HIP_TRY(hipMemcpy(out4 + 1, g.cursor.p, 8, hipMemcpyDeviceToHost));
+    out4[3] = g.ran_chunks;
     return VBM25_OK;
 }
 

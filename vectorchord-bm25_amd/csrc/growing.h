@@ -22,25 +22,9 @@
 
 #include "device_types.h"
 #include "topk_reg.h"
+#include "growing_tile.h"
 
 namespace vbm25 {
-
-// postings of term t with g in tile j
-__device__ __forceinline__ uint2 grow_tile_range(const DevGrowing &G, uint32_t t, uint32_t j) {
-    const uint32_t ti = G.tab_idx[t];
-    if (ti != NONE32) return make_uint2(G.tab[ti + j], G.tab[ti + j + 1]);
-    const uint32_t a = G.term_start[t], b = G.term_start[t + 1];
-    auto lower = [&](uint32_t lo, uint32_t hi, uint64_t g) {
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (uint64_t(G.post_g[mid]) < g) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-    };
-    const uint32_t lo = j == 0 ? a : lower(a, b, uint64_t(j) * GT);
-    const uint32_t hi = j + 1 >= G.n_tiles ? b : lower(lo, b, uint64_t(j + 1) * GT);
-    return make_uint2(lo, hi);
-}
 
 // the records of one query: the sealed list S (ns) and the growing list (gs, gg; ng, best first) merged as vbm25_merge_hits merges
 // them -- a growing hit goes before a sealed one only with a higher score.  Every entry is placed by its rank (binary search in the

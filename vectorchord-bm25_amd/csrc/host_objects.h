@@ -81,6 +81,10 @@ struct Tuning {
     uint32_t bigk_dense_min_docs = 1u << 20;  // ... on an index of at least this many documents.  The per-query path costs what the index
                                    // holds (about 0.1 ms a query at 2^20 documents); the crossover itself has not been measured
     uint64_t bigk_dense_seg = 1ull << 20;  // ... candidate entries of a dense query's segment at most (never below k rounded up to a tile)
+    int bigk_grow = 1;             // k > 1024 with a growing segment attached: its part of a run is batched -- one candidate scan of the growing
+                                   // postings, the select and tile sort of bigk.hip, one merge (growing_bigk.h); 0: the per-query branch (an
+                                   // accumulator per growing document, a launch per term, a radix sort of the segment per query).  The
+                                   // default follows profiles/growing_bigk_cost.json
     int dense_big = 1;             // 256 < k <= 1024: dense queries of <= D_T terms take scan_dense_kernel<1024> (the survivor list in LDS);
                                    // 0: every query of such a batch takes scan_many_kernel.  On: profiles/dense_big_cost.json (C5, k = 1000: 270 -> 67 ms)
     uint32_t dense_big_min_docs = 65536;  // ... on an index of at least this many documents (four full windows: below, nothing is skipped
@@ -194,6 +198,20 @@ struct BigkState {
     DeviceBuffer dstate, dhist;
 };
 constexpr uint32_t BIGK_STAT_WORDS = 4;
+
+// The growing segment's k > 1024 route (growing_bigk.h, switch bigk_grow): the scratch -- sized when the segment is attached and
+// again by the first run after an append has outgrown it (vbm25_batch::gr_n) --, the descriptors a run computes on the host (a
+// query's capacity follows the segment's postings of the moment) and the last run's tally.  Descriptor q is query q.
+struct GrowBigkState {
+    uint64_t chunk_cand = 0;              // candidate entries of the scratch: a chunk's segments fit it
+    uint32_t chunk_q = 0, surv_stride = 0;  // queries a chunk holds at most (the survivor rows), k rounded up to tiles
+    DeviceBuffer cand_key, cand_doc, surv_key, surv_doc, cursor, surv_cnt, sel, qd, terms;
+    std::vector<BigkQuery> h_qd;
+    std::vector<uint32_t> h_terms;                 // the queries' indexed terms with a growing posting, in query order
+    std::vector<uint32_t> h_cap, h_base, h_chunk;  // per query: capacity and segment start; the chunks' first queries and the end
+    uint32_t ran_items = 0, ran_chunks = 0;
+    bool ran = false;
+};
 
 // An event more than one object refers to: the end of a timed detached run (vbm25_batch_run on the batch's own stream) belongs to its
 // batch and is the start of the next such run's exclusive share (vbm25_batch_kernel_ms), whichever of the two objects goes first
@@ -311,6 +329,7 @@ struct vbm25_batch {
     vbm25::DeviceBuffer gr_sealed, gr_sealed_cnt, gr_ls, gr_lg, gr_lc, gr_acc, gr_keys, gr_iota, gr_docs, gr_tmp;
     size_t gr_tmp_bytes = 0;
     uint32_t gr_n = 0;  // growing documents the k > 1024 scratch holds
+    vbm25::GrowBigkState gb;  // k > 1024, switch bigk_grow: the batched route's scratch (then gr_acc .. gr_tmp are not allocated)
     std::vector<uint8_t> h_dense;          // per query: dense (scratch of set_queries, sized once)
     std::vector<uint8_t> h_sparse_big;     // per query: takes scan_sparse_big_kernel (sized once, when the batch's route exists)
     std::vector<unsigned long long> h_postings;
@@ -397,6 +416,10 @@ int bigk_plan(vbm25_batch *bt);
 int bigk_run(vbm25_batch *bt, hipStream_t st);
 int bigk_debug_win(vbm25_batch *bt, uint32_t *out4);
 int bigk_debug_dense(vbm25_batch *bt, uint32_t *out4);
+// ... and the growing segment's part of such a batch's run (switch bigk_grow): scratch for n_grow documents, the launches, the tally
+int growing_bigk_scratch(vbm25_batch *bt, uint32_t n_grow);
+int growing_bigk_run(vbm25_batch *bt, const vbm25_hit *sealed, const uint32_t *sealed_cnt, hipStream_t st);
+int growing_bigk_debug(vbm25_batch *bt, uint32_t *out4);
 // growing.hip: grow_delete_kernel over a deletion bitmap in HBM (tid.hip makes one from a TID set)
 int growing_delete_by_bits(vbm25_device_growing *gs, const uint32_t *bits);
 // filter.hip

@@ -1162,9 +1162,11 @@ int batch_grow_buffer(DeviceBuffer &b, size_t bytes) {
     return b.alloc(bytes);
 }
 
-// k > 1024: the accumulator, the sort's arrays and the iota for n_grow documents.  Sized when the segment is attached and again by
-// the first run after an append has outgrown them (bt->gr_n).
+// k > 1024: the batched route's scratch (switch bigk_grow: growing_bigk_scratch, bigk.hip), or the per-query branch's accumulator,
+// sort arrays and iota for n_grow documents.  Sized when the segment is attached and again by the first run after an append has
+// outgrown them (bt->gr_n).
 static int batch_growing_bigk_scratch(vbm25_batch *bt, uint32_t n_grow) {
+    if (bt->tune.bigk_grow) return growing_bigk_scratch(bt, n_grow);
     const size_t n = std::max<size_t>(n_grow, 1);
     size_t tb = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
@@ -1236,7 +1238,8 @@ static int growing_enqueue(vbm25_batch *bt, hipStream_t st) {
         sealed = bt->gr_sealed.as<vbm25_hit>();
         sealed_cnt = bt->gr_sealed_cnt.as<uint32_t>();
     }
-    if (bt->bigk) {
+    if (bt->bigk && bt->tune.bigk_grow) return growing_bigk_run(bt, sealed, sealed_cnt, st);  // batched: growing_bigk.h
+    if (bt->bigk) {  // (switch bigk_grow = 0: one query at a time, the comparison)
         const uint32_t n = std::max(gs->n_grow, 1u);
         for (uint32_t q = 0; q < nq; ++q) {
             HIP_TRY(hipMemsetAsync(bt->gr_acc.p, 0, 8ull * n, st));
@@ -1444,7 +1447,7 @@ int vbm25_batch_device_results(vbm25_batch *bt, void **hits, void **n_hits) {
 // tuning / test aid (not declared in include/vbm25.h): process-wide switches, read when a batch object is created.
 // Names: dense_x1000, dense, ne, fused, ne_ratio, dense_items, range_items, range_min_chunk, range_grid, dense_grid, fused_items, arith,
 // win, win_force, win_items, win_planes, win_guided, win_grid, win_skew, run_overlap, id16_max_blocks, bigk_sparse, bigk_cand_max, bigk_chunk_cand,
-// bigk_item_win, bigk_win, bigk_win_min_docs, bigk_win_tile, bigk_dense, bigk_dense_min_docs, bigk_dense_seg, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
+// bigk_item_win, bigk_grow, bigk_win, bigk_win_min_docs, bigk_win_tile, bigk_dense, bigk_dense_min_docs, bigk_dense_seg, dense_big, dense_big_min_docs, sparse_big, sparse_big_min_docs, dbg; cast_wave_max and cast_group_max (read
 // at the start of each vbm25_documents_cast and vbm25_caster_submit); cast_pack and cast_grid (read at each vbm25_caster_submit); eval_grid (read at the start of each vbm25_documents_bind / vbm25_evaluate_documents
 // and each scorer call); fwd_grid, fwd_wave_max and fwd_group_max (read at the start of each vbm25_index_bind); rerank_part and rerank_buf (read at the start of each scorer call); tid_grid (read at each launch of
 // tid_match_kernel) and tid_dir (read at each vbm25_tid_set_create); live_sort_max (read at each vbm25_reranker_sync).
@@ -1488,6 +1491,7 @@ int vbm25_tuning_set(const char *name, long long value) {
     else if (n == "bigk_win") g_tune.bigk_win = value != 0;
     else if (n == "bigk_win_min_docs") g_tune.bigk_win_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "bigk_win_tile") g_tune.bigk_win_tile = (uint32_t)std::min<long long>(std::max(0ll, value), 4ll);
+    else if (n == "bigk_grow") g_tune.bigk_grow = value != 0;
     else if (n == "bigk_dense") g_tune.bigk_dense = value != 0;
     else if (n == "bigk_dense_min_docs") g_tune.bigk_dense_min_docs = (uint32_t)std::min<long long>(std::max(0ll, value), 0xffffffffll);
     else if (n == "bigk_dense_seg") g_tune.bigk_dense_seg = (uint64_t)std::min<long long>(std::max(1ll, value), 1ll << 30);
@@ -1629,6 +1633,18 @@ int vbm25_batch_debug_bigk_win(vbm25_batch *bt, uint32_t *out4) {
     if (int rc = use_device(bt->index->device)) return rc;
     HIP_TRY(hipStreamSynchronize(bt->last_stream));
     return bigk_debug_win(bt, out4);
+}
+
+// test / tool aid (not declared in include/vbm25.h): the growing segment's part of the last k > 1024 run on the batched route (switch
+// bigk_grow) -- out[0] the work items of growing_bigk_scan_kernel, out[1] the candidates it appended, out[2] the candidates the sealed
+// k-th score pruned, out[3] the chunks.  Zeros at k <= 1024, with no segment attached and under bigk_grow = 0.
+int vbm25_batch_debug_bigk_grow(vbm25_batch *bt, uint32_t *out4) {
+    if (!bt || !out4) return set_error(VBM25_ERR_INVALID, "NULL argument");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!bt->bigk || !bt->growing || !bt->tune.bigk_grow) return VBM25_OK;
+    if (int rc = use_device(bt->index->device)) return rc;
+    HIP_TRY(hipStreamSynchronize(bt->last_stream));
+    return growing_bigk_debug(bt, out4);
 }
 
 // test / tool aid (not declared in include/vbm25.h): the dense half of the last k > 1024 run -- out[0] the dense queries it batched, out[1]
